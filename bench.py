@@ -12,12 +12,17 @@ launches; results are identical to one call per iteration), with 3 batches in fl
 (Rounds 1-3 stepped in batches of 32; a launch carries a fixed ~15 us of ramp-up and tail, which 64 iterations
 amortise over twice the paths: `--batch 32` reproduces the old step.)
 
-The timed block -- EXACTLY `--steps` steps between barrier + device synchronisation on both sides -- is repeated
-`--repeats` (15) times inside one run (a single block is ~40 ms; fifteen are ~0.6 s of GPU time): `ms_per_step` and
-`value` are the MEDIAN block's (ms_per_step x steps = that block's wall), `ms_per_step_min` / `_max` and `value_min` /
-`_max` give the spread over the blocks, `ms_per_step_blocks` lists them all.
+The timed block -- EXACTLY `--steps` steps between barrier + device synchronisation on both sides -- runs once by default,
+so `--steps K` is the number of timed steps of the headline pass and `ms_per_step` is what one of them took.  `--repeats R`
+repeats the block R times inside one run: `ms_per_step` and `value` are then the MEDIAN block's (ms_per_step x steps = that
+block's wall), `ms_per_step_min` / `_max` and `value_min` / `_max` give the spread over the blocks, `ms_per_step_blocks`
+lists them all.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+`--dump-outputs DIR` writes, after the headline pass's timed blocks, what that pass computed by its last step -- the frame a
+caller of the hot path reads back -- as DIR/<name>.npy (float32): two builds run with the same arguments render the same
+iterations of the same scene and can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
         N > 1 without a torchrun environment: bench.py starts its N ranks itself (a child `python -m
         torch.distributed.run`, before this process has touched the GPU) and relays rank 0's JSON line
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (what the driver does)
@@ -76,8 +81,9 @@ def parse(argv=None):
                     help="steps per timed block (one step = --batch iterations of the whole frame, times N with --scaling weak); default 32 "
                          "on one GPU (1024 spp = 16 x the 64 spp of BASELINE config C2), 20 on N GPUs")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 4)")
-    ap.add_argument("--repeats", type=int, default=15,
-                    help="how many times the timed block of --steps steps is repeated inside the run (median reported, min / max beside it)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="how many times the timed block of --steps steps is run (default 1: --steps is the number of timed steps; R > 1: the median "
+                         "block reported, min / max beside it)")
     ap.add_argument("--scene", default=os.path.join(ROOT, "scenes", "cornell.txt"))
     ap.add_argument("--res", type=int, nargs=2, default=[1280, 720])
     ap.add_argument("--depth", type=int, default=8)
@@ -107,6 +113,9 @@ def parse(argv=None):
     ap.add_argument("--valu-rate-json", default=os.path.join(ROOT, "profiles", "valu_issue_rate.json"),
                     help="measured cycles per wave64 vector instruction per SIMD (profiles/valu_issue_rate.hip)")
     ap.add_argument("--dump-frame", default=None, help="rank 0 writes the final frame (float32 W*H*3 running sum) to this .npy file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the headline pass computed by its last timed step to DIR/<name>.npy (float32, at most 64 MB in all): "
+                         "frame.npy = the accumulated radiance (H x W x 3 running sum), or a fixed seeded sample of its pixels when larger")
     ap.add_argument("--configs", type=int, default=None,
                     help="1: after the headline line's own measurement, measure the other BASELINE configurations that fit one GPU -- C4 (glass, 1920x1080, "
                          "depth 16), C5 on one GPU (64 spheres, 4096x4096, 16 spp per step) and the mesh scene -- a few timed blocks each, every one "
@@ -130,6 +139,25 @@ def parse(argv=None):
                     help="--group: 1 = config C3 as written instead of the batch mode: one pt_group_iterate (one iteration out of batches traced ahead on every "
                          "member + the frame's reduce) per ITERATION")
     return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all arrays together
+
+
+def dump_outputs(dirname, frame, W, H):
+    """--dump-outputs: the frame (float32 running radiance sum, W*H*3) as DIR/frame.npy, shape (H, W, 3); when that exceeds
+    DUMP_MAX_BYTES, the same fixed sample of pixels on every run (seed 0) as frame_sample.npy (n x 3) with their indices
+    y * W + x as frame_sample_pixels.npy (float64, exact)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(H * W, 3)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(dirname, "frame.npy"), frame.reshape(H, W, 3))
+        return
+    n = DUMP_MAX_BYTES // (3 * 4 + 8)
+    pix = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+    np.save(os.path.join(dirname, "frame_sample.npy"), frame[pix])
+    np.save(os.path.join(dirname, "frame_sample_pixels.npy"), pix.astype(np.float64))
 
 
 def self_launch(args):
@@ -474,6 +502,8 @@ def run_group(args):
         out["workload"] = "%s %dx%d, %d bounces" % (os.path.relpath(args.scene, ROOT), W, H, D)
         if args.dump_frame:
             np.save(args.dump_frame, frame)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame, W, H)
     finally:
         g.destroy()
     print(json.dumps(out), flush=True)
@@ -768,6 +798,8 @@ def run(args, ctx):
     cntA = A["counters"]
     if args.dump_frame and rank == 0:
         np.save(args.dump_frame, (frame if world > 1 else accum).cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (frame if world > 1 else accum).cpu().numpy(), W, H)
 
     def reading(scaling, ev, collective, steps, warmup, c3=False, pipeline=None):
         m = measure(scaling, ev, collective, steps, 1, warmup, c3=c3, pipeline=pipeline)

@@ -176,3 +176,26 @@ def test_group_mode_renders_the_one_device_frame(pt, tmp_path):
     assert d["members"] == 1 and d["collective"].startswith("rccl reduce") and d["iterations_committed"] == (1 + 2 * 2) * 64
     assert 0 < d["ms_per_iteration"] < 0.2 and d["host_enqueue_us_per_iteration"] > 0
     assert np.array_equal(np.load(dump).view(np.uint32), _batched_frame(pt, 5 * 64).view(np.uint32))
+
+
+def test_steps_and_dump_outputs(pt, tmp_path):
+    # `--steps K` with no `--repeats`: exactly K timed steps, `ms_per_step` their wall / K.  `--dump-outputs DIR` leaves what the
+    # headline pass computed by its last step -- the frame of warm-up + timed iterations -- as DIR/frame.npy, equal on a second run.
+    import numpy as np
+    if pt.device_count() < 1:
+        pytest.fail("no HIP device: GPU tests must run on the MI355X box")
+    frames = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-spp", "0",
+                            "--per-iteration-sample", "0", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["repeats"] == 1 and len(d["ms_per_step_blocks"]) == 1
+        assert d["ms_per_step"] == d["ms_per_step_blocks"][0] > 0
+        assert sorted(os.listdir(out)) == ["frame.npy"]
+        f = np.load(out / "frame.npy")
+        assert f.dtype == np.float32 and f.shape == (720, 1280, 3)
+        frames.append(f)
+    assert np.array_equal(frames[0].view(np.uint32), frames[1].view(np.uint32))
+    assert np.array_equal(frames[0].reshape(-1).view(np.uint32), _batched_frame(pt, (1 + 3) * 64).view(np.uint32))
