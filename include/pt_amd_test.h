@@ -84,6 +84,12 @@ int pt_test_camera_cull_margin(const PtCamera *cam, const PtGeom *geoms, int nge
 /* The same tables for inspection (host only, no GPU needed): rects4[4 i ..] = primitive i's pixel rectangle, scene_rect4 = their
  * union, spans2[2 (y ngeoms + i) ..] = the pixels x0 .. x1 of row y from which primitive i is reachable (x0 > x1: none). */
 int pt_test_camera_cull_tables(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int32_t *rects4, int32_t *scene_rect4, int32_t *spans2);
+/* The camera rays' packed work list pt_init builds from those tables for shard (shard_rank, shard_count), here without its length cap
+ * (host only, no GPU needed).  sizes4 = {lanes of the list (-1: not built), entries of sig_idx, pixels listed, pixels of the shard}.
+ * pix[lane] = x | y << 16 or 0xffffffff (padding), wave2[2 w ..] = {first, end} of wave w's primitives in sig_idx.  Call with pix,
+ * wave2 or sig_idx NULL for the sizes alone: pix takes sizes4[0] words, wave2 sizes4[0] / 32, sig_idx sizes4[1]. */
+int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
+                        int32_t *sig_idx, int64_t *sizes4);
 /* Triangle meshes.  pt_test_mesh_intersect: `n` rays against ONE mesh geom on the GPU, through the hierarchy (flat = 0) or a
  * plain list of its triangles (flat = 1: the brute-force rule); outputs keep their input values on a miss; culled[i] = 1 when
  * the bounding-ball test (certainMiss) rejected the ray -- t[i] is NaN if the full test hits nevertheless (must not happen).

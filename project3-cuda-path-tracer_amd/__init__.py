@@ -65,7 +65,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_utilhash", "pt_test_rng", "pt_test_intersect", "pt_test_hemisphere", "pt_test_sincos", "pt_test_reflect_refract",
     "pt_test_slab_quotients", "pt_test_slab_quotients_sweep", "pt_test_box_fast_sweep", "pt_test_sphere_cull_sweep", "pt_test_unscaled_sqrt_sweep",
     "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_bvh",
-    "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables",
+    "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep",
 ]
@@ -164,6 +164,7 @@ def _bind(L, with_tests):
         L.pt_test_mesh_cull_sweep.argtypes = [vp, vp, i32, C.c_uint64, i64] + [u64p] * 3
         L.pt_test_camera_cull_sweep.argtypes = [vp, vp, i32, i32] + [u64p] * 3
         L.pt_test_camera_cull_tables.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.pt_test_camera_list.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.pt_test_camera_cull_margin.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_double), u64p]
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
@@ -759,6 +760,22 @@ def camera_cull_tables(camera, geoms):
     spans = np.zeros((H, len(geoms), 2), np.int32)
     _tcheck(test_lib().pt_test_camera_cull_tables(_p(cam), _p(geoms), len(geoms), _p(rects), _p(scene), _p(spans)))
     return rects, scene, spans
+
+
+def camera_list(camera, geoms, shard_rank=0, shard_count=1):
+    """The camera rays' packed work list pt_init builds for one shard (host only, no length cap).  Returns None where it is not built,
+    else (pix (n,) uint32: x | y << 16 or 0xffffffff, wave ranges (n / 64, 2), signature entries, pixels listed, pixels of the shard)."""
+    cam = np.ascontiguousarray(camera)
+    geoms = np.ascontiguousarray(geoms)
+    sizes = np.zeros(4, np.int64)
+    _tcheck(test_lib().pt_test_camera_list(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, None, None, None, _p(sizes)))
+    if sizes[0] < 0:
+        return None
+    pix = np.zeros(int(sizes[0]), np.uint32)
+    wave = np.zeros((int(sizes[0]) // 64, 2), np.int32)
+    sig = np.zeros(int(sizes[1]), np.int32)
+    _tcheck(test_lib().pt_test_camera_list(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, _p(pix), _p(wave), _p(sig), _p(sizes)))
+    return pix, wave, sig, int(sizes[2]), int(sizes[3])
 
 
 def test_camera_cull_sweep(camera, geoms, samples=1):

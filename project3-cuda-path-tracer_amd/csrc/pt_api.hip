@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <limits>
 #include <map>
 #include <memory>
 #include <string>
@@ -114,6 +115,8 @@ struct State {
     SphereCull *dSphCull = nullptr; // sphere-heavy scenes: packed culling data of the spheres, and ...
     SphereCull *dSphGroups = nullptr;   // ... scenes of hundreds of them: the bounding balls of the table's groups (BounceArgs::sphGroups)
     bool grouped = false;           // ... whose later bounces take the k_bounce<..., GROUPS> instantiations
+    int *dCamWave = nullptr, *dCamSigIdx = nullptr;   // camera rays: the packed work list (build_camera_list), or none
+    uint32_t *dCamPix = nullptr;
     int *dRowOff = nullptr, *dRowIdx = nullptr;   // camera-ray bounce: per image row, the primitives whose pixel rectangle covers it
     int *dClassIdx = nullptr;       // later bounces: per queue class, the primitives to look at (KParams::classOff)
     float4 *dMeshRecs = nullptr;    // ptd::MeshUnit[]: triangles and inner nodes of every mesh of the scene (k_bounce<., ., ., true>)
@@ -286,6 +289,7 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     ba.ctrl = sl.ctrl; ba.ggeoms = R().dgeoms; ba.gmats = R().dmats; ba.ghit = R().dGeomHit; ba.contrib = contrib; ba.hitMask = sl.hitMask;
     ba.sphCull = R().dSphCull; ba.classIdx = R().dClassIdx;
     ba.rowOff = R().dRowOff; ba.rowIdx = R().dRowIdx;
+    ba.camPix = R().dCamPix; ba.camWave = R().dCamWave; ba.camSigIdx = R().dCamSigIdx;
     ba.walls = R().dwalls;
     ba.meshRecs = R().dMeshRecs;
     ba.hostFault = R().hostFaultDev;
@@ -602,6 +606,9 @@ void free_renderer() {
     if (R().dClassIdx) (void)hipFree(R().dClassIdx);
     if (R().dRowOff) (void)hipFree(R().dRowOff);
     if (R().dRowIdx) (void)hipFree(R().dRowIdx);
+    if (R().dCamPix) (void)hipFree(R().dCamPix);
+    if (R().dCamWave) (void)hipFree(R().dCamWave);
+    if (R().dCamSigIdx) (void)hipFree(R().dCamSigIdx);
     if (R().dMeshRecs) (void)hipFree(R().dMeshRecs);
     if (R().dWalkIdx) (void)hipFree(R().dWalkIdx);
     if (R().dWalkRowOff) (void)hipFree(R().dWalkRowOff);
@@ -1185,6 +1192,27 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             HIPCHECK(hipMalloc(&R().dRowIdx, cc.rowIdx.size() * sizeof(int)));
             HIPCHECK(hipMemcpy(R().dRowIdx, cc.rowIdx.data(), cc.rowIdx.size() * sizeof(int), hipMemcpyHostToDevice));
         }
+        // ... and, where the camera-ray instantiation can take it (pinhole, no meshes -- their walk shares the row bands' index space,
+        // BounceArgs::meshHit -- and not the sphere-heavy one), the packed work list in place of the row bands: the tiles' index space of
+        // one iteration is then the list (KParams::nLocalPad), and every pixel outside it is tallied at once (KParams::firstSkipped)
+        const bool listOff = getenv("PT_AMD_NO_CAMERA_LIST") && atoi(getenv("PT_AMD_NO_CAMERA_LIST"));   // (the variable: tests only)
+        CameraList cl;
+        if (!listOff && !R().dof && !R().mesh && !R().many &&
+            build_camera_list(cc, Wd, H, o.shard_rank, o.shard_count, k.nLocalPad, cl) && !cl.pix.empty()) {
+            k.nLocalPad = (int)cl.pix.size();
+            k.firstSkipped = (int)((long long)R().nLocal - cl.listed);
+            magic_divisor((uint32_t)k.nLocalPad, k.magicN, k.shiftN);
+            for (uint64_t q = 0; q * (uint64_t)k.nLocalPad < (1ull << 30); q = q < 64 ? q + 1 : q * 2 + 1)
+                for (uint64_t n : {q * k.nLocalPad, q * k.nLocalPad + k.nLocalPad - 1})
+                    if (n < (1ull << 30) && (uint32_t)((n * k.magicN) >> k.shiftN) != (uint32_t)(n / (uint64_t)k.nLocalPad))
+                        return fail(PT_ERR_INVALID, "pt_init: magic division self-check failed for d=%d n=%llu", k.nLocalPad, (unsigned long long)n);
+            HIPCHECK(hipMalloc(&R().dCamPix, cl.pix.size() * sizeof(uint32_t)));
+            HIPCHECK(hipMemcpy(R().dCamPix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIPCHECK(hipMalloc(&R().dCamWave, cl.wave.size() * sizeof(int)));
+            HIPCHECK(hipMemcpy(R().dCamWave, cl.wave.data(), cl.wave.size() * sizeof(int), hipMemcpyHostToDevice));
+            HIPCHECK(hipMalloc(&R().dCamSigIdx, cl.sigIdx.size() * sizeof(int)));
+            HIPCHECK(hipMemcpy(R().dCamSigIdx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
         if (!meshRecs.empty()) {
             // the mesh walks (k_mesh_walk) look at the meshes alone: the classes' lists, one list of all, the rows' lists (pairs as rowIdx's)
             std::vector<int> w;
@@ -1301,8 +1329,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // others.  Either the grid can be made coprime to the tiles per row (both must stay multiples of kSub, so only for an
     // odd tile count per row), or the kernel rotates the k-th tile of a workgroup k bands to the right inside its row,
     // which needs a grid that is a multiple of the tiles per row (k_bounce<true, .>).
+    // (the packed work list of camera rays has no column bands: nothing to rotate)
     R().prm.tilesPerRow = 0;
-    if (R().prm.Wp / kBlock > 1) {
+    if (R().prm.Wp / kBlock > 1 && R().dCamPix == nullptr) {
         const int perRow = R().prm.Wp / kBlock;
         auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
         if (gcd(perRow, kSub) == 1) {

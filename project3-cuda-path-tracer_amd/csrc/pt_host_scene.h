@@ -740,6 +740,84 @@ void build_camera_cull(const PtGeom *geoms, int ngeoms, const KParams &k, bool o
     if (cc.rowIdx.empty()) { cc.rowIdx.push_back(0); cc.rowIdx.push_back(0); }
 }
 
+// Camera rays as a packed work list (k_bounce<true, ...> of pinhole scenes without meshes or many small primitives): the pixels of this
+// shard's rows (y % shardCount == shardRank) that at least one row span of build_camera_cull covers, grouped by their SIGNATURE -- the
+// primitives whose spans cover the pixel, file order -- and every group padded to whole waves.  A wave then holds pixels of one
+// signature: its lanes all test exactly the primitives the row lists would have let each of them test, none of them idle for another
+// lane's primitive, and the frame's pixels that no span covers (misses whatever their jitter) take no lane at all.  Which lane takes
+// which pixel changes no result: the camera ray's jitter and the scatter are keyed on the pixel, and the iterations are committed in order.
+//   pix     per lane: x | y << 16 (image row y), kCamPad for the padding -- groups padded to 64 lanes, the list to whole tiles (kBlock)
+//   wave    per wave of 64 lanes: {first, end} of its signature's primitives in sigIdx (padding waves: an empty range)
+//   sigIdx  the signatures' primitives, one run per signature
+// false (the kernels keep the row-band tiles): no row lists, a row of more than kCamListRowMax spans (the grouping is quadratic in them),
+// more than kCamListSigMax signatures, or a list longer than maxLen lanes (the caller passes the row bands' own index space: the list
+// never visits more lanes than the tiles it replaces).  Needs W, H <= 32768 (the pixel word), which the row lists already do.
+constexpr int kCamListRowMax = 64, kCamListSigMax = 1 << 16;
+struct CameraList {
+    std::vector<uint32_t> pix;
+    std::vector<int> wave, sigIdx;
+    int nSig = 0;
+    long long listed = 0;                   // pixels in the list
+};
+bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int shardCount, long long maxLen, CameraList &cl) {
+    cl.pix.clear(); cl.wave.clear(); cl.sigIdx.clear();
+    cl.nSig = 0; cl.listed = 0;
+    if (cc.rowOff.empty() || W > 32768 || H > 32768 || shardCount < 1 || shardRank < 0 || shardRank >= shardCount) return false;
+    std::map<std::vector<int>, int> ids;
+    std::vector<std::vector<uint32_t>> groups;        // per signature its pixels, row-major
+    std::vector<std::vector<int>> sigs;
+    std::vector<int> cuts, act;
+    for (int y = shardRank; y < H; y += shardCount) {
+        const int e0 = cc.rowOff[y], e1 = cc.rowOff[y + 1];
+        if (e1 - e0 > kCamListRowMax) return false;
+        // the row's spans cut it into runs of one signature: between consecutive span ends
+        cuts.clear();
+        for (int e = e0; e < e1; ++e) {
+            const int sp = cc.rowIdx[2 * e + 1], x0 = std::max(sp & 0xffff, 0), x1 = std::min(sp >> 16, W - 1);
+            if (x0 <= x1) { cuts.push_back(x0); cuts.push_back(x1 + 1); }
+        }
+        std::sort(cuts.begin(), cuts.end());
+        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+            const int a = cuts[c], b = cuts[c + 1];
+            act.clear();
+            for (int e = e0; e < e1; ++e) {
+                const int sp = cc.rowIdx[2 * e + 1];
+                if ((sp & 0xffff) <= a && (sp >> 16) >= a) act.push_back(cc.rowIdx[2 * e]);
+            }
+            if (act.empty()) continue;
+            auto it = ids.emplace(act, (int)sigs.size());
+            if (it.second) {
+                if ((int)sigs.size() >= kCamListSigMax) return false;
+                sigs.push_back(act);
+                groups.emplace_back();
+            }
+            std::vector<uint32_t> &g = groups[(size_t)it.first->second];
+            for (int x = a; x < b; ++x) g.push_back((uint32_t)x | ((uint32_t)y << 16));
+            cl.listed += b - a;
+        }
+    }
+    long long len = 0;
+    for (const auto &g : groups) len += ((long long)g.size() + 63) / 64 * 64;
+    len = (len + kBlock - 1) / kBlock * kBlock;
+    if (len > maxLen) return false;
+    cl.pix.reserve((size_t)len);
+    cl.wave.reserve((size_t)len / 32);
+    for (size_t s = 0; s < groups.size(); ++s) {
+        const int first = (int)cl.sigIdx.size();
+        cl.sigIdx.insert(cl.sigIdx.end(), sigs[s].begin(), sigs[s].end());
+        const int end = (int)cl.sigIdx.size();
+        cl.pix.insert(cl.pix.end(), groups[s].begin(), groups[s].end());
+        cl.pix.resize((cl.pix.size() + 63) / 64 * 64, kCamPad);
+        while (cl.wave.size() < cl.pix.size() / 32) { cl.wave.push_back(first); cl.wave.push_back(end); }
+    }
+    cl.pix.resize((size_t)len, kCamPad);
+    cl.wave.resize((size_t)len / 32, 0);
+    if (cl.sigIdx.empty()) cl.sigIdx.push_back(0);
+    cl.nSig = (int)sigs.size();
+    return true;
+}
+
 // host mirrors of the glm ops used for the camera basis (same op order as ptd::)
 struct H3 { float x, y, z; };
 H3 hcross(H3 x, H3 y) { return H3{x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; }

@@ -564,6 +564,34 @@ int pt_test_camera_cull_tables(const PtCamera *cam, const PtGeom *geoms, int nge
     return PT_OK;
 }
 
+// host only: the camera rays' packed work list pt_init builds from the same tables (build_camera_list), for one shard, without a length cap
+int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
+                        int32_t *sig_idx, int64_t *sizes4) {
+    if (!cam || !geoms || ngeoms < 1 || !sizes4) return fail(PT_ERR_INVALID, "pt_test_camera_list: bad argument");
+    if (cam->resolution[0] < 1 || cam->resolution[1] < 1) return fail(PT_ERR_INVALID, "pt_test_camera_list: bad resolution");
+    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(PT_ERR_INVALID, "pt_test_camera_list: bad shard");
+    KParams k;
+    memset(&k, 0, sizeof k);
+    camera_params(*cam, k);
+    k.ngeoms = ngeoms;
+    std::vector<GeomDev> hg(ngeoms);
+    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i], k.pos);
+    CameraCull cc;
+    build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
+    CameraList cl;
+    const bool built = build_camera_list(cc, k.W, k.H, shard_rank, shard_count, std::numeric_limits<long long>::max(), cl);
+    sizes4[0] = built ? (int64_t)cl.pix.size() : -1;
+    sizes4[1] = (int64_t)cl.sigIdx.size();
+    sizes4[2] = cl.listed;
+    sizes4[3] = (int64_t)(k.H > shard_rank ? (k.H - shard_rank + shard_count - 1) / shard_count : 0) * k.W;
+    if (built && pix && wave2 && sig_idx) {
+        memcpy(pix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t));
+        memcpy(wave2, cl.wave.data(), cl.wave.size() * sizeof(int));
+        memcpy(sig_idx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int));
+    }
+    return PT_OK;
+}
+
 int pt_test_camera_cull_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t *hits, uint64_t *culled,
                               uint64_t *violations) {
     NEED_GPU();

@@ -421,6 +421,9 @@ struct BounceArgs {
     const int *rowOff;                  // camera rays (a tile is 256 pixels of one row): the primitives that can be reached from image row y are the entries
     const int *rowIdx;                  //   rowOff[y] .. rowOff[y + 1] of rowIdx, file order: pairs {primitive, x0 | x1 << 16} = the row's pixels
                                         //   inside the hull of the primitive's projected corners (pt_init); rowOff == nullptr: every primitive
+    const uint32_t *camPix;             // camera rays from the packed work list (pt_init: build_camera_list), or nullptr (the row-band tiles):
+    const int *camWave;                 //   per lane its pixel x | y << 16 (kCamPad: none), per wave {first, end} of its signature's primitives
+    const int *camSigIdx;               //   in camSigIdx; the list is KParams::nLocalPad lanes long
     uint32_t *hostFault;                // the sticky fault word's copy in page-locked host memory (written by a batch's last launch), or nullptr
     // ---- scenes with meshes: the walks run AHEAD of the bounce (k_mesh_walk) and leave, per path of a tile that lists a mesh, the nearest
     // mesh hit: meshHit[i] = bits of its distance << 32 | the winning triangle's unit << 1 | front side (all ones: none), i = the path's slot
@@ -772,6 +775,25 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
             r.pk = c.pk;                                        // pixelIndex | batch index << pixBits
         }
     };
+    // ---- camera rays from the packed work list (pinhole scenes without meshes or many small primitives, where pt_init built one:
+    // build_camera_list).  Tile T is 256 consecutive entries of iteration T / (list tiles); a lane's entry is its pixel, a wave's the
+    // range of its signature's primitives.  Both are requested one tile ahead, like the later bounces' paths: the lane's word is ONE
+    // load that flies during the previous tile's compaction, the wave's range a scalar load beside it.
+    constexpr bool kCamListOk = FIRST && !DOF && !MESH && !MANY;
+    const bool camList = kCamListOk && launder(kargs)->camPix != nullptr;      // (wave-uniform)
+    uint32_t camWord = kCamPad, camItb = 0u, camJ0 = 0u;                       // the next tile's: the lane's pixel, its iteration, first entry
+    int camSig0 = 0, camSig1 = 0;                                              // ... the wave's primitives: camSigIdx[camSig0 .. camSig1)
+    auto requestCam = [&](uint32_t Tq, uint32_t tid) {
+        const ArgsPtr A = launder(kargs);
+        const uint32_t idx0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)Tq) * kBlock;
+        camItb = fastDiv(idx0, A->prm.magicN, A->prm.shiftN);
+        camJ0 = idx0 - camItb * (uint32_t)A->prm.nLocalPad;
+        camWord = A->camPix[camJ0 + tid];
+        const uint32_t wq = (camJ0 >> 6) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+        const PT_CAS int *const wr = (const PT_CAS int *)(A->camWave) + 2 * wq;
+        camSig0 = wr[0];
+        camSig1 = wr[1];
+    };
     // the first tile of this workgroup that needs work, and its paths
     uint32_t T = blockIdx.x - rowShift;      // (FIRST with rotated bands: the first tile of the row; else the tile itself)
     TileMeta nextMeta = {false, 0u, 0u, nullptr, 0u};
@@ -779,6 +801,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
     if (!FIRST) {
         while (T < numTiles && !setupTile(T, threadIdx.x, nextMeta)) T += gridDim.x;
         if (T < numTiles) loadTile(nextMeta, nextRegs);
+    } else if (camList && T < numTiles) {
+        requestCam(T, threadIdx.x);
     }
     __syncthreads();                         // (materials, hit records, iteration hashes, the cleared scratch: staged by the prologue)
     // ---- TICKETS (later bounces that compact): a workgroup's first two tiles are static (blockIdx, blockIdx + grid), every further one
@@ -810,7 +834,17 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
         int itb = 0;                                            // which iteration of the batch this path belongs to
         int px = 0, py = 0;                                     // pixel coordinates (FIRST only)
         uint32_t recIdx0 = 0u;                                  // FIRST, MESH: the tile's first index in the padded pixel space (BounceArgs::meshHit)
-        if (FIRST) {
+        int sig0 = 0, sig1 = 0;                                 // FIRST from the work list: the wave's primitives
+        if (FIRST && camList) {
+            // (no scene-rectangle skip: the list holds only pixels some primitive's span covers, and no tile of padding alone)
+            const uint32_t w = camWord;
+            valid = w != kCamPad;
+            px = (int)(w & 0xffffu);
+            py = (int)(w >> 16);
+            itb = (int)camItb;
+            sig0 = camSig0;
+            sig1 = camSig1;
+        } else if (FIRST) {
             const ArgsPtr A = launder(kargs);
             const PT_CAS KParams &prm = A->prm;
             // Tile T = b + k grid covers 256 pixels of one (padded) row.  A row is `perRow` tiles; when the grid is a multiple
@@ -876,7 +910,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 const ArgsPtr A = launder(kargs);
                 const PT_CAS KParams &prm = A->prm;
                 pix = px + py * prm.W;
-                inScene = px >= prm.sceneRect[0] && px <= prm.sceneRect[2] && py >= prm.sceneRect[1] && py <= prm.sceneRect[3];
+                if (!camList) inScene = px >= prm.sceneRect[0] && px <= prm.sceneRect[2] && py >= prm.sceneRect[1] && py <= prm.sceneRect[3];
                 if (inScene) {
                     // camera ray (spec S2), jitter from the depth-0 stream of (iteration, pixel)
                     pixHash = utilhash((uint32_t)pix);              // (once: the scatter's engine below is keyed on the same pixel)
@@ -993,7 +1027,12 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 typedef int int2v __attribute__((ext_vector_type(2)));
                 const PT_CAS int2v *rowList = nullptr;               // camera rays of a whole-tile row: {primitive, its pixel span in this row}
                 bool listed = !FIRST;
-                if (FIRST) {
+                if (FIRST && camList) {
+                    // (a wave of the work list: every lane's pixel lies in the spans of exactly these primitives)
+                    gk0 = sig0; gk1 = sig1;
+                    classIdx = (const PT_CAS int *)(A->camSigIdx);
+                    listed = true;
+                } else if (FIRST) {
                     gk0 = 0; gk1 = A->prm.ngeoms;
                     classIdx = (const PT_CAS int *)(A->rowIdx);
                     if (!DOF && A->rowOff != nullptr) {
@@ -1013,7 +1052,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 const bool onlyOne = !FIRST && !PACKED && gk1 - gk0 == 1;
                 for (int gk = gk0; gk < gk1; ++gk) {
                     int g, span = 0;
-                    if (FIRST && listed) {
+                    if (FIRST && listed && !camList) {
                         const int2v e = rowList[gk];
                         g = e.x; span = e.y;
                     } else {
@@ -1035,7 +1074,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     // (testing the WAVE's pixel span against the rectangle in scalar registers instead -- a wave of a camera-ray tile
                     // is 64 consecutive pixels of one row -- saved 2 % of the vector instructions and cost 20 % more scalar ones:
                     // 1.5 % slower, not kept)
-                    if (FIRST && !DOF) {
+                    if (FIRST && !DOF && !camList) {
                         if (listed) inRect = (px >= (span & 0xffff)) & (px <= (span >> 16));   // (the list is this row's)
                         else inRect = (px >= G.rect[0]) & (px <= G.rect[2]) & (py >= G.rect[1]) & (py <= G.rect[3]);
                         if (__ballot(inRect) == 0ull) continue;
@@ -1662,6 +1701,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
         if (!FIRST) {       // the next tile of this workgroup that needs work: its loads fly during the compaction below
             while (Tnext < numTiles && !setupTile(Tnext, tid, nextMeta)) Tnext += gridDim.x;
             if (Tnext < numTiles) loadTile(nextMeta, nextRegs);
+        } else if (camList && Tnext < numTiles) {
+            requestCam(Tnext, tid);
         }
         probe(18);                                              // (compaction)
         const bool alive = (fl & 1u) != 0u;
