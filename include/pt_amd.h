@@ -124,10 +124,10 @@ typedef struct PtOptions {
 
 #define PT_MAX_DEPTH 62
 #define PT_MAX_BATCH 256
-/* Bumped whenever a struct of this header changes size or meaning (6: round 6 -- pt_group_iterate / pt_group_reduce, the group's asynchronous
+/* Bumped whenever a struct of this header changes size or meaning (7: PtTexture / PtTexBinding, pt_set_textures; 6: round 6 -- pt_group_iterate / pt_group_reduce, the group's asynchronous
  * assembly; 5: contexts and groups; PtMesh has carried `normals` and `materials` since 4).  A host built against another header finds out with
  * pt_abi_version() != PT_AMD_ABI_VERSION before it passes structs. */
-#define PT_AMD_ABI_VERSION 6
+#define PT_AMD_ABI_VERSION 7
 int pt_abi_version(void);
 
 typedef struct PtCounters {
@@ -177,6 +177,33 @@ typedef struct PtMesh {
 int pt_set_meshes(const PtMesh *meshes, int nmeshes);
 /* ... the same with the caller's sizeof(PtMesh): PT_ERR_INVALID instead of strided garbage when host and library disagree about the struct */
 int pt_set_meshes_sized(const PtMesh *meshes, int nmeshes, size_t mesh_struct_bytes);
+
+/* Texture mapping (PBRT 10.4; a README extra the reference names and does not implement, so the semantics are build-defined --
+ * csrc/pt_device.h, "texture mapping", gives every operation):
+ *   - a texture is bound to a PRIMITIVE (PtMaterial stays the reference's Material) and multiplies its material's colour (RGB) wherever the
+ *     renderer uses it: the diffuse albedo and the emitted radiance.  SPECRGB and the material's switches are untouched; no random number is
+ *     drawn and no path changes its course;
+ *   - texels are linear float RGB, row 0 = the image's top row; repeat wrapping, bilinear filtering, v = 0 at the bottom (the OBJ convention);
+ *   - texture coordinates: a mesh blends its triangles' corner UVs with the hit's barycentrics; a cube maps each face's square to [0, 1]^2
+ *     (axis a: u = q[(a + 1) % 3] + 0.5, v = q[(a + 2) % 3] + 0.5 of the object-space hit point q); a sphere takes longitude and latitude
+ *     of its object-space hit direction (u = 0.5 + atan2(z, x) / 2 pi, v = 0.5 + asin(y) / pi).
+ * pt_set_textures registers textures and bindings for the NEXT pt_init (copied; kept across pt_free like pt_set_meshes' triangles;
+ * (NULL, 0, ..., NULL, 0, ...) clears them); the struct sizes are the caller's sizeof, as pt_set_meshes_sized takes it.  pt_init fails with
+ * PT_ERR_INVALID when a binding names a geom or texture out of range or a geom twice, a mesh binding has no UVs or another triangle count than
+ * the registered mesh, a binding of a sphere or cube has UVs, a texel is non-finite, a side is outside 1..16384, or the textures hold 2^28 texels
+ * or more.  Scenes with a bound texture take k_bounce instantiations of their own; other scenes run what they ran before. */
+typedef struct PtTexture {
+    int32_t width, height;
+    const float *rgb;       /* width x height x 3 floats, row 0 = top */
+} PtTexture;
+typedef struct PtTexBinding {
+    int32_t geom;           /* index into pt_init's geoms */
+    int32_t texture;        /* index into the registered textures */
+    int32_t ntris;          /* mesh geoms: the mesh's triangle count; spheres and cubes: 0 */
+    const float *uvs;       /* mesh geoms: ntris x 6 floats, the corner UVs (u0, v0, u1, v1, u2, v2) of every triangle; others NULL */
+} PtTexBinding;
+int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings, int nbindings,
+                    size_t binding_struct_bytes);
 
 /* pathtraceInit: upload scene, allocate the accumulator and the SoA path-state buffers.
  * Replaces reference src/pathtrace.cu:75-85.  Calling it twice without pt_free re-initialises. */
@@ -238,7 +265,7 @@ int pt_compact_nonzero_i32(const int32_t *in_dev, int32_t *out_dev, int64_t n, i
  * The reference's renderer is one set of file-static globals bound to device 0 (src/pathtrace.cu:70-71, src/preview.cpp:107).  Here a
  * renderer is a context: pt_ctx_create makes one, pt_ctx_make_current(ctx) makes every function above act on it for the calling thread
  * (NULL: back to the default context), pt_ctx_destroy frees its renderer and the context.  A context initialised on a device makes that
- * device current when it is made current.  pt_set_meshes registers meshes per context. */
+ * device current when it is made current.  pt_set_meshes and pt_set_textures register per context. */
 typedef struct PtContext PtContext;
 PtContext *pt_ctx_create(void);               /* NULL: out of memory */
 int        pt_ctx_make_current(PtContext *ctx /* NULL = the default context */);
@@ -279,6 +306,8 @@ void pt_group_destroy(PtGroup *g);
 int  pt_group_size(const PtGroup *g);
 const char *pt_group_collective(const PtGroup *g);
 int  pt_group_set_meshes(PtGroup *g, const PtMesh *meshes, int nmeshes);
+int  pt_group_set_textures(PtGroup *g, const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings,
+                           int nbindings, size_t binding_struct_bytes);
 int  pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
                    const PtOptions *opts /* may be NULL */);
 int  pt_group_iterate_batch(PtGroup *g, int frame, int first_iter, int count);

@@ -135,6 +135,13 @@ int pt_test_sincos(const float *x, int n, float *s, float *c);
 int pt_test_pow(const float *x, const float *e, int n, float *out);   /* build-defined x^e of the imperfect-specular sampler */
 int pt_test_reflect_refract(const float *I3, const float *N3, const float *eta, int n, float *refl3,
                             float *refr3);
+/* texture mapping (pt_amd.h, pt_device.h "texture mapping"): the kernels' own device functions over host arrays.
+ * pt_test_texture_sample: one texture of w x h texels (rgb: w * h * 3 floats, row 0 = top) at n coordinate pairs uv2 -> rgb_out3.
+ * pt_test_texture_uv: n texture coordinates -> uv_out2.  kind 0 (sphere): in = n x 3, the object-space hit point; kind 1 (cube): the same,
+ * face[i] = the hit face (axis * 2 + (sign > 0)); kind 2 (mesh): in = n x 8, {u, v} the barycentrics and the triangle's corner UVs
+ * {u0, v0, u1, v1, u2, v2}.  `face` is read for cubes only (may be NULL otherwise). */
+int pt_test_texture_sample(const float *rgb, int w, int h, const float *uv2, int n, float *rgb_out3);
+int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, float *uv_out2);
 
 #ifdef __cplusplus
 }

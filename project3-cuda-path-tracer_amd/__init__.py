@@ -57,8 +57,9 @@ ABI_SYMBOLS = [
     "pt_ctx_create", "pt_ctx_make_current", "pt_ctx_current", "pt_ctx_destroy",
     "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_collective", "pt_group_set_meshes", "pt_group_init", "pt_group_iterate_batch",
     "pt_group_iterate", "pt_group_reduce", "pt_group_sync", "pt_group_readback", "pt_group_counters",
+    "pt_set_textures", "pt_group_set_textures",
 ]
-PT_AMD_ABI_VERSION = 6
+PT_AMD_ABI_VERSION = 7
 # every symbol include/pt_amd_test.h declares: libpt_amd_test.so only -- the product library must NOT export them
 TEST_ABI_SYMBOLS = [
     "pt_debug_trace_paths",
@@ -67,7 +68,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_bvh",
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
-    "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep",
+    "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
 ]
 
 
@@ -79,6 +80,14 @@ class PtOptions(C.Structure):
 
 class PtMesh(C.Structure):
     _fields_ = [("geom", C.c_int32), ("ntris", C.c_int32), ("tris", C.c_void_p), ("normals", C.c_void_p), ("materials", C.c_void_p)]
+
+
+class PtTexture(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgb", C.c_void_p)]
+
+
+class PtTexBinding(C.Structure):
+    _fields_ = [("geom", C.c_int32), ("texture", C.c_int32), ("ntris", C.c_int32), ("uvs", C.c_void_p)]
 
 
 class PtCounters(C.Structure):
@@ -132,6 +141,8 @@ def _bind(L, with_tests):
     L.pt_group_collective.argtypes = [vp]
     L.pt_group_collective.restype = C.c_char_p
     L.pt_group_set_meshes.argtypes = [vp, C.POINTER(PtMesh), i32]
+    L.pt_set_textures.argtypes = [C.POINTER(PtTexture), i32, C.c_size_t, C.POINTER(PtTexBinding), i32, C.c_size_t]
+    L.pt_group_set_textures.argtypes = [vp, C.POINTER(PtTexture), i32, C.c_size_t, C.POINTER(PtTexBinding), i32, C.c_size_t]
     L.pt_group_init.argtypes = [vp, vp, vp, i32, vp, i32, i32, C.POINTER(PtOptions)]
     L.pt_group_iterate_batch.argtypes = [vp, i32, i32, i32]
     L.pt_group_iterate.argtypes = [vp, i32, i32]
@@ -170,6 +181,8 @@ def _bind(L, with_tests):
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
         L.pt_test_group_fail_next_reduce.argtypes = [vp, i32]
         L.pt_test_sphere_group_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p, u64p, C.POINTER(C.c_int32)]
+        L.pt_test_texture_sample.argtypes = [vp, i32, i32, vp, i32, vp]
+        L.pt_test_texture_uv.argtypes = [i32, vp, vp, i32, vp]
     return L
 
 
@@ -264,9 +277,14 @@ def host_lib():
             getattr(H, n).argtypes = [vp, C.c_int]
         H.pth_scene_mesh_tris.argtypes = [vp, C.c_int]
         H.pth_scene_mesh_tris.restype = vp
-        for n in ("pth_scene_mesh_normals", "pth_scene_mesh_materials"):
+        for n in ("pth_scene_mesh_normals", "pth_scene_mesh_materials", "pth_scene_mesh_uvs", "pth_scene_texture_rgb"):
             getattr(H, n).argtypes = [vp, C.c_int]
             getattr(H, n).restype = vp
+        H.pth_scene_num_textures.argtypes = [vp]
+        for n in ("pth_scene_texture_width", "pth_scene_texture_height", "pth_scene_geom_texture"):
+            getattr(H, n).argtypes = [vp, C.c_int]
+        H.pth_scene_texture_path.argtypes = [vp, C.c_int]
+        H.pth_scene_texture_path.restype = C.c_char_p
         for n in ("pth_save_png", "pth_save_hdr"):
             getattr(H, n).argtypes = [C.c_char_p, vp, C.c_int, C.c_int, C.c_float]
             getattr(H, n).restype = C.c_int
@@ -300,6 +318,7 @@ class Scene:
         self.meshes = {}
         self.mesh_normals = {}      # geom index -> (ntris, 9) vertex normals (`vn`); absent: flat shading
         self.mesh_materials = {}    # geom index -> (ntris,) int32 scene material per face (`usemtl <k>`, -1 = the object's); absent: none
+        self.mesh_uvs = {}          # geom index -> (ntris, 6) float32 corner texture coordinates (`vt`); absent: none
         for i in range(H.pth_scene_num_meshes(h)):
             nt = H.pth_scene_mesh_ntris(h, i)
             g = H.pth_scene_mesh_geom(h, i)
@@ -309,6 +328,17 @@ class Scene:
                 self.mesh_normals[g] = np.frombuffer(C.string_at(nptr, 36 * nt), np.float32).reshape(nt, 9).copy()
             if mptr:
                 self.mesh_materials[g] = np.frombuffer(C.string_at(mptr, 4 * nt), np.int32).copy()
+            uptr = H.pth_scene_mesh_uvs(h, i)
+            if uptr:
+                self.mesh_uvs[g] = np.frombuffer(C.string_at(uptr, 24 * nt), np.float32).reshape(nt, 6).copy()
+        # `TEXTURE <file>` lines: the scene's textures ((H, W, 3) float32, row 0 = top) and per geom the index of its texture or -1
+        self.textures = []
+        self.texture_paths = []
+        for i in range(H.pth_scene_num_textures(h)):
+            tw, th = H.pth_scene_texture_width(h, i), H.pth_scene_texture_height(h, i)
+            self.textures.append(np.frombuffer(C.string_at(H.pth_scene_texture_rgb(h, i), 12 * tw * th), np.float32).reshape(th, tw, 3).copy())
+            self.texture_paths.append(H.pth_scene_texture_path(h, i).decode())
+        self.geom_textures = np.array([H.pth_scene_geom_texture(h, g) for g in range(ng)], np.int32)
         w, hh = (int(v) for v in self.camera["resolution"][0])
         self.image = np.zeros((hh, w, 3), np.float32)   # RenderState::image (src/sceneStructs.h:53)
 
@@ -348,6 +378,7 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
     cam = np.ascontiguousarray(scene.camera)
     depth = scene.traceDepth if traceDepth is None else traceDepth
     set_meshes(getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None))
+    set_textures(*_scene_textures(scene))
     global _atexit_registered
     if not _atexit_registered:
         # an interpreter that exits with a live renderer (an exception between pathtrace and pathtraceFree): drain the streams
@@ -360,7 +391,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
     _scene = scene
     global _last_init
     _last_init = (cam, geoms, mats, depth, (shard_rank, shard_count, device, flags, lens_radius, focal_distance),
-                  (getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None)))
+                  (getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None)),
+                  _scene_textures(scene))
 
 
 def _mesh_array(meshes, normals=None, materials=None):
@@ -385,6 +417,39 @@ def set_meshes(meshes, normals=None, materials=None, L=None):
     arr, n, alive = _mesh_array(meshes, normals, materials)
     L = L or lib()
     _check(L.pt_set_meshes_sized(arr, n, C.sizeof(PtMesh)), L)
+
+
+def _scene_textures(scene):
+    """(textures, geom_textures, mesh_uvs) of a Scene -- or of any object with those attributes; none: untextured"""
+    return (list(getattr(scene, "textures", None) or []), getattr(scene, "geom_textures", None), getattr(scene, "mesh_uvs", None) or {})
+
+
+def _texture_arrays(textures, geom_textures=None, mesh_uvs=None):
+    """(PtTexture array, count, PtTexBinding array, count, the arrays they point into) for pt_set_textures / pt_group_set_textures.
+    A geom is bound when geom_textures[g] >= 0; a bound mesh geom carries its UVs from mesh_uvs[g] ((ntris, 6) float32)."""
+    tex = [np.ascontiguousarray(t, np.float32).reshape(np.shape(t)[0], np.shape(t)[1], 3) for t in textures]
+    tarr = (PtTexture * max(len(tex), 1))()
+    for i, t in enumerate(tex):
+        tarr[i] = PtTexture(t.shape[1], t.shape[0], t.ctypes.data)
+    gt = [] if geom_textures is None else [int(x) for x in np.asarray(geom_textures).reshape(-1)]
+    binds, uvs = [], []
+    for g, k in enumerate(gt):
+        if k < 0:
+            continue
+        u = (mesh_uvs or {}).get(g)
+        u = None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 6)
+        uvs.append(u)
+        binds.append(PtTexBinding(g, k, 0 if u is None else len(u), None if u is None else u.ctypes.data))
+    barr = (PtTexBinding * max(len(binds), 1))(*binds)
+    return tarr, len(tex), barr, len(binds), (tex, uvs)
+
+
+def set_textures(textures, geom_textures=None, mesh_uvs=None, L=None):
+    """pt_set_textures for the next pathtraceInit: `textures` a list of (H, W, 3) float32 images (row 0 = top), `geom_textures` per geom the
+    index of its texture or -1, `mesh_uvs` {geom index: (ntris, 6) corner UVs} for the textured meshes.  Empty lists clear."""
+    tarr, nt, barr, nb, alive = _texture_arrays(textures, geom_textures, mesh_uvs)
+    L = L or lib()
+    _check(L.pt_set_textures(tarr, nt, C.sizeof(PtTexture), barr, nb, C.sizeof(PtTexBinding)), L)
 
 
 def pathtrace(pbo, frame, iteration, readback=True):
@@ -454,12 +519,13 @@ def debug_trace_paths(iteration, bounces, npixels):
     if _last_init is None:
         raise PtError("debug_trace_paths before pathtraceInit")
     T = test_lib()
-    cam, geoms, mats, depth, (rank, count, device, flags, lens_radius, focal_distance), meshes = _last_init
+    cam, geoms, mats, depth, (rank, count, device, flags, lens_radius, focal_distance), meshes, textures = _last_init
     if _lib is T:                                    # (renderer_from_test_library: the renderer IS the test library's)
         own = False
     else:
         own = True
         set_meshes(*meshes, L=T)
+        set_textures(*textures, L=T)
         opt = PtOptions(rank, count, device, flags & ~(PT_FLAG_TRACE_AHEAD | PT_FLAG_KERNEL_TIMING), 1, 1, None, None, lens_radius, focal_distance)
         _tcheck(T.pt_init(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), depth, C.byref(opt)))
     try:
@@ -515,6 +581,8 @@ class Group:
         geoms, mats, cam = (np.ascontiguousarray(x) for x in (scene.geoms, scene.materials, scene.camera))
         arr, nm, alive = _mesh_array(getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None))
         _check(lib().pt_group_set_meshes(self.handle, arr, nm))
+        tarr, nt, barr, nb, alive_t = _texture_arrays(*_scene_textures(scene))
+        _check(lib().pt_group_set_textures(self.handle, tarr, nt, C.sizeof(PtTexture), barr, nb, C.sizeof(PtTexBinding)))
         opt = PtOptions(0, 1, -1, flags, pipeline_depth, max_batch, None, None, lens_radius, focal_distance)
         _check(lib().pt_group_init(self.handle, _p(cam), _p(geoms), len(geoms), _p(mats), len(mats),
                                    scene.traceDepth if traceDepth is None else traceDepth, C.byref(opt)))
@@ -651,6 +719,25 @@ def test_hemisphere(normals, iter_index_depth):
     iid = np.ascontiguousarray(iter_index_depth, np.int32).reshape(-1, 3)
     out = np.empty_like(normals)
     _tcheck(test_lib().pt_test_hemisphere(_p(normals), _p(iid), len(normals), _p(out)))
+    return out
+
+
+def test_texture_sample(texture, uv):
+    """The kernels' bilinear texture lookup on the GPU: texture (H, W, 3) float32 (row 0 = top), uv (n, 2) -> (n, 3) float32."""
+    t = np.ascontiguousarray(texture, np.float32)
+    u = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.empty((len(u), 3), np.float32)
+    _tcheck(test_lib().pt_test_texture_sample(_p(t), t.shape[1], t.shape[0], _p(u), len(u), _p(out)))
+    return out
+
+
+def test_texture_uv(kind, inp, face=None):
+    """The kernels' texture coordinates on the GPU: kind 0 sphere / 1 cube (inp (n, 3) object-space hit points, face (n,) int32 for cubes),
+    2 mesh (inp (n, 8): barycentric u, v and the corner UVs u0 v0 u1 v1 u2 v2) -> (n, 2) float32."""
+    a = np.ascontiguousarray(inp, np.float32).reshape(len(inp), -1)
+    f = None if face is None else np.ascontiguousarray(face, np.int32)
+    out = np.empty((len(a), 2), np.float32)
+    _tcheck(test_lib().pt_test_texture_uv(kind, _p(a), None if f is None else _p(f), len(a), _p(out)))
     return out
 
 

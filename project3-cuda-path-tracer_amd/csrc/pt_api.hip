@@ -77,6 +77,8 @@ int fail(int code, const char *fmt, ...) {
     } while (0)
 
 constexpr int kMaxSlots = 4;
+constexpr int kTexSizeMax = 16384;     // largest side of a texture (pt_set_textures)
+constexpr long long kTexTexelsMax = 1ll << 28;   // the textures of a scene hold fewer texels
 
 // One in-flight iteration: its own stream, path buffers, counters and deferred-radiance buffer.
 struct Slot {
@@ -120,6 +122,11 @@ struct State {
     int *dRowOff = nullptr, *dRowIdx = nullptr;   // camera-ray bounce: per image row, the primitives whose pixel rectangle covers it
     int *dClassIdx = nullptr;       // later bounces: per queue class, the primitives to look at (KParams::classOff)
     float4 *dMeshRecs = nullptr;    // ptd::MeshUnit[]: triangles and inner nodes of every mesh of the scene (k_bounce<., ., ., true>)
+    // textured scenes (k_bounce<..., TEX>): BounceArgs::texGeom / texDesc / texels / texUV
+    ptd::TexGeom *dTexGeom = nullptr;
+    int4 *dTexDesc = nullptr;
+    float4 *dTexels = nullptr, *dTexUV = nullptr;
+    bool tex = false;       // a texture is bound to at least one primitive
     bool mesh = false;      // the scene holds triangle meshes: the k_bounce<., false, ., true> variants
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
     int *dWalkIdx = nullptr, *dWalkRowOff = nullptr;
@@ -166,6 +173,11 @@ struct State {
     // triangle soups registered by pt_set_meshes, consumed by the next pt_init (kept across pt_free: the reference's
     // Free -> Init restart protocol re-initialises the same scene)
     std::vector<ptm::HostMesh> meshes;
+    // ... and so are the textures and their bindings registered by pt_set_textures
+    struct HostTexture { int w = 0, h = 0; std::vector<float> rgb; };              // rgb: w * h * 3, or empty where w or h is out of range
+    struct HostTexBinding { int geom = 0, texture = 0, ntris = 0; std::vector<float> uvs; };
+    std::vector<HostTexture> textures;
+    std::vector<HostTexBinding> texBindings;
 };
 
 // Renderer instances.  The reference keeps its renderer in file-static globals (src/pathtrace.cu:70-71: one per process, not
@@ -225,9 +237,21 @@ int resolve_events(std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms
 
 // The instantiation of k_bounce a launch takes: FIRST (camera rays), MANY (per-lane sphere lists: scenes with more than
 // kBinMax spheres), DOF (thin lens: the camera-ray launch only), MESH (scenes with triangle meshes).
-template <bool F, bool M, bool D, bool ME, bool PL = false, bool CU = false, bool GR = false>
-const void *kb() { return reinterpret_cast<const void *>(k_bounce<F, M, D, ME, PL, CU, GR>); }
+template <bool F, bool M, bool D, bool ME, bool PL = false, bool CU = false, bool GR = false, bool TX = false>
+const void *kb() { return reinterpret_cast<const void *>(k_bounce<F, M, D, ME, PL, CU, GR, TX>); }
+// textured scenes: twelve instantiations of their own -- never PLAIN or GROUPS, and MANY always in the form that sweeps cubes too
+const void *bounce_kernel_tex(bool first, bool dof) {
+    if (R().many && R().mesh) return first ? (dof ? kb<true, true, true, true, false, true, false, true>() : kb<true, true, false, true, false, true, false, true>())
+                                           : kb<false, true, false, true, false, true, false, true>();
+    if (R().many) return first ? (dof ? kb<true, true, true, false, false, true, false, true>() : kb<true, true, false, false, false, true, false, true>())
+                               : kb<false, true, false, false, false, true, false, true>();
+    if (R().mesh) return first ? (dof ? kb<true, false, true, true, false, false, false, true>() : kb<true, false, false, true, false, false, false, true>())
+                               : kb<false, false, false, true, false, false, false, true>();
+    return first ? (dof ? kb<true, false, true, false, false, false, false, true>() : kb<true, false, false, false, false, false, false, true>())
+                 : kb<false, false, false, false, false, false, false, true>();
+}
 const void *bounce_kernel(bool first, bool dof) {
+    if (R().tex) return bounce_kernel_tex(first, dof);
     // (plain scenes -- diffuse / emissive / perfect-mirror materials, no README extra: the instantiations without the rarer branches)
     if (R().plain && !R().mesh && !R().many && !dof) return first ? kb<true, false, false, false, true>() : kb<false, false, false, false, true>();
     if (R().grouped && !first)            // hundreds of swept primitives: the two-level sweep, nothing of the scene's tables in LDS
@@ -299,6 +323,7 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     ba.walkAll0 = R().walkAll0; ba.walkAll1 = R().walkAll1;
     ba.walkMeshRows = R().dWalkMeshRows; ba.walkMeshLds = R().walkMeshLds;
     ba.sphGroups = R().dSphGroups;
+    ba.texGeom = R().dTexGeom; ba.texDesc = R().dTexDesc; ba.texels = R().dTexels; ba.texUV = R().dTexUV;
     void *kargs[] = {&ba};
     const bool first = depth == 1;
     // scenes with meshes: the walks of this bounce's rays, ahead of it (pt_mesh_walk.h)
@@ -613,10 +638,18 @@ void free_renderer() {
     if (R().dWalkIdx) (void)hipFree(R().dWalkIdx);
     if (R().dWalkRowOff) (void)hipFree(R().dWalkRowOff);
     if (R().dWalkMeshRows) (void)hipFree(R().dWalkMeshRows);
-    {   // (the registered meshes outlive the renderer: see State::meshes)
+    if (R().dTexGeom) (void)hipFree(R().dTexGeom);
+    if (R().dTexDesc) (void)hipFree(R().dTexDesc);
+    if (R().dTexels) (void)hipFree(R().dTexels);
+    if (R().dTexUV) (void)hipFree(R().dTexUV);
+    {   // (the registered meshes and textures outlive the renderer: see State::meshes)
         std::vector<ptm::HostMesh> keep = std::move(R().meshes);
+        std::vector<State::HostTexture> keepTex = std::move(R().textures);
+        std::vector<State::HostTexBinding> keepBind = std::move(R().texBindings);
         R() = State();
         R().meshes = std::move(keep);
+        R().textures = std::move(keepTex);
+        R().texBindings = std::move(keepBind);
     }
 }
 }  // namespace
@@ -654,6 +687,38 @@ int pt_set_meshes(const PtMesh *meshes, int nmeshes) {
     return PT_OK;
 }
 
+int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings, int nbindings,
+                    size_t binding_struct_bytes) {
+    if (texture_struct_bytes != sizeof(PtTexture) || binding_struct_bytes != sizeof(PtTexBinding))
+        return fail(PT_ERR_INVALID, "pt_set_textures: the caller's PtTexture / PtTexBinding are %zu / %zu bytes, this library's %zu / %zu (ABI version %d here)",
+                    texture_struct_bytes, binding_struct_bytes, sizeof(PtTexture), sizeof(PtTexBinding), PT_AMD_ABI_VERSION);
+    if (ntextures < 0 || nbindings < 0 || (ntextures && !textures) || (nbindings && !bindings)) return fail(PT_ERR_INVALID, "pt_set_textures: null argument");
+    // (sizes, indices and values are checked by pt_init, against the scene; what cannot be copied safely is not copied and refused there)
+    for (int i = 0; i < ntextures; ++i)
+        if (textures[i].width >= 1 && textures[i].width <= kTexSizeMax && textures[i].height >= 1 && textures[i].height <= kTexSizeMax && !textures[i].rgb)
+            return fail(PT_ERR_INVALID, "pt_set_textures: texture %d has no texels", i);
+    for (int i = 0; i < nbindings; ++i)
+        if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_textures: binding %d: bad UVs", i);
+    R().textures.clear();
+    R().texBindings.clear();
+    long long texels = 0;
+    for (int i = 0; i < ntextures; ++i) {
+        State::HostTexture t;
+        t.w = textures[i].width; t.h = textures[i].height;
+        const bool sized = t.w >= 1 && t.w <= kTexSizeMax && t.h >= 1 && t.h <= kTexSizeMax;
+        if (sized) texels += (long long)t.w * t.h;
+        if (sized && texels < kTexTexelsMax) t.rgb.assign(textures[i].rgb, textures[i].rgb + (size_t)t.w * t.h * 3);
+        R().textures.push_back(std::move(t));
+    }
+    for (int i = 0; i < nbindings; ++i) {
+        State::HostTexBinding b;
+        b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris;
+        if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
+        R().texBindings.push_back(std::move(b));
+    }
+    return PT_OK;
+}
+
 int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
             const PtOptions *opts) {
     if (!cam || ngeoms < 0 || nmats < 0 || (ngeoms && !geoms) || (nmats && !mats))
@@ -673,6 +738,34 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     for (const ptm::HostMesh &m : R().meshes)
         if (m.geom < 0 || m.geom >= ngeoms || geoms[m.geom].type != PT_MESH)
             return fail(PT_ERR_INVALID, "pt_init: triangles registered for geom %d, which is not a mesh of this scene (pt_set_meshes)", m.geom);
+    {   // textures (pt_set_textures)
+        long long texels = 0;
+        for (size_t i = 0; i < R().textures.size(); ++i) {
+            const State::HostTexture &t = R().textures[i];
+            if (t.w < 1 || t.w > kTexSizeMax || t.h < 1 || t.h > kTexSizeMax)
+                return fail(PT_ERR_INVALID, "pt_init: texture %zu is %d x %d (each side 1..%d)", i, t.w, t.h, kTexSizeMax);
+            texels += (long long)t.w * t.h;
+            if (texels >= kTexTexelsMax) return fail(PT_ERR_INVALID, "pt_init: the textures hold 2^28 texels or more");
+            for (float c : t.rgb)
+                if (!std::isfinite(c)) return fail(PT_ERR_INVALID, "pt_init: texture %zu holds a non-finite texel", i);
+        }
+        std::vector<char> bound(ngeoms, 0);
+        for (size_t i = 0; i < R().texBindings.size(); ++i) {
+            const State::HostTexBinding &b = R().texBindings[i];
+            if (b.geom < 0 || b.geom >= ngeoms) return fail(PT_ERR_INVALID, "pt_init: texture binding %zu names geom %d of %d", i, b.geom, ngeoms);
+            if (b.texture < 0 || b.texture >= (int)R().textures.size())
+                return fail(PT_ERR_INVALID, "pt_init: texture binding %zu names texture %d of %zu", i, b.texture, R().textures.size());
+            if (bound[b.geom]++) return fail(PT_ERR_INVALID, "pt_init: geom %d has two texture bindings", b.geom);
+            if (geoms[b.geom].type == PT_MESH) {
+                const ptm::HostMesh *hm_ = mesh_of(b.geom);
+                if (b.uvs.empty()) return fail(PT_ERR_INVALID, "pt_init: textured mesh geom %d has no UVs", b.geom);
+                if ((size_t)b.ntris * 9 != hm_->tris.size())
+                    return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for mesh geom %d of %zu", b.ntris, b.geom, hm_->tris.size() / 9);
+            } else if (!b.uvs.empty() || b.ntris != 0) {
+                return fail(PT_ERR_INVALID, "pt_init: UVs given for geom %d, which is not a mesh", b.geom);
+            }
+        }
+    }
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
     register_exit_handler();
     free_renderer();
@@ -862,6 +955,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     const bool flatMeshes = getenv("PT_AMD_MESH_FLAT") && atoi(getenv("PT_AMD_MESH_FLAT"));   // tests only: no hierarchy
     std::vector<std::array<float, 6>> meshBox(ngeoms ? ngeoms : 1);
     std::vector<const float *> boxes(ngeoms ? ngeoms : 1, nullptr);
+    std::vector<uint32_t> triBase(ngeoms ? ngeoms : 1, 0u);      // (textured meshes: the unit of the first triangle record, ptm::appendMesh)
     for (int i = 0; i < ngeoms; ++i) {
         float *box = meshBox[i].data();
         const bool isMesh = geoms[i].type == PT_MESH;
@@ -881,7 +975,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         }
         pack_geom(geoms[i], hg[i], k.pos, isMesh ? box : nullptr);
         hg[i].meshRoot = root;
-        if (isMesh) { hg[i].meshStride = stride; hg[i].meshUnit0 = unit0; hg[i].meshUnit1 = root; }
+        if (isMesh) { hg[i].meshStride = stride; hg[i].meshUnit0 = unit0; hg[i].meshUnit1 = root; triBase[i] = (unit0 + 3u) & ~3u; }
         if (geoms[i].type == PT_CUBE) {
             if (k.nCubes >= 32767) return fail(PT_ERR_INVALID, "pt_init: more than 32767 cubes");
             hg[i].frameSlot = (short)k.nCubes++;
@@ -1033,6 +1127,38 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     HIPCHECK(hipMalloc(&R().dwalls, hw.size() * sizeof(WallBox)));
     HIPCHECK(hipMemcpy(R().dwalls, hw.data(), hw.size() * sizeof(WallBox), hipMemcpyHostToDevice));
     R().mesh = !meshRecs.empty();
+    R().tex = !R().texBindings.empty();
+    if (R().tex) {         // every texel one float4, the textures one after another; per primitive its TexGeom; per textured triangle two float4
+        std::vector<int4> desc;
+        std::vector<float4> texels, uv;
+        for (const State::HostTexture &t : R().textures) {
+            desc.push_back(make_int4((int)texels.size(), t.w, t.h, 0));
+            for (size_t q = 0; q < (size_t)t.w * t.h; ++q) texels.push_back(make_float4(t.rgb[3 * q], t.rgb[3 * q + 1], t.rgb[3 * q + 2], 0.0f));
+        }
+        std::vector<ptd::TexGeom> tg(ngeoms ? ngeoms : 1, ptd::TexGeom{-1, 0, 0, 0});
+        for (int i = 0; i < ngeoms; ++i) tg[i].kind = geoms[i].type == PT_CUBE ? 1 : (geoms[i].type == PT_MESH ? 2 : 0);
+        for (const State::HostTexBinding &b : R().texBindings) {
+            tg[b.geom].tex = b.texture;
+            if (b.uvs.empty()) continue;
+            tg[b.geom].uvBase = (int)(uv.size() / 2);
+            tg[b.geom].triBase = (int)triBase[b.geom];
+            for (int f = 0; f < b.ntris; ++f) {
+                const float *c = b.uvs.data() + 6 * (size_t)f;
+                uv.push_back(make_float4(c[0], c[1], c[2], c[3]));
+                uv.push_back(make_float4(c[4], c[5], 0.0f, 0.0f));
+            }
+            if (uv.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many textured triangles");
+        }
+        if (uv.empty()) uv.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        HIPCHECK(hipMalloc(&R().dTexGeom, tg.size() * sizeof(ptd::TexGeom)));
+        HIPCHECK(hipMemcpy(R().dTexGeom, tg.data(), tg.size() * sizeof(ptd::TexGeom), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc(&R().dTexDesc, desc.size() * sizeof(int4)));
+        HIPCHECK(hipMemcpy(R().dTexDesc, desc.data(), desc.size() * sizeof(int4), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc(&R().dTexels, texels.size() * sizeof(float4)));
+        HIPCHECK(hipMemcpy(R().dTexels, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc(&R().dTexUV, uv.size() * sizeof(float4)));
+        HIPCHECK(hipMemcpy(R().dTexUV, uv.data(), uv.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
     if (R().mesh) {
         HIPCHECK(hipMalloc(&R().dMeshRecs, (meshRecs.size() + 4) * sizeof(ptd::MeshUnit)));     // (+ 4: a walk may read the record behind the last one)
         HIPCHECK(hipMemcpy(R().dMeshRecs, meshRecs.data(), meshRecs.size() * sizeof(ptd::MeshUnit), hipMemcpyHostToDevice));
@@ -1102,7 +1228,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         std::vector<SphereCull> groups;
         {
             const char *ge = getenv("PT_AMD_GROUPS");
-            R().grouped = meshRecs.empty() && (ge ? atoi(ge) != 0 : nswept >= kGroupedMin);
+            // (textured scenes never: the grouped sweep is the ungrouped one's result, bit for bit, and the TEX forms leave it out)
+            R().grouped = meshRecs.empty() && !R().tex && (ge ? atoi(ge) != 0 : nswept >= kGroupedMin);
             if (R().grouped) {
                 int n0 = k.sphN0;
                 const double ob = scene_origin_bound(geoms, ngeoms, hg);

@@ -970,9 +970,10 @@ __device__ __forceinline__ float meshIntersectionTest(const GD &g, const float4 
 // What a walk's WINNER -- triangle record `best` -- means for the ray: the outputs of meshIntersectionTest, from the triangle alone.  The
 // render kernels' walks run ahead of the bounce, in a kernel of their own (pt_mesh_walk.h), and leave the winner's unit per path; the bounce
 // evaluates it here: t, and (u, v) for the vertex normals, are the triangle test's, evaluated once more (same operands, same bits).
-template <bool CAM_ORIGIN = false, typename GD>
+// BARY (textured scenes): the hit's barycentric (u, v) into *bary as well, whether the triangle has vertex normals or not.
+template <bool CAM_ORIGIN = false, bool BARY = false, typename GD>
 __device__ __forceinline__ float meshWinner(const GD &g, const float4 *recs, uint32_t best, bool front, F3 ro_w, F3 rd_w, F3 &P, F3 &nsrc,
-                                            bool &outside, int &faceMat) {
+                                            bool &outside, int &faceMat, float2 *bary = nullptr) {
     const F3 ro = CAM_ORIGIN ? f3(g.camObj[0], g.camObj[1], g.camObj[2]) : mulMV(g.inv, ro_w, 1.0f);
     const F3 rd = normalize(mulMV0(g.inv, g.invZ, rd_w));
     const float4 a = recs[(size_t)best], b = recs[(size_t)best + 1], c = recs[(size_t)best + 2];
@@ -987,6 +988,7 @@ __device__ __forceinline__ float meshWinner(const GD &g, const float4 *recs, uin
     const F3 sv = ro - w0;
     const F3 q = cross(sv, e1);
     const float tbest = f * dot(e2, q);
+    if (BARY) *bary = make_float2(f * dot(sv, p), f * dot(rd, q));
     if (nref != 0u) {
         const float u = f * dot(sv, p);
         const float v = f * dot(rd, q);
@@ -1040,6 +1042,104 @@ __device__ __forceinline__ F3 hitNormal(const GeomDev &g, F3 nsrc, bool outside)
     const int face = cubeFace(nsrc, ok);
     return cubeFrameVector(g.cubeFrame, face, 0, ok);
 }
+
+// ---- texture mapping (PBRT 10.4; the reference names it among its README extras and holds no texture code, so the semantics are
+// build-defined).  A texture is bound to a primitive and multiplies its material's colour (RGB) where the kernel forms it: the diffuse
+// albedo and the emitted radiance alike.  No random number is drawn and no path changes its course.  Every fp32 operation below is one IEEE
+// operation (-ffp-contract=off), in the order written, so that tests/test_textures_cpu.py restates it in numpy bit for bit:
+//   sample(u, v)  u, v non-finite -> 0; u -= floor(u), v -= floor(v) (repeat); x = u * W - 0.5, y = (1 - v) * H - 0.5 (row 0 = the
+//                 image's top row, v = 0 its bottom: the OBJ convention); x0 = floor(x), fx = x - x0, x0 < 0 -> x0 + W, x1 = x0 + 1,
+//                 x1 == W -> 0 (same for y); top = a + (b - a) * fx, bottom = c + (d - c) * fx along x in rows y0 and y1, then
+//                 top + (bottom - top) * fy.  A constant texture returns its colour exactly; no input leaves the texture.
+//   mesh          uv = (uv0 * w + uv1 * u) + uv2 * v, w = (1 - u) - v: the winner's barycentrics, as the vertex-normal blend
+//   cube          the hit face's axis a (cubeFace): u = q[(a + 1) % 3] + 0.5, v = q[(a + 2) % 3] + 0.5
+//   sphere        d = normalize(q); u = 0.5 + atan2Poly(d.z, d.x) * (1 / 2pi), v = 0.5 + asinPoly(d.y) * (1 / pi)
+// q is the object-space hit point: the sphere test's own (nsrc), for a cube inverseTransform * (P, 1) of the world-space hit point.
+constexpr float kInvTwoPi = 0.15915493667125701904296875f, kInvPi = 0.3183098733425140380859375f, kHalfPi = 1.57079637050628662109375f,
+                kQuarterPi = 0.785398185253143310546875f, kPiF = 3.1415927410125732421875f;
+// atan on [0, 1] (cephes atanf: one reduction at tan(pi / 8), then its degree-9 odd polynomial)
+__device__ __forceinline__ float atan01Poly(float t) {
+    const bool big = t > 0.4142135623730950f;
+    const float x = big ? (t - 1.0f) / (t + 1.0f) : t;
+    const float z = x * x;
+    float p = 8.05374449538e-2f;
+    p = p * z - 1.38776856032e-1f;
+    p = p * z + 1.99777106478e-1f;
+    p = p * z - 3.33329491539e-1f;
+    const float r = (p * z) * x + x;
+    return big ? kQuarterPi + r : r;
+}
+// atan2(y, x) from atan01Poly of min / max (0 for y = x = 0)
+__device__ __forceinline__ float atan2Poly(float y, float x) {
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+    const bool steep = ay > ax;
+    const float mx = steep ? ay : ax, mn = steep ? ax : ay;
+    const float t = mx > 0.0f ? mn / mx : 0.0f;
+    float r = atan01Poly(t);
+    r = steep ? kHalfPi - r : r;
+    r = x < 0.0f ? kPiF - r : r;
+    return y < 0.0f ? -r : r;
+}
+// asin (cephes asinf: |x| > 0.5 through asin(x) = pi / 2 - 2 asin(sqrt((1 - x) / 2))); |x| is clamped to 1
+__device__ __forceinline__ float asinPoly(float x) {
+    float a = __builtin_fabsf(x);
+    a = a > 1.0f ? 1.0f : a;
+    const bool big = a > 0.5f;
+    const float z = big ? 0.5f * (1.0f - a) : a * a;
+    const float s = big ? __builtin_sqrtf(z) : a;
+    float p = 4.2163199048e-2f;
+    p = p * z + 2.4181311049e-2f;
+    p = p * z + 4.5470025998e-2f;
+    p = p * z + 7.4953002686e-2f;
+    p = p * z + 1.6666752422e-1f;
+    const float r0 = (p * z) * s + s;
+    const float r = big ? kHalfPi - 2.0f * r0 : r0;
+    return x < 0.0f ? -r : r;
+}
+__device__ __forceinline__ void sphereUV(F3 q, float &u, float &v) {
+    const F3 d = normalize(q);
+    u = 0.5f + atan2Poly(d.z, d.x) * kInvTwoPi;
+    v = 0.5f + asinPoly(d.y) * kInvPi;
+}
+__device__ __forceinline__ void cubeUV(F3 q, int face, float &u, float &v) {
+    const int a = face >> 1;
+    const float qs[3] = {q.x, q.y, q.z};
+    u = qs[a == 2 ? 0 : a + 1] + 0.5f;
+    v = qs[a == 0 ? 2 : a - 1] + 0.5f;
+}
+// uv = the triangle's corner UVs {u0, v0, u1, v1, u2, v2}
+__device__ __forceinline__ void meshUV(float4 c01, float2 c2, float bu, float bv, float &u, float &v) {
+    const float w = (1.0f - bu) - bv;
+    u = (c01.x * w + c01.z * bu) + c2.x * bv;
+    v = (c01.y * w + c01.w * bu) + c2.y * bv;
+}
+// one texture of `texels` (one float4 per texel, rows top to bottom) at texel offset `off`, W x H
+__device__ __forceinline__ F3 textureSample(const float4 *texels, int off, int W, int H, float u, float v) {
+    u = __builtin_isfinite(u) ? u : 0.0f;
+    v = __builtin_isfinite(v) ? v : 0.0f;
+    u = u - __builtin_floorf(u);
+    v = v - __builtin_floorf(v);
+    const float x = u * (float)W - 0.5f, y = (1.0f - v) * (float)H - 0.5f;
+    const float xf0 = __builtin_floorf(x), yf0 = __builtin_floorf(y);
+    const float fx = x - xf0, fy = y - yf0;
+    int x0 = (int)xf0, y0 = (int)yf0;
+    x0 = x0 < 0 ? x0 + W : (x0 >= W ? W - 1 : x0);      // (x lies in [-0.5, W - 0.5]: the second arm never runs, it bounds the index)
+    y0 = y0 < 0 ? y0 + H : (y0 >= H ? H - 1 : y0);
+    x0 = x0 < 0 ? 0 : x0;
+    y0 = y0 < 0 ? 0 : y0;
+    const int x1 = x0 + 1 == W ? 0 : x0 + 1, y1 = y0 + 1 == H ? 0 : y0 + 1;
+    const float4 *r0 = texels + off + (size_t)y0 * W, *r1 = texels + off + (size_t)y1 * W;
+    const float4 a = r0[x0], b = r0[x1], c = r1[x0], d = r1[x1];
+    const F3 top = f3(a.x + (b.x - a.x) * fx, a.y + (b.y - a.y) * fx, a.z + (b.z - a.z) * fx);
+    const F3 bot = f3(c.x + (d.x - c.x) * fx, c.y + (d.y - c.y) * fx, c.z + (d.z - c.z) * fx);
+    return f3(top.x + (bot.x - top.x) * fy, top.y + (bot.y - top.y) * fy, top.z + (bot.z - top.z) * fy);
+}
+// per-primitive binding (k_bounce<..., TEX>): texture (-1: none), kind (0 sphere, 1 cube, 2 mesh), the mesh's first row of
+// BounceArgs::texUV and the unit of its first triangle record
+struct TexGeom {
+    int tex, kind, uvBase, triBase;
+};
+static_assert(sizeof(TexGeom) == 16, "one dwordx4");
 
 // Per-geom record staged in LDS for the per-lane lookups that follow the nearest-hit loop: the sphere's normal matrix
 // (12 floats), the material index, the type and the cube's six face frames.  Lanes of a wave index different geoms, so

@@ -468,6 +468,18 @@ int pt_group_set_meshes(PtGroup *g, const PtMesh *meshes, int nmeshes) {
     return PT_OK;
 }
 
+int pt_group_set_textures(PtGroup *g, const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings,
+                          int nbindings, size_t binding_struct_bytes) {
+    if (!g) return fail(PT_ERR_INVALID, "pt_group_set_textures: null group");
+    CurrentGuard guard;
+    for (PtContext *c : g->ctx) {
+        t_ctx = &c->st;
+        int rc = pt_set_textures(textures, ntextures, texture_struct_bytes, bindings, nbindings, binding_struct_bytes);
+        if (rc) return rc;
+    }
+    return PT_OK;
+}
+
 int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
                   const PtOptions *opts) {
     if (!g || !cam) return fail(PT_ERR_INVALID, "pt_group_init: null argument");

@@ -907,3 +907,38 @@ int pt_test_reflect_refract(const float *I3, const float *N3, const float *eta, 
     return PT_OK;
 }
 
+int pt_test_texture_sample(const float *rgb, int w, int h, const float *uv2, int n, float *rgb_out3) {
+    NEED_GPU();
+    if (w < 1 || h < 1 || w > kTexSizeMax || h > kTexSizeMax || !rgb || n < 0 || (n && (!uv2 || !rgb_out3)))
+        return fail(PT_ERR_INVALID, "pt_test_texture_sample: bad argument");
+    if (n == 0) return PT_OK;
+    std::vector<float4> tx((size_t)w * h);
+    for (size_t q = 0; q < tx.size(); ++q) tx[q] = make_float4(rgb[3 * q], rgb[3 * q + 1], rgb[3 * q + 2], 0.0f);
+    DevBuf<float4> t;
+    DevBuf<float> a, o;
+    UP(t, tx.data(), tx.size());
+    UP(a, uv2, (size_t)n * 2);
+    int rc = o.alloc((size_t)n * 3); if (rc) return rc;
+    hipLaunchKernelGGL(k_test_texture_sample, GRID(n), t.p, w, h, a.p, n, o.p);
+    HIPCHECK(hipDeviceSynchronize());
+    DOWN(rgb_out3, o, (size_t)n * 3);
+    return PT_OK;
+}
+
+int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, float *uv_out2) {
+    NEED_GPU();
+    if (kind < 0 || kind > 2 || n < 0 || (n && (!in || !uv_out2 || (kind == 1 && !face)))) return fail(PT_ERR_INVALID, "pt_test_texture_uv: bad argument");
+    if (n == 0) return PT_OK;
+    if (kind == 1)
+        for (int i = 0; i < n; ++i)
+            if (face[i] < 0 || face[i] > 5) return fail(PT_ERR_INVALID, "pt_test_texture_uv: face %d", face[i]);
+    DevBuf<float> a, o;
+    DevBuf<int> f;
+    UP(a, in, (size_t)n * (kind == 2 ? 8 : 3));
+    if (kind == 1) UP(f, face, n);
+    int rc = o.alloc((size_t)n * 2); if (rc) return rc;
+    hipLaunchKernelGGL(k_test_texture_uv, GRID(n), kind, a.p, f.p, n, o.p);
+    HIPCHECK(hipDeviceSynchronize());
+    DOWN(uv_out2, o, (size_t)n * 2);
+    return PT_OK;
+}

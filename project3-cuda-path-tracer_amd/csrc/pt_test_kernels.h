@@ -787,6 +787,26 @@ __global__ void k_test_sincos(const float *x, int n, float *s, float *c) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) sincosPoly(x[i], s[i], c[i]);
 }
+__global__ void k_test_texture_sample(const float4 *texels, int w, int h, const float *uv, int n, float *out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const F3 c = textureSample(texels, 0, w, h, uv[2 * i], uv[2 * i + 1]);
+    out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
+}
+__global__ void k_test_texture_uv(int kind, const float *in, const int *face, int n, float *out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float u, v;
+    if (kind == 2) {
+        const float *e = in + 8 * (size_t)i;
+        meshUV(make_float4(e[2], e[3], e[4], e[5]), make_float2(e[6], e[7]), e[0], e[1], u, v);
+    } else {
+        const F3 q = f3(in[3 * i], in[3 * i + 1], in[3 * i + 2]);
+        if (kind == 1) cubeUV(q, face[i], u, v);
+        else sphereUV(q, u, v);
+    }
+    out[2 * i] = u; out[2 * i + 1] = v;
+}
 __global__ void k_test_reflect_refract(const float *I, const float *N, const float *eta, int n, float *rl, float *rr) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

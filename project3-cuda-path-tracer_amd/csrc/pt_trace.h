@@ -441,6 +441,13 @@ struct BounceArgs {
     const float4 *walkMeshRows;
     int walkMeshLds;
     const SphereCull *sphGroups;        // scenes of hundreds of swept primitives: the groups' bounding balls (KParams::nSphGroups), or nullptr
+    // ---- textured scenes (k_bounce<..., TEX>; nullptr otherwise): per primitive its ptd::TexGeom, per texture {first texel, W, H, 0}, every
+    // texture's texels (one float4 each, rows top to bottom, textures one after another), per mesh triangle its corner UVs as two float4
+    // {u0, v0, u1, v1}, {u2, v2, 0, 0} (row TexGeom::uvBase + the triangle's ordinal)
+    const ptd::TexGeom *texGeom;
+    const int4 *texDesc;
+    const float4 *texels;
+    const float4 *texUV;
 };
 typedef const PT_CAS BounceArgs *ArgsPtr;
 typedef const PT_CAS GeomDev *GeomPtr;
@@ -485,7 +492,10 @@ static_assert(sizeof(CullGroup) == 32 && offsetof(GeomDev, cullFlags) - offsetof
 // then per LANE the members of the groups its ray may reach), and neither hit records nor matrix rows nor face frames are staged in LDS,
 // in the camera-ray bounce either (518 primitives' records left it three workgroups per CU): instantiations of their own, so that the
 // 64-sphere configuration runs the code it ran before.
-template <bool FIRST, bool MANY, bool DOF = false, bool MESH = false, bool PLAIN = false, bool CUBES = false, bool GROUPS = false>
+// TEX: a texture is bound to at least one primitive -- the hit's texel scales its material's colour (ptd::textureSample; pt_init picks
+// these instantiations for textured scenes only, never with PLAIN or GROUPS, so that an untextured scene runs exactly the code it ran before).
+// Their later bounces of scenes that are not sphere-heavy run one workgroup per CU fewer: the sampler's registers would otherwise spill.
+template <bool FIRST, bool MANY, bool DOF = false, bool MESH = false, bool PLAIN = false, bool CUBES = false, bool GROUPS = false, bool TEX = false>
 #ifndef PT_MESH_WG_FIRST
 #define PT_MESH_WG_FIRST 7
 #define PT_MESH_WG_NEXT 7
@@ -496,10 +506,11 @@ template <bool FIRST, bool MANY, bool DOF = false, bool MESH = false, bool PLAIN
 #ifndef PT_CUBES_WG
 #define PT_CUBES_WG 4
 #endif
-__global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG) : (MESH ? (MANY ? 4 : (FIRST ? PT_MESH_WG_FIRST : PT_MESH_WG_NEXT)) : (DOF ? 5 : (MANY ? (FIRST ? 7 : (GROUPS ? PT_GROUPS_WG : 6)) : 8)))) void k_bounce(BounceArgs argsByValue) {
+__global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG) : (MESH ? (MANY ? 4 : (FIRST ? PT_MESH_WG_FIRST : PT_MESH_WG_NEXT)) : (DOF ? 5 : (MANY ? (FIRST ? 7 : (GROUPS ? PT_GROUPS_WG : 6)) : 8))) - ((TEX && !MANY && !FIRST) ? 1 : 0)) void k_bounce(BounceArgs argsByValue) {
     static_assert(MANY || !CUBES, "swept cubes only exist where primitives are swept");
     static_assert(!GROUPS || (MANY && !MESH && !DOF), "groups: sphere-heavy scenes without meshes (the camera-ray bounce: its pinhole form)");
     static_assert(FIRST || !DOF, "the lens only concerns the camera-ray bounce");
+    static_assert(!TEX || (!PLAIN && !GROUPS && (!MANY || CUBES)), "textured scenes: the general forms (MANY: the one that sweeps both types)");
     (void)argsByValue;
     const ArgsPtr kargs = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     censusEnter();                       // (instrumented build only)
@@ -962,6 +973,9 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
             // (an int, not a bool: a loop-carried per-lane flag would live in an SGPR pair and cost three mask operations at
             // every merge point of the loop over the primitives; as a VGPR it costs one select per update)
             int outsideI = __float_as_int(anyFloat());
+            // TEX with MESH: the mesh winner's barycentrics and triangle record (the texture coordinates are blended after the loop)
+            float2 texBary = make_float2(0.0f, 0.0f);
+            uint32_t texUnit = 0u;
             const float dd = dot(dir, dir);
             int nCand = 0;                                       // MANY: spheres recorded by this lane
             float *s_sph = nullptr;                              // MANY: [ngeoms][kSphRowFloats], then [kListMax][kBlock] lists
@@ -1068,6 +1082,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     bool o = false;
                     int fm = 0;                                      // MESH: 1 + the material of the face that was hit, if it has its own
                     float t = -1.0f;
+                    float2 bary = make_float2(0.0f, 0.0f);           // (TEX: a mesh hit's barycentrics)
+                    uint32_t unitHit = 0u;
                     // camera rays: only the lanes whose pixel lies in the primitive's rectangle take the test.  A predicate and a
                     // wave-uniform skip, not a per-lane `continue`: the loop over the primitives stays a scalar loop
                     bool inRect = true;
@@ -1089,8 +1105,10 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         const ArgsPtr A2 = launder(kargs);
                         const unsigned long long rec = A2->meshHit[FIRST ? recIdx0 + tid : nextMeta.idx];
                         const uint32_t unit = (uint32_t)rec >> 1;
-                        if (rec != ~0ull && unit >= G.meshUnit0 && unit < G.meshUnit1)
-                            t = meshWinner<FIRST && !DOF>(G, A2->meshRecs, unit, ((uint32_t)rec & 1u) != 0u, org, dir, p, n, o, fm);
+                        if (rec != ~0ull && unit >= G.meshUnit0 && unit < G.meshUnit1) {
+                            t = meshWinner<FIRST && !DOF, TEX>(G, A2->meshRecs, unit, ((uint32_t)rec & 1u) != 0u, org, dir, p, n, o, fm, TEX ? &bary : nullptr);
+                            if (TEX) unitHit = unit;
+                        }
                     } else if (!PACKED && ((flags & 1) == 0 || (MANY && (flags & 64) != 0))) {    // (PACKED: no swept primitive comes this way)
                         probe(3);
                         // a sphere -- or, in a scene with many small primitives, a small cube (flag bit 6): the bounding ball first;
@@ -1114,6 +1132,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     if (t > 0.0f && (hit < 0 || t < tbest || (PACKED && t == tbest && g < hit))) {
                         // (bit 0: the hit is on the outside; MESH: the bits above it carry the face's own material, 1 + its index)
                         tbest = t; hit = g; P = p; nsrc = n; outsideI = (o ? 1 : 0) | (MESH ? fm << 1 : 0);
+                        if (TEX && MESH) { texBary = bary; texUnit = unitHit; }
                     }
                 }
             }
@@ -1476,6 +1495,26 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         ghMaterial = faceMat - 1;
                         const MaterialDev &Mf = smats[ghMaterial];
                         mcol = f3(Mf.color[0], Mf.color[1], Mf.color[2]);
+                    }
+                }
+                if (TEX) {
+                    // a bound texture scales the material's colour: the albedo and the emitted radiance (ptd::textureSample)
+                    const ArgsPtr A = launder(kargs);
+                    const int4 tg = *reinterpret_cast<const int4 *>(A->texGeom + hit);   // TexGeom {tex, kind, uvBase, triBase}
+                    if (tg.x >= 0) {
+                        float u, v;
+                        if (MESH && tg.y == 2) {
+                            const size_t row = (size_t)tg.z + (texUnit - (uint32_t)tg.w) / (uint32_t)kMeshTriUnits;
+                            const float4 c01 = A->texUV[2 * row], c2 = A->texUV[2 * row + 1];
+                            meshUV(c01, make_float2(c2.x, c2.y), texBary.x, texBary.y, u, v);
+                        } else if (tg.y == 1) {
+                            const F3 q = mulMV(A->ggeoms[hit].inv, P, 1.0f);
+                            cubeUV(q, faceOk ? face : 0, u, v);
+                        } else {
+                            sphereUV(nsrc, u, v);
+                        }
+                        const int4 td = A->texDesc[tg.x];                         // {first texel, W, H, 0}
+                        mcol = mcol * textureSample(A->texels, td.x, td.y, td.z, u, v);
                     }
                 }
                 const MaterialDev &M = smats[ghMaterial];       // (the fields of the rarer branches)

@@ -37,6 +37,18 @@ const int *pth_scene_mesh_materials(void *s, int i) {
     const Mesh &m = static_cast<Scene *>(s)->meshes[i];
     return m.mats.empty() ? NULL : m.mats.data();
 }
+// texture coordinates (ntris x 6) of mesh i, or NULL when the OBJ gave none
+const float *pth_scene_mesh_uvs(void *s, int i) {
+    const Mesh &m = static_cast<Scene *>(s)->meshes[i];
+    return m.uvs.empty() ? NULL : m.uvs.data();
+}
+// image textures (`TEXTURE <file>`): width x height x 3 floats each, row 0 = top; per geom the index of its texture or -1
+int pth_scene_num_textures(void *s) { return (int)static_cast<Scene *>(s)->textures.size(); }
+int pth_scene_texture_width(void *s, int i) { return static_cast<Scene *>(s)->textures[i].width; }
+int pth_scene_texture_height(void *s, int i) { return static_cast<Scene *>(s)->textures[i].height; }
+const float *pth_scene_texture_rgb(void *s, int i) { return static_cast<Scene *>(s)->textures[i].rgb.data(); }
+const char *pth_scene_texture_path(void *s, int i) { return static_cast<Scene *>(s)->textures[i].path.c_str(); }
+int pth_scene_geom_texture(void *s, int g) { return static_cast<Scene *>(s)->geomTextures[g]; }
 void pth_scene_set_resolution(void *s, int w, int h) { static_cast<Scene *>(s)->setResolution(w, h); }
 
 // saveImage (reference src/main.cpp:49-70) on a W*H*3 running sum: /samples, X mirror, PNG

@@ -66,6 +66,32 @@ void pathtraceInit(Scene *scene) {
         meshes.push_back(m);
     }
 #endif
+    // `TEXTURE <file>` lines: the scene's textures, and per textured object its binding (a mesh's with its corner UVs)
+    std::vector<PtTexture> textures;
+    std::vector<PtTexBinding> bindings;
+#ifdef PT_SCENE_HAS_TEXTURES
+    for (size_t i = 0; i < scene->textures.size(); ++i) {
+        PtTexture t;
+        t.width = scene->textures[i].width;
+        t.height = scene->textures[i].height;
+        t.rgb = scene->textures[i].rgb.data();
+        textures.push_back(t);
+    }
+    for (size_t g = 0; g < scene->geomTextures.size(); ++g) {
+        if (scene->geomTextures[g] < 0) continue;
+        PtTexBinding b;
+        b.geom = (int)g;
+        b.texture = scene->geomTextures[g];
+        b.ntris = 0;
+        b.uvs = NULL;
+        for (size_t i = 0; i < scene->meshes.size(); ++i)
+            if (scene->meshes[i].geom == (int)g) {
+                b.ntris = (int)(scene->meshes[i].tris.size() / 9);
+                b.uvs = scene->meshes[i].uvs.empty() ? NULL : scene->meshes[i].uvs.data();
+            }
+        bindings.push_back(b);
+    }
+#endif
     int members = 1;
     if (const char *e = getenv("PT_AMD_DEVICES")) members = atoi(e);
     if (members >= 2) {
@@ -75,8 +101,12 @@ void pathtraceInit(Scene *scene) {
         }
         if (!group) checkPtError(pt_group_create(&group, members, NULL), "pathtraceInit (PT_AMD_DEVICES)");
         checkPtError(pt_group_set_meshes(group, meshes.empty() ? NULL : meshes.data(), (int)meshes.size()), "pathtraceInit");
+        checkPtError(pt_group_set_textures(group, textures.empty() ? NULL : textures.data(), (int)textures.size(), sizeof(PtTexture),
+                                           bindings.empty() ? NULL : bindings.data(), (int)bindings.size(), sizeof(PtTexBinding)), "pathtraceInit");
     } else {
         checkPtError(pt_set_meshes_sized(meshes.empty() ? NULL : meshes.data(), (int)meshes.size(), sizeof(PtMesh)), "pathtraceInit");
+        checkPtError(pt_set_textures(textures.empty() ? NULL : textures.data(), (int)textures.size(), sizeof(PtTexture),
+                                     bindings.empty() ? NULL : bindings.data(), (int)bindings.size(), sizeof(PtTexBinding)), "pathtraceInit");
     }
     int status;
     for (;;) {

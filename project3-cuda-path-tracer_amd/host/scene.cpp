@@ -6,9 +6,13 @@
 //     `mesh <file.obj>` (path relative to the scene file) loads a Wavefront OBJ into Scene::meshes (loadObj below)
 //   * the specular exponent keyword is SPECEX (:164) although the README says SPECX
 //   * CRLF / CR / LF line ends; '//' comment lines are simply unknown keywords
+//   * `TEXTURE <file>` in an OBJECT block (next to TRANS / ROTAT / SCALE; path relative to the scene file) binds an image texture to the
+//     object (loadTexture); the reference's loader skips the unknown keyword, so a textured scene still loads there, untextured
 // Unlike the reference, fields whose keyword is missing are zero instead of uninitialised.
 #include "scene.h"
 
+#include <cctype>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -28,13 +32,15 @@ lin::vec3 triple(const Tokens &t) { return lin::vec3(num(t, 1), num(t, 2), num(t
 // to the vertices read so far); polygons are fanned from their first vertex.  `vn x y z` + the third field of a face corner give
 // vertex normals: kept only when EVERY corner of EVERY face names one (else the mesh is shaded flat).  `usemtl <k>` (k an integer
 // = a MATERIAL of the scene file) gives the faces that follow a material of their own; any other name returns to the object's.
+// `vt u v` + the second field of a face corner give texture coordinates, kept by the same all-or-nothing rule as the normals.
 // Every other statement is ignored.
-bool loadObj(const std::string &path, std::vector<float> &tris, std::vector<float> &normalsOut, std::vector<int> &matsOut) {
+bool loadObj(const std::string &path, std::vector<float> &tris, std::vector<float> &normalsOut, std::vector<int> &matsOut,
+             std::vector<float> &uvsOut) {
     std::ifstream fp(path.c_str());
     if (!fp.is_open()) return false;
-    std::vector<float> verts, vnorm, normals;
+    std::vector<float> verts, vnorm, normals, vtex, uvs;
     std::vector<int> mats;
-    bool allNormals = true, anyMat = false;
+    bool allNormals = true, anyMat = false, allUvs = true;
     int curMat = -1;
     std::string line;
     while (std::getline(fp, line)) {
@@ -46,6 +52,10 @@ bool loadObj(const std::string &path, std::vector<float> &tris, std::vector<floa
             ss >> c[0] >> c[1] >> c[2];
             std::vector<float> &dst = keyword == "v" ? verts : vnorm;
             for (int a = 0; a < 3; ++a) dst.push_back((float)c[a]);
+        } else if (keyword == "vt") {
+            double c[2] = {0, 0};
+            ss >> c[0] >> c[1];
+            for (int a = 0; a < 2; ++a) vtex.push_back((float)c[a]);
         } else if (keyword == "usemtl") {
             std::string tok;
             curMat = -1;
@@ -55,8 +65,8 @@ bool loadObj(const std::string &path, std::vector<float> &tris, std::vector<floa
                 if (end && *end == 0 && k >= 0 && k < 1000000) curMat = (int)k;
             }
         } else if (keyword == "f") {
-            const int nv = (int)(verts.size() / 3), nn = (int)(vnorm.size() / 3);
-            std::vector<int> corner, ncorner;
+            const int nv = (int)(verts.size() / 3), nn = (int)(vnorm.size() / 3), nt = (int)(vtex.size() / 2);
+            std::vector<int> corner, ncorner, tcorner;
             std::string ref;
             bool ok = true;
             while (ss >> ref) {
@@ -73,10 +83,21 @@ bool loadObj(const std::string &path, std::vector<float> &tris, std::vector<floa
                     if (j != 0 && q >= 0 && q < nn) nk = q;
                 }
                 ncorner.push_back(nk);
+                int tk = -1;                                   // the texture coordinate: the field between the two '/'
+                if (s1 != std::string::npos && s1 + 1 < ref.size() && ref[s1 + 1] != '/') {
+                    const int j = atoi(ref.c_str() + s1 + 1);
+                    const int q = j > 0 ? j - 1 : nt + j;
+                    if (j != 0 && q >= 0 && q < nt) tk = q;
+                }
+                tcorner.push_back(tk);
             }
             for (size_t k = 2; ok && k < corner.size(); ++k) {
                 const int tri[3] = {corner[0], corner[k - 1], corner[k]};
                 const int ntri[3] = {ncorner[0], ncorner[k - 1], ncorner[k]};
+                const int ttri[3] = {tcorner[0], tcorner[k - 1], tcorner[k]};
+                for (int c = 0; c < 3; ++c)
+                    for (int a = 0; a < 2; ++a) uvs.push_back(ttri[c] >= 0 ? vtex[2 * (size_t)ttri[c] + a] : 0.0f);
+                if (ttri[0] < 0 || ttri[1] < 0 || ttri[2] < 0) allUvs = false;
                 for (int c = 0; c < 3; ++c)
                     for (int a = 0; a < 3; ++a) {
                         tris.push_back(verts[3 * (size_t)tri[c] + a]);
@@ -90,9 +111,89 @@ bool loadObj(const std::string &path, std::vector<float> &tris, std::vector<floa
     }
     if (allNormals && !tris.empty()) normalsOut = normals; else normalsOut.clear();
     if (anyMat) matsOut = mats; else matsOut.clear();
+    if (allUvs && !tris.empty()) uvsOut = uvs; else uvsOut.clear();
     return true;
 }
 
+// PPM / PFM header tokens: whitespace-separated, '#' starts a comment up to the line's end (PPM)
+bool headerToken(std::istream &in, std::string &tok) {
+    tok.clear();
+    int c;
+    while ((c = in.get()) != EOF) {
+        if (c == '#' && tok.empty()) {
+            while ((c = in.get()) != EOF && c != '\n' && c != '\r') {}
+            continue;
+        }
+        if (isspace(c)) {
+            if (!tok.empty()) return true;
+            continue;
+        }
+        tok.push_back((char)c);
+    }
+    return !tok.empty();
+}
+int headerInt(std::istream &in) {
+    std::string t;
+    if (!headerToken(in, t)) return -1;
+    char *end = nullptr;
+    const long v = strtol(t.c_str(), &end, 10);
+    return (end && *end == 0 && v >= 0 && v <= (1l << 30)) ? (int)v : -1;
+}
+
+}  // namespace
+
+Texture loadTexture(const std::string &path) {
+    std::ifstream in(path.c_str(), std::ios::binary);
+    if (!in.is_open()) throw std::runtime_error("cannot read texture " + path);
+    std::string magic;
+    headerToken(in, magic);
+    Texture t;
+    t.path = path;
+    const bool ppm = magic == "P3" || magic == "P6", pfm = magic == "PF" || magic == "Pf";
+    if (!ppm && !pfm) throw std::runtime_error("texture " + path + ": not a PPM (P3 / P6) or PFM (PF / Pf) file");
+    t.width = headerInt(in);
+    t.height = headerInt(in);
+    if (t.width < 1 || t.height < 1 || (long long)t.width * t.height > (1ll << 28))
+        throw std::runtime_error("texture " + path + ": bad size");
+    const size_t n = (size_t)t.width * t.height;
+    t.rgb.resize(3 * n);
+    if (ppm) {
+        if (headerInt(in) != 255) throw std::runtime_error("texture " + path + ": only 8-bit PPM (maxval 255) is read");
+        for (size_t i = 0; i < 3 * n; ++i) {
+            int b;
+            if (magic == "P6") {
+                b = in.get();                                    // (the header's single whitespace byte was consumed with maxval)
+                if (b == EOF) throw std::runtime_error("texture " + path + ": truncated");
+            } else {
+                b = headerInt(in);
+                if (b < 0 || b > 255) throw std::runtime_error("texture " + path + ": bad sample");
+            }
+            t.rgb[i] = (float)b / 255.0f;
+        }
+    } else {
+        std::string scale;
+        if (!headerToken(in, scale)) throw std::runtime_error("texture " + path + ": truncated");
+        const bool little = atof(scale.c_str()) < 0.0;           // (PFM: a negative scale = little-endian samples)
+        const int ch = magic == "PF" ? 3 : 1;
+        std::vector<unsigned char> raw(4 * (size_t)ch * n);
+        if (!in.read(reinterpret_cast<char *>(raw.data()), (std::streamsize)raw.size())) throw std::runtime_error("texture " + path + ": truncated");
+        for (size_t i = 0; i < (size_t)ch * n; ++i) {
+            const unsigned char *b = raw.data() + 4 * i;
+            const uint32_t w = little ? (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24
+                                      : (uint32_t)b[3] | (uint32_t)b[2] << 8 | (uint32_t)b[1] << 16 | (uint32_t)b[0] << 24;
+            float f;
+            memcpy(&f, &w, 4);
+            // PFM stores its rows bottom to top: sample i of file row r is texel row height - 1 - r
+            const size_t px = i / ch, r = px / t.width, x = px % t.width;
+            const size_t dst = ((size_t)(t.height - 1 - r) * t.width + x) * 3;
+            if (ch == 3) t.rgb[dst + i % 3] = f;
+            else t.rgb[dst] = t.rgb[dst + 1] = t.rgb[dst + 2] = f;     // (Pf: one grey sample per texel)
+        }
+    }
+    return t;
+}
+
+namespace {
 void deriveFov(Camera &camera, float fovy) {
     // reference src/scene.cpp:133-136
     float yscaled = std::tan(fovy * (PI / 180));
@@ -143,6 +244,13 @@ Scene::Scene(std::string filename, bool verbose_) : verbose(verbose_) {
             std::cout << "WARNING: mesh of object " << meshes[i].geom << ": " << bad << " faces name a material (usemtl <k>) the scene has "
                       << "not (" << materials.size() << " MATERIAL blocks): they take the object's material" << std::endl;
     }
+    // a textured mesh needs texture coordinates on every corner (`vt`): without them the scene cannot be rendered
+    geomTextures.resize(geoms.size(), -1);
+    for (size_t i = 0; i < meshes.size(); ++i)
+        if (geomTextures[meshes[i].geom] >= 0 && meshes[i].uvs.empty()) {
+            std::cout << "ERROR: object " << meshes[i].geom << " is textured and its mesh has no texture coordinates - aborting!" << std::endl;
+            throw std::runtime_error("textured mesh without texture coordinates");
+        }
 }
 
 Scene::~Scene() {}
@@ -223,7 +331,7 @@ int Scene::loadGeom(std::string objectid) {
                 Mesh m;
                 m.geom = (int)geoms.size();
                 const std::string path = t[1][0] == '/' ? t[1] : dir + t[1];
-                if (loadObj(path, m.tris, m.normals, m.mats) && !m.tris.empty()) {
+                if (loadObj(path, m.tris, m.normals, m.mats, m.uvs) && !m.tris.empty()) {
                     if (verbose) std::cout << "Creating new mesh (" << m.tris.size() / 9 << " triangles)..." << std::endl;
                     g.type = MESH;
                     meshes.push_back(m);
@@ -247,6 +355,24 @@ int Scene::loadGeom(std::string objectid) {
         if (key(t, "TRANS")) g.translation = triple(t);
         else if (key(t, "ROTAT")) g.rotation = triple(t);
         else if (key(t, "SCALE")) g.scale = triple(t);
+        else if (key(t, "TEXTURE") && t.size() >= 2) {
+            const std::string path = t[1][0] == '/' ? t[1] : dir + t[1];
+            int k = -1;
+            for (size_t j = 0; j < textures.size(); ++j)
+                if (textures[j].path == path) k = (int)j;
+            if (k < 0) {
+                try {
+                    textures.push_back(loadTexture(path));
+                } catch (const std::exception &e) {
+                    // like an unreadable mesh: a texture that cannot be read is a scene that cannot be rendered
+                    std::cout << "ERROR: " << e.what() << " - aborting!" << std::endl;
+                    throw;
+                }
+                k = (int)textures.size() - 1;
+            }
+            geomTextures.resize(geoms.size() + 1, -1);
+            geomTextures[geoms.size()] = k;
+        }
     }
     g.transform = utilityCore::buildTransformationMatrix(g.translation, g.rotation, g.scale);
     g.inverseTransform = lin::inverse(g.transform);

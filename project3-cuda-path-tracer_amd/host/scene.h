@@ -9,6 +9,8 @@
 
 // (tells pathtrace_shim.cpp that this Scene has `meshes`; the reference's own scene.h, which the shim also builds against, has not)
 #define PT_SCENE_HAS_MESHES 1
+// (... and `textures`, `geomTextures` and Mesh::uvs: image textures bound to objects by a `TEXTURE <file>` line of their OBJECT block)
+#define PT_SCENE_HAS_TEXTURES 1
 
 // Triangles of one `mesh` object (README.md:112-116, 236), in the OBJ file's coordinates = the geom's object space.
 struct Mesh {
@@ -16,7 +18,18 @@ struct Mesh {
     std::vector<float> tris;    // 9 floats per triangle: v0, v1, v2
     std::vector<float> normals; // 9 floats per triangle: the vertex normals n0, n1, n2 (`vn`, smooth shading) -- or EMPTY: flat shading
     std::vector<int> mats;      // one per triangle: the scene material of that face (`usemtl <k>`), -1 = the object's own -- or EMPTY
+    std::vector<float> uvs;     // 6 floats per triangle: the corner texture coordinates u0 v0 u1 v1 u2 v2 (`vt`) -- or EMPTY
 };
+
+// An image texture (`TEXTURE <file>`): PPM (P3 / P6, 8 bits: texel = byte / 255, no sRGB decoding) or PFM (PF / Pf, float).  Linear RGB,
+// row 0 = the image's top row.
+struct Texture {
+    std::string path;           // as resolved against the scene file's directory: objects naming the same file share the texture
+    int width = 0, height = 0;
+    std::vector<float> rgb;     // width * height * 3
+};
+// Reads a PPM or PFM file; throws std::runtime_error when it cannot.
+Texture loadTexture(const std::string &path);
 
 class Scene {
 private:
@@ -39,5 +52,7 @@ public:
     std::vector<Geom> geoms;            // in file order = intersection order (first geom wins distance ties)
     std::vector<Material> materials;    // indexed by Geom::materialid
     std::vector<Mesh> meshes;           // one per Geom of type MESH, file order
+    std::vector<Texture> textures;      // every texture file the scene names, once, in order of first mention
+    std::vector<int> geomTextures;      // per geom: index into textures, or -1 (untextured)
     RenderState state;                  // camera, iteration count, depth, output name, host image
 };

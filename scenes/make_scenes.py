@@ -5,6 +5,8 @@ cornell.txt / sphere.txt carry the same numeric content as the reference's examp
 byte-identical structs from both).  cornell_glass.txt (BASELINE config C4) and spheres64.txt
 (config C5) are authored by this build as SURVEY.md section 8(d) specifies.  cornell_mesh.txt / mesh_small.txt use the
 scene format's third object type, "mesh" (README.md:236), with OBJ files generated here under scenes/models/.
+cornell_textured.txt binds image textures to objects (`TEXTURE <file>`, texture mapping [PBRT 10.4], a README extra) -- the
+textures are generated here under scenes/textures/ (ASCII PPM), the UV-mapped torus under scenes/models/.
 """
 import math
 import os
@@ -206,6 +208,69 @@ def write_obj(name, title, v, f, vn=None, usemtl=None):
             fp.write("f " + " ".join(("%d//%d" % (i + 1, i + 1)) if vn else str(i + 1) for i in face) + "\n")
 
 
+def torus_uv(nu, nv, R=0.35, r=0.15):
+    """torus() with texture coordinates: the grid's (i / nu, j / nv), the seams on vertices of their own -- (v, vt, faces of (v, vt) corners)"""
+    v, f = torus(nu, nv, R, r)
+    vt = [(i / nu, j / nv) for i in range(nu + 1) for j in range(nv + 1)]
+    ft = []
+    for i in range(nu):
+        for j in range(nv):
+            t = lambda a, b: a * (nv + 1) + b
+            ft.append((t(i, j), t(i + 1, j), t(i + 1, j + 1), t(i, j + 1)))
+    return v, vt, [tuple(zip(fv, tv)) for fv, tv in zip(f, ft)]
+
+
+def write_obj_uv(name, title, v, vt, f):
+    """faces of (vertex, texture coordinate) corners: `f i/j ...`"""
+    os.makedirs(os.path.join(HERE, "models"), exist_ok=True)
+    with open(os.path.join(HERE, "models", name), "w") as fp:
+        fp.write(f"# {title} (generated by scenes/make_scenes.py)\n")
+        for p in v:
+            fp.write("v %.6f %.6f %.6f\n" % p)
+        for p in vt:
+            fp.write("vt %.6f %.6f\n" % p)
+        for face in f:
+            fp.write("f " + " ".join("%d/%d" % (i + 1, j + 1) for i, j in face) + "\n")
+
+
+def write_ppm_p3(name, rows, title):
+    """8-bit ASCII PPM (rows top to bottom, each a list of (r, g, b) bytes)"""
+    os.makedirs(os.path.join(HERE, "textures"), exist_ok=True)
+    with open(os.path.join(HERE, "textures", name), "w") as fp:
+        fp.write("P3\n# %s (generated by scenes/make_scenes.py)\n%d %d\n255\n" % (title, len(rows[0]), len(rows)))
+        for row in rows:
+            fp.write(" ".join("%d %d %d" % p for p in row) + "\n")
+
+
+def cornell_textured():
+    s = ("// Cornell box with image textures (`TEXTURE <file>`, texture mapping): a checker back wall (a cube), a latitude-longitude\n"
+         "// texture on a diffuse sphere and a grid texture on a UV-mapped torus mesh\n\n")
+    for i, m in enumerate(CORNELL_MATS):
+        s += material(i, *m)
+    s += camera("800 800", 45, 5000, 8, "cornell_textured")
+    for i, o in enumerate(CORNELL_OBJS[:6]):
+        s += obj(i, *o)
+        if i == 3:
+            s = s[:-1] + "TEXTURE textures/checker.ppm\n\n"
+    s += obj(6, "diffuse sphere, latitude-longitude texture", "sphere", 1, "-1.5 4 -1", "0 30 0", "3 3 3")[:-1] + "TEXTURE textures/latlong.ppm\n\n"
+    s += obj(7, "UV-mapped torus", "mesh models/torus_uv.obj", 1, "2.2 2.2 1.5", "50 0 25", "4 4 4")[:-1] + "TEXTURE textures/grid.ppm\n\n"
+    return s
+
+
+def textures():
+    # 64 x 64 checker of 8 x 8-texel cells
+    a, b = (235, 235, 235), (40, 60, 160)
+    write_ppm_p3("checker.ppm", [[a if ((x // 8) + (y // 8)) % 2 == 0 else b for x in range(64)] for y in range(64)], "64 x 64 checker, 8 x 8-texel cells")
+    # 32 x 16 latitude-longitude bands: 8 hues around, darker towards the poles
+    hues = [(230, 80, 60), (240, 180, 40), (120, 200, 60), (40, 180, 170), (60, 110, 230), (150, 80, 220), (230, 90, 170), (200, 200, 200)]
+    write_ppm_p3("latlong.ppm", [[tuple(int(c * (0.45 + 0.55 * math.sin(math.pi * (y + 0.5) / 16))) for c in hues[x // 4]) for x in range(32)]
+                                  for y in range(16)], "32 x 16 latitude-longitude bands")
+    # 16 x 8 grid: u in red, v in green, cell parity in blue (ASCII, like every asset of scenes/: the loader's PFM path is tested with
+    # fixtures the tests write themselves)
+    write_ppm_p3("grid.ppm", [[(round(255 * (x + 0.5) / 16), round(255 * (1 - (y + 0.5) / 8)), 230 if (x + y) % 2 else 50) for x in range(16)]
+                              for y in range(8)], "16 x 8 grid: u in red, v in green, cell parity in blue")
+
+
 def unit_cube():
     """[-0.5, 0.5]^3 as six outward counter-clockwise quads: -x, +x, -y, +y, -z, +z"""
     v = [(x, y, z) for x in (-0.5, 0.5) for y in (-0.5, 0.5) for z in (-0.5, 0.5)]          # index = 4 x + 2 y + z
@@ -285,6 +350,9 @@ def main():
     w("cubes64.txt", lattice_scene("64 rotated cubes in Cornell's room", "cubes64", "cube", 4, 7001, True))
     w("spheres512.txt", lattice_scene("512 spheres in Cornell's room", "spheres512", "sphere", 8, 7002, False))
     w("room_tilted.txt", room_tilted())
+    textures()
+    write_obj_uv("torus_uv.obj", "torus, 16 x 8 quads = 256 triangles, with texture coordinates (vt)", *torus_uv(16, 8))
+    w("cornell_textured.txt", cornell_textured())
 
 
 if __name__ == "__main__":
