@@ -22,7 +22,12 @@ lists them all.
 caller of the hot path reads back -- as DIR/<name>.npy (float32): two builds run with the same arguments render the same
 iterations of the same scene and can be compared output for output.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+A plain run does only what its headline needs: set up, warm up, time the steps, write `--dump-outputs`, print the line (metric,
+value, ms_per_step, the repeats' spread and `config`, its path tallies taken from the headline pass's own blocks).  Everything
+else -- the readings below, `roofline`, `cpu_baseline`, `box_calibration`, the other configurations and the device groups --
+runs only with `--full`, each as described here.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
         N > 1 without a torchrun environment: bench.py starts its N ranks itself (a child `python -m
         torch.distributed.run`, before this process has touched the GPU) and relays rank 0's JSON line
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (what the driver does)
@@ -31,15 +36,14 @@ N > 1: image rows are sharded round-robin over the ranks (row y -> rank y % N), 
 own rows (packed), and ONE collective -- RCCL over xGMI -- assembles the frame at rank 0: the reduce(sum, float32, 3 W H,
 root 0) of zero-padded full frames that north_star and SURVEY 8e name (the default since round 6), or `--collective gather`:
 the gather of the row blocks (disjoint rows: both are bit-identical to 1 GPU; the gather moves 1/N of the bytes).  The
-N > 1 line carries both readings (`multi_gpu.value_collective_gather`).  `--collective-every batch` (default) issues it after every
-committed wavefront batch, `--collective-every 1` after every single iteration (BASELINE config C3 as written:
-one pt_iterate + one collective per iteration).  The default run also times a bounded sample of the per-iteration
-mode and reports it in config.per_iteration_collective.
+N > 1 line of a `--full` run carries both readings (`multi_gpu.value_collective_gather`).  `--collective-every batch` (default)
+issues it after every committed wavefront batch, `--collective-every 1` after every single iteration (BASELINE config C3 as
+written: one pt_iterate + one collective per iteration).
 `--scaling weak` (default): a step on N GPUs is `--batch` x N iterations of the whole frame -- every rank traces its 1/N of
 the rows for N times the iterations, as many paths per step as the single GPU (a renderer's weak scaling: N times the
 samples per pixel in the same time); value = all ranks' paths / the slowest rank's time.  `--scaling strong`: a step is
 `--batch` iterations whatever N (config C3 as written: a fixed number of samples, divided; ranks then fuse steps into
-fatter wavefront batches).  At N = 1 the two are the same run.  ONE N > 1 run reports all three readings of "N GPUs",
+fatter wavefront batches).  At N = 1 the two are the same run.  ONE N > 1 `--full` run reports all three readings of "N GPUs",
 each over whole steps: `value_weak`, `value_strong` (collective per wavefront batch) and `value_c3_as_written` (strong,
 one pt_iterate + one reduce(sum) of zero-padded full frames per ITERATION: BASELINE config C3 to the letter), plus
 `collective_bytes_per_call` and the collective's share of a step; `value` = the one `--scaling` names (default weak:
@@ -50,8 +54,8 @@ itself, and the reduce of a double-buffered snapshot runs on a stream of its own
 commit (distributed.PerIterationReducer); at N = 1 the reduce goes through a one-rank RCCL group, so the protocol's
 per-iteration cost is a hardware number even without a second GPU.  It is timed over the same `--steps` steps as `value`.
 
-Prints ONE JSON line on rank 0, with `roofline` (dominant kernel = the fused bounce kernel, HIP-event timed on the
-streams it runs on, against the 8 TB/s HBM peak) and `cpu_baseline` (the single-thread CPU oracle on a bounded
+Prints ONE JSON line on rank 0; with `--full` it also carries `roofline` (dominant kernel = the fused bounce kernel, HIP-event
+timed on the streams it runs on, against the 8 TB/s HBM peak) and `cpu_baseline` (the single-thread CPU oracle on a bounded
 sample of the same workload; N = 1 only).
 """
 import argparse
@@ -87,7 +91,10 @@ def parse(argv=None):
     ap.add_argument("--scene", default=os.path.join(ROOT, "scenes", "cornell.txt"))
     ap.add_argument("--res", type=int, nargs=2, default=[1280, 720])
     ap.add_argument("--depth", type=int, default=8)
-    ap.add_argument("--cpu-spp", type=int, default=40, help="spp of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass, measure everything else the line can carry: the other readings, roofline, CPU baseline, box "
+                         "calibration, other configurations and device groups.  Without it a run times the headline pass alone")
+    ap.add_argument("--cpu-spp", type=int, default=40, help="--full: spp of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--pipeline", type=int, default=3,
                     help="batches in flight (PtOptions.pipeline_depth; 0 = library default 3).  Round 4: 3 -- with steps of 64 iterations a third "
                          "batch in flight is worth +1.5 .. 4 %% (profiles/exp_r4i.sh, exp_r4k.sh); the per-iteration reading of config C3 keeps 2")
@@ -102,12 +109,12 @@ def parse(argv=None):
                     help="N > 1: assemble the frame at rank 0 after every wavefront batch, or after every iteration")
     ap.add_argument("--collective", default="reduce", choices=["gather", "reduce"],
                     help="N > 1: reduce(sum, float32, 3 W H, root 0) of zero-padded full frames -- the collective north_star and SURVEY 8e name (default "
-                         "since round 6) -- or the gather of the packed row blocks (1/N of the bytes: rows are disjoint); the N > 1 line carries BOTH readings")
+                         "since round 6) -- or the gather of the packed row blocks (1/N of the bytes: rows are disjoint); a --full N > 1 line carries BOTH readings")
     ap.add_argument("--per-iteration-sample", type=int, default=None,
-                    help="whole steps timed in the per-iteration mode of BASELINE config C3 (strong scaling, one pt_iterate + one "
+                    help="--full: whole steps timed in the per-iteration mode of BASELINE config C3 (strong scaling, one pt_iterate + one "
                          "reduce per iteration, N = 1 included); default = --steps; 0 = skip")
-    ap.add_argument("--dump-c3-frame", default=None, help="rank 0 writes the frame the per-iteration mode's last reduce delivered to this .npy file")
-    ap.add_argument("--extra-passes", type=int, default=1, help="N > 1: 0 = only the pass `--scaling` names (no value_weak / value_strong pair)")
+    ap.add_argument("--dump-c3-frame", default=None, help="--full: rank 0 writes the frame the per-iteration mode's last reduce delivered to this .npy file")
+    ap.add_argument("--extra-passes", type=int, default=1, help="--full, N > 1: 0 = only the pass `--scaling` names (no value_weak / value_strong pair)")
     ap.add_argument("--pmc-traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"),
                     help="PMC counters per bounce-kernel launch from the rocprofv3 --pmc passes (profiles/README.md)")
     ap.add_argument("--valu-rate-json", default=os.path.join(ROOT, "profiles", "valu_issue_rate.json"),
@@ -117,16 +124,16 @@ def parse(argv=None):
                     help="rank 0 writes what the headline pass computed by its last timed step to DIR/<name>.npy (float32, at most 64 MB in all): "
                          "frame.npy = the accumulated radiance (H x W x 3 running sum), or a fixed seeded sample of its pixels when larger")
     ap.add_argument("--configs", type=int, default=None,
-                    help="1: after the headline line's own measurement, measure the other BASELINE configurations that fit one GPU -- C4 (glass, 1920x1080, "
+                    help="--full: 1 = after the headline line's own measurement, measure the other BASELINE configurations that fit one GPU -- C4 (glass, 1920x1080, "
                          "depth 16), C5 on one GPU (64 spheres, 4096x4096, 16 spp per step) and the mesh scene -- a few timed blocks each, every one "
-                         "in a child process of its own, and report them under `configs` with a roofline each.  Default: 1 for the plain "
-                         "`python bench.py [--steps K --warmup W]` on one GPU, 0 as soon as a scene / frame / depth / batch is given")
+                         "in a child process of its own, and report them under `configs` with a roofline each.  Default: 1 for "
+                         "`python bench.py --full [--steps K --warmup W]` on one GPU, 0 as soon as a scene / frame / depth / batch is given")
     ap.add_argument("--roofline-bound", default="hbm", choices=["hbm", "valu_fp32"],
-                    help="what `roofline` prices the bounce kernel against: the 8 TB/s of HBM (the contract's bound; C2, C4, meshes) or the vector "
+                    help="--full: what `roofline` prices the bounce kernel against: the 8 TB/s of HBM (the contract's bound; C2, C4, meshes) or the vector "
                          "units' fp32 issue rate (SURVEY 8d: the 64-sphere configuration C5 is VALU-bound; needs that configuration's counters, --pmc-key)")
     ap.add_argument("--pmc-key", default=None, help="take the PMC counters from profiles/pmc_configs.json[<key>] instead of --pmc-traffic-json")
     ap.add_argument("--group-blocks", type=int, default=None,
-                    help="1: also measure the C ABI's device groups in child processes (`--group`): at N = 1 eight members on the one device and config C3 as "
+                    help="--full: 1 = also measure the C ABI's device groups in child processes (`--group`): at N = 1 eight members on the one device and config C3 as "
                          "written through the library's own collective, at N > 1 a group over the N devices beside the ranks' reading.  Default: as --configs "
                          "at N = 1, as --extra-passes at N > 1")
     ap.add_argument("--group", type=int, default=0,
@@ -361,7 +368,7 @@ def other_configs(args):
     out = {}
     for key, extra, what in OTHER_CONFIGS:
         extra = [os.path.join(ROOT, a) if a.startswith("scenes/") else a for a in extra]     # (whatever directory the driver runs from)
-        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--repeats", "3", "--cpu-spp", "0", "--per-iteration-sample", "0",
+        cmd = [sys.executable, os.path.abspath(__file__)] + extra + ["--full", "--repeats", "3", "--cpu-spp", "0", "--per-iteration-sample", "0",
                                                                       "--configs", "0", "--pmc-key", key, "--pipeline", str(args.pipeline)]
         t0 = time.perf_counter()
         try:
@@ -549,10 +556,12 @@ def _on_sigterm(signum, frame):
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if not args.full and (args.dump_c3_frame or args.configs or args.group_blocks):
+        sys.exit("bench.py: --dump-c3-frame, --configs 1 and --group-blocks 1 ask for what only a --full run measures")
     if args.configs is None:
-        # the driver's plain command (flags --gpus / --steps / --warmup only) reports every one-GPU configuration; any other run is about ONE
+        # `--full` with no flags but --gpus / --steps / --warmup reports every one-GPU configuration; any other run is about ONE
         d = parse([])
-        args.configs = 1 if (args.gpus == 1 and world == 1 and all(getattr(args, k) == getattr(d, k) for k in
+        args.configs = 1 if (args.full and args.gpus == 1 and world == 1 and all(getattr(args, k) == getattr(d, k) for k in
                                                                      ("scene", "res", "depth", "batch", "pipeline", "scaling", "cpu_spp", "repeats"))) else 0
     if args.group > 0:
         sys.exit(run_group(args))
@@ -785,7 +794,7 @@ def run(args, ctx):
 
     every = args.collective_every
     # ---- pass A: the headline number (`--scaling`, `--collective-every`, `--collective`), repeated blocks --------------
-    telemetry = BoxTelemetry(torch, device_index) if rank == 0 else None
+    telemetry = BoxTelemetry(torch, device_index) if (rank == 0 and args.full) else None
     if telemetry:
         telemetry.start()
     if os.environ.get("BENCH_MARK_FILE") and rank == 0:    # (tests: "the timed blocks are about to start")
@@ -814,9 +823,9 @@ def run(args, ctx):
             r["mode"] += " of zero-padded full frames, snapshot double-buffered, the reduce on its own stream"
         return r
 
-    # ---- N > 1: the collective on its own (its bytes and its share of a step), then the other readings of "N GPUs" -------
+    # ---- --full, N > 1: the collective on its own (its bytes and its share of a step), then the other readings of "N GPUs" -------
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         calls = 10
         barrier()
         t0 = time.perf_counter()
@@ -840,13 +849,13 @@ def run(args, ctx):
             other_coll = "gather" if args.collective == "reduce" else "reduce"
             multi["value_collective_" + other_coll] = reading(args.scaling, every, other_coll, args.steps, min(args.warmup, 2))
 
-    # ---- BASELINE config C3 to the letter, N >= 1: a fixed number of samples divided over the ranks, one pt_iterate and one
+    # ---- --full: BASELINE config C3 to the letter, N >= 1: a fixed number of samples divided over the ranks, one pt_iterate and one
     #      reduce(sum) of zero-padded full frames per ITERATION (the reference's per-iteration full-frame transfer,
     #      src/pathtrace.cu:170-171), as the overlapped fast path of distributed.PerIterationReducer.  N = 1: through a one-rank
     #      RCCL group, so that the protocol's per-iteration cost is a hardware number without a second GPU.
     c3 = None
     c3_steps = args.steps if args.per_iteration_sample is None else args.per_iteration_sample
-    if c3_steps > 0 and (world > 1 or args.extra_passes):
+    if args.full and c3_steps > 0 and (world > 1 or args.extra_passes):
         try:
             if world == 1 and not dist.is_initialized():
                 ptdist.init_process_group(backend, single_rank=True)
@@ -863,21 +872,26 @@ def run(args, ctx):
             c3 = {"error": repr(e)}
         ctx.pop("reducer", None)
 
-    # ---- pass B: same steps with HIP events around every launch (roofline of the bounce kernel); one
+    iters_block = args.steps * I                             # iterations of one timed block
+    # ---- pass B (--full): same steps with HIP events around every launch (roofline of the bounce kernel); one
     #      batch in flight, so that a launch's duration is the kernel's own and not its share of a GPU it
     #      co-occupies with the neighbouring batches' launches
-    Bp = measure(args.scaling, every, args.collective, args.steps, 1, min(args.warmup, 2), flags=pt.PT_FLAG_KERNEL_TIMING, pipeline=1)
-    dtB = Bp["walls"][0]
-    cnt = Bp["counters"]
-    pt.pathtraceFree()
+    if args.full:
+        Bp = measure(args.scaling, every, args.collective, args.steps, 1, min(args.warmup, 2), flags=pt.PT_FLAG_KERNEL_TIMING, pipeline=1)
+        dtB = Bp["walls"][0]
+        cnt, cnt_iters = Bp["counters"], iters_block
+        pt.pathtraceFree()
+    else:
+        # a plain run's path tallies are the headline pass's own, over all of its timed blocks
+        cnt, cnt_iters = cntA, iters_block * len(A["walls"])
 
-    # ---- the C ABI's own multi-device host path (pt_group_*: ONE process, a host thread and a renderer per member, the library's collective;
+    # ---- --full: the C ABI's own multi-device host path (pt_group_*: ONE process, a host thread and a renderer per member, the library's collective;
     #      SURVEY 8e), each reading in a child process of its own (`bench.py --group`), while this process's renderers are freed and its ranks wait:
     #      N = 1: eight members on the one device against the headline, and config C3 as written through the library's own per-iteration reduce
     #             (a one-rank RCCL communicator: the call path a one-GPU box can run);
     #      N > 1: rank 0 starts a group over the N devices -- what the reference's single-process host (src/main.cpp:72-113) would drive.
     groups = None
-    want_groups = args.group_blocks if args.group_blocks is not None else (args.configs if world == 1 else args.extra_passes)
+    want_groups = args.full and (args.group_blocks if args.group_blocks is not None else (args.configs if world == 1 else args.extra_passes))
     def wait_for_rank0(key):
         """the other ranks wait ON THE HOST for rank 0's child process (a key of the rendezvous store): a collective barrier would spin on
         their GPUs for as long as the group measurement -- which uses those very GPUs -- takes"""
@@ -908,46 +922,44 @@ def run(args, ctx):
         wait_for_rank0("pt_amd_group_blocks_done")
         barrier()
 
-    iters_block = args.steps * I                             # iterations of one timed block
     liveA = [int(cntA.live[d]) for d in range(D + 2)]
     live = [int(cnt.live[d]) for d in range(D + 2)]
     # paths that actually travel through the path pools: a survivor that certainly misses everything ends at its scatter and
     # is counted in live[d + 1] (it does enter that bounce and miss) without ever being written or read
     moved = [int(cnt.live[d]) - int(cnt.ended_early[d]) for d in range(D + 2)]
-    hits = int(cnt.light_hits)
-    # algorithmic HBM bytes of the bounce launches: read every queued path (bounce 1 builds its camera
-    # rays in registers and reads nothing), write every queued survivor (nothing is written after the last
-    # bounce), park the radiance of every emitter hit
-    bounce_bytes = sum(PATH_BYTES * moved[d] for d in range(2, D + 1)) \
-        + sum(PATH_BYTES * moved[d + 1] for d in range(1, D)) + ACCUM_BYTES * hits
-    launches = max(int(cnt.bounce_launches), 1)
-    iters_per_launch = maxb      # (N > 1: the last launch of a run may carry fewer steps; the PMC figures are N = 1 only)
-    avg_ms = cnt.bounce_kernel_ms / launches
-    achieved = bounce_bytes / launches / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
     # whole-frame path counts: summed over the ranks (every rank holds the counts of its own rows)
     live_sum, moved_sum, liveA_sum = (sum_over_ranks([sum(live[1:D + 1]), sum(moved[1:D + 1]), sum(liveA[1:D + 1])]))
-    # PMC counters of the bounce kernel from the committed rocprofv3 passes.  They are stored PER ITERATION of a launch's
-    # batch together with the configuration they were collected on; used only for that very configuration (frame,
-    # depth, iterations per launch), scaled by the iterations a launch of THIS run carries -- else null.
-    traffic, valu_insts, lds_conf, pmc_src, valu_util = None, None, None, None, None
-    try:
-        pmc = json.load(open(args.pmc_traffic_json))
-        if args.pmc_key:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_configs.json")))[args.pmc_key]
-        here = ["%s %dx%d" % (os.path.relpath(args.scene, ROOT), W, H), "%d bounces" % D]
-        if world == 1 and pmc.get("workload") == here and pmc.get("iterations_per_launch") == iters_per_launch:
-            traffic = pmc["hbm_bytes_per_launch_iteration"] * iters_per_launch
-            valu_insts = pmc["valu_wave_insts_per_launch_iteration"] * iters_per_launch
-            lds_conf = pmc.get("lds_bank_conflict_cycles_per_launch")
-            valu_util = pmc.get("valu_utilisation_counter_derived")
-            pmc_src = pmc.get("source")
-    except Exception:
-        pass
-    rate = valu_issue_rate(args.valu_rate_json, 6)
 
-    if rank == 0:
-        nominal = P * D * iters_block
-        walls = sorted(A["walls"])
+    def roofline():
+        """`--full`: the bounce kernel against its bound, from pass B's HIP-event timed launches and the committed PMC counters"""
+        hits = int(cnt.light_hits)
+        # algorithmic HBM bytes of the bounce launches: read every queued path (bounce 1 builds its camera
+        # rays in registers and reads nothing), write every queued survivor (nothing is written after the last
+        # bounce), park the radiance of every emitter hit
+        bounce_bytes = sum(PATH_BYTES * moved[d] for d in range(2, D + 1)) \
+            + sum(PATH_BYTES * moved[d + 1] for d in range(1, D)) + ACCUM_BYTES * hits
+        launches = max(int(cnt.bounce_launches), 1)
+        iters_per_launch = maxb      # (N > 1: the last launch of a run may carry fewer steps; the PMC figures are N = 1 only)
+        avg_ms = cnt.bounce_kernel_ms / launches
+        achieved = bounce_bytes / launches / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        # PMC counters of the bounce kernel from the committed rocprofv3 passes.  They are stored PER ITERATION of a launch's
+        # batch together with the configuration they were collected on; used only for that very configuration (frame,
+        # depth, iterations per launch), scaled by the iterations a launch of THIS run carries -- else null.
+        traffic, valu_insts, lds_conf, pmc_src, valu_util = None, None, None, None, None
+        try:
+            pmc = json.load(open(args.pmc_traffic_json))
+            if args.pmc_key:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "pmc_configs.json")))[args.pmc_key]
+            here = ["%s %dx%d" % (os.path.relpath(args.scene, ROOT), W, H), "%d bounces" % D]
+            if world == 1 and pmc.get("workload") == here and pmc.get("iterations_per_launch") == iters_per_launch:
+                traffic = pmc["hbm_bytes_per_launch_iteration"] * iters_per_launch
+                valu_insts = pmc["valu_wave_insts_per_launch_iteration"] * iters_per_launch
+                lds_conf = pmc.get("lds_bank_conflict_cycles_per_launch")
+                valu_util = pmc.get("valu_utilisation_counter_derived")
+                pmc_src = pmc.get("source")
+        except Exception:
+            pass
+        rate = valu_issue_rate(args.valu_rate_json, 6)
         rf = {"bound": "hbm", "kernel": ("k_mesh_walk + k_bounce (the walks of the bounce's rays through the meshes' hierarchies, then the fused bounce: one pair "
                                          "of launches per bounce and batch, timed together)") if getattr(scene, "meshes", None) else
                                         "k_bounce (fused [camera rays+]intersect+shade+compact, one launch per bounce and batch)",
@@ -991,6 +1003,11 @@ def run(args, ctx):
                        "counted": "SQ_INSTS_VALU per launch x 64 lanes x 2 FLOP (one FMA issue slot each) / the launch's HIP-event duration",
                        "hbm": hbm})
             rf.pop("frac_pipelined", None)
+        return rf
+
+    if rank == 0:
+        nominal = P * D * iters_block
+        walls = sorted(A["walls"])
         out = {
             "metric": "Mpaths/sec (paths = pixels x bounces x spp) at %dx%d, %d bounces" % (W, H, D),
             "value": round(nominal / dt / 1e6, 2), "unit": "Mpaths/s",
@@ -1013,14 +1030,15 @@ def run(args, ctx):
                        "iterations_per_wavefront_batch": maxb,
                        "batches_in_flight": args.pipeline if args.pipeline > 0 else 3,
                        "collective_every": None if world == 1 else every,
-                       "live_segments_per_iteration": round(live_sum / max(iters_block, 1), 1),
+                       "live_segments_per_iteration": round(live_sum / max(cnt_iters, 1), 1),
                        # unterminated paths entering bounce d = 1 .. depth, per iteration (rank 0's rows when N > 1): the reference's
                        # compaction analysis, README.md:284-293
-                       "live_per_bounce_per_iteration": [round(live[d] / max(iters_block, 1), 1) for d in range(1, D + 1)],
-                       "queued_segments_per_iteration": round(moved_sum / max(iters_block, 1), 1),
+                       "live_per_bounce_per_iteration": [round(live[d] / max(cnt_iters, 1), 1) for d in range(1, D + 1)],
+                       "queued_segments_per_iteration": round(moved_sum / max(cnt_iters, 1), 1),
                        "live_Msegments_per_s": round(liveA_sum / len(walls) / dt / 1e6, 2)},
-            "roofline": rf,
         }
+        if args.full:
+            out["roofline"] = rf = roofline()
         if multi:
             out["value_" + args.scaling] = {"value": out["value"], "unit": "Mpaths/s", "steps": args.steps, "iterations_per_step": I,
                                             "iterations_per_wavefront_batch": maxb, "ms_per_step": out["ms_per_step"],
@@ -1045,23 +1063,24 @@ def run(args, ctx):
             out.update(groups)
             out["multi_device_note"] = ("pt_group's RCCL reduce has only ever run in a ONE-rank communicator: no multi-GPU node was available to any build round; "
                                         "N > 1 figures of either path are unmeasured unless this line's n_gpus says otherwise")
-        out["box_calibration"] = box_calibration(pt, torch)
-        tm = telemetry.report() if telemetry else None
-        out["box_calibration"]["telemetry_during_timed_blocks"] = tm
-        # the vector-issue bound once more at the shader clock the card actually ran at (the figures above price it at the 2.4 GHz maximum;
-        # under this load the card settles some 10 % below it, at ~1.2 of its 1.4 kW cap)
-        try:
-            sclk = tm["sclk_mhz"]["median"] * 1e6
-            v = rf.get("valu")
-            if v and sclk > 0:
-                v["frac_of_issue_bound_at_measured_sclk"] = {k: round(x * CLOCK_HZ / sclk, 4) for k, x in v["frac_of_issue_bound"].items()}
-                v["measured_sclk_mhz"] = tm["sclk_mhz"]["median"]
-        except (TypeError, KeyError):
-            pass
-        if world == 1 and args.cpu_spp > 0:
-            out["cpu_baseline"] = cpu_baseline(args, scene, pt)
-        if world == 1 and args.configs:
-            out["configs"] = other_configs(args)
+        if args.full:
+            out["box_calibration"] = box_calibration(pt, torch)
+            tm = telemetry.report() if telemetry else None
+            out["box_calibration"]["telemetry_during_timed_blocks"] = tm
+            # the vector-issue bound once more at the shader clock the card actually ran at (the figures above price it at the 2.4 GHz maximum;
+            # under this load the card settles some 10 % below it, at ~1.2 of its 1.4 kW cap)
+            try:
+                sclk = tm["sclk_mhz"]["median"] * 1e6
+                v = rf.get("valu")
+                if v and sclk > 0:
+                    v["frac_of_issue_bound_at_measured_sclk"] = {k: round(x * CLOCK_HZ / sclk, 4) for k, x in v["frac_of_issue_bound"].items()}
+                    v["measured_sclk_mhz"] = tm["sclk_mhz"]["median"]
+            except (TypeError, KeyError):
+                pass
+            if world == 1 and args.cpu_spp > 0:
+                out["cpu_baseline"] = cpu_baseline(args, scene, pt)
+            if world == 1 and args.configs:
+                out["configs"] = other_configs(args)
         # a block measured by a child process that failed stands in the line with an `error` key -- and is NAMED here, so that a line that
         # lacks a configuration cannot pass for a complete one
         failed = [k for k, v in out.get("configs", {}).items() if "error" in v]

@@ -8,7 +8,7 @@ L=$ROOT/project3-cuda-path-tracer_amd/csrc
 OUT=$ROOT/gpurun_out/abpmc; mkdir -p $OUT
 for v in "$@"; do
   rm -rf $OUT/pmc$v
-  (cd /tmp && PT_AMD_LIB=$L/libpt_amd$v.so rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_SALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc$v -- python3 $ROOT/bench.py $args --cpu-spp 0 --pipeline 1 --per-iteration-sample 0 --repeats 1 > $OUT/log$v.txt 2>&1) || { echo "pmc pass failed for lib$v"; tail -5 $OUT/log$v.txt; }
+  (cd /tmp && PT_AMD_LIB=$L/libpt_amd$v.so rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_SALU GRBM_GUI_ACTIVE --output-format csv -d $OUT/pmc$v -- python3 $ROOT/bench.py --full $args --cpu-spp 0 --pipeline 1 --per-iteration-sample 0 --repeats 1 > $OUT/log$v.txt 2>&1) || { echo "pmc pass failed for lib$v"; tail -5 $OUT/log$v.txt; }
   python3 - $OUT/pmc$v "lib$v" <<'PY'
 import csv, glob, sys, collections, re
 files = glob.glob(sys.argv[1] + "/*/*counter_collection.csv")

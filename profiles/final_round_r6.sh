@@ -20,7 +20,7 @@ b)
   ;;
 c)
   bash profiles/bench_configs.sh $OUT/configs 2>&1 | tee $OUT/configs.txt
-  python bench.py > $OUT/default_run.json 2> $OUT/default_run.err && echo "default run ok"
+  python bench.py --full > $OUT/default_run.json 2> $OUT/default_run.err && echo "default run ok"
   ;;
 d)
   python profiles/generality.py 2>&1 | grep -v "amdgpu.ids" | tee $OUT/generality.txt

@@ -15,7 +15,7 @@ for name in SCENES:
     for it in (1, 2): ref.iterate(it, want)
     pt.pathtraceFree(); pt.pathtraceInit(sc, max_batch=2); pt.pathtrace_batch(None, 0, 1, 2); got = pt.readback(96 * 64); pt.pathtraceFree()
     same = bool(np.array_equal(got.view(np.uint32), want.view(np.uint32)))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scene", os.path.join(ROOT, "scenes", name), "--steps", "3", "--warmup", "1", "--repeats", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scene", os.path.join(ROOT, "scenes", name), "--steps", "3", "--warmup", "1", "--repeats", "3",
                         "--batch", "16", "--cpu-spp", "0", "--per-iteration-sample", "0", "--configs", "0"], capture_output=True, text=True, timeout=600)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:

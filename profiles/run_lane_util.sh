@@ -9,7 +9,7 @@ ARGS=${2:-}
 OUT=$PWD/gpurun_out/lane_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 $PWD/bench.py --steps ${STEPS:-8} --warmup 2 --cpu-spp 0 --pipeline 1 --per-iteration-sample 0 --configs 0 --repeats 1 $ARGS"
+BENCH="python3 $PWD/bench.py --full --steps ${STEPS:-8} --warmup 2 --cpu-spp 0 --pipeline 1 --per-iteration-sample 0 --configs 0 --repeats 1 $ARGS"
 cd /tmp
 rocprofv3 -L > $OUT/counters_available.txt 2>&1 || true
 p=1

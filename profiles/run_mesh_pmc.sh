@@ -8,7 +8,7 @@ TAG=${1:-r03_mesh}
 OUT=$PWD/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 $PWD/bench.py --steps 8 --warmup 2 --cpu-spp 0 --pipeline 1 --repeats 1 --scene $PWD/${SCENE:-scenes/cornell_mesh.txt}"
+BENCH="python3 $PWD/bench.py --full --steps 8 --warmup 2 --cpu-spp 0 --pipeline 1 --repeats 1 --scene $PWD/${SCENE:-scenes/cornell_mesh.txt}"
 cd /tmp
 rocprofv3 -L > $OUT/avail.txt 2>&1 || true
 i=0

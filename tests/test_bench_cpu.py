@@ -46,3 +46,21 @@ def test_dump_outputs_samples_a_large_frame_the_same_way_every_time(monkeypatch,
     assert vals.dtype == np.float32 and pix.dtype == np.float64 and len(vals) == len(pix) == 4000 // 20
     assert np.all(np.diff(pix) > 0) and pix[-1] < W * H
     assert np.array_equal(vals, frame.reshape(-1, 3)[pix.astype(np.int64)])
+
+
+def test_full_is_off_by_default(monkeypatch):
+    b = _bench(monkeypatch)
+    assert b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"]).full is False
+    assert b.parse(["--full"]).full is True
+
+
+def test_what_only_a_full_run_measures_needs_full():
+    # (a plain run would silently leave the file unwritten or the blocks unmeasured; it refuses before touching the GPU)
+    import subprocess
+    import sys
+    from conftest import ROOT
+    for extra in (["--dump-c3-frame", "c3.npy"], ["--configs", "1"], ["--group-blocks", "1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0"] + extra,
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 1 and "--full" in r.stderr, (extra, r.stderr[-2000:])
+        assert not [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,8 +1,10 @@
-"""bench.py prints ONE JSON line with the contract's keys (metric, value, roofline, cpu_baseline, ...)."""
+"""bench.py prints ONE JSON line with the contract's keys: a plain run the headline's (metric, value, ms_per_step, ...), a `--full` run
+everything else beside them (roofline, cpu_baseline, the other configurations, ...)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -15,7 +17,7 @@ def test_bench_json_contract(pt, tmp_path):
     if pt.device_count() < 1:
         pytest.fail("no HIP device: GPU tests must run on the MI355X box")
     dump, dump_c3 = str(tmp_path / "frame.npy"), str(tmp_path / "frame_c3.npy")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-spp", "1", "--repeats", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-spp", "1", "--repeats", "5",
                         "--dump-frame", dump, "--dump-c3-frame", dump_c3],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -87,12 +89,12 @@ def test_bench_json_contract(pt, tmp_path):
 
 
 def test_driver_command_reports_every_one_gpu_configuration(pt):
-    # round 5: the driver's own command -- `python bench.py` with nothing but --steps / --warmup -- carries, beside
+    # round 5: `python bench.py --full` with nothing but --steps / --warmup carries, beside
     # the headline C2 line, a `configs` block: C4, C5 on one of its eight GPUs and the mesh scene, each measured by a child bench.py of its
     # own and each with a roofline priced against the bound SURVEY 8d names (C5: the vector units)
     if pt.device_count() < 1:
         pytest.fail("no HIP device: GPU tests must run on the MI355X box")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["steps"] == 4 and d["warmup"] == 2 and "cpu_baseline" in d and "roofline" in d
@@ -131,9 +133,37 @@ def test_driver_command_reports_every_one_gpu_configuration(pt):
     assert "pt_group_iterate per iteration" in c3["mode"]
     assert "error" not in d["value_c3_as_written_torch_distributed"] and "unmeasured" in d["multi_device_note"]
     # a run that is about ONE configuration carries no block
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-spp", "0", "--per-iteration-sample", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-spp", "0", "--per-iteration-sample", "0",
                         "--repeats", "2"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "configs" not in json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_plain_run_times_the_headline_alone(pt, tmp_path):
+    # a plain `bench.py --gpus 1 --steps K --warmup W` does what its headline needs and nothing more: no extra pass, no child process, no CPU
+    # baseline -- at most 30 s of the whole run's wall outside its warm-up and timed steps
+    if pt.device_count() < 1:
+        pytest.fail("no HIP device: GPU tests must run on the MI355X box")
+    steps, warmup = 3, 1
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "Mpaths/sec (paths = pixels x bounces x spp) at 1280x720, 8 bounces"
+    assert d["unit"] == "Mpaths/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == steps and d["warmup"] == warmup and d["repeats"] == 1 and d["ms_per_step"] == d["ms_per_step_blocks"][0] > 0
+    assert abs(d["value"] - 1280 * 720 * 8 * 64 / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01 and d["value"] > 1000.0
+    for k in ("roofline", "cpu_baseline", "box_calibration", "value_c3_as_written", "configs", "configs_failed", "group_8_members_one_device"):
+        assert k not in d, k
+    # the path tallies come from the headline pass's own blocks: every pixel the camera sees starts a path
+    c = d["config"]
+    assert len(c["live_per_bounce_per_iteration"]) == 8 and 0 < c["live_per_bounce_per_iteration"][0] <= 1280 * 720
+    assert c["live_per_bounce_per_iteration"][-1] <= c["live_per_bounce_per_iteration"][0] and c["live_Msegments_per_s"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame.npy"]
+    assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def _batched_frame(pt, iterations):

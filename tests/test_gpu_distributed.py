@@ -98,7 +98,7 @@ def _single_rank_frame(pt, iterations, batch):
                                                        ("batch", ["--collective", "gather", "--batch", "16"], 4, "strong"),
                                                        ("batch", ["--collective", "gather", "--batch", "96"], 3, "weak")])
 def test_bench_two_ranks_contract(pt, tmp_path, every, extra, ranks, scaling):
-    # bench.py --gpus 2 (and 4) WITHOUT a torchrun environment: it starts its ranks itself (torch.distributed.run as a
+    # bench.py --full --gpus 2 (and 4) WITHOUT a torchrun environment: it starts its ranks itself (torch.distributed.run as a
     # child, one process per rank -- exactly what the driver launches); gloo stands in for RCCL because both ranks
     # share the box's single GPU.  Rank 0's assembled 1280x720 frame must equal the single-rank render BIT FOR BIT,
     # with the collective after every batch, after every iteration, and as the reduce of zero-padded frames.
@@ -109,7 +109,7 @@ def test_bench_two_ranks_contract(pt, tmp_path, every, extra, ranks, scaling):
         env.pop(k, None)
     dump, dump_c3 = str(tmp_path / "frame.npy"), str(tmp_path / "frame_c3.npy")
     steps, warmup, repeats = 3, 1, 2
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", str(steps), "--warmup", str(warmup),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(ranks), "--steps", str(steps), "--warmup", str(warmup),
                         "--repeats", str(repeats), "--collective-every", every, "--per-iteration-sample", "1", "--dump-frame", dump,
                         "--dump-c3-frame", dump_c3] + extra + ([] if "--group-blocks" in extra else ["--group-blocks", "0"])
                        + ([] if scaling == "weak" else ["--scaling", "strong"]),                # (weak is the default)
