@@ -205,6 +205,27 @@ typedef struct PtTexBinding {
 int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings, int nbindings,
                     size_t binding_struct_bytes);
 
+/* Bump mapping (PBRT 10.5.1; a README extra the reference names and does not implement, so the semantics are build-defined --
+ * csrc/pt_device.h, "bump mapping", gives every operation):
+ *   - a height map -- one of the textures registered with pt_set_textures, channel 0, sampled as textures are -- and a scale (world units of
+ *     displacement per unit of texel value) bound to a PRIMITIVE tilt the normal it is shaded with, by the height's central differences one
+ *     texel apart along the texture coordinates textures use.  A height map needs no colour binding;
+ *   - the tilted normal replaces the surface normal in refraction, mirror reflection, the SPECEX lobe, the diffuse hemisphere and the
+ *     direct-lighting cosine; the ray's origin offset, the side (eta), emission and the texture colour keep the unbumped surface.  A path whose
+ *     new direction would cross the geometric surface from its origin offset ends there, adding nothing.
+ * pt_set_bump_maps registers bindings for the NEXT pt_init (copied; kept across pt_free; (NULL, 0, ...) clears them).  pt_init fails with
+ * PT_ERR_INVALID when a binding names a geom or texture out of range or a geom twice, a mesh binding has no UVs or another triangle count than
+ * the registered mesh, a binding of a sphere or cube has UVs, or a scale is non-finite.  Scenes with a bound height map take k_bounce
+ * instantiations of their own; other scenes, textured ones included, run what they ran before.  (Additive: the ABI version stays.) */
+typedef struct PtBumpBinding {
+    int32_t geom;           /* index into pt_init's geoms */
+    int32_t texture;        /* index into the textures registered with pt_set_textures */
+    float scale;            /* finite */
+    int32_t ntris;          /* mesh geoms: the mesh's triangle count; spheres and cubes: 0 */
+    const float *uvs;       /* mesh geoms: ntris x 6 floats, the corner UVs (u0, v0, u1, v1, u2, v2) of every triangle; others NULL */
+} PtBumpBinding;
+int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes);
+
 /* pathtraceInit: upload scene, allocate the accumulator and the SoA path-state buffers.
  * Replaces reference src/pathtrace.cu:75-85.  Calling it twice without pt_free re-initialises. */
 int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats,
@@ -265,7 +286,7 @@ int pt_compact_nonzero_i32(const int32_t *in_dev, int32_t *out_dev, int64_t n, i
  * The reference's renderer is one set of file-static globals bound to device 0 (src/pathtrace.cu:70-71, src/preview.cpp:107).  Here a
  * renderer is a context: pt_ctx_create makes one, pt_ctx_make_current(ctx) makes every function above act on it for the calling thread
  * (NULL: back to the default context), pt_ctx_destroy frees its renderer and the context.  A context initialised on a device makes that
- * device current when it is made current.  pt_set_meshes and pt_set_textures register per context. */
+ * device current when it is made current.  pt_set_meshes, pt_set_textures and pt_set_bump_maps register per context. */
 typedef struct PtContext PtContext;
 PtContext *pt_ctx_create(void);               /* NULL: out of memory */
 int        pt_ctx_make_current(PtContext *ctx /* NULL = the default context */);
@@ -308,6 +329,7 @@ const char *pt_group_collective(const PtGroup *g);
 int  pt_group_set_meshes(PtGroup *g, const PtMesh *meshes, int nmeshes);
 int  pt_group_set_textures(PtGroup *g, const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings,
                            int nbindings, size_t binding_struct_bytes);
+int  pt_group_set_bump_maps(PtGroup *g, const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes);
 int  pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
                    const PtOptions *opts /* may be NULL */);
 int  pt_group_iterate_batch(PtGroup *g, int frame, int first_iter, int count);

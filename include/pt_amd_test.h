@@ -142,6 +142,12 @@ int pt_test_reflect_refract(const float *I3, const float *N3, const float *eta, 
  * {u0, v0, u1, v1, u2, v2}.  `face` is read for cubes only (may be NULL otherwise). */
 int pt_test_texture_sample(const float *rgb, int w, int h, const float *uv2, int n, float *rgb_out3);
 int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, float *uv_out2);
+/* bump mapping (pt_amd.h, pt_device.h "bump mapping"): the kernels' gradient, tangents and shading normal over host arrays.  One height map of
+ * w x h texels (row 0 = top); per hit kind[i] (0 sphere, 1 cube, 2 mesh) and 40 floats of `in`: {scale, outside (0 / 1), N (3), dir (3),
+ * transform (12, column-major 3 x 4)}, then sphere: the object-space hit point q; cube: q and the face (axis * 2 + (sign > 0), as a float);
+ * mesh: the barycentric u, v, the corner UVs u0 v0 u1 v1 u2 v2 and the object-space corners p0 p1 p2 (tangents: the library's own host code).
+ * out: 16 floats per hit {hu, hv, Pu (3), Pv (3), Ns (3), bumped (0 / 1), u, v, 0, 0}; Ns = N where the hit stays unbumped. */
+int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, const float *in, int n, float *out);
 
 #ifdef __cplusplus
 }

@@ -57,7 +57,7 @@ ABI_SYMBOLS = [
     "pt_ctx_create", "pt_ctx_make_current", "pt_ctx_current", "pt_ctx_destroy",
     "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_collective", "pt_group_set_meshes", "pt_group_init", "pt_group_iterate_batch",
     "pt_group_iterate", "pt_group_reduce", "pt_group_sync", "pt_group_readback", "pt_group_counters",
-    "pt_set_textures", "pt_group_set_textures",
+    "pt_set_textures", "pt_group_set_textures", "pt_set_bump_maps", "pt_group_set_bump_maps",
 ]
 PT_AMD_ABI_VERSION = 7
 # every symbol include/pt_amd_test.h declares: libpt_amd_test.so only -- the product library must NOT export them
@@ -69,6 +69,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
+    "pt_test_bump_normal",
 ]
 
 
@@ -88,6 +89,10 @@ class PtTexture(C.Structure):
 
 class PtTexBinding(C.Structure):
     _fields_ = [("geom", C.c_int32), ("texture", C.c_int32), ("ntris", C.c_int32), ("uvs", C.c_void_p)]
+
+
+class PtBumpBinding(C.Structure):
+    _fields_ = [("geom", C.c_int32), ("texture", C.c_int32), ("scale", C.c_float), ("ntris", C.c_int32), ("uvs", C.c_void_p)]
 
 
 class PtCounters(C.Structure):
@@ -143,6 +148,8 @@ def _bind(L, with_tests):
     L.pt_group_set_meshes.argtypes = [vp, C.POINTER(PtMesh), i32]
     L.pt_set_textures.argtypes = [C.POINTER(PtTexture), i32, C.c_size_t, C.POINTER(PtTexBinding), i32, C.c_size_t]
     L.pt_group_set_textures.argtypes = [vp, C.POINTER(PtTexture), i32, C.c_size_t, C.POINTER(PtTexBinding), i32, C.c_size_t]
+    L.pt_set_bump_maps.argtypes = [C.POINTER(PtBumpBinding), i32, C.c_size_t]
+    L.pt_group_set_bump_maps.argtypes = [vp, C.POINTER(PtBumpBinding), i32, C.c_size_t]
     L.pt_group_init.argtypes = [vp, vp, vp, i32, vp, i32, i32, C.POINTER(PtOptions)]
     L.pt_group_iterate_batch.argtypes = [vp, i32, i32, i32]
     L.pt_group_iterate.argtypes = [vp, i32, i32]
@@ -183,6 +190,7 @@ def _bind(L, with_tests):
         L.pt_test_sphere_group_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p, u64p, C.POINTER(C.c_int32)]
         L.pt_test_texture_sample.argtypes = [vp, i32, i32, vp, i32, vp]
         L.pt_test_texture_uv.argtypes = [i32, vp, vp, i32, vp]
+        L.pt_test_bump_normal.argtypes = [vp, i32, i32, vp, vp, i32, vp]
     return L
 
 
@@ -281,8 +289,10 @@ def host_lib():
             getattr(H, n).argtypes = [vp, C.c_int]
             getattr(H, n).restype = vp
         H.pth_scene_num_textures.argtypes = [vp]
-        for n in ("pth_scene_texture_width", "pth_scene_texture_height", "pth_scene_geom_texture"):
+        for n in ("pth_scene_texture_width", "pth_scene_texture_height", "pth_scene_geom_texture", "pth_scene_geom_bump"):
             getattr(H, n).argtypes = [vp, C.c_int]
+        H.pth_scene_geom_bump_scale.argtypes = [vp, C.c_int]
+        H.pth_scene_geom_bump_scale.restype = C.c_float
         H.pth_scene_texture_path.argtypes = [vp, C.c_int]
         H.pth_scene_texture_path.restype = C.c_char_p
         for n in ("pth_save_png", "pth_save_hdr"):
@@ -339,6 +349,9 @@ class Scene:
             self.textures.append(np.frombuffer(C.string_at(H.pth_scene_texture_rgb(h, i), 12 * tw * th), np.float32).reshape(th, tw, 3).copy())
             self.texture_paths.append(H.pth_scene_texture_path(h, i).decode())
         self.geom_textures = np.array([H.pth_scene_geom_texture(h, g) for g in range(ng)], np.int32)
+        # `BUMP <file> <scale>` lines: per geom the index of its height map among `textures` or -1, and its scale (0 where unbumped)
+        self.geom_bumps = np.array([H.pth_scene_geom_bump(h, g) for g in range(ng)], np.int32)
+        self.bump_scales = np.array([H.pth_scene_geom_bump_scale(h, g) for g in range(ng)], np.float32)
         w, hh = (int(v) for v in self.camera["resolution"][0])
         self.image = np.zeros((hh, w, 3), np.float32)   # RenderState::image (src/sceneStructs.h:53)
 
@@ -379,6 +392,7 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
     depth = scene.traceDepth if traceDepth is None else traceDepth
     set_meshes(getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None))
     set_textures(*_scene_textures(scene))
+    set_bump_maps(*_scene_bumps(scene))
     global _atexit_registered
     if not _atexit_registered:
         # an interpreter that exits with a live renderer (an exception between pathtrace and pathtraceFree): drain the streams
@@ -392,7 +406,7 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
     global _last_init
     _last_init = (cam, geoms, mats, depth, (shard_rank, shard_count, device, flags, lens_radius, focal_distance),
                   (getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None)),
-                  _scene_textures(scene))
+                  _scene_textures(scene), _scene_bumps(scene))
 
 
 def _mesh_array(meshes, normals=None, materials=None):
@@ -442,6 +456,37 @@ def _texture_arrays(textures, geom_textures=None, mesh_uvs=None):
         binds.append(PtTexBinding(g, k, 0 if u is None else len(u), None if u is None else u.ctypes.data))
     barr = (PtTexBinding * max(len(binds), 1))(*binds)
     return tarr, len(tex), barr, len(binds), (tex, uvs)
+
+
+def _scene_bumps(scene):
+    """(geom_bumps, bump_scales, mesh_uvs) of a Scene -- or of any object with those attributes; none: unbumped (a scene object without
+    them CLEARS the bump maps of an earlier one)"""
+    return (getattr(scene, "geom_bumps", None), getattr(scene, "bump_scales", None), getattr(scene, "mesh_uvs", None) or {})
+
+
+def _bump_arrays(geom_bumps=None, bump_scales=None, mesh_uvs=None):
+    """(PtBumpBinding array, count, the arrays they point into) for pt_set_bump_maps / pt_group_set_bump_maps.  A geom is bumped when
+    geom_bumps[g] >= 0 (an index into the registered textures), with scale bump_scales[g]; a bumped mesh geom carries its UVs from mesh_uvs[g]."""
+    gb = [] if geom_bumps is None else [int(x) for x in np.asarray(geom_bumps).reshape(-1)]
+    sc = np.zeros(len(gb), np.float32) if bump_scales is None else np.asarray(bump_scales, np.float32).reshape(-1)
+    binds, uvs = [], []
+    for g, k in enumerate(gb):
+        if k < 0:
+            continue
+        u = (mesh_uvs or {}).get(g)
+        u = None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 6)
+        uvs.append(u)
+        binds.append(PtBumpBinding(g, k, float(sc[g]), 0 if u is None else len(u), None if u is None else u.ctypes.data))
+    barr = (PtBumpBinding * max(len(binds), 1))(*binds)
+    return barr, len(binds), uvs
+
+
+def set_bump_maps(geom_bumps=None, bump_scales=None, mesh_uvs=None, L=None):
+    """pt_set_bump_maps for the next pathtraceInit: `geom_bumps` per geom the index of its height map among the textures of set_textures
+    or -1, `bump_scales` per geom its scale, `mesh_uvs` {geom index: (ntris, 6) corner UVs} for the bumped meshes.  None / empty clears."""
+    barr, nb, alive = _bump_arrays(geom_bumps, bump_scales, mesh_uvs)
+    L = L or lib()
+    _check(L.pt_set_bump_maps(barr, nb, C.sizeof(PtBumpBinding)), L)
 
 
 def set_textures(textures, geom_textures=None, mesh_uvs=None, L=None):
@@ -519,13 +564,14 @@ def debug_trace_paths(iteration, bounces, npixels):
     if _last_init is None:
         raise PtError("debug_trace_paths before pathtraceInit")
     T = test_lib()
-    cam, geoms, mats, depth, (rank, count, device, flags, lens_radius, focal_distance), meshes, textures = _last_init
+    cam, geoms, mats, depth, (rank, count, device, flags, lens_radius, focal_distance), meshes, textures, bumps = _last_init
     if _lib is T:                                    # (renderer_from_test_library: the renderer IS the test library's)
         own = False
     else:
         own = True
         set_meshes(*meshes, L=T)
         set_textures(*textures, L=T)
+        set_bump_maps(*bumps, L=T)
         opt = PtOptions(rank, count, device, flags & ~(PT_FLAG_TRACE_AHEAD | PT_FLAG_KERNEL_TIMING), 1, 1, None, None, lens_radius, focal_distance)
         _tcheck(T.pt_init(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), depth, C.byref(opt)))
     try:
@@ -583,6 +629,8 @@ class Group:
         _check(lib().pt_group_set_meshes(self.handle, arr, nm))
         tarr, nt, barr, nb, alive_t = _texture_arrays(*_scene_textures(scene))
         _check(lib().pt_group_set_textures(self.handle, tarr, nt, C.sizeof(PtTexture), barr, nb, C.sizeof(PtTexBinding)))
+        bbarr, nbb, alive_b = _bump_arrays(*_scene_bumps(scene))
+        _check(lib().pt_group_set_bump_maps(self.handle, bbarr, nbb, C.sizeof(PtBumpBinding)))
         opt = PtOptions(0, 1, -1, flags, pipeline_depth, max_batch, None, None, lens_radius, focal_distance)
         _check(lib().pt_group_init(self.handle, _p(cam), _p(geoms), len(geoms), _p(mats), len(mats),
                                    scene.traceDepth if traceDepth is None else traceDepth, C.byref(opt)))
@@ -738,6 +786,17 @@ def test_texture_uv(kind, inp, face=None):
     f = None if face is None else np.ascontiguousarray(face, np.int32)
     out = np.empty((len(a), 2), np.float32)
     _tcheck(test_lib().pt_test_texture_uv(kind, _p(a), None if f is None else _p(f), len(a), _p(out)))
+    return out
+
+
+def test_bump_normal(height, kind, inp):
+    """The kernels' bump mapping on the GPU (include/pt_amd_test.h, pt_test_bump_normal): height (H, W) float32 (row 0 = top), kind (n,) int32,
+    inp (n, 40) float32 -> (n, 16) float32 {hu, hv, Pu, Pv, Ns, bumped, u, v, 0, 0}."""
+    hm = np.ascontiguousarray(height, np.float32)
+    k = np.ascontiguousarray(kind, np.int32).reshape(-1)
+    a = np.ascontiguousarray(inp, np.float32).reshape(len(k), 40)
+    out = np.empty((len(k), 16), np.float32)
+    _tcheck(test_lib().pt_test_bump_normal(_p(hm), hm.shape[1], hm.shape[0], _p(k), _p(a), len(k), _p(out)))
     return out
 
 

@@ -51,6 +51,7 @@ using namespace ptk;
 
 static_assert(sizeof(PtGeom) == 236 && sizeof(PtMaterial) == 44 && sizeof(PtCamera) == 52,
               "layout must equal reference src/sceneStructs.h:18-47");
+static_assert(sizeof(PtBumpBinding) == 24, "PtBumpBinding: 24 bytes (include/pt_amd.h)");
 namespace {
 
 // =====================================================================================================
@@ -79,6 +80,21 @@ int fail(int code, const char *fmt, ...) {
 constexpr int kMaxSlots = 4;
 constexpr int kTexSizeMax = 16384;     // largest side of a texture (pt_set_textures)
 constexpr long long kTexTexelsMax = 1ll << 28;   // the textures of a scene hold fewer texels
+// A bumped mesh triangle's object-space tangents (ptd "bump mapping", mesh), fp32 in the order written there (this file is compiled
+// with -ffp-contract=off for the host too): tri = its corners p0 p1 p2 (9 floats), uv = u0 v0 u1 v1 u2 v2 -> {Tu, det != 0}, {Tv, 0}
+void meshTangents(const float *tri, const float *uv, float4 &tu, float4 &tv) {
+    const float e1[3] = {tri[3] - tri[0], tri[4] - tri[1], tri[5] - tri[2]};
+    const float e2[3] = {tri[6] - tri[0], tri[7] - tri[1], tri[8] - tri[2]};
+    const float du1 = uv[2] - uv[0], dv1 = uv[3] - uv[1], du2 = uv[4] - uv[0], dv2 = uv[5] - uv[1];
+    const float det = du1 * dv2 - du2 * dv1;
+    float a[3], b[3];
+    for (int k = 0; k < 3; ++k) {
+        a[k] = (e1[k] * dv2 - e2[k] * dv1) / det;
+        b[k] = (e2[k] * du1 - e1[k] * du2) / det;
+    }
+    tu = make_float4(a[0], a[1], a[2], det != 0.0f ? 1.0f : 0.0f);
+    tv = make_float4(b[0], b[1], b[2], 0.0f);
+}
 
 // One in-flight iteration: its own stream, path buffers, counters and deferred-radiance buffer.
 struct Slot {
@@ -126,7 +142,11 @@ struct State {
     ptd::TexGeom *dTexGeom = nullptr;
     int4 *dTexDesc = nullptr;
     float4 *dTexels = nullptr, *dTexUV = nullptr;
-    bool tex = false;       // a texture is bound to at least one primitive
+    bool tex = false;       // a texture is bound to at least one primitive (or a height map: BUMP forms are TEX forms)
+    // bump-mapped scenes (k_bounce<..., BUMP>): BounceArgs::bumpGeom / bumpUV / bumpTan
+    ptd::BumpGeom *dBumpGeom = nullptr;
+    float4 *dBumpUV = nullptr, *dBumpTan = nullptr;
+    bool bump = false;      // a height map is bound to at least one primitive
     bool mesh = false;      // the scene holds triangle meshes: the k_bounce<., false, ., true> variants
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
     int *dWalkIdx = nullptr, *dWalkRowOff = nullptr;
@@ -178,6 +198,9 @@ struct State {
     struct HostTexBinding { int geom = 0, texture = 0, ntris = 0; std::vector<float> uvs; };
     std::vector<HostTexture> textures;
     std::vector<HostTexBinding> texBindings;
+    // ... and the height maps registered by pt_set_bump_maps (texture: an index into `textures`)
+    struct HostBumpBinding { int geom = 0, texture = 0, ntris = 0; float scale = 0.0f; std::vector<float> uvs; };
+    std::vector<HostBumpBinding> bumpBindings;
 };
 
 // Renderer instances.  The reference keeps its renderer in file-static globals (src/pathtrace.cu:70-71: one per process, not
@@ -237,10 +260,22 @@ int resolve_events(std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms
 
 // The instantiation of k_bounce a launch takes: FIRST (camera rays), MANY (per-lane sphere lists: scenes with more than
 // kBinMax spheres), DOF (thin lens: the camera-ray launch only), MESH (scenes with triangle meshes).
-template <bool F, bool M, bool D, bool ME, bool PL = false, bool CU = false, bool GR = false, bool TX = false>
-const void *kb() { return reinterpret_cast<const void *>(k_bounce<F, M, D, ME, PL, CU, GR, TX>); }
+template <bool F, bool M, bool D, bool ME, bool PL = false, bool CU = false, bool GR = false, bool TX = false, bool BU = false>
+const void *kb() { return reinterpret_cast<const void *>(k_bounce<F, M, D, ME, PL, CU, GR, TX, BU>); }
+// bump-mapped scenes: the twelve TEX forms again, with BUMP
+const void *bounce_kernel_bump(bool first, bool dof) {
+    if (R().many && R().mesh) return first ? (dof ? kb<true, true, true, true, false, true, false, true, true>() : kb<true, true, false, true, false, true, false, true, true>())
+                                           : kb<false, true, false, true, false, true, false, true, true>();
+    if (R().many) return first ? (dof ? kb<true, true, true, false, false, true, false, true, true>() : kb<true, true, false, false, false, true, false, true, true>())
+                               : kb<false, true, false, false, false, true, false, true, true>();
+    if (R().mesh) return first ? (dof ? kb<true, false, true, true, false, false, false, true, true>() : kb<true, false, false, true, false, false, false, true, true>())
+                               : kb<false, false, false, true, false, false, false, true, true>();
+    return first ? (dof ? kb<true, false, true, false, false, false, false, true, true>() : kb<true, false, false, false, false, false, false, true, true>())
+                 : kb<false, false, false, false, false, false, false, true, true>();
+}
 // textured scenes: twelve instantiations of their own -- never PLAIN or GROUPS, and MANY always in the form that sweeps cubes too
 const void *bounce_kernel_tex(bool first, bool dof) {
+    if (R().bump) return bounce_kernel_bump(first, dof);
     if (R().many && R().mesh) return first ? (dof ? kb<true, true, true, true, false, true, false, true>() : kb<true, true, false, true, false, true, false, true>())
                                            : kb<false, true, false, true, false, true, false, true>();
     if (R().many) return first ? (dof ? kb<true, true, true, false, false, true, false, true>() : kb<true, true, false, false, false, true, false, true>())
@@ -324,6 +359,7 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     ba.walkMeshRows = R().dWalkMeshRows; ba.walkMeshLds = R().walkMeshLds;
     ba.sphGroups = R().dSphGroups;
     ba.texGeom = R().dTexGeom; ba.texDesc = R().dTexDesc; ba.texels = R().dTexels; ba.texUV = R().dTexUV;
+    ba.bumpGeom = R().dBumpGeom; ba.bumpUV = R().dBumpUV; ba.bumpTan = R().dBumpTan;
     void *kargs[] = {&ba};
     const bool first = depth == 1;
     // scenes with meshes: the walks of this bounce's rays, ahead of it (pt_mesh_walk.h)
@@ -642,14 +678,19 @@ void free_renderer() {
     if (R().dTexDesc) (void)hipFree(R().dTexDesc);
     if (R().dTexels) (void)hipFree(R().dTexels);
     if (R().dTexUV) (void)hipFree(R().dTexUV);
-    {   // (the registered meshes and textures outlive the renderer: see State::meshes)
+    if (R().dBumpGeom) (void)hipFree(R().dBumpGeom);
+    if (R().dBumpUV) (void)hipFree(R().dBumpUV);
+    if (R().dBumpTan) (void)hipFree(R().dBumpTan);
+    {   // (the registered meshes, textures and height maps outlive the renderer: see State::meshes)
         std::vector<ptm::HostMesh> keep = std::move(R().meshes);
         std::vector<State::HostTexture> keepTex = std::move(R().textures);
         std::vector<State::HostTexBinding> keepBind = std::move(R().texBindings);
+        std::vector<State::HostBumpBinding> keepBump = std::move(R().bumpBindings);
         R() = State();
         R().meshes = std::move(keep);
         R().textures = std::move(keepTex);
         R().texBindings = std::move(keepBind);
+        R().bumpBindings = std::move(keepBump);
     }
 }
 }  // namespace
@@ -683,6 +724,24 @@ int pt_set_meshes(const PtMesh *meshes, int nmeshes) {
         if (meshes[i].normals) m.normals.assign(meshes[i].normals, meshes[i].normals + 9 * (size_t)meshes[i].ntris);
         if (meshes[i].materials) m.mats.assign(meshes[i].materials, meshes[i].materials + (size_t)meshes[i].ntris);
         R().meshes.push_back(std::move(m));
+    }
+    return PT_OK;
+}
+
+int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes) {
+    if (binding_struct_bytes != sizeof(PtBumpBinding))
+        return fail(PT_ERR_INVALID, "pt_set_bump_maps: the caller's PtBumpBinding is %zu bytes, this library's %zu (ABI version %d here)",
+                    binding_struct_bytes, sizeof(PtBumpBinding), PT_AMD_ABI_VERSION);
+    if (nbindings < 0 || (nbindings && !bindings)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: null argument");
+    for (int i = 0; i < nbindings; ++i)
+        if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: binding %d: bad UVs", i);
+    // (indices, counts and the scale are checked by pt_init, against the scene)
+    R().bumpBindings.clear();
+    for (int i = 0; i < nbindings; ++i) {
+        State::HostBumpBinding b;
+        b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris; b.scale = bindings[i].scale;
+        if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
+        R().bumpBindings.push_back(std::move(b));
     }
     return PT_OK;
 }
@@ -763,6 +822,23 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                     return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for mesh geom %d of %zu", b.ntris, b.geom, hm_->tris.size() / 9);
             } else if (!b.uvs.empty() || b.ntris != 0) {
                 return fail(PT_ERR_INVALID, "pt_init: UVs given for geom %d, which is not a mesh", b.geom);
+            }
+        }
+        std::vector<char> bumped(ngeoms, 0);
+        for (size_t i = 0; i < R().bumpBindings.size(); ++i) {
+            const State::HostBumpBinding &b = R().bumpBindings[i];
+            if (b.geom < 0 || b.geom >= ngeoms) return fail(PT_ERR_INVALID, "pt_init: bump binding %zu names geom %d of %d", i, b.geom, ngeoms);
+            if (b.texture < 0 || b.texture >= (int)R().textures.size())
+                return fail(PT_ERR_INVALID, "pt_init: bump binding %zu names texture %d of %zu", i, b.texture, R().textures.size());
+            if (bumped[b.geom]++) return fail(PT_ERR_INVALID, "pt_init: geom %d has two bump bindings", b.geom);
+            if (!std::isfinite(b.scale)) return fail(PT_ERR_INVALID, "pt_init: bump binding %zu has a non-finite scale", i);
+            if (geoms[b.geom].type == PT_MESH) {
+                const ptm::HostMesh *hm_ = mesh_of(b.geom);
+                if (b.uvs.empty()) return fail(PT_ERR_INVALID, "pt_init: bumped mesh geom %d has no UVs", b.geom);
+                if ((size_t)b.ntris * 9 != hm_->tris.size())
+                    return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for bumped mesh geom %d of %zu", b.ntris, b.geom, hm_->tris.size() / 9);
+            } else if (!b.uvs.empty() || b.ntris != 0) {
+                return fail(PT_ERR_INVALID, "pt_init: UVs given for bumped geom %d, which is not a mesh", b.geom);
             }
         }
     }
@@ -1127,7 +1203,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     HIPCHECK(hipMalloc(&R().dwalls, hw.size() * sizeof(WallBox)));
     HIPCHECK(hipMemcpy(R().dwalls, hw.data(), hw.size() * sizeof(WallBox), hipMemcpyHostToDevice));
     R().mesh = !meshRecs.empty();
-    R().tex = !R().texBindings.empty();
+    R().bump = !R().bumpBindings.empty();
+    R().tex = !R().texBindings.empty() || R().bump;
     if (R().tex) {         // every texel one float4, the textures one after another; per primitive its TexGeom; per textured triangle two float4
         std::vector<int4> desc;
         std::vector<float4> texels, uv;
@@ -1158,6 +1235,36 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         HIPCHECK(hipMemcpy(R().dTexels, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice));
         HIPCHECK(hipMalloc(&R().dTexUV, uv.size() * sizeof(float4)));
         HIPCHECK(hipMemcpy(R().dTexUV, uv.data(), uv.size() * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    if (R().bump) {        // per primitive its BumpGeom; per bumped triangle two float4 of corner UVs and two of tangents (a mesh's rows of its own,
+                           // even where its texture binding carries the same UVs)
+        std::vector<ptd::BumpGeom> bg(ngeoms ? ngeoms : 1, ptd::BumpGeom{-1, 0, 0, 0});
+        std::vector<float4> uv, tan;
+        for (const State::HostBumpBinding &b : R().bumpBindings) {
+            bg[b.geom].tex = b.texture;
+            memcpy(&bg[b.geom].scaleBits, &b.scale, 4);
+            if (b.uvs.empty()) continue;
+            const ptm::HostMesh *hm_ = mesh_of(b.geom);
+            bg[b.geom].uvBase = (int)(uv.size() / 2);
+            bg[b.geom].triBase = (int)triBase[b.geom];
+            for (int f = 0; f < b.ntris; ++f) {
+                const float *c = b.uvs.data() + 6 * (size_t)f;
+                uv.push_back(make_float4(c[0], c[1], c[2], c[3]));
+                uv.push_back(make_float4(c[4], c[5], 0.0f, 0.0f));
+                float4 tu, tv;
+                meshTangents(hm_->tris.data() + 9 * (size_t)f, c, tu, tv);
+                tan.push_back(tu);
+                tan.push_back(tv);
+            }
+            if (uv.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many bumped triangles");
+        }
+        if (uv.empty()) { uv.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f)); tan.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f)); }
+        HIPCHECK(hipMalloc(&R().dBumpGeom, bg.size() * sizeof(ptd::BumpGeom)));
+        HIPCHECK(hipMemcpy(R().dBumpGeom, bg.data(), bg.size() * sizeof(ptd::BumpGeom), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc(&R().dBumpUV, uv.size() * sizeof(float4)));
+        HIPCHECK(hipMemcpy(R().dBumpUV, uv.data(), uv.size() * sizeof(float4), hipMemcpyHostToDevice));
+        HIPCHECK(hipMalloc(&R().dBumpTan, tan.size() * sizeof(float4)));
+        HIPCHECK(hipMemcpy(R().dBumpTan, tan.data(), tan.size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     if (R().mesh) {
         HIPCHECK(hipMalloc(&R().dMeshRecs, (meshRecs.size() + 4) * sizeof(ptd::MeshUnit)));     // (+ 4: a walk may read the record behind the last one)

@@ -1141,6 +1141,77 @@ struct TexGeom {
 };
 static_assert(sizeof(TexGeom) == 16, "one dwordx4");
 
+// ---- bump mapping (PBRT 10.5.1; a README extra the reference names -- "combine with texture mapping" -- and holds no code for, so the
+// semantics are build-defined).  A height map (a registered texture, channel 0) and a scale s bound to a primitive tilt the normal it is
+// shaded with; the walks, the new ray's origin offset, `outside`, eta, emission, the texture colour and the random draws stay.  Every fp32
+// operation is one IEEE operation (-ffp-contract=off), in the order written; tests/bump_ref.py restates it in numpy bit for bit:
+//   gradient   h(u, v) = textureSample(u, v).x; hu = (s * (h(u + 1 / W, v) - h(u - 1 / W, v))) * (W * 0.5), hv the same along v with H
+//   tangents   Pu = L Tu, Pv = L Tv with L the transform's linear part: (L T).x = (m0 * T.x + m3 * T.y) + m6 * T.z (mulL)
+//     cube     face axis a: Tu = e[(a + 1) % 3], Tv = e[(a + 2) % 3] (cubeUV): Pu, Pv are L's columns, read, not multiplied
+//     sphere   d = normalize(q), rho = sqrt(d.x * d.x + d.z * d.z); Tu = (pi * -d.z, 0, pi * d.x),
+//              Tv = (pi/2 * ((-d.y * d.x) / rho), pi/2 * rho, pi/2 * ((-d.y * d.z) / rho)) (pi, pi/2: kPiF, kHalfPi)
+//     mesh     per triangle on the host (meshTangents): E1 = p1 - p0, E2 = p2 - p0, du1 = u1 - u0, dv1 = v1 - v0, du2 = u2 - u0,
+//              dv2 = v2 - v0, det = du1 * dv2 - du2 * dv1; Tu = (E1 * dv2 - E2 * dv1) / det, Tv = (E2 * du1 - E1 * du2) / det
+//              (per component, the divisions last)
+//   normal     N the unit normal shaded today (facing the ray; a mesh's interpolated one): J = dot(N, cross(Pu, Pv)),
+//              a = cross(Pv, N) * hu + cross(N, Pu) * hv, g = (a.x / J, a.y / J, a.z / J); Ns = normalize(N - g) outside, normalize(N + g)
+//              inside.  g does not change sign with N, so both sides see one surface, displaced along the outward normal.
+//   unbumped   (N kept, bit for bit) hu == 0 && hv == 0; J == 0; g or Ns not finite; rho == 0 (the poles); det == 0; dot(Ns, dir) >= 0.
+// k_bounce<..., BUMP> then shades with Ns where it used N -- refraction (c, Fresnel, refract), mirror reflect, the SPECEX lobe and its
+// fallback test, the diffuse hemisphere (frame hemisphereFrame(Ns), cubes included) and the direct-lighting cosine -- and ends, adding
+// nothing, a path whose new direction lies on the far side of the GEOMETRIC surface from its origin offset: dot(d, N) <= 0 (reflection,
+// diffuse, lobe, light rays) or dot(d, N) >= 0 (refraction).
+__device__ __forceinline__ float heightSample(const float4 *texels, int off, int W, int H, float u, float v) {
+    return textureSample(texels, off, W, H, u, v).x;
+}
+__device__ __forceinline__ void bumpGradient(const float4 *texels, int off, int W, int H, float s, float u, float v, float &hu, float &hv) {
+    const float fw = (float)W, fh = (float)H;
+    const float du = 1.0f / fw, dv = 1.0f / fh;
+    const float hr = heightSample(texels, off, W, H, u + du, v), hl = heightSample(texels, off, W, H, u - du, v);
+    const float ht = heightSample(texels, off, W, H, u, v + dv), hb = heightSample(texels, off, W, H, u, v - dv);
+    hu = (s * (hr - hl)) * (fw * 0.5f);
+    hv = (s * (ht - hb)) * (fh * 0.5f);
+}
+// the linear part of a column-major transform (GeomDev::xf) times a vector
+template <typename P>
+__device__ __forceinline__ F3 mulL(P m, F3 v) {
+    return f3((m[0] * v.x + m[3] * v.y) + m[6] * v.z, (m[1] * v.x + m[4] * v.y) + m[7] * v.z, (m[2] * v.x + m[5] * v.y) + m[8] * v.z);
+}
+// object-space tangents of a sphere hit at q; false at the poles
+__device__ __forceinline__ bool sphereTangents(F3 q, F3 &Tu, F3 &Tv) {
+    const F3 d = normalize(q);
+    const float rho = __builtin_sqrtf(d.x * d.x + d.z * d.z);
+    Tu = f3(kPiF * -d.z, 0.0f, kPiF * d.x);
+    Tv = f3(kHalfPi * ((-d.y * d.x) / rho), kHalfPi * rho, kHalfPi * ((-d.y * d.z) / rho));
+    return rho != 0.0f;
+}
+// a cube face's world tangents: columns (a + 1) % 3 and (a + 2) % 3 of the transform
+template <typename P>
+__device__ __forceinline__ void cubeTangents(P m, int face, F3 &Pu, F3 &Pv) {
+    const int a = face >> 1;
+    const int cu = a == 2 ? 0 : a + 1, cv = a == 0 ? 2 : a - 1;
+    Pu = f3(m[3 * cu], m[3 * cu + 1], m[3 * cu + 2]);
+    Pv = f3(m[3 * cv], m[3 * cv + 1], m[3 * cv + 2]);
+}
+// the shading normal; false (Ns untouched): the hit stays unbumped
+__device__ __forceinline__ bool bumpNormal(F3 N, F3 Pu, F3 Pv, float hu, float hv, bool outside, F3 dir, F3 &Ns) {
+    const float J = dot(N, cross(Pu, Pv));
+    const F3 a = cross(Pv, N) * hu + cross(N, Pu) * hv;
+    const F3 g = f3(a.x / J, a.y / J, a.z / J);
+    const F3 n = normalize(outside ? N - g : N + g);
+    const bool fin = __builtin_isfinite(g.x) && __builtin_isfinite(g.y) && __builtin_isfinite(g.z) && __builtin_isfinite(n.x) &&
+                     __builtin_isfinite(n.y) && __builtin_isfinite(n.z);
+    const bool ok = !(hu == 0.0f && hv == 0.0f) && J != 0.0f && fin && dot(n, dir) < 0.0f;
+    if (ok) Ns = n;
+    return ok;
+}
+// per-primitive bump binding (k_bounce<..., BUMP>): height texture (-1: none), the scale's bits, the mesh's first row of
+// BounceArgs::bumpUV / bumpTan and the unit of its first triangle record
+struct BumpGeom {
+    int tex, scaleBits, uvBase, triBase;
+};
+static_assert(sizeof(BumpGeom) == 16, "one dwordx4");
+
 // Per-geom record staged in LDS for the per-lane lookups that follow the nearest-hit loop: the sphere's normal matrix
 // (12 floats), the material index, the type and the cube's six face frames.  Lanes of a wave index different geoms, so
 // the row stride is 76 words: consecutive rows start 12 banks apart and 8 different rows are conflict-free

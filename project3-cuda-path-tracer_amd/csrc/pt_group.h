@@ -468,6 +468,17 @@ int pt_group_set_meshes(PtGroup *g, const PtMesh *meshes, int nmeshes) {
     return PT_OK;
 }
 
+int pt_group_set_bump_maps(PtGroup *g, const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes) {
+    if (!g) return fail(PT_ERR_INVALID, "pt_group_set_bump_maps: null group");
+    CurrentGuard guard;
+    for (PtContext *c : g->ctx) {
+        t_ctx = &c->st;
+        int rc = pt_set_bump_maps(bindings, nbindings, binding_struct_bytes);
+        if (rc) return rc;
+    }
+    return PT_OK;
+}
+
 int pt_group_set_textures(PtGroup *g, const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings,
                           int nbindings, size_t binding_struct_bytes) {
     if (!g) return fail(PT_ERR_INVALID, "pt_group_set_textures: null group");

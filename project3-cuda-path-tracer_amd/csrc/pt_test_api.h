@@ -942,3 +942,31 @@ int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, fl
     DOWN(uv_out2, o, (size_t)n * 2);
     return PT_OK;
 }
+
+int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, const float *in, int n, float *out) {
+    NEED_GPU();
+    if (w < 1 || h < 1 || w > kTexSizeMax || h > kTexSizeMax || !height || n < 0 || (n && (!kind || !in || !out)))
+        return fail(PT_ERR_INVALID, "pt_test_bump_normal: bad argument");
+    if (n == 0) return PT_OK;
+    std::vector<float4> tx((size_t)w * h), tan(2 * (size_t)n, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    for (size_t q = 0; q < tx.size(); ++q) tx[q] = make_float4(height[q], height[q], height[q], 0.0f);
+    for (int i = 0; i < n; ++i) {
+        if (kind[i] < 0 || kind[i] > 2) return fail(PT_ERR_INVALID, "pt_test_bump_normal: kind %d", kind[i]);
+        const float *e = in + 40 * (size_t)i;
+        if (kind[i] == 1 && !(e[23] >= 0.0f && e[23] <= 5.0f && e[23] == (float)(int)e[23]))
+            return fail(PT_ERR_INVALID, "pt_test_bump_normal: face %g", e[23]);
+        if (kind[i] == 2) meshTangents(e + 28, e + 22, tan[2 * (size_t)i], tan[2 * (size_t)i + 1]);
+    }
+    DevBuf<float4> t, tg;
+    DevBuf<float> a, o;
+    DevBuf<int> k;
+    UP(t, tx.data(), tx.size());
+    UP(tg, tan.data(), tan.size());
+    UP(a, in, (size_t)n * 40);
+    UP(k, kind, n);
+    int rc = o.alloc((size_t)n * 16); if (rc) return rc;
+    hipLaunchKernelGGL(k_test_bump_normal, GRID(n), t.p, w, h, k.p, a.p, tg.p, n, o.p);
+    HIPCHECK(hipDeviceSynchronize());
+    DOWN(out, o, (size_t)n * 16);
+    return PT_OK;
+}

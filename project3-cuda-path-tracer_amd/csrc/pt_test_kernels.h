@@ -793,6 +793,43 @@ __global__ void k_test_texture_sample(const float4 *texels, int w, int h, const 
     const F3 c = textureSample(texels, 0, w, h, uv[2 * i], uv[2 * i + 1]);
     out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
 }
+// one hit per thread: in = 40 floats {scale, outside, N, dir, xf (12, column-major), then sphere q / cube q, face / mesh bary u v, corner
+// UVs}; tan = the host's mesh tangents (meshTangents); out = 16 floats {hu, hv, Pu, Pv, Ns, bumped, u, v, 0, 0}
+__global__ void k_test_bump_normal(const float4 *texels, int w, int h, const int *kind, const float *in, const float4 *tan, int n, float *out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *e = in + 40 * (size_t)i;
+    const F3 N = f3(e[2], e[3], e[4]), dir = f3(e[5], e[6], e[7]);
+    const float *xf = e + 8;
+    float u, v;
+    F3 Pu, Pv;
+    bool tok = true;
+    if (kind[i] == 2) {
+        meshUV(make_float4(e[22], e[23], e[24], e[25]), make_float2(e[26], e[27]), e[20], e[21], u, v);
+        const float4 tu = tan[2 * (size_t)i], tv = tan[2 * (size_t)i + 1];
+        tok = tu.w != 0.0f;
+        Pu = mulL(xf, f3(tu.x, tu.y, tu.z));
+        Pv = mulL(xf, f3(tv.x, tv.y, tv.z));
+    } else if (kind[i] == 1) {
+        const int face = (int)e[23];
+        cubeUV(f3(e[20], e[21], e[22]), face, u, v);
+        cubeTangents(xf, face, Pu, Pv);
+    } else {
+        const F3 q = f3(e[20], e[21], e[22]);
+        sphereUV(q, u, v);
+        F3 Tu, Tv;
+        tok = sphereTangents(q, Tu, Tv);
+        Pu = mulL(xf, Tu);
+        Pv = mulL(xf, Tv);
+    }
+    float hu, hv;
+    bumpGradient(texels, 0, w, h, e[0], u, v, hu, hv);
+    F3 Ns = N;
+    const bool b = tok && bumpNormal(N, Pu, Pv, hu, hv, e[1] != 0.0f, dir, Ns);
+    float *o = out + 16 * (size_t)i;
+    o[0] = hu; o[1] = hv; o[2] = Pu.x; o[3] = Pu.y; o[4] = Pu.z; o[5] = Pv.x; o[6] = Pv.y; o[7] = Pv.z;
+    o[8] = Ns.x; o[9] = Ns.y; o[10] = Ns.z; o[11] = b ? 1.0f : 0.0f; o[12] = u; o[13] = v; o[14] = 0.0f; o[15] = 0.0f;
+}
 __global__ void k_test_texture_uv(int kind, const float *in, const int *face, int n, float *out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

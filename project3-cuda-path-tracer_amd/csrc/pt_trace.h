@@ -448,6 +448,12 @@ struct BounceArgs {
     const int4 *texDesc;
     const float4 *texels;
     const float4 *texUV;
+    // ---- bump-mapped scenes (k_bounce<..., BUMP>; nullptr otherwise): per primitive its ptd::BumpGeom (the height map indexes texDesc), per
+    // bumped mesh triangle its corner UVs as texUV's rows are, and its object-space tangents {Tu, det != 0}, {Tv, 0} (pt_init, in fp32:
+    // ptd "bump mapping"); both at row BumpGeom::uvBase + the triangle's ordinal
+    const ptd::BumpGeom *bumpGeom;
+    const float4 *bumpUV;
+    const float4 *bumpTan;
 };
 typedef const PT_CAS BounceArgs *ArgsPtr;
 typedef const PT_CAS GeomDev *GeomPtr;
@@ -495,7 +501,10 @@ static_assert(sizeof(CullGroup) == 32 && offsetof(GeomDev, cullFlags) - offsetof
 // TEX: a texture is bound to at least one primitive -- the hit's texel scales its material's colour (ptd::textureSample; pt_init picks
 // these instantiations for textured scenes only, never with PLAIN or GROUPS, so that an untextured scene runs exactly the code it ran before).
 // Their later bounces of scenes that are not sphere-heavy run one workgroup per CU fewer: the sampler's registers would otherwise spill.
-template <bool FIRST, bool MANY, bool DOF = false, bool MESH = false, bool PLAIN = false, bool CUBES = false, bool GROUPS = false, bool TEX = false>
+// BUMP (TEX forms only): a height map is bound to at least one primitive -- the hit is shaded with the tilted normal (ptd "bump mapping").
+// Two of their camera-ray forms (pinhole without meshes, lens with meshes) run one workgroup per CU fewer again, for the same reason.
+template <bool FIRST, bool MANY, bool DOF = false, bool MESH = false, bool PLAIN = false, bool CUBES = false, bool GROUPS = false, bool TEX = false,
+          bool BUMP = false>
 #ifndef PT_MESH_WG_FIRST
 #define PT_MESH_WG_FIRST 7
 #define PT_MESH_WG_NEXT 7
@@ -506,11 +515,13 @@ template <bool FIRST, bool MANY, bool DOF = false, bool MESH = false, bool PLAIN
 #ifndef PT_CUBES_WG
 #define PT_CUBES_WG 4
 #endif
-__global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG) : (MESH ? (MANY ? 4 : (FIRST ? PT_MESH_WG_FIRST : PT_MESH_WG_NEXT)) : (DOF ? 5 : (MANY ? (FIRST ? 7 : (GROUPS ? PT_GROUPS_WG : 6)) : 8))) - ((TEX && !MANY && !FIRST) ? 1 : 0)) void k_bounce(BounceArgs argsByValue) {
+__global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG) : (MESH ? (MANY ? 4 : (FIRST ? PT_MESH_WG_FIRST : PT_MESH_WG_NEXT)) : (DOF ? 5 : (MANY ? (FIRST ? 7 : (GROUPS ? PT_GROUPS_WG : 6)) : 8))) - ((TEX && !MANY && !FIRST) ? 1 : 0) -
+                                 ((BUMP && !MANY && FIRST && DOF == MESH) ? 1 : 0)) void k_bounce(BounceArgs argsByValue) {
     static_assert(MANY || !CUBES, "swept cubes only exist where primitives are swept");
     static_assert(!GROUPS || (MANY && !MESH && !DOF), "groups: sphere-heavy scenes without meshes (the camera-ray bounce: its pinhole form)");
     static_assert(FIRST || !DOF, "the lens only concerns the camera-ray bounce");
     static_assert(!TEX || (!PLAIN && !GROUPS && (!MANY || CUBES)), "textured scenes: the general forms (MANY: the one that sweeps both types)");
+    static_assert(!BUMP || TEX, "bump-mapped scenes: the TEX forms");
     (void)argsByValue;
     const ArgsPtr kargs = (ArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
     censusEnter();                       // (instrumented build only)
@@ -1484,6 +1495,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                                                    : s_nan;
                 const float *const fv = faceOk ? ghFrame + 9 * face : nanRow;
                 const F3 N = isSphere ? hitNormalSphere(ghNm, nsrc, outside) : f3(fv[0], fv[1], fv[2]);
+                F3 Ns = N;                                       // the normal the hit is shaded with (BUMP: tilted by the height map)
+                bool bumped = false;
                 F3 mcol = mcolMany;
                 if (!MANY) {
                     uint32_t off = (uint32_t)(reinterpret_cast<const unsigned char *>(hrec1) - smem);
@@ -1515,6 +1528,40 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         }
                         const int4 td = A->texDesc[tg.x];                         // {first texel, W, H, 0}
                         mcol = mcol * textureSample(A->texels, td.x, td.y, td.z, u, v);
+                    }
+                    if (BUMP) {
+                        // a bound height map tilts the shading normal (ptd "bump mapping"): the hit's (u, v), the world tangents there,
+                        // the height's central differences
+                        const int4 bg = *reinterpret_cast<const int4 *>(A->bumpGeom + hit);    // BumpGeom {tex, scale bits, uvBase, triBase}
+                        if (bg.x >= 0) {
+                            const float *xf = A->ggeoms[hit].xf;
+                            float u, v;
+                            F3 Pu, Pv;
+                            bool tok = true;
+                            if (MESH && tg.y == 2) {
+                                const size_t row = (size_t)bg.z + (texUnit - (uint32_t)bg.w) / (uint32_t)kMeshTriUnits;
+                                const float4 c01 = A->bumpUV[2 * row], c2 = A->bumpUV[2 * row + 1];
+                                meshUV(c01, make_float2(c2.x, c2.y), texBary.x, texBary.y, u, v);
+                                const float4 tu = A->bumpTan[2 * row], tv = A->bumpTan[2 * row + 1];
+                                tok = tu.w != 0.0f;                                        // (det == 0: unbumped)
+                                Pu = mulL(xf, f3(tu.x, tu.y, tu.z));
+                                Pv = mulL(xf, f3(tv.x, tv.y, tv.z));
+                            } else if (tg.y == 1) {
+                                const F3 q = mulMV(A->ggeoms[hit].inv, P, 1.0f);
+                                cubeUV(q, faceOk ? face : 0, u, v);
+                                cubeTangents(xf, faceOk ? face : 0, Pu, Pv);
+                            } else {
+                                sphereUV(nsrc, u, v);
+                                F3 Tu, Tv;
+                                tok = sphereTangents(nsrc, Tu, Tv);
+                                Pu = mulL(xf, Tu);
+                                Pv = mulL(xf, Tv);
+                            }
+                            const int4 td = A->texDesc[bg.x];
+                            float hu, hv;
+                            bumpGradient(A->texels, td.x, td.y, td.z, __int_as_float(bg.y), u, v, hu, hv);
+                            bumped = tok && bumpNormal(N, Pu, Pv, hu, hv, outside, dir, Ns);
+                        }
                     }
                 }
                 const MaterialDev &M = smats[ghMaterial];       // (the fields of the rarer branches)
@@ -1552,9 +1599,10 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     const F3 scol = f3(M.specColor[0], M.specColor[1], M.specColor[2]);
                     F3 ndir = dir, norg;
                     bool diffuse = false;                        // the hemisphere is sampled at one place, after the branches
+                    bool through = false;                        // (BUMP: the new ray is the transmitted one)
                     if (!PLAIN && mRefr > 0.0f) {
                         const float eta = outside ? M.invIor : M.ior;
-                        const float c = dot(N, dir);
+                        const float c = dot(Ns, dir);
                         const float k = 1.0f - eta * eta * (1.0f - c * c);
                         const float u = u01(rng);
                         bool doReflect = true;
@@ -1568,11 +1616,12 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             doReflect = u < fres;
                         }
                         if (doReflect) {
-                            ndir = reflect(dir, N);
+                            ndir = reflect(dir, Ns);
                             norg = P + N * 0.001f;
                             col = col * scol;
                         } else {
-                            ndir = refract(dir, N, eta);
+                            ndir = refract(dir, Ns, eta);
+                            through = true;
                             norg = P - N * 0.001f;
                             col = col * mcol;
                         }
@@ -1582,8 +1631,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         if (!PLAIN && (hotNow() & kHotMixWeighted)) col = col * 2.0f;
                         const float u = u01(rng);
                         if (u < 0.5f) {
-                            ndir = reflect(dir, N);
-                            if (!PLAIN && M.invSpecExp1 > 0.0f) ndir = specularLobeDirection(ndir, N, M.invSpecExp1, rng);   // SPECEX > 0
+                            ndir = reflect(dir, Ns);
+                            if (!PLAIN && M.invSpecExp1 > 0.0f) ndir = specularLobeDirection(ndir, Ns, M.invSpecExp1, rng);   // SPECEX > 0
                             col = col * scol;
                         } else {
                             diffuse = true;
@@ -1624,7 +1673,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             const F3 target = mulMV(m, f3(bx[0] + ux * bx[3], bx[1] + uy * bx[4], bx[2] + uz * bx[5]), 1.0f);
                             const F3 toward = target - norg;
                             ndir = normalize(toward);
-                            float w = dot(N, ndir);
+                            float w = dot(Ns, ndir);
                             w = w > 0.0f ? w : 0.0f;
                             // ... and by the share of the hemisphere the emitter's bounding ball covers, min(1, rho^2 / r^2)
                             float cover = rho2 / dot(toward, toward);
@@ -1644,13 +1693,13 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         float up, cOver, sOver;
                         hemisphereDraws(rng, up, cOver, sOver);
                         F3 p1, p2;                                // the sampler's tangent frame: computed for a sphere, looked up for a cube face
-                        if (isSphere) {
-                            hemisphereFrame(N, p1, p2);
+                        if (isSphere || (BUMP && bumped)) {      // (a face's tabled frame belongs to its unbumped normal)
+                            hemisphereFrame(Ns, p1, p2);
                         } else {
                             p1 = f3(fv[3], fv[4], fv[5]);
                             p2 = f3(fv[6], fv[7], fv[8]);
                         }
-                        ndir = hemisphereCombine(N, p1, p2, up, cOver, sOver);
+                        ndir = hemisphereCombine(Ns, p1, p2, up, cOver, sOver);
                     }
                     org = norg;
                     dir = ndir;
@@ -1729,6 +1778,11 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             }
                         }
                     }
+                    // BUMP, the geometric side rule: a tilted normal can send the new ray to the far side of the surface from its origin
+                    // offset (P + N 0.001 / P - N 0.001 for the transmitted ray).  That path ends here, adding nothing, like one that leaves
+                    // the scene -- so every ray that lives on leaves towards its origin's side, as without a bump map, and the wall bins, the
+                    // half-line certificates and the candidacy bit above keep the guarantee they reason from (DESIGN, `BUMP`)
+                    if (BUMP && bumped && (through ? dot(ndir, N) >= 0.0f : dot(ndir, N) <= 0.0f)) fl = 4u;
                 }
             }
         }

@@ -49,6 +49,9 @@ int pth_scene_texture_height(void *s, int i) { return static_cast<Scene *>(s)->t
 const float *pth_scene_texture_rgb(void *s, int i) { return static_cast<Scene *>(s)->textures[i].rgb.data(); }
 const char *pth_scene_texture_path(void *s, int i) { return static_cast<Scene *>(s)->textures[i].path.c_str(); }
 int pth_scene_geom_texture(void *s, int g) { return static_cast<Scene *>(s)->geomTextures[g]; }
+// height maps (`BUMP <file> <scale>`): per geom the index of its texture or -1, and its scale
+int pth_scene_geom_bump(void *s, int g) { return static_cast<Scene *>(s)->geomBumps[g]; }
+float pth_scene_geom_bump_scale(void *s, int g) { return static_cast<Scene *>(s)->bumpScales[g]; }
 void pth_scene_set_resolution(void *s, int w, int h) { static_cast<Scene *>(s)->setResolution(w, h); }
 
 // saveImage (reference src/main.cpp:49-70) on a W*H*3 running sum: /samples, X mirror, PNG

@@ -92,6 +92,25 @@ void pathtraceInit(Scene *scene) {
         bindings.push_back(b);
     }
 #endif
+    // `BUMP <file> <scale>` lines: per bump-mapped object its height map (one of the textures above), its scale and a mesh's corner UVs
+    std::vector<PtBumpBinding> bumps;
+#ifdef PT_SCENE_HAS_BUMPS
+    for (size_t g = 0; g < scene->geomBumps.size(); ++g) {
+        if (scene->geomBumps[g] < 0) continue;
+        PtBumpBinding b;
+        b.geom = (int)g;
+        b.texture = scene->geomBumps[g];
+        b.scale = scene->bumpScales[g];
+        b.ntris = 0;
+        b.uvs = NULL;
+        for (size_t i = 0; i < scene->meshes.size(); ++i)
+            if (scene->meshes[i].geom == (int)g) {
+                b.ntris = (int)(scene->meshes[i].tris.size() / 9);
+                b.uvs = scene->meshes[i].uvs.empty() ? NULL : scene->meshes[i].uvs.data();
+            }
+        bumps.push_back(b);
+    }
+#endif
     int members = 1;
     if (const char *e = getenv("PT_AMD_DEVICES")) members = atoi(e);
     if (members >= 2) {
@@ -103,10 +122,12 @@ void pathtraceInit(Scene *scene) {
         checkPtError(pt_group_set_meshes(group, meshes.empty() ? NULL : meshes.data(), (int)meshes.size()), "pathtraceInit");
         checkPtError(pt_group_set_textures(group, textures.empty() ? NULL : textures.data(), (int)textures.size(), sizeof(PtTexture),
                                            bindings.empty() ? NULL : bindings.data(), (int)bindings.size(), sizeof(PtTexBinding)), "pathtraceInit");
+        checkPtError(pt_group_set_bump_maps(group, bumps.empty() ? NULL : bumps.data(), (int)bumps.size(), sizeof(PtBumpBinding)), "pathtraceInit");
     } else {
         checkPtError(pt_set_meshes_sized(meshes.empty() ? NULL : meshes.data(), (int)meshes.size(), sizeof(PtMesh)), "pathtraceInit");
         checkPtError(pt_set_textures(textures.empty() ? NULL : textures.data(), (int)textures.size(), sizeof(PtTexture),
                                      bindings.empty() ? NULL : bindings.data(), (int)bindings.size(), sizeof(PtTexBinding)), "pathtraceInit");
+        checkPtError(pt_set_bump_maps(bumps.empty() ? NULL : bumps.data(), (int)bumps.size(), sizeof(PtBumpBinding)), "pathtraceInit");
     }
     int status;
     for (;;) {

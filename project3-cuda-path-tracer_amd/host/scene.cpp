@@ -8,10 +8,13 @@
 //   * CRLF / CR / LF line ends; '//' comment lines are simply unknown keywords
 //   * `TEXTURE <file>` in an OBJECT block (next to TRANS / ROTAT / SCALE; path relative to the scene file) binds an image texture to the
 //     object (loadTexture); the reference's loader skips the unknown keyword, so a textured scene still loads there, untextured
+//   * `BUMP <file> <scale>` likewise binds a height map (any texture file; channel 0) and its scale: the files are shared with TEXTURE by
+//     resolved path; a missing or non-finite scale fails the load; the reference's loader skips this keyword too
 // Unlike the reference, fields whose keyword is missing are zero instead of uninitialised.
 #include "scene.h"
 
 #include <cctype>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -251,6 +254,27 @@ Scene::Scene(std::string filename, bool verbose_) : verbose(verbose_) {
             std::cout << "ERROR: object " << meshes[i].geom << " is textured and its mesh has no texture coordinates - aborting!" << std::endl;
             throw std::runtime_error("textured mesh without texture coordinates");
         }
+    // ... and so does a bump-mapped one
+    geomBumps.resize(geoms.size(), -1);
+    bumpScales.resize(geoms.size(), 0.0f);
+    for (size_t i = 0; i < meshes.size(); ++i)
+        if (geomBumps[meshes[i].geom] >= 0 && meshes[i].uvs.empty()) {
+            std::cout << "ERROR: object " << meshes[i].geom << " is bump-mapped and its mesh has no texture coordinates - aborting!" << std::endl;
+            throw std::runtime_error("bump-mapped mesh without texture coordinates");
+        }
+}
+
+int Scene::textureIndex(const std::string &path) {
+    for (size_t j = 0; j < textures.size(); ++j)
+        if (textures[j].path == path) return (int)j;
+    try {
+        textures.push_back(loadTexture(path));
+    } catch (const std::exception &e) {
+        // like an unreadable mesh: a texture that cannot be read is a scene that cannot be rendered
+        std::cout << "ERROR: " << e.what() << " - aborting!" << std::endl;
+        throw;
+    }
+    return (int)textures.size() - 1;
 }
 
 Scene::~Scene() {}
@@ -356,22 +380,22 @@ int Scene::loadGeom(std::string objectid) {
         else if (key(t, "ROTAT")) g.rotation = triple(t);
         else if (key(t, "SCALE")) g.scale = triple(t);
         else if (key(t, "TEXTURE") && t.size() >= 2) {
-            const std::string path = t[1][0] == '/' ? t[1] : dir + t[1];
-            int k = -1;
-            for (size_t j = 0; j < textures.size(); ++j)
-                if (textures[j].path == path) k = (int)j;
-            if (k < 0) {
-                try {
-                    textures.push_back(loadTexture(path));
-                } catch (const std::exception &e) {
-                    // like an unreadable mesh: a texture that cannot be read is a scene that cannot be rendered
-                    std::cout << "ERROR: " << e.what() << " - aborting!" << std::endl;
-                    throw;
-                }
-                k = (int)textures.size() - 1;
-            }
+            const int k = textureIndex(t[1][0] == '/' ? t[1] : dir + t[1]);
             geomTextures.resize(geoms.size() + 1, -1);
             geomTextures[geoms.size()] = k;
+        }
+        else if (key(t, "BUMP") && t.size() >= 2) {
+            char *end = nullptr;
+            const float s = t.size() >= 3 ? strtof(t[2].c_str(), &end) : 0.0f;
+            if (t.size() < 3 || !end || *end != 0 || !std::isfinite(s)) {
+                std::cout << "ERROR: object " << objectid << ": BUMP needs a file and a finite scale - aborting!" << std::endl;
+                throw std::runtime_error("BUMP without a finite scale");
+            }
+            const int k = textureIndex(t[1][0] == '/' ? t[1] : dir + t[1]);
+            geomBumps.resize(geoms.size() + 1, -1);
+            bumpScales.resize(geoms.size() + 1, 0.0f);
+            geomBumps[geoms.size()] = k;
+            bumpScales[geoms.size()] = s;
         }
     }
     g.transform = utilityCore::buildTransformationMatrix(g.translation, g.rotation, g.scale);

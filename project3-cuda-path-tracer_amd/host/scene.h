@@ -11,6 +11,8 @@
 #define PT_SCENE_HAS_MESHES 1
 // (... and `textures`, `geomTextures` and Mesh::uvs: image textures bound to objects by a `TEXTURE <file>` line of their OBJECT block)
 #define PT_SCENE_HAS_TEXTURES 1
+// (... and `geomBumps`, `bumpScales`: height maps bound to objects by a `BUMP <file> <scale>` line of their OBJECT block)
+#define PT_SCENE_HAS_BUMPS 1
 
 // Triangles of one `mesh` object (README.md:112-116, 236), in the OBJ file's coordinates = the geom's object space.
 struct Mesh {
@@ -36,6 +38,7 @@ private:
     std::ifstream fp_in;                          // the scene file while it is being parsed
     int loadMaterial(std::string materialid);     // MATERIAL block: exactly 7 keyword lines
     int loadGeom(std::string objectid);           // OBJECT block: type, material, TRANS/ROTAT/SCALE up to a blank line
+    int textureIndex(const std::string &path);    // index of the texture file `path` in `textures`, loaded at its first mention
     int loadCamera();                             // CAMERA block: 5 keyword lines + EYE/VIEW/UP up to a blank line
     bool verbose;
     std::string dir;                              // directory of the scene file ("" or ending in '/'): mesh paths are relative to it
@@ -54,5 +57,7 @@ public:
     std::vector<Mesh> meshes;           // one per Geom of type MESH, file order
     std::vector<Texture> textures;      // every texture file the scene names, once, in order of first mention
     std::vector<int> geomTextures;      // per geom: index into textures, or -1 (untextured)
+    std::vector<int> geomBumps;         // per geom: index into textures of its height map, or -1 (unbumped)
+    std::vector<float> bumpScales;      // per geom: the height map's scale (0 where unbumped)
     RenderState state;                  // camera, iteration count, depth, output name, host image
 };

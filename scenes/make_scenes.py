@@ -7,6 +7,8 @@ byte-identical structs from both).  cornell_glass.txt (BASELINE config C4) and s
 scene format's third object type, "mesh" (README.md:236), with OBJ files generated here under scenes/models/.
 cornell_textured.txt binds image textures to objects (`TEXTURE <file>`, texture mapping [PBRT 10.4], a README extra) -- the
 textures are generated here under scenes/textures/ (ASCII PPM), the UV-mapped torus under scenes/models/.
+cornell_bump.txt binds height maps (`BUMP <file> <scale>`, bump mapping [PBRT 10.5.1], a README extra) -- grey ASCII PPMs under
+scenes/textures/ as well.
 """
 import math
 import os
@@ -271,6 +273,38 @@ def textures():
                               for y in range(8)], "16 x 8 grid: u in red, v in green, cell parity in blue")
 
 
+def write_height_p3(name, rows, title):
+    """a grey height map: rows of values in [0, 1], r = g = b = round(255 h)"""
+    write_ppm_p3(name, [[(round(255 * h),) * 3 for h in row] for row in rows], title)
+
+
+def bump_textures():
+    # 32 x 32 bricks: 4 courses of 16-texel bricks, every other course shifted by half a brick; mortar 2 texels wide, lower by 0.7
+    write_height_p3("bricks.ppm", [[0.3 if (y % 8 < 2 or (x + (8 if (y // 8) % 2 else 0)) % 16 < 2) else 1.0 for x in range(32)] for y in range(32)],
+                    "32 x 32 height map: bricks and mortar")
+    # 32 x 16 ripples around the sphere's axis: six waves in longitude, three in latitude
+    write_height_p3("ripple.ppm", [[0.5 + 0.25 * math.sin(2 * math.pi * 6 * (x + 0.5) / 32) + 0.25 * math.sin(2 * math.pi * 3 * (y + 0.5) / 16)
+                                    for x in range(32)] for y in range(16)], "32 x 16 height map: ripples in longitude and latitude")
+    # 16 x 8 ridges along v: a triangle wave of period 4 texels in u
+    write_height_p3("ridges.ppm", [[abs(((x % 4) - 1.5) / 1.5) for x in range(16)] for y in range(8)], "16 x 8 height map: ridges along v")
+
+
+def cornell_bump():
+    s = ("// Cornell box with height maps (`BUMP <file> <scale>`, bump mapping): a brick back wall (a cube), a rippled mirror sphere and a\n"
+         "// UV-mapped torus with both a grid texture and ridges\n\n")
+    for i, m in enumerate(CORNELL_MATS):
+        s += material(i, *m)
+    s += camera("800 800", 45, 5000, 8, "cornell_bump")
+    for i, o in enumerate(CORNELL_OBJS[:6]):
+        s += obj(i, *o)
+        if i == 3:
+            s = s[:-1] + "BUMP textures/bricks.ppm 0.05\n\n"
+    s += obj(6, "mirror sphere, ripples", "sphere", 4, "-1.5 4 -1", "0 30 0", "3 3 3")[:-1] + "BUMP textures/ripple.ppm 0.02\n\n"
+    s += (obj(7, "UV-mapped torus, grid texture and ridges", "mesh models/torus_uv.obj", 1, "2.2 2.2 1.5", "50 0 25", "4 4 4")[:-1]
+          + "TEXTURE textures/grid.ppm\nBUMP textures/ridges.ppm 0.05\n\n")
+    return s
+
+
 def unit_cube():
     """[-0.5, 0.5]^3 as six outward counter-clockwise quads: -x, +x, -y, +y, -z, +z"""
     v = [(x, y, z) for x in (-0.5, 0.5) for y in (-0.5, 0.5) for z in (-0.5, 0.5)]          # index = 4 x + 2 y + z
@@ -353,6 +387,8 @@ def main():
     textures()
     write_obj_uv("torus_uv.obj", "torus, 16 x 8 quads = 256 triangles, with texture coordinates (vt)", *torus_uv(16, 8))
     w("cornell_textured.txt", cornell_textured())
+    bump_textures()
+    w("cornell_bump.txt", cornell_bump())
 
 
 if __name__ == "__main__":
