@@ -262,6 +262,32 @@ int pt_unpin_host(void);
 /* sendImageToPBO into a HOST buffer (W*H*4 bytes). Synchronises. */
 int pt_readback_rgba8(int iter, uint8_t *rgba_host);
 
+/* ---- denoiser: an edge-avoiding a-trous wavelet filter over the image, guided by first-hit position and normal (Dammertz et al., HPG 2010;
+ * csrc/pt_denoise.h gives every operation, tests/denoise_ref.py restates it).  `levels` passes of a 5 x 5 B3-spline stencil whose taps lie
+ * 2^level pixels apart; a tap's weight falls with the squared differences of colour (sigma_color, halved per level), guide normal (sigma_normal)
+ * and guide position (sigma_position, world units): w = h * exp(-(|dc|^2 / sc^2 + |dn|^2 / sn^2 + |dp|^2 / sp^2)); a sigma of +inf switches its
+ * term off (all three: the plain blur).  A pixel that hit something and one that hit nothing never mix.
+ * The guide buffers are the nearest hits of the camera rays iteration `guide_iter` traces (its jitter, and its lens sample with depth of field):
+ * world-space point and distance, the un-bumped shading normal, the primitive's index (-1, distance -1 and zeros for a miss).
+ *   pt_denoise         filters the accumulator's mean over `samples` (sum / samples) into rgb_mean_host, W*H*3 floats
+ *   pt_denoise_rgba8   ... and applies sendImageToPBO's conversion to it: clamp((int)(mean * 255.0), 0, 255), W*H*4 bytes
+ *   pt_gbuffer         the guide buffers themselves
+ * All three run on the context's stream behind every iteration committed so far, synchronise like pt_readback and leave the accumulator
+ * untouched (a caller-owned accum_dev too): rendering may go on afterwards.  Guide and filter buffers are allocated on first use and freed by
+ * pt_free / pt_init; the guide buffers are kept for the guide_iter they were made for until then.
+ * PT_ERR_NOT_INIT before pt_init; PT_ERR_INVALID for levels outside 1..8, a sigma that is 0, negative or NaN, guide_iter < 1, samples < 1,
+ * another struct size than this header's, and for a renderer initialised with shard_count > 1 or PT_FLAG_ACCUM_SHARD_ROWS (its accumulator
+ * is not a frame).  Device groups are out of scope: pt_group_* has no denoiser; filter what pt_group_readback returns in a context of its own.
+ * (Additive: the ABI version stays.) */
+typedef struct PtDenoiseParams {
+    int32_t levels;          /* 1..8 */
+    int32_t guide_iter;      /* >= 1: the iteration whose camera rays give the guide buffers */
+    float sigma_color, sigma_normal, sigma_position;   /* > 0, +inf allowed; NaN, 0, negatives refused */
+} PtDenoiseParams;
+int pt_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, float *rgb_mean_host /* W*H*3 */);
+int pt_denoise_rgba8(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, uint8_t *rgba_host);
+int pt_gbuffer(int guide_iter, float *pos_t_host /* W*H*4 */, float *nrm_host /* W*H*3 */, int32_t *geom_host /* W*H */);
+
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);
 

@@ -148,6 +148,11 @@ int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, fl
  * mesh: the barycentric u, v, the corner UVs u0 v0 u1 v1 u2 v2 and the object-space corners p0 p1 p2 (tangents: the library's own host code).
  * out: 16 floats per hit {hu, hv, Pu (3), Pv (3), Ns (3), bumped (0 / 1), u, v, 0, 0}; Ns = N where the hit stays unbumped. */
 int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, const float *in, int n, float *out);
+/* the denoiser (pt_amd.h, csrc/pt_denoise.h): pt_denoise of THIS library's renderer with the form of k_atrous named -- 0: the product's
+ * choice per level, 1: the plain gather, 2 / 3: LDS tiles of 64 x 4 / 64 x 8 pixels of a residue class -- every form gives the same bits.
+ * ms (or NULL): 1 + levels kernel times by HIP events, k_gbuffer first (0 when the guide buffers were cached), then each level. */
+int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms);
+int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
 
 #ifdef __cplusplus
 }

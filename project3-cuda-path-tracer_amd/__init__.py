@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "pt_group_create", "pt_group_destroy", "pt_group_size", "pt_group_collective", "pt_group_set_meshes", "pt_group_init", "pt_group_iterate_batch",
     "pt_group_iterate", "pt_group_reduce", "pt_group_sync", "pt_group_readback", "pt_group_counters",
     "pt_set_textures", "pt_group_set_textures", "pt_set_bump_maps", "pt_group_set_bump_maps",
+    "pt_denoise", "pt_denoise_rgba8", "pt_gbuffer",
 ]
 PT_AMD_ABI_VERSION = 7
 # every symbol include/pt_amd_test.h declares: libpt_amd_test.so only -- the product library must NOT export them
@@ -69,7 +70,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
-    "pt_test_bump_normal",
+    "pt_test_bump_normal", "pt_test_denoise", "pt_test_exp_neg_poly",
 ]
 
 
@@ -93,6 +94,11 @@ class PtTexBinding(C.Structure):
 
 class PtBumpBinding(C.Structure):
     _fields_ = [("geom", C.c_int32), ("texture", C.c_int32), ("scale", C.c_float), ("ntris", C.c_int32), ("uvs", C.c_void_p)]
+
+
+class PtDenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("guide_iter", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float)]
 
 
 class PtCounters(C.Structure):
@@ -157,6 +163,9 @@ def _bind(L, with_tests):
     L.pt_group_sync.argtypes = [vp]
     L.pt_group_readback.argtypes = [vp, vp]
     L.pt_group_counters.argtypes = [vp, C.POINTER(PtCounters)]
+    L.pt_denoise.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, vp]
+    L.pt_denoise_rgba8.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, vp]
+    L.pt_gbuffer.argtypes = [i32, vp, vp, vp]
     if with_tests:
         L.pt_debug_trace_paths.argtypes = [i32, i32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
         u64p = C.POINTER(C.c_uint64)
@@ -191,6 +200,8 @@ def _bind(L, with_tests):
         L.pt_test_texture_sample.argtypes = [vp, i32, i32, vp, i32, vp]
         L.pt_test_texture_uv.argtypes = [i32, vp, vp, i32, vp]
         L.pt_test_bump_normal.argtypes = [vp, i32, i32, vp, vp, i32, vp]
+        L.pt_test_denoise.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, i32, vp, vp]
+        L.pt_test_exp_neg_poly.argtypes = [vp, i32, vp]
     return L
 
 
@@ -544,6 +555,69 @@ def readback(npixels):
 def readback_rgba8(iteration, npixels):
     out = np.empty((npixels, 4), np.uint8)
     _check(lib().pt_readback_rgba8(iteration, _p(out)))
+    return out
+
+
+# default sigmas of the denoiser: colour in units of the image's mean (few samples of a scene with a bright light are far apart), the normal's
+# in units of a unit vector's difference, the position's in world units (Cornell's box is 10 units wide): the values tests/test_denoise_cpu.py
+# tries on a 4-iteration Cornell frame
+DENOISE_SIGMA_COLOR, DENOISE_SIGMA_NORMAL, DENOISE_SIGMA_POSITION = 2.0, 0.35, 2.0
+
+
+def _frame_pixels():
+    if _scene is None:
+        raise PtError("no scene: pathtraceInit first")
+    res = _scene.camera["resolution"][0]
+    return int(res[0]) * int(res[1])
+
+
+def _denoise_params(levels, sigma_color, sigma_normal, sigma_position, guide_iter):
+    return PtDenoiseParams(levels, guide_iter, sigma_color, sigma_normal, sigma_position)
+
+
+def denoise(samples, levels=5, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+            sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1):
+    """The accumulator's mean over `samples`, filtered by `levels` passes of the edge-avoiding a-trous filter (pt_denoise): W*H*3 floats.
+    The accumulator is left as it is."""
+    out = np.empty(_frame_pixels() * 3, np.float32)
+    prm = _denoise_params(levels, sigma_color, sigma_normal, sigma_position, guide_iter)
+    _check(lib().pt_denoise(samples, C.byref(prm), C.sizeof(prm), _p(out)))
+    return out
+
+
+def denoise_rgba8(samples, levels=5, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+                  sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1):
+    """... converted like the preview's pixels (pt_denoise_rgba8): (W*H, 4) bytes."""
+    out = np.empty((_frame_pixels(), 4), np.uint8)
+    prm = _denoise_params(levels, sigma_color, sigma_normal, sigma_position, guide_iter)
+    _check(lib().pt_denoise_rgba8(samples, C.byref(prm), C.sizeof(prm), _p(out)))
+    return out
+
+
+def gbuffer(guide_iter=1):
+    """The denoiser's guide buffers (pt_gbuffer): the nearest hits of iteration `guide_iter`'s camera rays as (pos_t (W*H, 4), normal (W*H, 3),
+    geom (W*H,) int32); a miss is (0, 0, 0, -1), zeros and -1."""
+    n = _frame_pixels()
+    pos_t, nrm, geom = np.empty((n, 4), np.float32), np.empty((n, 3), np.float32), np.empty(n, np.int32)
+    _check(lib().pt_gbuffer(guide_iter, _p(pos_t), _p(nrm), _p(geom)))
+    return pos_t, nrm, geom
+
+
+def test_denoise(samples, form, levels=5, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
+                 sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1, timing=False):
+    """denoise() with the form of k_atrous named (test library, inside renderer_from_test_library): 0 the product's choice, 1 the plain gather,
+    2 / 3 LDS tiles of 64 x 4 / 64 x 8.  timing=True: also the kernel times in ms, k_gbuffer first (0 when cached), then each level."""
+    out = np.empty(_frame_pixels() * 3, np.float32)
+    ms = np.zeros(1 + levels, np.float32)
+    prm = _denoise_params(levels, sigma_color, sigma_normal, sigma_position, guide_iter)
+    _tcheck(test_lib().pt_test_denoise(samples, C.byref(prm), C.sizeof(prm), form, _p(out), _p(ms) if timing else None))
+    return (out, ms) if timing else out
+
+
+def test_exp_neg_poly(a):
+    a = np.ascontiguousarray(a, np.float32)
+    out = np.empty_like(a)
+    _tcheck(test_lib().pt_test_exp_neg_poly(_p(a), a.size, _p(out)))
     return out
 
 

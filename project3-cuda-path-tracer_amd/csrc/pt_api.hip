@@ -39,6 +39,7 @@
 #include "pt_trace.h"
 #include "pt_mesh_walk.h"
 #include "pt_mesh.h"
+#include "pt_denoise.h"
 // The entry points of include/pt_amd_test.h (device primitives one by one, soundness sweeps, the fault-word hook) exist only in
 // the second link target of this source, libpt_amd_test.so (-DPT_TEST_API): the product library exports none of them.
 #ifdef PT_TEST_API
@@ -52,6 +53,7 @@ using namespace ptk;
 static_assert(sizeof(PtGeom) == 236 && sizeof(PtMaterial) == 44 && sizeof(PtCamera) == 52,
               "layout must equal reference src/sceneStructs.h:18-47");
 static_assert(sizeof(PtBumpBinding) == 24, "PtBumpBinding: 24 bytes (include/pt_amd.h)");
+static_assert(sizeof(PtDenoiseParams) == 20, "PtDenoiseParams: 20 bytes (include/pt_amd.h)");
 namespace {
 
 // =====================================================================================================
@@ -148,6 +150,13 @@ struct State {
     float4 *dBumpUV = nullptr, *dBumpTan = nullptr;
     bool bump = false;      // a height map is bound to at least one primitive
     bool mesh = false;      // the scene holds triangle meshes: the k_bounce<., false, ., true> variants
+    int meshStackNeed = 0;  // ... and the stack levels a brute-force walk of them needs per lane (k_gbuffer)
+    // the denoiser (pt_denoise.h), all allocated on first use: the guide buffers of iteration dnGuideIter (0: none yet), the float4 images
+    // the filter's levels pass on, and the packed RGB the last level writes
+    float4 *dnPosT = nullptr, *dnNrmId = nullptr, *dnPing[2] = {nullptr, nullptr};
+    float *dnOut = nullptr;
+    uchar4 *dnRgba = nullptr;       // pt_denoise_rgba8's bytes
+    int dnGuideIter = 0;
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
     int *dWalkIdx = nullptr, *dWalkRowOff = nullptr;
     float4 *dWalkMeshRows = nullptr;   // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows); walkMeshLds: how many of them a workgroup stages in LDS (all, or none)
@@ -594,6 +603,132 @@ void register_exit_handler() {
     std::call_once(once, [] { atexit(exit_handler); });
 }
 
+// ---- the denoiser (pt_denoise.h) ---------------------------------------------------------------------------------------------------
+// which form of k_atrous a level takes: the plain gather, or the LDS-tiled one with one or two rows per wave
+enum { kAtrousAuto = 0, kAtrousGather = 1, kAtrousTiled4 = 2, kAtrousTiled8 = 3 };
+
+template <bool F, bool L>
+const void *atrous_kernel(int form) {
+    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_gather<F, L>);
+    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_tiled<F, L, 1>);
+    return reinterpret_cast<const void *>(k_atrous_tiled<F, L, 2>);
+}
+
+// timing events that go away on every path out of their scope
+struct EventSet {
+    hipEvent_t ev[10] = {nullptr};
+    ~EventSet() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+int denoise_refusals(const char *who) {
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
+    if (R().prm.shardCount > 1 || (R().flags & PT_FLAG_ACCUM_SHARD_ROWS))
+        return fail(PT_ERR_INVALID, "%s: the renderer holds a row shard, its accumulator is not a frame", who);
+    return PT_OK;
+}
+
+// the guide buffers of iteration `guideIter`, on the caller's stream (cached until pt_init / pt_free); ms: the kernel's time, 0 when cached
+int ensure_guides(int guideIter, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (guideIter < 1 || guideIter >= kIterEnd) return fail(PT_ERR_INVALID, "guide_iter must be 1..4194303");
+    const size_t P = (size_t)R().P;
+    if (!R().dnPosT) HIPCHECK(hipMalloc(&R().dnPosT, P * sizeof(float4)));
+    if (!R().dnNrmId) HIPCHECK(hipMalloc(&R().dnNrmId, P * sizeof(float4)));
+    if (R().dnGuideIter == guideIter) return PT_OK;
+    const size_t stackBytes = R().mesh ? (size_t)std::max(R().meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0;
+    if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "guide buffers: a mesh hierarchy needs %d stack levels", R().meshStackNeed);
+    EventSet es;
+    hipEvent_t &e0 = es.ev[0], &e1 = es.ev[1];
+    if (ms) {
+        HIPCHECK(hipEventCreate(&e0));
+        HIPCHECK(hipEventCreate(&e1));
+        HIPCHECK(hipEventRecord(e0, R().stream));
+    }
+    R().dnGuideIter = 0;
+    hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), stackBytes, R().stream, R().prm, R().dgeoms,
+                       reinterpret_cast<const float4 *>(R().dMeshRecs), guideIter, R().dnPosT, R().dnNrmId);
+    HIPCHECK(hipGetLastError());
+    if (ms) {
+        HIPCHECK(hipEventRecord(e1, R().stream));
+        HIPCHECK(hipEventSynchronize(e1));
+        HIPCHECK(hipEventElapsedTime(ms, e0, e1));
+    }
+    R().dnGuideIter = guideIter;
+    return PT_OK;
+}
+
+// The filter's levels on the caller's stream, behind every committed iteration; the result is left in R().dnOut (packed RGB).
+// form: kAtrousAuto is the product's choice per level (UNMEASURED so far: see below); ms (or NULL): 1 + levels kernel times, k_gbuffer first.
+int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, float *ms, const char *who) {
+    int rc = denoise_refusals(who);
+    if (rc) return rc;
+    if (!p || bytes != sizeof(PtDenoiseParams))
+        return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseParams));
+    if (samples < 1) return fail(PT_ERR_INVALID, "%s: samples must be >= 1", who);
+    if (p->levels < 1 || p->levels > 8) return fail(PT_ERR_INVALID, "%s: levels must be 1..8", who);
+    for (float sg : {p->sigma_color, p->sigma_normal, p->sigma_position})
+        if (!(sg > 0.0f)) return fail(PT_ERR_INVALID, "%s: a sigma must be > 0 (+inf switches its term off)", who);
+    if (form < kAtrousAuto || form > kAtrousTiled8) return fail(PT_ERR_INVALID, "%s: unknown kernel form %d", who, form);
+    rc = ensure_guides(p->guide_iter, ms);
+    if (rc) return rc;
+    const size_t P = (size_t)R().P;
+    if (!R().dnOut) HIPCHECK(hipMalloc(&R().dnOut, P * 3 * sizeof(float)));
+    for (int k = 0; k < 2 && k < p->levels - 1; ++k)
+        if (!R().dnPing[k]) HIPCHECK(hipMalloc(&R().dnPing[k], P * sizeof(float4)));
+    AtrousArgs A;
+    A.accum = R().image;
+    A.posT = R().dnPosT; A.nrmId = R().dnNrmId;
+    A.W = R().prm.W; A.H = R().prm.H;
+    A.samples = (float)samples;
+    const float invC0 = 1.0f / (p->sigma_color * p->sigma_color);
+    A.invN = 1.0f / (p->sigma_normal * p->sigma_normal);
+    A.invP = 1.0f / (p->sigma_position * p->sigma_position);
+    EventSet es;
+    hipEvent_t *const ev = es.ev;
+    if (ms)
+        for (int i = 0; i <= p->levels; ++i) HIPCHECK(hipEventCreate(&ev[i]));
+    for (int i = 0; i < p->levels; ++i) {
+        const bool first = i == 0, last = i == p->levels - 1;
+        A.step = 1 << i;
+        A.invC = invC0 * (float)(1 << (2 * i));
+        A.cin = first ? nullptr : R().dnPing[(i - 1) & 1];
+        A.cout = last ? nullptr : R().dnPing[i & 1];
+        A.out3 = last ? R().dnOut : nullptr;
+        // (NOT measured yet -- profiles/denoise_cost.py is the measurement to run: the expectation is that the tiled form wins while a class's
+        // rows still share cache lines, and the gather, whose taps stay coalesced at every step, beyond)
+        int f = form != kAtrousAuto ? form : (A.step <= kAtrousTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
+        unsigned long long grid = f == kAtrousGather ? atrousGridGather(A.W, A.H) : atrousGridTiled(A.W, A.H, A.step, f == kAtrousTiled4 ? 1 : 2);
+        if (grid > 0x7fffffffull) {       // (a frame of few, very long rows at a large step: more tiles than a launch holds)
+            f = kAtrousGather;
+            grid = atrousGridGather(A.W, A.H);
+        }
+        const void *kern = first ? (last ? atrous_kernel<true, true>(f) : atrous_kernel<true, false>(f))
+                                 : (last ? atrous_kernel<false, true>(f) : atrous_kernel<false, false>(f));
+        void *kargs[] = {&A};
+        if (ms) HIPCHECK(hipEventRecord(ev[i], R().stream));
+        HIPCHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
+    }
+    if (ms) {
+        HIPCHECK(hipEventRecord(ev[p->levels], R().stream));
+        HIPCHECK(hipEventSynchronize(ev[p->levels]));
+        for (int i = 0; i < p->levels; ++i) HIPCHECK(hipEventElapsedTime(&ms[1 + i], ev[i], ev[i + 1]));
+    }
+    HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
+int denoise_to_host(int samples, const PtDenoiseParams *p, size_t bytes, int form, float *ms, float *rgb_mean_host, const char *who) {
+    if (!rgb_mean_host) return fail(PT_ERR_INVALID, "%s: null", who);
+    int rc = denoise_run(samples, p, bytes, form, ms, who);
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
@@ -681,6 +816,12 @@ void free_renderer() {
     if (R().dBumpGeom) (void)hipFree(R().dBumpGeom);
     if (R().dBumpUV) (void)hipFree(R().dBumpUV);
     if (R().dBumpTan) (void)hipFree(R().dBumpTan);
+    if (R().dnPosT) (void)hipFree(R().dnPosT);
+    if (R().dnNrmId) (void)hipFree(R().dnNrmId);
+    if (R().dnPing[0]) (void)hipFree(R().dnPing[0]);
+    if (R().dnPing[1]) (void)hipFree(R().dnPing[1]);
+    if (R().dnOut) (void)hipFree(R().dnOut);
+    if (R().dnRgba) (void)hipFree(R().dnRgba);
     {   // (the registered meshes, textures and height maps outlive the renderer: see State::meshes)
         std::vector<ptm::HostMesh> keep = std::move(R().meshes);
         std::vector<State::HostTexture> keepTex = std::move(R().textures);
@@ -1203,6 +1344,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     HIPCHECK(hipMalloc(&R().dwalls, hw.size() * sizeof(WallBox)));
     HIPCHECK(hipMemcpy(R().dwalls, hw.data(), hw.size() * sizeof(WallBox), hipMemcpyHostToDevice));
     R().mesh = !meshRecs.empty();
+    R().meshStackNeed = meshStackNeed;
     R().bump = !R().bumpBindings.empty();
     R().tex = !R().texBindings.empty() || R().bump;
     if (R().tex) {         // every texel one float4, the textures one after another; per primitive its TexGeom; per textured triangle two float4
@@ -1721,6 +1863,42 @@ int pt_readback_rgba8(int iter, uint8_t *rgba_host) {
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(rgba_host, tmp.p, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+// ---- the denoiser: an edge-avoiding a-trous filter over the accumulator's mean (pt_denoise.h) -------------------------------
+int pt_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, float *rgb_mean_host) {
+    return denoise_to_host(samples, p, params_struct_bytes, kAtrousAuto, nullptr, rgb_mean_host, "pt_denoise");
+}
+
+int pt_denoise_rgba8(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, uint8_t *rgba_host) {
+    if (!rgba_host) return fail(PT_ERR_INVALID, "pt_denoise_rgba8: null");
+    int rc = denoise_run(samples, p, params_struct_bytes, kAtrousAuto, nullptr, "pt_denoise_rgba8");
+    if (rc) return rc;
+    if (!R().dnRgba) HIPCHECK(hipMalloc(&R().dnRgba, (size_t)R().P * sizeof(uchar4)));
+    // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
+    hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut, R().P, 1, R().dnRgba);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+int pt_gbuffer(int guide_iter, float *pos_t_host, float *nrm_host, int32_t *geom_host) {
+    int rc = denoise_refusals("pt_gbuffer");
+    if (rc) return rc;
+    if (!pos_t_host || !nrm_host || !geom_host) return fail(PT_ERR_INVALID, "pt_gbuffer: null");
+    rc = ensure_guides(guide_iter, nullptr);
+    if (rc) return rc;
+    const size_t P = (size_t)R().P;
+    std::vector<float> tmp(P * 4);
+    HIPCHECK(hipMemcpyAsync(pos_t_host, R().dnPosT, P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipMemcpyAsync(tmp.data(), R().dnNrmId, P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    for (size_t i = 0; i < P; ++i) {
+        memcpy(nrm_host + 3 * i, tmp.data() + 4 * i, 3 * sizeof(float));
+        memcpy(geom_host + i, tmp.data() + 4 * i + 3, sizeof(int32_t));
+    }
     return readback_fault();
 }
 

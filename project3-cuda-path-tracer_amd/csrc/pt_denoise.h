@@ -1,0 +1,238 @@
+// pt_denoise.h -- the edge-avoiding a-trous wavelet filter over the renderer's image, guided by first-hit position and normal
+// (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination Filtering", HPG 2010).
+// Two kernels, both outside the render path (k_bounce, k_mesh_walk, k_commit and their arguments do not know of them):
+//   k_gbuffer   the guide buffers: the nearest hit of the camera rays of ONE iteration, brute force over the scene's primitives
+//   k_atrous    one level of the filter (the hot path): a 5 x 5 stencil with holes, LDS-tiled per residue class or a plain gather
+// Included by pt_api.hip only.
+//
+// ---- the filter, operation by operation (tests/denoise_ref.py restates it in numpy, bit for bit: every fp32 operation below is one IEEE
+// operation, -ffp-contract=off, in the order written) ----
+//   guides      pos_t[p] = (P.x, P.y, P.z, t), nrm_id[p] = (N.x, N.y, N.z, bits of the int32 geom index); a miss is (0, 0, 0, -1) and
+//               (0, 0, 0, id = -1).  N is the un-bumped shading normal (hitNormal; a mesh with `vn`: the blended vertex normal).
+//   colour      level 0 reads the accumulator: c0.k = sum.k / (float)samples, one correctly rounded division per channel; levels
+//               1 .. levels - 1 read the float4 image the level before wrote; the last level writes packed RGB.
+//   taps        level i has step s = 2^i.  For the output pixel p the taps are q = p + s (dx, dy), dy = -2 .. 2 (outer loop), dx = -2 .. 2
+//               (inner loop), in that order; a tap outside the frame is skipped.
+//   weights     h = [1/16, 1/4, 3/8, 1/4, 1/16], hw = h[dy + 2] * h[dx + 2] (exact).  The centre tap has w = hw, nothing is evaluated for
+//               it.  A tap of which exactly one of p, q is a miss (id < 0) has weight 0: it is skipped like a tap outside the frame.
+//               Every other tap:  a = dot(dc, dc) * invC_i;  a = a + dot(dn, dn) * invN;  a = a + dot(dp, dp) * invP;  w = hw * expNegPoly(a)
+//               with dc, dn, dp = q - p of the level's input colour, the normal and the position, dot = ptd::dot ((x + y) + z).
+//   sums        sumW += w;  sumC.k += c_q.k * w  (a multiplication and an addition), from sumW = sumC.k = 0;  out.k = sumC.k / sumW.
+//               The centre tap alone gives sumW >= 9 / 64: no guard.
+//   expNegPoly  ptd::expNegPoly (pt_device.h): t = a * (-1.44269504088896341f); !(t >= -126) -> 0 (NaN lands there); else exp2Poly(t),
+//               the exponential half of powPoly.
+//   sigmas      on the host, fp32: invC_i = (1 / (sigma_color * sigma_color)) * 4^i (Dammertz halves the colour sigma per level),
+//               invN = 1 / (sigma_normal * sigma_normal), invP = 1 / (sigma_position * sigma_position); a sigma of +inf gives 0: term off.
+// The result of a pixel is a function of the frame alone: neither kernel form, nor the tile shape, nor the order of the workgroups enters.
+#pragma once
+#include "pt_trace.h"
+
+namespace ptk {
+
+// ---- guide buffers ---------------------------------------------------------------------------------------------------------------
+// One thread per pixel of the FULL frame (blocks of kBlock; dynamic LDS = the lanes' mesh traversal stacks, [levels][kBlock] words, as
+// k_test_mesh has them).  The camera ray is the one iteration `guideIter` traces for the pixel (cameraRayAt: jitter, and the lens when the
+// camera has one); it is tested against EVERY primitive in index order with the renderer's exact tests -- no culling table, no certificate --
+// and the nearest hit is chosen as the oracle's nearest_hit does: t > 0, smallest t, an equal t keeps the lower index.  The primitive index is
+// wave-uniform: its record arrives through the scalar path.
+__global__ __launch_bounds__(kBlock) void k_gbuffer(KParams prm, const GeomDev *ggeoms, const float4 *meshRecs, int guideIter, float4 *posT,
+                                                    float4 *nrmId) {
+    extern __shared__ uint32_t s_gbufStack[];
+    const int npix = prm.W * prm.H;
+    const int pix = blockIdx.x * kBlock + threadIdx.x;
+    const int pc = pix < npix ? pix : npix - 1;       // (lanes beyond the frame trace its last pixel and store nothing)
+    const int y = (int)fastDiv((uint32_t)pc, prm.magicW, prm.shiftW);
+    const int x = pc - y * prm.W;
+    F3 org, dir;
+    cameraRayAt(prm, iterationHash(guideIter, 0), pc, x, y, org, dir);
+    const GeomPtr geoms = (GeomPtr)ggeoms;
+    int hit = -1;
+    float tMin = 0.0f;
+    F3 P = f3(0.0f, 0.0f, 0.0f), nsrc = f3(0.0f, 0.0f, 0.0f);
+    bool outside = false;
+    for (int g = 0; g < prm.ngeoms; ++g) {
+        const PT_CAS GeomDev &G = *(launder(geoms) + g);
+        F3 tp = f3(0.0f, 0.0f, 0.0f), tn = f3(0.0f, 0.0f, 0.0f);
+        bool to = false;
+        float t;
+        if ((G.flags & 32) != 0) t = meshIntersectionTest<false, kBlock>(G, meshRecs, G.meshRoot, G.meshStride, s_gbufStack + threadIdx.x, org, dir, tp, tn, to);
+        else if ((G.flags & 1) == 0) t = sphereIntersectionTest(G, org, dir, tp, tn, to);
+        else t = boxIntersectionTest<false>(G, org, dir, tp, tn, to);
+        if (t > 0.0f && (hit < 0 || t < tMin)) {
+            tMin = t;
+            hit = g;
+            P = tp;
+            nsrc = tn;
+            outside = to;
+        }
+    }
+    if (pix >= npix) return;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, -1.0f), b = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    if (hit >= 0) {
+        const F3 N = hitNormal(ggeoms[hit], nsrc, outside);       // (per lane: the winner's record through the vector path, once)
+        a = make_float4(P.x, P.y, P.z, tMin);
+        b = make_float4(N.x, N.y, N.z, __int_as_float(hit));
+    }
+    posT[pix] = a;
+    nrmId[pix] = b;
+}
+
+// ---- one level of the filter -------------------------------------------------------------------------------------------------------
+struct AtrousArgs {
+    const float *accum;       // FIRST: the accumulator, packed RGB sums
+    const float4 *cin;        // later levels: the level before
+    float4 *cout;             // every level but the last
+    float *out3;              // LAST: packed RGB
+    const float4 *posT, *nrmId;
+    int W, H, step;
+    float samples;            // FIRST: (float)samples
+    float invC, invN, invP;
+};
+
+constexpr int kAtrousOutside = (int)0x80000000;      // LDS halo: the id of an entry outside the frame (ids of the frame are >= -1)
+constexpr int kAtrousTileW = 64;                     // a wave filters 64 consecutive pixels of one row of its residue class
+constexpr int kAtrousPitch = kAtrousTileW + 4;       // ... whose LDS rows carry the two-pixel halo on either side
+constexpr int kAtrousTiledMaxStep = 4;               // levels of a larger step take the plain gather (pt_api.hip: denoise_run); a choice by reasoning, unmeasured
+
+__device__ __forceinline__ float atrousH(int i) { return i == 2 ? 0.375f : ((i == 1 || i == 3) ? 0.25f : 0.0625f); }
+
+// one tap that lies inside the frame
+template <bool CENTRE>
+__device__ __forceinline__ void atrousTap(const AtrousArgs &A, float hw, float4 cq, float4 nq, float4 pq, float4 cp, float4 np, float4 pp,
+                                          float &sumW, F3 &sumC) {
+    float w = hw;
+    if (!CENTRE) {
+        if ((__float_as_int(nq.w) < 0) != (__float_as_int(np.w) < 0)) return;     // exactly one of the two is a miss
+        const F3 dc = f3(cq.x, cq.y, cq.z) - f3(cp.x, cp.y, cp.z);
+        const F3 dn = f3(nq.x, nq.y, nq.z) - f3(np.x, np.y, np.z);
+        const F3 dp = f3(pq.x, pq.y, pq.z) - f3(pp.x, pp.y, pp.z);
+        float a = dot(dc, dc) * A.invC;
+        a = a + dot(dn, dn) * A.invN;
+        a = a + dot(dp, dp) * A.invP;
+        w = hw * expNegPoly(a);
+    }
+    sumW += w;
+    sumC.x += cq.x * w;
+    sumC.y += cq.y * w;
+    sumC.z += cq.z * w;
+}
+
+template <bool FIRST>
+__device__ __forceinline__ float4 atrousColour(const AtrousArgs &A, size_t pix) {
+    if (!FIRST) return A.cin[pix];
+    const float *s = A.accum + 3 * pix;
+    return make_float4(s[0] / A.samples, s[1] / A.samples, s[2] / A.samples, 0.0f);
+}
+template <bool LAST>
+__device__ __forceinline__ void atrousStore(const AtrousArgs &A, size_t pix, F3 sumC, float sumW) {
+    const float r = sumC.x / sumW, g = sumC.y / sumW, b = sumC.z / sumW;
+    if (LAST) {
+        float *o = A.out3 + 3 * pix;
+        o[0] = r; o[1] = g; o[2] = b;
+    } else {
+        A.cout[pix] = make_float4(r, g, b, 0.0f);
+    }
+}
+
+// The plain gather: a workgroup filters 64 x 4 neighbouring pixels, every tap is a load through L2.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(kBlock) void k_atrous_gather(AtrousArgs A) {
+    const int tilesX = (A.W + kAtrousTileW - 1) / kAtrousTileW;
+    const int tY = (int)(blockIdx.x / (unsigned)tilesX), tX = (int)(blockIdx.x - (unsigned)tY * (unsigned)tilesX);
+    const int x = tX * kAtrousTileW + (int)(threadIdx.x & 63u), y = tY * 4 + (int)(threadIdx.x >> 6);
+    if (x >= A.W || y >= A.H) return;
+    const size_t pix = (size_t)x + (size_t)y * (size_t)A.W;
+    const float4 cp = atrousColour<FIRST>(A, pix), np = A.nrmId[pix], pp = A.posT[pix];
+    float sumW = 0.0f;
+    F3 sumC = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * A.step;
+        if (qy < 0 || qy >= A.H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * A.step;
+            const float hw = atrousH(dy + 2) * atrousH(dx + 2);
+            if (dx == 0 && dy == 0) {
+                atrousTap<true>(A, hw, cp, np, pp, cp, np, pp, sumW, sumC);
+            } else if (qx >= 0 && qx < A.W) {
+                const size_t q = (size_t)qx + (size_t)qy * (size_t)A.W;
+                const float4 nq = A.nrmId[q];
+                atrousTap<false>(A, hw, atrousColour<FIRST>(A, q), nq, A.posT[q], cp, np, pp, sumW, sumC);
+            }
+        }
+    }
+    atrousStore<LAST>(A, pix, sumC, sumW);
+}
+
+// The LDS-tiled form.  The taps of a level stay inside one residue class (x mod s, y mod s), in which they are a DENSE 5 x 5 stencil: a
+// workgroup owns a tile of 64 x (4 RPT) pixels of one class, stages the tile and its two-pixel halo -- colour, normal + id, position: three
+// float4 images of kAtrousPitch x (4 RPT + 4) entries -- in LDS once and filters from there, RPT rows per wave.  A wave reads 64 consecutive
+// 16-byte entries of one LDS row per tap (ds_read_b128: each of its 16-lane groups covers the 16 slots of the 256-byte bank row exactly
+// once, whatever dx and the row pitch: no bank conflict); the staging writes are 16-byte stores of consecutive entries.
+// Grid: classes x tiles of the largest class; a tile beyond its class's extent returns before the barrier.
+template <bool FIRST, bool LAST, int RPT>
+__global__ __launch_bounds__(kBlock) void k_atrous_tiled(AtrousArgs A) {
+    constexpr int TH = 4 * RPT, ROWS = TH + 4, ENTRIES = kAtrousPitch * ROWS;
+    __shared__ float4 s_c[ENTRIES], s_n[ENTRIES], s_p[ENTRIES];
+    const int s = A.step;
+    const int cw = (A.W + s - 1) / s, ch = (A.H + s - 1) / s;          // extent of the largest class
+    const int tilesX = (cw + kAtrousTileW - 1) / kAtrousTileW, tilesY = (ch + TH - 1) / TH;
+    const unsigned perClass = (unsigned)tilesX * (unsigned)tilesY;
+    const int cls = (int)(blockIdx.x / perClass), tile = (int)(blockIdx.x - (unsigned)cls * perClass);
+    const int ry = cls / s, rx = cls - ry * s;
+    const int tY = tile / tilesX, tX = tile - tY * tilesX;
+    const int cx0 = tX * kAtrousTileW, cy0 = tY * TH;                   // the tile's first pixel, in class coordinates
+    if (rx + s * cx0 >= A.W || ry + s * cy0 >= A.H) return;             // (workgroup-uniform)
+    for (int e = (int)threadIdx.x; e < ENTRIES; e += kBlock) {
+        const int ly = e / kAtrousPitch, lx = e - ly * kAtrousPitch;
+        const int x = rx + s * (cx0 + lx - 2), y = ry + s * (cy0 + ly - 2);
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(kAtrousOutside)), p = c;
+        if (x >= 0 && x < A.W && y >= 0 && y < A.H) {
+            const size_t q = (size_t)x + (size_t)y * (size_t)A.W;
+            c = atrousColour<FIRST>(A, q);
+            n = A.nrmId[q];
+            p = A.posT[q];
+        }
+        s_c[e] = c; s_n[e] = n; s_p[e] = p;
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x & 63u), wy = (int)(threadIdx.x >> 6);
+    const int x = rx + s * (cx0 + tx);
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        const int ly = wy + 4 * r;
+        const int y = ry + s * (cy0 + ly);
+        if (x >= A.W || y >= A.H) continue;
+        const int e0 = (ly + 2) * kAtrousPitch + tx + 2;
+        const float4 cp = s_c[e0], np = s_n[e0], pp = s_p[e0];
+        float sumW = 0.0f;
+        F3 sumC = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const float hw = atrousH(dy + 2) * atrousH(dx + 2);
+                if (dx == 0 && dy == 0) {
+                    atrousTap<true>(A, hw, cp, np, pp, cp, np, pp, sumW, sumC);
+                } else {
+                    const int e = e0 + dy * kAtrousPitch + dx;
+                    const float4 nq = s_n[e];
+                    if (__float_as_int(nq.w) != kAtrousOutside) atrousTap<false>(A, hw, s_c[e], nq, s_p[e], cp, np, pp, sumW, sumC);
+                }
+            }
+        }
+        atrousStore<LAST>(A, (size_t)x + (size_t)y * (size_t)A.W, sumC, sumW);
+    }
+}
+
+// workgroups of a level's launch
+inline unsigned atrousGridGather(int W, int H) {
+    return (unsigned)((W + kAtrousTileW - 1) / kAtrousTileW) * (unsigned)((H + 3) / 4);
+}
+inline unsigned long long atrousGridTiled(int W, int H, int s, int rpt) {
+    const int cw = (W + s - 1) / s, ch = (H + s - 1) / s, th = 4 * rpt;
+    return (unsigned long long)((cw + kAtrousTileW - 1) / kAtrousTileW) * (unsigned long long)((ch + th - 1) / th) * (unsigned long long)s * (unsigned long long)s;
+}
+
+}  // namespace ptk

@@ -273,6 +273,21 @@ __device__ __forceinline__ void sincosPoly(float x, float &s, float &c) {
     c = ((k + 1) & 2) ? -c0 : c0;
 }
 
+// 2^t for -126 <= t <= 0 (the callers' range; cephes exp2f): nearest integer, a degree-6 polynomial on the remainder in [-1/2, 1/2], the
+// integer added to the exponent field.  The exponential half of powPoly, shared with expNegPoly; the CPU oracle's pow_poly ends with it.
+__device__ __forceinline__ float exp2Poly(float t) {
+    const float nf = __builtin_rintf(t);
+    const float g = t - nf;
+    float q = 1.535336188319500e-4f;
+    q = q * g + 1.339887440266574e-3f;
+    q = q * g + 9.618437357674640e-3f;
+    q = q * g + 5.550332471162809e-2f;
+    q = q * g + 2.402264791363012e-1f;
+    q = q * g + 6.931472028550421e-1f;
+    const float r = q * g + 1.0f;
+    return __uint_as_float(__float_as_uint(r) + (uint32_t)((int)nf << 23));
+}
+
 // Build-defined x^e for 0 <= x <= 1, 0 < e <= 1 (imperfect specular: cos(theta) = xi^(1/(n+1)), GPU Gems 3 ch. 20 eq. 7-9,
 // named by the reference's README.md:171-185): exp2(e * log2(x)) with the cephes logf / exp2f polynomials, operation for
 // operation the CPU oracle's pow_poly (relative error ~2e-6).
@@ -301,16 +316,15 @@ __device__ __forceinline__ float powPoly(float x, float e) {
     const float l2 = ln * 1.44269504088896341f + (float)k;
     const float t = e * l2;
     if (t < -126.0f) return 0.0f;
-    const float nf = __builtin_rintf(t);
-    const float g = t - nf;
-    float q = 1.535336188319500e-4f;
-    q = q * g + 1.339887440266574e-3f;
-    q = q * g + 9.618437357674640e-3f;
-    q = q * g + 5.550332471162809e-2f;
-    q = q * g + 2.402264791363012e-1f;
-    q = q * g + 6.931472028550421e-1f;
-    const float r = q * g + 1.0f;
-    return __uint_as_float(__float_as_uint(r) + (uint32_t)((int)nf << 23));
+    return exp2Poly(t);
+}
+
+// exp(-a) for a >= 0, the range weight of the a-trous filter (pt_denoise.h): 2^(a * -log2(e)) by exp2Poly; results below 2^-126 are 0, and so
+// is the result of a NaN.  For x = 0.5 powPoly's logarithm is exactly -1, so expNegPoly(a) == powPoly(0.5f, a * 1.44269504088896341f).
+__device__ __forceinline__ float expNegPoly(float a) {
+    const float t = a * (-1.44269504088896341f);
+    if (!(t >= -126.0f)) return 0.0f;
+    return exp2Poly(t);
 }
 
 // 1.0f / sqrtf(x), both correctly rounded, for x within 256 ulps of 1 without the square root and the division.

@@ -877,6 +877,22 @@ int pt_test_pow(const float *x, const float *e, int n, float *out) {
     return PT_OK;
 }
 
+int pt_test_exp_neg_poly(const float *a, int n, float *out) {
+    NEED_GPU();
+    if (n <= 0) return PT_OK;
+    DevBuf<float> x, o;
+    UP(x, a, n);
+    int rc = o.alloc(n); if (rc) return rc;
+    hipLaunchKernelGGL(k_test_exp_neg_poly, GRID(n), x.p, n, o.p);
+    HIPCHECK(hipDeviceSynchronize());
+    DOWN(out, o, n);
+    return PT_OK;
+}
+
+int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms) {
+    return denoise_to_host(samples, p, params_struct_bytes, form, ms, rgb_mean_host, "pt_test_denoise");
+}
+
 int pt_test_sincos(const float *x, int n, float *s, float *c) {
     NEED_GPU();
     if (n <= 0) return PT_OK;

@@ -38,6 +38,10 @@ __global__ void k_test_pow(const float *x, const float *e, int n, float *out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = powPoly(x[i], e[i]);
 }
+__global__ void k_test_exp_neg_poly(const float *a, int n, float *out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = expNegPoly(a[i]);
+}
 __global__ void k_test_utilhash(const uint32_t *in, uint32_t *out, int n) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = utilhash(in[i]);

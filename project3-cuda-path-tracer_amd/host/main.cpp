@@ -4,9 +4,11 @@
 // output name <FILE>.<start time>.<N>samp.png, X mirrored, divided by the sample count.
 //
 //   pt_render SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B]
-//                           [--lens RADIUS FOCALDISTANCE] [--direct]
+//                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
+// --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
+// iteration's first hits (include/pt_amd.h); the usual image is written as without the option.
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -33,6 +35,8 @@ static bool writeHdr = false;
 static int batch = 1;
 static float lensRadius = 0.0f, focalDistance = 0.0f;
 static bool directLighting = false;
+static PtDenoiseParams denoiseParams;
+static bool denoise = false;
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 
 static std::string currentTimeString() {
@@ -60,6 +64,22 @@ static void saveImage() {
     if (writeHdr) img.saveHDR(ss.str());   // the reference keeps this behind a comment, src/main.cpp:69
 }
 
+static void check(int status, const char *what);
+// --denoise: the filtered mean, before the renderer is freed
+static void saveDenoised() {
+    if (!denoise) return;
+    std::vector<lin::vec3> mean((size_t)width * height);
+    check(pt_denoise(iteration, &denoiseParams, sizeof denoiseParams, (float *)mean.data()), "pt_denoise");
+    image img(width, height);
+    for (int x = 0; x < width; x++)
+        for (int y = 0; y < height; y++) img.setPixel(width - 1 - x, y, mean[x + (y * width)]);
+    std::ostringstream ss;
+    if (outBase.empty()) ss << renderState->imageName << "." << startTimeString << "." << (float)iteration << "samp";
+    else ss << outBase;
+    ss << ".denoised";
+    img.savePNG(ss.str());
+}
+
 // one trip through the reference's per-frame function; returns false when rendering is complete
 static bool runHip() {
     if (iteration == 0) {
@@ -72,6 +92,7 @@ static bool runHip() {
         return true;
     }
     saveImage();
+    saveDenoised();
     pathtraceFree();
     return false;
 }
@@ -114,13 +135,14 @@ static void renderBatched() {
     }
     check(pt_readback((float *)renderState->image.data()), "pt_readback");
     saveImage();
+    saveDenoised();
     pt_free();
 }
 
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP]\n", argv[0]);
         return 1;
     }
     try {
@@ -139,6 +161,15 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--batch") && i + 1 < argc) batch = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--lens") && i + 2 < argc) { lensRadius = (float)atof(argv[i + 1]); focalDistance = (float)atof(argv[i + 2]); i += 2; }
         else if (!strcmp(argv[i], "--direct")) directLighting = true;
+        else if (!strcmp(argv[i], "--denoise") && i + 4 < argc) {
+            denoise = true;
+            denoiseParams.levels = atoi(argv[i + 1]);
+            denoiseParams.guide_iter = 1;
+            denoiseParams.sigma_color = (float)atof(argv[i + 2]);
+            denoiseParams.sigma_normal = (float)atof(argv[i + 3]);
+            denoiseParams.sigma_position = (float)atof(argv[i + 4]);
+            i += 4;
+        }
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
     pathtraceExtras(lensRadius, focalDistance, directLighting);
