@@ -153,6 +153,14 @@ int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, 
  * ms (or NULL): 1 + levels kernel times by HIP events, k_gbuffer first (0 when the guide buffers were cached), then each level. */
 int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms);
 int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
+/* The selector of k_bounce's forms (host only, no GPU needed): state_bits = a renderer's state and a launch's `first` -- bit 0 first, 1 dof
+ * (thin lens), 2 many, 3 sweptCubes, 4 mesh, 5 grouped, 6 tex, 7 bump, 8 plain -- -> *form_bits = the nine template flags of the
+ * instantiation the launch takes (bit 0 FIRST, 1 MANY, 2 DOF, 3 MESH, 4 PLAIN, 5 CUBES, 6 GROUPS, 7 TEX, 8 BUMP), by the very function
+ * pt_init calls; PT_ERR_INVALID when the library holds no such instantiation (a state no renderer reaches). */
+int pt_test_bounce_form(uint32_t state_bits, uint32_t *form_bits);
+/* device allocations THIS library's renderers and temporaries hold right now (every one has one owner type, which counts in this
+ * library only): 0 after pt_free */
+int64_t pt_test_live_device_buffers(void);
 
 #ifdef __cplusplus
 }

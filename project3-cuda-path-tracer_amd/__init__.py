@@ -70,7 +70,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
-    "pt_test_bump_normal", "pt_test_denoise", "pt_test_exp_neg_poly",
+    "pt_test_bump_normal", "pt_test_denoise", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
 ]
 
 
@@ -202,6 +202,9 @@ def _bind(L, with_tests):
         L.pt_test_bump_normal.argtypes = [vp, i32, i32, vp, vp, i32, vp]
         L.pt_test_denoise.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, i32, vp, vp]
         L.pt_test_exp_neg_poly.argtypes = [vp, i32, vp]
+        L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
+        L.pt_test_live_device_buffers.argtypes = []
+        L.pt_test_live_device_buffers.restype = i64
     return L
 
 

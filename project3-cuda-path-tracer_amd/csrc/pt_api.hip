@@ -30,6 +30,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include <mutex>
@@ -78,6 +79,67 @@ int fail(int code, const char *fmt, ...) {
             return fail(PT_ERR_HIP, "HIP error (%s:%d): %s: %s", "pt_api.hip", __LINE__, #expr, \
                         hipGetErrorString(e_));                                                     \
     } while (0)
+// ... and for the functions of this file that return PT_OK or what fail() returned
+#define PTCHECK(expr)                                                                               \
+    do {                                                                                            \
+        int rc_ = (expr);                                                                           \
+        if (rc_) return rc_;                                                                        \
+    } while (0)
+
+// an environment variable that switches something on (experiments and tests): set, and not to 0
+bool env_flag(const char *name) {
+    const char *e = getenv(name);
+    return e && atoi(e);
+}
+
+#ifdef PT_TEST_API
+std::atomic<long long> g_liveDevBufs{0};     // pt_test_live_device_buffers(): allocations DevBufs hold right now (the product carries no counter)
+inline void count_devbuf(int d) { g_liveDevBufs += d; }
+#else
+inline void count_devbuf(int) {}
+#endif
+
+// The owner of one device allocation: every table of a renderer (State, Slot) and every temporary of this file.  Move-only; a buffer
+// that has been released -- or moved from -- does nothing in its destructor, so a State that free_renderer has emptied makes no HIP
+// call when it is destroyed (the default context is destroyed after the runtime's own exit handlers: see exit_handler).
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    void release() {
+        if (!p) return;
+        (void)hipFree(p);
+        p = nullptr;
+        count_devbuf(-1);
+    }
+    // n elements (at least one: a kernel may be handed the pointer of an empty table), uninitialised / zeroed / copied from the host
+    // (`slack`: elements behind the copied ones, left uninitialised)
+    int alloc(size_t n) {
+        release();
+        HIPCHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        count_devbuf(1);
+        return PT_OK;
+    }
+    int alloc_zeroed(size_t n) {
+        PTCHECK(alloc(n));
+        HIPCHECK(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)));
+        return PT_OK;
+    }
+    int upload(const T *src, size_t n, size_t slack = 0) {
+        PTCHECK(alloc(n + slack));
+        if (n) HIPCHECK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return PT_OK;
+    }
+    int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
+};
 
 constexpr int kMaxSlots = 4;
 constexpr int kTexSizeMax = 16384;     // largest side of a texture (pt_set_textures)
@@ -101,13 +163,13 @@ void meshTangents(const float *tri, const float *uv, float4 &tu, float4 &tv) {
 // One in-flight iteration: its own stream, path buffers, counters and deferred-radiance buffer.
 struct Slot {
     hipStream_t stream = nullptr;
-    float *pathbuf[2] = {nullptr, nullptr};      // two path pools (ping-pong by bounce), poolChunks * kChunk paths per array
-    unsigned long long *chunkList[2] = {nullptr, nullptr}; // per pool: [kSeg][poolChunks] chunk lists of the queue it holds
+    DevBuf<float> pathbuf[2];      // two path pools (ping-pong by bounce), poolChunks * kChunk paths per array
+    DevBuf<unsigned long long> chunkList[2];   // per pool: [kSeg][poolChunks] chunk lists of the queue it holds
     uint32_t gen[2] = {0, 0};      // per pool: serial number of the launch that filled it (tags the chunk-list entries)
-    Ctrl *ctrl = nullptr;
-    float *contrib = nullptr;      // maxBatch x W*H*3: an entry is valid while its bit of `hitMask` is set
-    uint32_t *hitMask = nullptr;   // ceil(maxBatch / 32) x W*H: which iterations of the batch wrote a pixel's `contrib`, zero between batches
-    unsigned long long *meshHit = nullptr;   // scenes with meshes: the walks' result per path of the bounce being launched (BounceArgs::meshHit)
+    DevBuf<Ctrl> ctrl;
+    DevBuf<float> contrib;         // maxBatch x W*H*3: an entry is valid while its bit of `hitMask` is set
+    DevBuf<uint32_t> hitMask;      // ceil(maxBatch / 32) x W*H: which iterations of the batch wrote a pixel's `contrib`, zero between batches
+    DevBuf<unsigned long long> meshHit;   // scenes with meshes: the walks' result per path of the bounce being launched (BounceArgs::meshHit)
     hipEvent_t evDone = nullptr;       // all bounce launches of the slot's current iteration finished
     hipEvent_t evCommitted = nullptr;  // k_commit consumed `contrib` (cleared the masks' bits)
     int parity = 0;                // which half of Ctrl::cursor the slot's next batch uses
@@ -122,44 +184,44 @@ struct State {
     int P = 0;              // W*H
     int nLocal = 0;
     int flags = 0;
-    float *image = nullptr;
-    bool ownImage = false;
+    float *image = nullptr;         // the accumulator the kernels add to: the caller's (PtOptions::accum_dev, never freed here), or ...
+    DevBuf<float> imageOwn;         // ... the renderer's own
     int nslots = 0;
     int maxBatch = 1;       // iterations that may share one wavefront (pt_iterate_batch)
     Slot slot[kMaxSlots];
-    GeomDev *dgeoms = nullptr;
-    float4 *dGeomHit = nullptr;     // GeomHitDev[ngeoms], as the kernels stage it in LDS (scenes that are not sphere-heavy)
-    float *dRows = nullptr;         // sphere-heavy scenes of hundreds of primitives: the matrix rows that do not go to LDS (BounceArgs::rows)
-    MaterialDev *dmats = nullptr;
-    WallBox *dwalls = nullptr;
-    SphereCull *dSphCull = nullptr; // sphere-heavy scenes: packed culling data of the spheres, and ...
-    SphereCull *dSphGroups = nullptr;   // ... scenes of hundreds of them: the bounding balls of the table's groups (BounceArgs::sphGroups)
+    DevBuf<GeomDev> dgeoms;
+    DevBuf<unsigned char> dGeomHit; // GeomHitDev[ngeoms], as the kernels stage it in LDS (scenes that are not sphere-heavy; those: one image of their tables)
+    DevBuf<float> dRows;            // sphere-heavy scenes of hundreds of primitives: the matrix rows that do not go to LDS (BounceArgs::rows)
+    DevBuf<MaterialDev> dmats;
+    DevBuf<WallBox> dwalls;
+    DevBuf<SphereCull> dSphCull;    // sphere-heavy scenes: packed culling data of the spheres, and ...
+    DevBuf<SphereCull> dSphGroups;  // ... scenes of hundreds of them: the bounding balls of the table's groups (BounceArgs::sphGroups)
     bool grouped = false;           // ... whose later bounces take the k_bounce<..., GROUPS> instantiations
-    int *dCamWave = nullptr, *dCamSigIdx = nullptr;   // camera rays: the packed work list (build_camera_list), or none
-    uint32_t *dCamPix = nullptr;
-    int *dRowOff = nullptr, *dRowIdx = nullptr;   // camera-ray bounce: per image row, the primitives whose pixel rectangle covers it
-    int *dClassIdx = nullptr;       // later bounces: per queue class, the primitives to look at (KParams::classOff)
-    float4 *dMeshRecs = nullptr;    // ptd::MeshUnit[]: triangles and inner nodes of every mesh of the scene (k_bounce<., ., ., true>)
+    DevBuf<int> dCamWave, dCamSigIdx;   // camera rays: the packed work list (build_camera_list), or none
+    DevBuf<uint32_t> dCamPix;
+    DevBuf<int> dRowOff, dRowIdx;   // camera-ray bounce: per image row, the primitives whose pixel rectangle covers it
+    DevBuf<int> dClassIdx;          // later bounces: per queue class, the primitives to look at (KParams::classOff)
+    DevBuf<ptd::MeshUnit> dMeshRecs;   // ptd::MeshUnit[]: triangles and inner nodes of every mesh of the scene (k_bounce<., ., ., true>)
     // textured scenes (k_bounce<..., TEX>): BounceArgs::texGeom / texDesc / texels / texUV
-    ptd::TexGeom *dTexGeom = nullptr;
-    int4 *dTexDesc = nullptr;
-    float4 *dTexels = nullptr, *dTexUV = nullptr;
+    DevBuf<ptd::TexGeom> dTexGeom;
+    DevBuf<int4> dTexDesc;
+    DevBuf<float4> dTexels, dTexUV;
     bool tex = false;       // a texture is bound to at least one primitive (or a height map: BUMP forms are TEX forms)
     // bump-mapped scenes (k_bounce<..., BUMP>): BounceArgs::bumpGeom / bumpUV / bumpTan
-    ptd::BumpGeom *dBumpGeom = nullptr;
-    float4 *dBumpUV = nullptr, *dBumpTan = nullptr;
+    DevBuf<ptd::BumpGeom> dBumpGeom;
+    DevBuf<float4> dBumpUV, dBumpTan;
     bool bump = false;      // a height map is bound to at least one primitive
     bool mesh = false;      // the scene holds triangle meshes: the k_bounce<., false, ., true> variants
     int meshStackNeed = 0;  // ... and the stack levels a brute-force walk of them needs per lane (k_gbuffer)
     // the denoiser (pt_denoise.h), all allocated on first use: the guide buffers of iteration dnGuideIter (0: none yet), the float4 images
     // the filter's levels pass on, and the packed RGB the last level writes
-    float4 *dnPosT = nullptr, *dnNrmId = nullptr, *dnPing[2] = {nullptr, nullptr};
-    float *dnOut = nullptr;
-    uchar4 *dnRgba = nullptr;       // pt_denoise_rgba8's bytes
+    DevBuf<float4> dnPosT, dnNrmId, dnPing[2];
+    DevBuf<float> dnOut;
+    DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes
     int dnGuideIter = 0;
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
-    int *dWalkIdx = nullptr, *dWalkRowOff = nullptr;
-    float4 *dWalkMeshRows = nullptr;   // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows); walkMeshLds: how many of them a workgroup stages in LDS (all, or none)
+    DevBuf<int> dWalkIdx, dWalkRowOff;
+    DevBuf<WalkMesh> dWalkMeshRows;    // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows); walkMeshLds: how many of them a workgroup stages in LDS (all, or none)
     int walkMeshLds = 0;
     int walkClassOff[kClsMax + 1] = {0}, walkAll0 = 0, walkAll1 = 0;
     int gridWalk = 0, gridWalkFirst = 0;
@@ -168,6 +230,7 @@ struct State {
     int poolChunks = 0;     // chunks per path pool (incl. the trash chunk 0); a pool holds poolChunks * kChunk paths per array
     int grid = 0;           // persistent grid of k_bounce<false>
     int gridFirst = 0;      // ... and of k_bounce<true> (its own register budget, hence its own residency)
+    const void *kernFirst = nullptr, *kernNext = nullptr;   // the forms of k_bounce the camera-ray launch / the later ones take (bounce_form)
     bool many = false;      // more than kBinMax small primitives (spheres, cubes that are neither walls nor binned): the k_bounce<., true> variants
     bool sweptCubes = false;  // ... some of them cubes (TileArgs::hot: kHotSweptCubes)
     bool dof = false;       // thin-lens camera: the k_bounce<true, ., true> variants for the camera-ray bounce
@@ -245,13 +308,51 @@ int reset_ctrl(Ctrl *dev, hipStream_t st) {
 
 PathPool pool(const Slot &sl, int which) {
     PathPool p;
-    p.base = sl.pathbuf[which];
-    p.list = sl.chunkList[which];
+    p.base = sl.pathbuf[which].p;
+    p.list = sl.chunkList[which].p;
     p.cap = (uint32_t)R().poolChunks << R().prm.chunkShift;
     return p;
 }
 
 #include "pt_host_scene.h"
+
+// magic_divisor for d, checked on the edges of every quotient range: n / d == (n * m) >> sh for the n < 2^30 the kernels divide
+int checked_magic(uint32_t d, uint32_t &m, uint32_t &sh) {
+    magic_divisor(d, m, sh);
+    for (uint64_t q = 0; q * d < (1ull << 30); q = q < 64 ? q + 1 : q * 2 + 1)
+        for (uint64_t n : {q * d, q * d + d - 1, (uint64_t)((1ull << 30) - 1) - q})
+            if (n < (1ull << 30) && (uint32_t)((n * m) >> sh) != (uint32_t)(n / d))
+                return fail(PT_ERR_INVALID, "pt_init: magic division self-check failed for d=%u n=%llu", d, (unsigned long long)n);
+    return PT_OK;
+}
+
+// One binding of pt_set_textures (scale == nullptr) or pt_set_bump_maps against the scene; bound: which primitives a binding of the kind names already
+int check_binding(const float *scale, size_t index, int geom, int texture, int ntris, const std::vector<float> &uvs, const PtGeom *geoms, int ngeoms,
+                  std::vector<char> &bound) {
+    const char *kind = scale ? "bump" : "texture", *meshKind = scale ? "bumped" : "textured", *bumped = scale ? "bumped " : "";
+    if (geom < 0 || geom >= ngeoms) return fail(PT_ERR_INVALID, "pt_init: %s binding %zu names geom %d of %d", kind, index, geom, ngeoms);
+    if (texture < 0 || texture >= (int)R().textures.size())
+        return fail(PT_ERR_INVALID, "pt_init: %s binding %zu names texture %d of %zu", kind, index, texture, R().textures.size());
+    if (bound[geom]++) return fail(PT_ERR_INVALID, "pt_init: geom %d has two %s bindings", geom, kind);
+    if (scale && !std::isfinite(*scale)) return fail(PT_ERR_INVALID, "pt_init: bump binding %zu has a non-finite scale", index);
+    if (geoms[geom].type == PT_MESH) {
+        if (uvs.empty()) return fail(PT_ERR_INVALID, "pt_init: %s mesh geom %d has no UVs", meshKind, geom);
+        const size_t have = mesh_of(geom)->tris.size();
+        if ((size_t)ntris * 9 != have) return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for %smesh geom %d of %zu", ntris, bumped, geom, have / 9);
+    } else if (!uvs.empty() || ntris != 0) {
+        return fail(PT_ERR_INVALID, "pt_init: UVs given for %sgeom %d, which is not a mesh", bumped, geom);
+    }
+    return PT_OK;
+}
+
+// a mesh binding's corner UVs (six floats per triangle) as the kernels read them: two float4 per triangle, {u0, v0, u1, v1}, {u2, v2, 0, 0}
+void pack_uvs(const std::vector<float> &uvs, int ntris, std::vector<float4> &out) {
+    for (int f = 0; f < ntris; ++f) {
+        const float *c = uvs.data() + 6 * (size_t)f;
+        out.push_back(make_float4(c[0], c[1], c[2], c[3]));
+        out.push_back(make_float4(c[4], c[5], 0.0f, 0.0f));
+    }
+}
 
 int resolve_events(std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms, long long &n) {
     for (auto &pr : v) {
@@ -267,50 +368,63 @@ int resolve_events(std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms
     return PT_OK;
 }
 
-// The instantiation of k_bounce a launch takes: FIRST (camera rays), MANY (per-lane sphere lists: scenes with more than
-// kBinMax spheres), DOF (thin lens: the camera-ray launch only), MESH (scenes with triangle meshes).
-template <bool F, bool M, bool D, bool ME, bool PL = false, bool CU = false, bool GR = false, bool TX = false, bool BU = false>
-const void *kb() { return reinterpret_cast<const void *>(k_bounce<F, M, D, ME, PL, CU, GR, TX, BU>); }
-// bump-mapped scenes: the twelve TEX forms again, with BUMP
-const void *bounce_kernel_bump(bool first, bool dof) {
-    if (R().many && R().mesh) return first ? (dof ? kb<true, true, true, true, false, true, false, true, true>() : kb<true, true, false, true, false, true, false, true, true>())
-                                           : kb<false, true, false, true, false, true, false, true, true>();
-    if (R().many) return first ? (dof ? kb<true, true, true, false, false, true, false, true, true>() : kb<true, true, false, false, false, true, false, true, true>())
-                               : kb<false, true, false, false, false, true, false, true, true>();
-    if (R().mesh) return first ? (dof ? kb<true, false, true, true, false, false, false, true, true>() : kb<true, false, false, true, false, false, false, true, true>())
-                               : kb<false, false, false, true, false, false, false, true, true>();
-    return first ? (dof ? kb<true, false, true, false, false, false, false, true, true>() : kb<true, false, false, false, false, false, false, true, true>())
-                 : kb<false, false, false, false, false, false, false, true, true>();
+// The forms of k_bounce.  A form is the word of its nine template flags, in the template's order: FIRST (camera rays), MANY (per-lane
+// lists of the swept primitives: scenes with more than kBinMax of them), DOF (thin lens: the camera-ray launch only), MESH (scenes with
+// triangle meshes), PLAIN, CUBES, GROUPS, TEX, BUMP.
+enum : uint32_t { kbFirst = 1, kbMany = 2, kbDof = 4, kbMesh = 8, kbPlain = 16, kbCubes = 32, kbGroups = 64, kbTex = 128, kbBump = 256, kbForms = 512 };
+
+// The forms that are instantiated -- each is a large kernel, so these 48 of the 512 words and no other: the textured ones (24: with and
+// without BUMP, never PLAIN or GROUPS, MANY always in the form that sweeps cubes too), the two PLAIN ones, the four GROUPS ones, and the
+// 18 of MANY (with or without CUBES) x MESH x camera rays with a lens / without / later bounces.
+constexpr bool bounce_form_valid(uint32_t f) {
+    const bool F = f & kbFirst, M = f & kbMany, D = f & kbDof, ME = f & kbMesh, PL = f & kbPlain, CU = f & kbCubes, GR = f & kbGroups,
+               TX = f & kbTex, BU = f & kbBump;
+    return f < kbForms && (!D || F) && (!BU || TX) && (!CU || M) && (!TX || (!PL && !GR && CU == M)) && (!PL || (!M && !ME && !D && !GR)) &&
+           (!GR || (M && !ME && !D));
 }
-// textured scenes: twelve instantiations of their own -- never PLAIN or GROUPS, and MANY always in the form that sweeps cubes too
-const void *bounce_kernel_tex(bool first, bool dof) {
-    if (R().bump) return bounce_kernel_bump(first, dof);
-    if (R().many && R().mesh) return first ? (dof ? kb<true, true, true, true, false, true, false, true>() : kb<true, true, false, true, false, true, false, true>())
-                                           : kb<false, true, false, true, false, true, false, true>();
-    if (R().many) return first ? (dof ? kb<true, true, true, false, false, true, false, true>() : kb<true, true, false, false, false, true, false, true>())
-                               : kb<false, true, false, false, false, true, false, true>();
-    if (R().mesh) return first ? (dof ? kb<true, false, true, true, false, false, false, true>() : kb<true, false, false, true, false, false, false, true>())
-                               : kb<false, false, false, true, false, false, false, true>();
-    return first ? (dof ? kb<true, false, true, false, false, false, false, true>() : kb<true, false, false, false, false, false, false, true>())
-                 : kb<false, false, false, false, false, false, false, true>();
+template <uint32_t f>
+const void *kb() {
+    if constexpr (bounce_form_valid(f))
+        return reinterpret_cast<const void *>(k_bounce<(f & kbFirst) != 0, (f & kbMany) != 0, (f & kbDof) != 0, (f & kbMesh) != 0, (f & kbPlain) != 0,
+                                                       (f & kbCubes) != 0, (f & kbGroups) != 0, (f & kbTex) != 0, (f & kbBump) != 0>);
+    else
+        return nullptr;
 }
-const void *bounce_kernel(bool first, bool dof) {
-    if (R().tex) return bounce_kernel_tex(first, dof);
-    // (plain scenes -- diffuse / emissive / perfect-mirror materials, no README extra: the instantiations without the rarer branches)
-    if (R().plain && !R().mesh && !R().many && !dof) return first ? kb<true, false, false, false, true>() : kb<false, false, false, false, true>();
-    if (R().grouped && !first)            // hundreds of swept primitives: the two-level sweep, nothing of the scene's tables in LDS
-        return R().sweptCubes ? kb<false, true, false, false, false, true, true>() : kb<false, true, false, false, false, false, true>();
-    if (R().grouped && !dof)              // ... and their (pinhole) camera-ray bounce: hit records, frames and rows from global memory too
-        return R().sweptCubes ? kb<true, true, false, false, false, true, true>() : kb<true, true, false, false, false, false, true>();
-    if (R().many && R().sweptCubes) {     // many small primitives, cubes among them: the per-lane tests take either type
-        if (R().mesh) return first ? (dof ? kb<true, true, true, true, false, true>() : kb<true, true, false, true, false, true>()) : kb<false, true, false, true, false, true>();
-        return first ? (dof ? kb<true, true, true, false, false, true>() : kb<true, true, false, false, false, true>()) : kb<false, true, false, false, false, true>();
-    }
-    if (R().mesh && R().many) return first ? (dof ? kb<true, true, true, true>() : kb<true, true, false, true>()) : kb<false, true, false, true>();
-    if (R().mesh) return first ? (dof ? kb<true, false, true, true>() : kb<true, false, false, true>()) : kb<false, false, false, true>();
-    if (first && dof) return R().many ? kb<true, true, true, false>() : kb<true, false, true, false>();
-    if (first) return R().many ? kb<true, true, false, false>() : kb<true, false, false, false>();
-    return R().many ? kb<false, true, false, false>() : kb<false, false, false, false>();
+template <size_t... f>
+const void *bounce_kernel_of(uint32_t form, std::index_sequence<f...>) {
+    static const void *const table[] = {kb<(uint32_t)f>()...};
+    return form < kbForms ? table[form] : nullptr;
+}
+// the kernel of a form, or nullptr: not one of the 48
+const void *bounce_kernel(uint32_t form) { return bounce_kernel_of(form, std::make_index_sequence<kbForms>()); }
+
+// The form a launch takes: `first` is the launch's (the camera-ray bounce), the rest the renderer's state (State: dof, many, sweptCubes,
+// mesh, grouped, tex, bump, plain).
+uint32_t bounce_form(bool first, bool dof, bool many, bool sweptCubes, bool mesh, bool grouped, bool tex, bool bump, bool plain) {
+    const bool D = first && dof;                      // thin lens: the camera-ray launch only
+    uint32_t f = (first ? kbFirst : 0u) | (many ? kbMany : 0u) | (D ? kbDof : 0u) | (mesh ? kbMesh : 0u);
+    // textured scenes: forms of their own -- never PLAIN or GROUPS (textured scenes are never grouped: the grouped sweep is the ungrouped
+    // one's result, bit for bit, and the TEX forms leave it out), and MANY always in the form that sweeps cubes too
+    if (tex) f |= kbTex;
+    if (bump) f |= kbBump;                            // bump-mapped scenes: the TEX forms again, with BUMP
+    // plain scenes -- diffuse / emissive / perfect-mirror materials, no README extra: the instantiations without the rarer branches
+    if (!tex && plain && !mesh && !many && !D) f |= kbPlain;
+    // many small primitives, cubes among them: the per-lane tests take either type
+    if (many && (tex || sweptCubes)) f |= kbCubes;
+    // hundreds of swept primitives: the two-level sweep, nothing of the scene's tables in LDS -- the later bounces and the (pinhole)
+    // camera-ray bounce, whose hit records, frames and rows come from global memory too; the grouped camera-ray bounce with a lens falls
+    // back to the flat sweep
+    if (!tex && grouped && !D) f |= kbGroups;
+    return f;
+}
+// ... resolved once by pt_init (State::kernFirst / kernNext); a state whose form is not instantiated is an internal error, never a fallback
+int resolve_bounce_kernel(bool first, const void **kernel) {
+    const uint32_t f = bounce_form(first, R().dof, R().many, R().sweptCubes, R().mesh, R().grouped, R().tex, R().bump, R().plain);
+    *kernel = bounce_kernel(f);
+    if (!*kernel)
+        return fail(PT_ERR_INVALID, "pt_init: internal error: no k_bounce form 0x%x (FIRST %d MANY %d DOF %d MESH %d PLAIN %d CUBES %d GROUPS %d TEX %d BUMP %d)", f,
+                    !!(f & kbFirst), !!(f & kbMany), !!(f & kbDof), !!(f & kbMesh), !!(f & kbPlain), !!(f & kbCubes), !!(f & kbGroups), !!(f & kbTex), !!(f & kbBump));
+    return PT_OK;
 }
 
 const void *walk_kernel(bool first, bool dof) {
@@ -354,27 +468,27 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     const bool lastBits = R().many && !R().mesh && R().prm.sphOMax > 0.0f && R().prm.emittersBinned;
     if (lastBits && nextIsLast) ba.tile.hot |= kHotWritesLastBits;
     if (lastBits && lastBounce && depth > 1) ba.tile.hot |= kHotReadsLastBits;
-    ba.ctrl = sl.ctrl; ba.ggeoms = R().dgeoms; ba.gmats = R().dmats; ba.ghit = R().dGeomHit; ba.contrib = contrib; ba.hitMask = sl.hitMask;
-    ba.sphCull = R().dSphCull; ba.classIdx = R().dClassIdx;
-    ba.rowOff = R().dRowOff; ba.rowIdx = R().dRowIdx;
-    ba.camPix = R().dCamPix; ba.camWave = R().dCamWave; ba.camSigIdx = R().dCamSigIdx;
-    ba.walls = R().dwalls;
-    ba.meshRecs = R().dMeshRecs;
+    ba.ctrl = sl.ctrl.p; ba.ggeoms = R().dgeoms.p; ba.gmats = R().dmats.p; ba.ghit = reinterpret_cast<const float4 *>(R().dGeomHit.p); ba.contrib = contrib; ba.hitMask = sl.hitMask.p;
+    ba.sphCull = R().dSphCull.p; ba.classIdx = R().dClassIdx.p;
+    ba.rowOff = R().dRowOff.p; ba.rowIdx = R().dRowIdx.p;
+    ba.camPix = R().dCamPix.p; ba.camWave = R().dCamWave.p; ba.camSigIdx = R().dCamSigIdx.p;
+    ba.walls = R().dwalls.p;
+    ba.meshRecs = reinterpret_cast<const float4 *>(R().dMeshRecs.p);
     ba.hostFault = R().hostFaultDev;
-    ba.rows = reinterpret_cast<const float4 *>(R().dRows);
-    ba.meshHit = sl.meshHit; ba.walkIdx = R().dWalkIdx; ba.walkRowOff = R().dWalkRowOff;
+    ba.rows = reinterpret_cast<const float4 *>(R().dRows.p);
+    ba.meshHit = sl.meshHit.p; ba.walkIdx = R().dWalkIdx.p; ba.walkRowOff = R().dWalkRowOff.p;
     memcpy(ba.walkClassOff, R().walkClassOff, sizeof ba.walkClassOff);
     ba.walkAll0 = R().walkAll0; ba.walkAll1 = R().walkAll1;
-    ba.walkMeshRows = R().dWalkMeshRows; ba.walkMeshLds = R().walkMeshLds;
-    ba.sphGroups = R().dSphGroups;
-    ba.texGeom = R().dTexGeom; ba.texDesc = R().dTexDesc; ba.texels = R().dTexels; ba.texUV = R().dTexUV;
-    ba.bumpGeom = R().dBumpGeom; ba.bumpUV = R().dBumpUV; ba.bumpTan = R().dBumpTan;
+    ba.walkMeshRows = reinterpret_cast<const float4 *>(R().dWalkMeshRows.p); ba.walkMeshLds = R().walkMeshLds;
+    ba.sphGroups = R().dSphGroups.p;
+    ba.texGeom = R().dTexGeom.p; ba.texDesc = R().dTexDesc.p; ba.texels = R().dTexels.p; ba.texUV = R().dTexUV.p;
+    ba.bumpGeom = R().dBumpGeom.p; ba.bumpUV = R().dBumpUV.p; ba.bumpTan = R().dBumpTan.p;
     void *kargs[] = {&ba};
     const bool first = depth == 1;
     // scenes with meshes: the walks of this bounce's rays, ahead of it (pt_mesh_walk.h)
     if (R().mesh)
         HIPCHECK(hipLaunchKernel(walk_kernel(first, first && R().dof), dim3(first ? R().gridWalkFirst : R().gridWalk), dim3(kBlock), kargs, R().ldsWalk, sl.stream));
-    HIPCHECK(hipLaunchKernel(bounce_kernel(first, first && R().dof), dim3(first ? R().gridFirst : R().grid), dim3(kBlock), kargs, first ? R().ldsBytes : R().ldsBytesNext, sl.stream));
+    HIPCHECK(hipLaunchKernel(first ? R().kernFirst : R().kernNext, dim3(first ? R().gridFirst : R().grid), dim3(kBlock), kargs, first ? R().ldsBytes : R().ldsBytesNext, sl.stream));
     if (e0) {
         HIPCHECK(hipEventRecord(e1, sl.stream));
         R().evBounce.emplace_back(e0, e1);
@@ -453,14 +567,21 @@ int sync_all() {
     return PT_OK;
 }
 
+// what a set fault word (Ctrl::error) is reported as
+std::string fault_message(uint32_t bits) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "device fault 0x%x:%s%s (results of this render are void; re-init)", bits,
+             (bits & kFaultPoolExhausted) ? " path pool exhausted" : "", (bits & kFaultReserveTimeout) ? " chunk reservation timed out" : "");
+    return buf;
+}
+
 int check_device_fault() {
     int rc = sync_all();
     if (rc) return rc;
     for (int i = 0; i < R().nslots; ++i) {
         uint32_t err = 0;
-        HIPCHECK(hipMemcpy(&err, &R().slot[i].ctrl->error, sizeof err, hipMemcpyDeviceToHost));
-        if (err) return fail(PT_ERR_DEVICE, "device fault 0x%x:%s%s (results of this render are void; re-init)", err,
-                             (err & kFaultPoolExhausted) ? " path pool exhausted" : "", (err & kFaultReserveTimeout) ? " chunk reservation timed out" : "");
+        HIPCHECK(hipMemcpy(&err, &R().slot[i].ctrl.p->error, sizeof err, hipMemcpyDeviceToHost));
+        if (err) return fail(PT_ERR_DEVICE, "%s", fault_message(err).c_str());
     }
     return PT_OK;
 }
@@ -477,7 +598,8 @@ int readback_fault() {
     return PT_OK;
 }
 
-int persistent_grid(const void *kernel, size_t lds, int *grid) {
+// The grid of a persistent kernel: the workgroups of it a CU holds at once x the CUs -- for k_bounce, or for the mesh walk ahead of it
+int persistent_grid(const void *kernel, size_t lds, bool walk, int *grid) {
     int dev = 0;
     HIPCHECK(hipGetDevice(&dev));
     hipDeviceProp_t prop;
@@ -485,17 +607,21 @@ int persistent_grid(const void *kernel, size_t lds, int *grid) {
     int perCU = 0;
     HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, kBlock, lds));
     if (perCU < 1) perCU = 1;
-    // All four instantiations fit eight workgroups per CU (<= 80 SGPRs, <= 64 VGPRs; the sphere-list variants seven).  A
-    // launch that has the GPU to itself (pipeline_depth 1) is fastest with all of them (0.253 ms against 0.274 with six);
-    // with batches in flight on neighbouring streams six per launch is better (131.2 G paths/s against 128.9 with eight):
-    // the two free wave slots per SIMD go to the neighbouring batch's launches, which fill this launch's tail.
-    int cap = R().nslots > 1 ? 6 : 8;
-    // PT_FLAG_TRACE_AHEAD (one call and one small commit per iteration while batches are traced ahead): four, so that the commit -- and the
-    // copies and collectives a caller puts behind it every iteration -- find free wave slots next to two batches' persistent workgroups
-    // instead of waiting for one of them to end (config C3 as written: 0.0538 -> 0.0492 ms per iteration, profiles/r05_c3_experiments.txt)
-    if ((R().flags & PT_FLAG_TRACE_AHEAD) && R().nslots > 1) cap = 4;
-    if (const char *e = getenv("PT_AMD_BLOCKS_PER_CU")) cap = atoi(e);   // experiments only
-    if (perCU > cap) perCU = cap;
+    if (walk) {      // (every workgroup that fits: none of the bounce kernel's caps)
+        if (const char *e = getenv("PT_AMD_WALK_BLOCKS_PER_CU")) perCU = std::max(1, atoi(e));   // experiments only
+    } else {
+        // All four instantiations fit eight workgroups per CU (<= 80 SGPRs, <= 64 VGPRs; the sphere-list variants seven).  A
+        // launch that has the GPU to itself (pipeline_depth 1) is fastest with all of them (0.253 ms against 0.274 with six);
+        // with batches in flight on neighbouring streams six per launch is better (131.2 G paths/s against 128.9 with eight):
+        // the two free wave slots per SIMD go to the neighbouring batch's launches, which fill this launch's tail.
+        int cap = R().nslots > 1 ? 6 : 8;
+        // PT_FLAG_TRACE_AHEAD (one call and one small commit per iteration while batches are traced ahead): four, so that the commit -- and the
+        // copies and collectives a caller puts behind it every iteration -- find free wave slots next to two batches' persistent workgroups
+        // instead of waiting for one of them to end (config C3 as written: 0.0538 -> 0.0492 ms per iteration, profiles/r05_c3_experiments.txt)
+        if ((R().flags & PT_FLAG_TRACE_AHEAD) && R().nslots > 1) cap = 4;
+        if (const char *e = getenv("PT_AMD_BLOCKS_PER_CU")) cap = atoi(e);   // experiments only
+        if (perCU > cap) perCU = cap;
+    }
     *grid = prop.multiProcessorCount * perCU;
     if (const char *e = getenv("PT_AMD_MAX_GRID")) *grid = std::max(1, std::min(*grid, atoi(e)));   // tests: a small or partitioned device's grid
     return PT_OK;
@@ -510,7 +636,7 @@ int trace_batch(Slot &sl, int first_iter, int count) {
     HIPCHECK(hipStreamWaitEvent(sl.stream, sl.evCommitted, 0));
     const int D = R().prm.traceDepth;
     for (int d = 1; d <= D; ++d) {
-        int rc = launch_bounce(sl, first_iter, count, d, d == D, sl.contrib, d + 1 == D);
+        int rc = launch_bounce(sl, first_iter, count, d, d == D, sl.contrib.p, d + 1 == D);
         if (rc) {
             // a launch failed with part of the batch enqueued: counters, parity and radiance buffers are half-updated, so the
             // renderer refuses further work until it is re-initialised (pt_free still releases everything)
@@ -533,10 +659,10 @@ int commit_range(Slot &sl, int count, int b0, int b1, bool discard) {
         }
         const int compact = (R().flags & PT_FLAG_ACCUM_SHARD_ROWS) ? 1 : 0;
         if (b1 == b0 + 1)      // one iteration of the batch (the reference's protocol over a batch traced ahead): the light kernel
-            hipLaunchKernelGGL(k_commit_one, dim3((R().nLocal + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib, sl.hitMask,
+            hipLaunchKernelGGL(k_commit_one, dim3((R().nLocal + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib.p, sl.hitMask.p,
                                compact, b0, discard ? 1 : 0, snap);
         else
-            hipLaunchKernelGGL(k_commit, dim3((R().nLocal + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib, sl.hitMask,
+            hipLaunchKernelGGL(k_commit, dim3((R().nLocal + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib.p, sl.hitMask.p,
                                count, compact, b0, b1, discard ? 1 : 0, snap);
         HIPCHECK(hipGetLastError());
     }
@@ -635,8 +761,8 @@ int ensure_guides(int guideIter, float *ms) {
     if (ms) *ms = 0.0f;
     if (guideIter < 1 || guideIter >= kIterEnd) return fail(PT_ERR_INVALID, "guide_iter must be 1..4194303");
     const size_t P = (size_t)R().P;
-    if (!R().dnPosT) HIPCHECK(hipMalloc(&R().dnPosT, P * sizeof(float4)));
-    if (!R().dnNrmId) HIPCHECK(hipMalloc(&R().dnNrmId, P * sizeof(float4)));
+    if (!R().dnPosT.p) PTCHECK(R().dnPosT.alloc(P));
+    if (!R().dnNrmId.p) PTCHECK(R().dnNrmId.alloc(P));
     if (R().dnGuideIter == guideIter) return PT_OK;
     const size_t stackBytes = R().mesh ? (size_t)std::max(R().meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0;
     if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "guide buffers: a mesh hierarchy needs %d stack levels", R().meshStackNeed);
@@ -648,8 +774,8 @@ int ensure_guides(int guideIter, float *ms) {
         HIPCHECK(hipEventRecord(e0, R().stream));
     }
     R().dnGuideIter = 0;
-    hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), stackBytes, R().stream, R().prm, R().dgeoms,
-                       reinterpret_cast<const float4 *>(R().dMeshRecs), guideIter, R().dnPosT, R().dnNrmId);
+    hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), stackBytes, R().stream, R().prm, R().dgeoms.p,
+                       reinterpret_cast<const float4 *>(R().dMeshRecs.p), guideIter, R().dnPosT.p, R().dnNrmId.p);
     HIPCHECK(hipGetLastError());
     if (ms) {
         HIPCHECK(hipEventRecord(e1, R().stream));
@@ -675,12 +801,12 @@ int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, f
     rc = ensure_guides(p->guide_iter, ms);
     if (rc) return rc;
     const size_t P = (size_t)R().P;
-    if (!R().dnOut) HIPCHECK(hipMalloc(&R().dnOut, P * 3 * sizeof(float)));
+    if (!R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
     for (int k = 0; k < 2 && k < p->levels - 1; ++k)
-        if (!R().dnPing[k]) HIPCHECK(hipMalloc(&R().dnPing[k], P * sizeof(float4)));
+        if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
     AtrousArgs A;
     A.accum = R().image;
-    A.posT = R().dnPosT; A.nrmId = R().dnNrmId;
+    A.posT = R().dnPosT.p; A.nrmId = R().dnNrmId.p;
     A.W = R().prm.W; A.H = R().prm.H;
     A.samples = (float)samples;
     const float invC0 = 1.0f / (p->sigma_color * p->sigma_color);
@@ -694,9 +820,9 @@ int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, f
         const bool first = i == 0, last = i == p->levels - 1;
         A.step = 1 << i;
         A.invC = invC0 * (float)(1 << (2 * i));
-        A.cin = first ? nullptr : R().dnPing[(i - 1) & 1];
-        A.cout = last ? nullptr : R().dnPing[i & 1];
-        A.out3 = last ? R().dnOut : nullptr;
+        A.cin = first ? nullptr : R().dnPing[(i - 1) & 1].p;
+        A.cout = last ? nullptr : R().dnPing[i & 1].p;
+        A.out3 = last ? R().dnOut.p : nullptr;
         // (NOT measured yet -- profiles/denoise_cost.py is the measurement to run: the expectation is that the tiled form wins while a class's
         // rows still share cache lines, and the gather, whose taps stay coalesced at every step, beyond)
         int f = form != kAtrousAuto ? form : (A.step <= kAtrousTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
@@ -724,20 +850,10 @@ int denoise_to_host(int samples, const PtDenoiseParams *p, size_t bytes, int for
     if (!rgb_mean_host) return fail(PT_ERR_INVALID, "%s: null", who);
     int rc = denoise_run(samples, p, bytes, form, ms, who);
     if (rc) return rc;
-    HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut.p, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
     return readback_fault();
 }
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) {
-        HIPCHECK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-        return PT_OK;
-    }
-};
 
 }  // namespace
 
@@ -763,7 +879,7 @@ namespace {
 // everything pt_init allocated (pt_free, and pt_init's own restart)
 void free_renderer() {
     // pathtraceFree before the first Init (src/main.cpp:91-94) must be a no-op
-    if (!R().init && !R().image && !R().dgeoms && R().nslots == 0 && !R().hostFault && !R().pinnedHost) return;
+    if (!R().init && !R().image && !R().dgeoms.p && R().nslots == 0 && !R().hostFault && !R().pinnedHost) return;
     if (R().device >= 0 && R().nslots > 0) (void)hipSetDevice(R().device);     // (a host that switched devices in between)
     for (int i = 0; i < kMaxSlots; ++i)
         if (R().slot[i].stream) (void)hipStreamSynchronize(R().slot[i].stream);
@@ -772,56 +888,16 @@ void free_renderer() {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
     }
-    R().evBounce.clear();
     for (hipEvent_t e : R().evFree) (void)hipEventDestroy(e);
-    R().evFree.clear();
     for (int i = 0; i < kMaxSlots; ++i) {
         Slot &sl = R().slot[i];
-        for (int k = 0; k < 2; ++k) {
-            if (sl.pathbuf[k]) (void)hipFree(sl.pathbuf[k]);
-            if (sl.chunkList[k]) (void)hipFree(sl.chunkList[k]);
-        }
-        if (sl.ctrl) (void)hipFree(sl.ctrl);
-        if (sl.contrib) (void)hipFree(sl.contrib);
-        if (sl.hitMask) (void)hipFree(sl.hitMask);
-        if (sl.meshHit) (void)hipFree(sl.meshHit);
         if (sl.evDone) (void)hipEventDestroy(sl.evDone);
         if (sl.evCommitted) (void)hipEventDestroy(sl.evCommitted);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
     }
     if (R().pinnedHost) (void)hipHostUnregister(R().pinnedHost);
     if (R().hostFault) (void)hipHostFree(R().hostFault);
-    if (R().ownImage && R().image) (void)hipFree(R().image);
-    if (R().dgeoms) (void)hipFree(R().dgeoms);
-    if (R().dGeomHit) (void)hipFree(R().dGeomHit);
-    if (R().dRows) (void)hipFree(R().dRows);
-    if (R().dmats) (void)hipFree(R().dmats);
-    if (R().dwalls) (void)hipFree(R().dwalls);
-    if (R().dSphCull) (void)hipFree(R().dSphCull);
-    if (R().dSphGroups) (void)hipFree(R().dSphGroups);
-    if (R().dClassIdx) (void)hipFree(R().dClassIdx);
-    if (R().dRowOff) (void)hipFree(R().dRowOff);
-    if (R().dRowIdx) (void)hipFree(R().dRowIdx);
-    if (R().dCamPix) (void)hipFree(R().dCamPix);
-    if (R().dCamWave) (void)hipFree(R().dCamWave);
-    if (R().dCamSigIdx) (void)hipFree(R().dCamSigIdx);
-    if (R().dMeshRecs) (void)hipFree(R().dMeshRecs);
-    if (R().dWalkIdx) (void)hipFree(R().dWalkIdx);
-    if (R().dWalkRowOff) (void)hipFree(R().dWalkRowOff);
-    if (R().dWalkMeshRows) (void)hipFree(R().dWalkMeshRows);
-    if (R().dTexGeom) (void)hipFree(R().dTexGeom);
-    if (R().dTexDesc) (void)hipFree(R().dTexDesc);
-    if (R().dTexels) (void)hipFree(R().dTexels);
-    if (R().dTexUV) (void)hipFree(R().dTexUV);
-    if (R().dBumpGeom) (void)hipFree(R().dBumpGeom);
-    if (R().dBumpUV) (void)hipFree(R().dBumpUV);
-    if (R().dBumpTan) (void)hipFree(R().dBumpTan);
-    if (R().dnPosT) (void)hipFree(R().dnPosT);
-    if (R().dnNrmId) (void)hipFree(R().dnNrmId);
-    if (R().dnPing[0]) (void)hipFree(R().dnPing[0]);
-    if (R().dnPing[1]) (void)hipFree(R().dnPing[1]);
-    if (R().dnOut) (void)hipFree(R().dnOut);
-    if (R().dnRgba) (void)hipFree(R().dnRgba);
+    // ... and every device table: the move-assignment below releases what the DevBufs of State and its Slots hold
     {   // (the registered meshes, textures and height maps outlive the renderer: see State::meshes)
         std::vector<ptm::HostMesh> keep = std::move(R().meshes);
         std::vector<State::HostTexture> keepTex = std::move(R().textures);
@@ -949,38 +1025,14 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             for (float c : t.rgb)
                 if (!std::isfinite(c)) return fail(PT_ERR_INVALID, "pt_init: texture %zu holds a non-finite texel", i);
         }
-        std::vector<char> bound(ngeoms, 0);
+        std::vector<char> bound(ngeoms, 0), bumped(ngeoms, 0);
         for (size_t i = 0; i < R().texBindings.size(); ++i) {
             const State::HostTexBinding &b = R().texBindings[i];
-            if (b.geom < 0 || b.geom >= ngeoms) return fail(PT_ERR_INVALID, "pt_init: texture binding %zu names geom %d of %d", i, b.geom, ngeoms);
-            if (b.texture < 0 || b.texture >= (int)R().textures.size())
-                return fail(PT_ERR_INVALID, "pt_init: texture binding %zu names texture %d of %zu", i, b.texture, R().textures.size());
-            if (bound[b.geom]++) return fail(PT_ERR_INVALID, "pt_init: geom %d has two texture bindings", b.geom);
-            if (geoms[b.geom].type == PT_MESH) {
-                const ptm::HostMesh *hm_ = mesh_of(b.geom);
-                if (b.uvs.empty()) return fail(PT_ERR_INVALID, "pt_init: textured mesh geom %d has no UVs", b.geom);
-                if ((size_t)b.ntris * 9 != hm_->tris.size())
-                    return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for mesh geom %d of %zu", b.ntris, b.geom, hm_->tris.size() / 9);
-            } else if (!b.uvs.empty() || b.ntris != 0) {
-                return fail(PT_ERR_INVALID, "pt_init: UVs given for geom %d, which is not a mesh", b.geom);
-            }
+            PTCHECK(check_binding(nullptr, i, b.geom, b.texture, b.ntris, b.uvs, geoms, ngeoms, bound));
         }
-        std::vector<char> bumped(ngeoms, 0);
         for (size_t i = 0; i < R().bumpBindings.size(); ++i) {
             const State::HostBumpBinding &b = R().bumpBindings[i];
-            if (b.geom < 0 || b.geom >= ngeoms) return fail(PT_ERR_INVALID, "pt_init: bump binding %zu names geom %d of %d", i, b.geom, ngeoms);
-            if (b.texture < 0 || b.texture >= (int)R().textures.size())
-                return fail(PT_ERR_INVALID, "pt_init: bump binding %zu names texture %d of %zu", i, b.texture, R().textures.size());
-            if (bumped[b.geom]++) return fail(PT_ERR_INVALID, "pt_init: geom %d has two bump bindings", b.geom);
-            if (!std::isfinite(b.scale)) return fail(PT_ERR_INVALID, "pt_init: bump binding %zu has a non-finite scale", i);
-            if (geoms[b.geom].type == PT_MESH) {
-                const ptm::HostMesh *hm_ = mesh_of(b.geom);
-                if (b.uvs.empty()) return fail(PT_ERR_INVALID, "pt_init: bumped mesh geom %d has no UVs", b.geom);
-                if ((size_t)b.ntris * 9 != hm_->tris.size())
-                    return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for bumped mesh geom %d of %zu", b.ntris, b.geom, hm_->tris.size() / 9);
-            } else if (!b.uvs.empty() || b.ntris != 0) {
-                return fail(PT_ERR_INVALID, "pt_init: UVs given for bumped geom %d, which is not a mesh", b.geom);
-            }
+            PTCHECK(check_binding(&b.scale, i, b.geom, b.texture, b.ntris, b.uvs, geoms, ngeoms, bumped));
         }
     }
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
@@ -1016,23 +1068,15 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     const H3 view{cam->view.x, cam->view.y, cam->view.z};
     k.shardRank = o.shard_rank; k.shardCount = o.shard_count;
     k.nLocal = R().nLocal;
-    magic_divisor((uint32_t)Wd, k.magicW, k.shiftW);
     magic_divisor((uint32_t)o.shard_count, k.magicS, k.shiftS);
     k.contribLocal = (o.shard_count > 1 && (long long)Wd * H < (1ll << 27)) ? 1 : 0;   // (the multiply-shift divisions hold below 2^27)
     // camera-ray tiles lie on rows padded to a multiple of the tile size (KParams::Wp)
     k.Wp = (Wd + kBlock - 1) / kBlock * kBlock;
     if ((long long)rows * k.Wp >= (1ll << 30)) return fail(PT_ERR_INVALID, "pt_init: frame too large (rows x padded width must stay below 2^30)");
     k.nLocalPad = rows * k.Wp;
-    magic_divisor((uint32_t)k.Wp, k.magicWp, k.shiftWp);
-    magic_divisor((uint32_t)std::max(k.nLocalPad, 1), k.magicN, k.shiftN);
-    for (uint32_t d : {(uint32_t)Wd, (uint32_t)k.Wp, (uint32_t)std::max(k.nLocalPad, 1)}) {       // self-check on the edges of every quotient range
-        uint32_t m, sh;
-        magic_divisor(d, m, sh);
-        for (uint64_t q = 0; q * d < (1ull << 30); q = q < 64 ? q + 1 : q * 2 + 1)
-            for (uint64_t n : {q * d, q * d + d - 1, (uint64_t)((1ull << 30) - 1) - q})
-                if (n < (1ull << 30) && (uint32_t)((n * m) >> sh) != (uint32_t)(n / d))
-                    return fail(PT_ERR_INVALID, "pt_init: magic division self-check failed for d=%u n=%llu", d, (unsigned long long)n);
-    }
+    PTCHECK(checked_magic((uint32_t)Wd, k.magicW, k.shiftW));
+    PTCHECK(checked_magic((uint32_t)k.Wp, k.magicWp, k.shiftWp));
+    PTCHECK(checked_magic((uint32_t)std::max(k.nLocalPad, 1), k.magicN, k.shiftN));
     k.ngeoms = ngeoms; k.nmats = nmats;
     // direct lighting: bounce `traceDepth` aims its diffuse scatter at a light and one more launch collects
     k.traceDepth = traceDepth + (direct ? 1 : 0);
@@ -1071,17 +1115,16 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     }
     R().dof = o.lens_radius > 0.0f;
     // plain: nothing in the scene takes the scatter's rarer branches (PT_AMD_NO_PLAIN: experiments / tests only)
-    R().plain = !direct && !(o.flags & PT_FLAG_MIXTURE_WEIGHTED) && !(getenv("PT_AMD_NO_PLAIN") && atoi(getenv("PT_AMD_NO_PLAIN")));
+    R().plain = !direct && !(o.flags & PT_FLAG_MIXTURE_WEIGHTED) && !env_flag("PT_AMD_NO_PLAIN");
     for (int i = 0; i < nmats; ++i)
         if (mats[i].hasRefractive > 0.0f || (mats[i].hasReflective > 0.0f && mats[i].specularExponent > 0.0f)) R().plain = false;
 
     if (o.accum_dev) {
         R().image = o.accum_dev;
-        R().ownImage = false;
     } else {
         const size_t n = (R().flags & PT_FLAG_ACCUM_SHARD_ROWS) ? (size_t)(R().nLocal > 0 ? R().nLocal : 1) : (size_t)R().P;
-        HIPCHECK(hipMalloc(&R().image, n * 3 * sizeof(float)));
-        R().ownImage = true;
+        PTCHECK(R().imageOwn.alloc(n * 3));
+        R().image = R().imageOwn.p;
         HIPCHECK(hipMemsetAsync(R().image, 0, n * 3 * sizeof(float), R().stream));
     }
     // Path pools: a bounce's queue is kSeg = kCls x kSub segments, each a list of chunks handed out on demand, one ahead of
@@ -1146,20 +1189,16 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         Slot &sl = R().slot[i];
         HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         for (int b = 0; b < 2; ++b) {
-            HIPCHECK(hipMalloc(&sl.pathbuf[b], cap * kNumArrays * sizeof(float)));
-            HIPCHECK(hipMalloc(&sl.chunkList[b], (size_t)kSeg * R().poolChunks * sizeof(unsigned long long)));
-            HIPCHECK(hipMemset(sl.chunkList[b], 0, (size_t)kSeg * R().poolChunks * sizeof(unsigned long long)));
+            PTCHECK(sl.pathbuf[b].alloc(cap * kNumArrays));
+            PTCHECK(sl.chunkList[b].alloc_zeroed((size_t)kSeg * R().poolChunks));
         }
-        HIPCHECK(hipMalloc(&sl.ctrl, sizeof(Ctrl)));
-        int rcc = reset_ctrl(sl.ctrl, nullptr);
-        if (rcc) return rcc;
+        PTCHECK(sl.ctrl.alloc(1));
+        PTCHECK(reset_ctrl(sl.ctrl.p, nullptr));
         // radiance buffers and iteration masks: the frame's pixels, or only this shard's (KParams::contribLocal)
         const size_t cpx = k.contribLocal ? (size_t)(R().nLocal > 0 ? R().nLocal : 1) : (size_t)R().P;
-        HIPCHECK(hipMalloc(&sl.contrib, (size_t)R().maxBatch * cpx * 3 * sizeof(float)));
-        HIPCHECK(hipMemset(sl.contrib, 0, (size_t)R().maxBatch * cpx * 3 * sizeof(float)));
-        HIPCHECK(hipMalloc(&sl.hitMask, (size_t)((R().maxBatch + 31) / 32) * cpx * sizeof(uint32_t)));
-        HIPCHECK(hipMemset(sl.hitMask, 0, (size_t)((R().maxBatch + 31) / 32) * cpx * sizeof(uint32_t)));
-        if (meshHitWords) HIPCHECK(hipMalloc(&sl.meshHit, meshHitWords * sizeof(unsigned long long)));
+        PTCHECK(sl.contrib.alloc_zeroed((size_t)R().maxBatch * cpx * 3));
+        PTCHECK(sl.hitMask.alloc_zeroed((size_t)((R().maxBatch + 31) / 32) * cpx));
+        if (meshHitWords) PTCHECK(sl.meshHit.alloc(meshHitWords));
         HIPCHECK(hipEventCreateWithFlags(&sl.evDone, hipEventDisableTiming));
         HIPCHECK(hipEventCreateWithFlags(&sl.evCommitted, hipEventDisableTiming));
     }
@@ -1169,7 +1208,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // triangle meshes: one record array for the scene, a hierarchy per mesh (pt_mesh.h)
     std::vector<ptd::MeshUnit> meshRecs;
     int meshStackNeed = 0;
-    const bool flatMeshes = getenv("PT_AMD_MESH_FLAT") && atoi(getenv("PT_AMD_MESH_FLAT"));   // tests only: no hierarchy
+    const bool flatMeshes = env_flag("PT_AMD_MESH_FLAT");   // tests only: no hierarchy
     std::vector<std::array<float, 6>> meshBox(ngeoms ? ngeoms : 1);
     std::vector<const float *> boxes(ngeoms ? ngeoms : 1, nullptr);
     std::vector<uint32_t> triBase(ngeoms ? ngeoms : 1, 0u);      // (textured meshes: the unit of the first triangle record, ptm::appendMesh)
@@ -1200,7 +1239,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     }
     // camera rays: pixel rectangles, their union and the per-row lists (thin lens: none -- rays start anywhere on the lens)
     CameraCull cc;
-    const bool cullOff = R().dof || (getenv("PT_AMD_NO_CAMERA_CULL") && atoi(getenv("PT_AMD_NO_CAMERA_CULL")));   // (the variable: tests only)
+    const bool cullOff = R().dof || env_flag("PT_AMD_NO_CAMERA_CULL");   // (the variable: tests only)
     build_camera_cull(geoms, ngeoms, k, cullOff, boxes, hg, cc);
     for (int a = 0; a < 4; ++a) k.sceneRect[a] = cc.sceneRect[a];
     {   // The camera-ray tiles' index space covers only the column bands (of kBlock pixels) and the rows of this shard that meet the
@@ -1224,16 +1263,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         k.firstSkipped = (int)((long long)R().nLocal - visited);
         k.Wp = std::max(nCols, 1) * kBlock;                       // (>= one band: the divisions below stay defined)
         k.nLocalPad = nCols > 0 ? nRows * k.Wp : 0;
-        magic_divisor((uint32_t)k.Wp, k.magicWp, k.shiftWp);
-        magic_divisor((uint32_t)std::max(k.nLocalPad, 1), k.magicN, k.shiftN);
-        for (uint32_t d : {(uint32_t)k.Wp, (uint32_t)std::max(k.nLocalPad, 1)}) {
-            uint32_t m, sh;
-            magic_divisor(d, m, sh);
-            for (uint64_t q = 0; q * d < (1ull << 30); q = q < 64 ? q + 1 : q * 2 + 1)
-                for (uint64_t n : {q * d, q * d + d - 1, (uint64_t)((1ull << 30) - 1) - q})
-                    if (n < (1ull << 30) && (uint32_t)((n * m) >> sh) != (uint32_t)(n / d))
-                        return fail(PT_ERR_INVALID, "pt_init: magic division self-check failed for d=%u n=%llu", d, (unsigned long long)n);
-        }
+        PTCHECK(checked_magic((uint32_t)k.Wp, k.magicWp, k.shiftWp));
+        PTCHECK(checked_magic((uint32_t)std::max(k.nLocalPad, 1), k.magicN, k.shiftN));
     }
     for (int i = 0; i < nmats; ++i) pack_material(mats[i], hm[i]);
     // Small primitives the queue is binned by (k_bounce): the spheres when there are at most kBinMax of them, then the
@@ -1304,7 +1335,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             hg[wallGeom[w]].flags |= (w + 1) << 2;
             hg[wallGeom[w]].cullFlags |= (w + 1) << 2;
         }
-        if (const char *e = getenv("PT_AMD_NO_WALLS")) { if (atoi(e)) { for (int i = 0; i < ngeoms; ++i) { hg[i].flags &= 3; hg[i].cullFlags &= 3; } k.nWalls = 0; k.wallOMax = 0.0f; k.nSlotWalls = 0; k.nPlaneWalls = 0; } }   // experiments only
+        if (env_flag("PT_AMD_NO_WALLS")) { for (int i = 0; i < ngeoms; ++i) { hg[i].flags &= 3; hg[i].cullFlags &= 3; } k.nWalls = 0; k.wallOMax = 0.0f; k.nSlotWalls = 0; k.nPlaneWalls = 0; }   // experiments only
         if (k.nPlaneWalls > 0) R().plain = false;      // (the rotated walls' certificate lives in the general instantiations only: k_bounce, wallPlanesOriented)
         k.allClassified = k.nWalls > 0 ? 1 : 0;
         for (int i = 0; i < ngeoms; ++i)
@@ -1318,10 +1349,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                 for (int fm : hm_->mats) emits = emits || (fm >= 0 && mats[fm].emittance > 0.0f);
         if (emits && !hg[i].binned) k.emittersBinned = 0;
     }
-    HIPCHECK(hipMalloc(&R().dgeoms, hg.size() * sizeof(GeomDev)));
-    HIPCHECK(hipMalloc(&R().dmats, hm.size() * sizeof(MaterialDev)));
-    HIPCHECK(hipMemcpy(R().dgeoms, hg.data(), hg.size() * sizeof(GeomDev), hipMemcpyHostToDevice));
-    HIPCHECK(hipMemcpy(R().dmats, hm.data(), hm.size() * sizeof(MaterialDev), hipMemcpyHostToDevice));
+    PTCHECK(R().dgeoms.upload(hg));
+    PTCHECK(R().dmats.upload(hm));
     {   // the per-primitive hit records, ready-made: a workgroup's prologue copies them to LDS in one round trip instead of following
         // primitive -> material index -> material on the device (every workgroup of every launch did)
         std::vector<GeomHitDev> hh(hg.size());
@@ -1338,11 +1367,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             memcpy(h.nm, G.invT, sizeof h.nm);
             memcpy(h.cubeFrame, G.cubeFrame, sizeof h.cubeFrame);
         }
-        HIPCHECK(hipMalloc(&R().dGeomHit, hh.size() * sizeof(GeomHitDev)));
-        HIPCHECK(hipMemcpy(R().dGeomHit, hh.data(), hh.size() * sizeof(GeomHitDev), hipMemcpyHostToDevice));
+        PTCHECK(R().dGeomHit.upload(reinterpret_cast<const unsigned char *>(hh.data()), hh.size() * sizeof(GeomHitDev)));
     }
-    HIPCHECK(hipMalloc(&R().dwalls, hw.size() * sizeof(WallBox)));
-    HIPCHECK(hipMemcpy(R().dwalls, hw.data(), hw.size() * sizeof(WallBox), hipMemcpyHostToDevice));
+    PTCHECK(R().dwalls.upload(hw));
     R().mesh = !meshRecs.empty();
     R().meshStackNeed = meshStackNeed;
     R().bump = !R().bumpBindings.empty();
@@ -1361,22 +1388,14 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             if (b.uvs.empty()) continue;
             tg[b.geom].uvBase = (int)(uv.size() / 2);
             tg[b.geom].triBase = (int)triBase[b.geom];
-            for (int f = 0; f < b.ntris; ++f) {
-                const float *c = b.uvs.data() + 6 * (size_t)f;
-                uv.push_back(make_float4(c[0], c[1], c[2], c[3]));
-                uv.push_back(make_float4(c[4], c[5], 0.0f, 0.0f));
-            }
+            pack_uvs(b.uvs, b.ntris, uv);
             if (uv.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many textured triangles");
         }
         if (uv.empty()) uv.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        HIPCHECK(hipMalloc(&R().dTexGeom, tg.size() * sizeof(ptd::TexGeom)));
-        HIPCHECK(hipMemcpy(R().dTexGeom, tg.data(), tg.size() * sizeof(ptd::TexGeom), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc(&R().dTexDesc, desc.size() * sizeof(int4)));
-        HIPCHECK(hipMemcpy(R().dTexDesc, desc.data(), desc.size() * sizeof(int4), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc(&R().dTexels, texels.size() * sizeof(float4)));
-        HIPCHECK(hipMemcpy(R().dTexels, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc(&R().dTexUV, uv.size() * sizeof(float4)));
-        HIPCHECK(hipMemcpy(R().dTexUV, uv.data(), uv.size() * sizeof(float4), hipMemcpyHostToDevice));
+        PTCHECK(R().dTexGeom.upload(tg));
+        PTCHECK(R().dTexDesc.upload(desc));
+        PTCHECK(R().dTexels.upload(texels));
+        PTCHECK(R().dTexUV.upload(uv));
     }
     if (R().bump) {        // per primitive its BumpGeom; per bumped triangle two float4 of corner UVs and two of tangents (a mesh's rows of its own,
                            // even where its texture binding carries the same UVs)
@@ -1389,29 +1408,21 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             const ptm::HostMesh *hm_ = mesh_of(b.geom);
             bg[b.geom].uvBase = (int)(uv.size() / 2);
             bg[b.geom].triBase = (int)triBase[b.geom];
+            pack_uvs(b.uvs, b.ntris, uv);
             for (int f = 0; f < b.ntris; ++f) {
-                const float *c = b.uvs.data() + 6 * (size_t)f;
-                uv.push_back(make_float4(c[0], c[1], c[2], c[3]));
-                uv.push_back(make_float4(c[4], c[5], 0.0f, 0.0f));
                 float4 tu, tv;
-                meshTangents(hm_->tris.data() + 9 * (size_t)f, c, tu, tv);
+                meshTangents(hm_->tris.data() + 9 * (size_t)f, b.uvs.data() + 6 * (size_t)f, tu, tv);
                 tan.push_back(tu);
                 tan.push_back(tv);
             }
             if (uv.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many bumped triangles");
         }
         if (uv.empty()) { uv.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f)); tan.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f)); }
-        HIPCHECK(hipMalloc(&R().dBumpGeom, bg.size() * sizeof(ptd::BumpGeom)));
-        HIPCHECK(hipMemcpy(R().dBumpGeom, bg.data(), bg.size() * sizeof(ptd::BumpGeom), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc(&R().dBumpUV, uv.size() * sizeof(float4)));
-        HIPCHECK(hipMemcpy(R().dBumpUV, uv.data(), uv.size() * sizeof(float4), hipMemcpyHostToDevice));
-        HIPCHECK(hipMalloc(&R().dBumpTan, tan.size() * sizeof(float4)));
-        HIPCHECK(hipMemcpy(R().dBumpTan, tan.data(), tan.size() * sizeof(float4), hipMemcpyHostToDevice));
+        PTCHECK(R().dBumpGeom.upload(bg));
+        PTCHECK(R().dBumpUV.upload(uv));
+        PTCHECK(R().dBumpTan.upload(tan));
     }
-    if (R().mesh) {
-        HIPCHECK(hipMalloc(&R().dMeshRecs, (meshRecs.size() + 4) * sizeof(ptd::MeshUnit)));     // (+ 4: a walk may read the record behind the last one)
-        HIPCHECK(hipMemcpy(R().dMeshRecs, meshRecs.data(), meshRecs.size() * sizeof(ptd::MeshUnit), hipMemcpyHostToDevice));
-    }
+    if (R().mesh) PTCHECK(R().dMeshRecs.upload(meshRecs.data(), meshRecs.size(), 4));     // (+ 4: a walk may read the record behind the last one)
 
     // The SWEPT primitives of a scene with many small ones (round 5: cubes too -- rounds 2-4 swept spheres only, and 64 small cubes cost
     // 4.7 x what 64 spheres did, profiles/r05_generality.txt): every sphere, and every cube that is neither a wall nor binned.  Their
@@ -1433,7 +1444,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             hg[i].cullFlags |= 64;
         }
     R().sweptCubes = nsweptCubes > 0;
-    if (nsweptCubes) HIPCHECK(hipMemcpy(R().dgeoms, hg.data(), hg.size() * sizeof(GeomDev), hipMemcpyHostToDevice));
+    if (nsweptCubes) PTCHECK(R().dgeoms.upload(hg));
     if (R().many) {        // the later bounces take the swept primitives from a packed copy of their culling data (ptk::SphereCull)
         std::vector<SphereCull> sc;
         for (int i = 0; i < ngeoms; ++i)
@@ -1487,13 +1498,11 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                 k.nSphGroups = (int)(sc.size() / (size_t)kSphGroupSize);
                 k.grpOMax = std::nextafter((float)ob, 0.0f);
                 k.grpLds = (int)sc.size() <= kGroupLdsMax ? 1 : 0;
-                HIPCHECK(hipMalloc(&R().dSphGroups, groups.size() * sizeof(SphereCull)));
-                HIPCHECK(hipMemcpy(R().dSphGroups, groups.data(), groups.size() * sizeof(SphereCull), hipMemcpyHostToDevice));
+                PTCHECK(R().dSphGroups.upload(groups));
             }
         }
         k.nSphCull = (int)sc.size();
-        HIPCHECK(hipMalloc(&R().dSphCull, sc.size() * sizeof(SphereCull)));
-        HIPCHECK(hipMemcpy(R().dSphCull, sc.data(), sc.size() * sizeof(SphereCull), hipMemcpyHostToDevice));
+        PTCHECK(R().dSphCull.upload(sc));
         // The tables a sphere-heavy workgroup stages in LDS -- the compact hit records, the cubes' face frames, the spheres' matrix rows,
         // the sweep's entry -> primitive map -- as ONE image in the kernel's own layout (k_bounce: S_GEOMHIT_SMALL .. behind S_SPH), so that
         // the prologue is a straight copy of 16-byte words: gathering them field by field from the primitives took ~30 dependent
@@ -1504,7 +1513,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             // them a workgroup of the 518-primitive scene took 103 KB of LDS, one per CU.  The limit: what four workgroups per CU leave each.)
             const size_t rowsAll = (size_t)ngeoms * kSphRowFloats * sizeof(float);
             const size_t ldsWithRows = sizeof(MaterialDev) * nmats + (size_t)miscWords(kClsMax) * sizeof(uint32_t) + hitB + frameB + rowsAll + (size_t)kListMax * kBlock * sizeof(uint16_t);
-            const bool rowsInLds = ldsWithRows <= 40 * 1024 && !R().grouped && !(getenv("PT_AMD_ROWS_GLOBAL") && atoi(getenv("PT_AMD_ROWS_GLOBAL")));   // (the variable: tests only)
+            const bool rowsInLds = ldsWithRows <= 40 * 1024 && !R().grouped && !env_flag("PT_AMD_ROWS_GLOBAL");   // (the variable: tests only)
             k.ldsRowFloats = rowsInLds ? ngeoms * kSphRowFloats : 0;
             const size_t rowB = rowsInLds ? rowsAll : 0, mapB = ((size_t)k.nSphCull + 7) / 8 * 8 * sizeof(uint16_t);
             // (+ 64 bytes: behind the last cube's frames a row of NaNs -- what k_bounce<..., GROUPS>, which reads the frames from this image in
@@ -1528,14 +1537,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                 const float qnan = std::nanf("");
                 for (int q = 0; q < 9; ++q) memcpy(blob.data() + hitB + (size_t)k.nCubes * 54 * sizeof(float) + q * sizeof(float), &qnan, sizeof qnan);
             }
-            if (R().dGeomHit) (void)hipFree(R().dGeomHit);
-            R().dGeomHit = nullptr;
-            HIPCHECK(hipMalloc(&R().dGeomHit, blob.size()));
-            HIPCHECK(hipMemcpy(R().dGeomHit, blob.data(), blob.size(), hipMemcpyHostToDevice));
-            if (!rowsInLds) {
-                HIPCHECK(hipMalloc(&R().dRows, rowsGlobal.size() * sizeof(float)));
-                HIPCHECK(hipMemcpy(R().dRows, rowsGlobal.data(), rowsGlobal.size() * sizeof(float), hipMemcpyHostToDevice));
-            }
+            PTCHECK(R().dGeomHit.upload(blob));      // (in place of the hit records uploaded above)
+            if (!rowsInLds) PTCHECK(R().dRows.upload(rowsGlobal));
         }
     }
     {   // Later bounces: which primitives a tile of queue class c looks at.  Class bit 3 = its paths may hit a binned primitive;
@@ -1563,31 +1566,22 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         k.classOff[kClsMax] = (int)idx.size();
         // camera rays: the per-row primitive lists (build_camera_cull)
         if (!cc.rowOff.empty()) {
-            HIPCHECK(hipMalloc(&R().dRowOff, cc.rowOff.size() * sizeof(int)));
-            HIPCHECK(hipMemcpy(R().dRowOff, cc.rowOff.data(), cc.rowOff.size() * sizeof(int), hipMemcpyHostToDevice));
-            HIPCHECK(hipMalloc(&R().dRowIdx, cc.rowIdx.size() * sizeof(int)));
-            HIPCHECK(hipMemcpy(R().dRowIdx, cc.rowIdx.data(), cc.rowIdx.size() * sizeof(int), hipMemcpyHostToDevice));
+            PTCHECK(R().dRowOff.upload(cc.rowOff));
+            PTCHECK(R().dRowIdx.upload(cc.rowIdx));
         }
         // ... and, where the camera-ray instantiation can take it (pinhole, no meshes -- their walk shares the row bands' index space,
         // BounceArgs::meshHit -- and not the sphere-heavy one), the packed work list in place of the row bands: the tiles' index space of
         // one iteration is then the list (KParams::nLocalPad), and every pixel outside it is tallied at once (KParams::firstSkipped)
-        const bool listOff = getenv("PT_AMD_NO_CAMERA_LIST") && atoi(getenv("PT_AMD_NO_CAMERA_LIST"));   // (the variable: tests only)
+        const bool listOff = env_flag("PT_AMD_NO_CAMERA_LIST");   // (the variable: tests only)
         CameraList cl;
         if (!listOff && !R().dof && !R().mesh && !R().many &&
             build_camera_list(cc, Wd, H, o.shard_rank, o.shard_count, k.nLocalPad, cl) && !cl.pix.empty()) {
             k.nLocalPad = (int)cl.pix.size();
             k.firstSkipped = (int)((long long)R().nLocal - cl.listed);
-            magic_divisor((uint32_t)k.nLocalPad, k.magicN, k.shiftN);
-            for (uint64_t q = 0; q * (uint64_t)k.nLocalPad < (1ull << 30); q = q < 64 ? q + 1 : q * 2 + 1)
-                for (uint64_t n : {q * k.nLocalPad, q * k.nLocalPad + k.nLocalPad - 1})
-                    if (n < (1ull << 30) && (uint32_t)((n * k.magicN) >> k.shiftN) != (uint32_t)(n / (uint64_t)k.nLocalPad))
-                        return fail(PT_ERR_INVALID, "pt_init: magic division self-check failed for d=%d n=%llu", k.nLocalPad, (unsigned long long)n);
-            HIPCHECK(hipMalloc(&R().dCamPix, cl.pix.size() * sizeof(uint32_t)));
-            HIPCHECK(hipMemcpy(R().dCamPix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIPCHECK(hipMalloc(&R().dCamWave, cl.wave.size() * sizeof(int)));
-            HIPCHECK(hipMemcpy(R().dCamWave, cl.wave.data(), cl.wave.size() * sizeof(int), hipMemcpyHostToDevice));
-            HIPCHECK(hipMalloc(&R().dCamSigIdx, cl.sigIdx.size() * sizeof(int)));
-            HIPCHECK(hipMemcpy(R().dCamSigIdx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int), hipMemcpyHostToDevice));
+            PTCHECK(checked_magic((uint32_t)k.nLocalPad, k.magicN, k.shiftN));
+            PTCHECK(R().dCamPix.upload(cl.pix));
+            PTCHECK(R().dCamWave.upload(cl.wave));
+            PTCHECK(R().dCamSigIdx.upload(cl.sigIdx));
         }
         if (!meshRecs.empty()) {
             // the mesh walks (k_mesh_walk) look at the meshes alone: the classes' lists, one list of all, the rows' lists (pairs as rowIdx's)
@@ -1606,7 +1600,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                     w.push_back(i);
                 }
             R().walkAll1 = (int)w.size();
-            HIPCHECK(hipMemcpy(R().dgeoms, hg.data(), hg.size() * sizeof(GeomDev), hipMemcpyHostToDevice));
+            PTCHECK(R().dgeoms.upload(hg));
             {   // the walk's rows, one per mesh in the order of their ordinals (ptk::WalkMesh)
                 const int nm = R().walkAll1 - R().walkAll0;
                 std::vector<WalkMesh> rowsW((size_t)nm);
@@ -1618,9 +1612,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                     memcpy(r.xf, G.xf, sizeof r.xf); memcpy(r.camObj, G.camObj, sizeof r.camObj);
                     r.stride = G.meshStride;
                 }
-                HIPCHECK(hipMalloc(&R().dWalkMeshRows, std::max<size_t>(rowsW.size(), 1) * sizeof(WalkMesh)));
-                HIPCHECK(hipMemcpy(R().dWalkMeshRows, rowsW.data(), rowsW.size() * sizeof(WalkMesh), hipMemcpyHostToDevice));
-                const bool forceGlobal = getenv("PT_AMD_WALK_ROWS_GLOBAL") && atoi(getenv("PT_AMD_WALK_ROWS_GLOBAL"));      // tests only
+                PTCHECK(R().dWalkMeshRows.upload(rowsW));
+                const bool forceGlobal = env_flag("PT_AMD_WALK_ROWS_GLOBAL");      // tests only
                 R().walkMeshLds = (nm <= kWalkMeshLdsMax && !forceGlobal) ? nm : 0;
             }
             if (!cc.rowOff.empty()) {
@@ -1632,15 +1625,12 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                         if (hg[cc.rowIdx[2 * e]].flags & 32) { w.push_back(cc.rowIdx[2 * e]); w.push_back(cc.rowIdx[2 * e + 1]); }
                 }
                 ro[cc.rowOff.size() - 1] = (int)(w.size() / 2);
-                HIPCHECK(hipMalloc(&R().dWalkRowOff, ro.size() * sizeof(int)));
-                HIPCHECK(hipMemcpy(R().dWalkRowOff, ro.data(), ro.size() * sizeof(int), hipMemcpyHostToDevice));
+                PTCHECK(R().dWalkRowOff.upload(ro));
             }
-            HIPCHECK(hipMalloc(&R().dWalkIdx, w.size() * sizeof(int)));
-            HIPCHECK(hipMemcpy(R().dWalkIdx, w.data(), w.size() * sizeof(int), hipMemcpyHostToDevice));
+            PTCHECK(R().dWalkIdx.upload(w));
         }
         if (idx.empty()) idx.push_back(0);
-        HIPCHECK(hipMalloc(&R().dClassIdx, idx.size() * sizeof(int)));
-        HIPCHECK(hipMemcpy(R().dClassIdx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+        PTCHECK(R().dClassIdx.upload(idx));
     }
     const size_t ldsFixed = sizeof(MaterialDev) * nmats + (size_t)miscWords((R().mesh || R().many) ? kClsMax : kCls) * sizeof(uint32_t) +
                             (R().many ? manyHitBytes(ngeoms) + (size_t)k.nCubes * 54 * sizeof(float) + manyFramePad(k.nCubes) +
@@ -1670,31 +1660,21 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     if (R().ldsBytesNext == 0) R().ldsBytesNext = R().ldsBytes;
     if (R().ldsBytes > 160 * 1024) return fail(PT_ERR_INVALID, "pt_init: scene does not fit the 160 KiB LDS (%zu B)", R().ldsBytes);
     if (nmats >= 4096) return fail(PT_ERR_INVALID, "pt_init: more than 4095 materials");      // (TileArgs::hot holds nmats in 12 bits)
-    const void *kFirst = bounce_kernel(true, R().dof);
-    const void *kNext = bounce_kernel(false, false);
+    PTCHECK(resolve_bounce_kernel(true, &R().kernFirst));
+    PTCHECK(resolve_bounce_kernel(false, &R().kernNext));
     if (R().ldsBytes > 64 * 1024) {
-        HIPCHECK(hipFuncSetAttribute(kFirst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsBytes));
-        HIPCHECK(hipFuncSetAttribute(kNext, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsBytes));
+        HIPCHECK(hipFuncSetAttribute(R().kernFirst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsBytes));
+        HIPCHECK(hipFuncSetAttribute(R().kernNext, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsBytes));
     }
     if (R().mesh)
         for (int first = 0; first < 2; ++first) {
             const void *kw = walk_kernel(first != 0, first && R().dof);
             if (R().ldsWalk > 64 * 1024) HIPCHECK(hipFuncSetAttribute(kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsWalk));
-            int dev = 0, perCU = 0;
-            HIPCHECK(hipGetDevice(&dev));
-            hipDeviceProp_t prop;
-            HIPCHECK(hipGetDeviceProperties(&prop, dev));
-            HIPCHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kw, kBlock, R().ldsWalk));
-            if (perCU < 1) perCU = 1;
-            if (const char *e = getenv("PT_AMD_WALK_BLOCKS_PER_CU")) perCU = std::max(1, atoi(e));   // experiments only
-            int &grid = first ? R().gridWalkFirst : R().gridWalk;
-            grid = prop.multiProcessorCount * perCU;
-            if (const char *e = getenv("PT_AMD_MAX_GRID")) grid = std::max(1, std::min(grid, atoi(e)));
+            PTCHECK(persistent_grid(kw, R().ldsWalk, true, first ? &R().gridWalkFirst : &R().gridWalk));
         }
     for (int first = 0; first < 2; ++first) {
         int &grid = first ? R().gridFirst : R().grid;
-        int rc = persistent_grid(first ? kFirst : kNext, first ? R().ldsBytes : R().ldsBytesNext, &grid);
-        if (rc) return rc;
+        PTCHECK(persistent_grid(first ? R().kernFirst : R().kernNext, first ? R().ldsBytes : R().ldsBytesNext, false, &grid));
         if (grid > R().numTilesMax) grid = R().numTilesMax;
         grid = (grid / kSub) * kSub;      // T % kSub == blockIdx % kSub for every tile T of a workgroup (kSub: a multiple of the mesh scenes' 4 too)
         if (grid < kSub) grid = kSub;
@@ -1707,7 +1687,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // which needs a grid that is a multiple of the tiles per row (k_bounce<true, .>).
     // (the packed work list of camera rays has no column bands: nothing to rotate)
     R().prm.tilesPerRow = 0;
-    if (R().prm.Wp / kBlock > 1 && R().dCamPix == nullptr) {
+    if (R().prm.Wp / kBlock > 1 && R().dCamPix.p == nullptr) {
         const int perRow = R().prm.Wp / kBlock;
         auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
         if (gcd(perRow, kSub) == 1) {
@@ -1720,7 +1700,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
             }
         }
     }
-    if (getenv("PT_AMD_VERBOSE") && atoi(getenv("PT_AMD_VERBOSE")))       // experiments: what pt_init decided
+    if (env_flag("PT_AMD_VERBOSE"))       // experiments: what pt_init decided
         fprintf(stderr, "pt_init: lds %zu / %zu B, grid %d / %d, mesh %d many %d plain %d, binned %d walls %d (slots %d, planes %d) allClassified %d, sphCull %d (cluster 0: %d) omax %g\n",
                 R().ldsBytes, R().ldsBytesNext, R().gridFirst, R().grid, (int)R().mesh, (int)R().many, (int)R().plain, k.nBinned, k.nWalls, k.nSlotWalls, k.nPlaneWalls, k.allClassified, k.nSphCull,
                 k.sphN0, (double)k.sphOMax);
@@ -1875,11 +1855,11 @@ int pt_denoise_rgba8(int samples, const PtDenoiseParams *p, size_t params_struct
     if (!rgba_host) return fail(PT_ERR_INVALID, "pt_denoise_rgba8: null");
     int rc = denoise_run(samples, p, params_struct_bytes, kAtrousAuto, nullptr, "pt_denoise_rgba8");
     if (rc) return rc;
-    if (!R().dnRgba) HIPCHECK(hipMalloc(&R().dnRgba, (size_t)R().P * sizeof(uchar4)));
+    if (!R().dnRgba.p) PTCHECK(R().dnRgba.alloc((size_t)R().P));
     // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
-    hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut, R().P, 1, R().dnRgba);
+    hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut.p, R().P, 1, R().dnRgba.p);
     HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba.p, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
     return readback_fault();
 }
@@ -1892,8 +1872,8 @@ int pt_gbuffer(int guide_iter, float *pos_t_host, float *nrm_host, int32_t *geom
     if (rc) return rc;
     const size_t P = (size_t)R().P;
     std::vector<float> tmp(P * 4);
-    HIPCHECK(hipMemcpyAsync(pos_t_host, R().dnPosT, P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
-    HIPCHECK(hipMemcpyAsync(tmp.data(), R().dnNrmId, P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipMemcpyAsync(pos_t_host, R().dnPosT.p, P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipMemcpyAsync(tmp.data(), R().dnNrmId.p, P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
     for (size_t i = 0; i < P; ++i) {
         memcpy(nrm_host + 3 * i, tmp.data() + 4 * i, 3 * sizeof(float));
@@ -1914,7 +1894,7 @@ int pt_counters(PtCounters *out) {
     Ctrl &h = *hp;
     uint32_t faultBits = 0;
     for (int i = 0; i < R().nslots; ++i) {
-        HIPCHECK(hipMemcpy(&h, R().slot[i].ctrl, sizeof h, hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(&h, R().slot[i].ctrl.p, sizeof h, hipMemcpyDeviceToHost));
         for (int d = 0; d < kMaxDepthSlots; ++d) {
             int64_t early = 0;
             for (int sg = 0; sg < kTallyShards; ++sg) early += (int64_t)h.early[d][sg][0];
@@ -1932,8 +1912,7 @@ int pt_counters(PtCounters *out) {
     out->bounce_kernel_ms = R().msBounce;
     out->raygen_kernel_ms = 0.0;   // camera rays are generated inside the first bounce launch
     out->raygen_launches = 0;
-    if (faultBits) return fail(PT_ERR_DEVICE, "device fault 0x%x:%s%s (results of this render are void; re-init)", faultBits,
-                               (faultBits & kFaultPoolExhausted) ? " path pool exhausted" : "", (faultBits & kFaultReserveTimeout) ? " chunk reservation timed out" : "");
+    if (faultBits) return fail(PT_ERR_DEVICE, "%s", fault_message(faultBits).c_str());
     return PT_OK;
 }
 
@@ -1949,11 +1928,11 @@ int pt_counters_reset(void) {
     for (int i = 0; i < R().nslots; ++i) {
         // the sticky fault word survives a counter reset
         uint32_t err = 0;
-        HIPCHECK(hipMemcpy(&err, &R().slot[i].ctrl->error, sizeof err, hipMemcpyDeviceToHost));
-        rc = reset_ctrl(R().slot[i].ctrl, nullptr);
+        HIPCHECK(hipMemcpy(&err, &R().slot[i].ctrl.p->error, sizeof err, hipMemcpyDeviceToHost));
+        rc = reset_ctrl(R().slot[i].ctrl.p, nullptr);
         if (rc) return rc;
         R().slot[i].parity = 0;
-        if (err) HIPCHECK(hipMemcpy(&R().slot[i].ctrl->error, &err, sizeof err, hipMemcpyHostToDevice));
+        if (err) HIPCHECK(hipMemcpy(&R().slot[i].ctrl.p->error, &err, sizeof err, hipMemcpyHostToDevice));
     }
     return PT_OK;
 }

@@ -32,8 +32,8 @@ int pt_debug_trace_paths(int iter, int bounces, float *origin3, float *dir3, flo
     }
     // private run on slot 0: re-arm its cursors, trace, read the queue entering bounce `bounces + 1`, re-arm again
     uint32_t err = 0;
-    HIPCHECK(hipMemcpy(&err, &sl.ctrl->error, sizeof err, hipMemcpyDeviceToHost));
-    rc = reset_ctrl(sl.ctrl, sl.stream);
+    HIPCHECK(hipMemcpy(&err, &sl.ctrl.p->error, sizeof err, hipMemcpyDeviceToHost));
+    rc = reset_ctrl(sl.ctrl.p, sl.stream);
     if (rc) return rc;
     for (int d = 1; d <= bounces; ++d) {
         rc = launch_bounce(sl, iter, 1, d, false, nullptr);  // no radiance, survivors always written
@@ -42,11 +42,11 @@ int pt_debug_trace_paths(int iter, int bounces, float *origin3, float *dir3, flo
     HIPCHECK(hipStreamSynchronize(sl.stream));
     // gather the kSeg segments (chunk lists) of that queue, then sort by pixel index
     static Ctrl h;
-    HIPCHECK(hipMemcpy(&h, sl.ctrl, sizeof h, hipMemcpyDeviceToHost));
-    rc = reset_ctrl(sl.ctrl, sl.stream);
+    HIPCHECK(hipMemcpy(&h, sl.ctrl.p, sizeof h, hipMemcpyDeviceToHost));
+    rc = reset_ctrl(sl.ctrl.p, sl.stream);
     if (rc) return rc;
     err |= h.error;
-    if (err) HIPCHECK(hipMemcpy(&sl.ctrl->error, &err, sizeof err, hipMemcpyHostToDevice));
+    if (err) HIPCHECK(hipMemcpy(&sl.ctrl.p->error, &err, sizeof err, hipMemcpyHostToDevice));
     if (h.error) return fail(PT_ERR_DEVICE, "pt_debug_trace_paths: device fault 0x%x", h.error);
     const PathPool pb = pool(sl, bounces & 1);
     const uint32_t gen = sl.gen[bounces & 1];
@@ -109,10 +109,23 @@ int pt_test_force_fault(int which) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_test_force_fault before pt_init");
     HIPCHECK(hipDeviceSynchronize());
     const uint32_t word = which == 2 ? 1u : 0u;
-    for (int i = 0; i < (which == 2 ? 1 : R().nslots); ++i) HIPCHECK(hipMemcpy(&R().slot[i].ctrl->error, &word, sizeof word, hipMemcpyHostToDevice));
+    for (int i = 0; i < (which == 2 ? 1 : R().nslots); ++i) HIPCHECK(hipMemcpy(&R().slot[i].ctrl.p->error, &word, sizeof word, hipMemcpyHostToDevice));
     if (R().hostFault) *R().hostFault = word;
     return PT_OK;
 }
+
+// (host only) the form of k_bounce the renderer's selector picks for a state: bit 0 first, 1 dof, 2 many, 3 sweptCubes, 4 mesh, 5 grouped, 6 tex,
+// 7 bump, 8 plain -> the nine template flags, bit 0 FIRST .. bit 8 BUMP; an error when that form is not instantiated
+int pt_test_bounce_form(uint32_t state_bits, uint32_t *form_bits) {
+    if (!form_bits || state_bits >= 512u) return fail(PT_ERR_INVALID, "pt_test_bounce_form: bad argument");
+    const auto bit = [state_bits](int i) { return ((state_bits >> i) & 1u) != 0; };
+    const uint32_t f = bounce_form(bit(0), bit(1), bit(2), bit(3), bit(4), bit(5), bit(6), bit(7), bit(8));
+    if (!bounce_kernel(f)) return fail(PT_ERR_INVALID, "pt_test_bounce_form: no k_bounce form 0x%x", f);
+    *form_bits = f;
+    return PT_OK;
+}
+
+int64_t pt_test_live_device_buffers(void) { return (int64_t)g_liveDevBufs.load(); }
 
 #define NEED_GPU() do { if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "no HIP device"); } while (0)
 #define UP(buf, host, count) do { int rc_ = buf.alloc(count); if (rc_) return rc_; \
