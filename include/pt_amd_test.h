@@ -158,6 +158,9 @@ int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's r
  * instantiation the launch takes (bit 0 FIRST, 1 MANY, 2 DOF, 3 MESH, 4 PLAIN, 5 CUBES, 6 GROUPS, 7 TEX, 8 BUMP), by the very function
  * pt_init calls; PT_ERR_INVALID when the library holds no such instantiation (a state no renderer reaches). */
 int pt_test_bounce_form(uint32_t state_bits, uint32_t *form_bits);
+/* The state pt_init left in THIS library's renderer (host only): *state_bits = its dof, many, sweptCubes, mesh, grouped, tex, bump and plain
+ * in the bit order pt_test_bounce_form takes them, bit 0 (`first`, a launch's) clear; PT_ERR_NOT_INIT before pt_init. */
+int pt_test_renderer_state(uint32_t *state_bits);
 /* device allocations THIS library's renderers and temporaries hold right now (every one has one owner type, which counts in this
  * library only): 0 after pt_free */
 int64_t pt_test_live_device_buffers(void);

@@ -71,6 +71,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
+    "pt_test_renderer_state",
 ]
 
 
@@ -205,6 +206,7 @@ def _bind(L, with_tests):
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
+        L.pt_test_renderer_state.argtypes = [C.POINTER(C.c_uint32)]
     return L
 
 

@@ -125,6 +125,17 @@ int pt_test_bounce_form(uint32_t state_bits, uint32_t *form_bits) {
     return PT_OK;
 }
 
+// (host only) the state pt_init left in this library's renderer, in pt_test_bounce_form's bit order with `first` (bit 0) clear
+int pt_test_renderer_state(uint32_t *state_bits) {
+    if (!state_bits) return fail(PT_ERR_INVALID, "pt_test_renderer_state: bad argument");
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_test_renderer_state before pt_init");
+    const bool s[9] = {false, R().dof, R().many, R().sweptCubes, R().mesh, R().grouped, R().tex, R().bump, R().plain};
+    uint32_t bits = 0u;
+    for (int i = 0; i < 9; ++i) bits |= (s[i] ? 1u : 0u) << i;
+    *state_bits = bits;
+    return PT_OK;
+}
+
 int64_t pt_test_live_device_buffers(void) { return (int64_t)g_liveDevBufs.load(); }
 
 #define NEED_GPU() do { if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "no HIP device"); } while (0)
