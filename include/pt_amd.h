@@ -92,6 +92,11 @@ enum {
                                     takes SURVEY S6's energy-conserving reading WITHOUT the 1 / p weight, because that is what the
                                     staff render shows (the weighted form is 1.32 x on Cornell's back wall).  This flag renders the
                                     documented reading: the branch taken carries its weight 2 (the oracle's mirror mode 1). */
+    PT_FLAG_MOMENTS = 32,        /* the renderer also keeps, per pixel, the sum of its samples' squared luminance (one more device buffer of W*H
+                                    floats, always the library's own): every commit adds l * l, l = (0.2126 r + 0.7152 g) + 0.0722 b of the sample
+                                    it adds to the accumulator, in the same iteration order.  What pt_readback_moments, pt_variance and
+                                    pt_denoise_var need.  The accumulator is bit-identical to the one without the flag.  PT_ERR_INVALID with
+                                    shard_count > 1 or PT_FLAG_ACCUM_SHARD_ROWS, and from pt_group_init. */
     PT_FLAG_DIRECT_LIGHTING = 4  /* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
@@ -287,6 +292,30 @@ typedef struct PtDenoiseParams {
 int pt_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, float *rgb_mean_host /* W*H*3 */);
 int pt_denoise_rgba8(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, uint8_t *rgba_host);
 int pt_gbuffer(int guide_iter, float *pos_t_host /* W*H*4 */, float *nrm_host /* W*H*3 */, int32_t *geom_host /* W*H */);
+
+/* ---- per-pixel variance and the variance-guided filter (a renderer initialised with PT_FLAG_MOMENTS; csrc/pt_denoise.h gives every operation,
+ * tests/denoise_var_ref.py restates it).  S = the accumulator's RGB sum, Q = the sum of the samples' squared luminance, n = samples:
+ *   pt_readback_moments   Q, W*H floats
+ *   pt_variance           the variance of every pixel's MEAN luminance: c = S / n, L = lum(c), d = max(Q / n - L * L, 0), v = d / (n - 1)
+ *   pt_denoise_var        the a-trous filter of pt_denoise with SVGF's colour term (Schied et al., HPG 2017) in place of sigma_color: a tap's weight
+ *                         falls with (lum(c_q) - lum(c_p))^2 / (sigma_lum^2 * g + 1e-8), g the 3 x 3 Gaussian-filtered variance around p, so ONE
+ *                         sigma_lum serves every sample count: noisy pixels blur, converged detail stays.  The variance is filtered along with
+ *                         the colour (weights squared) and passed from level to level; var_host (or NULL) receives the last level's.
+ *   pt_denoise_var_rgba8  ... and sendImageToPBO's conversion of the filtered mean, as pt_denoise_rgba8
+ * Guides, stencil, sigma_normal / sigma_position, guide_iter, the stream, the synchronisation and the buffers' lifetime are pt_denoise's; both
+ * accumulators are left untouched.  PT_ERR_NOT_INIT before pt_init; PT_ERR_INVALID without PT_FLAG_MOMENTS, for samples < 2, levels outside
+ * 1..8, a sigma that is 0, negative or NaN (+inf switches its term off), guide_iter < 1 and another struct size than this header's.
+ * (Additive: the ABI version stays.) */
+int pt_readback_moments(float *lum_sq_sum_host /* W*H */);
+int pt_variance(int samples, float *var_mean_host /* W*H */);
+typedef struct PtDenoiseVarParams {
+    int32_t levels;          /* 1..8 */
+    int32_t guide_iter;      /* >= 1 */
+    float sigma_lum, sigma_normal, sigma_position;   /* > 0, +inf allowed; NaN, 0, negatives refused */
+} PtDenoiseVarParams;
+int pt_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, float *rgb_mean_host /* W*H*3 */,
+                   float *var_host /* W*H or NULL */);
+int pt_denoise_var_rgba8(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, uint8_t *rgba_host);
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

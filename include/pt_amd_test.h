@@ -152,6 +152,8 @@ int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, 
  * choice per level, 1: the plain gather, 2 / 3: LDS tiles of 64 x 4 / 64 x 8 pixels of a residue class -- every form gives the same bits.
  * ms (or NULL): 1 + levels kernel times by HIP events, k_gbuffer first (0 when the guide buffers were cached), then each level. */
 int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms);
+/* ... and pt_denoise_var with the form of k_atrous_var named, the same four forms; var_host may be NULL; ms as above. */
+int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms);
 int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
 /* The selector of k_bounce's forms (host only, no GPU needed): state_bits = a renderer's state and a launch's `first` -- bit 0 first, 1 dof
  * (thin lens), 2 many, 3 sweptCubes, 4 mesh, 5 grouped, 6 tex, 7 bump, 8 plain -- -> *form_bits = the nine template flags of the

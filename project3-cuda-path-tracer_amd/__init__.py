@@ -45,6 +45,7 @@ PT_FLAG_ACCUM_SHARD_ROWS = 2
 PT_FLAG_DIRECT_LIGHTING = 4
 PT_FLAG_TRACE_AHEAD = 8
 PT_FLAG_MIXTURE_WEIGHTED = 16
+PT_FLAG_MOMENTS = 32
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -59,6 +60,7 @@ ABI_SYMBOLS = [
     "pt_group_iterate", "pt_group_reduce", "pt_group_sync", "pt_group_readback", "pt_group_counters",
     "pt_set_textures", "pt_group_set_textures", "pt_set_bump_maps", "pt_group_set_bump_maps",
     "pt_denoise", "pt_denoise_rgba8", "pt_gbuffer",
+    "pt_readback_moments", "pt_variance", "pt_denoise_var", "pt_denoise_var_rgba8",
 ]
 PT_AMD_ABI_VERSION = 7
 # every symbol include/pt_amd_test.h declares: libpt_amd_test.so only -- the product library must NOT export them
@@ -70,7 +72,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
-    "pt_test_bump_normal", "pt_test_denoise", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
+    "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state",
 ]
 
@@ -99,6 +101,11 @@ class PtBumpBinding(C.Structure):
 
 class PtDenoiseParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("guide_iter", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_position", C.c_float)]
+
+
+class PtDenoiseVarParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("guide_iter", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_position", C.c_float)]
 
 
@@ -167,6 +174,10 @@ def _bind(L, with_tests):
     L.pt_denoise.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, vp]
     L.pt_denoise_rgba8.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, vp]
     L.pt_gbuffer.argtypes = [i32, vp, vp, vp]
+    L.pt_readback_moments.argtypes = [vp]
+    L.pt_variance.argtypes = [i32, vp]
+    L.pt_denoise_var.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, vp, vp]
+    L.pt_denoise_var_rgba8.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, vp]
     if with_tests:
         L.pt_debug_trace_paths.argtypes = [i32, i32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
         u64p = C.POINTER(C.c_uint64)
@@ -202,6 +213,7 @@ def _bind(L, with_tests):
         L.pt_test_texture_uv.argtypes = [i32, vp, vp, i32, vp]
         L.pt_test_bump_normal.argtypes = [vp, i32, i32, vp, vp, i32, vp]
         L.pt_test_denoise.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, i32, vp, vp]
+        L.pt_test_denoise_var.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, i32, vp, vp, vp]
         L.pt_test_exp_neg_poly.argtypes = [vp, i32, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
@@ -388,8 +400,9 @@ _scene = None
 
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
-                  mixture_weighted=False):
+                  mixture_weighted=False, moments=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    moments: PT_FLAG_MOMENTS -- the renderer also sums every sample's squared luminance (readback_moments, variance, denoise_var).
     lens_radius / focal_distance / direct_lighting: the README extras (depth of field, direct lighting), off by default.
     trace_ahead: PT_FLAG_TRACE_AHEAD -- pathtrace(pbo, frame, iter) called once per iteration draws on batches of max_batch
     iterations traced ahead (same image, bit for bit)."""
@@ -400,6 +413,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_TRACE_AHEAD
     if mixture_weighted:        # the REFL > 0 mixture with its 1 / p weights (src/interactions.h:54-58 to the letter; default: without)
         flags |= PT_FLAG_MIXTURE_WEIGHTED
+    if moments:
+        flags |= PT_FLAG_MOMENTS
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -617,6 +632,56 @@ def test_denoise(samples, form, levels=5, sigma_color=DENOISE_SIGMA_COLOR, sigma
     prm = _denoise_params(levels, sigma_color, sigma_normal, sigma_position, guide_iter)
     _tcheck(test_lib().pt_test_denoise(samples, C.byref(prm), C.sizeof(prm), form, _p(out), _p(ms) if timing else None))
     return (out, ms) if timing else out
+
+
+# the variance-guided filter's colour sigma, in standard errors of the pixel's mean luminance: one value for every sample count
+DENOISE_SIGMA_LUM = 4.0
+
+
+def readback_moments():
+    """Per pixel the sum of its samples' squared luminance (pt_readback_moments; a renderer initialised with moments=True): W*H floats."""
+    out = np.empty(_frame_pixels(), np.float32)
+    _check(lib().pt_readback_moments(_p(out)))
+    return out
+
+
+def variance(samples):
+    """The variance of every pixel's mean luminance over `samples` (pt_variance): W*H floats."""
+    out = np.empty(_frame_pixels(), np.float32)
+    _check(lib().pt_variance(samples, _p(out)))
+    return out
+
+
+def denoise_var(samples, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma_normal=DENOISE_SIGMA_NORMAL, sigma_position=DENOISE_SIGMA_POSITION,
+                guide_iter=1, with_variance=False):
+    """The accumulator's mean over `samples` through the variance-guided a-trous filter (pt_denoise_var): W*H*3 floats; with_variance=True:
+    (that, the filtered variance of the mean luminance, W*H floats).  Both accumulators are left as they are."""
+    n = _frame_pixels()
+    out = np.empty(n * 3, np.float32)
+    var = np.empty(n, np.float32) if with_variance else None
+    prm = PtDenoiseVarParams(levels, guide_iter, sigma_lum, sigma_normal, sigma_position)
+    _check(lib().pt_denoise_var(samples, C.byref(prm), C.sizeof(prm), _p(out), _p(var) if with_variance else None))
+    return (out, var) if with_variance else out
+
+
+def denoise_var_rgba8(samples, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma_normal=DENOISE_SIGMA_NORMAL,
+                      sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1):
+    """... converted like the preview's pixels (pt_denoise_var_rgba8): (W*H, 4) bytes."""
+    out = np.empty((_frame_pixels(), 4), np.uint8)
+    prm = PtDenoiseVarParams(levels, guide_iter, sigma_lum, sigma_normal, sigma_position)
+    _check(lib().pt_denoise_var_rgba8(samples, C.byref(prm), C.sizeof(prm), _p(out)))
+    return out
+
+
+def test_denoise_var(samples, form, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma_normal=DENOISE_SIGMA_NORMAL,
+                     sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1, timing=False):
+    """denoise_var(with_variance=True) with the form of k_atrous_var named, as test_denoise: (rgb, variance[, ms])."""
+    n = _frame_pixels()
+    out, var = np.empty(n * 3, np.float32), np.empty(n, np.float32)
+    ms = np.zeros(1 + levels, np.float32)
+    prm = PtDenoiseVarParams(levels, guide_iter, sigma_lum, sigma_normal, sigma_position)
+    _tcheck(test_lib().pt_test_denoise_var(samples, C.byref(prm), C.sizeof(prm), form, _p(out), _p(var), _p(ms) if timing else None))
+    return (out, var, ms) if timing else (out, var)
 
 
 def test_exp_neg_poly(a):

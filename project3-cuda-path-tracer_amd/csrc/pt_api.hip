@@ -55,6 +55,7 @@ static_assert(sizeof(PtGeom) == 236 && sizeof(PtMaterial) == 44 && sizeof(PtCame
               "layout must equal reference src/sceneStructs.h:18-47");
 static_assert(sizeof(PtBumpBinding) == 24, "PtBumpBinding: 24 bytes (include/pt_amd.h)");
 static_assert(sizeof(PtDenoiseParams) == 20, "PtDenoiseParams: 20 bytes (include/pt_amd.h)");
+static_assert(sizeof(PtDenoiseVarParams) == 20, "PtDenoiseVarParams: 20 bytes (include/pt_amd.h)");
 namespace {
 
 // =====================================================================================================
@@ -186,6 +187,7 @@ struct State {
     int flags = 0;
     float *image = nullptr;         // the accumulator the kernels add to: the caller's (PtOptions::accum_dev, never freed here), or ...
     DevBuf<float> imageOwn;         // ... the renderer's own
+    DevBuf<float> moments;          // PT_FLAG_MOMENTS: per pixel the sum of its samples' squared luminance (k_commit<true>); always the renderer's own
     int nslots = 0;
     int maxBatch = 1;       // iterations that may share one wavefront (pt_iterate_batch)
     Slot slot[kMaxSlots];
@@ -218,6 +220,7 @@ struct State {
     DevBuf<float4> dnPosT, dnNrmId, dnPing[2];
     DevBuf<float> dnOut;
     DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes
+    DevBuf<float> dnVar;            // pt_variance's / pt_denoise_var's variance image
     int dnGuideIter = 0;
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
     DevBuf<int> dWalkIdx, dWalkRowOff;
@@ -658,12 +661,14 @@ int commit_range(Slot &sl, int count, int b0, int b1, bool discard) {
             R().snapWait = nullptr;
         }
         const int compact = (R().flags & PT_FLAG_ACCUM_SHARD_ROWS) ? 1 : 0;
+        const dim3 grid((R().nLocal + kBlock - 1) / kBlock);
+        float *const mom = R().moments.p;      // PT_FLAG_MOMENTS: the <true> instantiations, which also square what they add
         if (b1 == b0 + 1)      // one iteration of the batch (the reference's protocol over a batch traced ahead): the light kernel
-            hipLaunchKernelGGL(k_commit_one, dim3((R().nLocal + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib.p, sl.hitMask.p,
-                               compact, b0, discard ? 1 : 0, snap);
+            hipLaunchKernelGGL(mom ? k_commit_one<true> : k_commit_one<false>, grid, dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib.p,
+                               sl.hitMask.p, compact, b0, discard ? 1 : 0, snap, mom);
         else
-            hipLaunchKernelGGL(k_commit, dim3((R().nLocal + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib.p, sl.hitMask.p,
-                               count, compact, b0, b1, discard ? 1 : 0, snap);
+            hipLaunchKernelGGL(mom ? k_commit<true> : k_commit<false>, grid, dim3(kBlock), 0, R().stream, R().prm, R().image, sl.contrib.p, sl.hitMask.p,
+                               count, compact, b0, b1, discard ? 1 : 0, snap, mom);
         HIPCHECK(hipGetLastError());
     }
     return PT_OK;
@@ -851,6 +856,87 @@ int denoise_to_host(int samples, const PtDenoiseParams *p, size_t bytes, int for
     int rc = denoise_run(samples, p, bytes, form, ms, who);
     if (rc) return rc;
     HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut.p, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+// ---- the second moments and the variance-guided filter (pt_denoise.h, k_atrous_var_*) ---------------------------------------------------
+int moments_refusals(const char *who) {
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
+    if (!R().moments.p) return fail(PT_ERR_INVALID, "%s: the renderer was initialised without PT_FLAG_MOMENTS", who);
+    return PT_OK;
+}
+
+template <bool F, bool L>
+const void *atrous_var_kernel(int form) {
+    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_var_gather<F, L>);
+    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 1>);
+    return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 2>);
+}
+
+// The variance-guided filter's levels on the caller's stream, as denoise_run: packed RGB in R().dnOut, the filtered variance in R().dnVar when
+// `wantVar`; ms (or NULL): 1 + levels kernel times, k_gbuffer first.
+int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, bool wantVar, float *ms, const char *who) {
+    PTCHECK(moments_refusals(who));
+    if (!p || bytes != sizeof(PtDenoiseVarParams))
+        return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseVarParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseVarParams));
+    if (samples < 2) return fail(PT_ERR_INVALID, "%s: samples must be >= 2 (a variance needs two)", who);
+    if (p->levels < 1 || p->levels > 8) return fail(PT_ERR_INVALID, "%s: levels must be 1..8", who);
+    for (float sg : {p->sigma_lum, p->sigma_normal, p->sigma_position})
+        if (!(sg > 0.0f)) return fail(PT_ERR_INVALID, "%s: a sigma must be > 0 (+inf switches its term off)", who);
+    if (form < kAtrousAuto || form > kAtrousTiled8) return fail(PT_ERR_INVALID, "%s: unknown kernel form %d", who, form);
+    PTCHECK(ensure_guides(p->guide_iter, ms));
+    const size_t P = (size_t)R().P;
+    if (!R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
+    if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc(P));
+    for (int k = 0; k < 2 && k < p->levels - 1; ++k)
+        if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
+    AtrousVarArgs A;
+    A.accum = R().image; A.moments = R().moments.p;
+    A.posT = R().dnPosT.p; A.nrmId = R().dnNrmId.p;
+    A.W = R().prm.W; A.H = R().prm.H;
+    A.samples = (float)samples; A.samplesM1 = (float)(samples - 1);
+    A.sl2 = p->sigma_lum * p->sigma_lum;
+    A.invN = 1.0f / (p->sigma_normal * p->sigma_normal);
+    A.invP = 1.0f / (p->sigma_position * p->sigma_position);
+    EventSet es;
+    hipEvent_t *const ev = es.ev;
+    if (ms)
+        for (int i = 0; i <= p->levels; ++i) HIPCHECK(hipEventCreate(&ev[i]));
+    for (int i = 0; i < p->levels; ++i) {
+        const bool first = i == 0, last = i == p->levels - 1;
+        A.step = 1 << i;
+        A.cin = first ? nullptr : R().dnPing[(i - 1) & 1].p;
+        A.cout = last ? nullptr : R().dnPing[i & 1].p;
+        A.out3 = last ? R().dnOut.p : nullptr;
+        A.outVar = last && wantVar ? R().dnVar.p : nullptr;
+        // the form per level: 64 x 8 tiles up to the largest step they were measured to win clearly at (profiles/denoise_var_cost.txt), the gather above
+        int f = form != kAtrousAuto ? form : (A.step <= kAtrousVarTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
+        unsigned long long grid = f == kAtrousGather ? atrousGridGather(A.W, A.H) : atrousGridTiled(A.W, A.H, A.step, f == kAtrousTiled4 ? 1 : 2);
+        if (grid > 0x7fffffffull) {
+            f = kAtrousGather;
+            grid = atrousGridGather(A.W, A.H);
+        }
+        const void *kern = first ? (last ? atrous_var_kernel<true, true>(f) : atrous_var_kernel<true, false>(f))
+                                 : (last ? atrous_var_kernel<false, true>(f) : atrous_var_kernel<false, false>(f));
+        void *kargs[] = {&A};
+        if (ms) HIPCHECK(hipEventRecord(ev[i], R().stream));
+        HIPCHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
+    }
+    if (ms) {
+        HIPCHECK(hipEventRecord(ev[p->levels], R().stream));
+        HIPCHECK(hipEventSynchronize(ev[p->levels]));
+        for (int i = 0; i < p->levels; ++i) HIPCHECK(hipEventElapsedTime(&ms[1 + i], ev[i], ev[i + 1]));
+    }
+    HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
+int denoise_var_to_host(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, float *ms, float *rgb_mean_host, float *var_host, const char *who) {
+    if (!rgb_mean_host) return fail(PT_ERR_INVALID, "%s: null", who);
+    PTCHECK(denoise_var_run(samples, p, bytes, form, var_host != nullptr, ms, who));
+    HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut.p, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    if (var_host) HIPCHECK(hipMemcpyAsync(var_host, R().dnVar.p, (size_t)R().P * sizeof(float), hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
     return readback_fault();
 }
@@ -1045,6 +1131,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     o.device = -1;
     if (opts) o = *opts;
     if (o.shard_count < 1 || o.shard_rank < 0 || o.shard_rank >= o.shard_count) return fail(PT_ERR_INVALID, "pt_init: bad shard %d/%d", o.shard_rank, o.shard_count);
+    if ((o.flags & PT_FLAG_MOMENTS) && (o.shard_count > 1 || (o.flags & PT_FLAG_ACCUM_SHARD_ROWS)))
+        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOMENTS needs the whole frame: no row shard, no PT_FLAG_ACCUM_SHARD_ROWS");
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     if (o.device >= 0) HIPCHECK(hipSetDevice(o.device));
@@ -1127,6 +1215,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         R().image = R().imageOwn.p;
         HIPCHECK(hipMemsetAsync(R().image, 0, n * 3 * sizeof(float), R().stream));
     }
+    if (R().flags & PT_FLAG_MOMENTS) PTCHECK(R().moments.alloc_zeroed((size_t)R().P));
     // Path pools: a bounce's queue is kSeg = kCls x kSub segments, each a list of chunks handed out on demand, one ahead of
     // their use (ptk::reserveRun).  At most nLocal * maxBatch paths are alive; every segment may end in a partly filled
     // chunk and holds one chunk installed ahead: ceil(paths / chunk) + 2 kSeg chunks always suffice, whatever the
@@ -1857,6 +1946,43 @@ int pt_denoise_rgba8(int samples, const PtDenoiseParams *p, size_t params_struct
     if (rc) return rc;
     if (!R().dnRgba.p) PTCHECK(R().dnRgba.alloc((size_t)R().P));
     // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
+    hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut.p, R().P, 1, R().dnRgba.p);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba.p, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+// ---- the second moments (PT_FLAG_MOMENTS), the variance of the mean, and the filter it guides (pt_denoise.h) -------------------------
+int pt_readback_moments(float *lum_sq_sum_host) {
+    PTCHECK(moments_refusals("pt_readback_moments"));
+    if (!lum_sq_sum_host) return fail(PT_ERR_INVALID, "pt_readback_moments: null");
+    HIPCHECK(hipMemcpyAsync(lum_sq_sum_host, R().moments.p, (size_t)R().P * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+int pt_variance(int samples, float *var_mean_host) {
+    PTCHECK(moments_refusals("pt_variance"));
+    if (!var_mean_host) return fail(PT_ERR_INVALID, "pt_variance: null");
+    if (samples < 2) return fail(PT_ERR_INVALID, "pt_variance: samples must be >= 2 (a variance needs two)");
+    if (!R().dnVar.p) PTCHECK(R().dnVar.alloc((size_t)R().P));
+    hipLaunchKernelGGL(k_variance, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().image, R().moments.p, R().P, (float)samples,
+                       (float)(samples - 1), R().dnVar.p);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(var_mean_host, R().dnVar.p, (size_t)R().P * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+int pt_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, float *rgb_mean_host, float *var_host) {
+    return denoise_var_to_host(samples, p, params_struct_bytes, kAtrousAuto, nullptr, rgb_mean_host, var_host, "pt_denoise_var");
+}
+
+int pt_denoise_var_rgba8(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, uint8_t *rgba_host) {
+    if (!rgba_host) return fail(PT_ERR_INVALID, "pt_denoise_var_rgba8: null");
+    PTCHECK(denoise_var_run(samples, p, params_struct_bytes, kAtrousAuto, false, nullptr, "pt_denoise_var_rgba8"));
+    if (!R().dnRgba.p) PTCHECK(R().dnRgba.alloc((size_t)R().P));
     hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut.p, R().P, 1, R().dnRgba.p);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba.p, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));

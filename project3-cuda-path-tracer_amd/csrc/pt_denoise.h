@@ -1,8 +1,10 @@
 // pt_denoise.h -- the edge-avoiding a-trous wavelet filter over the renderer's image, guided by first-hit position and normal
 // (Dammertz, Sewtz, Hanika, Lensch: "Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination Filtering", HPG 2010).
-// Two kernels, both outside the render path (k_bounce, k_mesh_walk, k_commit and their arguments do not know of them):
-//   k_gbuffer   the guide buffers: the nearest hit of the camera rays of ONE iteration, brute force over the scene's primitives
-//   k_atrous    one level of the filter (the hot path): a 5 x 5 stencil with holes, LDS-tiled per residue class or a plain gather
+// Its kernels, all outside the render path (k_bounce, k_mesh_walk, k_commit and their arguments do not know of them):
+//   k_gbuffer     the guide buffers: the nearest hit of the camera rays of ONE iteration, brute force over the scene's primitives
+//   k_atrous      one level of the filter (the hot path): a 5 x 5 stencil with holes, LDS-tiled per residue class or a plain gather
+//   k_variance    the variance of every pixel's mean luminance, from the accumulator and the second moments (PT_FLAG_MOMENTS)
+//   k_atrous_var  one level of the variance-guided filter: k_atrous with SVGF's colour term, the variance carried in the colour's .w (below)
 // Included by pt_api.hip only.
 //
 // ---- the filter, operation by operation (tests/denoise_ref.py restates it in numpy, bit for bit: every fp32 operation below is one IEEE
@@ -93,6 +95,8 @@ constexpr int kAtrousOutside = (int)0x80000000;      // LDS halo: the id of an e
 constexpr int kAtrousTileW = 64;                     // a wave filters 64 consecutive pixels of one row of its residue class
 constexpr int kAtrousPitch = kAtrousTileW + 4;       // ... whose LDS rows carry the two-pixel halo on either side
 constexpr int kAtrousTiledMaxStep = 4;               // levels of a larger step take the plain gather (pt_api.hip: denoise_run); a choice by reasoning, unmeasured
+constexpr int kAtrousVarTiledMaxStep = 8;            // ... of the variance-guided filter (denoise_var_run): measured -- at step 8 the 64 x 8 tiles beat the gather by a sixth at
+                                                     // 1280 x 720, at step 16 by less than two spreads, beyond nothing is measured (profiles/denoise_var_cost.txt)
 
 __device__ __forceinline__ float atrousH(int i) { return i == 2 ? 0.375f : ((i == 1 || i == 3) ? 0.25f : 0.0625f); }
 
@@ -223,6 +227,230 @@ __global__ __launch_bounds__(kBlock) void k_atrous_tiled(AtrousArgs A) {
             }
         }
         atrousStore<LAST>(A, (size_t)x + (size_t)y * (size_t)A.W, sumC, sumW);
+    }
+}
+
+// ---- the variance-guided filter (SVGF's spatial filter: Schied et al., "Spatiotemporal Variance-Guided Filtering", HPG 2017) ---------
+// k_atrous with the colour term weighted by each pixel's own measured standard error instead of one global sigma_color; the variance of the
+// pixel's mean luminance rides in the colour float4's .w, so a level stages and moves what k_atrous's does.  Guides, taps, hw, the tap order,
+// the hit / miss rule, expNegPoly and the two forms are k_atrous's (above).  tests/denoise_var_ref.py restates every operation, bit for bit:
+//   lum         lum(c) = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z
+//   level 0     reads the accumulator S and the second moments Q (PT_FLAG_MOMENTS: k_commit<true>, k_commit_one<true>), n = (float)samples:
+//               c.k = S.k / n;  L = lum(c);  d = Q / n - L * L;  d = d > 0 ? d : 0 (a NaN gives 0);  v = d / (float)(samples - 1)
+//   prefilter   g = gv / gw over the 3 x 3 taps q = p + s (dx, dy), dy = -1 .. 1 (outer loop), dx = -1 .. 1 (inner loop), centre included,
+//               k = k3[dy + 1] * k3[dx + 1], k3 = [1/4, 1/2, 1/4]:  gw += k;  gv += v_q * k  from 0; a tap outside the frame or across the
+//               hit / miss border is skipped
+//   scale       invL = 1.0f / (sl2 * g + 1e-8f), sl2 = sigma_lum * sigma_lum (host, fp32); sl2 = +inf: invL = 0, the term is off whatever g is
+//               (inf * 0 would be a NaN).  NOT halved per level: the variance shrinks by itself.
+//   taps        dl = lum(c_q) - lum(c_p);  a = (dl * dl) * invL;  a = a + dot(dn, dn) * invN;  a = a + dot(dp, dp) * invP;  w = hw * expNegPoly(a);
+//               the centre tap has w = hw
+//   sums        sumW += w;  sumC.k += c_q.k * w;  sumV += v_q * (w * w);   c' = sumC / sumW;  v' = sumV / (sumW * sumW)
+// The last level writes packed RGB and, where asked for, the filtered variance.
+struct AtrousVarArgs {
+    const float *accum, *moments;   // FIRST: the accumulator's packed RGB sums and the sums of squared luminance
+    const float4 *cin;              // later levels: the level before, (r, g, b, variance)
+    float4 *cout;                   // every level but the last
+    float *out3, *outVar;           // LAST: packed RGB, and the variance (or NULL)
+    const float4 *posT, *nrmId;
+    int W, H, step;
+    float samples, samplesM1;       // FIRST: (float)samples, (float)(samples - 1)
+    float sl2, invN, invP;
+};
+
+__device__ __forceinline__ float atrousLum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
+// the mean colour and the variance of its luminance from the two accumulators (k_variance, and level 0 of the filter)
+__device__ __forceinline__ float4 meanAndVariance(const float *accum, const float *moments, size_t pix, float n, float nM1) {
+    const float *s = accum + 3 * pix;
+    const float r = s[0] / n, g = s[1] / n, b = s[2] / n;
+    const float L = atrousLum(r, g, b);
+    float d = moments[pix] / n - L * L;
+    d = d > 0.0f ? d : 0.0f;
+    return make_float4(r, g, b, d / nM1);
+}
+
+// pt_variance: the variance of every pixel's mean luminance
+__global__ __launch_bounds__(kBlock) void k_variance(const float *accum, const float *moments, int npix, float n, float nM1, float *var) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= npix) return;
+    var[i] = meanAndVariance(accum, moments, (size_t)i, n, nM1).w;
+}
+
+template <bool FIRST>
+__device__ __forceinline__ float4 atrousVarColour(const AtrousVarArgs &A, size_t pix) {
+    if (!FIRST) return A.cin[pix];
+    return meanAndVariance(A.accum, A.moments, pix, A.samples, A.samplesM1);
+}
+
+__device__ __forceinline__ float atrousK3(int i) { return i == 1 ? 0.5f : 0.25f; }
+
+// one tap of the 3 x 3 variance prefilter that lies inside the frame: (variance, bits of the id) of the tap, the id's bits of the centre
+__device__ __forceinline__ void atrousVarPre(float k, float vq, float idq, float idp, float &gw, float &gv) {
+    if ((__float_as_int(idq) < 0) != (__float_as_int(idp) < 0)) return;
+    gw += k;
+    gv += vq * k;
+}
+
+__device__ __forceinline__ float atrousInvL(const AtrousVarArgs &A, float gw, float gv) {
+    const float g = gv / gw;
+    return A.sl2 <= 3.402823466e38f ? 1.0f / (A.sl2 * g + 1e-8f) : 0.0f;      // (uniform: +inf switches the term off)
+}
+
+// one tap of the 5 x 5 stencil that lies inside the frame; lp = lum(cp)
+template <bool CENTRE>
+__device__ __forceinline__ void atrousVarTap(const AtrousVarArgs &A, float hw, float invL, float4 cq, float4 nq, float4 pq, float lp, float4 np, float4 pp,
+                                             float &sumW, F3 &sumC, float &sumV) {
+    float w = hw;
+    if (!CENTRE) {
+        if ((__float_as_int(nq.w) < 0) != (__float_as_int(np.w) < 0)) return;     // exactly one of the two is a miss
+        const float dl = atrousLum(cq.x, cq.y, cq.z) - lp;
+        const F3 dn = f3(nq.x, nq.y, nq.z) - f3(np.x, np.y, np.z);
+        const F3 dp = f3(pq.x, pq.y, pq.z) - f3(pp.x, pp.y, pp.z);
+        float a = (dl * dl) * invL;
+        a = a + dot(dn, dn) * A.invN;
+        a = a + dot(dp, dp) * A.invP;
+        w = hw * expNegPoly(a);
+    }
+    sumW += w;
+    sumC.x += cq.x * w;
+    sumC.y += cq.y * w;
+    sumC.z += cq.z * w;
+    sumV += cq.w * (w * w);
+}
+
+template <bool LAST>
+__device__ __forceinline__ void atrousVarStore(const AtrousVarArgs &A, size_t pix, F3 sumC, float sumV, float sumW) {
+    const float r = sumC.x / sumW, g = sumC.y / sumW, b = sumC.z / sumW, v = sumV / (sumW * sumW);
+    if (LAST) {
+        float *o = A.out3 + 3 * pix;
+        o[0] = r; o[1] = g; o[2] = b;
+        if (A.outVar) A.outVar[pix] = v;
+    } else {
+        A.cout[pix] = make_float4(r, g, b, v);
+    }
+}
+
+// The plain gather, as k_atrous_gather.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(kBlock) void k_atrous_var_gather(AtrousVarArgs A) {
+    const int tilesX = (A.W + kAtrousTileW - 1) / kAtrousTileW;
+    const int tY = (int)(blockIdx.x / (unsigned)tilesX), tX = (int)(blockIdx.x - (unsigned)tY * (unsigned)tilesX);
+    const int x = tX * kAtrousTileW + (int)(threadIdx.x & 63u), y = tY * 4 + (int)(threadIdx.x >> 6);
+    if (x >= A.W || y >= A.H) return;
+    const size_t pix = (size_t)x + (size_t)y * (size_t)A.W;
+    const float4 cp = atrousVarColour<FIRST>(A, pix), np = A.nrmId[pix], pp = A.posT[pix];
+    float gw = 0.0f, gv = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int qy = y + dy * A.step;
+        if (qy < 0 || qy >= A.H) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx * A.step;
+            const float k = atrousK3(dy + 1) * atrousK3(dx + 1);
+            if (dx == 0 && dy == 0) {
+                atrousVarPre(k, cp.w, np.w, np.w, gw, gv);
+            } else if (qx >= 0 && qx < A.W) {
+                const size_t q = (size_t)qx + (size_t)qy * (size_t)A.W;
+                atrousVarPre(k, atrousVarColour<FIRST>(A, q).w, A.nrmId[q].w, np.w, gw, gv);
+            }
+        }
+    }
+    const float invL = atrousInvL(A, gw, gv), lp = atrousLum(cp.x, cp.y, cp.z);
+    float sumW = 0.0f, sumV = 0.0f;
+    F3 sumC = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = y + dy * A.step;
+        if (qy < 0 || qy >= A.H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = x + dx * A.step;
+            const float hw = atrousH(dy + 2) * atrousH(dx + 2);
+            if (dx == 0 && dy == 0) {
+                atrousVarTap<true>(A, hw, invL, cp, np, pp, lp, np, pp, sumW, sumC, sumV);
+            } else if (qx >= 0 && qx < A.W) {
+                const size_t q = (size_t)qx + (size_t)qy * (size_t)A.W;
+                const float4 nq = A.nrmId[q];
+                atrousVarTap<false>(A, hw, invL, atrousVarColour<FIRST>(A, q), nq, A.posT[q], lp, np, pp, sumW, sumC, sumV);
+            }
+        }
+    }
+    atrousVarStore<LAST>(A, pix, sumC, sumV, sumW);
+}
+
+// The LDS-tiled form, as k_atrous_tiled: the same three float4 images of the same shape, the colour image's .w now the variance.  The 3 x 3
+// prefilter reads the .w of the eight inner taps' colour and normal + id entries once more: 16 ds_read_b32 per row next to the taps' 16-byte
+// reads, each striding 16 bytes across the wave (four lanes per bank).  The levels are bound by vector issue, not by LDS
+// (profiles/denoise_var_cost.txt: a tiled level costs 1.00 - 1.12 x the plain filter's), so the entries are not kept in registers for them.
+template <bool FIRST, bool LAST, int RPT>
+__global__ __launch_bounds__(kBlock) void k_atrous_var_tiled(AtrousVarArgs A) {
+    constexpr int TH = 4 * RPT, ROWS = TH + 4, ENTRIES = kAtrousPitch * ROWS;
+    __shared__ float4 s_c[ENTRIES], s_n[ENTRIES], s_p[ENTRIES];
+    const int s = A.step;
+    const int cw = (A.W + s - 1) / s, ch = (A.H + s - 1) / s;          // extent of the largest class
+    const int tilesX = (cw + kAtrousTileW - 1) / kAtrousTileW, tilesY = (ch + TH - 1) / TH;
+    const unsigned perClass = (unsigned)tilesX * (unsigned)tilesY;
+    const int cls = (int)(blockIdx.x / perClass), tile = (int)(blockIdx.x - (unsigned)cls * perClass);
+    const int ry = cls / s, rx = cls - ry * s;
+    const int tY = tile / tilesX, tX = tile - tY * tilesX;
+    const int cx0 = tX * kAtrousTileW, cy0 = tY * TH;                   // the tile's first pixel, in class coordinates
+    if (rx + s * cx0 >= A.W || ry + s * cy0 >= A.H) return;             // (workgroup-uniform)
+    for (int e = (int)threadIdx.x; e < ENTRIES; e += kBlock) {
+        const int ly = e / kAtrousPitch, lx = e - ly * kAtrousPitch;
+        const int x = rx + s * (cx0 + lx - 2), y = ry + s * (cy0 + ly - 2);
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(kAtrousOutside)), p = c;
+        if (x >= 0 && x < A.W && y >= 0 && y < A.H) {
+            const size_t q = (size_t)x + (size_t)y * (size_t)A.W;
+            c = atrousVarColour<FIRST>(A, q);
+            n = A.nrmId[q];
+            p = A.posT[q];
+        }
+        s_c[e] = c; s_n[e] = n; s_p[e] = p;
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x & 63u), wy = (int)(threadIdx.x >> 6);
+    const int x = rx + s * (cx0 + tx);
+#pragma unroll
+    for (int r = 0; r < RPT; ++r) {
+        const int ly = wy + 4 * r;
+        const int y = ry + s * (cy0 + ly);
+        if (x >= A.W || y >= A.H) continue;
+        const int e0 = (ly + 2) * kAtrousPitch + tx + 2;
+        const float4 cp = s_c[e0], np = s_n[e0], pp = s_p[e0];
+        float gw = 0.0f, gv = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) {
+                const float k = atrousK3(dy + 1) * atrousK3(dx + 1);
+                if (dx == 0 && dy == 0) {
+                    atrousVarPre(k, cp.w, np.w, np.w, gw, gv);
+                } else {
+                    const int e = e0 + dy * kAtrousPitch + dx;
+                    const float idq = s_n[e].w;
+                    if (__float_as_int(idq) != kAtrousOutside) atrousVarPre(k, s_c[e].w, idq, np.w, gw, gv);
+                }
+            }
+        }
+        const float invL = atrousInvL(A, gw, gv), lp = atrousLum(cp.x, cp.y, cp.z);
+        float sumW = 0.0f, sumV = 0.0f;
+        F3 sumC = f3(0.0f, 0.0f, 0.0f);
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) {
+#pragma unroll
+            for (int dx = -2; dx <= 2; ++dx) {
+                const float hw = atrousH(dy + 2) * atrousH(dx + 2);
+                if (dx == 0 && dy == 0) {
+                    atrousVarTap<true>(A, hw, invL, cp, np, pp, lp, np, pp, sumW, sumC, sumV);
+                } else {
+                    const int e = e0 + dy * kAtrousPitch + dx;
+                    const float4 nq = s_n[e];
+                    if (__float_as_int(nq.w) != kAtrousOutside) atrousVarTap<false>(A, hw, invL, s_c[e], nq, s_p[e], lp, np, pp, sumW, sumC, sumV);
+                }
+            }
+        }
+        atrousVarStore<LAST>(A, (size_t)x + (size_t)y * (size_t)A.W, sumC, sumV, sumW);
     }
 }
 

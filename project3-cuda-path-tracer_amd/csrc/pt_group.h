@@ -495,6 +495,7 @@ int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeo
                   const PtOptions *opts) {
     if (!g || !cam) return fail(PT_ERR_INVALID, "pt_group_init: null argument");
     if (cam->resolution[0] <= 0 || cam->resolution[1] <= 0) return fail(PT_ERR_INVALID, "pt_group_init: bad resolution");
+    if (opts && (opts->flags & PT_FLAG_MOMENTS)) return fail(PT_ERR_INVALID, "pt_group_init: PT_FLAG_MOMENTS is not for groups (their members hold row shards)");
     CurrentGuard guard;
     const int n = (int)g->ctx.size();
     {   // a re-init (the reference's Free -> Init restart): the old renderers go first, then the buffers they accumulate into

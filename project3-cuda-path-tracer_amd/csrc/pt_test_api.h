@@ -917,6 +917,10 @@ int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_
     return denoise_to_host(samples, p, params_struct_bytes, form, ms, rgb_mean_host, "pt_test_denoise");
 }
 
+int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms) {
+    return denoise_var_to_host(samples, p, params_struct_bytes, form, ms, rgb_mean_host, var_host, "pt_test_denoise_var");
+}
+
 int pt_test_sincos(const float *x, int n, float *s, float *c) {
     NEED_GPU();
     if (n <= 0) return PT_OK;

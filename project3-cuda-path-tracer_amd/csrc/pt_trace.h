@@ -1944,8 +1944,13 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
 // `snap` (round 6; device groups, pt_group.h): a full frame that receives the value of EVERY pixel of this shard after the commit --
 // the snapshot a frame reduce reads while the next iteration is committed -- in the same pass: the accumulator is read once, for the
 // addition and for the copy (a separate 11 MB device-to-device copy per iteration cost config C3 as written ~7 us each).
+// k_commit<true> (PT_FLAG_MOMENTS; never with row shards or a snapshot): `moments`, one float per pixel of the frame, receives the square
+// of every added sample's luminance in the same iteration order: l = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  Q = Q + l * l -- each one
+// fp32 operation -- from the entries this launch reads anyway.  A discarded entry adds nothing.  k_commit<false> is the kernel as it was
+// before the template, instruction for instruction (profiles/denoise_var_resource_usage.txt); it never reads `moments`.
+template <bool MOMENTS>
 __global__ __launch_bounds__(kBlock) void k_commit(KParams prm, float *image, float *contrib, uint32_t *hitMask, int batch, int compactRows,
-                                                   int b0, int b1, int discard, float *snap) {
+                                                   int b0, int b1, int discard, float *snap, float *moments) {
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= prm.nLocal) return;
     const int lr = j / prm.W;
@@ -1980,6 +1985,8 @@ __global__ __launch_bounds__(kBlock) void k_commit(KParams prm, float *image, fl
         return;
     }
     if (!snap) { ax = px[0]; ay = px[1]; az = px[2]; }
+    float aq = 0.0f;
+    if (MOMENTS) aq = moments[gpix];
 #pragma unroll
     for (int w = 0; w < kWordsMax; ++w) {
         uint32_t m = mw[w];
@@ -2004,10 +2011,17 @@ __global__ __launch_bounds__(kBlock) void k_commit(KParams prm, float *image, fl
             // zeros per consumed entry, 141 MB per batch of 64 on C2)
 #pragma unroll
             for (int q = 0; q < 16; ++q)
-                if (b[q] >= 0 && !discard) { ax += v[q][0]; ay += v[q][1]; az += v[q][2]; }
+                if (b[q] >= 0 && !discard) {
+                    ax += v[q][0]; ay += v[q][1]; az += v[q][2];
+                    if (MOMENTS) {
+                        const float l = (0.2126f * v[q][0] + 0.7152f * v[q][1]) + 0.0722f * v[q][2];
+                        aq = aq + l * l;
+                    }
+                }
         }
     }
     if (!discard) { px[0] = ax; px[1] = ay; px[2] = az; }
+    if (MOMENTS && !discard) moments[gpix] = aq;
     if (sp) { sp[0] = ax; sp[1] = ay; sp[2] = az; }
 }
 
@@ -2016,8 +2030,9 @@ __global__ __launch_bounds__(kBlock) void k_commit(KParams prm, float *image, fl
 // eight mask words per lane -- 100 VGPRs, four waves per SIMD -- through this case too, and a per-iteration commit costs the tracing
 // kernels next to it its whole duration (they are bound by vector issue: profiles/r06_group_experiments.txt).  Same loads, same single
 // addition per channel, same stores: the accumulator is bit-identical.
+template <bool MOMENTS>
 __global__ __launch_bounds__(kBlock) void k_commit_one(KParams prm, float *image, float *contrib, uint32_t *hitMask, int compactRows, int b, int discard,
-                                                       float *snap) {
+                                                       float *snap, float *moments) {
     const int j = blockIdx.x * kBlock + threadIdx.x;
     if (j >= prm.nLocal) return;
     const int lr = j / prm.W;
@@ -2039,10 +2054,16 @@ __global__ __launch_bounds__(kBlock) void k_commit_one(KParams prm, float *image
     float *const c = contrib + 3 * ((size_t)b * frame + pix);
     const float cx = c[0], cy = c[1], cz = c[2];
     if (!snap) { ax = px[0]; ay = px[1]; az = px[2]; }
+    float aq = 0.0f;
+    if (MOMENTS) aq = moments[gpix];
     *mp = word & ~bit;                                           // (the entry itself is dead until its bit is set again: no re-zeroing)
     if (!discard) {
         ax += cx; ay += cy; az += cz;
         px[0] = ax; px[1] = ay; px[2] = az;
+        if (MOMENTS) {
+            const float l = (0.2126f * cx + 0.7152f * cy) + 0.0722f * cz;
+            moments[gpix] = aq + l * l;
+        }
     }
     if (sp) { sp[0] = ax; sp[1] = ay; sp[2] = az; }
 }

@@ -5,10 +5,13 @@
 //
 //   pt_render SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B]
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
+//                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
 // iteration's first hits (include/pt_amd.h); the usual image is written as without the option.
+// --denoise-var writes the same file through pt_denoise_var, the variance-guided filter: the renderer then runs with PT_FLAG_MOMENTS.
+// One of the two at most.
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -37,7 +40,10 @@ static float lensRadius = 0.0f, focalDistance = 0.0f;
 static bool directLighting = false;
 static PtDenoiseParams denoiseParams;
 static bool denoise = false;
+static PtDenoiseVarParams denoiseVarParams;
+static bool denoiseVar = false;
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
+void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 
 static std::string currentTimeString() {
     time_t now;
@@ -67,9 +73,10 @@ static void saveImage() {
 static void check(int status, const char *what);
 // --denoise: the filtered mean, before the renderer is freed
 static void saveDenoised() {
-    if (!denoise) return;
+    if (!denoise && !denoiseVar) return;
     std::vector<lin::vec3> mean((size_t)width * height);
-    check(pt_denoise(iteration, &denoiseParams, sizeof denoiseParams, (float *)mean.data()), "pt_denoise");
+    if (denoise) check(pt_denoise(iteration, &denoiseParams, sizeof denoiseParams, (float *)mean.data()), "pt_denoise");
+    else check(pt_denoise_var(iteration, &denoiseVarParams, sizeof denoiseVarParams, (float *)mean.data(), NULL), "pt_denoise_var");
     image img(width, height);
     for (int x = 0; x < width; x++)
         for (int y = 0; y < height; y++) img.setPixel(width - 1 - x, y, mean[x + (y * width)]);
@@ -113,6 +120,7 @@ static void renderBatched() {
     opt.lens_radius = lensRadius;
     opt.focal_distance = focalDistance;
     if (directLighting) opt.flags |= PT_FLAG_DIRECT_LIGHTING;
+    if (denoiseVar) opt.flags |= PT_FLAG_MOMENTS;
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -142,7 +150,7 @@ static void renderBatched() {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP]\n", argv[0]);
         return 1;
     }
     try {
@@ -170,9 +178,20 @@ int main(int argc, char **argv) {
             denoiseParams.sigma_position = (float)atof(argv[i + 4]);
             i += 4;
         }
+        else if (!strcmp(argv[i], "--denoise-var") && i + 4 < argc) {
+            denoiseVar = true;
+            denoiseVarParams.levels = atoi(argv[i + 1]);
+            denoiseVarParams.guide_iter = 1;
+            denoiseVarParams.sigma_lum = (float)atof(argv[i + 2]);
+            denoiseVarParams.sigma_normal = (float)atof(argv[i + 3]);
+            denoiseVarParams.sigma_position = (float)atof(argv[i + 4]);
+            i += 4;
+        }
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
+    if (denoise && denoiseVar) { fprintf(stderr, "--denoise and --denoise-var exclude each other\n"); return 1; }
     pathtraceExtras(lensRadius, focalDistance, directLighting);
+    pathtraceMoments(denoiseVar);
     iteration = 0;
     width = renderState->camera.resolution.x;
     height = renderState->camera.resolution.y;

@@ -16,6 +16,7 @@ static Scene *hst_scene = NULL;
 static PtGroup *group = NULL;
 static float extraLens = 0.0f, extraFocal = 0.0f;   // README extras (pathtraceExtras), off = the reference's renderer
 static bool extraDirect = false;
+static bool extraMoments = false;                   // pathtraceMoments: PT_FLAG_MOMENTS for the next pathtraceInit
 
 static void checkPtError(int status, const char *msg) {
     if (status == PT_OK) return;
@@ -33,6 +34,7 @@ void pathtraceInit(Scene *scene) {
     opt.lens_radius = extraLens;        // ... unless pathtraceExtras() switched a README extra on
     opt.focal_distance = extraFocal;
     if (extraDirect) opt.flags |= PT_FLAG_DIRECT_LIGHTING;
+    if (extraMoments) opt.flags |= PT_FLAG_MOMENTS;
     // The reference's host calls pathtrace(pbo, frame, iter) once per iteration with iter = 1, 2, 3, ... (src/main.cpp:97-103):
     // the library traces such a sequence in wavefront batches AHEAD of the calls (PT_FLAG_TRACE_AHEAD; same image after every
     // call, bit for bit), so a call costs a commit instead of eight small dependent launches.  A camera move goes through
@@ -163,6 +165,10 @@ void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting)
     extraFocal = focalDistance;
     extraDirect = directLighting;
 }
+
+// Not a reference symbol either: the next pathtraceInit also keeps the samples' second moments (PT_FLAG_MOMENTS: pt_variance,
+// pt_denoise_var).  Not with PT_AMD_DEVICES: a group refuses the flag.
+void pathtraceMoments(bool on) { extraMoments = on; }
 
 void pathtraceFree() {
     if (group) {
