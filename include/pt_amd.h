@@ -317,6 +317,42 @@ int pt_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struc
                    float *var_host /* W*H or NULL */);
 int pt_denoise_var_rgba8(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, uint8_t *rgba_host);
 
+/* ---- render to a noise threshold (a renderer initialised with PT_FLAG_MOMENTS; csrc/pt_noise.h gives every operation, tests/noise_ref.py
+ * restates it).  The frame is judged per tile of PT_NOISE_TILE x PT_NOISE_TILE pixels, not per pixel: a pixel whose samples all missed the
+ * light has variance 0 and looks converged, while a tile's summed variance is an unbiased estimate.  With v, L of pt_variance per pixel:
+ *   r(tile) = (sum v / N) / max(sum L / N, lum_floor)^2,  N = the tile's pixels inside the frame;  sqrt(r) = the tile's relative standard error
+ *   a tile is unconverged iff r > threshold * threshold (fp32; a NaN r is not);  max_rel_var = the largest r of the frame, NaN ignored
+ *   pt_noise_stats     the statistics of the accumulator as `samples` iterations left it; tile_rel_var_host (or NULL) receives r[ty][tx].  Runs
+ *                      on the context's stream behind every commit and synchronises, like pt_variance; both accumulators are left untouched.
+ *                      out->converged is judged with a fraction of 0: no tile above the threshold.
+ *   pt_iterate_until   renders iterations first_iter, first_iter + 1, ... (the accumulator holds 1 .. first_iter - 1) in rounds of check_every
+ *                      -- the last one cut at max_samples; each round pt_iterate_batch calls of at most max_batch -- and after every round that
+ *                      ends with at least min_samples checks the frame on the device: it is converged when
+ *                      unconverged <= floor((double)max_unconverged_fraction * tiles).  lookahead 0: the host waits for each check before it
+ *                      enqueues more; *samples_done = s*, the first checked count that is converged.  lookahead 1: the next round is enqueued
+ *                      BEFORE the host waits for the check (for the check's event alone), so the GPU never idles for the decision and that
+ *                      round counts: *samples_done = min(s* + check_every, max_samples).  Never converged: max_samples.  Deterministic either
+ *                      way, and both accumulators equal pt_iterate_batch over iterations 1 .. *samples_done bit for bit.  `out`: the
+ *                      statistics of the final accumulator, with out->converged = how the loop ended.  Returns PT_OK either way; synchronises
+ *                      and reports a device fault as pt_sync does.  samples_done may be NULL.
+ * PT_ERR_NOT_INIT before pt_init; PT_ERR_INVALID without PT_FLAG_MOMENTS (row shards and device groups refuse that flag), with
+ * PT_FLAG_TRACE_AHEAD in effect (pt_iterate_until), for samples < 2, min_samples < 2, max_samples < 2, a threshold or lum_floor that is not
+ * finite and > 0, a fraction outside 0..1 or NaN, check_every < 1, first_iter < 1, max_samples < first_iter or beyond the last iteration,
+ * lookahead other than 0 or 1, a null `out` or target and another struct size than this header's.  (Additive: the ABI version stays.) */
+#define PT_NOISE_TILE 16
+typedef struct PtNoiseStats {
+    int32_t samples, tiles_x, tiles_y, converged;
+    int64_t tiles, unconverged;
+    float max_rel_var, thr2;     /* thr2 = threshold * threshold, what the tiles' r was compared with */
+} PtNoiseStats;
+int pt_noise_stats(int samples, float threshold, float lum_floor, PtNoiseStats *out, size_t stats_struct_bytes,
+                   float *tile_rel_var_host /* tiles_y * tiles_x, or NULL */);
+typedef struct PtNoiseTarget {
+    float threshold, lum_floor, max_unconverged_fraction;
+    int32_t min_samples, max_samples, check_every, lookahead;
+} PtNoiseTarget;
+int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t target_struct_bytes, PtNoiseStats *out, int32_t *samples_done);
+
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);
 

@@ -155,6 +155,12 @@ int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_
 /* ... and pt_denoise_var with the form of k_atrous_var named, the same four forms; var_host may be NULL; ms as above. */
 int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms);
 int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
+/* the noise statistics (pt_amd.h, csrc/pt_noise.h): k_noise_stats -- the kernel pt_noise_stats launches -- over host arrays of any w x h, no
+ * renderer needed: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h); out, tile_rel_var_host (or NULL) as pt_noise_stats.  tiles_per_wave: how many
+ * tiles a wave of the grid takes, 1..64, 0 = the library's choice -- every value gives the same bits.  ms (or NULL) with
+ * reps >= 1: 2 * reps kernel times by HIP events, {k_noise_stats, k_variance over the same arrays} alternating, after one untimed launch of each. */
+int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, int h, int samples, float threshold, float lum_floor, PtNoiseStats *out,
+                        size_t stats_struct_bytes, float *tile_rel_var_host, int tiles_per_wave, int reps, float *ms);
 /* The selector of k_bounce's forms (host only, no GPU needed): state_bits = a renderer's state and a launch's `first` -- bit 0 first, 1 dof
  * (thin lens), 2 many, 3 sweptCubes, 4 mesh, 5 grouped, 6 tex, 7 bump, 8 plain -- -> *form_bits = the nine template flags of the
  * instantiation the launch takes (bit 0 FIRST, 1 MANY, 2 DOF, 3 MESH, 4 PLAIN, 5 CUBES, 6 GROUPS, 7 TEX, 8 BUMP), by the very function

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "pt_set_textures", "pt_group_set_textures", "pt_set_bump_maps", "pt_group_set_bump_maps",
     "pt_denoise", "pt_denoise_rgba8", "pt_gbuffer",
     "pt_readback_moments", "pt_variance", "pt_denoise_var", "pt_denoise_var_rgba8",
+    "pt_noise_stats", "pt_iterate_until",
 ]
 PT_AMD_ABI_VERSION = 7
 # every symbol include/pt_amd_test.h declares: libpt_amd_test.so only -- the product library must NOT export them
@@ -72,7 +73,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
-    "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
+    "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state",
 ]
 
@@ -107,6 +108,19 @@ class PtDenoiseParams(C.Structure):
 class PtDenoiseVarParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("guide_iter", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float),
                 ("sigma_position", C.c_float)]
+
+
+PT_NOISE_TILE = 16
+
+
+class PtNoiseStats(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("converged", C.c_int32), ("tiles", C.c_int64),
+                ("unconverged", C.c_int64), ("max_rel_var", C.c_float), ("thr2", C.c_float)]
+
+
+class PtNoiseTarget(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("lum_floor", C.c_float), ("max_unconverged_fraction", C.c_float), ("min_samples", C.c_int32),
+                ("max_samples", C.c_int32), ("check_every", C.c_int32), ("lookahead", C.c_int32)]
 
 
 class PtCounters(C.Structure):
@@ -178,6 +192,8 @@ def _bind(L, with_tests):
     L.pt_variance.argtypes = [i32, vp]
     L.pt_denoise_var.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, vp, vp]
     L.pt_denoise_var_rgba8.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, vp]
+    L.pt_noise_stats.argtypes = [i32, C.c_float, C.c_float, C.POINTER(PtNoiseStats), C.c_size_t, vp]
+    L.pt_iterate_until.argtypes = [i32, i32, C.POINTER(PtNoiseTarget), C.c_size_t, C.POINTER(PtNoiseStats), C.POINTER(C.c_int32)]
     if with_tests:
         L.pt_debug_trace_paths.argtypes = [i32, i32, vp, vp, vp, vp, C.POINTER(C.c_int32)]
         u64p = C.POINTER(C.c_uint64)
@@ -214,6 +230,7 @@ def _bind(L, with_tests):
         L.pt_test_bump_normal.argtypes = [vp, i32, i32, vp, vp, i32, vp]
         L.pt_test_denoise.argtypes = [i32, C.POINTER(PtDenoiseParams), C.c_size_t, i32, vp, vp]
         L.pt_test_denoise_var.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, i32, vp, vp, vp]
+        L.pt_test_noise_stats.argtypes = [vp, vp, i32, i32, i32, C.c_float, C.c_float, C.POINTER(PtNoiseStats), C.c_size_t, vp, i32, i32, vp]
         L.pt_test_exp_neg_poly.argtypes = [vp, i32, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
@@ -536,11 +553,21 @@ def pathtrace(pbo, frame, iteration, readback=True):
         _check(lib().pt_readback(_p(_scene.image)))
 
 
-def pathtrace_batch(pbo, frame, first_iteration, count, readback=False):
-    """`count` iterations in one wavefront (pt_iterate_batch); same result as `count` pathtrace() calls."""
-    _check(lib().pt_iterate_batch(frame, first_iteration, count, pbo or None))
+def pathtrace_batch(pbo, frame, first_iteration, count, readback=False, until=None):
+    """`count` iterations in one wavefront (pt_iterate_batch); same result as `count` pathtrace() calls.
+    until: a noise threshold, or a dict of iterate_until()'s keywords with one -- then AT MOST `count` iterations (any number, in batches of
+    max_batch) are rendered, until the frame's tiles pass (pt_iterate_until; no `pbo`), and (statistics, samples_done) is returned."""
+    if until is not None:
+        if pbo:
+            raise PtError("pathtrace_batch: until= takes no pbo")
+        kw = dict(until) if isinstance(until, dict) else {"threshold": until}
+        res = iterate_until(first_iteration, max_samples=first_iteration + count - 1, frame=frame, **kw)
+    else:
+        _check(lib().pt_iterate_batch(frame, first_iteration, count, pbo or None))
+        res = None
     if readback and _scene is not None:
         _check(lib().pt_readback(_p(_scene.image)))
+    return res
 
 
 def pathtraceFree():
@@ -682,6 +709,62 @@ def test_denoise_var(samples, form, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma
     prm = PtDenoiseVarParams(levels, guide_iter, sigma_lum, sigma_normal, sigma_position)
     _tcheck(test_lib().pt_test_denoise_var(samples, C.byref(prm), C.sizeof(prm), form, _p(out), _p(var), _p(ms) if timing else None))
     return (out, var, ms) if timing else (out, var)
+
+
+# the luminance a tile's mean is floored with before the noise statistics divide by it: 5 % of a white diffuse surface's
+NOISE_LUM_FLOOR = 0.05
+
+
+def _noise_result(st, tile_map):
+    out = {f: getattr(st, f) for f, _ in PtNoiseStats._fields_}
+    out["converged"] = bool(out["converged"])
+    if tile_map is not None:
+        out["tile_rel_var"] = tile_map.reshape(st.tiles_y, st.tiles_x)
+    return out
+
+
+def _frame_tiles():
+    res = _scene.camera["resolution"][0] if _scene is not None else (0, 0)
+    return ((int(res[0]) + PT_NOISE_TILE - 1) // PT_NOISE_TILE) * ((int(res[1]) + PT_NOISE_TILE - 1) // PT_NOISE_TILE)
+
+
+def noise_stats(samples, threshold, lum_floor=NOISE_LUM_FLOOR, tile_map=False):
+    """How converged the accumulator is after `samples` iterations (pt_noise_stats; a renderer initialised with moments=True): a dict of
+    PtNoiseStats' fields -- tiles of 16 x 16 pixels, `unconverged` of them with a relative standard error above `threshold`, max_rel_var the
+    largest squared one -- and with tile_map=True "tile_rel_var", (tiles_y, tiles_x) floats."""
+    _frame_pixels()
+    st = PtNoiseStats()
+    tm = np.empty(_frame_tiles(), np.float32) if tile_map else None
+    _check(lib().pt_noise_stats(samples, threshold, lum_floor, C.byref(st), C.sizeof(st), _p(tm) if tile_map else None))
+    return _noise_result(st, tm)
+
+
+def iterate_until(first_iteration, threshold, max_samples, lum_floor=NOISE_LUM_FLOOR, max_unconverged_fraction=0.0, min_samples=2, check_every=8,
+                  lookahead=1, frame=0):
+    """Render iterations first_iteration, ... until the frame's tiles pass `threshold` or `max_samples` are in the accumulator
+    (pt_iterate_until): (the final accumulator's statistics as noise_stats gives them, samples_done)."""
+    tgt = PtNoiseTarget(threshold, lum_floor, max_unconverged_fraction, min_samples, max_samples, check_every, lookahead)
+    st = PtNoiseStats()
+    done = C.c_int32(0)
+    _check(lib().pt_iterate_until(frame, first_iteration, C.byref(tgt), C.sizeof(tgt), C.byref(st), C.byref(done)))
+    return _noise_result(st, None), int(done.value)
+
+
+def test_noise_stats(rgb_sum, lum_sq_sum, w, h, samples, threshold, lum_floor=NOISE_LUM_FLOOR, tiles_per_wave=0, timing_reps=0):
+    """noise_stats(tile_map=True) of host arrays S (h, w, 3) and Q (h, w) through k_noise_stats, no renderer; tiles_per_wave: the tiles a wave
+    of the grid takes (0: the library's choice; the same bits whatever it is); timing_reps > 0: (that, ms) with ms (reps, 2): k_noise_stats'
+    and k_variance's kernel times over the same arrays."""
+    S = np.ascontiguousarray(rgb_sum, np.float32).reshape(-1)
+    Q = np.ascontiguousarray(lum_sq_sum, np.float32).reshape(-1)
+    if S.size != w * h * 3 or Q.size != w * h:
+        raise PtError("test_noise_stats: S must hold w * h * 3 floats, Q w * h")
+    st = PtNoiseStats()
+    tm = np.empty(((w + PT_NOISE_TILE - 1) // PT_NOISE_TILE) * ((h + PT_NOISE_TILE - 1) // PT_NOISE_TILE), np.float32)
+    ms = np.zeros((max(timing_reps, 1), 2), np.float32)
+    _tcheck(test_lib().pt_test_noise_stats(_p(S), _p(Q), w, h, samples, threshold, lum_floor, C.byref(st), C.sizeof(st), _p(tm), tiles_per_wave, timing_reps,
+                                           _p(ms) if timing_reps > 0 else None))
+    res = _noise_result(st, tm)
+    return (res, ms) if timing_reps > 0 else res
 
 
 def test_exp_neg_poly(a):

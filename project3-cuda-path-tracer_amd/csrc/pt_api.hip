@@ -41,6 +41,7 @@
 #include "pt_mesh_walk.h"
 #include "pt_mesh.h"
 #include "pt_denoise.h"
+#include "pt_noise.h"
 // The entry points of include/pt_amd_test.h (device primitives one by one, soundness sweeps, the fault-word hook) exist only in
 // the second link target of this source, libpt_amd_test.so (-DPT_TEST_API): the product library exports none of them.
 #ifdef PT_TEST_API
@@ -56,6 +57,8 @@ static_assert(sizeof(PtGeom) == 236 && sizeof(PtMaterial) == 44 && sizeof(PtCame
 static_assert(sizeof(PtBumpBinding) == 24, "PtBumpBinding: 24 bytes (include/pt_amd.h)");
 static_assert(sizeof(PtDenoiseParams) == 20, "PtDenoiseParams: 20 bytes (include/pt_amd.h)");
 static_assert(sizeof(PtDenoiseVarParams) == 20, "PtDenoiseVarParams: 20 bytes (include/pt_amd.h)");
+static_assert(sizeof(PtNoiseStats) == 40 && sizeof(PtNoiseTarget) == 28, "PtNoiseStats: 40 bytes, PtNoiseTarget: 28 (include/pt_amd.h)");
+static_assert(PT_NOISE_TILE == ptk::kNoiseTile, "include/pt_amd.h and csrc/pt_noise.h name one tile size");
 namespace {
 
 // =====================================================================================================
@@ -222,6 +225,13 @@ struct State {
     DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes
     DevBuf<float> dnVar;            // pt_variance's / pt_denoise_var's variance image
     int dnGuideIter = 0;
+    // the noise statistics (pt_noise.h), all allocated on first use: the frame's two result words on the device, the tile map, and -- for
+    // pt_iterate_until, whose checks the host reads while the stream runs on -- two copies of the words in page-locked memory, each with the
+    // event that says its copy has landed
+    DevBuf<uint32_t> noiseFrame;
+    DevBuf<float> noiseMap;
+    uint32_t *noiseHost = nullptr;      // 2 x 2 words
+    hipEvent_t noiseEv[2] = {nullptr, nullptr};
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
     DevBuf<int> dWalkIdx, dWalkRowOff;
     DevBuf<WalkMesh> dWalkMeshRows;    // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows); walkMeshLds: how many of them a workgroup stages in LDS (all, or none)
@@ -941,6 +951,55 @@ int denoise_var_to_host(int samples, const PtDenoiseVarParams *p, size_t bytes, 
     return readback_fault();
 }
 
+
+// ---- the noise statistics and the loop that renders until they pass (pt_noise.h) ------------------------------------------------------------
+// a threshold or a luminance floor: finite and > 0
+bool noise_positive(float v) { return v > 0.0f && v <= std::numeric_limits<float>::max(); }
+
+// k_noise_stats over `accum` / `moments` on stream `st`: zero the two words, the kernel, and -- `host` given -- their copy to the host
+int noise_launch(const float *accum, const float *moments, int W, int H, int samples, float lumFloor, float thr2, uint32_t *frame, float *tileMap,
+                 uint32_t *host, hipStream_t st, int tilesPerWave = kNoiseTilesPerWave) {
+    const long long tx = (W + kNoiseTile - 1) / kNoiseTile, ty = (H + kNoiseTile - 1) / kNoiseTile;
+    if (tx * ty > 0x3fffffffll) return fail(PT_ERR_INVALID, "noise statistics: more than 2^30 tiles");
+    const int tiles = (int)(tx * ty), perBlock = 4 * tilesPerWave;
+    HIPCHECK(hipMemsetAsync(frame, 0, 2 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_noise_stats, dim3((tiles + perBlock - 1) / perBlock), dim3(kBlock), 0, st, accum, moments, W, H, (int)tx, tiles, tilesPerWave,
+                       (float)samples, (float)(samples - 1), lumFloor, thr2, frame, tileMap);
+    HIPCHECK(hipGetLastError());
+    if (host) HIPCHECK(hipMemcpyAsync(host, frame, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    return PT_OK;
+}
+
+// what the two words say, judged with the fraction `frac` of tiles that may stay unconverged
+void noise_fill(PtNoiseStats *out, int W, int H, int samples, float thr2, const uint32_t *words, float frac) {
+    out->samples = samples;
+    out->tiles_x = (W + kNoiseTile - 1) / kNoiseTile;
+    out->tiles_y = (H + kNoiseTile - 1) / kNoiseTile;
+    out->tiles = (int64_t)out->tiles_x * out->tiles_y;
+    out->unconverged = (int64_t)words[0];
+    memcpy(&out->max_rel_var, &words[1], sizeof(float));
+    out->thr2 = thr2;
+    out->converged = out->unconverged <= (int64_t)std::floor((double)frac * (double)out->tiles) ? 1 : 0;
+}
+
+int noise_buffers() {
+    if (!R().noiseFrame.p) PTCHECK(R().noiseFrame.alloc(2));
+    if (!R().noiseHost) {
+        HIPCHECK(hipHostMalloc((void **)&R().noiseHost, 4 * sizeof(uint32_t), hipHostMallocDefault));
+        for (hipEvent_t &e : R().noiseEv) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    return PT_OK;
+}
+
+// one check of the accumulator as the caller's stream will have it behind everything enqueued so far: the kernel, the copy of its words into
+// page-locked copy `k`, the event
+int noise_enqueue_check(int k, int samples, float lumFloor, float thr2) {
+    PTCHECK(noise_launch(R().image, R().moments.p, R().prm.W, R().prm.H, samples, lumFloor, thr2, R().noiseFrame.p, nullptr, R().noiseHost + 2 * k,
+                         R().stream));
+    HIPCHECK(hipEventRecord(R().noiseEv[k], R().stream));
+    return PT_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -983,6 +1042,9 @@ void free_renderer() {
     }
     if (R().pinnedHost) (void)hipHostUnregister(R().pinnedHost);
     if (R().hostFault) (void)hipHostFree(R().hostFault);
+    if (R().noiseHost) (void)hipHostFree(R().noiseHost);
+    for (hipEvent_t e : R().noiseEv)
+        if (e) (void)hipEventDestroy(e);
     // ... and every device table: the move-assignment below releases what the DevBufs of State and its Slots hold
     {   // (the registered meshes, textures and height maps outlive the renderer: see State::meshes)
         std::vector<ptm::HostMesh> keep = std::move(R().meshes);
@@ -1988,6 +2050,93 @@ int pt_denoise_var_rgba8(int samples, const PtDenoiseVarParams *p, size_t params
     HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba.p, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
     return readback_fault();
+}
+
+// ---- the noise statistics of 16 x 16 tiles, and rendering until they pass (pt_noise.h) -----------------------------------------------------
+int pt_noise_stats(int samples, float threshold, float lum_floor, PtNoiseStats *out, size_t stats_struct_bytes, float *tile_rel_var_host) {
+    PTCHECK(moments_refusals("pt_noise_stats"));
+    if (!out || stats_struct_bytes != sizeof(PtNoiseStats))
+        return fail(PT_ERR_INVALID, "pt_noise_stats: the caller's PtNoiseStats is %zu bytes, this library's %zu", out ? stats_struct_bytes : (size_t)0,
+                    sizeof(PtNoiseStats));
+    if (samples < 2) return fail(PT_ERR_INVALID, "pt_noise_stats: samples must be >= 2 (a variance needs two)");
+    if (!noise_positive(threshold) || !noise_positive(lum_floor)) return fail(PT_ERR_INVALID, "pt_noise_stats: threshold and lum_floor must be finite and > 0");
+    PTCHECK(noise_buffers());
+    const int W = R().prm.W, H = R().prm.H;
+    const size_t tiles = (size_t)((W + kNoiseTile - 1) / kNoiseTile) * (size_t)((H + kNoiseTile - 1) / kNoiseTile);
+    if (tile_rel_var_host && !R().noiseMap.p) PTCHECK(R().noiseMap.alloc(tiles));
+    const float thr2 = threshold * threshold;
+    PTCHECK(noise_launch(R().image, R().moments.p, W, H, samples, lum_floor, thr2, R().noiseFrame.p, tile_rel_var_host ? R().noiseMap.p : nullptr,
+                         R().noiseHost, R().stream));
+    if (tile_rel_var_host) HIPCHECK(hipMemcpyAsync(tile_rel_var_host, R().noiseMap.p, tiles * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    noise_fill(out, W, H, samples, thr2, R().noiseHost, 0.0f);
+    return readback_fault();
+}
+
+int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t target_struct_bytes, PtNoiseStats *out, int32_t *samples_done) {
+    PTCHECK(moments_refusals("pt_iterate_until"));
+    if (!t || target_struct_bytes != sizeof(PtNoiseTarget))
+        return fail(PT_ERR_INVALID, "pt_iterate_until: the caller's PtNoiseTarget is %zu bytes, this library's %zu", t ? target_struct_bytes : (size_t)0,
+                    sizeof(PtNoiseTarget));
+    if (!out) return fail(PT_ERR_INVALID, "pt_iterate_until: null");
+    if (R().flags & PT_FLAG_TRACE_AHEAD) return fail(PT_ERR_INVALID, "pt_iterate_until: not with PT_FLAG_TRACE_AHEAD (the loop enqueues its own batches)");
+    if (!noise_positive(t->threshold) || !noise_positive(t->lum_floor))
+        return fail(PT_ERR_INVALID, "pt_iterate_until: threshold and lum_floor must be finite and > 0");
+    if (!(t->max_unconverged_fraction >= 0.0f && t->max_unconverged_fraction <= 1.0f))
+        return fail(PT_ERR_INVALID, "pt_iterate_until: max_unconverged_fraction must be 0..1");
+    if (t->min_samples < 2) return fail(PT_ERR_INVALID, "pt_iterate_until: min_samples must be >= 2 (a variance needs two)");
+    if (t->check_every < 1) return fail(PT_ERR_INVALID, "pt_iterate_until: check_every must be >= 1");
+    if (first_iter < 1) return fail(PT_ERR_INVALID, "pt_iterate_until: first_iter must be >= 1");
+    if (t->max_samples < first_iter) return fail(PT_ERR_INVALID, "pt_iterate_until: max_samples lies before first_iter");
+    if (t->max_samples < 2 || t->max_samples >= kIterEnd)
+        return fail(PT_ERR_INVALID, "pt_iterate_until: max_samples must be 2..4194303 (a variance needs two; seed bits, pathtrace.cu:43)");
+    if (t->lookahead != 0 && t->lookahead != 1) return fail(PT_ERR_INVALID, "pt_iterate_until: lookahead must be 0 or 1");
+    PTCHECK(noise_buffers());
+    const int W = R().prm.W, H = R().prm.H;
+    const float thr2 = t->threshold * t->threshold, frac = t->max_unconverged_fraction;
+    int s = first_iter - 1;          // the samples the accumulator holds behind everything enqueued
+    int pending = -1, pendingAt = 0; // the page-locked copy of a check that is in flight, and the sample count it judges
+    int statsAt = 0;                 // `out` holds the statistics of that many samples (0: of nothing yet)
+    int checks = 0;
+    bool converged = false;
+    // wait for the check in flight -- its event alone: the stream may already hold the next round -- and judge it
+    auto resolve = [&]() -> int {
+        HIPCHECK(hipEventSynchronize(R().noiseEv[pending]));
+        noise_fill(out, W, H, pendingAt, thr2, R().noiseHost + 2 * pending, frac);
+        statsAt = pendingAt;
+        pending = -1;
+        converged = out->converged != 0;
+        return PT_OK;
+    };
+    while (s < t->max_samples && !converged) {
+        const int round = std::min(t->check_every, t->max_samples - s);
+        for (int done = 0; done < round;) {
+            const int b = std::min(R().maxBatch, round - done);
+            PTCHECK(pt_iterate_batch(frame, s + 1 + done, b, nullptr));
+            done += b;
+        }
+        s += round;
+        if (pending >= 0) {          // lookahead: the round just enqueued counts whichever way the check before it went
+            PTCHECK(resolve());
+            if (converged) break;
+        }
+        if (s < t->min_samples) continue;
+        pending = checks++ & 1;
+        pendingAt = s;
+        PTCHECK(noise_enqueue_check(pending, s, t->lum_floor, thr2));
+        if (t->lookahead == 0 || s == t->max_samples) PTCHECK(resolve());
+    }
+    if (statsAt != s) {              // the final accumulator's statistics: a lookahead round came after the last check, or none was due
+        const bool how = converged;
+        pending = checks++ & 1;
+        pendingAt = s;
+        PTCHECK(noise_enqueue_check(pending, s, t->lum_floor, thr2));
+        PTCHECK(resolve());
+        converged = how;
+    }
+    out->converged = converged ? 1 : 0;
+    if (samples_done) *samples_done = s;
+    return check_device_fault();
 }
 
 int pt_gbuffer(int guide_iter, float *pos_t_host, float *nrm_host, int32_t *geom_host) {

@@ -921,6 +921,51 @@ int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_
     return denoise_var_to_host(samples, p, params_struct_bytes, form, ms, rgb_mean_host, var_host, "pt_test_denoise_var");
 }
 
+int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, int h, int samples, float threshold, float lum_floor, PtNoiseStats *out,
+                        size_t stats_struct_bytes, float *tile_rel_var_host, int tiles_per_wave, int reps, float *ms) {
+    NEED_GPU();
+    if (!rgb_sum || !lum_sq_sum || !out || stats_struct_bytes != sizeof(PtNoiseStats) || w < 1 || h < 1 || samples < 2 || !noise_positive(threshold) ||
+        !noise_positive(lum_floor) || (ms && reps < 1) || tiles_per_wave < 0 || tiles_per_wave > 64)
+        return fail(PT_ERR_INVALID, "pt_test_noise_stats: bad argument");
+    const size_t P = (size_t)w * h, tiles = (size_t)((w + kNoiseTile - 1) / kNoiseTile) * (size_t)((h + kNoiseTile - 1) / kNoiseTile);
+    DevBuf<float> S, Q, map, var;
+    DevBuf<uint32_t> frame;
+    UP(S, rgb_sum, P * 3);
+    UP(Q, lum_sq_sum, P);
+    int rc = frame.alloc(2); if (rc) return rc;
+    if (tile_rel_var_host) { rc = map.alloc(tiles); if (rc) return rc; }
+    const float thr2 = threshold * threshold;
+    const int tpw = tiles_per_wave ? tiles_per_wave : kNoiseTilesPerWave;
+    uint32_t words[2] = {0u, 0u};
+    rc = noise_launch(S.p, Q.p, w, h, samples, lum_floor, thr2, frame.p, map.p, nullptr, nullptr, tpw); if (rc) return rc;
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(words, frame.p, sizeof words, hipMemcpyDeviceToHost));
+    if (tile_rel_var_host) DOWN(tile_rel_var_host, map, tiles);
+    noise_fill(out, w, h, samples, thr2, words, 0.0f);
+    if (!ms) return PT_OK;
+    if (P > 0x7fffffffull - kBlock) return fail(PT_ERR_INVALID, "pt_test_noise_stats: k_variance indexes with an int");
+    rc = var.alloc(P); if (rc) return rc;
+    const int tilesX = (w + kNoiseTile - 1) / kNoiseTile;
+    const dim3 gridN((unsigned)((tiles + 4 * tpw - 1) / (4 * tpw))), gridV((unsigned)((P + kBlock - 1) / kBlock));
+    const float n = (float)samples, nM1 = (float)(samples - 1);
+    EventSet es;
+    for (int i = 0; i < 3; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    hipLaunchKernelGGL(k_variance, gridV, dim3(kBlock), 0, nullptr, S.p, Q.p, (int)P, n, nM1, var.p);      // (k_noise_stats has run above)
+    for (int r = 0; r < reps; ++r) {
+        HIPCHECK(hipMemsetAsync(frame.p, 0, 2 * sizeof(uint32_t), nullptr));
+        HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        hipLaunchKernelGGL(k_noise_stats, gridN, dim3(kBlock), 0, nullptr, S.p, Q.p, w, h, tilesX, (int)tiles, tpw, n, nM1, lum_floor, thr2, frame.p, map.p);
+        HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+        hipLaunchKernelGGL(k_variance, gridV, dim3(kBlock), 0, nullptr, S.p, Q.p, (int)P, n, nM1, var.p);
+        HIPCHECK(hipEventRecord(es.ev[2], nullptr));
+        HIPCHECK(hipEventSynchronize(es.ev[2]));
+        HIPCHECK(hipEventElapsedTime(&ms[2 * r], es.ev[0], es.ev[1]));
+        HIPCHECK(hipEventElapsedTime(&ms[2 * r + 1], es.ev[1], es.ev[2]));
+    }
+    HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
 int pt_test_sincos(const float *x, int n, float *s, float *c) {
     NEED_GPU();
     if (n <= 0) return PT_OK;

@@ -6,12 +6,17 @@
 //   pt_render SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B]
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
+//                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
 // iteration's first hits (include/pt_amd.h); the usual image is written as without the option.
 // --denoise-var writes the same file through pt_denoise_var, the variance-guided filter: the renderer then runs with PT_FLAG_MOMENTS.
 // One of the two at most.
+// --noise-threshold T renders until no 16 x 16 tile's relative standard error lies above T (pt_iterate_until, include/pt_amd.h) -- with
+// --noise-fraction F until at most that fraction of the tiles does -- checking every K iterations (--check-every, default 8) while the next
+// K are already being traced; --iterations becomes the cap.  The renderer then runs with PT_FLAG_MOMENTS through the C ABI like --batch
+// (B may be 1), the PNG is normalised by the samples actually taken, and one line reports them.
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -19,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <ctime>
 #include <sstream>
@@ -42,6 +48,9 @@ static PtDenoiseParams denoiseParams;
 static bool denoise = false;
 static PtDenoiseVarParams denoiseVarParams;
 static bool denoiseVar = false;
+static bool noiseTarget = false;
+static float noiseThreshold = 0.0f, noiseFraction = 0.0f;
+static int checkEvery = 8;
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 
@@ -120,7 +129,7 @@ static void renderBatched() {
     opt.lens_radius = lensRadius;
     opt.focal_distance = focalDistance;
     if (directLighting) opt.flags |= PT_FLAG_DIRECT_LIGHTING;
-    if (denoiseVar) opt.flags |= PT_FLAG_MOMENTS;
+    if (denoiseVar || noiseTarget) opt.flags |= PT_FLAG_MOMENTS;
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -136,7 +145,23 @@ static void renderBatched() {
                   (const PtMaterial *)scene->materials.data(), (int)scene->materials.size(), renderState->traceDepth, &opt),
           "pt_init");
     const int total = (int)renderState->iterations;
-    while (iteration < total) {
+    if (noiseTarget) {
+        PtNoiseTarget t;
+        t.threshold = noiseThreshold;
+        t.lum_floor = 0.05f;
+        t.max_unconverged_fraction = noiseFraction;
+        t.min_samples = 2;
+        t.max_samples = total;
+        t.check_every = checkEvery;
+        t.lookahead = 1;
+        PtNoiseStats st;
+        int32_t done = 0;
+        check(pt_iterate_until(0, 1, &t, sizeof t, &st, &done), "pt_iterate_until");
+        iteration = done;
+        printf("noise threshold %g: %d samples, converged %s, %lld of %lld tiles above it, largest relative standard error %.4f\n", noiseThreshold,
+               iteration, st.converged ? "yes" : "no", (long long)st.unconverged, (long long)st.tiles, sqrt((double)st.max_rel_var));
+    }
+    while (!noiseTarget && iteration < total) {
         const int n = total - iteration < batch ? total - iteration : batch;
         check(pt_iterate_batch(0, iteration + 1, n, NULL), "pt_iterate_batch");
         iteration += n;
@@ -150,7 +175,7 @@ static void renderBatched() {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]]\n", argv[0]);
         return 1;
     }
     try {
@@ -187,6 +212,9 @@ int main(int argc, char **argv) {
             denoiseVarParams.sigma_position = (float)atof(argv[i + 4]);
             i += 4;
         }
+        else if (!strcmp(argv[i], "--noise-threshold") && i + 1 < argc) { noiseTarget = true; noiseThreshold = (float)atof(argv[++i]); }
+        else if (!strcmp(argv[i], "--noise-fraction") && i + 1 < argc) noiseFraction = (float)atof(argv[++i]);
+        else if (!strcmp(argv[i], "--check-every") && i + 1 < argc) checkEvery = atoi(argv[++i]);
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
     if (denoise && denoiseVar) { fprintf(stderr, "--denoise and --denoise-var exclude each other\n"); return 1; }
@@ -196,11 +224,11 @@ int main(int argc, char **argv) {
     width = renderState->camera.resolution.x;
     height = renderState->camera.resolution.y;
     const auto t0 = std::chrono::steady_clock::now();
-    if (batch > 1) renderBatched();
+    if (batch > 1 || noiseTarget) renderBatched();
     else while (runHip()) {}
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("%d iterations of %dx%d, depth %d: %.3f s wall (init, %s and PNG included)\n", iteration, width, height,
-           renderState->traceDepth, s, batch > 1 ? "one D2H copy" : "per-iteration D2H copy");
+           renderState->traceDepth, s, batch > 1 || noiseTarget ? "one D2H copy" : "per-iteration D2H copy");
     delete scene;
     return 0;
 }
