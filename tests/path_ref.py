@@ -35,8 +35,9 @@ def _sphere(ro, rd, tmin):
     hit = disc > 0
     t = np.where(hit & (t0 > 0), t0, np.where(hit & (t1 > 0), t1, np.inf))
     inside = hit & (t0 <= 0) & (t1 > 0)
-    # the origin's own surface, or a ray that grazes the sphere (the closest approach within 1e-6 of the radius, ahead of the origin)
-    shaky = (hit & ((np.abs(t0) < tmin) | (np.abs(t1) < tmin))) | ((np.abs(disc) < 1e-6 * a) & (b < 0))
+    # the origin's own surface, or a ray that grazes the sphere (the closest approach within 1e-6 of the radius, ahead of the origin -- or
+    # within what float32 leaves of the renderer's radicand b^2 / a - (ro . ro - 0.25) from far away: a few ulps of its two terms)
+    shaky = (hit & ((np.abs(t0) < tmin) | (np.abs(t1) < tmin))) | ((np.abs(disc) < np.maximum(1e-6 * a, 4e-7 * (b * b + a * _dot(ro, ro)))) & (b < 0))
     return t, inside, shaky
 
 
@@ -70,13 +71,13 @@ def _mesh(ro, rd, tris):
     return t[i, k], k, np.stack([bu[i, k], bv[i, k]], 1)
 
 
-def cast(scene, o, d, tmin=1e-4, near=1e-4, edge=2 * OFFSET):
+def cast(scene, o, d, tmin=1e-4, near=1e-4, edge=2 * OFFSET, inside_cube=False):
     """Rays (o, d) (n, 3) against every primitive.  Returns per ray: prim (-1: nothing), t, gap (the runner-up's distance relative to the
     nearest, (t2 - t1) / t1), P (world), q (object space, SHORT of the surface as the renderer's), axis / sign (a cube's face: the axis of largest |q| and its sign), tri / bary
     (a mesh's triangle and barycentrics), Ng (the outward geometric normal, world), outside, N (Ng turned to the ray's side, as the hit is
     shaded), short (the world vector by which the renderer's hit point stops short of P) and ambiguous: two primitives within `near` of
     each other, a root within `tmin` of the origin, a grazed sphere, a cube hit within `edge` (world units) of an edge, a triangle hit within
-    1e-4 (barycentric) of an edge, an origin inside a cube."""
+    1e-4 (barycentric) of an edge, an origin inside a cube (kept with `inside_cube`: the hit is the exit face, N the inward normal there)."""
     o, d = np.asarray(o, np.float64).reshape(-1, 3), np.asarray(d, np.float64).reshape(-1, 3)
     n, ng = len(o), len(scene.geoms)
     i = np.arange(n)
@@ -120,7 +121,7 @@ def cast(scene, o, d, tmin=1e-4, near=1e-4, edge=2 * OFFSET):
     scale = np.array([np.array(G["scale"], np.float64) for G in scene.geoms])[prim]
     room = (0.5 - np.abs(q)) * scale                                  # world distance to each pair of faces
     room[i, axis] = np.inf
-    amb |= cube & ((room.min(1) < edge) | inside[prim, i])
+    amb |= cube & ((room.min(1) < edge) | (inside[prim, i] & (not inside_cube)))
     mesh = some & (kinds == 2)
     ktri, kb = tri[prim, i], bary[prim, i]
     for g in np.unique(prim[mesh]):
