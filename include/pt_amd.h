@@ -232,7 +232,10 @@ typedef struct PtBumpBinding {
 int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes);
 
 /* pathtraceInit: upload scene, allocate the accumulator and the SoA path-state buffers.
- * Replaces reference src/pathtrace.cu:75-85.  Calling it twice without pt_free re-initialises. */
+ * Replaces reference src/pathtrace.cu:75-85.  Calling it twice without pt_free re-initialises.
+ * A scene or an option that is refused -- every PT_ERR_INVALID -- is refused before anything is touched: nothing is allocated or released,
+ * and the renderer that was there stays initialised and usable.  PT_ERR_NO_GPU and PT_ERR_HIP (a failed HIP call; pools that do not fit
+ * the free device memory, which is measured after the old renderer has given its own back) leave the context without a renderer. */
 int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats,
             int traceDepth, const PtOptions *opts /* may be NULL */);
 

@@ -169,6 +169,16 @@ int pt_test_bounce_form(uint32_t state_bits, uint32_t *form_bits);
 /* The state pt_init left in THIS library's renderer (host only): *state_bits = its dof, many, sweptCubes, mesh, grouped, tex, bump and plain
  * in the bit order pt_test_bounce_form takes them, bit 0 (`first`, a launch's) clear; PT_ERR_NOT_INIT before pt_init. */
 int pt_test_renderer_state(uint32_t *state_bits);
+/* What pt_init would plan for a scene, without a device (host only; csrc/pt_scene_plan.h: plan_scene): pt_init's arguments, with the meshes,
+ * textures and bindings registered with THIS library.  PT_OK and a summary of the plan -- state_bits as pt_test_renderer_state gives them --
+ * or the refusal pt_init would answer with (PT_ERR_INVALID, pt_last_error); no renderer is touched either way. */
+typedef struct PtTestPlanSummary {
+    uint32_t state_bits;
+    int32_t nBinned, nWalls, nSphCull, nSphGroups, nLocalPad, firstSkipped, poolChunks;
+    uint64_t ldsBytes, ldsBytesNext;
+} PtTestPlanSummary;
+int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
+                       PtTestPlanSummary *out);
 /* device allocations THIS library's renderers and temporaries hold right now (every one has one owner type, which counts in this
  * library only): 0 after pt_free */
 int64_t pt_test_live_device_buffers(void);

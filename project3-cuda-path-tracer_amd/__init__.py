@@ -74,7 +74,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
-    "pt_test_renderer_state",
+    "pt_test_renderer_state", "pt_test_scene_plan",
 ]
 
 
@@ -82,6 +82,11 @@ class PtOptions(C.Structure):
     _fields_ = [("shard_rank", C.c_int32), ("shard_count", C.c_int32), ("device", C.c_int32),
                 ("flags", C.c_int32), ("pipeline_depth", C.c_int32), ("max_batch", C.c_int32),
                 ("stream", C.c_void_p), ("accum_dev", C.c_void_p), ("lens_radius", C.c_float), ("focal_distance", C.c_float)]
+
+
+class PtTestPlanSummary(C.Structure):      # include/pt_amd_test.h
+    _fields_ = [("state_bits", C.c_uint32)] + [(n, C.c_int32) for n in ("nBinned", "nWalls", "nSphCull", "nSphGroups", "nLocalPad", "firstSkipped", "poolChunks")] + \
+               [("ldsBytes", C.c_uint64), ("ldsBytesNext", C.c_uint64)]
 
 
 class PtMesh(C.Structure):
@@ -236,6 +241,7 @@ def _bind(L, with_tests):
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
         L.pt_test_renderer_state.argtypes = [C.POINTER(C.c_uint32)]
+        L.pt_test_scene_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(PtOptions), C.POINTER(PtTestPlanSummary)]
     return L
 
 
@@ -455,6 +461,24 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
     _last_init = (cam, geoms, mats, depth, (shard_rank, shard_count, device, flags, lens_radius, focal_distance),
                   (getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None)),
                   _scene_textures(scene), _scene_bumps(scene))
+
+
+def scene_plan(scene, traceDepth=None, **options):
+    """pt_test_scene_plan: what pathtraceInit(scene, ...) would plan, on the host alone (no GPU) -- a PtTestPlanSummary, or the PtError of
+    the refusal.  options: PtOptions fields by name (flags, shard_rank, shard_count, max_batch, lens_radius, ...)."""
+    T = test_lib()
+    # (the scene's meshes, textures and bindings are registered with the test library, as pathtraceInit registers them with the renderer's)
+    set_meshes(getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None), L=T)
+    set_textures(*_scene_textures(scene), L=T)
+    set_bump_maps(*_scene_bumps(scene), L=T)
+    opt = PtOptions(shard_count=1, device=-1)
+    for name, value in options.items():
+        setattr(opt, name, value)
+    geoms, mats, cam = np.ascontiguousarray(scene.geoms), np.ascontiguousarray(scene.materials), np.ascontiguousarray(scene.camera)
+    out = PtTestPlanSummary()
+    _check(T.pt_test_scene_plan(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), scene.traceDepth if traceDepth is None else traceDepth,
+                                C.byref(opt), C.byref(out)), T)
+    return out
 
 
 def _mesh_array(meshes, normals=None, materials=None):

@@ -145,24 +145,8 @@ struct DevBuf {
     int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
 };
 
-constexpr int kMaxSlots = 4;
-constexpr int kTexSizeMax = 16384;     // largest side of a texture (pt_set_textures)
-constexpr long long kTexTexelsMax = 1ll << 28;   // the textures of a scene hold fewer texels
-// A bumped mesh triangle's object-space tangents (ptd "bump mapping", mesh), fp32 in the order written there (this file is compiled
-// with -ffp-contract=off for the host too): tri = its corners p0 p1 p2 (9 floats), uv = u0 v0 u1 v1 u2 v2 -> {Tu, det != 0}, {Tv, 0}
-void meshTangents(const float *tri, const float *uv, float4 &tu, float4 &tv) {
-    const float e1[3] = {tri[3] - tri[0], tri[4] - tri[1], tri[5] - tri[2]};
-    const float e2[3] = {tri[6] - tri[0], tri[7] - tri[1], tri[8] - tri[2]};
-    const float du1 = uv[2] - uv[0], dv1 = uv[3] - uv[1], du2 = uv[4] - uv[0], dv2 = uv[5] - uv[1];
-    const float det = du1 * dv2 - du2 * dv1;
-    float a[3], b[3];
-    for (int k = 0; k < 3; ++k) {
-        a[k] = (e1[k] * dv2 - e2[k] * dv1) / det;
-        b[k] = (e2[k] * du1 - e1[k] * du2) / det;
-    }
-    tu = make_float4(a[0], a[1], a[2], det != 0.0f ? 1.0f : 0.0f);
-    tv = make_float4(b[0], b[1], b[2], 0.0f);
-}
+#include "pt_host_scene.h"
+#include "pt_scene_plan.h"
 
 // One in-flight iteration: its own stream, path buffers, counters and deferred-radiance buffer.
 struct Slot {
@@ -179,20 +163,14 @@ struct Slot {
     int parity = 0;                // which half of Ctrl::cursor the slot's next batch uses
 };
 
-struct State {
+// (it keeps the scalars of the scene's plan -- cam, prm, P, nLocal, flags, the flags that pick the forms of k_bounce, the sizes -- as its base)
+struct State : PlanScalars {
     bool init = false;
     int device = 0;
     hipStream_t stream = nullptr;   // the caller's stream: commits, PBO conversion, readback
-    PtCamera cam;
-    KParams prm;
-    int P = 0;              // W*H
-    int nLocal = 0;
-    int flags = 0;
     float *image = nullptr;         // the accumulator the kernels add to: the caller's (PtOptions::accum_dev, never freed here), or ...
     DevBuf<float> imageOwn;         // ... the renderer's own
     DevBuf<float> moments;          // PT_FLAG_MOMENTS: per pixel the sum of its samples' squared luminance (k_commit<true>); always the renderer's own
-    int nslots = 0;
-    int maxBatch = 1;       // iterations that may share one wavefront (pt_iterate_batch)
     Slot slot[kMaxSlots];
     DevBuf<GeomDev> dgeoms;
     DevBuf<unsigned char> dGeomHit; // GeomHitDev[ngeoms], as the kernels stage it in LDS (scenes that are not sphere-heavy; those: one image of their tables)
@@ -201,7 +179,6 @@ struct State {
     DevBuf<WallBox> dwalls;
     DevBuf<SphereCull> dSphCull;    // sphere-heavy scenes: packed culling data of the spheres, and ...
     DevBuf<SphereCull> dSphGroups;  // ... scenes of hundreds of them: the bounding balls of the table's groups (BounceArgs::sphGroups)
-    bool grouped = false;           // ... whose later bounces take the k_bounce<..., GROUPS> instantiations
     DevBuf<int> dCamWave, dCamSigIdx;   // camera rays: the packed work list (build_camera_list), or none
     DevBuf<uint32_t> dCamPix;
     DevBuf<int> dRowOff, dRowIdx;   // camera-ray bounce: per image row, the primitives whose pixel rectangle covers it
@@ -211,13 +188,9 @@ struct State {
     DevBuf<ptd::TexGeom> dTexGeom;
     DevBuf<int4> dTexDesc;
     DevBuf<float4> dTexels, dTexUV;
-    bool tex = false;       // a texture is bound to at least one primitive (or a height map: BUMP forms are TEX forms)
     // bump-mapped scenes (k_bounce<..., BUMP>): BounceArgs::bumpGeom / bumpUV / bumpTan
     DevBuf<ptd::BumpGeom> dBumpGeom;
     DevBuf<float4> dBumpUV, dBumpTan;
-    bool bump = false;      // a height map is bound to at least one primitive
-    bool mesh = false;      // the scene holds triangle meshes: the k_bounce<., false, ., true> variants
-    int meshStackNeed = 0;  // ... and the stack levels a brute-force walk of them needs per lane (k_gbuffer)
     // the denoiser (pt_denoise.h), all allocated on first use: the guide buffers of iteration dnGuideIter (0: none yet), the float4 images
     // the filter's levels pass on, and the packed RGB the last level writes
     DevBuf<float4> dnPosT, dnNrmId, dnPing[2];
@@ -234,21 +207,11 @@ struct State {
     hipEvent_t noiseEv[2] = {nullptr, nullptr};
     // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
     DevBuf<int> dWalkIdx, dWalkRowOff;
-    DevBuf<WalkMesh> dWalkMeshRows;    // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows); walkMeshLds: how many of them a workgroup stages in LDS (all, or none)
-    int walkMeshLds = 0;
-    int walkClassOff[kClsMax + 1] = {0}, walkAll0 = 0, walkAll1 = 0;
+    DevBuf<WalkMesh> dWalkMeshRows;    // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows)
     int gridWalk = 0, gridWalkFirst = 0;
-    size_t ldsWalk = 0;
-    int numTilesMax = 0;    // upper bound of tiles in one bounce queue (incl. one partial tile per segment)
-    int poolChunks = 0;     // chunks per path pool (incl. the trash chunk 0); a pool holds poolChunks * kChunk paths per array
     int grid = 0;           // persistent grid of k_bounce<false>
     int gridFirst = 0;      // ... and of k_bounce<true> (its own register budget, hence its own residency)
     const void *kernFirst = nullptr, *kernNext = nullptr;   // the forms of k_bounce the camera-ray launch / the later ones take (bounce_form)
-    bool many = false;      // more than kBinMax small primitives (spheres, cubes that are neither walls nor binned): the k_bounce<., true> variants
-    bool sweptCubes = false;  // ... some of them cubes (TileArgs::hot: kHotSweptCubes)
-    bool dof = false;       // thin-lens camera: the k_bounce<true, ., true> variants for the camera-ray bounce
-    bool plain = false;     // no refractive material, no specular exponent on a reflective one, no direct lighting: k_bounce<..., PLAIN>
-    size_t ldsBytes = 0, ldsBytesNext = 0;   // dynamic LDS of the camera-ray launch / of the later ones
     long long iterations = 0;
     long long seq = 0;      // batches enqueued since pt_init: slot = seq % nslots
     // PT_FLAG_TRACE_AHEAD: batches traced ahead of the pt_iterate calls that will ask for their iterations, oldest first.
@@ -279,12 +242,9 @@ struct State {
     // Free -> Init restart protocol re-initialises the same scene)
     std::vector<ptm::HostMesh> meshes;
     // ... and so are the textures and their bindings registered by pt_set_textures
-    struct HostTexture { int w = 0, h = 0; std::vector<float> rgb; };              // rgb: w * h * 3, or empty where w or h is out of range
-    struct HostTexBinding { int geom = 0, texture = 0, ntris = 0; std::vector<float> uvs; };
     std::vector<HostTexture> textures;
     std::vector<HostTexBinding> texBindings;
     // ... and the height maps registered by pt_set_bump_maps (texture: an index into `textures`)
-    struct HostBumpBinding { int geom = 0, texture = 0, ntris = 0; float scale = 0.0f; std::vector<float> uvs; };
     std::vector<HostBumpBinding> bumpBindings;
 };
 
@@ -300,12 +260,6 @@ std::vector<State *> g_contexts;          // every context pt_ctx_create made an
 std::mutex g_groupMutex;                  // guards g_groups
 std::vector<PtGroup *> g_groups;          // every group pt_group_create made and pt_group_destroy has not released (the exit handler destroys them:
                                           // their issuing threads, communicators, streams and frame buffers -- pt_group.h)
-
-const ptm::HostMesh *mesh_of(int geom) {
-    for (const ptm::HostMesh &m : R().meshes)
-        if (m.geom == geom) return &m;
-    return nullptr;
-}
 
 int count_devices() {
     int n = 0;
@@ -325,46 +279,6 @@ PathPool pool(const Slot &sl, int which) {
     p.list = sl.chunkList[which].p;
     p.cap = (uint32_t)R().poolChunks << R().prm.chunkShift;
     return p;
-}
-
-#include "pt_host_scene.h"
-
-// magic_divisor for d, checked on the edges of every quotient range: n / d == (n * m) >> sh for the n < 2^30 the kernels divide
-int checked_magic(uint32_t d, uint32_t &m, uint32_t &sh) {
-    magic_divisor(d, m, sh);
-    for (uint64_t q = 0; q * d < (1ull << 30); q = q < 64 ? q + 1 : q * 2 + 1)
-        for (uint64_t n : {q * d, q * d + d - 1, (uint64_t)((1ull << 30) - 1) - q})
-            if (n < (1ull << 30) && (uint32_t)((n * m) >> sh) != (uint32_t)(n / d))
-                return fail(PT_ERR_INVALID, "pt_init: magic division self-check failed for d=%u n=%llu", d, (unsigned long long)n);
-    return PT_OK;
-}
-
-// One binding of pt_set_textures (scale == nullptr) or pt_set_bump_maps against the scene; bound: which primitives a binding of the kind names already
-int check_binding(const float *scale, size_t index, int geom, int texture, int ntris, const std::vector<float> &uvs, const PtGeom *geoms, int ngeoms,
-                  std::vector<char> &bound) {
-    const char *kind = scale ? "bump" : "texture", *meshKind = scale ? "bumped" : "textured", *bumped = scale ? "bumped " : "";
-    if (geom < 0 || geom >= ngeoms) return fail(PT_ERR_INVALID, "pt_init: %s binding %zu names geom %d of %d", kind, index, geom, ngeoms);
-    if (texture < 0 || texture >= (int)R().textures.size())
-        return fail(PT_ERR_INVALID, "pt_init: %s binding %zu names texture %d of %zu", kind, index, texture, R().textures.size());
-    if (bound[geom]++) return fail(PT_ERR_INVALID, "pt_init: geom %d has two %s bindings", geom, kind);
-    if (scale && !std::isfinite(*scale)) return fail(PT_ERR_INVALID, "pt_init: bump binding %zu has a non-finite scale", index);
-    if (geoms[geom].type == PT_MESH) {
-        if (uvs.empty()) return fail(PT_ERR_INVALID, "pt_init: %s mesh geom %d has no UVs", meshKind, geom);
-        const size_t have = mesh_of(geom)->tris.size();
-        if ((size_t)ntris * 9 != have) return fail(PT_ERR_INVALID, "pt_init: UVs of %d triangles for %smesh geom %d of %zu", ntris, bumped, geom, have / 9);
-    } else if (!uvs.empty() || ntris != 0) {
-        return fail(PT_ERR_INVALID, "pt_init: UVs given for %sgeom %d, which is not a mesh", bumped, geom);
-    }
-    return PT_OK;
-}
-
-// a mesh binding's corner UVs (six floats per triangle) as the kernels read them: two float4 per triangle, {u0, v0, u1, v1}, {u2, v2, 0, 0}
-void pack_uvs(const std::vector<float> &uvs, int ntris, std::vector<float4> &out) {
-    for (int f = 0; f < ntris; ++f) {
-        const float *c = uvs.data() + 6 * (size_t)f;
-        out.push_back(make_float4(c[0], c[1], c[2], c[3]));
-        out.push_back(make_float4(c[4], c[5], 0.0f, 0.0f));
-    }
 }
 
 int resolve_events(std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms, long long &n) {
@@ -411,7 +325,7 @@ const void *bounce_kernel_of(uint32_t form, std::index_sequence<f...>) {
 // the kernel of a form, or nullptr: not one of the 48
 const void *bounce_kernel(uint32_t form) { return bounce_kernel_of(form, std::make_index_sequence<kbForms>()); }
 
-// The form a launch takes: `first` is the launch's (the camera-ray bounce), the rest the renderer's state (State: dof, many, sweptCubes,
+// The form a launch takes: `first` is the launch's (the camera-ray bounce), the rest the renderer's state (PlanScalars: dof, many, sweptCubes,
 // mesh, grouped, tex, bump, plain).
 uint32_t bounce_form(bool first, bool dof, bool many, bool sweptCubes, bool mesh, bool grouped, bool tex, bool bump, bool plain) {
     const bool D = first && dof;                      // thin lens: the camera-ray launch only
@@ -431,8 +345,8 @@ uint32_t bounce_form(bool first, bool dof, bool many, bool sweptCubes, bool mesh
     return f;
 }
 // ... resolved once by pt_init (State::kernFirst / kernNext); a state whose form is not instantiated is an internal error, never a fallback
-int resolve_bounce_kernel(bool first, const void **kernel) {
-    const uint32_t f = bounce_form(first, R().dof, R().many, R().sweptCubes, R().mesh, R().grouped, R().tex, R().bump, R().plain);
+int resolve_bounce_kernel(const PlanScalars &s, bool first, const void **kernel) {
+    const uint32_t f = bounce_form(first, s.dof, s.many, s.sweptCubes, s.mesh, s.grouped, s.tex, s.bump, s.plain);
     *kernel = bounce_kernel(f);
     if (!*kernel)
         return fail(PT_ERR_INVALID, "pt_init: internal error: no k_bounce form 0x%x (FIRST %d MANY %d DOF %d MESH %d PLAIN %d CUBES %d GROUPS %d TEX %d BUMP %d)", f,
@@ -1048,9 +962,9 @@ void free_renderer() {
     // ... and every device table: the move-assignment below releases what the DevBufs of State and its Slots hold
     {   // (the registered meshes, textures and height maps outlive the renderer: see State::meshes)
         std::vector<ptm::HostMesh> keep = std::move(R().meshes);
-        std::vector<State::HostTexture> keepTex = std::move(R().textures);
-        std::vector<State::HostTexBinding> keepBind = std::move(R().texBindings);
-        std::vector<State::HostBumpBinding> keepBump = std::move(R().bumpBindings);
+        std::vector<HostTexture> keepTex = std::move(R().textures);
+        std::vector<HostTexBinding> keepBind = std::move(R().texBindings);
+        std::vector<HostBumpBinding> keepBump = std::move(R().bumpBindings);
         R() = State();
         R().meshes = std::move(keep);
         R().textures = std::move(keepTex);
@@ -1103,7 +1017,7 @@ int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t bindin
     // (indices, counts and the scale are checked by pt_init, against the scene)
     R().bumpBindings.clear();
     for (int i = 0; i < nbindings; ++i) {
-        State::HostBumpBinding b;
+        HostBumpBinding b;
         b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris; b.scale = bindings[i].scale;
         if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
         R().bumpBindings.push_back(std::move(b));
@@ -1127,7 +1041,7 @@ int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_str
     R().texBindings.clear();
     long long texels = 0;
     for (int i = 0; i < ntextures; ++i) {
-        State::HostTexture t;
+        HostTexture t;
         t.w = textures[i].width; t.h = textures[i].height;
         const bool sized = t.w >= 1 && t.w <= kTexSizeMax && t.h >= 1 && t.h <= kTexSizeMax;
         if (sized) texels += (long long)t.w * t.h;
@@ -1135,7 +1049,7 @@ int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_str
         R().textures.push_back(std::move(t));
     }
     for (int i = 0; i < nbindings; ++i) {
-        State::HostTexBinding b;
+        HostTexBinding b;
         b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris;
         if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
         R().texBindings.push_back(std::move(b));
@@ -1143,690 +1057,115 @@ int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_str
     return PT_OK;
 }
 
+// The device half of pt_init.  The scene is planned on the host first (pt_scene_plan.h: plan_scene), and a scene that is refused there --
+// every PT_ERR_INVALID -- has touched nothing: no allocation made or released, the renderer that was there still initialised and usable.
+// Only then the old renderer goes, and what can still fail (PT_ERR_NO_GPU, PT_ERR_HIP: the memory budget, which has to see the memory the
+// old renderer gave back) leaves the context without a renderer.
 int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
             const PtOptions *opts) {
-    if (!cam || ngeoms < 0 || nmats < 0 || (ngeoms && !geoms) || (nmats && !mats))
-        return fail(PT_ERR_INVALID, "pt_init: null argument");
-    if (cam->resolution[0] <= 0 || cam->resolution[1] <= 0) return fail(PT_ERR_INVALID, "pt_init: bad resolution");
-    const bool direct = opts && (opts->flags & PT_FLAG_DIRECT_LIGHTING);
-    if (traceDepth < 1 || traceDepth + (direct ? 1 : 0) > PT_MAX_DEPTH)
-        return fail(PT_ERR_INVALID, "pt_init: traceDepth must be 1..%d", PT_MAX_DEPTH - (direct ? 1 : 0));
-    if (opts && (!(opts->lens_radius >= 0.0f) || (opts->lens_radius > 0.0f && !(opts->focal_distance > 0.0f))))
-        return fail(PT_ERR_INVALID, "pt_init: lens_radius must be >= 0 and focal_distance > 0 with a lens");
-    if ((long long)cam->resolution[0] * cam->resolution[1] > (1ll << 30)) return fail(PT_ERR_INVALID, "pt_init: frame too large");
-    for (int i = 0; i < ngeoms; ++i) {
-        if (geoms[i].type != PT_SPHERE && geoms[i].type != PT_CUBE && geoms[i].type != PT_MESH) return fail(PT_ERR_INVALID, "pt_init: geom %d has unknown type", i);
-        if (geoms[i].type == PT_MESH && !mesh_of(i)) return fail(PT_ERR_INVALID, "pt_init: geom %d is a mesh without triangles (pt_set_meshes)", i);
-        if (geoms[i].materialid < 0 || geoms[i].materialid >= nmats) return fail(PT_ERR_INVALID, "pt_init: geom %d references material %d", i, geoms[i].materialid);
-    }
-    for (const ptm::HostMesh &m : R().meshes)
-        if (m.geom < 0 || m.geom >= ngeoms || geoms[m.geom].type != PT_MESH)
-            return fail(PT_ERR_INVALID, "pt_init: triangles registered for geom %d, which is not a mesh of this scene (pt_set_meshes)", m.geom);
-    {   // textures (pt_set_textures)
-        long long texels = 0;
-        for (size_t i = 0; i < R().textures.size(); ++i) {
-            const State::HostTexture &t = R().textures[i];
-            if (t.w < 1 || t.w > kTexSizeMax || t.h < 1 || t.h > kTexSizeMax)
-                return fail(PT_ERR_INVALID, "pt_init: texture %zu is %d x %d (each side 1..%d)", i, t.w, t.h, kTexSizeMax);
-            texels += (long long)t.w * t.h;
-            if (texels >= kTexTexelsMax) return fail(PT_ERR_INVALID, "pt_init: the textures hold 2^28 texels or more");
-            for (float c : t.rgb)
-                if (!std::isfinite(c)) return fail(PT_ERR_INVALID, "pt_init: texture %zu holds a non-finite texel", i);
-        }
-        std::vector<char> bound(ngeoms, 0), bumped(ngeoms, 0);
-        for (size_t i = 0; i < R().texBindings.size(); ++i) {
-            const State::HostTexBinding &b = R().texBindings[i];
-            PTCHECK(check_binding(nullptr, i, b.geom, b.texture, b.ntris, b.uvs, geoms, ngeoms, bound));
-        }
-        for (size_t i = 0; i < R().bumpBindings.size(); ++i) {
-            const State::HostBumpBinding &b = R().bumpBindings[i];
-            PTCHECK(check_binding(&b.scale, i, b.geom, b.texture, b.ntris, b.uvs, geoms, ngeoms, bumped));
-        }
-    }
+    const PtOptions o = effective_options(opts);
+    ScenePlan plan;
+    PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, o, R().meshes, R().textures, R().texBindings, R().bumpBindings}, plan));
+    const void *kernFirst = nullptr, *kernNext = nullptr;
+    PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
+    PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
     register_exit_handler();
     free_renderer();
 
-    PtOptions o;
-    memset(&o, 0, sizeof o);
-    o.shard_count = 1;
-    o.device = -1;
-    if (opts) o = *opts;
-    if (o.shard_count < 1 || o.shard_rank < 0 || o.shard_rank >= o.shard_count) return fail(PT_ERR_INVALID, "pt_init: bad shard %d/%d", o.shard_rank, o.shard_count);
-    if ((o.flags & PT_FLAG_MOMENTS) && (o.shard_count > 1 || (o.flags & PT_FLAG_ACCUM_SHARD_ROWS)))
-        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOMENTS needs the whole frame: no row shard, no PT_FLAG_ACCUM_SHARD_ROWS");
-    if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
-    if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
+    State &S = R();
+    static_cast<PlanScalars &>(S) = plan;
+    S.kernFirst = kernFirst;
+    S.kernNext = kernNext;
     if (o.device >= 0) HIPCHECK(hipSetDevice(o.device));
-    HIPCHECK(hipGetDevice(&R().device));
-    R().stream = (hipStream_t)o.stream;
-    R().flags = o.flags;
-    R().cam = *cam;
-
-    HIPCHECK(hipHostMalloc((void **)&R().hostFault, sizeof(uint32_t), hipHostMallocMapped));
-    *R().hostFault = 0u;
-    HIPCHECK(hipHostGetDevicePointer((void **)&R().hostFaultDev, R().hostFault, 0));
-
-    const int Wd = cam->resolution[0], H = cam->resolution[1];
-    R().P = Wd * H;
-    const int rows = H > o.shard_rank ? (H - o.shard_rank + o.shard_count - 1) / o.shard_count : 0;
-    R().nLocal = rows * Wd;
-
-    KParams &k = R().prm;
-    memset(&k, 0, sizeof k);
-    camera_params(*cam, k);
-    const H3 view{cam->view.x, cam->view.y, cam->view.z};
-    k.shardRank = o.shard_rank; k.shardCount = o.shard_count;
-    k.nLocal = R().nLocal;
-    magic_divisor((uint32_t)o.shard_count, k.magicS, k.shiftS);
-    k.contribLocal = (o.shard_count > 1 && (long long)Wd * H < (1ll << 27)) ? 1 : 0;   // (the multiply-shift divisions hold below 2^27)
-    // camera-ray tiles lie on rows padded to a multiple of the tile size (KParams::Wp)
-    k.Wp = (Wd + kBlock - 1) / kBlock * kBlock;
-    if ((long long)rows * k.Wp >= (1ll << 30)) return fail(PT_ERR_INVALID, "pt_init: frame too large (rows x padded width must stay below 2^30)");
-    k.nLocalPad = rows * k.Wp;
-    PTCHECK(checked_magic((uint32_t)Wd, k.magicW, k.shiftW));
-    PTCHECK(checked_magic((uint32_t)k.Wp, k.magicWp, k.shiftWp));
-    PTCHECK(checked_magic((uint32_t)std::max(k.nLocalPad, 1), k.magicN, k.shiftN));
-    k.ngeoms = ngeoms; k.nmats = nmats;
-    // direct lighting: bounce `traceDepth` aims its diffuse scatter at a light and one more launch collects
-    k.traceDepth = traceDepth + (direct ? 1 : 0);
-    k.directDepth = direct ? traceDepth : 0;
-    // the emitters of the direct-lighting bounce, file order: primitives with an emissive material, sampled through their unit cube --
-    // and meshes (round 5) whose own or any of whose faces' materials emits, through the object-space bounds of their vertices
-    // (the CPU oracle restates this loop operation for operation: its rebuild_emitters)
-    k.nEmit = 0;
-    for (int i = 0; i < ngeoms && k.nEmit < kEmitMax; ++i) {
-        bool emits = mats[geoms[i].materialid].emittance > 0.0f;
-        float c[3] = {0.0f, 0.0f, 0.0f}, e[3] = {1.0f, 1.0f, 1.0f};
-        if (geoms[i].type == PT_MESH) {
-            const ptm::HostMesh *hm_ = mesh_of(i);
-            if (!hm_ || hm_->tris.size() < 9) continue;
-            for (int fm : hm_->mats) emits = emits || (fm >= 0 && fm < nmats && mats[fm].emittance > 0.0f);
-            float lo[3] = {hm_->tris[0], hm_->tris[1], hm_->tris[2]}, hi[3] = {lo[0], lo[1], lo[2]};
-            for (size_t q = 0; q + 2 < hm_->tris.size(); q += 3)
-                for (int a = 0; a < 3; ++a) {
-                    lo[a] = lo[a] < hm_->tris[q + a] ? lo[a] : hm_->tris[q + a];
-                    hi[a] = hi[a] < hm_->tris[q + a] ? hm_->tris[q + a] : hi[a];
-                }
-            for (int a = 0; a < 3; ++a) { c[a] = (lo[a] + hi[a]) * 0.5f; e[a] = hi[a] - lo[a]; }
-        }
-        if (!emits) continue;
-        const PtVec3 sc = geoms[i].scale;
-        const float sx = sc.x * e[0], sy = sc.y * e[1], sz = sc.z * e[2];
-        k.emitRho2[k.nEmit] = ((sx * sx + sy * sy) + sz * sz) * 0.25f;
-        for (int a = 0; a < 3; ++a) { k.emitBox[k.nEmit][a] = c[a]; k.emitBox[k.nEmit][3 + a] = e[a]; }
-        k.emitGeom[k.nEmit++] = i;
-    }
-    k.lensRadius = o.lens_radius;
-    k.focalDistance = o.focal_distance;
-    {
-        const H3 vn = hnormalize(view);
-        k.viewN[0] = vn.x; k.viewN[1] = vn.y; k.viewN[2] = vn.z;
-    }
-    R().dof = o.lens_radius > 0.0f;
-    // plain: nothing in the scene takes the scatter's rarer branches (PT_AMD_NO_PLAIN: experiments / tests only)
-    R().plain = !direct && !(o.flags & PT_FLAG_MIXTURE_WEIGHTED) && !env_flag("PT_AMD_NO_PLAIN");
-    for (int i = 0; i < nmats; ++i)
-        if (mats[i].hasRefractive > 0.0f || (mats[i].hasReflective > 0.0f && mats[i].specularExponent > 0.0f)) R().plain = false;
+    HIPCHECK(hipGetDevice(&S.device));
+    S.stream = (hipStream_t)o.stream;
+    HIPCHECK(hipHostMalloc((void **)&S.hostFault, sizeof(uint32_t), hipHostMallocMapped));
+    *S.hostFault = 0u;
+    HIPCHECK(hipHostGetDevicePointer((void **)&S.hostFaultDev, S.hostFault, 0));
 
     if (o.accum_dev) {
-        R().image = o.accum_dev;
+        S.image = o.accum_dev;
     } else {
-        const size_t n = (R().flags & PT_FLAG_ACCUM_SHARD_ROWS) ? (size_t)(R().nLocal > 0 ? R().nLocal : 1) : (size_t)R().P;
-        PTCHECK(R().imageOwn.alloc(n * 3));
-        R().image = R().imageOwn.p;
-        HIPCHECK(hipMemsetAsync(R().image, 0, n * 3 * sizeof(float), R().stream));
+        const size_t n = (S.flags & PT_FLAG_ACCUM_SHARD_ROWS) ? (size_t)(S.nLocal > 0 ? S.nLocal : 1) : (size_t)S.P;
+        PTCHECK(S.imageOwn.alloc(n * 3));
+        S.image = S.imageOwn.p;
+        HIPCHECK(hipMemsetAsync(S.image, 0, n * 3 * sizeof(float), S.stream));
     }
-    if (R().flags & PT_FLAG_MOMENTS) PTCHECK(R().moments.alloc_zeroed((size_t)R().P));
-    // Path pools: a bounce's queue is kSeg = kCls x kSub segments, each a list of chunks handed out on demand, one ahead of
-    // their use (ptk::reserveRun).  At most nLocal * maxBatch paths are alive; every segment may end in a partly filled
-    // chunk and holds one chunk installed ahead: ceil(paths / chunk) + 2 kSeg chunks always suffice, whatever the
-    // distribution over the classes (+ the trash chunk 0).  Chunk size: a power of two, at least 2048 (rounds 1-3: ~1/1024 of the
-    // paths, so that the slack stayed around 10 % while a chunk outlasts the appends of one memory round trip).
-    R().maxBatch = o.max_batch > 0 ? o.max_batch : 1;
-    {   // a path carries pixelIndex | batch index << pixBits in ONE word (ptk::PathC)
-        int pixBits = 1, batchBits = 0;
-        while (((long long)k.W * k.H - 1) >> pixBits) ++pixBits;
-        while ((R().maxBatch - 1) >> batchBits) ++batchBits;
-        if (pixBits + batchBits > 32)
-            return fail(PT_ERR_INVALID, "pt_init: %d x %d pixels and max_batch %d need %d + %d bits of a path's 32-bit index word: lower max_batch", k.W, k.H,
-                        R().maxBatch, pixBits, batchBits);
-        k.pixBits = pixBits;
-    }
-    if (R().maxBatch == 1) R().flags &= ~PT_FLAG_TRACE_AHEAD;   // nothing to trace ahead with: every call traces its own iteration
-    // slots are 32-bit element indices with 32-bit byte offsets: paths per pool must stay below 2^30
-    const long long maxPaths = (long long)R().nLocal * R().maxBatch;
-    if (maxPaths > (1ll << 29)) return fail(PT_ERR_INVALID, "pt_init: max_batch x pixels too large (limit 2^29 paths per batch)");
-    if ((long long)k.nLocalPad * R().maxBatch >= (1ll << 30))     // (the camera-ray tiles' index space: rows padded to the tile size)
-        return fail(PT_ERR_INVALID, "pt_init: max_batch x rows x padded width too large (limit 2^30)");
-    R().numTilesMax = (int)((maxPaths + kBlock - 1) / kBlock) + kSeg;
-    // (round 4: ~1/256 of the paths, at most 2^18, where it was 1/1024 and 2^17 -- a run that opens a new chunk pays a dependent
-    // look-up of the chunk list INSIDE the reservation's window, and four times fewer of them are +2 % on C2, +4 % on the closed box
-    // (profiles/r04_chunk_size_sweep.txt); the slack of 2 kSeg chunks then doubles a mid-sized pool, which 288 GB shrug off)
-    k.chunkShift = kMinChunkShift;
-    while (k.chunkShift < 18 && (maxPaths >> k.chunkShift) > 256) ++k.chunkShift;
-    if (const char *e = getenv("PT_AMD_CHUNK_SHIFT")) {      // experiments only
-        const int v = atoi(e);
-        if (v >= kMinChunkShift && v <= 20) k.chunkShift = v;
-    }
-    const long long chunkPaths = 1ll << k.chunkShift;
-    R().poolChunks = (int)((maxPaths + chunkPaths - 1) / chunkPaths) + 2 * kSeg + 1;
-    if (const char *e = getenv("PT_AMD_POOL_CHUNKS")) {      // tests only: an undersized pool must fail loudly (PT_ERR_DEVICE)
-        const int v = atoi(e);
-        if (v >= kSeg + 2) R().poolChunks = v;
-    }
-    k.poolChunks = R().poolChunks;
-    const size_t cap = (size_t)R().poolChunks << k.chunkShift;
-    // scenes with meshes: a record per path of a bounce's input queue (camera rays: per pixel of the tiles' padded index space) -- BounceArgs::meshHit
-    bool anyMesh = false;
-    for (int i = 0; i < ngeoms; ++i) anyMesh = anyMesh || geoms[i].type == PT_MESH;
-    const size_t meshHitWords = anyMesh ? std::max(cap, (size_t)k.nLocalPad * (size_t)R().maxBatch) : 0;
-    // Iterations are independent (RNG keyed on pixel/iteration/depth), so up to `nslots` of them are in flight
-    // on their own streams; the small late-bounce launches of one overlap the big early launches of the next.
-    R().nslots = o.pipeline_depth > 0 ? o.pipeline_depth : 3;
+    if (S.flags & PT_FLAG_MOMENTS) PTCHECK(S.moments.alloc_zeroed((size_t)S.P));
+    // radiance buffers and iteration masks: the frame's pixels, or only this shard's (KParams::contribLocal)
+    const size_t cpx = S.prm.contribLocal ? (size_t)(S.nLocal > 0 ? S.nLocal : 1) : (size_t)S.P;
+    const size_t contribFloats = (size_t)S.maxBatch * cpx * 3, maskWords = (size_t)((S.maxBatch + 31) / 32) * cpx;
     {   // the memory budget BEFORE the first large allocation: a batch that does not fit fails here, with nothing to undo
-        const size_t cpx = k.contribLocal ? (size_t)(R().nLocal > 0 ? R().nLocal : 1) : (size_t)R().P;
-        const size_t perSlot = 2 * (cap * kNumArrays * sizeof(float) + (size_t)kSeg * R().poolChunks * sizeof(unsigned long long)) + sizeof(Ctrl) +
-                               (size_t)R().maxBatch * cpx * 3 * sizeof(float) + (size_t)((R().maxBatch + 31) / 32) * cpx * sizeof(uint32_t) +
-                               meshHitWords * sizeof(unsigned long long);
-        const size_t need = perSlot * (size_t)R().nslots;
+        const size_t perSlot = 2 * (S.poolCap * kNumArrays * sizeof(float) + (size_t)kSeg * S.poolChunks * sizeof(unsigned long long)) + sizeof(Ctrl) +
+                               contribFloats * sizeof(float) + maskWords * sizeof(uint32_t) + S.meshHitWords * sizeof(unsigned long long);
+        const size_t need = perSlot * (size_t)S.nslots;
         size_t freeB = 0, totalB = 0;
         HIPCHECK(hipMemGetInfo(&freeB, &totalB));
         if (need > freeB)
             return fail(PT_ERR_HIP, "pt_init: %.2f GB of path pools and radiance buffers (max_batch %d x pipeline_depth %d) exceed the %.2f GB of free "
-                        "device memory: lower max_batch or pipeline_depth", need / 1e9, R().maxBatch, R().nslots, freeB / 1e9);
+                        "device memory: lower max_batch or pipeline_depth", need / 1e9, S.maxBatch, S.nslots, freeB / 1e9);
     }
-    for (int i = 0; i < R().nslots; ++i) {
-        Slot &sl = R().slot[i];
+    for (int i = 0; i < S.nslots; ++i) {
+        Slot &sl = S.slot[i];
         HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         for (int b = 0; b < 2; ++b) {
-            PTCHECK(sl.pathbuf[b].alloc(cap * kNumArrays));
-            PTCHECK(sl.chunkList[b].alloc_zeroed((size_t)kSeg * R().poolChunks));
+            PTCHECK(sl.pathbuf[b].alloc(S.poolCap * kNumArrays));
+            PTCHECK(sl.chunkList[b].alloc_zeroed((size_t)kSeg * S.poolChunks));
         }
         PTCHECK(sl.ctrl.alloc(1));
         PTCHECK(reset_ctrl(sl.ctrl.p, nullptr));
-        // radiance buffers and iteration masks: the frame's pixels, or only this shard's (KParams::contribLocal)
-        const size_t cpx = k.contribLocal ? (size_t)(R().nLocal > 0 ? R().nLocal : 1) : (size_t)R().P;
-        PTCHECK(sl.contrib.alloc_zeroed((size_t)R().maxBatch * cpx * 3));
-        PTCHECK(sl.hitMask.alloc_zeroed((size_t)((R().maxBatch + 31) / 32) * cpx));
-        if (meshHitWords) PTCHECK(sl.meshHit.alloc(meshHitWords));
+        PTCHECK(sl.contrib.alloc_zeroed(contribFloats));
+        PTCHECK(sl.hitMask.alloc_zeroed(maskWords));
+        if (S.meshHitWords) PTCHECK(sl.meshHit.alloc(S.meshHitWords));
         HIPCHECK(hipEventCreateWithFlags(&sl.evDone, hipEventDisableTiming));
         HIPCHECK(hipEventCreateWithFlags(&sl.evCommitted, hipEventDisableTiming));
     }
 
-    std::vector<GeomDev> hg(ngeoms ? ngeoms : 1);
-    std::vector<MaterialDev> hm(nmats ? nmats : 1);
-    // triangle meshes: one record array for the scene, a hierarchy per mesh (pt_mesh.h)
-    std::vector<ptd::MeshUnit> meshRecs;
-    int meshStackNeed = 0;
-    const bool flatMeshes = env_flag("PT_AMD_MESH_FLAT");   // tests only: no hierarchy
-    std::vector<std::array<float, 6>> meshBox(ngeoms ? ngeoms : 1);
-    std::vector<const float *> boxes(ngeoms ? ngeoms : 1, nullptr);
-    std::vector<uint32_t> triBase(ngeoms ? ngeoms : 1, 0u);      // (textured meshes: the unit of the first triangle record, ptm::appendMesh)
-    for (int i = 0; i < ngeoms; ++i) {
-        float *box = meshBox[i].data();
-        const bool isMesh = geoms[i].type == PT_MESH;
-        if (isMesh) boxes[i] = box;
-        uint32_t root = ptd::kMeshEnd, stride = 0;
-        const uint32_t unit0 = (uint32_t)meshRecs.size();        // (the mesh's units: its triangles -- and normals -- lie in [unit0, root))
-        if (isMesh) {
-            const ptm::HostMesh *hm_ = mesh_of(i);
-            for (int fm : hm_->mats)
-                if (fm >= nmats) return fail(PT_ERR_INVALID, "pt_init: a face of mesh geom %d names material %d of %d", i, fm, nmats);
-            const ptm::MeshLayout lay = ptm::appendMesh(hm_->tris.data(), (int)(hm_->tris.size() / 9), flatMeshes, meshRecs, box,
-                                                        hm_->normals.empty() ? nullptr : hm_->normals.data(), hm_->mats.empty() ? nullptr : hm_->mats.data());
-            root = lay.root;
-            stride = lay.stride;
-            meshStackNeed = std::max(meshStackNeed, lay.stackNeed);
-            if (meshRecs.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many triangles");
-        }
-        pack_geom(geoms[i], hg[i], k.pos, isMesh ? box : nullptr);
-        hg[i].meshRoot = root;
-        if (isMesh) { hg[i].meshStride = stride; hg[i].meshUnit0 = unit0; hg[i].meshUnit1 = root; triBase[i] = (unit0 + 3u) & ~3u; }
-        if (geoms[i].type == PT_CUBE) {
-            if (k.nCubes >= 32767) return fail(PT_ERR_INVALID, "pt_init: more than 32767 cubes");
-            hg[i].frameSlot = (short)k.nCubes++;
-        }
+    // the plan's tables, each once; a table the scene does not have is empty and stays without a buffer (the walks' tables of a scene with
+    // meshes and the groups of a grouped one get theirs even when empty: a kernel may be handed the pointer of an empty table)
+    const auto up = [](auto &buf, const auto &table) { return table.empty() ? (int)PT_OK : buf.upload(table); };
+    PTCHECK(up(S.dgeoms, plan.hg));
+    PTCHECK(up(S.dmats, plan.hm));
+    PTCHECK(up(S.dGeomHit, plan.geomHit));
+    PTCHECK(up(S.dRows, plan.rowsGlobal));
+    PTCHECK(up(S.dwalls, plan.hw));
+    PTCHECK(up(S.dTexGeom, plan.texGeom));
+    PTCHECK(up(S.dTexDesc, plan.texDesc));
+    PTCHECK(up(S.dTexels, plan.texels));
+    PTCHECK(up(S.dTexUV, plan.texUV));
+    PTCHECK(up(S.dBumpGeom, plan.bumpGeom));
+    PTCHECK(up(S.dBumpUV, plan.bumpUV));
+    PTCHECK(up(S.dBumpTan, plan.bumpTan));
+    if (S.mesh) {
+        PTCHECK(S.dMeshRecs.upload(plan.meshRecs.data(), plan.meshRecs.size(), 4));     // (+ 4: a walk may read the record behind the last one)
+        PTCHECK(S.dWalkIdx.upload(plan.walkIdx));
+        PTCHECK(S.dWalkMeshRows.upload(plan.walkMeshRows));
     }
-    // camera rays: pixel rectangles, their union and the per-row lists (thin lens: none -- rays start anywhere on the lens)
-    CameraCull cc;
-    const bool cullOff = R().dof || env_flag("PT_AMD_NO_CAMERA_CULL");   // (the variable: tests only)
-    build_camera_cull(geoms, ngeoms, k, cullOff, boxes, hg, cc);
-    for (int a = 0; a < 4; ++a) k.sceneRect[a] = cc.sceneRect[a];
-    {   // The camera-ray tiles' index space covers only the column bands (of kBlock pixels) and the rows of this shard that meet the
-        // scene rectangle: at 16:9 two of Cornell's five bands lie outside it, and a workgroup spent a tenth of the launch
-        // stepping over their tiles one by one.  The pixels never visited are misses whatever their jitter: tallied at once.
-        const int perRow = k.Wp / kBlock;
-        int c0 = 0, c1 = perRow - 1, r0 = 0, r1 = rows - 1;
-        if (cc.sceneRect[0] > cc.sceneRect[2] || cc.sceneRect[1] > cc.sceneRect[3]) {      // nothing can be hit
-            c1 = -1; r1 = -1;
-        } else {
-            c0 = std::max(cc.sceneRect[0], 0) / kBlock;
-            c1 = std::min(std::min(cc.sceneRect[2], Wd - 1) / kBlock, perRow - 1);
-            // rows y = lr * shard_count + shard_rank inside [sceneRect[1], sceneRect[3]]
-            const int y0 = std::max(cc.sceneRect[1], 0), y1 = std::min(cc.sceneRect[3], H - 1);
-            r0 = y0 <= o.shard_rank ? 0 : (y0 - o.shard_rank + o.shard_count - 1) / o.shard_count;
-            r1 = y1 < o.shard_rank ? -1 : std::min((y1 - o.shard_rank) / o.shard_count, rows - 1);
-        }
-        const int nCols = std::max(c1 - c0 + 1, 0), nRows = std::max(r1 - r0 + 1, 0);
-        const long long visited = nCols > 0 && nRows > 0 ? (long long)nRows * (std::min(Wd, (c1 + 1) * kBlock) - c0 * kBlock) : 0;
-        k.firstY0 = (nRows > 0 ? r0 : 0) * o.shard_count + o.shard_rank;      // (the first column: the band of sceneRect[0], k_bounce)
-        k.firstSkipped = (int)((long long)R().nLocal - visited);
-        k.Wp = std::max(nCols, 1) * kBlock;                       // (>= one band: the divisions below stay defined)
-        k.nLocalPad = nCols > 0 ? nRows * k.Wp : 0;
-        PTCHECK(checked_magic((uint32_t)k.Wp, k.magicWp, k.shiftWp));
-        PTCHECK(checked_magic((uint32_t)std::max(k.nLocalPad, 1), k.magicN, k.shiftN));
-    }
-    for (int i = 0; i < nmats; ++i) pack_material(mats[i], hm[i]);
-    // Small primitives the queue is binned by (k_bounce): the spheres when there are at most kBinMax of them, then the
-    // cubes whose bounding ball is small against the scene's (<= 0.3 of its radius), smallest first.  A choice that only
-    // steers which tiles skip which tests; results never depend on it.
-    {
-        double cm[3] = {0, 0, 0}, sceneR = 0;
-        for (int i = 0; i < ngeoms; ++i)
-            for (int a = 0; a < 3; ++a) cm[a] += hg[i].centre[a] / std::max(ngeoms, 1);
-        for (int i = 0; i < ngeoms; ++i) {
-            const double dx = hg[i].centre[0] - cm[0], dy = hg[i].centre[1] - cm[1], dz = hg[i].centre[2] - cm[2];
-            const double r = std::sqrt(dx * dx + dy * dy + dz * dz) + hg[i].boundR;
-            if (std::isfinite(r)) sceneR = std::max(sceneR, r);
-        }
-        int nsph = 0;
-        for (int i = 0; i < ngeoms; ++i) nsph += geoms[i].type == PT_SPHERE;
-        std::vector<std::pair<double, int>> cand;
-        for (int i = 0; i < ngeoms; ++i) {
-            if (!std::isfinite(hg[i].cullR2)) continue;                       // never culled: cannot take part
-            const double r = hg[i].boundR;
-            if (geoms[i].type == PT_SPHERE) { if (nsph <= kBinMax) cand.emplace_back(-1.0, i); }   // spheres first
-            else if (r <= 0.3 * sceneR) cand.emplace_back(r, i);
-        }
-        std::sort(cand.begin(), cand.end());
-        k.nBinned = 0;
-        for (size_t c = 0; c < cand.size() && k.nBinned < kBinMax; ++c) {
-            k.binGeom[k.nBinned++] = cand[c].second;
-            hg[cand[c].second].binned = 1;
-            hg[cand[c].second].flags |= 2;
-            hg[cand[c].second].cullFlags |= 2;
-        }
-    }
-    // Mesh scenes bin by two candidate bits (pt_trace.h: kClsMax): the costliest binned mesh (most triangles) alone in group 1 when there is
-    // another binned primitive beside it, everything else in group 0 -- a tile of the next bounce then walks that mesh only when its paths
-    // can hit it, with all its lanes, instead of every cand tile walking every mesh with some.
-    int binGroup[kBinMax] = {0, 0, 0, 0};
-    if (!meshRecs.empty() && k.nBinned > 1) {
-        int bestB = -1;
-        size_t bestTris = 0;
-        for (int b = 0; b < k.nBinned; ++b)
-            if (geoms[k.binGeom[b]].type == PT_MESH) {
-                const size_t nt = mesh_of(k.binGeom[b])->tris.size() / 9;
-                if (nt > bestTris) { bestTris = nt; bestB = b; }
-            }
-        if (bestB >= 0) binGroup[bestB] = 1;
-    }
-    for (int b = 0; b < kBinMax; ++b) {                      // (KParams::binCull: the binned primitives' culling groups, inline)
-        for (int q = 0; q < 8; ++q) k.binCull[b][q] = 0.0f;
-        k.binCull[b][3] = -INFINITY;                          // beyond nBinned: certified for everybody
-        if (b < k.nBinned) {
-            const GeomDev &G = hg[k.binGeom[b]];
-            k.binCull[b][0] = G.centre[0]; k.binCull[b][1] = G.centre[1]; k.binCull[b][2] = G.centre[2];
-            k.binCull[b][3] = G.cullR2; k.binCull[b][4] = G.cullK;
-            // word 5: the primitive's candidate bit in a survivor's class (k_bounce<..., MESH>): 1 = group 0, 2 = group 1
-            const uint32_t bit = 1u << binGroup[b];
-            memcpy(&k.binCull[b][5], &bit, sizeof bit);
-        }
-    }
-    // Walls: the large cubes -- not binned, finite -- at most kWallMax of them, the largest first.  Survivors are classed by
-    // the one wall they can still hit (ptd::wallCertainMiss against the inflated world boxes computed here), so a tile of
-    // the next bounce tests one wall instead of all of them, and a survivor that can hit nothing at all ends at once.
-    // A choice that only steers which tiles skip which tests; results never depend on it.
-    std::vector<WallBox> hw(kWallMax);
-    {
-        std::vector<int> wallGeom;
-        choose_walls(geoms, ngeoms, hg, k, hw, wallGeom);
-        for (int w = 0; w < k.nWalls; ++w) {
-            hg[wallGeom[w]].flags |= (w + 1) << 2;
-            hg[wallGeom[w]].cullFlags |= (w + 1) << 2;
-        }
-        if (env_flag("PT_AMD_NO_WALLS")) { for (int i = 0; i < ngeoms; ++i) { hg[i].flags &= 3; hg[i].cullFlags &= 3; } k.nWalls = 0; k.wallOMax = 0.0f; k.nSlotWalls = 0; k.nPlaneWalls = 0; }   // experiments only
-        if (k.nPlaneWalls > 0) R().plain = false;      // (the rotated walls' certificate lives in the general instantiations only: k_bounce, wallPlanesOriented)
-        k.allClassified = k.nWalls > 0 ? 1 : 0;
-        for (int i = 0; i < ngeoms; ++i)
-            if (!hg[i].binned && (hg[i].flags & 28) == 0) k.allClassified = 0;
-    }
-    k.emittersBinned = k.nBinned > 0 ? 1 : 0;
-    for (int i = 0; i < ngeoms; ++i) {
-        bool emits = mats[geoms[i].materialid].emittance > 0.0f;
-        if (geoms[i].type == PT_MESH)                   // (a mesh emits when any of its faces' own materials does)
-            if (const ptm::HostMesh *hm_ = mesh_of(i))
-                for (int fm : hm_->mats) emits = emits || (fm >= 0 && mats[fm].emittance > 0.0f);
-        if (emits && !hg[i].binned) k.emittersBinned = 0;
-    }
-    PTCHECK(R().dgeoms.upload(hg));
-    PTCHECK(R().dmats.upload(hm));
-    {   // the per-primitive hit records, ready-made: a workgroup's prologue copies them to LDS in one round trip instead of following
-        // primitive -> material index -> material on the device (every workgroup of every launch did)
-        std::vector<GeomHitDev> hh(hg.size());
-        for (size_t i = 0; i < hg.size(); ++i) {
-            GeomHitDev &h = hh[i];
-            memset(&h, 0, sizeof h);
-            const GeomDev &G = hg[i];
-            const int mi = (int)i < ngeoms && G.material >= 0 && G.material < nmats ? G.material : 0;
-            const MaterialDev &M = hm[(size_t)mi];
-            h.type = G.type;
-            h.emittance = M.emittance; h.hasReflective = M.hasReflective; h.hasRefractive = M.hasRefractive;
-            for (int a = 0; a < 3; ++a) h.color[a] = M.color[a];
-            h.material = G.material;
-            memcpy(h.nm, G.invT, sizeof h.nm);
-            memcpy(h.cubeFrame, G.cubeFrame, sizeof h.cubeFrame);
-        }
-        PTCHECK(R().dGeomHit.upload(reinterpret_cast<const unsigned char *>(hh.data()), hh.size() * sizeof(GeomHitDev)));
-    }
-    PTCHECK(R().dwalls.upload(hw));
-    R().mesh = !meshRecs.empty();
-    R().meshStackNeed = meshStackNeed;
-    R().bump = !R().bumpBindings.empty();
-    R().tex = !R().texBindings.empty() || R().bump;
-    if (R().tex) {         // every texel one float4, the textures one after another; per primitive its TexGeom; per textured triangle two float4
-        std::vector<int4> desc;
-        std::vector<float4> texels, uv;
-        for (const State::HostTexture &t : R().textures) {
-            desc.push_back(make_int4((int)texels.size(), t.w, t.h, 0));
-            for (size_t q = 0; q < (size_t)t.w * t.h; ++q) texels.push_back(make_float4(t.rgb[3 * q], t.rgb[3 * q + 1], t.rgb[3 * q + 2], 0.0f));
-        }
-        std::vector<ptd::TexGeom> tg(ngeoms ? ngeoms : 1, ptd::TexGeom{-1, 0, 0, 0});
-        for (int i = 0; i < ngeoms; ++i) tg[i].kind = geoms[i].type == PT_CUBE ? 1 : (geoms[i].type == PT_MESH ? 2 : 0);
-        for (const State::HostTexBinding &b : R().texBindings) {
-            tg[b.geom].tex = b.texture;
-            if (b.uvs.empty()) continue;
-            tg[b.geom].uvBase = (int)(uv.size() / 2);
-            tg[b.geom].triBase = (int)triBase[b.geom];
-            pack_uvs(b.uvs, b.ntris, uv);
-            if (uv.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many textured triangles");
-        }
-        if (uv.empty()) uv.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        PTCHECK(R().dTexGeom.upload(tg));
-        PTCHECK(R().dTexDesc.upload(desc));
-        PTCHECK(R().dTexels.upload(texels));
-        PTCHECK(R().dTexUV.upload(uv));
-    }
-    if (R().bump) {        // per primitive its BumpGeom; per bumped triangle two float4 of corner UVs and two of tangents (a mesh's rows of its own,
-                           // even where its texture binding carries the same UVs)
-        std::vector<ptd::BumpGeom> bg(ngeoms ? ngeoms : 1, ptd::BumpGeom{-1, 0, 0, 0});
-        std::vector<float4> uv, tan;
-        for (const State::HostBumpBinding &b : R().bumpBindings) {
-            bg[b.geom].tex = b.texture;
-            memcpy(&bg[b.geom].scaleBits, &b.scale, 4);
-            if (b.uvs.empty()) continue;
-            const ptm::HostMesh *hm_ = mesh_of(b.geom);
-            bg[b.geom].uvBase = (int)(uv.size() / 2);
-            bg[b.geom].triBase = (int)triBase[b.geom];
-            pack_uvs(b.uvs, b.ntris, uv);
-            for (int f = 0; f < b.ntris; ++f) {
-                float4 tu, tv;
-                meshTangents(hm_->tris.data() + 9 * (size_t)f, b.uvs.data() + 6 * (size_t)f, tu, tv);
-                tan.push_back(tu);
-                tan.push_back(tv);
-            }
-            if (uv.size() >= (1ull << 31)) return fail(PT_ERR_INVALID, "pt_init: too many bumped triangles");
-        }
-        if (uv.empty()) { uv.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f)); tan.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f)); }
-        PTCHECK(R().dBumpGeom.upload(bg));
-        PTCHECK(R().dBumpUV.upload(uv));
-        PTCHECK(R().dBumpTan.upload(tan));
-    }
-    if (R().mesh) PTCHECK(R().dMeshRecs.upload(meshRecs.data(), meshRecs.size(), 4));     // (+ 4: a walk may read the record behind the last one)
+    PTCHECK(up(S.dSphCull, plan.sc));
+    if (S.grouped) PTCHECK(S.dSphGroups.upload(plan.groups));
+    PTCHECK(up(S.dRowOff, plan.cc.rowOff));
+    PTCHECK(up(S.dRowIdx, plan.cc.rowIdx));
+    PTCHECK(up(S.dCamPix, plan.cl.pix));
+    PTCHECK(up(S.dCamWave, plan.cl.wave));
+    PTCHECK(up(S.dCamSigIdx, plan.cl.sigIdx));
+    PTCHECK(up(S.dWalkRowOff, plan.walkRowOff));
+    PTCHECK(up(S.dClassIdx, plan.classIdx));
 
-    // The SWEPT primitives of a scene with many small ones (round 5: cubes too -- rounds 2-4 swept spheres only, and 64 small cubes cost
-    // 4.7 x what 64 spheres did, profiles/r05_generality.txt): every sphere, and every cube that is neither a wall nor binned.  Their
-    // bounding balls are swept per lane from a packed table (ptk::SphereCull) instead of being visited one by one by the whole wave.
-    std::vector<char> swept(ngeoms, 0);
-    int nswept = 0, nsweptCubes = 0;
-    for (int i = 0; i < ngeoms; ++i) {
-        const bool smallCube = geoms[i].type == PT_CUBE && !hg[i].binned && (hg[i].flags & 28) == 0 && std::isfinite(hg[i].cullR2);
-        swept[i] = geoms[i].type == PT_SPHERE || smallCube;
-        nswept += swept[i];
+    if (S.ldsBytes > 64 * 1024) {
+        HIPCHECK(hipFuncSetAttribute(S.kernFirst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsBytes));
+        HIPCHECK(hipFuncSetAttribute(S.kernNext, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsBytes));
     }
-    R().many = nswept > kBinMax;
-    if (R().many && ngeoms > 65535) return fail(PT_ERR_INVALID, "pt_init: more than 65535 primitives");
-    if (!R().many) std::fill(swept.begin(), swept.end(), 0);
-    for (int i = 0; i < ngeoms; ++i)
-        if (swept[i] && geoms[i].type == PT_CUBE) {
-            ++nsweptCubes;
-            hg[i].flags |= 64;                        // (bit 6: a swept cube -- the camera-ray bounce lists it like a sphere)
-            hg[i].cullFlags |= 64;
-        }
-    R().sweptCubes = nsweptCubes > 0;
-    if (nsweptCubes) PTCHECK(R().dgeoms.upload(hg));
-    if (R().many) {        // the later bounces take the swept primitives from a packed copy of their culling data (ptk::SphereCull)
-        std::vector<SphereCull> sc;
-        for (int i = 0; i < ngeoms; ++i)
-            if (swept[i]) {
-                SphereCull e;
-                memset(&e, 0, sizeof e);
-                for (int a = 0; a < 3; ++a) e.centre[a] = hg[i].centre[a];
-                e.cullR2 = hg[i].cullR2;
-                e.cullK = hg[i].cullK + kUnitDirSlack;      // (the sweep's direction is normalised approximately: sphereHalfLineExcess)
-                e.geom = i;
-                sc.push_back(e);
-            }
-        // the K |oc|^2 term of the certificate folded into the sweep's direction (ptd::sphereHalfLineExcessScaled): one factor for the
-        // scene, from its largest K, and every threshold multiplied by its square -- both rounded upwards (the conservative side)
-        double kmax = 0.0;
-        for (const SphereCull &e : sc) kmax = std::max(kmax, (double)e.cullK);
-        const float sdir = std::nextafter((float)std::sqrt(1.0 / (1.0 - kmax)), INFINITY);
-        k.sphDirScale = sdir;
-        for (SphereCull &e : sc)
-            if (std::isfinite(e.cullR2)) e.cullR2 = std::nextafter((float)((double)e.cullR2 * (double)sdir * (double)sdir), INFINITY);
-        // two spatial CLUSTERS (scenes without meshes, whose second candidate bit is free): build_sphere_clusters
-        k.sphN0 = 0; k.sphOMax = 0.0f;
-        for (int g = 0; g < 2; ++g) for (int q = 0; q < 8; ++q) k.sphBox[g][q] = 0.0f;
-        if (meshRecs.empty()) {
-            std::vector<int> binned(k.binGeom, k.binGeom + k.nBinned);
-            build_sphere_clusters(geoms, ngeoms, hg, binned, sc, k.sphN0, k.sphOMax, k.sphBox);
-        }
-        if (k.sphOMax <= 0.0f) { k.sphN0 = 0; k.sphOMax = -1.0f; }      // no clusters: no certificate is issued, every tile sweeps the whole table
-        else if (k.nWalls > 0) {
-            // with the spheres behind candidate bits too, a survivor whose certificates leave no wall, no binned primitive and no cluster has
-            // nothing left to hit (KParams::allClassified) -- when there is no primitive of another kind
-            k.allClassified = 1;
-            for (int i = 0; i < ngeoms; ++i)
-                if (!hg[i].binned && (hg[i].flags & 28) == 0 && !swept[i]) k.allClassified = 0;
-        }
-        if (sc.size() % 2) sc.push_back(sc.back());      // (two per scalar load; testing a sphere twice changes nothing)
-        // Hundreds of swept primitives (round 6): the flat sweep of the later bounces is linear in their number (512 spheres: 3.5 x the time of 64).
-        // The table then comes in spatial groups of kSphGroupSize with a bounding ball each, and the later bounces take instantiations of their
-        // own (k_bounce<..., GROUPS>: two-level sweep, no scene table in LDS).  PT_AMD_GROUPS=0 / 1: never / whenever possible (experiments, tests).
-        k.nSphGroups = 0; k.grpN0 = 0; k.grpOMax = 0.0f; k.grpLds = 0;
-        std::vector<SphereCull> groups;
-        {
-            const char *ge = getenv("PT_AMD_GROUPS");
-            // (textured scenes never: the grouped sweep is the ungrouped one's result, bit for bit, and the TEX forms leave it out)
-            R().grouped = meshRecs.empty() && !R().tex && (ge ? atoi(ge) != 0 : nswept >= kGroupedMin);
-            if (R().grouped) {
-                int n0 = k.sphN0;
-                const double ob = scene_origin_bound(geoms, ngeoms, hg);
-                build_sphere_groups(sc, n0, ob, sdir, groups, k.grpN0);
-                k.sphN0 = n0;
-                k.nSphGroups = (int)(sc.size() / (size_t)kSphGroupSize);
-                k.grpOMax = std::nextafter((float)ob, 0.0f);
-                k.grpLds = (int)sc.size() <= kGroupLdsMax ? 1 : 0;
-                PTCHECK(R().dSphGroups.upload(groups));
-            }
-        }
-        k.nSphCull = (int)sc.size();
-        PTCHECK(R().dSphCull.upload(sc));
-        // The tables a sphere-heavy workgroup stages in LDS -- the compact hit records, the cubes' face frames, the spheres' matrix rows,
-        // the sweep's entry -> primitive map -- as ONE image in the kernel's own layout (k_bounce: S_GEOMHIT_SMALL .. behind S_SPH), so that
-        // the prologue is a straight copy of 16-byte words: gathering them field by field from the primitives took ~30 dependent
-        // round trips, 28 us at the head of every launch of C5 (profiles/timeline_phases.py: 62 k cycles against Cornell's 10 k).
-        {
-            const size_t hitB = manyHitBytes(ngeoms), frameB = (size_t)k.nCubes * 54 * sizeof(float) + manyFramePad(k.nCubes);
-            // (scenes of hundreds of primitives: the matrix rows -- 112 B per primitive -- stay in global memory, KParams::ldsRowFloats = 0; with
-            // them a workgroup of the 518-primitive scene took 103 KB of LDS, one per CU.  The limit: what four workgroups per CU leave each.)
-            const size_t rowsAll = (size_t)ngeoms * kSphRowFloats * sizeof(float);
-            const size_t ldsWithRows = sizeof(MaterialDev) * nmats + (size_t)miscWords(kClsMax) * sizeof(uint32_t) + hitB + frameB + rowsAll + (size_t)kListMax * kBlock * sizeof(uint16_t);
-            const bool rowsInLds = ldsWithRows <= 40 * 1024 && !R().grouped && !env_flag("PT_AMD_ROWS_GLOBAL");   // (the variable: tests only)
-            k.ldsRowFloats = rowsInLds ? ngeoms * kSphRowFloats : 0;
-            const size_t rowB = rowsInLds ? rowsAll : 0, mapB = ((size_t)k.nSphCull + 7) / 8 * 8 * sizeof(uint16_t);
-            // (+ 64 bytes: behind the last cube's frames a row of NaNs -- what k_bounce<..., GROUPS>, which reads the frames from this image in
-            // global memory, selects for a cube hit without an exit slab, as the other kernels select their NaN row in LDS)
-            std::vector<unsigned char> blob(hitB + frameB + rowB + mapB + 64, 0);
-            std::vector<float> rowsGlobal(rowsInLds ? 0 : (size_t)ngeoms * kSphRowFloats, 0.0f);
-            GeomHitSmall *hs = reinterpret_cast<GeomHitSmall *>(blob.data());
-            float *fr = reinterpret_cast<float *>(blob.data() + hitB);
-            float *rows = rowsInLds ? reinterpret_cast<float *>(blob.data() + hitB + frameB) : rowsGlobal.data();
-            uint16_t *map = reinterpret_cast<uint16_t *>(blob.data() + hitB + frameB + rowB);
-            for (int g = 0; g < ngeoms; ++g) {
-                const GeomDev &G = hg[g];
-                memcpy(hs[g].nm, G.invT, sizeof hs[g].nm);
-                hs[g].material = G.material; hs[g].type = G.type; hs[g].frame = G.type == 1 ? (int)G.frameSlot : 0;
-                if (G.type == 1) memcpy(fr + (size_t)G.frameSlot * 54, G.cubeFrame, 54 * sizeof(float));
-                float *r = rows + (size_t)g * kSphRowFloats;
-                memcpy(r, G.inv, 12 * sizeof(float)); memcpy(r + 12, G.xf, 12 * sizeof(float)); memcpy(r + 24, G.invZ, 3 * sizeof(float));
-            }
-            for (int i = 0; i < k.nSphCull; ++i) map[i] = (uint16_t)sc[i].geom;
-            if (R().grouped) {
-                const float qnan = std::nanf("");
-                for (int q = 0; q < 9; ++q) memcpy(blob.data() + hitB + (size_t)k.nCubes * 54 * sizeof(float) + q * sizeof(float), &qnan, sizeof qnan);
-            }
-            PTCHECK(R().dGeomHit.upload(blob));      // (in place of the hit records uploaded above)
-            if (!rowsInLds) PTCHECK(R().dRows.upload(rowsGlobal));
-        }
-    }
-    {   // Later bounces: which primitives a tile of queue class c looks at.  Class bit 3 = its paths may hit a binned primitive;
-        // bits 0-2 in a scene with walls = the one wall they can still hit (6: any, 7: none), else the direction octant.
-        std::vector<int> idx;
-        const int ncls = (R().mesh || R().many) ? kClsMax : kCls;                 // (mesh and sphere-heavy scenes: two candidate bits, 32 classes)
-        for (int c = 0; c < kClsMax; ++c) {
-            k.classOff[c] = (int)idx.size();
-            if (c >= ncls) continue;
-            const int small = c >> 3;                                          // candidate bits: which groups of binned primitives
-            const int wall = k.nWalls > 0 ? (c & 7) : 6;
-            for (int i = 0; i < ngeoms; ++i) {
-                if (swept[i]) continue;                                          // swept from their packed culling data
-                if (hg[i].binned) {
-                    int grp = 0;
-                    for (int b = 0; b < k.nBinned; ++b)
-                        if (k.binGeom[b] == i) grp = binGroup[b];
-                    if (!((small >> grp) & 1)) continue;
-                }
-                const int w = (hg[i].flags >> 2) & 7;                          // 1 + index among the walls, 0: not one
-                if (w != 0 && wall != 6 && w != wall + 1) continue;
-                idx.push_back(i);
-            }
-        }
-        k.classOff[kClsMax] = (int)idx.size();
-        // camera rays: the per-row primitive lists (build_camera_cull)
-        if (!cc.rowOff.empty()) {
-            PTCHECK(R().dRowOff.upload(cc.rowOff));
-            PTCHECK(R().dRowIdx.upload(cc.rowIdx));
-        }
-        // ... and, where the camera-ray instantiation can take it (pinhole, no meshes -- their walk shares the row bands' index space,
-        // BounceArgs::meshHit -- and not the sphere-heavy one), the packed work list in place of the row bands: the tiles' index space of
-        // one iteration is then the list (KParams::nLocalPad), and every pixel outside it is tallied at once (KParams::firstSkipped)
-        const bool listOff = env_flag("PT_AMD_NO_CAMERA_LIST");   // (the variable: tests only)
-        CameraList cl;
-        if (!listOff && !R().dof && !R().mesh && !R().many &&
-            build_camera_list(cc, Wd, H, o.shard_rank, o.shard_count, k.nLocalPad, cl) && !cl.pix.empty()) {
-            k.nLocalPad = (int)cl.pix.size();
-            k.firstSkipped = (int)((long long)R().nLocal - cl.listed);
-            PTCHECK(checked_magic((uint32_t)k.nLocalPad, k.magicN, k.shiftN));
-            PTCHECK(R().dCamPix.upload(cl.pix));
-            PTCHECK(R().dCamWave.upload(cl.wave));
-            PTCHECK(R().dCamSigIdx.upload(cl.sigIdx));
-        }
-        if (!meshRecs.empty()) {
-            // the mesh walks (k_mesh_walk) look at the meshes alone: the classes' lists, one list of all, the rows' lists (pairs as rowIdx's)
-            std::vector<int> w;
-            for (int c = 0; c < kClsMax; ++c) {
-                R().walkClassOff[c] = (int)w.size();
-                for (int e = k.classOff[c]; e < (c + 1 < kClsMax ? k.classOff[c + 1] : (int)idx.size()); ++e)
-                    if (hg[idx[e]].flags & 32) w.push_back(idx[e]);
-            }
-            R().walkClassOff[kClsMax] = (int)w.size();
-            R().walkAll0 = (int)w.size();
-            for (int i = 0; i < ngeoms; ++i)
-                if (hg[i].flags & 32) {
-                    if (w.size() - (size_t)R().walkAll0 >= 32767) return fail(PT_ERR_INVALID, "pt_init: more than 32767 meshes");
-                    hg[i].frameSlot = (short)(w.size() - (size_t)R().walkAll0);     // (a mesh's ordinal: its row of the walk's LDS table)
-                    w.push_back(i);
-                }
-            R().walkAll1 = (int)w.size();
-            PTCHECK(R().dgeoms.upload(hg));
-            {   // the walk's rows, one per mesh in the order of their ordinals (ptk::WalkMesh)
-                const int nm = R().walkAll1 - R().walkAll0;
-                std::vector<WalkMesh> rowsW((size_t)nm);
-                for (int q = 0; q < nm; ++q) {
-                    const GeomDev &G = hg[(size_t)w[(size_t)R().walkAll0 + q]];
-                    WalkMesh &r = rowsW[(size_t)q];
-                    memcpy(r.inv, G.inv, sizeof r.inv); memcpy(r.invZ, G.invZ, sizeof r.invZ);
-                    r.root = G.meshRoot;
-                    memcpy(r.xf, G.xf, sizeof r.xf); memcpy(r.camObj, G.camObj, sizeof r.camObj);
-                    r.stride = G.meshStride;
-                }
-                PTCHECK(R().dWalkMeshRows.upload(rowsW));
-                const bool forceGlobal = env_flag("PT_AMD_WALK_ROWS_GLOBAL");      // tests only
-                R().walkMeshLds = (nm <= kWalkMeshLdsMax && !forceGlobal) ? nm : 0;
-            }
-            if (!cc.rowOff.empty()) {
-                if (w.size() % 2) w.push_back(0);                  // (the rows' entries are pairs: offsets count pairs from the array's start)
-                std::vector<int> ro(cc.rowOff.size());
-                for (size_t y = 0; y + 1 < cc.rowOff.size(); ++y) {
-                    ro[y] = (int)(w.size() / 2);
-                    for (int e = cc.rowOff[y]; e < cc.rowOff[y + 1]; ++e)
-                        if (hg[cc.rowIdx[2 * e]].flags & 32) { w.push_back(cc.rowIdx[2 * e]); w.push_back(cc.rowIdx[2 * e + 1]); }
-                }
-                ro[cc.rowOff.size() - 1] = (int)(w.size() / 2);
-                PTCHECK(R().dWalkRowOff.upload(ro));
-            }
-            PTCHECK(R().dWalkIdx.upload(w));
-        }
-        if (idx.empty()) idx.push_back(0);
-        PTCHECK(R().dClassIdx.upload(idx));
-    }
-    const size_t ldsFixed = sizeof(MaterialDev) * nmats + (size_t)miscWords((R().mesh || R().many) ? kClsMax : kCls) * sizeof(uint32_t) +
-                            (R().many ? manyHitBytes(ngeoms) + (size_t)k.nCubes * 54 * sizeof(float) + manyFramePad(k.nCubes) +
-                                          (size_t)k.ldsRowFloats * sizeof(float)
-                                    : sizeof(GeomHitDev) * ngeoms);
-    // (sphere-heavy scenes: the camera-ray launch keeps the lanes' candidate lists behind the tables, the later ones only the sweep's
-    // entry -> primitive map -- 4 KB less, which is what their seventh workgroup per CU needs)
-    // (... and, behind the map, the pooled pass's pair descriptors: [kWaves][64] words)
-    const size_t sphMapBytes = ((size_t)k.nSphCull + 7) / 8 * 8 * sizeof(uint16_t), pairBytes = (size_t)kBlock * sizeof(uint32_t);
-    k.pairOff = (int)(ldsFixed + sphMapBytes);
-    R().ldsBytes = ldsFixed + (R().many ? std::max((size_t)kListMax * kBlock * sizeof(uint16_t), sphMapBytes + pairBytes) : 0);
-    R().ldsBytesNext = (R().many && !R().mesh) ? ldsFixed + sphMapBytes + pairBytes : 0;
-    if (R().grouped && !R().dof)      // (the camera-ray bounce of a grouped scene: the materials and the lanes' candidate lists)
-        R().ldsBytes = sizeof(MaterialDev) * nmats + (size_t)miscWords(kClsMax) * sizeof(uint32_t) + (size_t)kListMax * kBlock * sizeof(uint16_t) + 16;
-    if (R().grouped)       // (the later bounces stage the materials and nothing else of the scene)
-    {
-        // (... and, behind them, the lanes' parked candidates: KParams::pairOff, [kCandPairs][kBlock] words)
-        const size_t members = sizeof(MaterialDev) * nmats + (size_t)miscWords(kClsMax) * sizeof(uint32_t) + (k.grpLds ? ((size_t)k.nSphCull * 18 + 15) / 16 * 16 : 0);
-        k.pairOff = (int)members;
-        R().ldsBytesNext = members + (size_t)kCandPairs * kBlock * sizeof(uint32_t) + 16;
-    }
-    k.meshStackOff = 0;
-    if (R().mesh) {        // (the lanes' stacks of far children belong to the walk's own launches: k_mesh_walk)
-        R().ldsWalk = walkLdsBytes(meshStackNeed, R().walkMeshLds);
-        if (R().ldsWalk > 160 * 1024) return fail(PT_ERR_INVALID, "pt_init: a mesh's hierarchy needs %d stack levels (%zu B of LDS for the lanes' stacks)", meshStackNeed, R().ldsWalk);
-    }
-    if (R().ldsBytesNext == 0) R().ldsBytesNext = R().ldsBytes;
-    if (R().ldsBytes > 160 * 1024) return fail(PT_ERR_INVALID, "pt_init: scene does not fit the 160 KiB LDS (%zu B)", R().ldsBytes);
-    if (nmats >= 4096) return fail(PT_ERR_INVALID, "pt_init: more than 4095 materials");      // (TileArgs::hot holds nmats in 12 bits)
-    PTCHECK(resolve_bounce_kernel(true, &R().kernFirst));
-    PTCHECK(resolve_bounce_kernel(false, &R().kernNext));
-    if (R().ldsBytes > 64 * 1024) {
-        HIPCHECK(hipFuncSetAttribute(R().kernFirst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsBytes));
-        HIPCHECK(hipFuncSetAttribute(R().kernNext, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsBytes));
-    }
-    if (R().mesh)
+    if (S.mesh)
         for (int first = 0; first < 2; ++first) {
-            const void *kw = walk_kernel(first != 0, first && R().dof);
-            if (R().ldsWalk > 64 * 1024) HIPCHECK(hipFuncSetAttribute(kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)R().ldsWalk));
-            PTCHECK(persistent_grid(kw, R().ldsWalk, true, first ? &R().gridWalkFirst : &R().gridWalk));
+            const void *kw = walk_kernel(first != 0, first && S.dof);
+            if (S.ldsWalk > 64 * 1024) HIPCHECK(hipFuncSetAttribute(kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsWalk));
+            PTCHECK(persistent_grid(kw, S.ldsWalk, true, first ? &S.gridWalkFirst : &S.gridWalk));
         }
     for (int first = 0; first < 2; ++first) {
-        int &grid = first ? R().gridFirst : R().grid;
-        PTCHECK(persistent_grid(first ? R().kernFirst : R().kernNext, first ? R().ldsBytes : R().ldsBytesNext, false, &grid));
-        if (grid > R().numTilesMax) grid = R().numTilesMax;
+        int &grid = first ? S.gridFirst : S.grid;
+        PTCHECK(persistent_grid(first ? S.kernFirst : S.kernNext, first ? S.ldsBytes : S.ldsBytesNext, false, &grid));
+        if (grid > S.numTilesMax) grid = S.numTilesMax;
         grid = (grid / kSub) * kSub;      // T % kSub == blockIdx % kSub for every tile T of a workgroup (kSub: a multiple of the mesh scenes' 4 too)
         if (grid < kSub) grid = kSub;
     }
@@ -1837,26 +1176,27 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // odd tile count per row), or the kernel rotates the k-th tile of a workgroup k bands to the right inside its row,
     // which needs a grid that is a multiple of the tiles per row (k_bounce<true, .>).
     // (the packed work list of camera rays has no column bands: nothing to rotate)
-    R().prm.tilesPerRow = 0;
-    if (R().prm.Wp / kBlock > 1 && R().dCamPix.p == nullptr) {
-        const int perRow = R().prm.Wp / kBlock;
+    const KParams &k = S.prm;
+    S.prm.tilesPerRow = 0;
+    if (k.Wp / kBlock > 1 && S.dCamPix.p == nullptr) {
+        const int perRow = k.Wp / kBlock;
         auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
         if (gcd(perRow, kSub) == 1) {
-            for (int tries = 0; tries < 64 && R().gridFirst > kSub && gcd(R().gridFirst, perRow) != 1; ++tries) R().gridFirst -= kSub;
+            for (int tries = 0; tries < 64 && S.gridFirst > kSub && gcd(S.gridFirst, perRow) != 1; ++tries) S.gridFirst -= kSub;
         } else {
             const int unit = perRow / gcd(perRow, kSub) * kSub;        // lcm(perRow, kSub)
-            if (R().gridFirst >= 4 * unit) {
-                R().gridFirst = R().gridFirst / unit * unit;
-                R().prm.tilesPerRow = perRow;
+            if (S.gridFirst >= 4 * unit) {
+                S.gridFirst = S.gridFirst / unit * unit;
+                S.prm.tilesPerRow = perRow;
             }
         }
     }
     if (env_flag("PT_AMD_VERBOSE"))       // experiments: what pt_init decided
         fprintf(stderr, "pt_init: lds %zu / %zu B, grid %d / %d, mesh %d many %d plain %d, binned %d walls %d (slots %d, planes %d) allClassified %d, sphCull %d (cluster 0: %d) omax %g\n",
-                R().ldsBytes, R().ldsBytesNext, R().gridFirst, R().grid, (int)R().mesh, (int)R().many, (int)R().plain, k.nBinned, k.nWalls, k.nSlotWalls, k.nPlaneWalls, k.allClassified, k.nSphCull,
+                S.ldsBytes, S.ldsBytesNext, S.gridFirst, S.grid, (int)S.mesh, (int)S.many, (int)S.plain, k.nBinned, k.nWalls, k.nSlotWalls, k.nPlaneWalls, k.allClassified, k.nSphCull,
                 k.sphN0, (double)k.sphOMax);
     HIPCHECK(hipDeviceSynchronize());
-    R().init = true;
+    S.init = true;
     g_err.clear();
     return PT_OK;
 }

@@ -125,14 +125,31 @@ int pt_test_bounce_form(uint32_t state_bits, uint32_t *form_bits) {
     return PT_OK;
 }
 
-// (host only) the state pt_init left in this library's renderer, in pt_test_bounce_form's bit order with `first` (bit 0) clear
+// a plan's state in pt_test_bounce_form's bit order with `first` (bit 0) clear
+uint32_t plan_state_bits(const PlanScalars &p) {
+    const bool s[9] = {false, p.dof, p.many, p.sweptCubes, p.mesh, p.grouped, p.tex, p.bump, p.plain};
+    uint32_t bits = 0u;
+    for (int i = 0; i < 9; ++i) bits |= (s[i] ? 1u : 0u) << i;
+    return bits;
+}
+
+// (host only) the state pt_init left in this library's renderer: the plan it stored
 int pt_test_renderer_state(uint32_t *state_bits) {
     if (!state_bits) return fail(PT_ERR_INVALID, "pt_test_renderer_state: bad argument");
     if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_test_renderer_state before pt_init");
-    const bool s[9] = {false, R().dof, R().many, R().sweptCubes, R().mesh, R().grouped, R().tex, R().bump, R().plain};
-    uint32_t bits = 0u;
-    for (int i = 0; i < 9; ++i) bits |= (s[i] ? 1u : 0u) << i;
-    *state_bits = bits;
+    *state_bits = plan_state_bits(R());
+    return PT_OK;
+}
+
+// (host only) what pt_init would plan for the scene -- its arguments, and the meshes, textures and bindings registered with this library --
+// or its refusal: plan_scene, no device
+int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
+                       PtTestPlanSummary *out) {
+    if (!out) return fail(PT_ERR_INVALID, "pt_test_scene_plan: bad argument");
+    ScenePlan p;
+    PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings}, p));
+    *out = PtTestPlanSummary{plan_state_bits(p), p.prm.nBinned, p.prm.nWalls, p.prm.nSphCull, p.prm.nSphGroups, p.prm.nLocalPad, p.prm.firstSkipped, p.poolChunks,
+                             (uint64_t)p.ldsBytes, (uint64_t)p.ldsBytesNext};
     return PT_OK;
 }
 

@@ -3,7 +3,10 @@ allocations those owners hold (pt_test_live_device_buffers).  Renderers that use
 height maps and a lens; the swept, grouped and row tables of a sphere-heavy scene; the camera list -- are initialised one over the other
 as the reference restarts (Free -> Init inside pt_init, no pt_free between), and nothing may be left behind: the same scene holds the same
 number of buffers and renders the same bits the second time, pt_free brings the count to zero -- after the denoiser's lazily allocated
-buffers too, and after a pt_init that was refused with its tables already allocated.  Every refusal here is a host-side argument check."""
+buffers too.  A pt_init that is refused touches nothing: pt_init plans the scene on the host (csrc/pt_scene_plan.h) before it releases or
+allocates anything, so the renderer that was there keeps its buffers, goes on rendering the same bits, and its state is the plan's.
+Every refusal here is a host-side argument check."""
+import ctypes as C
 import os
 import types
 
@@ -88,7 +91,7 @@ def scenes(gpu, tmp_path_factory):
         out[name] = sc
     assert len(out["a"].meshes) == 1 and len(out["a"].mesh_uvs) == 1 and len(out["a"].textures) == 2
     assert out["a"].geom_textures[6] == 0 and out["a"].geom_bumps[6] == 1 and int((out["b"].geoms["type"] == 0).sum()) == 16
-    # one sphere and 4096 materials: refused by pt_init's checks of the scene's size, which come after the tables have been built
+    # one sphere and 4096 materials: refused by pt_init's checks of the scene's size, the last ones of its plan
     sph = out["b"].geoms[out["b"].geoms["type"] == 0][:1].copy()
     sph["materialid"] = 0
     out["refused"] = types.SimpleNamespace(geoms=sph, materials=np.repeat(out["b"].materials[:1], 4096), camera=out["b"].camera.copy(),
@@ -130,13 +133,32 @@ def test_restarts_leave_no_device_buffer_behind(gpu, scenes, monkeypatch):
 def test_a_refused_init_leaves_no_device_buffer_behind(gpu, scenes):
     live = gpu.test_lib().pt_test_live_device_buffers
     with gpu.renderer_from_test_library():
-        c1, _ = _frame(gpu, scenes["c"])
+        gpu.pathtraceInit(scenes["c"], traceDepth=DEPTH)                 # iterations 1 and 2, uninterrupted
+        gpu.pathtrace(None, 0, 1, readback=False)
+        gpu.pathtrace(None, 0, 2, readback=False)
+        want = gpu.readback(W * H).view(np.uint32).copy()
+        c1, _ = _frame(gpu, scenes["c"])                                  # ... and with a refused pt_init between them
+        held = live()
         with pytest.raises(gpu.PtError, match="pt_amd error -1"):        # PT_ERR_INVALID
             gpu.pathtraceInit(scenes["refused"], traceDepth=DEPTH)
-        assert live() > 0                               # (refused late: what it had allocated is still held ...)
-        gpu.pathtraceFree()
-        assert live() == 0                              # (... until pt_free)
-        c2, _ = _frame(gpu, scenes["c"])
-        assert np.array_equal(c1, c2)
+        assert live() == held > 0                       # (nothing allocated, nothing released)
+        gpu.pathtrace(None, 0, 2, readback=False)       # (the renderer that was there is still initialised)
+        c2 = gpu.readback(W * H).view(np.uint32)
+        assert c1.any() and not np.array_equal(c1, c2) and np.array_equal(c2, want)
         gpu.pathtraceFree()
         assert live() == 0
+
+
+def test_the_renderer_state_is_the_plans(gpu, scenes, monkeypatch):
+    state = C.c_uint32(0)
+    with gpu.renderer_from_test_library():
+        for name, env, kw in (("a", None, dict(lens_radius=0.1, focal_distance=9.0)), ("a", None, {}), ("b", None, {}), ("b", "PT_AMD_GROUPS", {}),
+                              ("c", None, {})):
+            if env:
+                monkeypatch.setenv(env, "1")
+            gpu.pathtraceInit(scenes[name], traceDepth=DEPTH, **kw)
+            assert gpu.test_lib().pt_test_renderer_state(C.byref(state)) == 0, gpu.test_lib().pt_last_error()
+            assert state.value == gpu.scene_plan(scenes[name], traceDepth=DEPTH, **kw).state_bits, (name, env, kw)
+            if env:
+                monkeypatch.delenv(env)
+        gpu.pathtraceFree()
