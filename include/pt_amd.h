@@ -100,7 +100,9 @@ enum {
     PT_FLAG_DIRECT_LIGHTING = 4  /* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
-                                    that ray hits (traceDepth + 1 launches; traceDepth <= PT_MAX_DEPTH - 1) */
+                                    that ray hits (traceDepth + 1 launches; traceDepth <= PT_MAX_DEPTH - 1).  A mesh is an
+                                    emissive primitive when its object's material or ANY of its faces' materials emits; the
+                                    point is drawn in the object-space bounding box of ALL its vertices either way */
 };
 
 typedef struct PtOptions {
@@ -174,8 +176,16 @@ typedef struct PtMesh {
      *              of a hit is then the barycentric blend n0 (1 - u - v) + n1 u + n2 v with the hit's own (u, v), turned to the side the
      *              counter-clockwise face normal points to and normalised (a blend of length zero keeps the face normal); everything
      *              else -- which side is "outside", the hit point, the invTranspose map to world space -- as for flat shading.
-     *   materials  ntris scene materials, one per face (an OBJ's `usemtl <k>`); -1 = the object's own.  pt_init fails with
-     *              PT_ERR_INVALID on an id >= nmats. */
+     *              The blended normal is the one the hit is SHADED with: reflection and its SPECEX lobe, refraction and Schlick's cosine,
+     *              the diffuse hemisphere, the direct-lighting cosine, the denoiser's guide normal -- and the new ray's origin, which sits
+     *              0.001 along it (against it for a refracted ray) from the hit point.  Which side of the surface the ray came from, and
+     *              with it eta, stays the geometric question.  The new origin lies on the geometric side its branch names as long as
+     *              0.001 (Ns . N) exceeds the 0.0001 object-space step the hit point is taken short of the surface, seen along N
+     *              (at most 0.0001 x the largest scale): normals bent by less than ~70 degrees on objects of scale <= 3.
+     *   materials  ntris scene materials, one per face (an OBJ's `usemtl <k>`); -1 = the object's own.  The FACE's material is the one
+     *              that scatters the path, ends it (an emissive face, which adds (colour x its RGB) x its emittance) or lets it go on
+     *              (a face without emittance on an emissive object).
+     *              pt_init fails with PT_ERR_INVALID on an id >= nmats. */
     const float *normals;   /* or NULL: flat shading */
     const int32_t *materials;   /* or NULL: every face takes the object's material */
 } PtMesh;

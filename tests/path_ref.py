@@ -4,7 +4,8 @@ ramp height map tilts the hit to.  Written from the geometry -- the sphere of ra
 triangles, each through the primitive's inverseTransform -- and from the documented semantics; nothing of the library, the oracle or
 texture_ref.py is called.  No random numbers, no sampling, no compaction: which branch a path took is read from its new state.
 
-A `scene` is any object with geoms, materials (the renderer's structured arrays), meshes {geom: (ntris, 9)}, mesh_uvs {geom: (ntris, 6)}.
+A `scene` is any object with geoms, materials (the renderer's structured arrays), meshes {geom: (ntris, 9)}, mesh_uvs {geom: (ntris, 6)} and,
+optionally, mesh_normals {geom: (ntris, 9)} and mesh_materials {geom: (ntris,)}.
 A classification float64 cannot settle against a float32 renderer is flagged `ambiguous`, never guessed."""
 import types
 
@@ -52,7 +53,7 @@ def _cube(ro, rd, tmin):
     return t, inside, shaky
 
 
-def _mesh(ro, rd, tris):
+def _mesh(ro, rd, tris, tmin=0.0):
     """nearest two-sided triangle per ray: (t, triangle, (bu, bv)), bu the weight of corner 1 and bv of corner 2"""
     v0, e1, e2 = tris[:, 0:3], tris[:, 3:6] - tris[:, 0:3], tris[:, 6:9] - tris[:, 0:3]
     p = np.cross(rd[:, None, :], e2[None])
@@ -65,19 +66,26 @@ def _mesh(ro, rd, tris):
         bv = f * _dot(qv, rd[:, None, :])
         t = f * _dot(qv, e2[None])
     ok = (det != 0) & (bu >= 0) & (bv >= 0) & (bu + bv <= 1) & (t > 0)
+    traw = t
     t = np.where(ok, t, np.inf)
     k = t.argmin(1)
     i = np.arange(len(ro))
-    return t[i, k], k, np.stack([bu[i, k], bv[i, k]], 1)
+    # (a triangle met within tmin of the origin, before or behind it: float32 may put that root on the other side of zero)
+    shaky = ((det != 0) & (bu >= 0) & (bv >= 0) & (bu + bv <= 1) & (np.abs(traw) < tmin)).any(1) if tmin else np.zeros(len(ro), bool)
+    return t[i, k], k, np.stack([bu[i, k], bv[i, k]], 1), shaky
 
 
 def cast(scene, o, d, tmin=1e-4, near=1e-4, edge=2 * OFFSET, inside_cube=False):
     """Rays (o, d) (n, 3) against every primitive.  Returns per ray: prim (-1: nothing), t, gap (the runner-up's distance relative to the
     nearest, (t2 - t1) / t1), P (world), q (object space, SHORT of the surface as the renderer's), axis / sign (a cube's face: the axis of largest |q| and its sign), tri / bary
     (a mesh's triangle and barycentrics), Ng (the outward geometric normal, world), outside, N (Ng turned to the ray's side, as the hit is
-    shaded), short (the world vector by which the renderer's hit point stops short of P) and ambiguous: two primitives within `near` of
-    each other, a root within `tmin` of the origin, a grazed sphere, a cube hit within `edge` (world units) of an edge, a triangle hit within
-    1e-4 (barycentric) of an edge, an origin inside a cube (kept with `inside_cube`: the hit is the exit face, N the inward normal there)."""
+    shaded), Ns (the SHADING normal: N, or for a mesh with scene.mesh_normals the blended vertex normal, turned to the face's side, taken to
+    world space and turned to the ray's side as N is; `blended` marks those hits), mat (the scene material: scene.mesh_materials' for the
+    triangle where that is >= 0, else the object's), short (the world vector by which the renderer's hit point stops short of P) and
+    ambiguous: two primitives within `near` of each other, a root within `tmin` of the origin (a triangle's too: a ray that re-enters the
+    surface it left), a grazed sphere, a cube hit within `edge` (world units) of an edge, a triangle hit within 1e-4 (barycentric) of an
+    edge, a blended normal shorter than 1e-3 or within 1e-3 (cosine) of square to its face, an origin inside a cube (kept with `inside_cube`:
+    the hit is the exit face, N the inward normal there)."""
     o, d = np.asarray(o, np.float64).reshape(-1, 3), np.asarray(d, np.float64).reshape(-1, 3)
     n, ng = len(o), len(scene.geoms)
     i = np.arange(n)
@@ -95,7 +103,7 @@ def cast(scene, o, d, tmin=1e-4, near=1e-4, edge=2 * OFFSET, inside_cube=False):
         elif kind == 1:
             T[g], inside[g], shaky[g] = _cube(ro, rd, tmin)
         else:
-            T[g], tri[g], bary[g] = _mesh(ro, rd, np.asarray(scene.meshes[g], np.float64).reshape(-1, 9))
+            T[g], tri[g], bary[g], shaky[g] = _mesh(ro, rd, np.asarray(scene.meshes[g], np.float64).reshape(-1, 9), tmin)
         with np.errstate(all="ignore"):
             Q[g] = ro + np.where(np.isfinite(T[g]), T[g], 0)[:, None] * rd
     order = np.argsort(T, 0)
@@ -132,11 +140,39 @@ def cast(scene, o, d, tmin=1e-4, near=1e-4, edge=2 * OFFSET, inside_cube=False):
     Ng = _unit(np.einsum("nji,nj->ni", invs, nobj))                   # (the inverse transpose takes normals to world space)
     outside = np.where(kinds == 2, _dot(Ng, d) < 0, ~inside[prim, i])
     N = np.where(outside[:, None], Ng, -Ng)
+    # the shading normal: a mesh with vertex normals blends them with the hit's barycentrics, turns the blend to the side the counter-clockwise
+    # face normal points to (a blend of length zero: the face normal) and takes it to world space; which side of the surface the ray is on
+    # stays the GEOMETRIC question above (include/pt_amd.h, PtMesh: "everything else as for flat shading")
+    Ns, blended = N.copy(), np.zeros(n, bool)
+    normals = getattr(scene, "mesh_normals", None) or {}
+    for g in np.unique(prim[mesh]):
+        if normals.get(g) is None:
+            continue
+        m = mesh & (prim == g)
+        n9 = np.asarray(normals[g], np.float64).reshape(-1, 9)[ktri[m]]
+        bu, bv = kb[m, 0:1], kb[m, 1:2]
+        blend = n9[:, 0:3] * (1 - bu - bv) + n9[:, 3:6] * bu + n9[:, 6:9] * bv
+        face = nobj[m]
+        along = _dot(blend, face)
+        blend = np.where((along < 0)[:, None], -blend, blend)
+        size = np.linalg.norm(blend, axis=1)
+        amb[m] |= (size < 1e-3) | (np.abs(along) < 1e-3 * size * np.linalg.norm(face, axis=1))
+        blend = np.where((size > 0)[:, None], blend, face)
+        w = _unit(np.einsum("nji,nj->ni", invs[m], blend))
+        Ns[m] = np.where(outside[m, None], w, -w)
+        blended[m] = True
+    # the scene material: the face's own (`usemtl`) where it has one, else the object's
+    mat = np.array([int(G["materialid"]) for G in scene.geoms])[prim]
+    for g, fm in (getattr(scene, "mesh_materials", None) or {}).items():
+        m = mesh & (prim == g)
+        own = np.asarray(fm, np.int64)[ktri[m]]
+        mat[m] = np.where(own >= 0, own, mat[m])
     L = np.array([_m(G, "transform")[:3, :3] for G in scene.geoms])[prim]
     short = SHORT * np.einsum("nij,nj->ni", L, _unit(np.einsum("nij,nj->ni", invs, d)))
     prim = np.where(some, prim, -1)
     return types.SimpleNamespace(short=short, prim=prim, kind=np.where(some, kinds, -1), t=t, gap=gap, P=o + np.where(some, t, 0)[:, None] * d, q=q, axis=axis,
-                                 sign=sign, tri=ktri, bary=kb, Ng=Ng, outside=outside, N=N, ambiguous=amb & some, d=d)
+                                 sign=sign, tri=ktri, bary=kb, Ng=Ng, outside=outside, N=N, Ns=Ns, blended=blended & some, mat=np.where(some, mat, -1),
+                                 ambiguous=amb & some, d=d)
 
 
 def take(hit, idx):
@@ -193,7 +229,7 @@ def predict_colour(scene, hit, col, texel, o_new, d_new, Ns=None):
     not within 1e-4, the side of the surface the new origin lies on (+1: the ray's), and how far the new origin lies from where this
     reference puts it, along N: it should sit OFFSET to that side of P - short)."""
     f = np.float32
-    mats = scene.materials[np.array([int(G["materialid"]) for G in scene.geoms])[hit.prim]]
+    mats = scene.materials[hit.mat]
     spec = mats[mats.dtype.names[2]].astype(f)
     mcol = mats["color"].astype(f) * np.asarray(texel, f)
     col = np.asarray(col, f)
@@ -211,7 +247,7 @@ def predict_colour(scene, hit, col, texel, o_new, d_new, Ns=None):
 def emitted(scene, hit, col, texel):
     """what a path that ends on an emitter adds to its pixel: (col * (material.color * texel)) * emittance, in float32"""
     f = np.float32
-    mats = scene.materials[np.array([int(G["materialid"]) for G in scene.geoms])[hit.prim]]
+    mats = scene.materials[hit.mat]
     return (np.asarray(col, f) * (mats["color"].astype(f) * np.asarray(texel, f))) * mats["emittance"].astype(f)[:, None]
 
 

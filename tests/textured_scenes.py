@@ -167,7 +167,7 @@ def ended_on_light(sc, prev, cur, white=False):
     o0, d0, c0, p0 = prev
     gone = np.flatnonzero(~np.isin(p0, cur[3]))
     idx, sub, tex, ci, texel, u, v, out = _classify(sc, o0[gone], d0[gone], white)
-    emit = sc.materials["emittance"][sc.geoms["materialid"][sub.prim]] > 0
+    emit = sc.materials["emittance"][sub.mat] > 0
     keep = emit & ~out
     return p0[gone][idx[keep]], pr.emitted(sc, pr.take(sub, keep), c0[gone][idx[keep]], texel[keep]), tex[keep], ci[keep]
 
