@@ -104,6 +104,14 @@ int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, in
 int pt_test_mesh_intersect(const PtGeom *geom, const float *tris, int ntris, int flat, const float *rays, int n, float *t,
                            float *p3, float *n3, int32_t *outside, int32_t *culled);
 int pt_test_mesh_bvh(const float *tris, int ntris, int octant, uint32_t *units4, int *nrecs, int *stack_need);
+/* pt_test_mesh_intersect with the mesh's attributes and the WINNER's name: `normals` (9 floats per triangle: vertex normals, or NULL: flat
+ * shading) and `mats` (one scene material per triangle, -1 = the object's, or NULL) as PtMesh's; the same outputs, plus tri[i] = the file
+ * index of the triangle that was hit (-1 on a miss) and face_mat[i] = that triangle's own material (-1: it has none, or a miss).  The
+ * index is read off a second walk of the same rays through the same records with word 10 of triangle k set to 1 + k: the walk itself
+ * (ptd::meshIntersectionTest) is the render kernels', unchanged. */
+int pt_test_mesh_intersect2(const PtGeom *geom, const float *tris, const float *normals, const int32_t *mats, int ntris, int flat,
+                            const float *rays, int n, float *t, float *p3, float *n3, int32_t *outside, int32_t *culled, int32_t *tri,
+                            int32_t *face_mat);
 /* certainMiss soundness for a mesh geom: `rays` pseudo-random rays dense in grazes of its bounding ball (origins 1/64 .. 64
  * radii away); *violations = rays the bounding-ball test rejected although the walk hits (must be 0), *hits = rays that hit */
 int pt_test_mesh_cull_sweep(const PtGeom *geom, const float *tris, int ntris, uint64_t seed, int64_t rays, uint64_t *culled,

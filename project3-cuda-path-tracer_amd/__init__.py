@@ -69,7 +69,7 @@ TEST_ABI_SYMBOLS = [
     "pt_debug_trace_paths",
     "pt_test_utilhash", "pt_test_rng", "pt_test_intersect", "pt_test_hemisphere", "pt_test_sincos", "pt_test_reflect_refract",
     "pt_test_slab_quotients", "pt_test_slab_quotients_sweep", "pt_test_box_fast_sweep", "pt_test_sphere_cull_sweep", "pt_test_unscaled_sqrt_sweep",
-    "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_bvh",
+    "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_intersect2", "pt_test_mesh_bvh",
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
@@ -220,6 +220,7 @@ def _bind(L, with_tests):
         L.pt_test_pow.argtypes = [vp, vp, i32, vp]
         L.pt_test_wall_box_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p, u64p]
         L.pt_test_mesh_intersect.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+        L.pt_test_mesh_intersect2.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         L.pt_test_mesh_bvh.argtypes = [vp, i32, i32, vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.pt_test_mesh_cull_sweep.argtypes = [vp, vp, i32, C.c_uint64, i64] + [u64p] * 3
         L.pt_test_camera_cull_sweep.argtypes = [vp, vp, i32, i32] + [u64p] * 3
@@ -977,6 +978,25 @@ def test_mesh_intersect(geom, tris, rays, flat=False, sentinel=-7.0):
     culled = np.zeros(n, np.int32)
     _tcheck(test_lib().pt_test_mesh_intersect(_p(g), _p(tr), len(tr), 1 if flat else 0, _p(rays), n, _p(t), _p(p), _p(nn), _p(o), _p(culled)))
     return t, p, nn, o, culled
+
+
+def test_mesh_intersect2(geom, tris, rays, normals=None, materials=None, flat=False, sentinel=-7.0):
+    """test_mesh_intersect with the mesh's attributes (normals (ntris, 9), materials (ntris,) or None) and the winner's name.  Returns t, p, n,
+    outside, culled, tri (the file index of the triangle that was hit, -1 on a miss), face_mat (its own material; -1: none, or a miss)."""
+    g = np.ascontiguousarray(geom).reshape(-1)[:1]
+    tr = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(tr), 9)
+    mat = None if materials is None else np.ascontiguousarray(materials, np.int32).reshape(len(tr))
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    n = len(rays)
+    t = np.empty(n, np.float32)
+    p = np.full((n, 3), sentinel, np.float32)
+    nn = np.full((n, 3), sentinel, np.float32)
+    o = np.ones(n, np.int32)
+    culled, tri, fm = np.zeros(n, np.int32), np.full(n, -2, np.int32), np.full(n, -2, np.int32)
+    _tcheck(test_lib().pt_test_mesh_intersect2(_p(g), _p(tr), None if nrm is None else _p(nrm), None if mat is None else _p(mat), len(tr),
+                                               1 if flat else 0, _p(rays), n, _p(t), _p(p), _p(nn), _p(o), _p(culled), _p(tri), _p(fm)))
+    return t, p, nn, o, culled, tri, fm
 
 
 def test_mesh_cull_sweep(geom, tris, seed, rays):

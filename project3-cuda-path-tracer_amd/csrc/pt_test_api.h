@@ -256,6 +256,55 @@ int pt_test_mesh_intersect(const PtGeom *geom, const float *tris, int ntris, int
     return PT_OK;
 }
 
+int pt_test_mesh_intersect2(const PtGeom *geom, const float *tris, const float *normals, const int32_t *mats, int ntris, int flat,
+                            const float *rays, int n, float *t, float *p3, float *n3, int32_t *outside, int32_t *culled, int32_t *tri,
+                            int32_t *face_mat) {
+    NEED_GPU();
+    if (!geom || !tris || ntris < 1 || geom->type != PT_MESH || !tri || !face_mat) return fail(PT_ERR_INVALID, "pt_test_mesh_intersect2: bad argument");
+    if (n <= 0) return PT_OK;
+    // the records twice: as pt_init lays them out, and with 1 + the triangle's file index in the material's word (same geometry, same refs)
+    std::vector<ptd::MeshUnit> recs, tagged;
+    std::vector<int> index((size_t)ntris);
+    for (int i = 0; i < ntris; ++i) index[(size_t)i] = i;
+    float box[6], box2[6];
+    const ptm::MeshLayout lay = ptm::appendMesh(tris, ntris, flat != 0, recs, box, normals, mats);
+    const ptm::MeshLayout lay2 = ptm::appendMesh(tris, ntris, flat != 0, tagged, box2, normals, index.data());
+    if (lay2.root != lay.root || lay2.stride != lay.stride || lay2.stackNeed != lay.stackNeed || tagged.size() != recs.size())
+        return fail(PT_ERR_INVALID, "pt_test_mesh_intersect2: the two record arrays differ in layout");
+    GeomDev hg;
+    pack_geom(*geom, hg, nullptr, box);
+    hg.meshRoot = lay.root;
+    hg.meshStride = lay.stride;
+    DevBuf<GeomDev> dg;
+    DevBuf<ptd::MeshUnit> drec, dtag;
+    DevBuf<int> dout, dcull, dtri, dfm;
+    DevBuf<float> dr, dt, dp, dn;
+    UP(dg, &hg, 1);
+    UP(drec, recs.data(), recs.size());
+    UP(dtag, tagged.data(), tagged.size());
+    UP(dr, rays, (size_t)n * 6);
+    UP(dp, p3, (size_t)n * 3);
+    UP(dn, n3, (size_t)n * 3);
+    UP(dout, outside, n);
+    int rc = dt.alloc(n); if (rc) return rc;
+    rc = dcull.alloc(n); if (rc) return rc;
+    rc = dtri.alloc(n); if (rc) return rc;
+    rc = dfm.alloc(n); if (rc) return rc;
+    const size_t stackBytes = (size_t)std::max(lay.stackNeed, 1) * 256 * sizeof(uint32_t);
+    if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "pt_test_mesh_intersect2: the hierarchy needs %d stack levels", lay.stackNeed);
+    hipLaunchKernelGGL(k_test_mesh2, dim3((unsigned)((n + 255) / 256)), dim3(256), stackBytes, 0, dg.p, reinterpret_cast<const float4 *>(drec.p),
+                       reinterpret_cast<const float4 *>(dtag.p), dr.p, n, dt.p, dp.p, dn.p, dout.p, dcull.p, dtri.p, dfm.p);
+    HIPCHECK(hipDeviceSynchronize());
+    DOWN(t, dt, n);
+    DOWN(p3, dp, (size_t)n * 3);
+    DOWN(n3, dn, (size_t)n * 3);
+    DOWN(outside, dout, n);
+    DOWN(culled, dcull, n);
+    DOWN(tri, dtri, n);
+    DOWN(face_mat, dfm, n);
+    return PT_OK;
+}
+
 int pt_test_mesh_cull_sweep(const PtGeom *geom, const float *tris, int ntris, uint64_t seed, int64_t rays, uint64_t *culled,
                             uint64_t *violations, uint64_t *hits) {
     NEED_GPU();

@@ -100,6 +100,38 @@ __global__ void k_test_mesh(const GeomDev *geom, const float4 *recs, const float
     n3[3 * i] = N.x; n3[3 * i + 1] = N.y; n3[3 * i + 2] = N.z;
     outside[i] = o ? 1 : 0;
 }
+// ... with the face's material, and the winner's file index: the same walk once more through `tagged`, a copy of the records whose
+// triangle k carries 1 + k where `recs` carries 1 + its material (same geometry, same refs: the same winner)
+__global__ void k_test_mesh2(const GeomDev *geom, const float4 *recs, const float4 *tagged, const float *rays, int n, float *t,
+                             float *p3, float *n3, int *outside, int *culled, int *tri, int *faceMat) {
+    extern __shared__ uint32_t s_meshStack[];
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const GeomDev G = *geom;
+    F3 ro = f3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]);
+    F3 rd = f3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    F3 P = f3(p3[3 * i], p3[3 * i + 1], p3[3 * i + 2]);
+    F3 N = f3(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2]);
+    bool o = outside[i] != 0;
+    F3 nsrc = f3(0, 0, 0);
+    int fm = 0, tag = 0;
+    const bool cull = certainMiss(G, ro, rd, dot(rd, rd));
+    const float tt = meshIntersectionTest<false, 256>(G, recs, G.meshRoot, G.meshStride, s_meshStack + threadIdx.x, ro, rd, P, nsrc, o, fm);
+    {
+        F3 P2 = P, n2 = nsrc;
+        bool o2 = o;
+        const float t2 = meshIntersectionTest<false, 256>(G, tagged, G.meshRoot, G.meshStride, s_meshStack + threadIdx.x, ro, rd, P2, n2, o2, tag);
+        if (t2 == -1.0f) tag = 0;
+    }
+    culled[i] = cull ? 1 : 0;
+    t[i] = cull && tt != -1.0f ? __builtin_nanf("") : tt;
+    if (tt != -1.0f) N = hitNormal(G, nsrc, o);
+    p3[3 * i] = P.x; p3[3 * i + 1] = P.y; p3[3 * i + 2] = P.z;
+    n3[3 * i] = N.x; n3[3 * i + 1] = N.y; n3[3 * i + 2] = N.z;
+    outside[i] = o ? 1 : 0;
+    tri[i] = tag - 1;
+    faceMat[i] = tt != -1.0f ? fm - 1 : -1;
+}
 // certainMiss soundness sweep for ONE mesh geom: rays as in k_sweep_sphere_cull (origins 1/64 .. 64 units from the bounding
 // ball's centre, aimed within ~1.3 radii of it: hits, grazes, near misses); a culled ray that the full walk hits is a violation
 __global__ void k_sweep_mesh_cull(const GeomDev *geom, const float4 *recs, unsigned long long seed, int per_thread,

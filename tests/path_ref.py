@@ -53,8 +53,9 @@ def _cube(ro, rd, tmin):
     return t, inside, shaky
 
 
-def _mesh(ro, rd, tris, tmin=0.0):
-    """nearest two-sided triangle per ray: (t, triangle, (bu, bv)), bu the weight of corner 1 and bv of corner 2"""
+def _mesh(ro, rd, tris, tmin=0.0, eps=0.0):
+    """nearest two-sided triangle per ray: (t, triangle, (bu, bv)), bu the weight of corner 1 and bv of corner 2.  `eps`: a triangle with
+    |det| < eps is not tested (the renderer's rule, glm's epsilon; rd must be a unit vector for it to mean the same)"""
     v0, e1, e2 = tris[:, 0:3], tris[:, 3:6] - tris[:, 0:3], tris[:, 6:9] - tris[:, 0:3]
     p = np.cross(rd[:, None, :], e2[None])
     det = _dot(p, e1[None])
@@ -65,7 +66,7 @@ def _mesh(ro, rd, tris, tmin=0.0):
         qv = np.cross(s, e1[None])
         bv = f * _dot(qv, rd[:, None, :])
         t = f * _dot(qv, e2[None])
-    ok = (det != 0) & (bu >= 0) & (bv >= 0) & (bu + bv <= 1) & (t > 0)
+    ok = (det != 0) & (np.abs(det) >= eps) & (bu >= 0) & (bv >= 0) & (bu + bv <= 1) & (t > 0)
     traw = t
     t = np.where(ok, t, np.inf)
     k = t.argmin(1)

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from adversarial_meshes import check_hierarchy, walk as _walk
 from conftest import SCENES
 
 f32 = np.float32
@@ -191,68 +192,12 @@ def test_icosphere_mesh_approximates_the_sphere(oracle):
 def test_hierarchy_invariants(pt):
     sc = pt.Scene(os.path.join(SCENES, "cornell_mesh.txt"))
     cases = [(t, o) for t in sc.meshes.values() for o in (0, 5)] + [(_cube_mesh(), o) for o in range(8)] + [(_cube_mesh()[:1], 3)]
-    LEAF = pt.MESH_LEAF
     for tris, octant in cases:
-        nt = len(tris)
-        recs, nodes, first, need = pt.mesh_bvh(tris, octant)
-        assert len(recs) == nt and len(nodes) == max(nt - 1, 1)
-        margin = f32(1e-5) * np.abs(tris).max()
-        v = tris.reshape(nt, 3, 3)
-        neg = np.array([(octant >> a) & 1 for a in range(3)], bool)
-        for i, r in enumerate(recs):                          # triangle i, file order: its vertices and the mesh's margin
-            assert np.array_equal(r["v0"], v[i][0]) and np.array_equal(r["v1"], v[i][1]) and np.array_equal(r["v2"], v[i][2])
-            assert r["margin"] == margin
-        box_lo = lambda t: v[t].min(0) - margin                # a triangle's own box, as the kernel derives it
-        box_hi = lambda t: v[t].max(0) + margin
-        def planes_of(lo, hi):
-            # the six halves of a box for this octant: entry planes, exit planes; lo rounded down, hi up (never inwards, and by
-            # less than one half-precision step)
-            lo16 = lo.astype(np.float16)
-            lo16 = np.where(lo16.astype(f32) > lo, np.nextafter(lo16, np.float16(-np.inf)), lo16)
-            hi16 = hi.astype(np.float16)
-            hi16 = np.where(hi16.astype(f32) < hi, np.nextafter(hi16, np.float16(np.inf)), hi16)
-            return np.concatenate([np.where(neg, hi16, lo16), np.where(neg, lo16, hi16)])
-
-        if nt == 1:
-            # a root whose near child is the triangle and whose far child is a box no ray passes (entered at +inf, left at -inf)
-            nd = nodes[0]
-            assert need == 0 and int(nd["ref"]) == LEAF
-            assert np.array_equal(nd["planes"], planes_of(box_lo(0), box_hi(0)))
-            fp = nd["far_planes"].astype(f32)
-            assert np.all(np.isinf(fp)) and np.all((fp[:3] > 0) != neg) and np.all((fp[3:] < 0) != neg)
+        # (the checker, shared with the adversarial meshes' tests: tests/adversarial_meshes.py)
+        depth, need_here, need = check_hierarchy(pt, tris, octant)
+        if len(tris) == 1:
             continue
-        # walk from the root (inner node 0): every triangle exactly once, every inner node exactly once; a child's box in its
-        # parent is the exact union of what lies below it, rounded outwards to half precision and stored as the planes a ray of
-        # the octant enters / leaves through; near child first
-        seen_tri, seen_node = [], []
-
-        def box_of(ref):
-            ref = int(ref)
-            if ref & LEAF:
-                t = (ref & ~LEAF) // 3
-                assert (ref & ~LEAF) % 3 == 0
-                seen_tri.append(t)
-                return box_lo(t), box_hi(t), 0, 0
-            assert (ref - first) % 2 == 0
-            k = (ref - first) // 2
-            assert 0 <= k < len(nodes)
-            seen_node.append(k)
-            nd = nodes[k]
-            nlo, nhi, nd_, nn = box_of(nd["ref"])
-            flo, fhi, fd_, fn = box_of(nd["far_ref"])
-            assert np.array_equal(nd["planes"], planes_of(nlo, nhi)) and np.array_equal(nd["far_planes"], planes_of(flo, fhi))
-            # the first child is the nearer one for this octant along some axis: its centre does not lie behind the second's
-            cl, cr = nlo + nhi, flo + fhi
-            assert any((cl[a] >= cr[a]) if (octant >> a) & 1 else (cl[a] <= cr[a]) for a in range(3))
-            # depth-first layout: the near child's inner nodes follow their parent directly, the far child's come after them
-            if not int(nd["ref"]) & LEAF:
-                assert (int(nd["ref"]) - first) // 2 == k + 1
-            return np.minimum(nlo, flo), np.maximum(nhi, fhi), 1 + max(nd_, fd_), max(1 + nn, fn)
-
-        _, _, depth, need_here = box_of(first)
-        assert sorted(seen_tri) == list(range(nt)) and sorted(seen_node) == list(range(nt - 1))
-        assert depth <= 3 * int(np.ceil(np.log2(max(nt, 1)))) + 2                      # no side of a split below an eighth: logarithmic
-        # the far children that can wait at once on a lane's stack: this copy's need is within what pt_init reserves for all eight
+        assert depth <= 3 * int(np.ceil(np.log2(max(len(tris), 1)))) + 2              # no side of a split below an eighth: logarithmic
         assert need_here <= need <= depth and need <= 24
 
 
@@ -277,7 +222,7 @@ def test_median_rebuild_bounds_the_stack(pt, oracle, monkeypatch):
         rd = oracle.normalize(d)
         wt, wp, wn, wo, wtri = oracle.mesh_intersect(ident, tris, np.concatenate([o, d]))
         octant = int(np.signbit(rd[0])) | int(np.signbit(rd[1])) << 1 | int(np.signbit(rd[2])) << 2
-        best, tbest, vis = _walk(*copies[octant][:3], tris, oracle, o, rd, copies[octant][3])
+        best, tbest, vis, _ = _walk(*copies[octant][:3], tris, oracle, o, rd, copies[octant][3])
         assert best == wtri
         hits += best >= 0
     assert hits > 150
@@ -310,64 +255,6 @@ def test_half_precision_planes_round_outwards_everywhere(pt):
                 assert np.all((np.abs(pl[big]) == 65504.0) | np.isinf(pl[big]))
 
 
-def _walk(recs, nodes, first, tris, oracle, ro, rd, need):
-    """The kernel's traversal (ptd::meshIntersectionTest) in numpy fp32 on object-space rays; triangle test by the oracle."""
-    LEAF = 0x80000000
-    nt = len(recs)
-    up, dn = f32(1.00001), f32(0.99999)
-    g = np.where(np.abs(rd) < f32(1e-30), np.copysign(f32(1e-30), rd), rd).astype(f32)
-    inv = (f32(1.0) / g).astype(f32)
-    c = (-(ro * inv)).astype(f32)
-    fma = lambda x: (x.astype(np.float64) * inv.astype(np.float64) + c.astype(np.float64)).astype(f32)   # exact in fp64, rounded once
-    best, tbest, visited, deepest = -1, f32(0), 0, 0
-
-    def box_pass(lo, hi):
-        a, b = fma(lo), fma(hi)
-        tn = np.max(np.minimum(a, b))
-        tf = np.min(np.maximum(a, b))
-        tmin = f32(tn * dn)
-        return bool(f32(tf * up) >= tmin and tf >= 0 and (best < 0 or not tmin > tbest)), tmin
-
-    def planes_pass(pl):
-        pl = pl.astype(f32)
-        tn, tf = np.max(fma(pl[:3])), np.min(fma(pl[3:]))
-        tmin = f32(tn * dn)
-        return bool(f32(tf * up) >= tmin and tf >= 0 and (best < 0 or not tmin > tbest))
-
-    ref = first
-    stack = []
-    margin = recs[0]["margin"]
-    while True:
-        visited += 1
-        pop = True
-        if ref & LEAF:
-            tri = (ref & ~LEAF) // 3
-            vv = np.stack([recs[tri]["v0"], recs[tri]["v1"], recs[tri]["v2"]])
-            ok, tmin = box_pass(vv.min(0) - margin, vv.max(0) + margin)
-            if ok:
-                v = tris[tri]
-                hit, tuv, front = oracle.mesh_triangle(ro, rd, v[0:3], v[3:6], v[6:9])
-                t = f32(tuv[0])
-                if hit and t >= tmin and (best < 0 or t < tbest or (t == tbest and tri < best)):
-                    best, tbest = tri, t
-        else:
-            nd = nodes[(int(ref) - first) // 2]
-            pn = planes_pass(nd["planes"])
-            pf = planes_pass(nd["far_planes"])
-            if pn and pf:
-                stack.append(int(nd["far_ref"]))
-                deepest = max(deepest, len(stack))
-            if pn or pf:
-                ref = int(nd["ref"]) if pn else int(nd["far_ref"])
-                pop = False
-        if pop:
-            if not stack:
-                break
-            ref = stack.pop()
-    assert deepest <= need
-    return best, tbest, visited
-
-
 def test_hierarchy_walk_equals_the_brute_force_rule(pt, oracle):
     sc = pt.Scene(os.path.join(SCENES, "cornell_mesh.txt"))
     ident = oracle.make_geom(2, 0, (0, 0, 0), (0, 0, 0), (1, 1, 1))       # identity: world space = object space
@@ -388,7 +275,7 @@ def test_hierarchy_walk_equals_the_brute_force_rule(pt, oracle):
             rd = oracle.normalize(d)
             wt, wp, wn, wo, wtri = oracle.mesh_intersect(ident, tris, np.concatenate([o, d]))
             octant = int(np.signbit(rd[0])) | int(np.signbit(rd[1])) << 1 | int(np.signbit(rd[2])) << 2
-            best, tbest, vis = _walk(*copies[octant][:3], tris, oracle, o, rd, copies[octant][3])
+            best, tbest, vis, _ = _walk(*copies[octant][:3], tris, oracle, o, rd, copies[octant][3])
             assert best == wtri, (g, i, best, wtri)
             hits += best >= 0
             visited += vis
