@@ -90,6 +90,15 @@ int pt_test_camera_cull_tables(const PtCamera *cam, const PtGeom *geoms, int nge
  * wave2 or sig_idx NULL for the sizes alone: pix takes sizes4[0] words, wave2 sizes4[0] / 32, sig_idx sizes4[1]. */
 int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
                         int32_t *sig_idx, int64_t *sizes4);
+/* The same list as pt_init builds it for the untextured forms: a one-cube signature's pixels split by the cube face every camera ray of
+ * theirs is certified to enter through (pt_host_scene.h: camera_face_certificate), face[w] = 2 axis + (side > 0) for wave w, or -1
+ * (host only).  sizes4 = {lanes (-1: not built), entries of sig_idx, pixels listed, pixels in resolved waves}; face takes sizes4[0] / 64. */
+int pt_test_camera_resolved(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
+                            int32_t *sig_idx, int32_t *face, int64_t *sizes4);
+/* Device sweep: for every resolved pixel of the unsharded list, `samples` seeded jitters and the four corners of the certificate's
+ * footprint -- the resolved wave's box test (pt_device.h: boxFaceHit) against boxIntersectionTest.  counts = {rays, rays on which
+ * (t > 0, outside, face, P bit for bit) differ -- must be 0 --, resolved pixels}. */
+int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t seed, uint64_t counts[3]);
 /* Triangle meshes.  pt_test_mesh_intersect: `n` rays against ONE mesh geom on the GPU, through the hierarchy (flat = 0) or a
  * plain list of its triangles (flat = 1: the brute-force rule); outputs keep their input values on a miss; culled[i] = 1 when
  * the bounding-ball test (certainMiss) rejected the ray -- t[i] is NaN if the full test hits nevertheless (must not happen).

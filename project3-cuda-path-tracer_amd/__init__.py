@@ -71,6 +71,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_slab_quotients", "pt_test_slab_quotients_sweep", "pt_test_box_fast_sweep", "pt_test_sphere_cull_sweep", "pt_test_unscaled_sqrt_sweep",
     "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_intersect2", "pt_test_mesh_bvh",
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
+    "pt_test_camera_resolved", "pt_test_face_hit_sweep",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
@@ -226,6 +227,8 @@ def _bind(L, with_tests):
         L.pt_test_camera_cull_sweep.argtypes = [vp, vp, i32, i32] + [u64p] * 3
         L.pt_test_camera_cull_tables.argtypes = [vp, vp, i32, vp, vp, vp]
         L.pt_test_camera_list.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+        L.pt_test_camera_resolved.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.pt_test_face_hit_sweep.argtypes = [vp, vp, i32, i32, C.c_uint64, u64p]
         L.pt_test_camera_cull_margin.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_double), u64p]
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
@@ -1193,6 +1196,33 @@ def camera_list(camera, geoms, shard_rank=0, shard_count=1):
     sig = np.zeros(int(sizes[1]), np.int32)
     _tcheck(test_lib().pt_test_camera_list(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, _p(pix), _p(wave), _p(sig), _p(sizes)))
     return pix, wave, sig, int(sizes[2]), int(sizes[3])
+
+
+def camera_resolved(camera, geoms, shard_rank=0, shard_count=1):
+    """camera_list as pt_init builds it for the untextured forms: one-cube signatures split by the cube face their pixels' camera rays are
+    certified to enter through (host only, no length cap).  Returns None where the list is not built, else (pix, wave ranges, signature
+    entries, per wave its face 2 axis + (side > 0) or -1)."""
+    cam = np.ascontiguousarray(camera)
+    geoms = np.ascontiguousarray(geoms)
+    sizes = np.zeros(4, np.int64)
+    _tcheck(test_lib().pt_test_camera_resolved(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, None, None, None, None, _p(sizes)))
+    if sizes[0] < 0:
+        return None
+    pix = np.zeros(int(sizes[0]), np.uint32)
+    wave = np.zeros((int(sizes[0]) // 64, 2), np.int32)
+    sig = np.zeros(int(sizes[1]), np.int32)
+    face = np.zeros(int(sizes[0]) // 64, np.int32)
+    _tcheck(test_lib().pt_test_camera_resolved(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, _p(pix), _p(wave), _p(sig), _p(face), _p(sizes)))
+    return pix, wave, sig, face
+
+
+def test_face_hit_sweep(camera, geoms, samples=64, seed=1):
+    """Device sweep of the resolved waves' box test against the full one.  Returns (rays, mismatches, resolved pixels)."""
+    cam = np.ascontiguousarray(camera)
+    geoms = np.ascontiguousarray(geoms)
+    c = (C.c_uint64 * 3)()
+    _tcheck(test_lib().pt_test_face_hit_sweep(_p(cam), _p(geoms), len(geoms), samples, seed, c))
+    return tuple(int(v) for v in c)
 
 
 def test_camera_cull_sweep(camera, geoms, samples=1):

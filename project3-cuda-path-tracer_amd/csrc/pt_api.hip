@@ -180,6 +180,7 @@ struct State : PlanScalars {
     DevBuf<SphereCull> dSphCull;    // sphere-heavy scenes: packed culling data of the spheres, and ...
     DevBuf<SphereCull> dSphGroups;  // ... scenes of hundreds of them: the bounding balls of the table's groups (BounceArgs::sphGroups)
     DevBuf<int> dCamWave, dCamSigIdx;   // camera rays: the packed work list (build_camera_list), or none
+    DevBuf<int> dCamFace;               // ... and its waves' resolved cube faces (CameraList::face)
     DevBuf<uint32_t> dCamPix;
     DevBuf<int> dRowOff, dRowIdx;   // camera-ray bounce: per image row, the primitives whose pixel rectangle covers it
     DevBuf<int> dClassIdx;          // later bounces: per queue class, the primitives to look at (KParams::classOff)
@@ -398,7 +399,7 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     ba.ctrl = sl.ctrl.p; ba.ggeoms = R().dgeoms.p; ba.gmats = R().dmats.p; ba.ghit = reinterpret_cast<const float4 *>(R().dGeomHit.p); ba.contrib = contrib; ba.hitMask = sl.hitMask.p;
     ba.sphCull = R().dSphCull.p; ba.classIdx = R().dClassIdx.p;
     ba.rowOff = R().dRowOff.p; ba.rowIdx = R().dRowIdx.p;
-    ba.camPix = R().dCamPix.p; ba.camWave = R().dCamWave.p; ba.camSigIdx = R().dCamSigIdx.p;
+    ba.camPix = R().dCamPix.p; ba.camWave = R().dCamWave.p; ba.camSigIdx = R().dCamSigIdx.p; ba.camFace = R().dCamFace.p;
     ba.walls = R().dwalls.p;
     ba.meshRecs = reinterpret_cast<const float4 *>(R().dMeshRecs.p);
     ba.hostFault = R().hostFaultDev;
@@ -1149,6 +1150,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     PTCHECK(up(S.dCamPix, plan.cl.pix));
     PTCHECK(up(S.dCamWave, plan.cl.wave));
     PTCHECK(up(S.dCamSigIdx, plan.cl.sigIdx));
+    PTCHECK(up(S.dCamFace, plan.cl.face));
     PTCHECK(up(S.dWalkRowOff, plan.walkRowOff));
     PTCHECK(up(S.dClassIdx, plan.classIdx));
 

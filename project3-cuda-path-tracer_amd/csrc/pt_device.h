@@ -568,6 +568,27 @@ __device__ __forceinline__ float boxIntersectionTest(const GD &g, F3 ro, F3 rd, 
     return -1.0f;
 }
 
+// The box test of a camera ray whose pixel pt_init RESOLVED to face `face` = 2 K + (s > 0) of cube g (pt_host_scene.h:
+// camera_face_certificate, where the argument is written out): the ray is certified to hit, from outside, through that face, with every
+// operand inside the ranges of sqrtUnscaled / divUnscaled -- so of boxIntersectionTest<., true> only the operations that make its
+// result remain, operation for operation: the direction transform, the fast path's normalize, the ONE quotient tmin = (s/2 - o_K) / qd_K
+// (the numerator as boxSlabsFastFinish and the reference's loop form it: +-.5 - o), the hit point.  No slab decision, no per-lane axis
+// select (`face` is wave-uniform), no distance (it is compared with nothing: the pixel's signature is g alone).  The caller supplies
+// outside = true and the face.  tests/test_gpu_camera_resolve.py sweeps it against boxIntersectionTest bit for bit.
+template <typename GD>
+__device__ __forceinline__ F3 boxFaceHit(const GD &g, int face, F3 rd) {
+    const F3 qo = f3(g.camObj[0], g.camObj[1], g.camObj[2]);
+    const F3 qdu = mulMV0(g.inv, g.invZ, rd);
+    const float s = sqrtUnscaled(dot(qdu, qdu));
+    const float inv = divUnscaled(1.0f, s, __builtin_amdgcn_rcpf(s));
+    const F3 qd = qdu * inv;
+    const int K = face >> 1;                                              // (wave-uniform)
+    const float oK = K == 0 ? qo.x : (K == 1 ? qo.y : qo.z), dK = K == 0 ? qd.x : (K == 1 ? qd.y : qd.z);
+    const float aK = ((face & 1) ? 0.5f : -0.5f) - oK;
+    const float tmin = divUnscaled(aK, dK, __builtin_amdgcn_rcpf(dK));
+    return mulMV(g.xf, getPointOnRay(qo, qd, tmin), 1.0f);
+}
+
 // Certain miss of a primitive, decided in WORLD space against its bounding ball for ~20 instructions.  Not an
 // approximation of the result but a sufficient condition for the reference's own miss:
 //   the image of the object-space ball of radius rho (1/2: the sphere itself; sqrt(3)/2: the cube's corners) lies inside

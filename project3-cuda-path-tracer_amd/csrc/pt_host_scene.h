@@ -756,12 +756,161 @@ constexpr int kCamListRowMax = 64, kCamListSigMax = 1 << 16;
 struct CameraList {
     std::vector<uint32_t> pix;
     std::vector<int> wave, sigIdx;
+    std::vector<int> face;                  // per wave: the cube face its pixels are resolved to (CameraResolve), or -1
     int nSig = 0;
     long long listed = 0;                   // pixels in the list
+    long long resolved = 0;                 // ... of them in waves with a face
 };
-bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int shardCount, long long maxLen, CameraList &cl) {
-    cl.pix.clear(); cl.wave.clear(); cl.sigIdx.clear();
-    cl.nSig = 0; cl.listed = 0;
+
+// THE FACE CERTIFICATE of a camera pixel.  A pixel whose signature is one cube g still runs the whole box test (ptd::boxIntersectionTest)
+// to learn which of six slab quotients is the answer.  For most such pixels -- the inside of a wall of the room -- the answer is the
+// same for every jitter: the ray enters g through one face (K, s), K the axis and s = +-1 the side.  camera_face_certificate says so
+// on the host, once per pt_init, and k_bounce<true, ...> then evaluates that one quotient alone (ptd::boxFaceHit).
+//
+// Pixel (x, y) is RESOLVED to (K, s) of cube g when
+//   (i)   the cube's data is tame (CubeCert::ok): every entry finite, |o|_1 <= 2^19 for o = the float32 object-space eye the kernel
+//         uses (GeomDev::camObj), the singular values of inverseTransform's linear part L inside [2^-30, 2^30] (bounded by
+//         |det L| / |L|_F^2 <= smin, smax <= |L|_F), and the world distance from the eye to the face is clear of rounding:
+//         smin(transform) (s o_K - 1/2 - 2e-4) >= 1e-4 (1 + |eye|_1 + |translation|_1 + |transform|_F);
+//   (ii)  s o_K >= 1/2 + 1e-2 + inset_K: the eye is outside the slab of axis K, on the side of the face, with room to spare;
+//   (iii) each of the four corner directions of the pixel's FOOTPRINT [x - 2, x + 3] x [y - 2, y + 3] (continuous pixel coordinates: the
+//         pixel square widened by the spans' own 2 px), q = L (view - right pixLenX (cx - W/2) - up pixLenY (cy - H/2)) in float64,
+//         moves towards the face, s q_K < 0 and |q_K| >= 1e-3 |q|, and crosses both planes x_K = s/2 -+ rho (s/2 - o_K), rho = 2^-12 --
+//         just in front of the face and just behind it -- at points whose other two coordinates j satisfy |p_j| <= 1/2 - inset_j,
+//         inset_j = 8 D_j + 1e-4 with D_j the fp32 displacement of the object-space line along axis j (inflated_object_box's term,
+//         its factor 8 for a cube included: four times the allowance the culling tables use, plus an absolute inset).
+// Why four corners do: q is affine in (cx, cy), so s q_K < 0 at the corners holds on the whole footprint, and the crossing point with a
+// plane x_K = c, p = o + (c - o_K) q / q_K, is a central projection of q: it maps the footprint, a convex set on which the denominator
+// keeps its sign, onto a convex quadrilateral whose corners are the corners' images.  The two other slabs' deflated cross-section is
+// convex as well, so all four corners inside put every ray of the footprint inside, on both planes.
+// What follows for every camera ray of the pixel, jitter in [0, 1)^2, as the reference's loop (src/intersections.h:51-77) evaluates it in
+// fp32: its direction is the exact one of some point of the pixel square up to ~1e-6 relative -- orders of magnitude inside the 2 px of
+// footprint, the spans' argument -- and its object-space line lies within D of the exact one.  Along the ray, parameter t_K of the face
+// plane: at (1 - rho) t_K and at (1 + rho) t_K the point is strictly inside the two other slabs by the inset, so those axes' entry
+// parameters lie below (1 - rho) t_K and their exit parameters above (1 + rho) t_K -- rho = 2^-12 against the fast path's doubt margin
+// 2^-19 and fp32 rounding ~2^-22.  Axis K's own entry is t_K > 0 (ii) and its exit is later still.  So tmin = t_K with the face
+// (K, s), tmax > tmin > 0: a hit, from outside, tmin = RN((s/2 - o_K) / qd_K) -- whether boxSlabsFastDecide or boxSlabsExact got there.
+// The ranges: the squared length of L d for a unit d lies in [smin^2, smax^2], inside sqrtUnscaled's and the fast path's [2^-80, 2^80),
+// its root inside divUnscaled's exhaustively tested [2^-40, 2^40]; |qd_K| >= ~1e-3 and |s/2 - o_K| in [1e-2, 2^19 + 1] are inside the range
+// on which divUnscaled equals IEEE division (tests/test_gpu_parity.py).  Hence the one quotient boxFaceHit forms is bit for bit the
+// reference's tmin, and P follows from it by the same operations.  The hit's distance |eye - P| is positive by (i): P lies 1e-4 object
+// units in front of the face, at least smin(transform) (s o_K - 1/2 - 1e-4) world units from the eye.
+// Whatever cannot be bounded -- a non-finite entry, a singular matrix, an eye inside or near a slab -- leaves the pixel unresolved.
+struct CubeCert {
+    bool ok = false;
+    double o[3], L[3][3], inset[3];
+    double clear = 0;                       // the least s o_K - 1/2 - inset_K: (ii)'s room and (i)'s distance
+};
+struct CameraResolve {
+    std::vector<CubeCert> cube;             // per primitive; ok only for a tame cube
+    double view[3], rx[3], uy[3];           // the camera basis: view, right * pixLenX, up * pixLenY
+    double halfW = 0, halfH = 0;
+    bool off = false;                       // (PT_AMD_NO_CAMERA_RESOLVE: split as usual, every wave -1)
+};
+constexpr double kFaceFootprint = 2.0, kFaceRho = 1.0 / 4096, kFaceClear = 1e-2, kFaceInsetAbs = 1e-4, kFaceInsetD = 8.0, kFaceMinSlope = 1e-3;
+void build_camera_resolve(const PtGeom *geoms, int ngeoms, const KParams &k, const std::vector<GeomDev> &hg, CameraResolve &cr) {
+    cr.cube.assign((size_t)(ngeoms > 0 ? ngeoms : 0), CubeCert());
+    for (int a = 0; a < 3; ++a) {
+        cr.view[a] = k.view[a];
+        cr.rx[a] = (double)k.right[a] * (double)k.pixLenX;
+        cr.uy[a] = (double)k.up[a] * (double)k.pixLenY;
+    }
+    cr.halfW = k.halfW;
+    cr.halfH = k.halfH;
+    const double eps = 5.9604644775390625e-08;                // 2^-24
+    for (int i = 0; i < ngeoms; ++i) {
+        const PtGeom &g = geoms[i];
+        if (g.type != PT_CUBE || (hg[i].flags & 33) != 1) continue;
+        CubeCert c;
+        bool fin = true;
+        double A[3], B[3], F2 = 0, T2 = 0, l1o = 0, l1e = 0, l1t = 0;
+        for (int r = 0; r < 3; ++r) {
+            c.o[r] = hg[i].camObj[r];
+            fin = fin && std::isfinite(c.o[r]);
+            l1o += std::fabs(c.o[r]);
+            l1e += std::fabs((double)k.pos[r]);
+            l1t += std::fabs((double)g.transform[12 + r]);
+            A[r] = std::fabs((double)g.inverseTransform[12 + r]);
+            B[r] = 0;
+            for (int j = 0; j < 3; ++j) {
+                c.L[r][j] = hg[i].inv[3 * j + r];
+                const double m = std::fabs(c.L[r][j]);
+                A[r] += m * std::fabs((double)k.pos[j]);
+                B[r] += m;
+                F2 += m * m;
+                T2 += (double)g.transform[j * 4 + r] * (double)g.transform[j * 4 + r];
+            }
+        }
+        auto det3 = [](double m00, double m01, double m02, double m10, double m11, double m12, double m20, double m21, double m22) {
+            return m00 * (m11 * m22 - m12 * m21) - m01 * (m10 * m22 - m12 * m20) + m02 * (m10 * m21 - m11 * m20);
+        };
+        const double detL = det3(c.L[0][0], c.L[0][1], c.L[0][2], c.L[1][0], c.L[1][1], c.L[1][2], c.L[2][0], c.L[2][1], c.L[2][2]);
+        const double detT = det3(g.transform[0], g.transform[4], g.transform[8], g.transform[1], g.transform[5], g.transform[9],
+                                 g.transform[2], g.transform[6], g.transform[10]);
+        if (!fin || !std::isfinite(F2) || !std::isfinite(T2) || !std::isfinite(detL) || !std::isfinite(detT) || !(F2 > 0) || !(T2 > 0)) continue;
+        const double sminL = std::fabs(detL) / F2, smaxL = std::sqrt(F2), sminT = std::fabs(detT) / T2;
+        if (!(sminL >= 0x1p-30) || !(smaxL <= 0x1p+30) || !(l1o <= 0x1p+19) || !(sminT > 0)) continue;
+        const double R = std::sqrt(A[0] * A[0] + A[1] * A[1] + A[2] * A[2]) + 1.0, smax = std::sqrt(T2);
+        for (int r = 0; r < 3; ++r) {
+            const double D = 8.0 * eps * A[r] + R * (8.0 * eps * B[r] * smax + 8.0 * eps);     // (inflated_object_box's D_i, a cube's factor)
+            c.inset[r] = kFaceInsetD * D + kFaceInsetAbs;
+            fin = fin && std::isfinite(c.inset[r]);       // (an inset of half a unit or more resolves nothing on that axis)
+        }
+        if (!fin) continue;
+        // (the eye's clearance from a face's plane in world units, (i): stored as the least object-space clearance that will do)
+        const double need = 1e-4 * (1.0 + l1e + l1t + smax) / sminT + 2e-4;
+        if (!std::isfinite(need)) continue;
+        c.clear = std::max(kFaceClear, need);
+        c.ok = true;
+        cr.cube[(size_t)i] = c;
+    }
+}
+// the face (2 K + (s > 0)) pixel (x, y) is resolved to on cube g, or -1
+int camera_face_certificate(const CameraResolve &cr, int g, int x, int y) {
+    if (g < 0 || (size_t)g >= cr.cube.size() || !cr.cube[(size_t)g].ok) return -1;
+    const CubeCert &c = cr.cube[(size_t)g];
+    // the four corner directions of the footprint, object space
+    double q[4][3], qn[4];
+    for (int corner = 0; corner < 4; ++corner) {
+        const double cx = (corner & 1) ? (double)x + 1.0 + kFaceFootprint : (double)x - kFaceFootprint;
+        const double cy = (corner & 2) ? (double)y + 1.0 + kFaceFootprint : (double)y - kFaceFootprint;
+        const double sx = cx - cr.halfW, sy = cy - cr.halfH;
+        double d[3];
+        for (int a = 0; a < 3; ++a) d[a] = cr.view[a] - cr.rx[a] * sx - cr.uy[a] * sy;
+        for (int r = 0; r < 3; ++r) q[corner][r] = c.L[r][0] * d[0] + c.L[r][1] * d[1] + c.L[r][2] * d[2];
+        qn[corner] = std::sqrt(q[corner][0] * q[corner][0] + q[corner][1] * q[corner][1] + q[corner][2] * q[corner][2]);
+        if (!std::isfinite(qn[corner]) || !(qn[corner] > 0)) return -1;
+    }
+    for (int K = 0; K < 3; ++K) {
+        const double s = c.o[K] > 0 ? 1.0 : -1.0;
+        if (!(s * c.o[K] >= 0.5 + c.clear + c.inset[K])) continue;           // (ii), and (i)'s distance
+        const double a = 0.5 * s - c.o[K];                                  // (sign -s)
+        bool ok = true;
+        for (int corner = 0; corner < 4 && ok; ++corner) {
+            const double qK = q[corner][K];
+            ok = s * qK < 0 && std::fabs(qK) >= kFaceMinSlope * qn[corner];
+            for (int side = 0; side < 2 && ok; ++side) {
+                const double lam = a * (side ? 1.0 + kFaceRho : 1.0 - kFaceRho) / qK;
+                ok = std::isfinite(lam) && lam > 0;
+                for (int j = 0; j < 3 && ok; ++j) {
+                    if (j == K) continue;
+                    const double pj = c.o[j] + lam * q[corner][j];
+                    ok = std::fabs(pj) <= 0.5 - c.inset[j];                 // (NaN fails)
+                }
+            }
+        }
+        if (ok) return 2 * K + (s > 0 ? 1 : 0);
+    }
+    return -1;
+}
+
+// `cr` (optional): a one-cube signature's pixels are split into the groups its faces resolve (camera_face_certificate) and the
+// unresolved rest, each padded to whole waves like a signature; CameraList::face names a wave's face.  A split that makes the list
+// longer than maxLen is dropped (every wave -1): the list never visits more lanes than the tiles it replaces.
+bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int shardCount, long long maxLen, CameraList &cl,
+                       const CameraResolve *cr = nullptr) {
+    cl.pix.clear(); cl.wave.clear(); cl.sigIdx.clear(); cl.face.clear();
+    cl.nSig = 0; cl.listed = 0; cl.resolved = 0;
     if (cc.rowOff.empty() || W > 32768 || H > 32768 || shardCount < 1 || shardRank < 0 || shardRank >= shardCount) return false;
     std::map<std::vector<int>, int> ids;
     std::vector<std::vector<uint32_t>> groups;        // per signature its pixels, row-major
@@ -797,22 +946,64 @@ bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int sh
             cl.listed += b - a;
         }
     }
+    auto padded = [](long long n) { return (n + 63) / 64 * 64; };
     long long len = 0;
-    for (const auto &g : groups) len += ((long long)g.size() + 63) / 64 * 64;
+    for (const auto &g : groups) len += padded((long long)g.size());
     len = (len + kBlock - 1) / kBlock * kBlock;
     if (len > maxLen) return false;
+    // the split of the one-cube signatures: per group its pixels' faces, stably sorted -- the unresolved rest (-1) first, then face by face
+    std::vector<std::vector<int>> faces(groups.size());
+    if (cr) {
+        long long lenSplit = 0;
+        for (size_t s = 0; s < groups.size(); ++s) {
+            std::vector<uint32_t> &g = groups[s];
+            if (sigs[s].size() != 1 || (size_t)sigs[s][0] >= cr->cube.size() || !cr->cube[(size_t)sigs[s][0]].ok) {
+                lenSplit += padded((long long)g.size());
+                continue;
+            }
+            std::vector<int> &f = faces[s];
+            f.resize(g.size());
+            long long n[7] = {0, 0, 0, 0, 0, 0, 0};
+            for (size_t i = 0; i < g.size(); ++i) {
+                f[i] = camera_face_certificate(*cr, sigs[s][0], (int)(g[i] & 0xffffu), (int)(g[i] >> 16));
+                ++n[f[i] + 1];
+            }
+            std::vector<uint32_t> gs(g.size());
+            std::vector<int> fs(g.size());
+            size_t at[7], o = 0;
+            for (int b = 0; b < 7; ++b) { at[b] = o; o += (size_t)n[b]; lenSplit += padded(n[b]); }
+            for (size_t i = 0; i < g.size(); ++i) { const size_t d = at[f[i] + 1]++; gs[d] = g[i]; fs[d] = f[i]; }
+            g.swap(gs);
+            f.swap(fs);
+        }
+        lenSplit = (lenSplit + kBlock - 1) / kBlock * kBlock;
+        if (lenSplit > maxLen) for (auto &f : faces) f.clear();
+        else len = lenSplit;
+    }
     cl.pix.reserve((size_t)len);
     cl.wave.reserve((size_t)len / 32);
+    cl.face.reserve((size_t)len / 64);
     for (size_t s = 0; s < groups.size(); ++s) {
         const int first = (int)cl.sigIdx.size();
         cl.sigIdx.insert(cl.sigIdx.end(), sigs[s].begin(), sigs[s].end());
         const int end = (int)cl.sigIdx.size();
-        cl.pix.insert(cl.pix.end(), groups[s].begin(), groups[s].end());
-        cl.pix.resize((cl.pix.size() + 63) / 64 * 64, kCamPad);
-        while (cl.wave.size() < cl.pix.size() / 32) { cl.wave.push_back(first); cl.wave.push_back(end); }
+        const std::vector<uint32_t> &g = groups[s];
+        const std::vector<int> &f = faces[s];
+        for (size_t i0 = 0; i0 < g.size();) {          // a run of one face (the whole group where it is not split)
+            size_t i1 = g.size();
+            const int fc = f.empty() ? -1 : f[i0];
+            if (!f.empty()) { i1 = i0; while (i1 < g.size() && f[i1] == fc) ++i1; }
+            cl.pix.insert(cl.pix.end(), g.begin() + (long)i0, g.begin() + (long)i1);
+            cl.pix.resize((cl.pix.size() + 63) / 64 * 64, kCamPad);
+            while (cl.wave.size() < cl.pix.size() / 32) { cl.wave.push_back(first); cl.wave.push_back(end); }
+            cl.face.resize(cl.pix.size() / 64, (cr && cr->off) ? -1 : fc);
+            if (fc >= 0 && !(cr && cr->off)) cl.resolved += (long long)(i1 - i0);
+            i0 = i1;
+        }
     }
     cl.pix.resize((size_t)len, kCamPad);
     cl.wave.resize((size_t)len / 32, 0);
+    cl.face.resize((size_t)len / 64, -1);
     if (cl.sigIdx.empty()) cl.sigIdx.push_back(0);
     cl.nSig = (int)sigs.size();
     return true;

@@ -733,8 +733,16 @@ void plan_classes(const SceneIn &in, ScenePlan &p) {
 int plan_camera_list(const SceneIn &in, ScenePlan &p) {
     KParams &k = p.prm;
     const bool listOff = env_flag("PT_AMD_NO_CAMERA_LIST");   // (the variable: tests only)
-    if (!listOff && !p.dof && !p.mesh && !p.many && build_camera_list(p.cc, k.W, k.H, in.o.shard_rank, in.o.shard_count, k.nLocalPad, p.cl) &&
-        !p.cl.pix.empty()) {
+    // the waves' face certificates (camera_face_certificate), where the instantiation reads them: not the textured forms
+    // (PT_AMD_NO_CAMERA_RESOLVE, tests only: the same list, every wave unresolved)
+    CameraResolve cr;
+    const bool resolve = !listOff && !p.dof && !p.mesh && !p.many && !p.tex;
+    if (resolve) {
+        build_camera_resolve(in.geoms, in.ngeoms, k, p.hg, cr);
+        cr.off = env_flag("PT_AMD_NO_CAMERA_RESOLVE");
+    }
+    if (!listOff && !p.dof && !p.mesh && !p.many &&
+        build_camera_list(p.cc, k.W, k.H, in.o.shard_rank, in.o.shard_count, k.nLocalPad, p.cl, resolve ? &cr : nullptr) && !p.cl.pix.empty()) {
         k.firstSkipped = (int)((long long)p.nLocal - p.cl.listed);
         return set_tile_space(k, k.Wp, (int)p.cl.pix.size());
     }

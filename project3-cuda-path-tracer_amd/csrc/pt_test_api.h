@@ -682,6 +682,86 @@ int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, in
     return PT_OK;
 }
 
+// host only: the list as pt_init builds it for the untextured forms -- one-cube signatures split by the face their pixels are
+// resolved to (camera_face_certificate) -- with the per-wave faces beside it; no length cap
+static bool test_camera_resolved_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, KParams &k,
+                                      std::vector<GeomDev> &hg, CameraList &cl) {
+    memset(&k, 0, sizeof k);
+    camera_params(*cam, k);
+    k.ngeoms = ngeoms;
+    hg.resize(ngeoms);
+    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i], k.pos);
+    CameraCull cc;
+    build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
+    CameraResolve cr;
+    build_camera_resolve(geoms, ngeoms, k, hg, cr);
+    return build_camera_list(cc, k.W, k.H, shard_rank, shard_count, std::numeric_limits<long long>::max(), cl, &cr);
+}
+int pt_test_camera_resolved(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
+                            int32_t *sig_idx, int32_t *face, int64_t *sizes4) {
+    if (!cam || !geoms || ngeoms < 1 || !sizes4) return fail(PT_ERR_INVALID, "pt_test_camera_resolved: bad argument");
+    if (cam->resolution[0] < 1 || cam->resolution[1] < 1) return fail(PT_ERR_INVALID, "pt_test_camera_resolved: bad resolution");
+    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(PT_ERR_INVALID, "pt_test_camera_resolved: bad shard");
+    KParams k;
+    std::vector<GeomDev> hg;
+    CameraList cl;
+    const bool built = test_camera_resolved_list(cam, geoms, ngeoms, shard_rank, shard_count, k, hg, cl);
+    sizes4[0] = built ? (int64_t)cl.pix.size() : -1;
+    sizes4[1] = (int64_t)cl.sigIdx.size();
+    sizes4[2] = cl.listed;
+    sizes4[3] = cl.resolved;
+    if (built && pix && wave2 && sig_idx && face) {
+        memcpy(pix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t));
+        memcpy(wave2, cl.wave.data(), cl.wave.size() * sizeof(int));
+        memcpy(sig_idx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int));
+        memcpy(face, cl.face.data(), cl.face.size() * sizeof(int));
+    }
+    return PT_OK;
+}
+
+int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t seed, uint64_t counts[3]) {
+    NEED_GPU();
+    if (!cam || !geoms || ngeoms < 1 || samples < 0 || samples > 4096 || !counts) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: bad argument");
+    if (cam->resolution[0] < 1 || cam->resolution[1] < 1 || (long long)cam->resolution[0] * cam->resolution[1] > (1ll << 22))
+        return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: bad resolution");
+    KParams k;
+    std::vector<GeomDev> hg;
+    CameraList cl;
+    if (!test_camera_resolved_list(cam, geoms, ngeoms, 0, 1, k, hg, cl)) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: no work list for this scene");
+    std::vector<int> entries;
+    for (size_t w = 0; w < cl.face.size(); ++w) {
+        if (cl.face[w] < 0) continue;
+        for (size_t l = 64 * w; l < 64 * w + 64; ++l)
+            if (cl.pix[l] != kCamPad) { entries.push_back((int)cl.pix[l]); entries.push_back(cl.sigIdx[(size_t)cl.wave[2 * w]]); entries.push_back(cl.face[w]); }
+    }
+    counts[0] = counts[1] = 0;
+    counts[2] = entries.size() / 3;
+    if (entries.empty()) return PT_OK;
+    const float cam16[16] = {k.view[0], k.view[1], k.view[2], k.up[0], k.up[1], k.up[2], k.right[0], k.right[1], k.right[2],
+                             k.pos[0], k.pos[1], k.pos[2], k.pixLenX, k.pixLenY, k.halfW, k.halfH};
+    DevBuf<GeomDev> dg;
+    DevBuf<float> dc;
+    DevBuf<int> de;
+    DevBuf<unsigned long long> cnt;
+    UP(dg, hg.data(), ngeoms);
+    UP(dc, cam16, 16);
+    UP(de, entries.data(), entries.size());
+    int rc = cnt.alloc(2);
+    if (rc) return rc;
+    HIPCHECK(hipMemset(cnt.p, 0, 16));
+    const long long total = (long long)(entries.size() / 3) * (samples + 4);
+    long long blocks = (total + 255) / 256;
+    if (blocks > (1 << 16)) blocks = 1 << 16;
+    hipLaunchKernelGGL(k_sweep_face_hit, dim3((unsigned)blocks), dim3(256), 0, 0, dg.p, dc.p, de.p, (int)(entries.size() / 3), samples,
+                       (unsigned long long)seed, cnt.p);
+    HIPCHECK(hipDeviceSynchronize());
+    unsigned long long h[2] = {0, 0};
+    HIPCHECK(hipMemcpy(h, cnt.p, 16, hipMemcpyDeviceToHost));
+    counts[0] = h[0];
+    counts[1] = h[1];
+    return PT_OK;
+}
+
 int pt_test_camera_cull_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t *hits, uint64_t *culled,
                               uint64_t *violations) {
     NEED_GPU();

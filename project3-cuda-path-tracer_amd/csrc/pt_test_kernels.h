@@ -733,6 +733,49 @@ __global__ void k_sweep_box_fast(const GeomDev *geoms, int ngeoms, unsigned long
     if (nh) atomicAdd(&cnt[2], (unsigned long long)nh);
     if (bad) atomicAdd(&cnt[3], (unsigned long long)bad);
 }
+// boxFaceHit (the box test of a camera ray whose pixel pt_init resolved to a cube face) next to boxIntersectionTest on the camera rays of
+// resolved pixels: entry e = {pixel x | y << 16, primitive, face}, `samples` seeded jitters per entry and then the four corners of the
+// certificate's footprint (jitter -2 / 3: rays no render sends, inside what the certificate covers).  cam16 = view, up, right, eye,
+// pixLenX, pixLenY, W / 2, H / 2.  cnt[0] = rays, cnt[1] = rays on which the two differ in (t > 0, outside, face, P bit for bit) -- must be 0.
+__global__ void k_sweep_face_hit(const GeomDev *geoms, const float *cam16, const int *entries, int nentries, int samples, unsigned long long seed,
+                                 unsigned long long *cnt) {
+    const long long per = samples + 4, total = (long long)nentries * per;
+    unsigned int nr = 0, bad = 0;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int e = (int)(i / per), k = (int)(i - (long long)e * per);
+        const int px = entries[3 * e] & 0xffff, py = (int)((uint32_t)entries[3 * e] >> 16), face = entries[3 * e + 2];
+        const GeomDev &G = geoms[entries[3 * e + 1]];
+        float jx, jy;
+        if (k < samples) {
+            unsigned long long x = seed + (unsigned long long)(i + 1) * 0x9E3779B97F4A7C15ull;
+            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+            jx = (float)(x >> 40) * (1.0f / 16777216.0f);
+            jy = (float)((x >> 16) & 0xffffffu) * (1.0f / 16777216.0f);
+        } else {
+            jx = ((k - samples) & 1) ? 3.0f : -2.0f;
+            jy = ((k - samples) & 2) ? 3.0f : -2.0f;
+        }
+        // the camera ray of k_bounce<true, ...>, operation for operation
+        const float sx = ((float)px + jx) - cam16[14];
+        const float sy = ((float)py + jy) - cam16[15];
+        const float a = cam16[12] * sx;
+        const float b = cam16[13] * sy;
+        const F3 view = f3(cam16[0], cam16[1], cam16[2]), up = f3(cam16[3], cam16[4], cam16[5]), right = f3(cam16[6], cam16[7], cam16[8]);
+        const F3 org = f3(cam16[9], cam16[10], cam16[11]);
+        const F3 dir = normalize((view - right * a) - up * b);
+        F3 P1 = f3(1, 2, 3), N1 = f3(4, 5, 6);
+        bool o1 = false;
+        const float t1 = boxIntersectionTest<false, true>(G, org, dir, P1, N1, o1);
+        const F3 P2 = boxFaceHit(G, face, dir);
+        const bool eq = t1 > 0.0f && o1 && __float_as_int(N1.x) == face && __float_as_uint(P1.x) == __float_as_uint(P2.x) &&
+                        __float_as_uint(P1.y) == __float_as_uint(P2.y) && __float_as_uint(P1.z) == __float_as_uint(P2.z);
+        bad += eq ? 0u : 1u;
+        ++nr;
+    }
+    if (nr) atomicAdd(&cnt[0], (unsigned long long)nr);
+    if (bad) atomicAdd(&cnt[1], (unsigned long long)bad);
+}
 // divUnscaled(1, s) = 1.0f / s on EVERY float of [2^-40, 2^40] (the fast normalize's reciprocal), and divUnscaled(a, d) = a / d on
 // pseudo-random pairs of the box test's range (|a| <= 2^20 + 1, 2^-40 <= |d| <= 2): bad[0] / bad[1] count bit mismatches
 __global__ void k_sweep_div_unscaled(unsigned long long seed, int per_thread, unsigned long long *bad) {

@@ -454,6 +454,9 @@ struct BounceArgs {
     const ptd::BumpGeom *bumpGeom;
     const float4 *bumpUV;
     const float4 *bumpTan;
+    // ---- camera rays from the packed work list: per wave the cube face its pixels are resolved to (pt_init: camera_face_certificate), or -1;
+    // nullptr where camPix is.  (Last: the offsets the later bounces read stay where they were)
+    const int *camFace;
 };
 typedef const PT_CAS BounceArgs *ArgsPtr;
 typedef const PT_CAS GeomDev *GeomPtr;
@@ -805,6 +808,11 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
     const bool camList = kCamListOk && launder(kargs)->camPix != nullptr;      // (wave-uniform)
     uint32_t camWord = kCamPad, camItb = 0u, camJ0 = 0u;                       // the next tile's: the lane's pixel, its iteration, first entry
     int camSig0 = 0, camSig1 = 0;                                              // ... the wave's primitives: camSigIdx[camSig0 .. camSig1)
+    // ... and the cube face the wave's pixels are resolved to, or -1 (pt_init: camera_face_certificate): such a wave's rays hit the one cube
+    // of its signature, from outside, through that face whatever their jitter -- no slab decision, no loop (ptd::boxFaceHit).  Not in the
+    // textured forms, which keep the code they ran before.
+    constexpr bool kResolveOk = kCamListOk && !TEX && !BUMP;
+    int camFace = -1;
     auto requestCam = [&](uint32_t Tq, uint32_t tid) {
         const ArgsPtr A = launder(kargs);
         const uint32_t idx0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)Tq) * kBlock;
@@ -815,6 +823,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
         const PT_CAS int *const wr = (const PT_CAS int *)(A->camWave) + 2 * wq;
         camSig0 = wr[0];
         camSig1 = wr[1];
+        if (kResolveOk) camFace = ((const PT_CAS int *)(A->camFace))[wq];
     };
     // the first tile of this workgroup that needs work, and its paths
     uint32_t T = blockIdx.x - rowShift;      // (FIRST with rotated bands: the first tile of the row; else the tile itself)
@@ -857,6 +866,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
         int px = 0, py = 0;                                     // pixel coordinates (FIRST only)
         uint32_t recIdx0 = 0u;                                  // FIRST, MESH: the tile's first index in the padded pixel space (BounceArgs::meshHit)
         int sig0 = 0, sig1 = 0;                                 // FIRST from the work list: the wave's primitives
+        int sigFace = -1;                                       // ... and the face they are resolved to (wave-uniform), or -1
         if (FIRST && camList) {
             // (no scene-rectangle skip: the list holds only pixels some primitive's span covers, and no tile of padding alone)
             const uint32_t w = camWord;
@@ -866,6 +876,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
             itb = (int)camItb;
             sig0 = camSig0;
             sig1 = camSig1;
+            if (kResolveOk) sigFace = camFace;
         } else if (FIRST) {
             const ArgsPtr A = launder(kargs);
             const PT_CAS KParams &prm = A->prm;
@@ -1043,7 +1054,16 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
             // Sphere-heavy scenes, later bounces: the spheres come from their packed culling data (order does not matter: the
             // nearest hit is taken by (distance, file order)), AFTER the loop over the primitives that are not spheres.
             constexpr bool PACKED = MANY && !FIRST;
-            if (inScene) {
+            if (kResolveOk && sigFace >= 0) {
+                // a resolved wave of the work list: the one cube of its signature, entered through the certified face
+                const ArgsPtr A = launder(kargs);
+                const int g = ((const PT_CAS int *)(A->camSigIdx))[sig0];
+                const PT_CAS GeomDev &G = *(launder((GeomPtr)(A->ggeoms)) + g);
+                P = boxFaceHit(G, sigFace, dir);
+                hit = g;
+                nsrc = f3(__int_as_float(sigFace), 0.0f, 0.0f);
+                outsideI = 1;
+            } else if (inScene) {
                 const ArgsPtr A = launder(kargs);
                 // a later tile looks at the list of its class; a camera-ray tile (256 pixels of one image row) at the list of
                 // its row -- the primitives whose pixel rectangle covers that row -- and their rectangles sort the lanes out
@@ -1074,7 +1094,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 const GeomPtr geoms = (GeomPtr)(A->ggeoms);
                 const bool earlyMiss = FIRST || hotWalls(hotNow()) == 0u || (tileCls & 7u) >= 6u;    // (wave-uniform)
                 // a later tile whose class lists ONE primitive (its paths' one wall): a hit's distance is compared with nothing (PACKED: the spheres follow)
-                const bool onlyOne = !FIRST && !PACKED && gk1 - gk0 == 1;
+                // (... and an unresolved wave of the work list whose signature is one primitive)
+                const bool onlyOne = ((!FIRST && !PACKED) || (kResolveOk && camList)) && gk1 - gk0 == 1;
                 for (int gk = gk0; gk < gk1; ++gk) {
                     int g, span = 0;
                     if (FIRST && listed && !camList) {
