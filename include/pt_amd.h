@@ -97,7 +97,14 @@ enum {
                                     it adds to the accumulator, in the same iteration order.  What pt_readback_moments, pt_variance and
                                     pt_denoise_var need.  The accumulator is bit-identical to the one without the flag.  PT_ERR_INVALID with
                                     shard_count > 1 or PT_FLAG_ACCUM_SHARD_ROWS, and from pt_group_init. */
-    PT_FLAG_DIRECT_LIGHTING = 4  /* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
+    PT_FLAG_TEMPORAL = 64,       /* temporal reprojection (section "temporal reprojection" below): a pt_init over the LIVE renderer of the same context
+                                    -- no pt_free in between -- keeps the old view's colour, second moment and sample count per pixel as the
+                                    context's HISTORY, and pt_denoise_var / pt_denoise_var_rgba8 of the new renderer filter the count-weighted blend
+                                    of that history, reprojected, with the new samples.  Nothing else reads it: both accumulators, pt_variance,
+                                    pt_noise_stats, pt_iterate_until, pt_readback* and pt_denoise are the unflagged renderer's bit for bit, and so is
+                                    pt_denoise_var while the context holds no history.  PT_ERR_INVALID without PT_FLAG_MOMENTS, with
+                                    PT_FLAG_TRACE_AHEAD, and with lens_radius > 0 (a thin lens has no single projection). */
+    PT_FLAG_DIRECT_LIGHTING = 4 /* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
                                     that ray hits (traceDepth + 1 launches; traceDepth <= PT_MAX_DEPTH - 1).  A mesh is an
@@ -242,7 +249,8 @@ typedef struct PtBumpBinding {
 int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes);
 
 /* pathtraceInit: upload scene, allocate the accumulator and the SoA path-state buffers.
- * Replaces reference src/pathtrace.cu:75-85.  Calling it twice without pt_free re-initialises.
+ * Replaces reference src/pathtrace.cu:75-85.  Calling it twice without pt_free re-initialises (and, between two PT_FLAG_TEMPORAL renderers
+ * of one resolution, is what carries the old view's samples over as the context's history: section "temporal reprojection").
  * A scene or an option that is refused -- every PT_ERR_INVALID -- is refused before anything is touched: nothing is allocated or released,
  * and the renderer that was there stays initialised and usable.  PT_ERR_NO_GPU and PT_ERR_HIP (a failed HIP call; pools that do not fit
  * the free device memory, which is measured after the old renderer has given its own back) leave the context without a renderer. */
@@ -365,6 +373,32 @@ typedef struct PtNoiseTarget {
     int32_t min_samples, max_samples, check_every, lookahead;
 } PtNoiseTarget;
 int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t target_struct_bytes, PtNoiseStats *out, int32_t *samples_done);
+
+/* ---- temporal reprojection (PT_FLAG_TEMPORAL; the temporal half of SVGF, Schied et al., HPG 2017, for a static scene under a moving pinhole
+ * camera; csrc/pt_temporal.h gives every operation, tests/temporal_ref.py restates it).  No function of its own: a flag, and what pt_init,
+ * pt_free and pt_denoise_var do under it.
+ *   HISTORY belongs to the context: per pixel of the OLD view its mean colour, mean squared luminance and effective sample count (at most
+ *   PT_TEMPORAL_MAX_HISTORY), that view's guide buffers of guide_iter 1 and its camera.  It is made at one moment only: pt_init called over a
+ *   live renderer (the "calling it twice re-initialises" path) when the old and the new renderer both carry the flag and have the same
+ *   resolution, the new scene has been accepted, and the old renderer has committed at least one iteration (its sample count is the number of
+ *   iterations it committed since its pt_init -- pt_counters_reset, which leaves the accumulators alone, leaves that count alone too).  The capture is recursive: what is kept is the old view's own blend of ITS history with ITS samples, so a camera
+ *   dragged through many views of a few samples each keeps accumulating up to the cap.  An old renderer without a committed iteration leaves
+ *   the history there was, with the camera it was made for.  An old view whose guide buffers cannot be made (pt_gbuffer's PT_ERR_INVALID: a
+ *   mesh hierarchy too deep for its stacks) ends the history instead: pt_init drops it and goes on.  A HIP call that fails during the capture is
+ *   PT_ERR_HIP like any other of pt_init's, and leaves the context without a renderer.  pt_free, pt_ctx_destroy, the exit handler and a pt_init without the flag or with
+ *   another resolution drop it; a refused pt_init leaves it as it was.  "The same scene" is the caller's promise: a caller that changes the scene
+ *   calls pt_free first.
+ *   pt_denoise_var / pt_denoise_var_rgba8 of a renderer whose context holds history: the new pixel's first hit (the guide buffers of the call's
+ *   guide_iter) is projected into the old camera; of the four old pixels around it those count that hold history, show the same primitive, a
+ *   normal within dot >= PT_TEMPORAL_NORMAL_DOT and lie within PT_TEMPORAL_PLANE_FRACTION * t of the new hit's tangent plane (t: the new hit's
+ *   distance); their bilinear weights must add up to more than PT_TEMPORAL_MIN_WEIGHT.  History hc of count Nh and the new sums S, Q of n
+ *   samples blend to c = (hc Nh + S) / (Nh + n), m2 = (hm2 Nh + Q) / (Nh + n), variance max(m2 - lum(c)^2, 0) / (Nh + n - 1): level 0 of the
+ *   filter reads that image instead of the accumulators' mean and variance.  A pixel without valid history (a disocclusion, the frame's edge)
+ *   gets exactly what it got without the flag. */
+#define PT_TEMPORAL_MAX_HISTORY 32.0f
+#define PT_TEMPORAL_NORMAL_DOT 0.9f
+#define PT_TEMPORAL_PLANE_FRACTION 0.01f
+#define PT_TEMPORAL_MIN_WEIGHT 0.5f
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

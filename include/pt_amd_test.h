@@ -169,9 +169,24 @@ int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, 
  * choice per level, 1: the plain gather, 2 / 3: LDS tiles of 64 x 4 / 64 x 8 pixels of a residue class -- every form gives the same bits.
  * ms (or NULL): 1 + levels kernel times by HIP events, k_gbuffer first (0 when the guide buffers were cached), then each level. */
 int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms);
-/* ... and pt_denoise_var with the form of k_atrous_var named, the same four forms; var_host may be NULL; ms as above. */
+/* ... and pt_denoise_var with the form of k_atrous_var named, the same four forms; var_host may be NULL; ms as above (on a renderer whose context
+ * holds history -- PT_FLAG_TEMPORAL -- k_temporal runs between k_gbuffer and level 0 and belongs to neither time). */
 int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms);
 int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
+/* temporal reprojection (pt_amd.h, csrc/pt_temporal.h).  cam16 = the old view's camera as k_temporal takes it, 16 floats: eye (3), pixLenX,
+ * pixLenY, halfW, halfH, then the rows r0, r1, r2 of the inverse of [view | -right | -up].
+ * pt_test_temporal_camera (host only, no GPU needed): cam16 of a PtCamera, by the function pt_init's capture calls.
+ * pt_test_temporal: k_temporal over host arrays of any w x h, no renderer needed -- capture 0: the filter form, out4 = (c, variance), out_n unused
+ * (may be NULL); capture 1: out4 = Hc', out_n = Hn'.  The current view: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h), pos_t4 / nrm_id4 its guide
+ * buffers as the device holds them (w * h * 4 each, .w of the second = the bits of the int32 primitive index); the history: hc4, hn, hpos_t4,
+ * hnrm_id4 likewise.  ms (or NULL) with reps >= 1: `reps` kernel times by HIP events, after one untimed launch.
+ * pt_test_history: the history THIS library's current context holds -- wh2 = its frame size, {0, 0}: none (nothing else is written then); every
+ * other pointer may be NULL. */
+int pt_test_temporal_camera(const PtCamera *cam, float *cam16);
+int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_sum, const float *lum_sq_sum, const float *pos_t4, const float *nrm_id4,
+                     const float *hc4, const float *hn, const float *hpos_t4, const float *hnrm_id4, const float *cam16, float *out4, float *out_n,
+                     int reps, float *ms);
+int pt_test_history(int32_t *wh2, float *hc4, float *hn, float *hpos_t4, float *hnrm_id4, float *cam16);
 /* the noise statistics (pt_amd.h, csrc/pt_noise.h): k_noise_stats -- the kernel pt_noise_stats launches -- over host arrays of any w x h, no
  * renderer needed: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h); out, tile_rel_var_host (or NULL) as pt_noise_stats.  tiles_per_wave: how many
  * tiles a wave of the grid takes, 1..64, 0 = the library's choice -- every value gives the same bits.  ms (or NULL) with

@@ -46,6 +46,10 @@ PT_FLAG_DIRECT_LIGHTING = 4
 PT_FLAG_TRACE_AHEAD = 8
 PT_FLAG_MIXTURE_WEIGHTED = 16
 PT_FLAG_MOMENTS = 32
+PT_FLAG_TEMPORAL = 64
+# the constants of temporal reprojection (include/pt_amd.h): the cap on a pixel's effective history, the least dot of the two normals, the
+# largest distance from the new hit's tangent plane as a fraction of the hit's distance, the least sum of bilinear weights
+PT_TEMPORAL_MAX_HISTORY, PT_TEMPORAL_NORMAL_DOT, PT_TEMPORAL_PLANE_FRACTION, PT_TEMPORAL_MIN_WEIGHT = 32.0, 0.9, 0.01, 0.5
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -75,7 +79,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
-    "pt_test_renderer_state", "pt_test_scene_plan",
+    "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
 ]
 
 
@@ -241,6 +245,9 @@ def _bind(L, with_tests):
         L.pt_test_denoise_var.argtypes = [i32, C.POINTER(PtDenoiseVarParams), C.c_size_t, i32, vp, vp, vp]
         L.pt_test_noise_stats.argtypes = [vp, vp, i32, i32, i32, C.c_float, C.c_float, C.POINTER(PtNoiseStats), C.c_size_t, vp, i32, i32, vp]
         L.pt_test_exp_neg_poly.argtypes = [vp, i32, vp]
+        L.pt_test_temporal_camera.argtypes = [vp, vp]
+        L.pt_test_temporal.argtypes = [i32, i32, i32, i32] + [vp] * 11 + [i32, vp]
+        L.pt_test_history.argtypes = [vp] * 6
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
@@ -427,8 +434,11 @@ _scene = None
 
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
-                  mixture_weighted=False, moments=False):
+                  mixture_weighted=False, moments=False, temporal=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    temporal: PT_FLAG_TEMPORAL (with moments=True, no lens, no trace_ahead) -- calling pathtraceInit AGAIN, WITHOUT pathtraceFree() in between,
+    with a moved camera is what carries the last view's samples over as history: denoise_var / denoise_var_rgba8 of the new renderer then filter
+    the blend of the reprojected history with the new samples.  pathtraceFree() drops the history (call it when the scene itself changes).
     moments: PT_FLAG_MOMENTS -- the renderer also sums every sample's squared luminance (readback_moments, variance, denoise_var).
     lens_radius / focal_distance / direct_lighting: the README extras (depth of field, direct lighting), off by default.
     trace_ahead: PT_FLAG_TRACE_AHEAD -- pathtrace(pbo, frame, iter) called once per iteration draws on batches of max_batch
@@ -442,6 +452,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_MIXTURE_WEIGHTED
     if moments:
         flags |= PT_FLAG_MOMENTS
+    if temporal:
+        flags |= PT_FLAG_TEMPORAL
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -793,6 +805,46 @@ def test_noise_stats(rgb_sum, lum_sq_sum, w, h, samples, threshold, lum_floor=NO
                                            _p(ms) if timing_reps > 0 else None))
     res = _noise_result(st, tm)
     return (res, ms) if timing_reps > 0 else res
+
+
+def test_temporal_camera(camera):
+    """pt_test_temporal_camera (host only): the 16 floats k_temporal takes for a view -- eye, pixLenX, pixLenY, halfW, halfH, the rows r0, r1, r2 --
+    of a CAMERA_DTYPE record."""
+    cam = np.ascontiguousarray(camera)
+    out = np.empty(16, np.float32)
+    _tcheck(test_lib().pt_test_temporal_camera(_p(cam), _p(out)))
+    return out
+
+
+def test_temporal(capture, w, h, samples, rgb_sum, lum_sq_sum, pos_t, nrm_id, hc, hn, hpos_t, hnrm_id, cam16, timing_reps=0):
+    """k_temporal over host arrays (test library, no renderer): the current view's S (h, w, 3), Q (h, w) and guide buffers pos_t, nrm_id
+    ((h, w, 4) float32 each, nrm_id[..., 3] = the bits of the int32 primitive index), the history hc (h, w, 4), hn (h, w) and its guides, the old
+    camera's 16 floats.  capture=False: the filter form, (h * w, 4) = (c, variance); capture=True: (Hc' (h * w, 4), Hn' (h * w,)).
+    timing_reps > 0: also the kernel times in ms."""
+    f = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(w * h * k)
+    S, Q, pos, nrm, Hc, Hn, Hpos, Hnrm = f(rgb_sum, 3), f(lum_sq_sum, 1), f(pos_t, 4), f(nrm_id, 4), f(hc, 4), f(hn, 1), f(hpos_t, 4), f(hnrm_id, 4)
+    cam = np.ascontiguousarray(cam16, np.float32).reshape(16)
+    out, out_n = np.empty((w * h, 4), np.float32), np.empty(w * h, np.float32)
+    ms = np.zeros(max(timing_reps, 1), np.float32)
+    _tcheck(test_lib().pt_test_temporal(1 if capture else 0, w, h, samples, _p(S), _p(Q), _p(pos), _p(nrm), _p(Hc), _p(Hn), _p(Hpos), _p(Hnrm), _p(cam),
+                                        _p(out), _p(out_n), timing_reps, _p(ms) if timing_reps > 0 else None))
+    res = (out, out_n) if capture else out
+    return (res, ms) if timing_reps > 0 else res
+
+
+def test_history():
+    """pt_test_history: the history the test library's current context holds (inside renderer_from_test_library) -- None, or a dict of hc
+    (H, W, 4), hn (H, W), hpos_t, hnrm_id (H, W, 4) and cam (16,)."""
+    T = test_lib()
+    wh = np.zeros(2, np.int32)
+    _tcheck(T.pt_test_history(_p(wh), None, None, None, None, None))
+    w, h = int(wh[0]), int(wh[1])
+    if w == 0:
+        return None
+    hc, hn, hpos, hnrm = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+    cam = np.empty(16, np.float32)
+    _tcheck(T.pt_test_history(_p(wh), _p(hc), _p(hn), _p(hpos), _p(hnrm), _p(cam)))
+    return dict(hc=hc, hn=hn, hpos_t=hpos, hnrm_id=hnrm, cam=cam)
 
 
 def test_exp_neg_poly(a):

@@ -42,6 +42,7 @@
 #include "pt_mesh.h"
 #include "pt_denoise.h"
 #include "pt_noise.h"
+#include "pt_temporal.h"
 // The entry points of include/pt_amd_test.h (device primitives one by one, soundness sweeps, the fault-word hook) exist only in
 // the second link target of this source, libpt_amd_test.so (-DPT_TEST_API): the product library exports none of them.
 #ifdef PT_TEST_API
@@ -163,6 +164,17 @@ struct Slot {
     int parity = 0;                // which half of Ctrl::cursor the slot's next batch uses
 };
 
+// PT_FLAG_TEMPORAL: what a context keeps of the view its last renderer rendered (pt_temporal.h).  Made by pt_init over a live renderer
+// (capture_history), read by denoise_var_run, dropped by free_renderer unless pt_init asks to keep it.
+struct History {
+    DevBuf<float4> hc[2];           // (mean r, g, b, mean squared luminance): a ping-pong pair, `cur` the half that holds the history ...
+    DevBuf<float> hn[2];            // ... and the effective sample counts, 0 = none
+    DevBuf<float4> hpos, hnrm;      // the old view's guide buffers of guide_iter 1, handed over by its renderer
+    TemporalCam cam = {};           // the old view's camera
+    int cur = 0, W = 0, H = 0;
+    bool live = false;
+};
+
 // (it keeps the scalars of the scene's plan -- cam, prm, P, nLocal, flags, the flags that pick the forms of k_bounce, the sizes -- as its base)
 struct State : PlanScalars {
     bool init = false;
@@ -214,6 +226,7 @@ struct State : PlanScalars {
     int gridFirst = 0;      // ... and of k_bounce<true> (its own register budget, hence its own residency)
     const void *kernFirst = nullptr, *kernNext = nullptr;   // the forms of k_bounce the camera-ray launch / the later ones take (bounce_form)
     long long iterations = 0;
+    long long committed = 0; // iterations committed into the accumulators since pt_init: `iterations` without pt_counters_reset's zeroing (the capture's n)
     long long seq = 0;      // batches enqueued since pt_init: slot = seq % nslots
     // PT_FLAG_TRACE_AHEAD: batches traced ahead of the pt_iterate calls that will ask for their iterations, oldest first.
     // A parked batch occupies its slot (radiance buffers, iteration masks) until its last iteration is committed or it
@@ -247,6 +260,8 @@ struct State : PlanScalars {
     std::vector<HostTexBinding> texBindings;
     // ... and the height maps registered by pt_set_bump_maps (texture: an index into `textures`)
     std::vector<HostBumpBinding> bumpBindings;
+    // ... and, across a pt_init over the live renderer only, the last view's samples (PT_FLAG_TEMPORAL)
+    History hist;
 };
 
 // Renderer instances.  The reference keeps its renderer in file-static globals (src/pathtrace.cu:70-71: one per process, not
@@ -630,7 +645,7 @@ int discard_ahead() {
 // so that no launch of this process is still executing when its queues, its code object and its memory go away.
 extern "C" void pt_free(void);
 extern "C" void pt_group_destroy(PtGroup *g);
-void free_renderer();
+void free_renderer(bool keepHistory = false);
 void exit_handler() {
     for (;;) {                                    // groups the host forgot: their members' renderers, threads, RCCL communicators, buffers
         PtGroup *g = nullptr;
@@ -686,6 +701,9 @@ int denoise_refusals(const char *who) {
     return PT_OK;
 }
 
+// dynamic LDS k_gbuffer needs for the renderer's scene: the lanes' mesh traversal stacks (a launch holds at most 64 KB)
+size_t guide_stack_bytes() { return R().mesh ? (size_t)std::max(R().meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0; }
+
 // the guide buffers of iteration `guideIter`, on the caller's stream (cached until pt_init / pt_free); ms: the kernel's time, 0 when cached
 int ensure_guides(int guideIter, float *ms) {
     if (ms) *ms = 0.0f;
@@ -694,7 +712,7 @@ int ensure_guides(int guideIter, float *ms) {
     if (!R().dnPosT.p) PTCHECK(R().dnPosT.alloc(P));
     if (!R().dnNrmId.p) PTCHECK(R().dnNrmId.alloc(P));
     if (R().dnGuideIter == guideIter) return PT_OK;
-    const size_t stackBytes = R().mesh ? (size_t)std::max(R().meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0;
+    const size_t stackBytes = guide_stack_bytes();
     if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "guide buffers: a mesh hierarchy needs %d stack levels", R().meshStackNeed);
     EventSet es;
     hipEvent_t &e0 = es.ev[0], &e1 = es.ev[1];
@@ -785,6 +803,63 @@ int denoise_to_host(int samples, const PtDenoiseParams *p, size_t bytes, int for
     return readback_fault();
 }
 
+// ---- temporal reprojection (pt_temporal.h) -----------------------------------------------------------------------------------------------
+// The old view's camera as k_temporal projects into it: camera_params takes `view` and `up` as given -- not unit, not orthogonal -- so the
+// rows are the inverse of the 3 x 3 matrix [view | -right | -up], in double, rounded once: the exact inverse of cameraRayAt's pinhole map.
+// (A singular basis -- view parallel to up -- gives rows that are not finite: every pixel then fails step 2 or 3 and has no history.)
+TemporalCam temporal_camera(const KParams &k) {
+    const double m[3][3] = {{k.view[0], -(double)k.right[0], -(double)k.up[0]},
+                            {k.view[1], -(double)k.right[1], -(double)k.up[1]},
+                            {k.view[2], -(double)k.right[2], -(double)k.up[2]}};
+    const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    const double det = m[0][0] * c00 + m[0][1] * c01 + m[0][2] * c02;
+    const double inv[3][3] = {{c00 / det, (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det, (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det},
+                              {c01 / det, (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det, (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det},
+                              {c02 / det, (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det, (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det}};
+    TemporalCam c;
+    for (int a = 0; a < 3; ++a) {
+        c.e[a] = k.pos[a];
+        c.r0[a] = (float)inv[0][a];
+        c.r1[a] = (float)inv[1][a];
+        c.r2[a] = (float)inv[2][a];
+    }
+    c.pixLenX = k.pixLenX; c.pixLenY = k.pixLenY; c.halfW = k.halfW; c.halfH = k.halfH;
+    return c;
+}
+
+// pt_init over a live PT_FLAG_TEMPORAL renderer that has committed R().committed >= 1 iterations: the old view's blend of ITS history with
+// ITS samples becomes the context's history (k_temporal<true> into the other half of the ping-pong pair), its guide buffers of iteration 1
+// -- the cached ones, or one k_gbuffer launch -- are handed over, and its camera is kept.  On the old renderer's stream, behind its commits.
+int capture_history() {
+    State &S = R();
+    History &hs = S.hist;
+    if (S.device >= 0) HIPCHECK(hipSetDevice(S.device));
+    PTCHECK(ensure_guides(1, nullptr));
+    const size_t P = (size_t)S.P;
+    const int nxt = hs.live ? hs.cur ^ 1 : 0;
+    if (!hs.hc[nxt].p) PTCHECK(hs.hc[nxt].alloc(P));
+    if (!hs.hn[nxt].p) PTCHECK(hs.hn[nxt].alloc(P));
+    TemporalArgs T;
+    T.accum = S.image; T.moments = S.moments.p;
+    T.posT = S.dnPosT.p; T.nrmId = S.dnNrmId.p;
+    T.hc = hs.live ? hs.hc[hs.cur].p : nullptr; T.hn = hs.live ? hs.hn[hs.cur].p : nullptr;
+    T.hpos = hs.hpos.p; T.hnrm = hs.hnrm.p;
+    T.cam = hs.cam;
+    T.W = S.prm.W; T.H = S.prm.H;
+    T.samples = (float)S.committed;       // (not `iterations`: pt_counters_reset zeroes that one and leaves the accumulators)
+    T.out = hs.hc[nxt].p; T.outN = hs.hn[nxt].p;
+    hipLaunchKernelGGL(k_temporal<true>, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(S.stream));      // (the guides it read are released next)
+    hs.hpos = std::move(S.dnPosT);
+    hs.hnrm = std::move(S.dnNrmId);
+    S.dnGuideIter = 0;
+    hs.cam = temporal_camera(S.prm);
+    hs.cur = nxt; hs.W = S.prm.W; hs.H = S.prm.H;
+    hs.live = true;
+    return PT_OK;
+}
+
 // ---- the second moments and the variance-guided filter (pt_denoise.h, k_atrous_var_*) ---------------------------------------------------
 int moments_refusals(const char *who) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
@@ -816,6 +891,23 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc(P));
     for (int k = 0; k < 2 && k < p->levels - 1; ++k)
         if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
+    // PT_FLAG_TEMPORAL with history: level 0 reads the blend of the reprojected history with the accumulators (k_temporal, into the ping-pong
+    // half the level before level 0 would have written) and so runs as a later level at step 1
+    const History &hist = R().hist;
+    const bool temporal = (R().flags & PT_FLAG_TEMPORAL) && hist.live && hist.W == R().prm.W && hist.H == R().prm.H;
+    if (temporal) {
+        if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc(P));
+        TemporalArgs T;
+        T.accum = R().image; T.moments = R().moments.p;
+        T.posT = R().dnPosT.p; T.nrmId = R().dnNrmId.p;
+        T.hc = hist.hc[hist.cur].p; T.hn = hist.hn[hist.cur].p; T.hpos = hist.hpos.p; T.hnrm = hist.hnrm.p;
+        T.cam = hist.cam;
+        T.W = R().prm.W; T.H = R().prm.H;
+        T.samples = (float)samples;
+        T.out = R().dnPing[1].p; T.outN = nullptr;
+        hipLaunchKernelGGL(k_temporal<false>, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, R().stream, T);
+        HIPCHECK(hipGetLastError());
+    }
     AtrousVarArgs A;
     A.accum = R().image; A.moments = R().moments.p;
     A.posT = R().dnPosT.p; A.nrmId = R().dnNrmId.p;
@@ -829,9 +921,9 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     if (ms)
         for (int i = 0; i <= p->levels; ++i) HIPCHECK(hipEventCreate(&ev[i]));
     for (int i = 0; i < p->levels; ++i) {
-        const bool first = i == 0, last = i == p->levels - 1;
+        const bool first = i == 0 && !temporal, last = i == p->levels - 1;
         A.step = 1 << i;
-        A.cin = first ? nullptr : R().dnPing[(i - 1) & 1].p;
+        A.cin = first ? nullptr : R().dnPing[(i + 1) & 1].p;
         A.cout = last ? nullptr : R().dnPing[i & 1].p;
         A.out3 = last ? R().dnOut.p : nullptr;
         A.outVar = last && wantVar ? R().dnVar.p : nullptr;
@@ -937,7 +1029,8 @@ void pt_free(void) {
 #pragma GCC visibility pop
 namespace {
 // everything pt_init allocated (pt_free, and pt_init's own restart)
-void free_renderer() {
+void free_renderer(bool keepHistory) {
+    if (!keepHistory) R().hist = History();        // (pt_init alone keeps it: a re-initialisation of a PT_FLAG_TEMPORAL renderer)
     // pathtraceFree before the first Init (src/main.cpp:91-94) must be a no-op
     if (!R().init && !R().image && !R().dgeoms.p && R().nslots == 0 && !R().hostFault && !R().pinnedHost) return;
     if (R().device >= 0 && R().nslots > 0) (void)hipSetDevice(R().device);     // (a host that switched devices in between)
@@ -966,7 +1059,9 @@ void free_renderer() {
         std::vector<HostTexture> keepTex = std::move(R().textures);
         std::vector<HostTexBinding> keepBind = std::move(R().texBindings);
         std::vector<HostBumpBinding> keepBump = std::move(R().bumpBindings);
+        History keepHist = std::move(R().hist);
         R() = State();
+        R().hist = std::move(keepHist);
         R().meshes = std::move(keep);
         R().textures = std::move(keepTex);
         R().texBindings = std::move(keepBind);
@@ -1072,7 +1167,22 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
     register_exit_handler();
-    free_renderer();
+    // PT_FLAG_TEMPORAL on the renderer that goes and on the one that comes, the same frame size and device: the context's history lives on,
+    // and the old view -- if it committed anything -- is blended into it first, on the old renderer's stream (free_renderer waits for it)
+    bool keepHistory = R().init && (R().flags & plan.flags & PT_FLAG_TEMPORAL) && R().prm.W == plan.prm.W && R().prm.H == plan.prm.H &&
+                       (o.device < 0 || o.device == R().device);
+    // (an old view whose scene k_gbuffer cannot trace -- a mesh hierarchy deeper than its 64 KB of stacks, the one thing pt_gbuffer answers
+    // PT_ERR_INVALID to -- has no guides to reproject through: the history ends there, and pt_init goes on.  What is left to fail in the
+    // capture is a HIP call: PT_ERR_HIP, which leaves the context without a renderer like every other one of pt_init's.)
+    if (keepHistory && R().committed >= 1 && guide_stack_bytes() > 64 * 1024) keepHistory = false;
+    if (keepHistory && R().committed >= 1) {
+        const int rc = capture_history();
+        if (rc) {
+            free_renderer();
+            return rc == PT_ERR_INVALID ? fail(PT_ERR_HIP, "pt_init: the capture of the old view failed: %s", std::string(g_err).c_str()) : rc;
+        }
+    }
+    free_renderer(keepHistory);
 
     State &S = R();
     static_cast<PlanScalars &>(S) = plan;
@@ -1264,6 +1374,7 @@ int pt_iterate_batch(int frame, int first_iter, int count, void *rgba8_dev) {
         HIPCHECK(hipGetLastError());
     }
     R().iterations += count;
+    R().committed += count;
     return PT_OK;
 }
 

@@ -234,6 +234,11 @@ int check_scene(const SceneIn &in) {
     if (o.shard_count < 1 || o.shard_rank < 0 || o.shard_rank >= o.shard_count) return fail(PT_ERR_INVALID, "pt_init: bad shard %d/%d", o.shard_rank, o.shard_count);
     if ((o.flags & PT_FLAG_MOMENTS) && (o.shard_count > 1 || (o.flags & PT_FLAG_ACCUM_SHARD_ROWS)))
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOMENTS needs the whole frame: no row shard, no PT_FLAG_ACCUM_SHARD_ROWS");
+    if (o.flags & PT_FLAG_TEMPORAL) {
+        if (!(o.flags & PT_FLAG_MOMENTS)) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_TEMPORAL needs PT_FLAG_MOMENTS (history carries the second moment)");
+        if (o.flags & PT_FLAG_TRACE_AHEAD) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_TEMPORAL is not for PT_FLAG_TRACE_AHEAD renderers");
+        if (o.lens_radius > 0.0f) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_TEMPORAL needs the pinhole camera (a thin lens has no single projection)");
+    }
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;

@@ -1,0 +1,132 @@
+// pt_temporal.h -- temporal reprojection (PT_FLAG_TEMPORAL): the temporal half of SVGF (Schied et al., HPG 2017) for a static scene under a
+// moving pinhole camera.  One kernel, outside the render path like the denoiser's (k_bounce, k_mesh_walk, k_commit and their arguments do not
+// know of it); included by pt_api.hip only.
+//   k_temporal<false>   the FILTER form: per pixel of the new view the count-weighted blend of the reprojected history with the new samples, as
+//                       the (r, g, b, variance) image level 0 of k_atrous_var_* then reads in place of meanAndVariance(S, Q)
+//   k_temporal<true>    the CAPTURE form: the same blend, stored as the next history (mean colour, mean squared luminance; the capped count)
+//
+// ---- the kernel, operation by operation (tests/temporal_ref.py restates it in numpy, bit for bit: every fp32 operation below is one IEEE
+// operation, -ffp-contract=off, in the order written; dot = (x + y) + z as ptd::dot) ----
+//   inputs      the current view: S (packed RGB sums), Q (sums of squared luminance), n = (float)samples, the guides (P, t) and (N, id);
+//               the history: Hc = (mean r, g, b, mean squared luminance m2), Hn = effective sample count (0: none), the old view's guides
+//               Hpos = (P_q, t_q), Hnrm = (N_q, id_q), and the old camera: eye e, pixLenX, pixLenY, halfW, halfH and the rows r0, r1, r2 of the
+//               inverse of [view | -right | -up] (the host inverts in double and rounds once: temporal_camera), the exact inverse of
+//               cameraRayAt's pinhole map dir ~ (view - right a) - up b
+//   1           id < 0: no history
+//   2           d = P - e;  s = dot(r0, d);  !(s > 0): no history (behind the old camera; a NaN lands here)
+//   3           a = dot(r1, d) / s;  b = dot(r2, d) / s;  u = (a / pixLenX + halfW) - 0.5f;  v = (b / pixLenY + halfH) - 0.5f;
+//               !(u > -1 && u < W && v > -1 && v < H): no history (W, H as floats; a NaN lands here)
+//   4           x0 = floor(u), wx = u - x0;  y0 = floor(v), wy = v - y0
+//   5           four taps q = (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner.  A tap counts iff q is inside the frame, Hn[q] > 0, id_q == id
+//               (integers), dot(N_q, N) >= c_n and |dot(P_q - P, N)| <= c_p * t.  Then w = (i ? wx : 1 - wx) * (j ? wy : 1 - wy);
+//               sumW += w;  sumC.k += Hc[q].k * w (k = r, g, b, m2);  sumN += Hn[q] * w  -- all from 0
+//   6           !(sumW > w_min): no history.  Else hc = sumC / sumW, hn = sumN / sumW, Nh = hn < cap ? hn : cap
+//   7           no history: hc = 0, Nh = 0.  tot = Nh + n;  c.k = (hc.k * Nh + S.k) / tot;  m2 = (hc.m2 * Nh + Q) / tot
+//   8  filter   L = atrousLum(c);  dd = m2 - L * L;  dd = dd > 0 ? dd : 0 (a NaN gives 0);  out = (c, dd / (tot - 1))
+//      capture  Hc' = (c, m2);  Hn' = tot < cap ? tot : cap
+// Without history step 7 is 0 * 0 + S = S over n and step 8 is meanAndVariance(S, Q) to the bit (sums are never -0: they grow from +0).
+// cap, c_n, c_p, w_min: PT_TEMPORAL_MAX_HISTORY, _NORMAL_DOT, _PLANE_FRACTION, _MIN_WEIGHT of include/pt_amd.h.
+//
+// Cost: a gather.  A pixel reads its own 60 bytes (S 12, Q 4, two guide float4s 32, and 12 of padding it does not use), up to four taps of
+// 52 bytes from four arrays -- neighbouring pixels project to neighbouring old pixels, so a wave's taps fall into the cache lines its
+// neighbours fetch -- and writes 16 (filter) or 20 bytes (capture).
+#pragma once
+#include "pt_denoise.h"
+
+namespace ptk {
+
+// the old view's camera as the kernel needs it: plain fp32 constants
+struct TemporalCam {
+    float e[3];
+    float pixLenX, pixLenY, halfW, halfH;
+    float r0[3], r1[3], r2[3];
+};
+
+struct TemporalArgs {
+    const float *accum, *moments;     // S, Q of the current view
+    const float4 *posT, *nrmId;       // its guides
+    const float4 *hc;                 // history: (mean r, g, b, m2) ...
+    const float *hn;                  // ... the effective sample count (NULL: the context holds no history -- every pixel takes step 7 without) ...
+    const float4 *hpos, *hnrm;        // ... and the old view's guides
+    TemporalCam cam;
+    int W, H;
+    float samples;
+    float4 *out;                      // filter: (c, variance); capture: Hc'
+    float *outN;                      // capture: Hn'
+};
+
+template <bool CAPTURE>
+__global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
+    const int npix = A.W * A.H;
+    const int pix = blockIdx.x * kBlock + threadIdx.x;
+    if (pix >= npix) return;
+    const float cap = PT_TEMPORAL_MAX_HISTORY;
+    const float4 pp = A.posT[pix], np = A.nrmId[pix];
+    const int id = __float_as_int(np.w);
+    float hcx = 0.0f, hcy = 0.0f, hcz = 0.0f, hcw = 0.0f, Nh = 0.0f;
+    if (A.hn != nullptr && id >= 0) {
+        const TemporalCam &c = A.cam;
+        const float dx = pp.x - c.e[0], dy = pp.y - c.e[1], dz = pp.z - c.e[2];
+        const float s = (c.r0[0] * dx + c.r0[1] * dy) + c.r0[2] * dz;
+        if (s > 0.0f) {
+            const float a = ((c.r1[0] * dx + c.r1[1] * dy) + c.r1[2] * dz) / s;
+            const float b = ((c.r2[0] * dx + c.r2[1] * dy) + c.r2[2] * dz) / s;
+            const float u = (a / c.pixLenX + c.halfW) - 0.5f;
+            const float v = (b / c.pixLenY + c.halfH) - 0.5f;
+            if (u > -1.0f && u < (float)A.W && v > -1.0f && v < (float)A.H) {
+                const float fx = __builtin_floorf(u), fy = __builtin_floorf(v);
+                const float wx = u - fx, wy = v - fy;
+                const int x0 = (int)fx, y0 = (int)fy;
+                const float lim = PT_TEMPORAL_PLANE_FRACTION * pp.w;
+                float sumW = 0.0f, sumN = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int qy = y0 + j;
+                    if (qy < 0 || qy >= A.H) continue;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int qx = x0 + i;
+                        if (qx < 0 || qx >= A.W) continue;
+                        const int q = qx + qy * A.W;
+                        const float nq = A.hn[q];
+                        if (!(nq > 0.0f)) continue;
+                        const float4 hn4 = A.hnrm[q];
+                        if (__float_as_int(hn4.w) != id) continue;
+                        if (!((hn4.x * np.x + hn4.y * np.y) + hn4.z * np.z >= PT_TEMPORAL_NORMAL_DOT)) continue;
+                        const float4 hp = A.hpos[q];
+                        const float off = ((hp.x - pp.x) * np.x + (hp.y - pp.y) * np.y) + (hp.z - pp.z) * np.z;
+                        if (!(__builtin_fabsf(off) <= lim)) continue;
+                        const float w = (i ? wx : 1.0f - wx) * (j ? wy : 1.0f - wy);
+                        const float4 h = A.hc[q];
+                        sumW += w;
+                        sx += h.x * w;
+                        sy += h.y * w;
+                        sz += h.z * w;
+                        sw += h.w * w;
+                        sumN += nq * w;
+                    }
+                }
+                if (sumW > PT_TEMPORAL_MIN_WEIGHT) {
+                    hcx = sx / sumW; hcy = sy / sumW; hcz = sz / sumW; hcw = sw / sumW;
+                    const float hn = sumN / sumW;
+                    Nh = hn < cap ? hn : cap;
+                }
+            }
+        }
+    }
+    const float *S = A.accum + 3 * (size_t)pix;
+    const float tot = Nh + A.samples;
+    const float r = (hcx * Nh + S[0]) / tot, g = (hcy * Nh + S[1]) / tot, b = (hcz * Nh + S[2]) / tot;
+    const float m2 = (hcw * Nh + A.moments[pix]) / tot;
+    if (CAPTURE) {
+        A.out[pix] = make_float4(r, g, b, m2);
+        A.outN[pix] = tot < cap ? tot : cap;
+    } else {
+        const float L = atrousLum(r, g, b);
+        float dd = m2 - L * L;
+        dd = dd > 0.0f ? dd : 0.0f;
+        A.out[pix] = make_float4(r, g, b, dd / (tot - 1.0f));
+    }
+}
+
+}  // namespace ptk

@@ -1067,6 +1067,78 @@ int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_
     return denoise_var_to_host(samples, p, params_struct_bytes, form, ms, rgb_mean_host, var_host, "pt_test_denoise_var");
 }
 
+static_assert(sizeof(TemporalCam) == 16 * sizeof(float), "pt_test_temporal's cam16 is a TemporalCam (include/pt_amd_test.h)");
+
+int pt_test_temporal_camera(const PtCamera *cam, float *cam16) {
+    if (!cam || !cam16 || cam->resolution[0] < 1 || cam->resolution[1] < 1) return fail(PT_ERR_INVALID, "pt_test_temporal_camera: bad argument");
+    KParams k{};
+    camera_params(*cam, k);
+    const TemporalCam c = temporal_camera(k);
+    memcpy(cam16, &c, sizeof c);
+    return PT_OK;
+}
+
+int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_sum, const float *lum_sq_sum, const float *pos_t4, const float *nrm_id4,
+                     const float *hc4, const float *hn, const float *hpos_t4, const float *hnrm_id4, const float *cam16, float *out4, float *out_n,
+                     int reps, float *ms) {
+    NEED_GPU();
+    if (w < 1 || h < 1 || (long long)w * h > (1ll << 30) || samples < 1 || !rgb_sum || !lum_sq_sum || !pos_t4 || !nrm_id4 || !hc4 || !hn || !hpos_t4 ||
+        !hnrm_id4 || !cam16 || !out4 || (capture && !out_n) || (ms && reps < 1))
+        return fail(PT_ERR_INVALID, "pt_test_temporal: bad argument");
+    const size_t P = (size_t)w * h;
+    DevBuf<float> S, Q, Hn, outN;
+    DevBuf<float4> pos, nrm, Hc, Hpos, Hnrm, out;
+    UP(S, rgb_sum, P * 3);
+    UP(Q, lum_sq_sum, P);
+    UP(Hn, hn, P);
+    UP(pos, reinterpret_cast<const float4 *>(pos_t4), P);
+    UP(nrm, reinterpret_cast<const float4 *>(nrm_id4), P);
+    UP(Hc, reinterpret_cast<const float4 *>(hc4), P);
+    UP(Hpos, reinterpret_cast<const float4 *>(hpos_t4), P);
+    UP(Hnrm, reinterpret_cast<const float4 *>(hnrm_id4), P);
+    int rc = out.alloc(P); if (rc) return rc;
+    rc = outN.alloc(P); if (rc) return rc;
+    TemporalArgs T;
+    T.accum = S.p; T.moments = Q.p; T.posT = pos.p; T.nrmId = nrm.p;
+    T.hc = Hc.p; T.hn = Hn.p; T.hpos = Hpos.p; T.hnrm = Hnrm.p;
+    memcpy(&T.cam, cam16, sizeof T.cam);
+    T.W = w; T.H = h; T.samples = (float)samples;
+    T.out = out.p; T.outN = outN.p;
+    const dim3 grid((unsigned)((P + kBlock - 1) / kBlock));
+    EventSet es;
+    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
+        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        if (capture) hipLaunchKernelGGL(k_temporal<true>, grid, dim3(kBlock), 0, nullptr, T);
+        else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(kBlock), 0, nullptr, T);
+        if (ms && r) {
+            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+            HIPCHECK(hipEventSynchronize(es.ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (capture) DOWN(out_n, outN, P);
+    return PT_OK;
+}
+
+int pt_test_history(int32_t *wh2, float *hc4, float *hn, float *hpos_t4, float *hnrm_id4, float *cam16) {
+    if (!wh2) return fail(PT_ERR_INVALID, "pt_test_history: null");
+    const History &hs = R().hist;
+    wh2[0] = hs.live ? hs.W : 0;
+    wh2[1] = hs.live ? hs.H : 0;
+    if (!hs.live) return PT_OK;
+    const size_t P = (size_t)hs.W * hs.H;
+    if (hc4) HIPCHECK(hipMemcpy(hc4, hs.hc[hs.cur].p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (hn) HIPCHECK(hipMemcpy(hn, hs.hn[hs.cur].p, P * sizeof(float), hipMemcpyDeviceToHost));
+    if (hpos_t4) HIPCHECK(hipMemcpy(hpos_t4, hs.hpos.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (hnrm_id4) HIPCHECK(hipMemcpy(hnrm_id4, hs.hnrm.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (cam16) memcpy(cam16, &hs.cam, sizeof hs.cam);
+    return PT_OK;
+}
+
 int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, int h, int samples, float threshold, float lum_floor, PtNoiseStats *out,
                         size_t stats_struct_bytes, float *tile_rel_var_host, int tiles_per_wave, int reps, float *ms) {
     NEED_GPU();

@@ -7,6 +7,7 @@
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 //                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
+//                           [--history-from EX EY EZ N]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
@@ -17,6 +18,11 @@
 // --noise-fraction F until at most that fraction of the tiles does -- checking every K iterations (--check-every, default 8) while the next
 // K are already being traced; --iterations becomes the cap.  The renderer then runs with PT_FLAG_MOMENTS through the C ABI like --batch
 // (B may be 1), the PNG is normalised by the samples actually taken, and one line reports them.
+// --history-from EX EY EZ N (with --denoise-var) is the camera move of an interactive session, headless: N iterations are rendered from the
+// eye (EX, EY, EZ) first, the renderer is then re-initialised at the scene's camera WITHOUT being freed -- both with PT_FLAG_TEMPORAL, so the
+// first view's samples become the context's history (include/pt_amd.h, "temporal reprojection") --, --iterations more are rendered there
+// (numbered N + 1, ...: fresh random numbers), and <out>.denoised.png is the filter of the blend.  The usual image holds the second view's
+// own samples alone.  Through the C ABI like --noise-threshold (B may be 1); not together with it.
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -51,6 +57,9 @@ static bool denoiseVar = false;
 static bool noiseTarget = false;
 static float noiseThreshold = 0.0f, noiseFraction = 0.0f;
 static int checkEvery = 8;
+static bool historyFrom = false;
+static float historyEye[3] = {0.0f, 0.0f, 0.0f};
+static int historyIterations = 0;
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 
@@ -130,6 +139,7 @@ static void renderBatched() {
     opt.focal_distance = focalDistance;
     if (directLighting) opt.flags |= PT_FLAG_DIRECT_LIGHTING;
     if (denoiseVar || noiseTarget) opt.flags |= PT_FLAG_MOMENTS;
+    if (historyFrom) opt.flags |= PT_FLAG_TEMPORAL;
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -141,6 +151,21 @@ static void renderBatched() {
         meshes.push_back(m);
     }
     check(pt_set_meshes(meshes.empty() ? NULL : meshes.data(), (int)meshes.size()), "pt_set_meshes");
+    int firstIter = 1;                 // the iteration number of the frame's first sample
+    if (historyFrom) {                 // the view before the camera moved: its samples stay behind as the context's history
+        PtCamera before;
+        memcpy(&before, &renderState->camera, sizeof before);
+        before.position.x = historyEye[0]; before.position.y = historyEye[1]; before.position.z = historyEye[2];
+        check(pt_init(&before, (const PtGeom *)scene->geoms.data(), (int)scene->geoms.size(), (const PtMaterial *)scene->materials.data(),
+                      (int)scene->materials.size(), renderState->traceDepth, &opt), "pt_init");
+        for (int done = 0; done < historyIterations;) {
+            const int n = historyIterations - done < batch ? historyIterations - done : batch;
+            check(pt_iterate_batch(0, done + 1, n, NULL), "pt_iterate_batch");
+            done += n;
+        }
+        firstIter = historyIterations + 1;
+    }
+    // (with --history-from: over the live renderer -- no pt_free -- which is what carries the history)
     check(pt_init((const PtCamera *)&renderState->camera, (const PtGeom *)scene->geoms.data(), (int)scene->geoms.size(),
                   (const PtMaterial *)scene->materials.data(), (int)scene->materials.size(), renderState->traceDepth, &opt),
           "pt_init");
@@ -163,7 +188,7 @@ static void renderBatched() {
     }
     while (!noiseTarget && iteration < total) {
         const int n = total - iteration < batch ? total - iteration : batch;
-        check(pt_iterate_batch(0, iteration + 1, n, NULL), "pt_iterate_batch");
+        check(pt_iterate_batch(0, firstIter + iteration, n, NULL), "pt_iterate_batch");
         iteration += n;
     }
     check(pt_readback((float *)renderState->image.data()), "pt_readback");
@@ -175,7 +200,7 @@ static void renderBatched() {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N]\n", argv[0]);
         return 1;
     }
     try {
@@ -215,20 +240,30 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--noise-threshold") && i + 1 < argc) { noiseTarget = true; noiseThreshold = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--noise-fraction") && i + 1 < argc) noiseFraction = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--check-every") && i + 1 < argc) checkEvery = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--history-from") && i + 4 < argc) {
+            historyFrom = true;
+            for (int a = 0; a < 3; ++a) historyEye[a] = (float)atof(argv[i + 1 + a]);
+            historyIterations = atoi(argv[i + 4]);
+            i += 4;
+        }
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
     if (denoise && denoiseVar) { fprintf(stderr, "--denoise and --denoise-var exclude each other\n"); return 1; }
+    if (historyFrom && (!denoiseVar || noiseTarget || historyIterations < 1)) {
+        fprintf(stderr, "--history-from needs --denoise-var and N >= 1, and does not go with --noise-threshold\n");
+        return 1;
+    }
     pathtraceExtras(lensRadius, focalDistance, directLighting);
     pathtraceMoments(denoiseVar);
     iteration = 0;
     width = renderState->camera.resolution.x;
     height = renderState->camera.resolution.y;
     const auto t0 = std::chrono::steady_clock::now();
-    if (batch > 1 || noiseTarget) renderBatched();
+    if (batch > 1 || noiseTarget || historyFrom) renderBatched();
     else while (runHip()) {}
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("%d iterations of %dx%d, depth %d: %.3f s wall (init, %s and PNG included)\n", iteration, width, height,
-           renderState->traceDepth, s, batch > 1 || noiseTarget ? "one D2H copy" : "per-iteration D2H copy");
+           renderState->traceDepth, s, batch > 1 || noiseTarget || historyFrom ? "one D2H copy" : "per-iteration D2H copy");
     delete scene;
     return 0;
 }
