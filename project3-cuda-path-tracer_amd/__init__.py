@@ -993,6 +993,54 @@ def save_hdr(basename, image_sum, samples):
 
 
 # --------------------------------------------------------------------------- primitive / scan entry points (host arrays)
+def _geoms_args(geoms):
+    """a PtGeom array as the entry points take it: (pointer, count)"""
+    g = np.ascontiguousarray(geoms)
+    return _p(g), len(g)
+
+
+def _camera_args(camera, geoms):
+    """(camera pointer, geoms pointer, count)"""
+    return (_p(np.ascontiguousarray(camera)),) + _geoms_args(geoms)
+
+
+def _mesh_args(geom, tris):
+    """one mesh geom and its triangles: (geom pointer, triangles pointer, triangle count)"""
+    tr = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
+    return _p(np.ascontiguousarray(geom).reshape(-1)[:1]), _p(tr), len(tr)
+
+
+def _u64_outs(fn, sizes, *args, then=()):
+    """fn(*args, one uint64 array of each of `sizes` by reference, *then) -> every value of them in order, as ints"""
+    outs = [(C.c_uint64 * n)() for n in sizes]
+    _tcheck(fn(*args, *outs, *then))
+    return tuple(int(v) for a in outs for v in a)
+
+
+def _ray_hits(rays, sentinel):
+    """the rays of an intersect test, their count, and its per-ray outputs t, p, n, outside, culled as the kernels expect to find them"""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    n = len(rays)
+    return rays, n, (np.empty(n, np.float32), np.full((n, 3), sentinel, np.float32), np.full((n, 3), sentinel, np.float32),
+                     np.ones(n, np.int32), np.zeros(n, np.int32))
+
+
+def _sized_camera_list(fn, camera, geoms, shard_rank, shard_count, faces):
+    """camera_list / camera_resolved in their two calls: the sizes with null arrays, then the arrays.  -> None where no list is built, else
+    ([pix, wave ranges, signature entries, and with `faces` the per-wave faces], sizes)"""
+    args = _camera_args(camera, geoms) + (shard_rank, shard_count)
+    sizes = np.zeros(4, np.int64)
+    _tcheck(fn(*args, *[None] * (4 if faces else 3), _p(sizes)))
+    if sizes[0] < 0:
+        return None
+    n = int(sizes[0])
+    out = [np.zeros(n, np.uint32), np.zeros((n // 64, 2), np.int32), np.zeros(int(sizes[1]), np.int32)]
+    if faces:
+        out.append(np.zeros(n // 64, np.int32))
+    _tcheck(fn(*args, *[_p(a) for a in out], _p(sizes)))
+    return out, sizes
+
+
 def test_utilhash(x):
     x = np.ascontiguousarray(x, np.uint32)
     out = np.empty_like(x)
@@ -1008,59 +1056,34 @@ def test_rng(seeds, ndraws):
 
 
 def test_intersect(geoms, geom_index, rays, sentinel=-7.0):
-    geoms = np.ascontiguousarray(geoms)
     gi = np.ascontiguousarray(geom_index, np.int32)
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-    n = len(rays)
-    t = np.empty(n, np.float32)
-    p = np.full((n, 3), sentinel, np.float32)
-    nn = np.full((n, 3), sentinel, np.float32)
-    o = np.ones(n, np.int32)
-    _tcheck(test_lib().pt_test_intersect(_p(geoms), len(geoms), _p(gi), _p(rays), n, _p(t), _p(p), _p(nn), _p(o)))
-    return t, p, nn, o
+    rays, n, outs = _ray_hits(rays, sentinel)
+    _tcheck(test_lib().pt_test_intersect(*_geoms_args(geoms), _p(gi), _p(rays), n, *[_p(a) for a in outs[:4]]))
+    return outs[:4]
 
 
 def test_mesh_intersect(geom, tris, rays, flat=False, sentinel=-7.0):
     """Rays against one mesh geom on the GPU (hierarchy, or flat=True: plain triangle list).  Returns t, p, n, outside, culled."""
-    g = np.ascontiguousarray(geom).reshape(-1)[:1]
-    tr = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-    n = len(rays)
-    t = np.empty(n, np.float32)
-    p = np.full((n, 3), sentinel, np.float32)
-    nn = np.full((n, 3), sentinel, np.float32)
-    o = np.ones(n, np.int32)
-    culled = np.zeros(n, np.int32)
-    _tcheck(test_lib().pt_test_mesh_intersect(_p(g), _p(tr), len(tr), 1 if flat else 0, _p(rays), n, _p(t), _p(p), _p(nn), _p(o), _p(culled)))
-    return t, p, nn, o, culled
+    rays, n, outs = _ray_hits(rays, sentinel)
+    _tcheck(test_lib().pt_test_mesh_intersect(*_mesh_args(geom, tris), 1 if flat else 0, _p(rays), n, *[_p(a) for a in outs]))
+    return outs
 
 
 def test_mesh_intersect2(geom, tris, rays, normals=None, materials=None, flat=False, sentinel=-7.0):
     """test_mesh_intersect with the mesh's attributes (normals (ntris, 9), materials (ntris,) or None) and the winner's name.  Returns t, p, n,
     outside, culled, tri (the file index of the triangle that was hit, -1 on a miss), face_mat (its own material; -1: none, or a miss)."""
-    g = np.ascontiguousarray(geom).reshape(-1)[:1]
-    tr = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
-    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(len(tr), 9)
-    mat = None if materials is None else np.ascontiguousarray(materials, np.int32).reshape(len(tr))
-    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-    n = len(rays)
-    t = np.empty(n, np.float32)
-    p = np.full((n, 3), sentinel, np.float32)
-    nn = np.full((n, 3), sentinel, np.float32)
-    o = np.ones(n, np.int32)
-    culled, tri, fm = np.zeros(n, np.int32), np.full(n, -2, np.int32), np.full(n, -2, np.int32)
-    _tcheck(test_lib().pt_test_mesh_intersect2(_p(g), _p(tr), None if nrm is None else _p(nrm), None if mat is None else _p(mat), len(tr),
-                                               1 if flat else 0, _p(rays), n, _p(t), _p(p), _p(nn), _p(o), _p(culled), _p(tri), _p(fm)))
-    return t, p, nn, o, culled, tri, fm
+    g, tr, nt = _mesh_args(geom, tris)
+    nrm = None if normals is None else _p(np.ascontiguousarray(normals, np.float32).reshape(nt, 9))
+    mat = None if materials is None else _p(np.ascontiguousarray(materials, np.int32).reshape(nt))
+    rays, n, outs = _ray_hits(rays, sentinel)
+    outs += (np.full(n, -2, np.int32), np.full(n, -2, np.int32))
+    _tcheck(test_lib().pt_test_mesh_intersect2(g, tr, nrm, mat, nt, 1 if flat else 0, _p(rays), n, *[_p(a) for a in outs]))
+    return outs
 
 
 def test_mesh_cull_sweep(geom, tris, seed, rays):
     """Device sweep of the bounding-ball test of one mesh geom.  Returns (culled, violations, hits)."""
-    g = np.ascontiguousarray(geom).reshape(-1)[:1]
-    tr = np.ascontiguousarray(tris, np.float32).reshape(-1, 9)
-    c, v, h = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    _tcheck(test_lib().pt_test_mesh_cull_sweep(_p(g), _p(tr), len(tr), seed, rays, C.byref(c), C.byref(v), C.byref(h)))
-    return c.value, v.value, h.value
+    return _u64_outs(test_lib().pt_test_mesh_cull_sweep, (1, 1, 1), *_mesh_args(geom, tris), seed, rays)
 
 
 MESH_LEAF = 0x80000000
@@ -1159,169 +1182,116 @@ def test_slab_quotients(o, d):
 
 
 def test_slab_quotients_sweep(seed, pairs):
-    m = C.c_uint64(0)
-    _tcheck(test_lib().pt_test_slab_quotients_sweep(seed, pairs, C.byref(m)))
-    return int(m.value)
+    return _u64_outs(test_lib().pt_test_slab_quotients_sweep, (1,), seed, pairs)[0]
 
 
 def test_unscaled_sqrt_sweep():
-    m = (C.c_uint64 * 4)()
-    _tcheck(test_lib().pt_test_unscaled_sqrt_sweep(m))
-    return [int(v) for v in m]
+    return list(_u64_outs(test_lib().pt_test_unscaled_sqrt_sweep, (4,)))
 
 
 def test_sphere_cull_sweep(geoms, seed, rays):
-    geoms = np.ascontiguousarray(geoms)
-    culled, bad = C.c_uint64(0), C.c_uint64(0)
-    _tcheck(test_lib().pt_test_sphere_cull_sweep(_p(geoms), len(geoms), seed, rays, C.byref(culled), C.byref(bad)))
-    return int(culled.value), int(bad.value)
+    return _u64_outs(test_lib().pt_test_sphere_cull_sweep, (1, 1), *_geoms_args(geoms), seed, rays)
 
 
 def test_sphere_halfline_sweep(geoms, seed, rays):
     """-> (certified misses, of them with the centre behind the origin, violations)"""
-    geoms = np.ascontiguousarray(geoms)
-    culled, behind, bad = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    _tcheck(test_lib().pt_test_sphere_halfline_sweep(_p(geoms), len(geoms), seed, rays, C.byref(culled), C.byref(behind), C.byref(bad)))
-    return int(culled.value), int(behind.value), int(bad.value)
+    return _u64_outs(test_lib().pt_test_sphere_halfline_sweep, (1, 1, 1), *_geoms_args(geoms), seed, rays)
+
+
+def _cluster_info(info):
+    """pt_test_sphere_clusters' info18 -> {omax, n0, boxes (2, 6): lo, hi}"""
+    return {"omax": float(info[0]), "n0": int(info[1]), "boxes": info[2:].reshape(2, 8)[:, :6].copy()}
 
 
 def test_sphere_cluster_sweep(geoms, seed, rays):
     """geoms: a whole scene (spheres and cubes) -> (certificates issued per cluster [2], violations, {omax, n0, boxes[2][6]})"""
-    geoms = np.ascontiguousarray(geoms)
-    cert = (C.c_uint64 * 2)()
-    bad = C.c_uint64(0)
     info = np.zeros(18, np.float32)
-    _tcheck(test_lib().pt_test_sphere_cluster_sweep(_p(geoms), len(geoms), seed, rays, cert, C.byref(bad), info.ctypes.data))
-    boxes = info[2:].reshape(2, 8)[:, :6].copy()
-    return [int(cert[0]), int(cert[1])], int(bad.value), {"omax": float(info[0]), "n0": int(info[1]), "boxes": boxes}
+    c0, c1, bad = _u64_outs(test_lib().pt_test_sphere_cluster_sweep, (2, 1), *_geoms_args(geoms), seed, rays, then=(info.ctypes.data,))
+    return [c0, c1], bad, _cluster_info(info)
 
 
 def test_sphere_group_sweep(geoms, seed, rays):
     """(group certificates issued, violations, groups): pt_test_sphere_group_sweep"""
-    g = np.ascontiguousarray(geoms)
-    cert, viol, ng = C.c_uint64(), C.c_uint64(), C.c_int32()
-    _tcheck(test_lib().pt_test_sphere_group_sweep(_p(g), len(g), seed, rays, C.byref(cert), C.byref(viol), C.byref(ng)))
-    return int(cert.value), int(viol.value), int(ng.value)
+    ng = C.c_int32()
+    return _u64_outs(test_lib().pt_test_sphere_group_sweep, (1, 1), *_geoms_args(geoms), seed, rays, then=(C.byref(ng),)) + (int(ng.value),)
 
 
 def sphere_clusters(geoms):
     """The two clusters of spheres pt_init builds for a sphere-heavy scene without meshes (host only).
     -> {omax, n0, boxes (2, 6): lo, hi}, table (primitive index per entry of the sweep's table: cluster 0 first, n0 entries)"""
-    geoms = np.ascontiguousarray(geoms)
     info = np.zeros(18, np.float32)
     table = np.zeros(len(geoms) + 2, np.int32)
     n = C.c_int32(0)
-    _tcheck(test_lib().pt_test_sphere_clusters(_p(geoms), len(geoms), info.ctypes.data, table.ctypes.data, len(table), C.byref(n)))
-    return {"omax": float(info[0]), "n0": int(info[1]), "boxes": info[2:].reshape(2, 8)[:, :6].copy()}, table[:n.value].copy()
+    _tcheck(test_lib().pt_test_sphere_clusters(*_geoms_args(geoms), info.ctypes.data, table.ctypes.data, len(table), C.byref(n)))
+    return _cluster_info(info), table[:n.value].copy()
 
 
 def test_wall_box_sweep(geoms, seed, rays):
-    geoms = np.ascontiguousarray(geoms)
-    culled, bad = C.c_uint64(0), C.c_uint64(0)
-    _tcheck(test_lib().pt_test_wall_box_sweep(_p(geoms), len(geoms), seed, rays, C.byref(culled), C.byref(bad)))
-    return int(culled.value), int(bad.value)
+    return _u64_outs(test_lib().pt_test_wall_box_sweep, (1, 1), *_geoms_args(geoms), seed, rays)
 
 
 def camera_cull_tables(camera, geoms):
     """The camera-ray culling tables pt_init derives (host only).  Returns (rects (n, 4), scene rect (4,), spans (H, n, 2))."""
-    cam = np.ascontiguousarray(camera)
-    geoms = np.ascontiguousarray(geoms)
-    H = int(cam["resolution"][0][1])
+    H = int(np.ascontiguousarray(camera)["resolution"][0][1])
     rects = np.zeros((len(geoms), 4), np.int32)
     scene = np.zeros(4, np.int32)
     spans = np.zeros((H, len(geoms), 2), np.int32)
-    _tcheck(test_lib().pt_test_camera_cull_tables(_p(cam), _p(geoms), len(geoms), _p(rects), _p(scene), _p(spans)))
+    _tcheck(test_lib().pt_test_camera_cull_tables(*_camera_args(camera, geoms), _p(rects), _p(scene), _p(spans)))
     return rects, scene, spans
 
 
 def camera_list(camera, geoms, shard_rank=0, shard_count=1):
     """The camera rays' packed work list pt_init builds for one shard (host only, no length cap).  Returns None where it is not built,
     else (pix (n,) uint32: x | y << 16 or 0xffffffff, wave ranges (n / 64, 2), signature entries, pixels listed, pixels of the shard)."""
-    cam = np.ascontiguousarray(camera)
-    geoms = np.ascontiguousarray(geoms)
-    sizes = np.zeros(4, np.int64)
-    _tcheck(test_lib().pt_test_camera_list(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, None, None, None, _p(sizes)))
-    if sizes[0] < 0:
-        return None
-    pix = np.zeros(int(sizes[0]), np.uint32)
-    wave = np.zeros((int(sizes[0]) // 64, 2), np.int32)
-    sig = np.zeros(int(sizes[1]), np.int32)
-    _tcheck(test_lib().pt_test_camera_list(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, _p(pix), _p(wave), _p(sig), _p(sizes)))
-    return pix, wave, sig, int(sizes[2]), int(sizes[3])
+    r = _sized_camera_list(test_lib().pt_test_camera_list, camera, geoms, shard_rank, shard_count, False)
+    return r and (*r[0], int(r[1][2]), int(r[1][3]))
 
 
 def camera_resolved(camera, geoms, shard_rank=0, shard_count=1):
     """camera_list as pt_init builds it for the untextured forms: one-cube signatures split by the cube face their pixels' camera rays are
     certified to enter through (host only, no length cap).  Returns None where the list is not built, else (pix, wave ranges, signature
     entries, per wave its face 2 axis + (side > 0) or -1)."""
-    cam = np.ascontiguousarray(camera)
-    geoms = np.ascontiguousarray(geoms)
-    sizes = np.zeros(4, np.int64)
-    _tcheck(test_lib().pt_test_camera_resolved(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, None, None, None, None, _p(sizes)))
-    if sizes[0] < 0:
-        return None
-    pix = np.zeros(int(sizes[0]), np.uint32)
-    wave = np.zeros((int(sizes[0]) // 64, 2), np.int32)
-    sig = np.zeros(int(sizes[1]), np.int32)
-    face = np.zeros(int(sizes[0]) // 64, np.int32)
-    _tcheck(test_lib().pt_test_camera_resolved(_p(cam), _p(geoms), len(geoms), shard_rank, shard_count, _p(pix), _p(wave), _p(sig), _p(face), _p(sizes)))
-    return pix, wave, sig, face
+    r = _sized_camera_list(test_lib().pt_test_camera_resolved, camera, geoms, shard_rank, shard_count, True)
+    return r and tuple(r[0])
 
 
 def test_face_hit_sweep(camera, geoms, samples=64, seed=1):
     """Device sweep of the resolved waves' box test against the full one.  Returns (rays, mismatches, resolved pixels)."""
-    cam = np.ascontiguousarray(camera)
-    geoms = np.ascontiguousarray(geoms)
-    c = (C.c_uint64 * 3)()
-    _tcheck(test_lib().pt_test_face_hit_sweep(_p(cam), _p(geoms), len(geoms), samples, seed, c))
-    return tuple(int(v) for v in c)
+    return _u64_outs(test_lib().pt_test_face_hit_sweep, (3,), *_camera_args(camera, geoms), samples, seed)
 
 
 def test_camera_cull_sweep(camera, geoms, samples=1):
     """Device sweep of the camera-ray culling for one (camera, primitive set).  Returns (hits, culled pairs, violations)."""
-    cam = np.ascontiguousarray(camera)
-    geoms = np.ascontiguousarray(geoms)
-    h, c, v = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    _tcheck(test_lib().pt_test_camera_cull_sweep(_p(cam), _p(geoms), len(geoms), samples, C.byref(h), C.byref(c), C.byref(v)))
-    return int(h.value), int(c.value), int(v.value)
+    return _u64_outs(test_lib().pt_test_camera_cull_sweep, (1, 1, 1), *_camera_args(camera, geoms), samples)
 
 
 def test_camera_cull_margin(camera, geoms, samples=1):
     """Device measurement of the culling tables' inflation margin for one (camera, primitive set).  Returns (largest fraction of the
     inflation a hit of the reference's test needed, hits that needed any)."""
-    cam = np.ascontiguousarray(camera)
-    geoms = np.ascontiguousarray(geoms)
-    w, n = C.c_double(), C.c_uint64()
-    _tcheck(test_lib().pt_test_camera_cull_margin(_p(cam), _p(geoms), len(geoms), samples, C.byref(w), C.byref(n)))
-    return float(w.value), int(n.value)
+    w = C.c_double()
+    needed, = _u64_outs(test_lib().pt_test_camera_cull_margin, (1,), *_camera_args(camera, geoms), samples, C.byref(w))
+    return float(w.value), needed
 
 
 def test_box_fast_sweep(geoms, seed, rays):
     """Device sweep of the box test's fast slab phase against the reference's loop.  Returns (rays, decided by the fast path, hits
     among those, bit mismatches, mismatches of the fast reciprocal, mismatches of the fast quotient)."""
-    geoms = np.ascontiguousarray(geoms)
-    c = (C.c_uint64 * 4)()
-    d = (C.c_uint64 * 2)()
-    _tcheck(test_lib().pt_test_box_fast_sweep(_p(geoms), len(geoms), seed, rays, c, d))
-    return tuple(int(v) for v in c) + tuple(int(v) for v in d)
+    return _u64_outs(test_lib().pt_test_box_fast_sweep, (4, 2), *_geoms_args(geoms), seed, rays)
 
 
 def test_wall_plane_sweep(geoms, seed, rays):
     """Device sweep of the one-plane-per-wall certificates.  Returns (walls with a plane, certified, violations, single-wall rays)."""
-    geoms = np.ascontiguousarray(geoms)
     n = C.c_int32(0)
-    c, v, s1 = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    _tcheck(test_lib().pt_test_wall_plane_sweep(_p(geoms), len(geoms), seed, rays, C.byref(n), C.byref(c), C.byref(v), C.byref(s1)))
-    return int(n.value), int(c.value), int(v.value), int(s1.value)
+    counts = _u64_outs(test_lib().pt_test_wall_plane_sweep, (1, 1, 1), *_geoms_args(geoms), seed, rays, C.byref(n))
+    return (int(n.value),) + counts
 
 
 def test_wall_planes(geoms):
     """Host only (no GPU): the planes pt_init keeps for rotated walls.  Returns (planes [nplane][5] = normal, threshold, far; wall_geom, nslot, nwalls)."""
-    geoms = np.ascontiguousarray(geoms)
     planes = np.zeros((6, 5), np.float32)
     wg = np.zeros(6, np.int32)
     ns, npl, nw = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    _tcheck(test_lib().pt_test_wall_planes(_p(geoms), len(geoms), _p(planes), _p(wg), C.byref(ns), C.byref(npl), C.byref(nw)))
+    _tcheck(test_lib().pt_test_wall_planes(*_geoms_args(geoms), _p(planes), _p(wg), C.byref(ns), C.byref(npl), C.byref(nw)))
     return planes[:npl.value].copy(), wg[:nw.value].copy(), int(ns.value), int(nw.value)
 
 

@@ -155,28 +155,171 @@ int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
 
 int64_t pt_test_live_device_buffers(void) { return (int64_t)g_liveDevBufs.load(); }
 
-#define NEED_GPU() do { if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "no HIP device"); } while (0)
-#define UP(buf, host, count) do { int rc_ = buf.alloc(count); if (rc_) return rc_; \
-    HIPCHECK(hipMemcpy(buf.p, host, (size_t)(count) * sizeof(*buf.p), hipMemcpyHostToDevice)); } while (0)
-#define DOWN(host, buf, count) HIPCHECK(hipMemcpy(host, buf.p, (size_t)(count) * sizeof(*buf.p), hipMemcpyDeviceToHost))
-#define GRID(n) dim3(((n) + 255) / 256), dim3(256), 0, 0
-
 int pt_test_group_fail_next_reduce(PtGroup *g, int count) {
     if (!g || count < 0) return fail(PT_ERR_INVALID, "pt_test_group_fail_next_reduce: bad argument");
     g->failReduces = count;
     return PT_OK;
 }
 
+// ---- what the entry points below share: launch, counters, grids, packed scenes ------------------------------
+#define NEED_GPU() do { if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "no HIP device"); } while (0)
+
+extern "C++" {     // (templates among them: pt_api.hip includes this file inside its extern "C" block)
+
+constexpr int kTestThreads = 256;     // every test kernel runs in one-dimensional blocks of this size
+inline dim3 blocks_for(long long n) { return dim3((unsigned)((n + kTestThreads - 1) / kTestThreads)); }      // one lane per element
+
+// a sweep's grid: `rays` at `per_thread` per lane, at least one block, at most `cap` (a lane's stream is a function of its global index:
+// the sweeps' counts depend on this)
+inline dim3 sweep_grid(long long rays, int per_thread, int threads, long long cap) {
+    const long long perBlock = (long long)per_thread * threads;
+    return dim3((unsigned)std::min(std::max((rays + perBlock - 1) / perBlock, 1ll), cap));
+}
+
+// every launch of a test kernel: on the null stream, checked, waited for
+template <typename... P, typename... A>
+int launch_wait(void (*kernel)(P...), dim3 grid, size_t ldsBytes, const A &...args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kTestThreads), ldsBytes, nullptr, args...);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+template <typename T>
+int download(T *host, const DevBuf<T> &buf, size_t n) {
+    HIPCHECK(hipMemcpy(host, buf.p, n * sizeof(T), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// the N 64-bit counters of a sweep: zeroed on the device, read into h after the launch and handed out in order
+template <int N>
+struct Counters {
+    DevBuf<unsigned long long> d;
+    unsigned long long h[N] = {};
+    int zero() { return d.alloc_zeroed(N); }
+    unsigned long long *at(int i) const { return d.p + i; }
+    int read(std::initializer_list<uint64_t *> outs = {}) {
+        PTCHECK(download(h, d, N));
+        int i = 0;
+        for (uint64_t *o : outs) *o = h[i++];
+        return PT_OK;
+    }
+};
+
+// the primitives as pt_init packs them (`eye`: with the object-space eye of the camera-ray tests), or the refusal of a type outside `allowed`
+enum : unsigned { kSpheres = 1u << PT_SPHERE, kCubes = 1u << PT_CUBE, kAnyGeom = ~0u };
+int pack_geoms(const PtGeom *geoms, int ngeoms, unsigned allowed, const float *eye, const char *fn, std::vector<GeomDev> &hg) {
+    hg.resize(ngeoms);
+    for (int i = 0; i < ngeoms; ++i) {
+        const int t = geoms[i].type;
+        if (allowed != kAnyGeom && (t < 0 || t > 31 || !((allowed >> t) & 1u)))
+            return fail(PT_ERR_INVALID, "%s: %s only", fn, allowed == kCubes ? "cubes" : "spheres and cubes");
+        pack_geom(geoms[i], hg[i], eye);
+    }
+    return PT_OK;
+}
+
+// the bounding box of every bounded primitive: where the cluster and group sweeps start their rays "from the scene"
+void scene_extent(const std::vector<GeomDev> &hg, F3 &slo, F3 &shi) {
+    slo = F3{INFINITY, INFINITY, INFINITY};
+    shi = F3{-INFINITY, -INFINITY, -INFINITY};
+    for (const GeomDev &g : hg) {
+        const float r = g.boundR;
+        if (!std::isfinite(r)) continue;
+        slo = F3{std::min(slo.x, g.centre[0] - r), std::min(slo.y, g.centre[1] - r), std::min(slo.z, g.centre[2] - r)};
+        shi = F3{std::max(shi.x, g.centre[0] + r), std::max(shi.y, g.centre[1] + r), std::max(shi.z, g.centre[2] + r)};
+    }
+}
+
+// the rays of an intersect test and what its kernel keeps per ray: t, the hit point and normal (in: the caller's sentinels), outside, culled
+struct RayHits {
+    DevBuf<float> rays, t, p, n;
+    DevBuf<int> outside, culled;
+    int up(const float *rays6, int count, const float *p3, const float *n3, const int32_t *out) {
+        PTCHECK(rays.upload(rays6, (size_t)count * 6));
+        PTCHECK(p.upload(p3, (size_t)count * 3));
+        PTCHECK(n.upload(n3, (size_t)count * 3));
+        PTCHECK(outside.upload(out, count));
+        PTCHECK(t.alloc(count));
+        return culled.alloc(count);
+    }
+    int down(int count, float *ht, float *p3, float *n3, int32_t *out, int32_t *cull) {
+        PTCHECK(download(ht, t, count));
+        PTCHECK(download(p3, p, (size_t)count * 3));
+        PTCHECK(download(n3, n, (size_t)count * 3));
+        PTCHECK(download(out, outside, count));
+        return cull ? download(cull, culled, count) : PT_OK;
+    }
+};
+
+// One mesh as pt_init lays it out: the records, and (upload) the packed geom with its root and stride, the walk's stacks in LDS -- or the
+// refusal of a hierarchy too deep for them -- and the device copies
+struct MeshFixture {
+    std::vector<ptd::MeshUnit> recs;
+    float box[6];
+    ptm::MeshLayout lay;
+    GeomDev hg;
+    size_t stackBytes = 0;
+    DevBuf<GeomDev> dg;
+    DevBuf<ptd::MeshUnit> drec;
+    void append(const float *tris, int ntris, bool flat, const float *normals = nullptr, const int32_t *mats = nullptr) {
+        lay = ptm::appendMesh(tris, ntris, flat, recs, box, normals, mats);
+    }
+    int upload(const PtGeom &geom, const char *fn) {
+        pack_geom(geom, hg, nullptr, box);
+        hg.meshRoot = lay.root;
+        hg.meshStride = lay.stride;
+        stackBytes = (size_t)std::max(lay.stackNeed, 1) * kTestThreads * sizeof(uint32_t);
+        if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "%s: the hierarchy needs %d stack levels", fn, lay.stackNeed);
+        PTCHECK(dg.upload(&hg, 1));
+        return drec.upload(recs);
+    }
+    const float4 *units() const { return reinterpret_cast<const float4 *>(drec.p); }
+};
+
+// One (camera, primitive set) as pt_init derives it.  pack: the camera constants with the row divisor, the packed primitives (object-space
+// eye).  cull: pack, then the rectangles, their union and the per-row lists.  list: a shard's packed work list without a length cap.
+struct CameraFixture {
+    KParams k;
+    std::vector<GeomDev> hg;
+    CameraCull cc;
+    int pack(const PtCamera *cam, const PtGeom *geoms, int ngeoms, unsigned allowed, long long maxPixels, const char *fn) {
+        if (cam->resolution[0] < 1 || cam->resolution[1] < 1 || (long long)cam->resolution[0] * cam->resolution[1] > maxPixels)
+            return fail(PT_ERR_INVALID, "%s: bad resolution", fn);
+        memset(&k, 0, sizeof k);
+        camera_params(*cam, k);
+        k.ngeoms = ngeoms;
+        magic_divisor((uint32_t)k.W, k.magicW, k.shiftW);
+        return pack_geoms(geoms, ngeoms, allowed, k.pos, fn, hg);
+    }
+    int cull(const PtCamera *cam, const PtGeom *geoms, int ngeoms, unsigned allowed, long long maxPixels, const char *fn) {
+        PTCHECK(pack(cam, geoms, ngeoms, allowed, maxPixels, fn));
+        build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
+        for (int a = 0; a < 4; ++a) k.sceneRect[a] = cc.sceneRect[a];
+        return PT_OK;
+    }
+    // (`resolve`: as for the untextured forms -- one-cube signatures split by the face their pixels are resolved to, camera_face_certificate --
+    // with the per-wave faces beside it; `built`: false where pt_init would build no list)
+    int list(const PtGeom *geoms, int shard_rank, int shard_count, bool resolve, const char *fn, CameraList &cl, bool &built) const {
+        if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(PT_ERR_INVALID, "%s: bad shard", fn);
+        CameraResolve cr;
+        if (resolve) build_camera_resolve(geoms, k.ngeoms, k, hg, cr);
+        built = build_camera_list(cc, k.W, k.H, shard_rank, shard_count, std::numeric_limits<long long>::max(), cl, resolve ? &cr : nullptr);
+        return PT_OK;
+    }
+};
+constexpr long long kAnyResolution = std::numeric_limits<long long>::max();
+
+}  // extern "C++"
+
 int pt_test_utilhash(const uint32_t *in, uint32_t *out, int n) {
     NEED_GPU();
     if (n <= 0) return PT_OK;
     DevBuf<uint32_t> a, b;
-    UP(a, in, n);
-    int rc = b.alloc(n); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_utilhash, GRID(n), a.p, b.p, n);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(out, b, n);
-    return PT_OK;
+    PTCHECK(a.upload(in, n));
+    PTCHECK(b.alloc(n));
+    PTCHECK(launch_wait(k_test_utilhash, blocks_for(n), 0, a.p, b.p, n));
+    return download(out, b, n);
 }
 
 int pt_test_rng(const uint32_t *seeds, int nseeds, int ndraws, float *u01_out) {
@@ -184,12 +327,10 @@ int pt_test_rng(const uint32_t *seeds, int nseeds, int ndraws, float *u01_out) {
     if (nseeds <= 0 || ndraws <= 0) return PT_OK;
     DevBuf<uint32_t> a;
     DevBuf<float> b;
-    UP(a, seeds, nseeds);
-    int rc = b.alloc((size_t)nseeds * ndraws); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_rng, GRID(nseeds), a.p, nseeds, ndraws, b.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(u01_out, b, (size_t)nseeds * ndraws);
-    return PT_OK;
+    PTCHECK(a.upload(seeds, nseeds));
+    PTCHECK(b.alloc((size_t)nseeds * ndraws));
+    PTCHECK(launch_wait(k_test_rng, blocks_for(nseeds), 0, a.p, nseeds, ndraws, b.p));
+    return download(u01_out, b, (size_t)nseeds * ndraws);
 }
 
 int pt_test_intersect(const PtGeom *geoms, int ngeoms, const int32_t *geom_index, const float *rays, int n, float *t,
@@ -198,25 +339,16 @@ int pt_test_intersect(const PtGeom *geoms, int ngeoms, const int32_t *geom_index
     if (n <= 0) return PT_OK;
     for (int i = 0; i < n; ++i)
         if (geom_index[i] < 0 || geom_index[i] >= ngeoms) return fail(PT_ERR_INVALID, "pt_test_intersect: geom index out of range");
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i]);
+    std::vector<GeomDev> hg;
+    PTCHECK(pack_geoms(geoms, ngeoms, kAnyGeom, nullptr, "pt_test_intersect", hg));
     DevBuf<GeomDev> dg;
-    DevBuf<int> di, dout;
-    DevBuf<float> dr, dt, dp, dn;
-    UP(dg, hg.data(), ngeoms);
-    UP(di, geom_index, n);
-    UP(dr, rays, (size_t)n * 6);
-    UP(dp, p3, (size_t)n * 3);
-    UP(dn, n3, (size_t)n * 3);
-    UP(dout, outside, n);
-    int rc = dt.alloc(n); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_intersect, GRID(n), dg.p, di.p, dr.p, n, dt.p, dp.p, dn.p, dout.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(t, dt, n);
-    DOWN(p3, dp, (size_t)n * 3);
-    DOWN(n3, dn, (size_t)n * 3);
-    DOWN(outside, dout, n);
-    return PT_OK;
+    DevBuf<int> di;
+    RayHits r;
+    PTCHECK(dg.upload(hg));
+    PTCHECK(di.upload(geom_index, n));
+    PTCHECK(r.up(rays, n, p3, n3, outside));
+    PTCHECK(launch_wait(k_test_intersect, blocks_for(n), 0, dg.p, di.p, r.rays.p, n, r.t.p, r.p.p, r.n.p, r.outside.p));
+    return r.down(n, t, p3, n3, outside, nullptr);
 }
 
 int pt_test_mesh_intersect(const PtGeom *geom, const float *tris, int ntris, int flat, const float *rays, int n, float *t,
@@ -224,36 +356,13 @@ int pt_test_mesh_intersect(const PtGeom *geom, const float *tris, int ntris, int
     NEED_GPU();
     if (!geom || !tris || ntris < 1 || geom->type != PT_MESH) return fail(PT_ERR_INVALID, "pt_test_mesh_intersect: bad argument");
     if (n <= 0) return PT_OK;
-    std::vector<ptd::MeshUnit> recs;
-    float box[6];
-    const ptm::MeshLayout lay = ptm::appendMesh(tris, ntris, flat != 0, recs, box);
-    GeomDev hg;
-    pack_geom(*geom, hg, nullptr, box);
-    hg.meshRoot = lay.root;
-    hg.meshStride = lay.stride;
-    DevBuf<GeomDev> dg;
-    DevBuf<ptd::MeshUnit> drec;
-    DevBuf<int> dout, dcull;
-    DevBuf<float> dr, dt, dp, dn;
-    UP(dg, &hg, 1);
-    UP(drec, recs.data(), recs.size());
-    UP(dr, rays, (size_t)n * 6);
-    UP(dp, p3, (size_t)n * 3);
-    UP(dn, n3, (size_t)n * 3);
-    UP(dout, outside, n);
-    int rc = dt.alloc(n); if (rc) return rc;
-    rc = dcull.alloc(n); if (rc) return rc;
-    const size_t stackBytes = (size_t)std::max(lay.stackNeed, 1) * 256 * sizeof(uint32_t);
-    if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "pt_test_mesh_intersect: the hierarchy needs %d stack levels", lay.stackNeed);
-    hipLaunchKernelGGL(k_test_mesh, dim3((unsigned)((n + 255) / 256)), dim3(256), stackBytes, 0, dg.p, reinterpret_cast<const float4 *>(drec.p),
-                       dr.p, n, dt.p, dp.p, dn.p, dout.p, dcull.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(t, dt, n);
-    DOWN(p3, dp, (size_t)n * 3);
-    DOWN(n3, dn, (size_t)n * 3);
-    DOWN(outside, dout, n);
-    DOWN(culled, dcull, n);
-    return PT_OK;
+    MeshFixture m;
+    RayHits r;
+    m.append(tris, ntris, flat != 0);
+    PTCHECK(m.upload(*geom, "pt_test_mesh_intersect"));
+    PTCHECK(r.up(rays, n, p3, n3, outside));
+    PTCHECK(launch_wait(k_test_mesh, blocks_for(n), m.stackBytes, m.dg.p, m.units(), r.rays.p, n, r.t.p, r.p.p, r.n.p, r.outside.p, r.culled.p));
+    return r.down(n, t, p3, n3, outside, culled);
 }
 
 int pt_test_mesh_intersect2(const PtGeom *geom, const float *tris, const float *normals, const int32_t *mats, int ntris, int flat,
@@ -263,46 +372,25 @@ int pt_test_mesh_intersect2(const PtGeom *geom, const float *tris, const float *
     if (!geom || !tris || ntris < 1 || geom->type != PT_MESH || !tri || !face_mat) return fail(PT_ERR_INVALID, "pt_test_mesh_intersect2: bad argument");
     if (n <= 0) return PT_OK;
     // the records twice: as pt_init lays them out, and with 1 + the triangle's file index in the material's word (same geometry, same refs)
-    std::vector<ptd::MeshUnit> recs, tagged;
+    MeshFixture m, tagged;
     std::vector<int> index((size_t)ntris);
     for (int i = 0; i < ntris; ++i) index[(size_t)i] = i;
-    float box[6], box2[6];
-    const ptm::MeshLayout lay = ptm::appendMesh(tris, ntris, flat != 0, recs, box, normals, mats);
-    const ptm::MeshLayout lay2 = ptm::appendMesh(tris, ntris, flat != 0, tagged, box2, normals, index.data());
-    if (lay2.root != lay.root || lay2.stride != lay.stride || lay2.stackNeed != lay.stackNeed || tagged.size() != recs.size())
+    m.append(tris, ntris, flat != 0, normals, mats);
+    tagged.append(tris, ntris, flat != 0, normals, index.data());
+    if (tagged.lay.root != m.lay.root || tagged.lay.stride != m.lay.stride || tagged.lay.stackNeed != m.lay.stackNeed || tagged.recs.size() != m.recs.size())
         return fail(PT_ERR_INVALID, "pt_test_mesh_intersect2: the two record arrays differ in layout");
-    GeomDev hg;
-    pack_geom(*geom, hg, nullptr, box);
-    hg.meshRoot = lay.root;
-    hg.meshStride = lay.stride;
-    DevBuf<GeomDev> dg;
-    DevBuf<ptd::MeshUnit> drec, dtag;
-    DevBuf<int> dout, dcull, dtri, dfm;
-    DevBuf<float> dr, dt, dp, dn;
-    UP(dg, &hg, 1);
-    UP(drec, recs.data(), recs.size());
-    UP(dtag, tagged.data(), tagged.size());
-    UP(dr, rays, (size_t)n * 6);
-    UP(dp, p3, (size_t)n * 3);
-    UP(dn, n3, (size_t)n * 3);
-    UP(dout, outside, n);
-    int rc = dt.alloc(n); if (rc) return rc;
-    rc = dcull.alloc(n); if (rc) return rc;
-    rc = dtri.alloc(n); if (rc) return rc;
-    rc = dfm.alloc(n); if (rc) return rc;
-    const size_t stackBytes = (size_t)std::max(lay.stackNeed, 1) * 256 * sizeof(uint32_t);
-    if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "pt_test_mesh_intersect2: the hierarchy needs %d stack levels", lay.stackNeed);
-    hipLaunchKernelGGL(k_test_mesh2, dim3((unsigned)((n + 255) / 256)), dim3(256), stackBytes, 0, dg.p, reinterpret_cast<const float4 *>(drec.p),
-                       reinterpret_cast<const float4 *>(dtag.p), dr.p, n, dt.p, dp.p, dn.p, dout.p, dcull.p, dtri.p, dfm.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(t, dt, n);
-    DOWN(p3, dp, (size_t)n * 3);
-    DOWN(n3, dn, (size_t)n * 3);
-    DOWN(outside, dout, n);
-    DOWN(culled, dcull, n);
-    DOWN(tri, dtri, n);
-    DOWN(face_mat, dfm, n);
-    return PT_OK;
+    RayHits r;
+    DevBuf<int> dtri, dfm;
+    PTCHECK(m.upload(*geom, "pt_test_mesh_intersect2"));
+    PTCHECK(tagged.drec.upload(tagged.recs));
+    PTCHECK(r.up(rays, n, p3, n3, outside));
+    PTCHECK(dtri.alloc(n));
+    PTCHECK(dfm.alloc(n));
+    PTCHECK(launch_wait(k_test_mesh2, blocks_for(n), m.stackBytes, m.dg.p, m.units(), tagged.units(), r.rays.p, n, r.t.p, r.p.p, r.n.p, r.outside.p,
+                        r.culled.p, dtri.p, dfm.p));
+    PTCHECK(r.down(n, t, p3, n3, outside, culled));
+    PTCHECK(download(tri, dtri, n));
+    return download(face_mat, dfm, n);
 }
 
 int pt_test_mesh_cull_sweep(const PtGeom *geom, const float *tris, int ntris, uint64_t seed, int64_t rays, uint64_t *culled,
@@ -310,45 +398,25 @@ int pt_test_mesh_cull_sweep(const PtGeom *geom, const float *tris, int ntris, ui
     NEED_GPU();
     if (!geom || !tris || ntris < 1 || geom->type != PT_MESH || !culled || !violations || !hits || rays < 0)
         return fail(PT_ERR_INVALID, "pt_test_mesh_cull_sweep: bad argument");
-    std::vector<ptd::MeshUnit> recs;
-    float box[6];
-    const ptm::MeshLayout lay = ptm::appendMesh(tris, ntris, false, recs, box);
-    GeomDev hg;
-    pack_geom(*geom, hg, nullptr, box);
-    hg.meshRoot = lay.root;
-    hg.meshStride = lay.stride;
-    if (!std::isfinite(hg.cullR2)) return fail(PT_ERR_INVALID, "pt_test_mesh_cull_sweep: this mesh is never culled");
-    DevBuf<GeomDev> dg;
-    DevBuf<ptd::MeshUnit> drec;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, &hg, 1);
-    UP(drec, recs.data(), recs.size());
-    int rc = cnt.alloc(3);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 24));
-    const int per_thread = 64, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    const size_t stackBytes = (size_t)std::max(lay.stackNeed, 1) * 256 * sizeof(uint32_t);
-    if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "pt_test_mesh_cull_sweep: the hierarchy needs %d stack levels", lay.stackNeed);
-    hipLaunchKernelGGL(k_sweep_mesh_cull, dim3((unsigned)blocks), dim3(threads), stackBytes, 0, dg.p, reinterpret_cast<const float4 *>(drec.p),
-                       (unsigned long long)seed, per_thread, cnt.p, cnt.p + 1, cnt.p + 2);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 24, hipMemcpyDeviceToHost));
-    *culled = h[0];
-    *violations = h[1];
-    *hits = h[2];
-    return PT_OK;
+    MeshFixture m;
+    Counters<3> cnt;
+    m.append(tris, ntris, false);
+    PTCHECK(m.upload(*geom, "pt_test_mesh_cull_sweep"));
+    if (!std::isfinite(m.hg.cullR2)) return fail(PT_ERR_INVALID, "pt_test_mesh_cull_sweep: this mesh is never culled");
+    PTCHECK(cnt.zero());
+    const int per_thread = 64;
+    PTCHECK(launch_wait(k_sweep_mesh_cull, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), m.stackBytes, m.dg.p, m.units(), seed, per_thread,
+                        cnt.at(0), cnt.at(1), cnt.at(2)));
+    return cnt.read({culled, violations, hits});
 }
 
 // host only: no GPU is touched
 int pt_test_mesh_bvh(const float *tris, int ntris, int octant, uint32_t *units4, int *nrecs, int *stack_need) {
     if (!tris || ntris < 1 || !units4 || !nrecs || !stack_need || octant < 0 || octant > 7) return fail(PT_ERR_INVALID, "pt_test_mesh_bvh: bad argument");
-    std::vector<ptd::MeshUnit> recs;
-    float box[6];
-    const ptm::MeshLayout lay = ptm::appendMesh(tris, ntris, false, recs, box);
+    MeshFixture m;
+    m.append(tris, ntris, false);
+    const std::vector<ptd::MeshUnit> &recs = m.recs;
+    const ptm::MeshLayout lay = m.lay;
     // units of 16 bytes: the triangles (three each), [one unit of padding when their count is odd,] this octant's inner nodes (two each)
     const uint32_t triUnits = (uint32_t)ptd::kMeshTriUnits * (uint32_t)ntris, pad = triUnits % 2u;
     const uint32_t total = triUnits + pad + lay.stride;
@@ -367,19 +435,24 @@ int pt_test_mesh_bvh(const float *tris, int ntris, int octant, uint32_t *units4,
     return PT_OK;
 }
 
+// the walls exactly as pt_init chooses and numbers them among `geoms`, cubes all (no primitive of the set is binned here)
+static int test_choose_walls(const PtGeom *geoms, int ngeoms, const char *fn, std::vector<GeomDev> &hg, KParams &k, std::vector<WallBox> &hw,
+                             std::vector<int> &wallGeom) {
+    PTCHECK(pack_geoms(geoms, ngeoms, kCubes, nullptr, fn, hg));
+    memset(&k, 0, sizeof k);
+    hw.resize(kWallMax);
+    choose_walls(geoms, ngeoms, hg, k, hw, wallGeom);
+    return PT_OK;
+}
+
 // host only: no GPU is touched
 int pt_test_wall_planes(const PtGeom *geoms, int ngeoms, float *planes, int32_t *wall_geom, int32_t *nslot, int32_t *nplane, int32_t *nwalls) {
     if (!geoms || ngeoms < 1 || !planes || !wall_geom || !nslot || !nplane || !nwalls) return fail(PT_ERR_INVALID, "pt_test_wall_planes: bad argument");
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) {
-        if (geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_wall_planes: cubes only");
-        pack_geom(geoms[i], hg[i]);
-    }
+    std::vector<GeomDev> hg;
     KParams k;
-    memset(&k, 0, sizeof k);
-    std::vector<WallBox> hw(kWallMax);
+    std::vector<WallBox> hw;
     std::vector<int> wallGeom;
-    choose_walls(geoms, ngeoms, hg, k, hw, wallGeom);
+    PTCHECK(test_choose_walls(geoms, ngeoms, "pt_test_wall_planes", hg, k, hw, wallGeom));
     *nslot = k.nSlotWalls; *nplane = k.nPlaneWalls; *nwalls = k.nWalls;
     for (int w = 0; w < kWallMax; ++w) {
         for (int q = 0; q < 5; ++q) planes[5 * w + q] = w < k.nPlaneWalls ? k.planeN[w][q] : 0.0f;
@@ -392,64 +465,39 @@ int pt_test_sphere_cull_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, in
                               uint64_t *violations) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !culled || !violations || rays < 0) return fail(PT_ERR_INVALID, "pt_test_sphere_cull_sweep: bad argument");
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i]);
+    std::vector<GeomDev> hg;
+    PTCHECK(pack_geoms(geoms, ngeoms, kAnyGeom, nullptr, "pt_test_sphere_cull_sweep", hg));
     DevBuf<GeomDev> dg;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    int rc = cnt.alloc(2);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 16));
-    const int per_thread = 256, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(k_sweep_sphere_cull, dim3((unsigned)blocks), dim3(threads), 0, 0, dg.p, ngeoms, (unsigned long long)seed,
-                       per_thread, cnt.p, cnt.p + 1);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[2] = {0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 16, hipMemcpyDeviceToHost));
-    *culled = h[0];
-    *violations = h[1];
-    return PT_OK;
+    Counters<2> cnt;
+    PTCHECK(dg.upload(hg));
+    PTCHECK(cnt.zero());
+    const int per_thread = 256;
+    PTCHECK(launch_wait(k_sweep_sphere_cull, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), 0, dg.p, ngeoms, seed, per_thread, cnt.at(0), cnt.at(1)));
+    return cnt.read({culled, violations});
 }
 
 int pt_test_sphere_halfline_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t *culled, uint64_t *behind,
                                   uint64_t *violations) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !culled || !behind || !violations || rays < 0) return fail(PT_ERR_INVALID, "pt_test_sphere_halfline_sweep: bad argument");
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) {
-        if (geoms[i].type != PT_SPHERE && geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_sphere_halfline_sweep: spheres and cubes only");
-        pack_geom(geoms[i], hg[i]);
-    }
+    std::vector<GeomDev> hg;
+    PTCHECK(pack_geoms(geoms, ngeoms, kSpheres | kCubes, nullptr, "pt_test_sphere_halfline_sweep", hg));
     DevBuf<GeomDev> dg;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    int rc = cnt.alloc(3);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 24));
-    const int per_thread = 256, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(k_sweep_sphere_halfline, dim3((unsigned)blocks), dim3(threads), 0, 0, dg.p, ngeoms, (unsigned long long)seed,
-                       per_thread, cnt.p, cnt.p + 1, cnt.p + 2);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 24, hipMemcpyDeviceToHost));
-    *culled = h[0];
-    *behind = h[1];
-    *violations = h[2];
-    return PT_OK;
+    Counters<3> cnt;
+    PTCHECK(dg.upload(hg));
+    PTCHECK(cnt.zero());
+    const int per_thread = 256;
+    PTCHECK(launch_wait(k_sweep_sphere_halfline, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), 0, dg.p, ngeoms, seed, per_thread, cnt.at(0),
+                        cnt.at(1), cnt.at(2)));
+    return cnt.read({culled, behind, violations});
 }
 
-// the sweep's table: every sphere of `geoms` with its culling data as pt_init packs it (thresholds scaled for the folded K |oc|^2 term)
-static void pack_sphere_cull(const PtGeom *geoms, int ngeoms, std::vector<GeomDev> &hg, std::vector<SphereCull> &sc) {
-    hg.resize(ngeoms);
+// the sweeps' table: the primitives of a scene of spheres and cubes, packed, and every sphere with its culling data as pt_init packs it
+// (thresholds scaled for the folded K |oc|^2 term)
+static int pack_sphere_cull(const PtGeom *geoms, int ngeoms, const char *fn, std::vector<GeomDev> &hg, std::vector<SphereCull> &sc) {
+    PTCHECK(pack_geoms(geoms, ngeoms, kSpheres | kCubes, nullptr, fn, hg));
     sc.clear();
     for (int i = 0; i < ngeoms; ++i) {
-        pack_geom(geoms[i], hg[i]);
         if (geoms[i].type != PT_SPHERE) continue;
         SphereCull e;
         memset(&e, 0, sizeof e);
@@ -464,89 +512,70 @@ static void pack_sphere_cull(const PtGeom *geoms, int ngeoms, std::vector<GeomDe
     const float sdir = std::nextafter((float)std::sqrt(1.0 / (1.0 - kmax)), INFINITY);
     for (SphereCull &e : sc)
         if (std::isfinite(e.cullR2)) e.cullR2 = std::nextafter((float)((double)e.cullR2 * (double)sdir * (double)sdir), INFINITY);
+    return PT_OK;
 }
+
+// the two clusters exactly as pt_init builds them for this scene (no primitive binned: binning only moves the choice of the split)
+struct SphereClusters {
+    std::vector<GeomDev> hg;
+    std::vector<SphereCull> sc;
+    int n0 = 0;
+    float omax = 0.0f, box[2][8];
+    int build(const PtGeom *geoms, int ngeoms, const char *fn) {
+        PTCHECK(pack_sphere_cull(geoms, ngeoms, fn, hg, sc));
+        if (!build_sphere_clusters(geoms, ngeoms, hg, std::vector<int>(), sc, n0, omax, box)) return fail(PT_ERR_INVALID, "%s: no clusters for this scene", fn);
+        return PT_OK;
+    }
+    void info(float *info18) const {
+        info18[0] = omax; info18[1] = (float)n0;
+        for (int g = 0; g < 2; ++g) for (int q = 0; q < 8; ++q) info18[2 + 8 * g + q] = box[g][q];
+    }
+};
 
 int pt_test_sphere_clusters(const PtGeom *geoms, int ngeoms, float *info18, int32_t *table, int32_t table_cap, int32_t *ntable) {
     if (!geoms || ngeoms < 2 || !info18 || !table || !ntable) return fail(PT_ERR_INVALID, "pt_test_sphere_clusters: bad argument");
-    for (int i = 0; i < ngeoms; ++i)
-        if (geoms[i].type == PT_MESH) return fail(PT_ERR_INVALID, "pt_test_sphere_clusters: spheres and cubes only");
-    std::vector<GeomDev> hg;
-    std::vector<SphereCull> sc;
-    pack_sphere_cull(geoms, ngeoms, hg, sc);
-    int n0 = 0;
-    float omax = 0.0f, box[2][8];
-    if (!build_sphere_clusters(geoms, ngeoms, hg, std::vector<int>(), sc, n0, omax, box))
-        return fail(PT_ERR_INVALID, "pt_test_sphere_clusters: no clusters for this scene");
-    if ((int)sc.size() > table_cap) return fail(PT_ERR_INVALID, "pt_test_sphere_clusters: table_cap too small (%d entries)", (int)sc.size());
-    info18[0] = omax; info18[1] = (float)n0;
-    for (int g = 0; g < 2; ++g) for (int q = 0; q < 8; ++q) info18[2 + 8 * g + q] = box[g][q];
-    for (size_t i = 0; i < sc.size(); ++i) table[i] = sc[i].geom;
-    *ntable = (int)sc.size();
+    SphereClusters c;
+    PTCHECK(c.build(geoms, ngeoms, "pt_test_sphere_clusters"));
+    if ((int)c.sc.size() > table_cap) return fail(PT_ERR_INVALID, "pt_test_sphere_clusters: table_cap too small (%d entries)", (int)c.sc.size());
+    c.info(info18);
+    for (size_t i = 0; i < c.sc.size(); ++i) table[i] = c.sc[i].geom;
+    *ntable = (int)c.sc.size();
     return PT_OK;
 }
 
 int pt_test_sphere_cluster_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t *certified2, uint64_t *violations, float *info18) {
     NEED_GPU();
     if (!geoms || ngeoms < 2 || !certified2 || !violations || rays < 0) return fail(PT_ERR_INVALID, "pt_test_sphere_cluster_sweep: bad argument");
-    // the clusters exactly as pt_init builds them for this scene (no primitive binned: binning only moves the choice of the split)
-    for (int i = 0; i < ngeoms; ++i)
-        if (geoms[i].type == PT_MESH) return fail(PT_ERR_INVALID, "pt_test_sphere_cluster_sweep: spheres and cubes only");
-    std::vector<GeomDev> hg;
-    std::vector<SphereCull> sc;
-    pack_sphere_cull(geoms, ngeoms, hg, sc);
-    int n0 = 0;
-    float omax = 0.0f, box[2][8];
-    if (!build_sphere_clusters(geoms, ngeoms, hg, std::vector<int>(), sc, n0, omax, box))
-        return fail(PT_ERR_INVALID, "pt_test_sphere_cluster_sweep: no clusters for this scene");
+    SphereClusters c;
+    PTCHECK(c.build(geoms, ngeoms, "pt_test_sphere_cluster_sweep"));
     std::vector<GeomDev> hs;
-    for (const SphereCull &e : sc) hs.push_back(hg[e.geom]);
+    for (const SphereCull &e : c.sc) hs.push_back(c.hg[e.geom]);
     WallBox hb[2];
     memset(hb, 0, sizeof hb);
     for (int g = 0; g < 2; ++g)
-        for (int a = 0; a < 3; ++a) { hb[g].lo[a] = box[g][a]; hb[g].hi[a] = box[g][3 + a]; }
-    F3 slo = F3{INFINITY, INFINITY, INFINITY}, shi = F3{-INFINITY, -INFINITY, -INFINITY};
-    for (int i = 0; i < ngeoms; ++i) {
-        const float r = hg[i].boundR;
-        if (!std::isfinite(r)) continue;
-        slo = F3{std::min(slo.x, hg[i].centre[0] - r), std::min(slo.y, hg[i].centre[1] - r), std::min(slo.z, hg[i].centre[2] - r)};
-        shi = F3{std::max(shi.x, hg[i].centre[0] + r), std::max(shi.y, hg[i].centre[1] + r), std::max(shi.z, hg[i].centre[2] + r)};
-    }
-    if (info18) {
-        info18[0] = omax; info18[1] = (float)n0;
-        for (int g = 0; g < 2; ++g) for (int q = 0; q < 8; ++q) info18[2 + 8 * g + q] = box[g][q];
-    }
+        for (int a = 0; a < 3; ++a) { hb[g].lo[a] = c.box[g][a]; hb[g].hi[a] = c.box[g][3 + a]; }
+    F3 slo, shi;
+    scene_extent(c.hg, slo, shi);
+    if (info18) c.info(info18);
     DevBuf<GeomDev> ds;
     DevBuf<WallBox> db;
-    DevBuf<unsigned long long> cnt;
-    UP(ds, hs.data(), (int)hs.size());
-    UP(db, hb, 2);
-    int rc = cnt.alloc(3);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 24));
-    const int per_thread = 64, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 22)) blocks = 1 << 22;
-    hipLaunchKernelGGL(k_sweep_sphere_clusters, dim3((unsigned)blocks), dim3(threads), 0, 0, ds.p, (int)hs.size(), n0, db.p, omax, slo, shi,
-                       (unsigned long long)seed, per_thread, cnt.p, cnt.p + 2);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long hc[3] = {0, 0, 0};
-    HIPCHECK(hipMemcpy(hc, cnt.p, 24, hipMemcpyDeviceToHost));
-    certified2[0] = hc[0];
-    certified2[1] = hc[1];
-    *violations = hc[2];
-    return PT_OK;
+    Counters<3> cnt;
+    PTCHECK(ds.upload(hs));
+    PTCHECK(db.upload(hb, 2));
+    PTCHECK(cnt.zero());
+    const int per_thread = 64;
+    PTCHECK(launch_wait(k_sweep_sphere_clusters, sweep_grid(rays, per_thread, kTestThreads, 1 << 22), 0, ds.p, (int)hs.size(), c.n0, db.p, c.omax, slo, shi,
+                        seed, per_thread, cnt.at(0), cnt.at(2)));
+    return cnt.read({certified2, certified2 + 1, violations});
 }
 
 int pt_test_sphere_group_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t *certified, uint64_t *violations, int32_t *ngroups) {
     NEED_GPU();
     if (!geoms || ngeoms < 2 || !certified || !violations || rays < 0) return fail(PT_ERR_INVALID, "pt_test_sphere_group_sweep: bad argument");
-    for (int i = 0; i < ngeoms; ++i)
-        if (geoms[i].type == PT_MESH) return fail(PT_ERR_INVALID, "pt_test_sphere_group_sweep: spheres and cubes only");
     // the groups exactly as pt_init builds them for this scene's spheres (one cluster: clusters only split the table in two before the grouping)
     std::vector<GeomDev> hg;
     std::vector<SphereCull> sc;
-    pack_sphere_cull(geoms, ngeoms, hg, sc);
+    PTCHECK(pack_sphere_cull(geoms, ngeoms, "pt_test_sphere_group_sweep", hg, sc));
     if (sc.size() < 2) return fail(PT_ERR_INVALID, "pt_test_sphere_group_sweep: fewer than two spheres");
     double kmax = 0.0;
     for (const SphereCull &e : sc) kmax = std::max(kmax, (double)e.cullK);
@@ -559,44 +588,28 @@ int pt_test_sphere_group_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, i
     if (ngroups) *ngroups = ng;
     std::vector<GeomDev> hs;
     for (const SphereCull &e : sc) hs.push_back(hg[e.geom]);
-    F3 slo = F3{INFINITY, INFINITY, INFINITY}, shi = F3{-INFINITY, -INFINITY, -INFINITY};
-    for (int i = 0; i < ngeoms; ++i) {
-        const float r = hg[i].boundR;
-        if (!std::isfinite(r)) continue;
-        slo = F3{std::min(slo.x, hg[i].centre[0] - r), std::min(slo.y, hg[i].centre[1] - r), std::min(slo.z, hg[i].centre[2] - r)};
-        shi = F3{std::max(shi.x, hg[i].centre[0] + r), std::max(shi.y, hg[i].centre[1] + r), std::max(shi.z, hg[i].centre[2] + r)};
-    }
+    F3 slo, shi;
+    scene_extent(hg, slo, shi);
     DevBuf<GeomDev> ds;
     DevBuf<SphereCull> dg;
-    DevBuf<unsigned long long> cnt;
-    UP(ds, hs.data(), (int)hs.size());
-    UP(dg, groups.data(), (int)groups.size());
-    int rc = cnt.alloc(2);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 16));
-    const int per_thread = 64, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 22)) blocks = 1 << 22;
-    hipLaunchKernelGGL(k_sweep_sphere_groups, dim3((unsigned)blocks), dim3(threads), 0, 0, ds.p, (int)hs.size(), dg.p, ng, sdir, std::nextafter((float)ob, 0.0f), slo, shi,
-                       (unsigned long long)seed, per_thread, cnt.p, cnt.p + 1);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long hc[2] = {0, 0};
-    HIPCHECK(hipMemcpy(hc, cnt.p, 16, hipMemcpyDeviceToHost));
-    *certified = hc[0];
-    *violations = hc[1];
-    return PT_OK;
+    Counters<2> cnt;
+    PTCHECK(ds.upload(hs));
+    PTCHECK(dg.upload(groups));
+    PTCHECK(cnt.zero());
+    const int per_thread = 64;
+    PTCHECK(launch_wait(k_sweep_sphere_groups, sweep_grid(rays, per_thread, kTestThreads, 1 << 22), 0, ds.p, (int)hs.size(), dg.p, ng, sdir,
+                        std::nextafter((float)ob, 0.0f), slo, shi, seed, per_thread, cnt.at(0), cnt.at(1)));
+    return cnt.read({certified, violations});
 }
 
 int pt_test_wall_box_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t *culled, uint64_t *violations) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !culled || !violations || rays < 0) return fail(PT_ERR_INVALID, "pt_test_wall_box_sweep: bad argument");
-    std::vector<GeomDev> hg(ngeoms);
+    std::vector<GeomDev> hg;
+    PTCHECK(pack_geoms(geoms, ngeoms, kCubes, nullptr, "pt_test_wall_box_sweep", hg));
     std::vector<WallBox> hw(ngeoms);
     std::vector<float> omax(ngeoms);
     for (int i = 0; i < ngeoms; ++i) {
-        if (geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_wall_box_sweep: cubes only");
-        pack_geom(geoms[i], hg[i]);
         double om = 0;
         const double b = wall_box(geoms[i], hw[i], &om);
         if (b < 0) return fail(PT_ERR_INVALID, "pt_test_wall_box_sweep: cube %d is not finite", i);
@@ -605,43 +618,28 @@ int pt_test_wall_box_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64
     DevBuf<GeomDev> dg;
     DevBuf<WallBox> dw;
     DevBuf<float> dm;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    UP(dw, hw.data(), ngeoms);
-    UP(dm, omax.data(), ngeoms);
-    int rc = cnt.alloc(2);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 16));
-    const int per_thread = 256, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(k_sweep_wall_box, dim3((unsigned)blocks), dim3(threads), 0, 0, dg.p, dw.p, dm.p, ngeoms, (unsigned long long)seed,
-                       per_thread, cnt.p, cnt.p + 1);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[2] = {0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 16, hipMemcpyDeviceToHost));
-    *culled = h[0];
-    *violations = h[1];
-    return PT_OK;
+    Counters<2> cnt;
+    PTCHECK(dg.upload(hg));
+    PTCHECK(dw.upload(hw));
+    PTCHECK(dm.upload(omax));
+    PTCHECK(cnt.zero());
+    const int per_thread = 256;
+    PTCHECK(launch_wait(k_sweep_wall_box, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), 0, dg.p, dw.p, dm.p, ngeoms, seed, per_thread, cnt.at(0),
+                        cnt.at(1)));
+    return cnt.read({culled, violations});
 }
 
 // host only: no GPU is touched
 int pt_test_camera_cull_tables(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int32_t *rects4, int32_t *scene_rect4, int32_t *spans2) {
     if (!cam || !geoms || ngeoms < 1 || !rects4 || !scene_rect4 || !spans2) return fail(PT_ERR_INVALID, "pt_test_camera_cull_tables: bad argument");
-    if (cam->resolution[0] < 1 || cam->resolution[1] < 1) return fail(PT_ERR_INVALID, "pt_test_camera_cull_tables: bad resolution");
-    KParams k;
-    memset(&k, 0, sizeof k);
-    camera_params(*cam, k);
-    k.ngeoms = ngeoms;
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i], k.pos);
-    CameraCull cc;
-    build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
+    CameraFixture f;
+    PTCHECK(f.cull(cam, geoms, ngeoms, kAnyGeom, kAnyResolution, "pt_test_camera_cull_tables"));
+    const std::vector<GeomDev> &hg = f.hg;
+    const CameraCull &cc = f.cc;
     for (int i = 0; i < ngeoms; ++i)
         for (int a = 0; a < 4; ++a) rects4[4 * i + a] = hg[i].rect[a];
     for (int a = 0; a < 4; ++a) scene_rect4[a] = cc.sceneRect[a];
-    for (int y = 0; y < k.H; ++y)
+    for (int y = 0; y < f.k.H; ++y)
         for (int i = 0; i < ngeoms; ++i) {
             int x0 = 1, x1 = 0;                                // (empty: the row's list does not hold the primitive)
             if (cc.rowOff.empty()) { x0 = hg[i].rect[0]; x1 = hg[i].rect[2]; }
@@ -654,80 +652,57 @@ int pt_test_camera_cull_tables(const PtCamera *cam, const PtGeom *geoms, int nge
     return PT_OK;
 }
 
+// what pt_test_camera_list and pt_test_camera_resolved hand out of a list (`face`: the resolved one's per-wave faces)
+static void copy_camera_list(const CameraList &cl, uint32_t *pix, int32_t *wave2, int32_t *sig_idx, int32_t *face) {
+    memcpy(pix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t));
+    memcpy(wave2, cl.wave.data(), cl.wave.size() * sizeof(int));
+    memcpy(sig_idx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int));
+    if (face) memcpy(face, cl.face.data(), cl.face.size() * sizeof(int));
+}
+
 // host only: the camera rays' packed work list pt_init builds from the same tables (build_camera_list), for one shard, without a length cap
 int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
                         int32_t *sig_idx, int64_t *sizes4) {
     if (!cam || !geoms || ngeoms < 1 || !sizes4) return fail(PT_ERR_INVALID, "pt_test_camera_list: bad argument");
-    if (cam->resolution[0] < 1 || cam->resolution[1] < 1) return fail(PT_ERR_INVALID, "pt_test_camera_list: bad resolution");
-    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(PT_ERR_INVALID, "pt_test_camera_list: bad shard");
-    KParams k;
-    memset(&k, 0, sizeof k);
-    camera_params(*cam, k);
-    k.ngeoms = ngeoms;
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i], k.pos);
-    CameraCull cc;
-    build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
+    CameraFixture f;
     CameraList cl;
-    const bool built = build_camera_list(cc, k.W, k.H, shard_rank, shard_count, std::numeric_limits<long long>::max(), cl);
+    bool built = false;
+    PTCHECK(f.cull(cam, geoms, ngeoms, kAnyGeom, kAnyResolution, "pt_test_camera_list"));
+    PTCHECK(f.list(geoms, shard_rank, shard_count, false, "pt_test_camera_list", cl, built));
     sizes4[0] = built ? (int64_t)cl.pix.size() : -1;
     sizes4[1] = (int64_t)cl.sigIdx.size();
     sizes4[2] = cl.listed;
-    sizes4[3] = (int64_t)(k.H > shard_rank ? (k.H - shard_rank + shard_count - 1) / shard_count : 0) * k.W;
-    if (built && pix && wave2 && sig_idx) {
-        memcpy(pix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t));
-        memcpy(wave2, cl.wave.data(), cl.wave.size() * sizeof(int));
-        memcpy(sig_idx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int));
-    }
+    sizes4[3] = (int64_t)(f.k.H > shard_rank ? (f.k.H - shard_rank + shard_count - 1) / shard_count : 0) * f.k.W;
+    if (built && pix && wave2 && sig_idx) copy_camera_list(cl, pix, wave2, sig_idx, nullptr);
     return PT_OK;
 }
 
-// host only: the list as pt_init builds it for the untextured forms -- one-cube signatures split by the face their pixels are
-// resolved to (camera_face_certificate) -- with the per-wave faces beside it; no length cap
-static bool test_camera_resolved_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, KParams &k,
-                                      std::vector<GeomDev> &hg, CameraList &cl) {
-    memset(&k, 0, sizeof k);
-    camera_params(*cam, k);
-    k.ngeoms = ngeoms;
-    hg.resize(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i], k.pos);
-    CameraCull cc;
-    build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
-    CameraResolve cr;
-    build_camera_resolve(geoms, ngeoms, k, hg, cr);
-    return build_camera_list(cc, k.W, k.H, shard_rank, shard_count, std::numeric_limits<long long>::max(), cl, &cr);
-}
+// host only: the list as pt_init builds it for the untextured forms, with the per-wave faces beside it; no length cap
 int pt_test_camera_resolved(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
                             int32_t *sig_idx, int32_t *face, int64_t *sizes4) {
     if (!cam || !geoms || ngeoms < 1 || !sizes4) return fail(PT_ERR_INVALID, "pt_test_camera_resolved: bad argument");
-    if (cam->resolution[0] < 1 || cam->resolution[1] < 1) return fail(PT_ERR_INVALID, "pt_test_camera_resolved: bad resolution");
-    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(PT_ERR_INVALID, "pt_test_camera_resolved: bad shard");
-    KParams k;
-    std::vector<GeomDev> hg;
+    CameraFixture f;
     CameraList cl;
-    const bool built = test_camera_resolved_list(cam, geoms, ngeoms, shard_rank, shard_count, k, hg, cl);
+    bool built = false;
+    PTCHECK(f.cull(cam, geoms, ngeoms, kAnyGeom, kAnyResolution, "pt_test_camera_resolved"));
+    PTCHECK(f.list(geoms, shard_rank, shard_count, true, "pt_test_camera_resolved", cl, built));
     sizes4[0] = built ? (int64_t)cl.pix.size() : -1;
     sizes4[1] = (int64_t)cl.sigIdx.size();
     sizes4[2] = cl.listed;
     sizes4[3] = cl.resolved;
-    if (built && pix && wave2 && sig_idx && face) {
-        memcpy(pix, cl.pix.data(), cl.pix.size() * sizeof(uint32_t));
-        memcpy(wave2, cl.wave.data(), cl.wave.size() * sizeof(int));
-        memcpy(sig_idx, cl.sigIdx.data(), cl.sigIdx.size() * sizeof(int));
-        memcpy(face, cl.face.data(), cl.face.size() * sizeof(int));
-    }
+    if (built && pix && wave2 && sig_idx && face) copy_camera_list(cl, pix, wave2, sig_idx, face);
     return PT_OK;
 }
 
 int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t seed, uint64_t counts[3]) {
     NEED_GPU();
     if (!cam || !geoms || ngeoms < 1 || samples < 0 || samples > 4096 || !counts) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: bad argument");
-    if (cam->resolution[0] < 1 || cam->resolution[1] < 1 || (long long)cam->resolution[0] * cam->resolution[1] > (1ll << 22))
-        return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: bad resolution");
-    KParams k;
-    std::vector<GeomDev> hg;
+    CameraFixture f;
     CameraList cl;
-    if (!test_camera_resolved_list(cam, geoms, ngeoms, 0, 1, k, hg, cl)) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: no work list for this scene");
+    bool built = false;
+    PTCHECK(f.cull(cam, geoms, ngeoms, kAnyGeom, 1ll << 22, "pt_test_face_hit_sweep"));
+    PTCHECK(f.list(geoms, 0, 1, true, "pt_test_face_hit_sweep", cl, built));
+    if (!built) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: no work list for this scene");
     std::vector<int> entries;
     for (size_t w = 0; w < cl.face.size(); ++w) {
         if (cl.face[w] < 0) continue;
@@ -737,111 +712,69 @@ int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms,
     counts[0] = counts[1] = 0;
     counts[2] = entries.size() / 3;
     if (entries.empty()) return PT_OK;
+    const KParams &k = f.k;
     const float cam16[16] = {k.view[0], k.view[1], k.view[2], k.up[0], k.up[1], k.up[2], k.right[0], k.right[1], k.right[2],
                              k.pos[0], k.pos[1], k.pos[2], k.pixLenX, k.pixLenY, k.halfW, k.halfH};
     DevBuf<GeomDev> dg;
     DevBuf<float> dc;
     DevBuf<int> de;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    UP(dc, cam16, 16);
-    UP(de, entries.data(), entries.size());
-    int rc = cnt.alloc(2);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 16));
+    Counters<2> cnt;
+    PTCHECK(dg.upload(f.hg));
+    PTCHECK(dc.upload(cam16, 16));
+    PTCHECK(de.upload(entries));
+    PTCHECK(cnt.zero());
+    // (one ray per lane, and lanes that stride over the rest where the cap cuts the grid: the kernel's streams are per ray)
     const long long total = (long long)(entries.size() / 3) * (samples + 4);
-    long long blocks = (total + 255) / 256;
-    if (blocks > (1 << 16)) blocks = 1 << 16;
-    hipLaunchKernelGGL(k_sweep_face_hit, dim3((unsigned)blocks), dim3(256), 0, 0, dg.p, dc.p, de.p, (int)(entries.size() / 3), samples,
-                       (unsigned long long)seed, cnt.p);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[2] = {0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 16, hipMemcpyDeviceToHost));
-    counts[0] = h[0];
-    counts[1] = h[1];
-    return PT_OK;
+    PTCHECK(launch_wait(k_sweep_face_hit, sweep_grid(total, 1, kTestThreads, 1 << 16), 0, dg.p, dc.p, de.p, (int)(entries.size() / 3), samples, seed,
+                        cnt.at(0)));
+    return cnt.read({counts, counts + 1});
 }
 
 int pt_test_camera_cull_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t *hits, uint64_t *culled,
                               uint64_t *violations) {
     NEED_GPU();
     if (!cam || !geoms || ngeoms < 1 || samples < 1 || !hits || !culled || !violations) return fail(PT_ERR_INVALID, "pt_test_camera_cull_sweep: bad argument");
-    if (cam->resolution[0] < 1 || cam->resolution[1] < 1 || (long long)cam->resolution[0] * cam->resolution[1] > (1ll << 26))
-        return fail(PT_ERR_INVALID, "pt_test_camera_cull_sweep: bad resolution");
-    for (int i = 0; i < ngeoms; ++i)
-        if (geoms[i].type != PT_SPHERE && geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_camera_cull_sweep: spheres and cubes only");
     // exactly what pt_init derives: camera constants, packed primitives (object-space eye), rectangles, union, row lists
-    KParams k;
-    memset(&k, 0, sizeof k);
-    camera_params(*cam, k);
-    k.ngeoms = ngeoms;
-    magic_divisor((uint32_t)k.W, k.magicW, k.shiftW);
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) pack_geom(geoms[i], hg[i], k.pos);
-    CameraCull cc;
-    build_camera_cull(geoms, ngeoms, k, false, std::vector<const float *>(ngeoms, nullptr), hg, cc);
-    for (int a = 0; a < 4; ++a) k.sceneRect[a] = cc.sceneRect[a];
+    CameraFixture f;
+    PTCHECK(f.cull(cam, geoms, ngeoms, kSpheres | kCubes, 1ll << 26, "pt_test_camera_cull_sweep"));
     DevBuf<GeomDev> dg;
     DevBuf<int> doff, didx;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    if (!cc.rowOff.empty()) {
-        UP(doff, cc.rowOff.data(), cc.rowOff.size());
-        UP(didx, cc.rowIdx.data(), cc.rowIdx.size());
+    Counters<3> cnt;
+    PTCHECK(dg.upload(f.hg));
+    if (!f.cc.rowOff.empty()) {
+        PTCHECK(doff.upload(f.cc.rowOff));
+        PTCHECK(didx.upload(f.cc.rowIdx));
     }
-    int rc = cnt.alloc(3);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 24));
-    const int npix = k.W * k.H;
-    hipLaunchKernelGGL(k_sweep_camera_cull, GRID(npix), k, dg.p, doff.p, didx.p, samples, cnt.p, cnt.p + 1, cnt.p + 2);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 24, hipMemcpyDeviceToHost));
-    *hits = h[0];
-    *culled = h[1];
-    *violations = h[2];
-    return PT_OK;
+    PTCHECK(cnt.zero());
+    PTCHECK(launch_wait(k_sweep_camera_cull, blocks_for(f.k.W * f.k.H), 0, f.k, dg.p, doff.p, didx.p, samples, cnt.at(0), cnt.at(1), cnt.at(2)));
+    return cnt.read({hits, culled, violations});
 }
 
 int pt_test_camera_cull_margin(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, double *worst_fraction, uint64_t *needed) {
     NEED_GPU();
     if (!cam || !geoms || ngeoms < 1 || samples < 1 || !worst_fraction || !needed) return fail(PT_ERR_INVALID, "pt_test_camera_cull_margin: bad argument");
-    if (cam->resolution[0] < 1 || cam->resolution[1] < 1 || (long long)cam->resolution[0] * cam->resolution[1] > (1ll << 26))
-        return fail(PT_ERR_INVALID, "pt_test_camera_cull_margin: bad resolution");
-    for (int i = 0; i < ngeoms; ++i)
-        if (geoms[i].type != PT_SPHERE && geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_camera_cull_margin: spheres and cubes only");
-    KParams k;
-    memset(&k, 0, sizeof k);
-    camera_params(*cam, k);
-    k.ngeoms = ngeoms;
-    magic_divisor((uint32_t)k.W, k.magicW, k.shiftW);
-    std::vector<GeomDev> hg(ngeoms);
+    CameraFixture f;
+    PTCHECK(f.pack(cam, geoms, ngeoms, kSpheres | kCubes, 1ll << 26, "pt_test_camera_cull_margin"));
     std::vector<double> infl(4 * (size_t)ngeoms, 0.0);
     for (int i = 0; i < ngeoms; ++i) {
-        pack_geom(geoms[i], hg[i], k.pos);
         double lo[3], hi[3];
-        inflated_object_box(geoms[i], k.pos, nullptr, lo, hi);
+        inflated_object_box(geoms[i], f.k.pos, nullptr, lo, hi);
         int rect[4];
         std::vector<std::pair<double, double>> hull;
-        project_geom(geoms[i], k, rect, nullptr, &hull);
+        project_geom(geoms[i], f.k, rect, nullptr, &hull);
         for (int a = 0; a < 3; ++a) infl[4 * i + a] = geoms[i].type == PT_CUBE ? hi[a] - 0.5 : hi[0];
         infl[4 * i + 3] = hull.empty() ? 0.0 : 1.0;          // (culling switched off for this primitive: nothing to measure)
     }
     DevBuf<GeomDev> dg;
     DevBuf<double> di;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    UP(di, infl.data(), infl.size());
-    int rc = cnt.alloc(2);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 16));
-    const int npix = k.W * k.H;
-    hipLaunchKernelGGL(k_sweep_camera_cull_margin, GRID(npix), k, dg.p, di.p, samples, cnt.p, cnt.p + 1);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[2] = {0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 16, hipMemcpyDeviceToHost));
-    memcpy(worst_fraction, &h[0], sizeof(double));
-    *needed = h[1];
+    Counters<2> cnt;
+    PTCHECK(dg.upload(f.hg));
+    PTCHECK(di.upload(infl));
+    PTCHECK(cnt.zero());
+    PTCHECK(launch_wait(k_sweep_camera_cull_margin, blocks_for(f.k.W * f.k.H), 0, f.k, dg.p, di.p, samples, cnt.at(0), cnt.at(1)));
+    PTCHECK(cnt.read());
+    memcpy(worst_fraction, &cnt.h[0], sizeof(double));
+    *needed = cnt.h[1];
     return PT_OK;
 }
 
@@ -849,17 +782,11 @@ int pt_test_wall_plane_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int
                              uint64_t *violations, uint64_t *single) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !nplane || !certified || !violations || !single || rays < 0) return fail(PT_ERR_INVALID, "pt_test_wall_plane_sweep: bad argument");
-    // the walls exactly as pt_init chooses and numbers them (no primitive of the set is binned here)
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) {
-        if (geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_wall_plane_sweep: cubes only");
-        pack_geom(geoms[i], hg[i]);
-    }
+    std::vector<GeomDev> hg;
     KParams k;
-    memset(&k, 0, sizeof k);
-    std::vector<WallBox> hw(kWallMax);
+    std::vector<WallBox> hw;
     std::vector<int> wallGeom;
-    choose_walls(geoms, ngeoms, hg, k, hw, wallGeom);
+    PTCHECK(test_choose_walls(geoms, ngeoms, "pt_test_wall_plane_sweep", hg, k, hw, wallGeom));
     *nplane = k.nSlotWalls + k.nPlaneWalls;
     *certified = *violations = *single = 0;
     if (k.nWalls < 1 || k.nSlotWalls + k.nPlaneWalls < 1) return PT_OK;
@@ -867,66 +794,42 @@ int pt_test_wall_plane_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int
     for (int w = 0; w < k.nWalls; ++w) wg[w] = hg[wallGeom[w]];
     DevBuf<GeomDev> dg;
     DevBuf<WallBox> dw;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, wg.data(), k.nWalls);
-    UP(dw, hw.data(), k.nWalls);
-    int rc = cnt.alloc(3);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 24));
-    const int per_thread = 256, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(k_sweep_wall_planes, dim3((unsigned)blocks), dim3(threads), 0, 0, k, dg.p, dw.p, (unsigned long long)seed, per_thread,
-                       cnt.p, cnt.p + 1, cnt.p + 2);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[3] = {0, 0, 0};
-    HIPCHECK(hipMemcpy(h, cnt.p, 24, hipMemcpyDeviceToHost));
-    *certified = h[0];
-    *violations = h[1];
-    *single = h[2];
-    return PT_OK;
+    Counters<3> cnt;
+    PTCHECK(dg.upload(wg));
+    PTCHECK(dw.upload(hw.data(), k.nWalls));
+    PTCHECK(cnt.zero());
+    const int per_thread = 256;
+    PTCHECK(launch_wait(k_sweep_wall_planes, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), 0, k, dg.p, dw.p, seed, per_thread, cnt.at(0), cnt.at(1),
+                        cnt.at(2)));
+    return cnt.read({certified, violations, single});
 }
 
 int pt_test_box_fast_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t counts[4], uint64_t div_mismatches[2]) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !counts || !div_mismatches || rays < 0) return fail(PT_ERR_INVALID, "pt_test_box_fast_sweep: bad argument");
-    std::vector<GeomDev> hg(ngeoms);
-    for (int i = 0; i < ngeoms; ++i) {
-        if (geoms[i].type != PT_CUBE) return fail(PT_ERR_INVALID, "pt_test_box_fast_sweep: cubes only");
-        pack_geom(geoms[i], hg[i]);
-    }
+    std::vector<GeomDev> hg;
+    PTCHECK(pack_geoms(geoms, ngeoms, kCubes, nullptr, "pt_test_box_fast_sweep", hg));
     DevBuf<GeomDev> dg;
-    DevBuf<unsigned long long> cnt;
-    UP(dg, hg.data(), ngeoms);
-    int rc = cnt.alloc(8);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(cnt.p, 0, 64));
     DevBuf<float> dump;
-    const bool verbose = getenv("PT_AMD_VERBOSE") && atoi(getenv("PT_AMD_VERBOSE"));
-    if (verbose && (rc = dump.alloc(8 * 24))) return rc;
-    const int per_thread = 256, threads = 256;
-    long long blocks = (rays + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(k_sweep_box_fast, dim3((unsigned)blocks), dim3(threads), 0, 0, dg.p, ngeoms, (unsigned long long)seed, per_thread, cnt.p,
-                       verbose ? dump.p : nullptr);
-    hipLaunchKernelGGL(k_sweep_div_unscaled, dim3(1 << 12), dim3(256), 0, 0, (unsigned long long)seed, 1024, cnt.p + 4);   // 2^20 threads
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[8];
-    HIPCHECK(hipMemcpy(h, cnt.p, 64, hipMemcpyDeviceToHost));
-    if (verbose && h[6]) {                                // (experiments: the first mismatching rays)
+    Counters<8> cnt;                                      // (0 .. 3: the box sweep's, 4 .. 5: the division's, 6: mismatching rays dumped)
+    PTCHECK(dg.upload(hg));
+    PTCHECK(cnt.zero());
+    const bool verbose = env_flag("PT_AMD_VERBOSE");
+    if (verbose) PTCHECK(dump.alloc(8 * 24));
+    const int per_thread = 256;
+    PTCHECK(launch_wait(k_sweep_box_fast, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), 0, dg.p, ngeoms, seed, per_thread, cnt.at(0),
+                        verbose ? dump.p : nullptr));
+    PTCHECK(launch_wait(k_sweep_div_unscaled, dim3(1 << 12), 0, seed, 1024, cnt.at(4)));   // 2^20 threads
+    PTCHECK(cnt.read({counts, counts + 1, counts + 2, counts + 3, div_mismatches, div_mismatches + 1}));
+    if (verbose && cnt.h[6]) {                            // (experiments: the first mismatching rays)
         float r[8 * 24];
-        HIPCHECK(hipMemcpy(r, dump.p, sizeof r, hipMemcpyDeviceToHost));
-        for (int i = 0; i < (int)std::min<unsigned long long>(h[6], 8); ++i) {
+        PTCHECK(download(r, dump, 8 * 24));
+        for (int i = 0; i < (int)std::min<unsigned long long>(cnt.h[6], 8); ++i) {
             const float *q = r + 24 * i;
             fprintf(stderr, "box sweep mismatch: geom %d org %.9g %.9g %.9g dir %.9g %.9g %.9g | t fast %.9g exact %.9g early %.9g outside %g %g | P %.9g %.9g %.9g / %.9g %.9g %.9g | n %a %a %a / %a %a %a\n",
                     (int)q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], q[10], q[11], q[12], q[13], q[14], q[15], q[16], q[17], q[18], q[19], q[20], q[21], q[22], q[23]);
         }
     }
-    for (int i = 0; i < 4; ++i) counts[i] = h[i];
-    div_mismatches[0] = h[4];
-    div_mismatches[1] = h[5];
     return PT_OK;
 }
 
@@ -934,51 +837,36 @@ int pt_test_slab_quotients(const float *o, const float *d, int n, float *t1, flo
     NEED_GPU();
     if (n <= 0) return PT_OK;
     DevBuf<float> a, b, q1, q2, r1, r2;
-    UP(a, o, n);
-    UP(b, d, n);
-    int rc;
-    if ((rc = q1.alloc(n)) || (rc = q2.alloc(n)) || (rc = r1.alloc(n)) || (rc = r2.alloc(n))) return rc;
-    hipLaunchKernelGGL(k_test_slab_quotients, GRID(n), a.p, b.p, n, q1.p, q2.p, r1.p, r2.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(t1, q1, n);
-    DOWN(t2, q2, n);
-    DOWN(ref1, r1, n);
-    DOWN(ref2, r2, n);
-    return PT_OK;
+    PTCHECK(a.upload(o, n));
+    PTCHECK(b.upload(d, n));
+    PTCHECK(q1.alloc(n));
+    PTCHECK(q2.alloc(n));
+    PTCHECK(r1.alloc(n));
+    PTCHECK(r2.alloc(n));
+    PTCHECK(launch_wait(k_test_slab_quotients, blocks_for(n), 0, a.p, b.p, n, q1.p, q2.p, r1.p, r2.p));
+    PTCHECK(download(t1, q1, n));
+    PTCHECK(download(t2, q2, n));
+    PTCHECK(download(ref1, r1, n));
+    return download(ref2, r2, n);
 }
 
 int pt_test_slab_quotients_sweep(uint64_t seed, int64_t pairs, uint64_t *mismatches) {
     NEED_GPU();
     if (!mismatches || pairs < 0) return fail(PT_ERR_INVALID, "pt_test_slab_quotients_sweep: bad argument");
-    DevBuf<unsigned long long> m;
-    int rc = m.alloc(1);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(m.p, 0, 8));
-    const int per_thread = 1024, threads = 256;
-    long long blocks = (pairs + (long long)per_thread * threads - 1) / ((long long)per_thread * threads);
-    if (blocks < 1) blocks = 1;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    hipLaunchKernelGGL(k_sweep_slab_quotients, dim3((unsigned)blocks), dim3(threads), 0, 0, (unsigned long long)seed, per_thread, m.p);
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h = 0;
-    HIPCHECK(hipMemcpy(&h, m.p, 8, hipMemcpyDeviceToHost));
-    *mismatches = h;
-    return PT_OK;
+    Counters<1> cnt;
+    PTCHECK(cnt.zero());
+    const int per_thread = 1024;
+    PTCHECK(launch_wait(k_sweep_slab_quotients, sweep_grid(pairs, per_thread, kTestThreads, 1 << 20), 0, seed, per_thread, cnt.at(0)));
+    return cnt.read({mismatches});
 }
 
 int pt_test_unscaled_sqrt_sweep(uint64_t mismatches[4]) {
     NEED_GPU();
     if (!mismatches) return fail(PT_ERR_INVALID, "pt_test_unscaled_sqrt_sweep: bad argument");
-    DevBuf<unsigned long long> m;
-    int rc = m.alloc(4);
-    if (rc) return rc;
-    HIPCHECK(hipMemset(m.p, 0, 32));
-    hipLaunchKernelGGL(k_sweep_unscaled_sqrt, dim3(1 << 14), dim3(256), 0, 0, m.p);   // 2^22 threads x 2^10 patterns
-    HIPCHECK(hipDeviceSynchronize());
-    unsigned long long h[4];
-    HIPCHECK(hipMemcpy(h, m.p, 32, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 4; ++i) mismatches[i] = h[i];
-    return PT_OK;
+    Counters<4> cnt;
+    PTCHECK(cnt.zero());
+    PTCHECK(launch_wait(k_sweep_unscaled_sqrt, dim3(1 << 14), 0, cnt.at(0)));   // 2^22 threads x 2^10 patterns
+    return cnt.read({mismatches, mismatches + 1, mismatches + 2, mismatches + 3});
 }
 
 #ifdef PT_PROBE_TIMELINE
@@ -1025,38 +913,32 @@ int pt_test_hemisphere(const float *normals3, const int32_t *iid3, int n, float 
     if (n <= 0) return PT_OK;
     DevBuf<float> a, o;
     DevBuf<int> b;
-    UP(a, normals3, (size_t)n * 3);
-    UP(b, iid3, (size_t)n * 3);
-    int rc = o.alloc((size_t)n * 3); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_hemisphere, GRID(n), a.p, b.p, n, o.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(out3, o, (size_t)n * 3);
-    return PT_OK;
+    PTCHECK(a.upload(normals3, (size_t)n * 3));
+    PTCHECK(b.upload(iid3, (size_t)n * 3));
+    PTCHECK(o.alloc((size_t)n * 3));
+    PTCHECK(launch_wait(k_test_hemisphere, blocks_for(n), 0, a.p, b.p, n, o.p));
+    return download(out3, o, (size_t)n * 3);
 }
 
 int pt_test_pow(const float *x, const float *e, int n, float *out) {
     NEED_GPU();
     if (n <= 0) return PT_OK;
     DevBuf<float> a, b, o;
-    UP(a, x, n);
-    UP(b, e, n);
-    int rc = o.alloc(n); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_pow, GRID(n), a.p, b.p, n, o.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(out, o, n);
-    return PT_OK;
+    PTCHECK(a.upload(x, n));
+    PTCHECK(b.upload(e, n));
+    PTCHECK(o.alloc(n));
+    PTCHECK(launch_wait(k_test_pow, blocks_for(n), 0, a.p, b.p, n, o.p));
+    return download(out, o, n);
 }
 
 int pt_test_exp_neg_poly(const float *a, int n, float *out) {
     NEED_GPU();
     if (n <= 0) return PT_OK;
     DevBuf<float> x, o;
-    UP(x, a, n);
-    int rc = o.alloc(n); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_exp_neg_poly, GRID(n), x.p, n, o.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(out, o, n);
-    return PT_OK;
+    PTCHECK(x.upload(a, n));
+    PTCHECK(o.alloc(n));
+    PTCHECK(launch_wait(k_test_exp_neg_poly, blocks_for(n), 0, x.p, n, o.p));
+    return download(out, o, n);
 }
 
 int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms) {
@@ -1088,14 +970,14 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
     const size_t P = (size_t)w * h;
     DevBuf<float> S, Q, Hn, outN;
     DevBuf<float4> pos, nrm, Hc, Hpos, Hnrm, out;
-    UP(S, rgb_sum, P * 3);
-    UP(Q, lum_sq_sum, P);
-    UP(Hn, hn, P);
-    UP(pos, reinterpret_cast<const float4 *>(pos_t4), P);
-    UP(nrm, reinterpret_cast<const float4 *>(nrm_id4), P);
-    UP(Hc, reinterpret_cast<const float4 *>(hc4), P);
-    UP(Hpos, reinterpret_cast<const float4 *>(hpos_t4), P);
-    UP(Hnrm, reinterpret_cast<const float4 *>(hnrm_id4), P);
+    PTCHECK(S.upload(rgb_sum, P * 3));
+    PTCHECK(Q.upload(lum_sq_sum, P));
+    PTCHECK(Hn.upload(hn, P));
+    PTCHECK(pos.upload(reinterpret_cast<const float4 *>(pos_t4), P));
+    PTCHECK(nrm.upload(reinterpret_cast<const float4 *>(nrm_id4), P));
+    PTCHECK(Hc.upload(reinterpret_cast<const float4 *>(hc4), P));
+    PTCHECK(Hpos.upload(reinterpret_cast<const float4 *>(hpos_t4), P));
+    PTCHECK(Hnrm.upload(reinterpret_cast<const float4 *>(hnrm_id4), P));
     int rc = out.alloc(P); if (rc) return rc;
     rc = outN.alloc(P); if (rc) return rc;
     TemporalArgs T;
@@ -1120,7 +1002,7 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
-    if (capture) DOWN(out_n, outN, P);
+    if (capture) PTCHECK(download(out_n, outN, P));
     return PT_OK;
 }
 
@@ -1148,8 +1030,8 @@ int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, in
     const size_t P = (size_t)w * h, tiles = (size_t)((w + kNoiseTile - 1) / kNoiseTile) * (size_t)((h + kNoiseTile - 1) / kNoiseTile);
     DevBuf<float> S, Q, map, var;
     DevBuf<uint32_t> frame;
-    UP(S, rgb_sum, P * 3);
-    UP(Q, lum_sq_sum, P);
+    PTCHECK(S.upload(rgb_sum, P * 3));
+    PTCHECK(Q.upload(lum_sq_sum, P));
     int rc = frame.alloc(2); if (rc) return rc;
     if (tile_rel_var_host) { rc = map.alloc(tiles); if (rc) return rc; }
     const float thr2 = threshold * threshold;
@@ -1158,7 +1040,7 @@ int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, in
     rc = noise_launch(S.p, Q.p, w, h, samples, lum_floor, thr2, frame.p, map.p, nullptr, nullptr, tpw); if (rc) return rc;
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(words, frame.p, sizeof words, hipMemcpyDeviceToHost));
-    if (tile_rel_var_host) DOWN(tile_rel_var_host, map, tiles);
+    if (tile_rel_var_host) PTCHECK(download(tile_rel_var_host, map, tiles));
     noise_fill(out, w, h, samples, thr2, words, 0.0f);
     if (!ms) return PT_OK;
     if (P > 0x7fffffffull - kBlock) return fail(PT_ERR_INVALID, "pt_test_noise_stats: k_variance indexes with an int");
@@ -1188,30 +1070,26 @@ int pt_test_sincos(const float *x, int n, float *s, float *c) {
     NEED_GPU();
     if (n <= 0) return PT_OK;
     DevBuf<float> a, ds, dc;
-    UP(a, x, n);
-    int rc = ds.alloc(n); if (rc) return rc;
-    rc = dc.alloc(n); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_sincos, GRID(n), a.p, n, ds.p, dc.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(s, ds, n);
-    DOWN(c, dc, n);
-    return PT_OK;
+    PTCHECK(a.upload(x, n));
+    PTCHECK(ds.alloc(n));
+    PTCHECK(dc.alloc(n));
+    PTCHECK(launch_wait(k_test_sincos, blocks_for(n), 0, a.p, n, ds.p, dc.p));
+    PTCHECK(download(s, ds, n));
+    return download(c, dc, n);
 }
 
 int pt_test_reflect_refract(const float *I3, const float *N3, const float *eta, int n, float *refl3, float *refr3) {
     NEED_GPU();
     if (n <= 0) return PT_OK;
     DevBuf<float> a, b, e, r1, r2;
-    UP(a, I3, (size_t)n * 3);
-    UP(b, N3, (size_t)n * 3);
-    UP(e, eta, n);
-    int rc = r1.alloc((size_t)n * 3); if (rc) return rc;
-    rc = r2.alloc((size_t)n * 3); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_reflect_refract, GRID(n), a.p, b.p, e.p, n, r1.p, r2.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(refl3, r1, (size_t)n * 3);
-    DOWN(refr3, r2, (size_t)n * 3);
-    return PT_OK;
+    PTCHECK(a.upload(I3, (size_t)n * 3));
+    PTCHECK(b.upload(N3, (size_t)n * 3));
+    PTCHECK(e.upload(eta, n));
+    PTCHECK(r1.alloc((size_t)n * 3));
+    PTCHECK(r2.alloc((size_t)n * 3));
+    PTCHECK(launch_wait(k_test_reflect_refract, blocks_for(n), 0, a.p, b.p, e.p, n, r1.p, r2.p));
+    PTCHECK(download(refl3, r1, (size_t)n * 3));
+    return download(refr3, r2, (size_t)n * 3);
 }
 
 int pt_test_texture_sample(const float *rgb, int w, int h, const float *uv2, int n, float *rgb_out3) {
@@ -1223,13 +1101,11 @@ int pt_test_texture_sample(const float *rgb, int w, int h, const float *uv2, int
     for (size_t q = 0; q < tx.size(); ++q) tx[q] = make_float4(rgb[3 * q], rgb[3 * q + 1], rgb[3 * q + 2], 0.0f);
     DevBuf<float4> t;
     DevBuf<float> a, o;
-    UP(t, tx.data(), tx.size());
-    UP(a, uv2, (size_t)n * 2);
-    int rc = o.alloc((size_t)n * 3); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_texture_sample, GRID(n), t.p, w, h, a.p, n, o.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(rgb_out3, o, (size_t)n * 3);
-    return PT_OK;
+    PTCHECK(t.upload(tx));
+    PTCHECK(a.upload(uv2, (size_t)n * 2));
+    PTCHECK(o.alloc((size_t)n * 3));
+    PTCHECK(launch_wait(k_test_texture_sample, blocks_for(n), 0, t.p, w, h, a.p, n, o.p));
+    return download(rgb_out3, o, (size_t)n * 3);
 }
 
 int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, float *uv_out2) {
@@ -1241,13 +1117,11 @@ int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, fl
             if (face[i] < 0 || face[i] > 5) return fail(PT_ERR_INVALID, "pt_test_texture_uv: face %d", face[i]);
     DevBuf<float> a, o;
     DevBuf<int> f;
-    UP(a, in, (size_t)n * (kind == 2 ? 8 : 3));
-    if (kind == 1) UP(f, face, n);
-    int rc = o.alloc((size_t)n * 2); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_texture_uv, GRID(n), kind, a.p, f.p, n, o.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(uv_out2, o, (size_t)n * 2);
-    return PT_OK;
+    PTCHECK(a.upload(in, (size_t)n * (kind == 2 ? 8 : 3)));
+    if (kind == 1) PTCHECK(f.upload(face, n));
+    PTCHECK(o.alloc((size_t)n * 2));
+    PTCHECK(launch_wait(k_test_texture_uv, blocks_for(n), 0, kind, a.p, f.p, n, o.p));
+    return download(uv_out2, o, (size_t)n * 2);
 }
 
 int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, const float *in, int n, float *out) {
@@ -1267,13 +1141,11 @@ int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, 
     DevBuf<float4> t, tg;
     DevBuf<float> a, o;
     DevBuf<int> k;
-    UP(t, tx.data(), tx.size());
-    UP(tg, tan.data(), tan.size());
-    UP(a, in, (size_t)n * 40);
-    UP(k, kind, n);
-    int rc = o.alloc((size_t)n * 16); if (rc) return rc;
-    hipLaunchKernelGGL(k_test_bump_normal, GRID(n), t.p, w, h, k.p, a.p, tg.p, n, o.p);
-    HIPCHECK(hipDeviceSynchronize());
-    DOWN(out, o, (size_t)n * 16);
-    return PT_OK;
+    PTCHECK(t.upload(tx));
+    PTCHECK(tg.upload(tan));
+    PTCHECK(a.upload(in, (size_t)n * 40));
+    PTCHECK(k.upload(kind, n));
+    PTCHECK(o.alloc((size_t)n * 16));
+    PTCHECK(launch_wait(k_test_bump_normal, blocks_for(n), 0, t.p, w, h, k.p, a.p, tg.p, n, o.p));
+    return download(out, o, (size_t)n * 16);
 }

@@ -32,6 +32,19 @@ __global__ __launch_bounds__(kBlock) void k_debug_camera_rays(KParams prm, int i
     pixOut[j] = pix;
 }
 
+// ---- what the k_sweep_* kernels share: a lane's pseudo-random stream and the flush of its local counts ----
+// xorshift64 from a state that differs per lane: by default the lane's global thread index (every launch of a sweep is one-dimensional)
+struct SweepRng {
+    unsigned long long x;                  // the state: a kernel that wants raw bit patterns reads it after a step()
+    __device__ SweepRng(unsigned long long seed, unsigned long long lane) : x(seed + lane * 0x9E3779B97F4A7C15ull) {}
+    __device__ explicit SweepRng(unsigned long long seed) : SweepRng(seed, blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) {}
+    __device__ unsigned long long step() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; }
+    __device__ float next() { return (float)(step() >> 40) * (1.0f / 16777216.0f); }      // 24 bits: [0, 1)
+};
+// a lane's count into the sweep's 64-bit counter (nothing to add: no atomic)
+__device__ __forceinline__ void sweepFlush(unsigned long long *counter, unsigned int n) {
+    if (n) atomicAdd(counter, (unsigned long long)n);
+}
 
 // ---- primitive test kernels (device functions exactly as the render kernels use them) -------------------
 __global__ void k_test_pow(const float *x, const float *e, int n, float *out) {
@@ -137,17 +150,14 @@ __global__ void k_test_mesh2(const GeomDev *geom, const float4 *recs, const floa
 __global__ void k_sweep_mesh_cull(const GeomDev *geom, const float4 *recs, unsigned long long seed, int per_thread,
                                   unsigned long long *culled, unsigned long long *violations, unsigned long long *hits) {
     extern __shared__ uint32_t s_meshStack[];
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc = 0, nv = 0, nh = 0;
     const GeomDev G = *geom;
     const F3 c = f3(G.centre[0], G.centre[1], G.centre[2]);
     const float R = __builtin_sqrtf(G.cullR2);
     for (int k = 0; k < per_thread; ++k) {
         float u[8];
-        for (int j = 0; j < 8; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 8; ++j) u[j] = rng.next();
         const float dist = R * __builtin_exp2f(u[0] * 12.0f - 6.0f);             // 1/64 .. 64 bounding radii
         const F3 od = normalize(f3(u[1] - 0.5f, u[2] - 0.5f, u[3] - 0.5f));
         const F3 org = c + od * dist;
@@ -163,23 +173,20 @@ __global__ void k_sweep_mesh_cull(const GeomDev *geom, const float4 *recs, unsig
         nh += t != -1.0f ? 1u : 0u;
         nv += cull && t != -1.0f ? 1u : 0u;
     }
-    if (nc) atomicAdd(culled, (unsigned long long)nc);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
-    if (nh) atomicAdd(hits, (unsigned long long)nh);
+    sweepFlush(culled, nc);
+    sweepFlush(violations, nv);
+    sweepFlush(hits, nh);
 }
 // certainMiss soundness sweep: pseudo-random rays (origins up to ~60 units away, aimed near the primitive's bounding
 // ball so that grazing cases are dense) against every primitive of `geoms`; counts culled rays and VIOLATIONS
 // (culled although the full test returns a hit).
 __global__ void k_sweep_sphere_cull(const GeomDev *geoms, int ngeoms, unsigned long long seed, int per_thread,
                                     unsigned long long *culled, unsigned long long *violations) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc = 0, nv = 0;
     for (int k = 0; k < per_thread; ++k) {
         float u[8];
-        for (int j = 0; j < 8; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 8; ++j) u[j] = rng.next();
         const GeomDev G = geoms[(blockIdx.x + k) % ngeoms];
         const F3 c = f3(G.centre[0], G.centre[1], G.centre[2]);
         const float dist = __builtin_exp2f(u[0] * 12.0f - 6.0f);                 // 1/64 .. 64 units
@@ -198,8 +205,8 @@ __global__ void k_sweep_sphere_cull(const GeomDev *geoms, int ngeoms, unsigned l
             if (t != -1.0f) ++nv;   // (N receives the normal source here)
         }
     }
-    if (nc) atomicAdd(culled, (unsigned long long)nc);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
+    sweepFlush(culled, nc);
+    sweepFlush(violations, nv);
 }
 
 // sphereHalfLineExcess soundness sweep (the certificate of k_bounce's packed sphere sweep, with the kernel's own approximate
@@ -210,14 +217,11 @@ __global__ void k_sweep_sphere_cull(const GeomDev *geoms, int ngeoms, unsigned l
 // Counts certified misses, those certified with the centre BEHIND the origin, and VIOLATIONS (certified although the full test hits).
 __global__ void k_sweep_sphere_halfline(const GeomDev *geoms, int ngeoms, unsigned long long seed, int per_thread,
                                         unsigned long long *culled, unsigned long long *behind, unsigned long long *violations) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc = 0, nb = 0, nv = 0;
     for (int k = 0; k < per_thread; ++k) {
         float u[10];
-        for (int j = 0; j < 10; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 10; ++j) u[j] = rng.next();
         const GeomDev G = geoms[(blockIdx.x + k) % ngeoms];
         const F3 c = f3(G.centre[0], G.centre[1], G.centre[2]);
         const float R = __builtin_sqrtf(G.cullR2);
@@ -257,9 +261,9 @@ __global__ void k_sweep_sphere_halfline(const GeomDev *geoms, int ngeoms, unsign
             if (t != -1.0f) ++nv;
         }
     }
-    if (nc) atomicAdd(culled, (unsigned long long)nc);
-    if (nb) atomicAdd(behind, (unsigned long long)nb);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
+    sweepFlush(culled, nc);
+    sweepFlush(behind, nb);
+    sweepFlush(violations, nv);
 }
 
 // wallCertainMiss soundness sweep: pseudo-random rays against every cube of `geoms` and its inflated world box `walls`
@@ -268,14 +272,11 @@ __global__ void k_sweep_sphere_halfline(const GeomDev *geoms, int ngeoms, unsign
 // mixed in); counts certified misses and VIOLATIONS (certified although the full test returns a hit).
 __global__ void k_sweep_wall_box(const GeomDev *geoms, const WallBox *walls, const float *omax, int ngeoms, unsigned long long seed,
                                  int per_thread, unsigned long long *culled, unsigned long long *violations) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc = 0, nv = 0;
     for (int k = 0; k < per_thread; ++k) {
         float u[10];
-        for (int j = 0; j < 10; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 10; ++j) u[j] = rng.next();
         const int gi = (blockIdx.x + k) % ngeoms;
         const GeomDev G = geoms[gi];
         const WallBox W = walls[gi];
@@ -300,8 +301,8 @@ __global__ void k_sweep_wall_box(const GeomDev *geoms, const WallBox *walls, con
             if (boxIntersectionTest<false>(G, org, dir, P, N, o) != -1.0f) ++nv;
         }
     }
-    if (nc) atomicAdd(culled, (unsigned long long)nc);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
+    sweepFlush(culled, nc);
+    sweepFlush(violations, nv);
 }
 
 // Soundness sweep of the sphere CLUSTERS' box certificates (k_bounce: CLUSTER; pt_api.hip: build_sphere_clusters): `spheres` in table
@@ -312,14 +313,11 @@ __global__ void k_sweep_wall_box(const GeomDev *geoms, const WallBox *walls, con
 // certified as missed sends the ray through the FULL test of every sphere of that cluster: a hit is a VIOLATION (must be 0).
 __global__ void k_sweep_sphere_clusters(const GeomDev *spheres, int nspheres, int n0, const WallBox *box, float omax, F3 sceneLo, F3 sceneHi,
                                         unsigned long long seed, int per_thread, unsigned long long *certified, unsigned long long *violations) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc0 = 0, nc1 = 0, nv = 0;
     for (int k = 0; k < per_thread; ++k) {
         float u[12];
-        for (int j = 0; j < 12; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 12; ++j) u[j] = rng.next();
         const int gsel = u[10] < 0.5f ? 0 : 1;
         const WallBox W = box[gsel];
         const F3 lo = f3(W.lo[0], W.lo[1], W.lo[2]), hi = f3(W.hi[0], W.hi[1], W.hi[2]);
@@ -374,9 +372,9 @@ __global__ void k_sweep_sphere_clusters(const GeomDev *spheres, int nspheres, in
             }
         }
     }
-    if (nc0) atomicAdd(certified, (unsigned long long)nc0);
-    if (nc1) atomicAdd(certified + 1, (unsigned long long)nc1);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
+    sweepFlush(certified, nc0);
+    sweepFlush(certified + 1, nc1);
+    sweepFlush(violations, nv);
 }
 
 // Soundness sweep of the sphere GROUPS' bounding balls (k_bounce<..., GROUPS>; pt_host_scene.h: build_sphere_groups): `spheres` in table order,
@@ -386,14 +384,11 @@ __global__ void k_sweep_sphere_clusters(const GeomDev *spheres, int nspheres, in
 // and non-unit lengths.  A group certified as missed sends the ray through the FULL test of each of its members: a hit is a VIOLATION (0).
 __global__ void k_sweep_sphere_groups(const GeomDev *spheres, int nspheres, const SphereCull *groups, int ngroups, float sdir, float omax, F3 sceneLo,
                                       F3 sceneHi, unsigned long long seed, int per_thread, unsigned long long *certified, unsigned long long *violations) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc = 0, nv = 0;
     for (int k = 0; k < per_thread; ++k) {
         float u[12];
-        for (int j = 0; j < 12; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 12; ++j) u[j] = rng.next();
         const SphereCull Gs = groups[(int)(u[10] * (float)ngroups) % ngroups];
         const F3 c = f3(Gs.centre[0], Gs.centre[1], Gs.centre[2]);
         const float R = __builtin_sqrtf(Gs.cullR2) / sdir;
@@ -442,8 +437,8 @@ __global__ void k_sweep_sphere_groups(const GeomDev *spheres, int nspheres, cons
             }
         }
     }
-    if (nc) atomicAdd(certified, (unsigned long long)nc);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
+    sweepFlush(certified, nc);
+    sweepFlush(violations, nv);
 }
 
 // Soundness sweep of the camera-ray culling (GeomDev::rect, KParams::sceneRect, the per-row lists with their hull spans): every
@@ -477,9 +472,9 @@ __global__ void k_sweep_camera_cull(KParams prm, const GeomDev *geoms, const int
             nv += (!reach && t > 0.0f) ? 1u : 0u;
         }
     }
-    if (nh) atomicAdd(hits, (unsigned long long)nh);
-    if (nc) atomicAdd(culled, (unsigned long long)nc);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
+    sweepFlush(hits, nh);
+    sweepFlush(culled, nc);
+    sweepFlush(violations, nv);
 }
 
 // How much of the culling tables' object-space inflation (pt_api.hip: inflated_object_box) do the reference's hits actually NEED?  For
@@ -555,7 +550,7 @@ __global__ void k_sweep_camera_cull_margin(KParams prm, const GeomDev *geoms, co
             worst = s > worst ? s : worst;
         }
     }
-    if (nn) atomicAdd(needed, (unsigned long long)nn);
+    sweepFlush(needed, nn);
     if (worst > 0.0) atomicMax(worstBits, (unsigned long long)__double_as_longlong(worst));
 }
 
@@ -566,17 +561,14 @@ __global__ void k_sweep_camera_cull_margin(KParams prm, const GeomDev *geoms, co
 // test hits is a VIOLATION.  `certified` counts (ray, wall) certificates, `single` the rays left with exactly one possible wall.
 __global__ void k_sweep_wall_planes(KParams prm, const GeomDev *wallGeoms, const WallBox *walls, unsigned long long seed, int per_thread,
                                     unsigned long long *certified, unsigned long long *violations, unsigned long long *single) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nc = 0, nv = 0, ns = 0;
     const int nPlane = prm.nSlotWalls + prm.nPlaneWalls;      // (walls certified by an axis slot's plane, then by the plane of a rotated cube's inner face)
     const F3 olo = f3(prm.outerLo[0], prm.outerLo[1], prm.outerLo[2]), ohi = f3(prm.outerHi[0], prm.outerHi[1], prm.outerHi[2]);
     const F3 oc = (olo + ohi) * 0.5f, oh = (ohi - olo) * 0.5f;
     for (int k = 0; k < per_thread; ++k) {
         float u[12];
-        for (int j = 0; j < 12; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 12; ++j) u[j] = rng.next();
         const int wi = (int)(u[0] * (float)prm.nWalls) % prm.nWalls;
         const WallBox W = walls[wi];
         const F3 wlo = f3(W.lo[0], W.lo[1], W.lo[2]), whi = f3(W.hi[0], W.hi[1], W.hi[2]);
@@ -644,9 +636,9 @@ __global__ void k_sweep_wall_planes(KParams prm, const GeomDev *wallGeoms, const
             }
         ns += __popc(possible) == 1 ? 1u : 0u;
     }
-    if (nc) atomicAdd(certified, (unsigned long long)nc);
-    if (nv) atomicAdd(violations, (unsigned long long)nv);
-    if (ns) atomicAdd(single, (unsigned long long)ns);
+    sweepFlush(certified, nc);
+    sweepFlush(violations, nv);
+    sweepFlush(single, ns);
 }
 
 // boxIntersectionTest with the fast slab phase (boxSlabsFast, falling back on the reference's loop) next to the test with the
@@ -655,14 +647,11 @@ __global__ void k_sweep_wall_planes(KParams prm, const GeomDev *wallGeoms, const
 // infinite and NaN components, axis-parallel ones.  cnt[0] = rays, [1] = rays the fast path decided, [2] = hits among those,
 // [3] = bit mismatches (t, and on a hit P, nsrc, outside; NaN == NaN) -- must be 0.
 __global__ void k_sweep_box_fast(const GeomDev *geoms, int ngeoms, unsigned long long seed, int per_thread, unsigned long long *cnt, float *dump) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int nr = 0, nf = 0, nh = 0, bad = 0;
     for (int k = 0; k < per_thread; ++k) {
         float u[16];
-        for (int j = 0; j < 16; ++j) {
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            u[j] = (float)(x >> 40) * (1.0f / 16777216.0f);
-        }
+        for (int j = 0; j < 16; ++j) u[j] = rng.next();
         const GeomDev &G = geoms[(int)(u[0] * (float)ngeoms) % ngeoms];
         // a point of the cube in object space: anywhere in it, on a face, on an edge, at a corner (coordinates snapped to +-.5)
         auto snap = [](float v, float w) { return w < 0.5f ? v - 0.5f : (w < 0.75f ? -0.5f : 0.5f); };
@@ -692,7 +681,7 @@ __global__ void k_sweep_box_fast(const GeomDev *geoms, int ngeoms, unsigned long
         else if (dk == 9) dir = f3(dir.x, dir.y * 1e-13f, dir.z * (u[14] < 0.5f ? 1e-20f : 1.0f));
         dir = normalize(dir);
         if (dk == 10) {                                  // raw bit patterns now and then: NaN, inf, denormals, huge
-            const uint32_t b = (uint32_t)x;
+            const uint32_t b = (uint32_t)rng.x;
             if (u[14] < 0.3f) dir.x = __uint_as_float(b); else if (u[14] < 0.6f) org.y = __uint_as_float(b); else dir = dir * __uint_as_float(b & 0x7fffffffu);
         }
         F3 P1 = f3(1, 2, 3), N1 = f3(4, 5, 6), P2 = P1, N2 = N1;
@@ -728,10 +717,10 @@ __global__ void k_sweep_box_fast(const GeomDev *geoms, int ngeoms, unsigned long
             if (boxSlabsFastDecide(qo, qdu, qd, hit, outs, axis)) { ++nf; nh += hit ? 1u : 0u; }
         }
     }
-    atomicAdd(&cnt[0], (unsigned long long)nr);
-    if (nf) atomicAdd(&cnt[1], (unsigned long long)nf);
-    if (nh) atomicAdd(&cnt[2], (unsigned long long)nh);
-    if (bad) atomicAdd(&cnt[3], (unsigned long long)bad);
+    sweepFlush(&cnt[0], nr);
+    sweepFlush(&cnt[1], nf);
+    sweepFlush(&cnt[2], nh);
+    sweepFlush(&cnt[3], bad);
 }
 // boxFaceHit (the box test of a camera ray whose pixel pt_init resolved to a cube face) next to boxIntersectionTest on the camera rays of
 // resolved pixels: entry e = {pixel x | y << 16, primitive, face}, `samples` seeded jitters per entry and then the four corners of the
@@ -747,11 +736,10 @@ __global__ void k_sweep_face_hit(const GeomDev *geoms, const float *cam16, const
         const GeomDev &G = geoms[entries[3 * e + 1]];
         float jx, jy;
         if (k < samples) {
-            unsigned long long x = seed + (unsigned long long)(i + 1) * 0x9E3779B97F4A7C15ull;
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-            jx = (float)(x >> 40) * (1.0f / 16777216.0f);
-            jy = (float)((x >> 16) & 0xffffffu) * (1.0f / 16777216.0f);
+            SweepRng rng(seed, (unsigned long long)(i + 1));      // (a stream per ray, not per lane: the grid is capped)
+            rng.step();
+            jx = rng.next();
+            jy = (float)((rng.x >> 16) & 0xffffffu) * (1.0f / 16777216.0f);
         } else {
             jx = ((k - samples) & 1) ? 3.0f : -2.0f;
             jy = ((k - samples) & 2) ? 3.0f : -2.0f;
@@ -773,8 +761,8 @@ __global__ void k_sweep_face_hit(const GeomDev *geoms, const float *cam16, const
         bad += eq ? 0u : 1u;
         ++nr;
     }
-    if (nr) atomicAdd(&cnt[0], (unsigned long long)nr);
-    if (bad) atomicAdd(&cnt[1], (unsigned long long)bad);
+    sweepFlush(&cnt[0], nr);
+    sweepFlush(&cnt[1], bad);
 }
 // divUnscaled(1, s) = 1.0f / s on EVERY float of [2^-40, 2^40] (the fast normalize's reciprocal), and divUnscaled(a, d) = a / d on
 // pseudo-random pairs of the box test's range (|a| <= 2^20 + 1, 2^-40 <= |d| <= 2): bad[0] / bad[1] count bit mismatches
@@ -786,9 +774,9 @@ __global__ void k_sweep_div_unscaled(unsigned long long seed, int per_thread, un
         const float q = divUnscaled(1.0f, s, __builtin_amdgcn_rcpf(s)), r = 1.0f / s;
         b0 += __float_as_uint(q) == __float_as_uint(r) ? 0u : 1u;
     }
-    unsigned long long x = seed + tid * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     for (int k = 0; k < per_thread; ++k) {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+        const unsigned long long x = rng.step();
         const uint32_t ab = (uint32_t)x, db = (uint32_t)(x >> 32);
         // a: sign, exponent 2^-25 .. 2^20, any mantissa (or exactly 0); d: sign, exponent 2^-40 .. 2^0, any mantissa
         float a = __uint_as_float((ab & 0x807fffffu) | ((uint32_t)(127 - 25 + (ab >> 23 & 63) % 46) << 23));
@@ -797,8 +785,8 @@ __global__ void k_sweep_div_unscaled(unsigned long long seed, int per_thread, un
         const float q = divUnscaled(a, d, __builtin_amdgcn_rcpf(d)), r = a / d;
         b1 += __float_as_uint(q) == __float_as_uint(r) ? 0u : 1u;
     }
-    if (b0) atomicAdd(&bad[0], (unsigned long long)b0);
-    if (b1) atomicAdd(&bad[1], (unsigned long long)b1);
+    sweepFlush(&bad[0], b0);
+    sweepFlush(&bad[1], b1);
 }
 // slabQuotients vs the compiler's correctly rounded division; counts mismatching lanes
 __global__ void k_test_slab_quotients(const float *o, const float *d, int n, float *t1, float *t2, float *r1, float *r2) {
@@ -810,10 +798,10 @@ __global__ void k_test_slab_quotients(const float *o, const float *d, int n, flo
 }
 // pseudo-random sweep entirely on the device: returns the number of bit mismatches (NaN == NaN)
 __global__ void k_sweep_slab_quotients(unsigned long long seed, int per_thread, unsigned long long *mismatches) {
-    unsigned long long x = seed + (blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x) * 0x9E3779B97F4A7C15ull;
+    SweepRng rng(seed);
     unsigned int bad = 0;
     for (int k = 0; k < per_thread; ++k) {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;                     // xorshift64
+        const unsigned long long x = rng.step();
         const uint32_t ob = (uint32_t)x, db = (uint32_t)(x >> 32);
         float o, d;
         if ((k & 3) == 0) {            // raw bit patterns: every exponent, denormals, inf, NaN
@@ -830,7 +818,7 @@ __global__ void k_sweep_slab_quotients(unsigned long long seed, int per_thread, 
         const bool e2 = __float_as_uint(t2) == __float_as_uint(r2) || (t2 != t2 && r2 != r2);
         bad += (e1 ? 0u : 1u) + (e2 ? 0u : 1u);
     }
-    if (bad) atomicAdd(mismatches, (unsigned long long)bad);
+    sweepFlush(mismatches, bad);
 }
 // sqrtUnscaled next to the compiler's correctly rounded sqrt on EVERY fp32 bit pattern of its range, and
 // inverseSqrtNearOne next to 1.0f / sqrtf on every bit pattern at all (thread t checks patterns t, t + stride, ...):
@@ -850,10 +838,10 @@ __global__ void k_sweep_unscaled_sqrt(unsigned long long *bad) {
         b0 += (__float_as_uint(a) == __float_as_uint(r) || (a != a && r != r)) ? 0u : 1u;
         ++n;
     }
-    if (b0) atomicAdd(&bad[0], (unsigned long long)b0);
-    atomicAdd(&bad[1], (unsigned long long)n);
-    if (b2) atomicAdd(&bad[2], (unsigned long long)b2);
-    if (n3) atomicAdd(&bad[3], (unsigned long long)n3);
+    sweepFlush(&bad[0], b0);
+    sweepFlush(&bad[1], n);
+    sweepFlush(&bad[2], b2);
+    sweepFlush(&bad[3], n3);
 }
 __global__ void k_test_hemisphere(const float *nrm, const int *iid, int n, float *out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
