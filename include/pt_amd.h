@@ -104,6 +104,11 @@ enum {
                                     pt_noise_stats, pt_iterate_until, pt_readback* and pt_denoise are the unflagged renderer's bit for bit, and so is
                                     pt_denoise_var while the context holds no history.  PT_ERR_INVALID without PT_FLAG_MOMENTS, with
                                     PT_FLAG_TRACE_AHEAD, and with lens_radius > 0 (a thin lens has no single projection). */
+    PT_FLAG_DISPLAY_FILTER = 128,/* the display filter (section "display filter" below): every call that writes sendImageToPBO's bytes of the
+                                    accumulator -- pt_iterate / pt_iterate_batch with rgba8_dev != NULL, pt_readback_rgba8 -- writes the bytes
+                                    pt_denoise_var_rgba8 with the PT_DISPLAY_* setting would return at that point of the stream, on the device and
+                                    without a synchronisation.  Everything else is the unflagged renderer's bit for bit.  PT_ERR_INVALID without
+                                    PT_FLAG_MOMENTS, and for a scene whose guide buffers cannot be made. */
     PT_FLAG_DIRECT_LIGHTING = 4 /* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
@@ -260,7 +265,8 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
 /* pathtrace(pbo, frame, iter): one iteration (1 spp), iter is 1-based like src/main.cpp:97-103.
  * Enqueues camera-ray generation, traceDepth fused intersect+shade+compact launches and, when
  * rgba8_dev != NULL, the sendImageToPBO conversion (src/pathtrace.cu:48-68) into that DEVICE
- * buffer of W*H uchar4.  Asynchronous on the configured stream.  Replaces src/pathtrace.cu:123-167. */
+ * buffer of W*H uchar4 -- under PT_FLAG_DISPLAY_FILTER the variance-guided filter's bytes instead of the raw accumulator's (section
+ * "display filter" below).  Asynchronous on the configured stream.  Replaces src/pathtrace.cu:123-167. */
 int pt_iterate(int frame, int iter, void *rgba8_dev /* may be NULL (headless) */);
 
 /* `count` consecutive iterations first_iter .. first_iter+count-1 traced as ONE wavefront (their paths share the
@@ -285,7 +291,7 @@ int pt_readback(float *rgb_sum_host);
 int pt_pin_host(void *host, size_t bytes);
 int pt_unpin_host(void);
 
-/* sendImageToPBO into a HOST buffer (W*H*4 bytes). Synchronises. */
+/* sendImageToPBO into a HOST buffer (W*H*4 bytes). Synchronises.  (Under PT_FLAG_DISPLAY_FILTER: the display filter's bytes, as pt_iterate's.) */
 int pt_readback_rgba8(int iter, uint8_t *rgba_host);
 
 /* ---- denoiser: an edge-avoiding a-trous wavelet filter over the image, guided by first-hit position and normal (Dammertz et al., HPG 2010;
@@ -399,6 +405,30 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
 #define PT_TEMPORAL_NORMAL_DOT 0.9f
 #define PT_TEMPORAL_PLANE_FRACTION 0.01f
 #define PT_TEMPORAL_MIN_WEIGHT 0.5f
+
+/* ---- display filter (PT_FLAG_DISPLAY_FILTER, with PT_FLAG_MOMENTS): the variance-guided filter where the display reads it.  No function of its
+ * own: a flag, and what the calls that write sendImageToPBO's bytes of the accumulator do under it.
+ *   pt_iterate / pt_iterate_batch with rgba8_dev != NULL write into rgba8_dev, and pt_readback_rgba8 returns, the bytes
+ *   pt_denoise_var_rgba8(n, &{PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA_NORMAL, PT_DISPLAY_SIGMA_POSITION},
+ *   ...) would return at that point of the stream: n is the count those calls divide by today (first_iter + count - 1, resp. iter), and where
+ *   the context holds history (PT_FLAG_TEMPORAL) the bytes include the blend with it.  With n == 1 -- a variance needs two samples -- the bytes
+ *   are the unfiltered conversion, as without the flag.
+ *   pt_iterate_batch enqueues the filter on the renderer's stream behind the commit: the guide buffers (once per renderer, while no pt_denoise*
+ *   or pt_gbuffer call asks for another guide_iter), the blend with the history where there is one, the levels, the last of which writes the
+ *   bytes itself.  No host synchronisation, no allocation: pt_init allocates the filter's buffers (guide buffers, two float4 images, one image of
+ *   bytes: 68 bytes per pixel) and counts them in its memory check.  pt_denoise_var* calls with other parameters share those buffers on the
+ *   same stream; each call's result is its own.
+ *   Both accumulators, pt_readback, pt_readback_moments, pt_variance, pt_noise_stats, pt_iterate_until, pt_denoise*, pt_gbuffer and the capture of
+ *   history are the unflagged renderer's bit for bit.
+ *   pt_init answers PT_ERR_INVALID, before anything is touched, to the flag without PT_FLAG_MOMENTS (so: with row shards, and from
+ *   pt_group_init) and for a scene whose guide buffers cannot be made (pt_gbuffer's PT_ERR_INVALID: a mesh hierarchy too deep for its stacks).
+ *   PT_FLAG_TRACE_AHEAD, a thin lens and direct lighting go with it.
+ * The setting -- the calls have no room for parameters -- is pt_denoise_var's default, the one that serves every sample count: */
+#define PT_DISPLAY_LEVELS 5
+#define PT_DISPLAY_GUIDE_ITER 1
+#define PT_DISPLAY_SIGMA_LUM 4.0f
+#define PT_DISPLAY_SIGMA_NORMAL 0.35f
+#define PT_DISPLAY_SIGMA_POSITION 2.0f
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

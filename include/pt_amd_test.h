@@ -172,6 +172,13 @@ int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_
 /* ... and pt_denoise_var with the form of k_atrous_var named, the same four forms; var_host may be NULL; ms as above (on a renderer whose context
  * holds history -- PT_FLAG_TEMPORAL -- k_temporal runs between k_gbuffer and level 0 and belongs to neither time). */
 int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms);
+/* the display path (PT_FLAG_DISPLAY_FILTER, pt_amd.h) of THIS library's renderer -- any PT_FLAG_MOMENTS renderer, the flag itself is not needed
+ * -- with the form of k_atrous_var named for every level, the last included: what pt_iterate(..., rgba8_dev) enqueues behind the commit, into
+ * rgba8_dev (DEVICE memory, W * H * 4 bytes), on the renderer's stream, without a synchronisation unless ms is given.  form: the four of
+ * pt_test_denoise.  fused 1: the last level writes the bytes itself (k_atrous_var_*<false, true, ., true>); 0: it writes packed RGB and
+ * k_to_rgba8 converts it -- the same bytes.  samples 1: the plain conversion.  ms (or NULL): 1 + PT_DISPLAY_LEVELS kernel times as
+ * pt_test_denoise_var's, the last level's with the k_to_rgba8 launch where fused is 0 (all 0 for samples 1). */
+int pt_test_display(int samples, int form, int fused, void *rgba8_dev, float *ms);
 int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
 /* temporal reprojection (pt_amd.h, csrc/pt_temporal.h).  cam16 = the old view's camera as k_temporal takes it, 16 floats: eye (3), pixLenX,
  * pixLenY, halfW, halfH, then the rows r0, r1, r2 of the inverse of [view | -right | -up].

@@ -50,6 +50,9 @@ PT_FLAG_TEMPORAL = 64
 # the constants of temporal reprojection (include/pt_amd.h): the cap on a pixel's effective history, the least dot of the two normals, the
 # largest distance from the new hit's tangent plane as a fraction of the hit's distance, the least sum of bilinear weights
 PT_TEMPORAL_MAX_HISTORY, PT_TEMPORAL_NORMAL_DOT, PT_TEMPORAL_PLANE_FRACTION, PT_TEMPORAL_MIN_WEIGHT = 32.0, 0.9, 0.01, 0.5
+PT_FLAG_DISPLAY_FILTER = 128
+# the display filter's one setting (include/pt_amd.h): denoise_var's defaults
+PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA_NORMAL, PT_DISPLAY_SIGMA_POSITION = 5, 1, 4.0, 0.35, 2.0
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -80,6 +83,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
+    "pt_test_display",
 ]
 
 
@@ -248,6 +252,7 @@ def _bind(L, with_tests):
         L.pt_test_temporal_camera.argtypes = [vp, vp]
         L.pt_test_temporal.argtypes = [i32, i32, i32, i32] + [vp] * 11 + [i32, vp]
         L.pt_test_history.argtypes = [vp] * 6
+        L.pt_test_display.argtypes = [i32, i32, i32, vp, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
@@ -434,8 +439,11 @@ _scene = None
 
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
-                  mixture_weighted=False, moments=False, temporal=False):
+                  mixture_weighted=False, moments=False, temporal=False, display_filter=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    display_filter: PT_FLAG_DISPLAY_FILTER (moments=True must be given with it: it implies nothing) -- the `pbo` of pathtrace / pathtrace_batch
+    and readback_rgba8 receive the bytes of denoise_var_rgba8 with its defaults (PT_DISPLAY_*) instead of the raw accumulator's, made on the
+    device behind the commit, on the renderer's stream, without a synchronisation.  Everything else is the unflagged renderer's.
     temporal: PT_FLAG_TEMPORAL (with moments=True, no lens, no trace_ahead) -- calling pathtraceInit AGAIN, WITHOUT pathtraceFree() in between,
     with a moved camera is what carries the last view's samples over as history: denoise_var / denoise_var_rgba8 of the new renderer then filter
     the blend of the reprojected history with the new samples.  pathtraceFree() drops the history (call it when the scene itself changes).
@@ -454,6 +462,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_MOMENTS
     if temporal:
         flags |= PT_FLAG_TEMPORAL
+    if display_filter:
+        flags |= PT_FLAG_DISPLAY_FILTER
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -587,7 +597,10 @@ def set_textures(textures, geom_textures=None, mesh_uvs=None, L=None):
 
 def pathtrace(pbo, frame, iteration, readback=True):
     """reference src/pathtrace.cu:123-174: one iteration; `pbo` is a DEVICE pointer (int) or None.
-    With readback=True the running sum lands in scene.image like the reference's D2H copy (:170-171)."""
+    With readback=True the running sum lands in scene.image like the reference's D2H copy (:170-171).
+    `pbo` receives sendImageToPBO's bytes of the accumulator over `iteration` samples -- under display_filter=True the bytes
+    denoise_var_rgba8(iteration) would return at that point of the stream (the blend with the context's history included; iteration 1: the
+    unfiltered bytes), written on the device behind the commit.  They are valid once the renderer's stream has passed them."""
     _check(lib().pt_iterate(frame, iteration, pbo or None))
     if readback and _scene is not None:
         _check(lib().pt_readback(_p(_scene.image)))
@@ -595,6 +608,8 @@ def pathtrace(pbo, frame, iteration, readback=True):
 
 def pathtrace_batch(pbo, frame, first_iteration, count, readback=False, until=None):
     """`count` iterations in one wavefront (pt_iterate_batch); same result as `count` pathtrace() calls.
+    `pbo` (a device pointer or None) receives the bytes of the accumulator over first_iteration + count - 1 samples; under display_filter=True
+    those of denoise_var_rgba8(first_iteration + count - 1), as pathtrace's.
     until: a noise threshold, or a dict of iterate_until()'s keywords with one -- then AT MOST `count` iterations (any number, in batches of
     max_batch) are rendered, until the frame's tiles pass (pt_iterate_until; no `pbo`), and (statistics, samples_done) is returned."""
     if until is not None:
@@ -640,6 +655,8 @@ def readback(npixels):
 
 
 def readback_rgba8(iteration, npixels):
+    """sendImageToPBO's bytes of the accumulator over `iteration` samples (pt_readback_rgba8): (npixels, 4).  Under display_filter=True the
+    bytes denoise_var_rgba8(iteration) returns -- what a `pbo` given to pathtrace would hold; iteration 1: the unfiltered bytes."""
     out = np.empty((npixels, 4), np.uint8)
     _check(lib().pt_readback_rgba8(iteration, _p(out)))
     return out
@@ -749,6 +766,16 @@ def test_denoise_var(samples, form, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma
     prm = PtDenoiseVarParams(levels, guide_iter, sigma_lum, sigma_normal, sigma_position)
     _tcheck(test_lib().pt_test_denoise_var(samples, C.byref(prm), C.sizeof(prm), form, _p(out), _p(var), _p(ms) if timing else None))
     return (out, var, ms) if timing else (out, var)
+
+
+def test_display(samples, form, pbo, fused=True, timing=False):
+    """pt_test_display (test library, inside renderer_from_test_library): the display path of a moments=True renderer into the DEVICE pointer
+    `pbo`, every level -- the last included -- in the form named (0 the product's choice, 1 the gather, 2 / 3 the tiles); fused=False: the
+    last level writes packed RGB and k_to_rgba8 converts it.  On the renderer's stream, not synchronised -- unless timing=True: then the
+    1 + PT_DISPLAY_LEVELS kernel times in ms are returned (k_gbuffer first; the last level's with k_to_rgba8 where fused=False)."""
+    ms = np.zeros(1 + PT_DISPLAY_LEVELS, np.float32)
+    _tcheck(test_lib().pt_test_display(samples, form, 1 if fused else 0, pbo, _p(ms) if timing else None))
+    return ms if timing else None
 
 
 # the luminance a tile's mean is floored with before the noise statistics divide by it: 5 % of a white diffuse surface's

@@ -205,10 +205,11 @@ struct State : PlanScalars {
     DevBuf<ptd::BumpGeom> dBumpGeom;
     DevBuf<float4> dBumpUV, dBumpTan;
     // the denoiser (pt_denoise.h), all allocated on first use: the guide buffers of iteration dnGuideIter (0: none yet), the float4 images
-    // the filter's levels pass on, and the packed RGB the last level writes
+    // the filter's levels pass on, and the packed RGB the last level writes.  (PT_FLAG_DISPLAY_FILTER: pt_init allocates the four float4
+    // images and dnRgba -- what the display path touches -- so that pt_iterate allocates nothing.)
     DevBuf<float4> dnPosT, dnNrmId, dnPing[2];
     DevBuf<float> dnOut;
-    DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes
+    DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes, and pt_readback_rgba8's under PT_FLAG_DISPLAY_FILTER
     DevBuf<float> dnVar;            // pt_variance's / pt_denoise_var's variance image
     int dnGuideIter = 0;
     // the noise statistics (pt_noise.h), all allocated on first use: the frame's two result words on the device, the tile map, and -- for
@@ -702,7 +703,7 @@ int denoise_refusals(const char *who) {
 }
 
 // dynamic LDS k_gbuffer needs for the renderer's scene: the lanes' mesh traversal stacks (a launch holds at most 64 KB)
-size_t guide_stack_bytes() { return R().mesh ? (size_t)std::max(R().meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0; }
+size_t guide_stack_bytes() { return guideStackBytes(R().mesh, R().meshStackNeed); }
 
 // the guide buffers of iteration `guideIter`, on the caller's stream (cached until pt_init / pt_free); ms: the kernel's time, 0 when cached
 int ensure_guides(int guideIter, float *ms) {
@@ -867,16 +868,24 @@ int moments_refusals(const char *who) {
     return PT_OK;
 }
 
-template <bool F, bool L>
+template <bool F, bool L, bool BYTES = false>
 const void *atrous_var_kernel(int form) {
-    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_var_gather<F, L>);
-    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 1>);
-    return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 2>);
+    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_var_gather<F, L, BYTES>);
+    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 1, BYTES>);
+    return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 2, BYTES>);
 }
+
+// PT_FLAG_DISPLAY_FILTER: the one setting of the display path (include/pt_amd.h)
+const PtDenoiseVarParams kDisplayParams = {PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA_NORMAL, PT_DISPLAY_SIGMA_POSITION};
 
 // The variance-guided filter's levels on the caller's stream, as denoise_run: packed RGB in R().dnOut, the filtered variance in R().dnVar when
 // `wantVar`; ms (or NULL): 1 + levels kernel times, k_gbuffer first.
-int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, bool wantVar, float *ms, const char *who) {
+// bytesOut (the display path; not with wantVar): sendImageToPBO's bytes of the filtered mean go there instead -- device memory of P uchar4 --
+// written by the last level itself (`fused`, the product's way: k_atrous_var_*<false, true, ., true>, measured faster than the pair in
+// profiles/display_cost.txt; R().dnOut is not touched then), or by k_to_rgba8 of R().dnOut behind it -- the test build's reference -- which
+// belongs to the last level's time in `ms`.  A last level that is also the first (levels 1, no history) has no fused form and takes the two launches.
+int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, bool wantVar, float *ms, const char *who,
+                    uchar4 *bytesOut = nullptr, bool fused = true) {
     PTCHECK(moments_refusals(who));
     if (!p || bytes != sizeof(PtDenoiseVarParams))
         return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseVarParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseVarParams));
@@ -887,14 +896,15 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     if (form < kAtrousAuto || form > kAtrousTiled8) return fail(PT_ERR_INVALID, "%s: unknown kernel form %d", who, form);
     PTCHECK(ensure_guides(p->guide_iter, ms));
     const size_t P = (size_t)R().P;
-    if (!R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
-    if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc(P));
-    for (int k = 0; k < 2 && k < p->levels - 1; ++k)
-        if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
     // PT_FLAG_TEMPORAL with history: level 0 reads the blend of the reprojected history with the accumulators (k_temporal, into the ping-pong
     // half the level before level 0 would have written) and so runs as a later level at step 1
     const History &hist = R().hist;
     const bool temporal = (R().flags & PT_FLAG_TEMPORAL) && hist.live && hist.W == R().prm.W && hist.H == R().prm.H;
+    const bool bytesFused = bytesOut && fused && (p->levels > 1 || temporal);
+    if (!bytesFused && !R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
+    if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc(P));
+    for (int k = 0; k < 2 && k < p->levels - 1; ++k)
+        if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
     if (temporal) {
         if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc(P));
         TemporalArgs T;
@@ -926,6 +936,7 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
         A.cin = first ? nullptr : R().dnPing[(i + 1) & 1].p;
         A.cout = last ? nullptr : R().dnPing[i & 1].p;
         A.out3 = last ? R().dnOut.p : nullptr;
+        if (last && bytesFused) A.out8 = bytesOut;
         A.outVar = last && wantVar ? R().dnVar.p : nullptr;
         // the form per level: 64 x 8 tiles up to the largest step they were measured to win clearly at (profiles/denoise_var_cost.txt), the gather above
         int f = form != kAtrousAuto ? form : (A.step <= kAtrousVarTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
@@ -935,10 +946,15 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
             grid = atrousGridGather(A.W, A.H);
         }
         const void *kern = first ? (last ? atrous_var_kernel<true, true>(f) : atrous_var_kernel<true, false>(f))
-                                 : (last ? atrous_var_kernel<false, true>(f) : atrous_var_kernel<false, false>(f));
+                                 : (last ? (bytesFused ? atrous_var_kernel<false, true, true>(f) : atrous_var_kernel<false, true>(f))
+                                         : atrous_var_kernel<false, false>(f));
         void *kargs[] = {&A};
         if (ms) HIPCHECK(hipEventRecord(ev[i], R().stream));
         HIPCHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
+    }
+    if (bytesOut && !bytesFused) {
+        // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
+        hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut.p, R().P, 1, bytesOut);
     }
     if (ms) {
         HIPCHECK(hipEventRecord(ev[p->levels], R().stream));
@@ -947,6 +963,18 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     }
     HIPCHECK(hipGetLastError());
     return PT_OK;
+}
+
+// PT_FLAG_DISPLAY_FILTER: the bytes of `samples` committed iterations as the display sees them, into device memory, on the renderer's stream
+// behind everything enqueued: pt_denoise_var_rgba8's with the shipped setting, or -- one sample has no variance -- the plain conversion.
+// pt_init allocated every buffer this touches; nothing here waits for the device.
+int display_bytes(int samples, uchar4 *out, const char *who, int form = kAtrousAuto, bool fused = true, float *ms = nullptr) {
+    if (samples < 2) {
+        hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().image, R().P, samples, out);
+        HIPCHECK(hipGetLastError());
+        return PT_OK;
+    }
+    return denoise_var_run(samples, &kDisplayParams, sizeof kDisplayParams, form, false, ms, who, out, fused);
 }
 
 int denoise_var_to_host(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, float *ms, float *rgb_mean_host, float *var_host, const char *who) {
@@ -1210,12 +1238,20 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     {   // the memory budget BEFORE the first large allocation: a batch that does not fit fails here, with nothing to undo
         const size_t perSlot = 2 * (S.poolCap * kNumArrays * sizeof(float) + (size_t)kSeg * S.poolChunks * sizeof(unsigned long long)) + sizeof(Ctrl) +
                                contribFloats * sizeof(float) + maskWords * sizeof(uint32_t) + S.meshHitWords * sizeof(unsigned long long);
-        const size_t need = perSlot * (size_t)S.nslots;
+        // ... and PT_FLAG_DISPLAY_FILTER's buffers: the guide buffers, the two float4 images of the levels, the bytes pt_readback_rgba8 copies
+        const size_t display = (S.flags & PT_FLAG_DISPLAY_FILTER) ? (size_t)S.P * (4 * sizeof(float4) + sizeof(uchar4)) : 0;
+        const size_t need = perSlot * (size_t)S.nslots + display;
         size_t freeB = 0, totalB = 0;
         HIPCHECK(hipMemGetInfo(&freeB, &totalB));
         if (need > freeB)
             return fail(PT_ERR_HIP, "pt_init: %.2f GB of path pools and radiance buffers (max_batch %d x pipeline_depth %d) exceed the %.2f GB of free "
                         "device memory: lower max_batch or pipeline_depth", need / 1e9, S.maxBatch, S.nslots, freeB / 1e9);
+    }
+    if (S.flags & PT_FLAG_DISPLAY_FILTER) {      // (pt_iterate under the flag allocates nothing)
+        PTCHECK(S.dnPosT.alloc((size_t)S.P));
+        PTCHECK(S.dnNrmId.alloc((size_t)S.P));
+        for (auto &ping : S.dnPing) PTCHECK(ping.alloc((size_t)S.P));
+        PTCHECK(S.dnRgba.alloc((size_t)S.P));
     }
     for (int i = 0; i < S.nslots; ++i) {
         Slot &sl = S.slot[i];
@@ -1368,7 +1404,10 @@ int pt_iterate_batch(int frame, int first_iter, int count, void *rgba8_dev) {
         HIPCHECK(hipEventRecord(sl.evCommitted, R().stream));
         R().seq += 1;
     }
-    if (rgba8_dev) {
+    if (rgba8_dev && (R().flags & PT_FLAG_DISPLAY_FILTER)) {
+        // the display filter: the guide buffers (once), the blend with the history, the levels, the bytes -- all behind the commit
+        PTCHECK(display_bytes(first_iter + count - 1, reinterpret_cast<uchar4 *>(rgba8_dev), "pt_iterate"));
+    } else if (rgba8_dev) {
         hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().image, R().P,
                            first_iter + count - 1, reinterpret_cast<uchar4 *>(rgba8_dev));
         HIPCHECK(hipGetLastError());
@@ -1440,6 +1479,12 @@ int pt_readback_rgba8(int iter, uint8_t *rgba_host) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_readback_rgba8 before pt_init");
     if (!rgba_host || iter < 1) return fail(PT_ERR_INVALID, "pt_readback_rgba8: bad argument");
     if (R().flags & PT_FLAG_ACCUM_SHARD_ROWS) return fail(PT_ERR_INVALID, "pt_readback_rgba8: accumulator is row-sharded");
+    if (R().flags & PT_FLAG_DISPLAY_FILTER) {
+        PTCHECK(display_bytes(iter, R().dnRgba.p, "pt_readback_rgba8"));
+        HIPCHECK(hipMemcpyAsync(rgba_host, R().dnRgba.p, (size_t)R().P * 4, hipMemcpyDeviceToHost, R().stream));
+        HIPCHECK(hipStreamSynchronize(R().stream));
+        return readback_fault();
+    }
     DevBuf<uchar4> tmp;
     int rc = tmp.alloc(R().P);
     if (rc) return rc;

@@ -245,12 +245,19 @@ __global__ __launch_bounds__(kBlock) void k_atrous_tiled(AtrousArgs A) {
 //   taps        dl = lum(c_q) - lum(c_p);  a = (dl * dl) * invL;  a = a + dot(dn, dn) * invN;  a = a + dot(dp, dp) * invP;  w = hw * expNegPoly(a);
 //               the centre tap has w = hw
 //   sums        sumW += w;  sumC.k += c_q.k * w;  sumV += v_q * (w * w);   c' = sumC / sumW;  v' = sumV / (sumW * sumW)
-// The last level writes packed RGB and, where asked for, the filtered variance.
+// The last level writes packed RGB and, where asked for, the filtered variance -- or, in its BYTES form (PT_FLAG_DISPLAY_FILTER: the level
+// that ends the display path), sendImageToPBO's bytes of the filtered colour and nothing else: k_to_rgba8's conversion of a mean of one sample,
+// (int)(x * 255.0) formed in double, clamped to 0 .. 255, .w = 0, one uchar4 store per lane -- the bytes k_to_rgba8 makes of the packed RGB,
+// without the 12 B per pixel written and read back in between.
 struct AtrousVarArgs {
     const float *accum, *moments;   // FIRST: the accumulator's packed RGB sums and the sums of squared luminance
     const float4 *cin;              // later levels: the level before, (r, g, b, variance)
     float4 *cout;                   // every level but the last
-    float *out3, *outVar;           // LAST: packed RGB, and the variance (or NULL)
+    union {
+        float *out3;                // LAST: packed RGB ...
+        uchar4 *out8;               // ... or, BYTES: the display's bytes (the same kernel argument: the other forms keep their layout)
+    };
+    float *outVar;                  // LAST: the variance (or NULL); BYTES: unused
     const float4 *posT, *nrmId;
     int W, H, step;
     float samples, samplesM1;       // FIRST: (float)samples, (float)(samples - 1)
@@ -318,10 +325,20 @@ __device__ __forceinline__ void atrousVarTap(const AtrousVarArgs &A, float hw, f
     sumV += cq.w * (w * w);
 }
 
-template <bool LAST>
+// k_to_rgba8's conversion of one channel of a mean (pt_trace.h)
+__device__ __forceinline__ unsigned char atrousByte(float x) {
+    const int i = (int)(x * 255.0);
+    return (unsigned char)(i < 0 ? 0 : (i > 255 ? 255 : i));
+}
+
+template <bool LAST, bool BYTES>
 __device__ __forceinline__ void atrousVarStore(const AtrousVarArgs &A, size_t pix, F3 sumC, float sumV, float sumW) {
     const float r = sumC.x / sumW, g = sumC.y / sumW, b = sumC.z / sumW, v = sumV / (sumW * sumW);
-    if (LAST) {
+    if (BYTES) {
+        uchar4 o;
+        o.w = 0; o.x = atrousByte(r); o.y = atrousByte(g); o.z = atrousByte(b);
+        A.out8[pix] = o;
+    } else if (LAST) {
         float *o = A.out3 + 3 * pix;
         o[0] = r; o[1] = g; o[2] = b;
         if (A.outVar) A.outVar[pix] = v;
@@ -331,8 +348,9 @@ __device__ __forceinline__ void atrousVarStore(const AtrousVarArgs &A, size_t pi
 }
 
 // The plain gather, as k_atrous_gather.
-template <bool FIRST, bool LAST>
+template <bool FIRST, bool LAST, bool BYTES = false>
 __global__ __launch_bounds__(kBlock) void k_atrous_var_gather(AtrousVarArgs A) {
+    static_assert(LAST || !BYTES, "only a last level writes the bytes");
     const int tilesX = (A.W + kAtrousTileW - 1) / kAtrousTileW;
     const int tY = (int)(blockIdx.x / (unsigned)tilesX), tX = (int)(blockIdx.x - (unsigned)tY * (unsigned)tilesX);
     const int x = tX * kAtrousTileW + (int)(threadIdx.x & 63u), y = tY * 4 + (int)(threadIdx.x >> 6);
@@ -376,15 +394,16 @@ __global__ __launch_bounds__(kBlock) void k_atrous_var_gather(AtrousVarArgs A) {
             }
         }
     }
-    atrousVarStore<LAST>(A, pix, sumC, sumV, sumW);
+    atrousVarStore<LAST, BYTES>(A, pix, sumC, sumV, sumW);
 }
 
 // The LDS-tiled form, as k_atrous_tiled: the same three float4 images of the same shape, the colour image's .w now the variance.  The 3 x 3
 // prefilter reads the .w of the eight inner taps' colour and normal + id entries once more: 16 ds_read_b32 per row next to the taps' 16-byte
 // reads, each striding 16 bytes across the wave (four lanes per bank).  The levels are bound by vector issue, not by LDS
 // (profiles/denoise_var_cost.txt: a tiled level costs 1.00 - 1.12 x the plain filter's), so the entries are not kept in registers for them.
-template <bool FIRST, bool LAST, int RPT>
+template <bool FIRST, bool LAST, int RPT, bool BYTES = false>
 __global__ __launch_bounds__(kBlock) void k_atrous_var_tiled(AtrousVarArgs A) {
+    static_assert(LAST || !BYTES, "only a last level writes the bytes");
     constexpr int TH = 4 * RPT, ROWS = TH + 4, ENTRIES = kAtrousPitch * ROWS;
     __shared__ float4 s_c[ENTRIES], s_n[ENTRIES], s_p[ENTRIES];
     const int s = A.step;
@@ -450,7 +469,7 @@ __global__ __launch_bounds__(kBlock) void k_atrous_var_tiled(AtrousVarArgs A) {
                 }
             }
         }
-        atrousVarStore<LAST>(A, (size_t)x + (size_t)y * (size_t)A.W, sumC, sumV, sumW);
+        atrousVarStore<LAST, BYTES>(A, (size_t)x + (size_t)y * (size_t)A.W, sumC, sumV, sumW);
     }
 }
 

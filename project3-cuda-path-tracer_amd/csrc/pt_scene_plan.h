@@ -45,6 +45,9 @@ PtOptions effective_options(const PtOptions *opts) {
     return o;
 }
 
+// dynamic LDS k_gbuffer needs for a scene: the lanes' mesh traversal stacks (a launch holds at most 64 KB)
+inline size_t guideStackBytes(bool mesh, int meshStackNeed) { return mesh ? (size_t)std::max(meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0; }
+
 // What the renderer keeps of a plan (State derives from it): the launches read these on every call.
 struct PlanScalars {
     PtCamera cam;
@@ -239,6 +242,8 @@ int check_scene(const SceneIn &in) {
         if (o.flags & PT_FLAG_TRACE_AHEAD) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_TEMPORAL is not for PT_FLAG_TRACE_AHEAD renderers");
         if (o.lens_radius > 0.0f) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_TEMPORAL needs the pinhole camera (a thin lens has no single projection)");
     }
+    if ((o.flags & PT_FLAG_DISPLAY_FILTER) && !(o.flags & PT_FLAG_MOMENTS))
+        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DISPLAY_FILTER needs PT_FLAG_MOMENTS (the filter is guided by the variance)");
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;
@@ -829,6 +834,9 @@ int plan_lds(const SceneIn &in, ScenePlan &p) {
     if (p.mesh) {        // (the lanes' stacks of far children belong to the walk's own launches: k_mesh_walk)
         p.ldsWalk = walkLdsBytes(p.meshStackNeed, p.walkMeshLds);
         if (p.ldsWalk > 160 * 1024) return fail(PT_ERR_INVALID, "pt_init: a mesh's hierarchy needs %d stack levels (%zu B of LDS for the lanes' stacks)", p.meshStackNeed, p.ldsWalk);
+        // (the display filter launches k_gbuffer from pt_iterate: what ensure_guides would refuse there is refused here, with its message)
+        if ((p.flags & PT_FLAG_DISPLAY_FILTER) && guideStackBytes(true, p.meshStackNeed) > 64 * 1024)
+            return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DISPLAY_FILTER: guide buffers: a mesh hierarchy needs %d stack levels", p.meshStackNeed);
     }
     if (p.ldsBytesNext == 0) p.ldsBytesNext = p.ldsBytes;
     if (p.ldsBytes > 160 * 1024) return fail(PT_ERR_INVALID, "pt_init: scene does not fit the 160 KiB LDS (%zu B)", p.ldsBytes);

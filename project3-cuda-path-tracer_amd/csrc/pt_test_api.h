@@ -949,6 +949,13 @@ int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_
     return denoise_var_to_host(samples, p, params_struct_bytes, form, ms, rgb_mean_host, var_host, "pt_test_denoise_var");
 }
 
+int pt_test_display(int samples, int form, int fused, void *rgba8_dev, float *ms) {
+    PTCHECK(moments_refusals("pt_test_display"));
+    if (!rgba8_dev || samples < 1 || (fused != 0 && fused != 1)) return fail(PT_ERR_INVALID, "pt_test_display: bad argument");
+    if (ms) std::fill(ms, ms + 1 + PT_DISPLAY_LEVELS, 0.0f);
+    return display_bytes(samples, reinterpret_cast<uchar4 *>(rgba8_dev), "pt_test_display", form, fused != 0, ms);
+}
+
 static_assert(sizeof(TemporalCam) == 16 * sizeof(float), "pt_test_temporal's cam16 is a TemporalCam (include/pt_amd_test.h)");
 
 int pt_test_temporal_camera(const PtCamera *cam, float *cam16) {

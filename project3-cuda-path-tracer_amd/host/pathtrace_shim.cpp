@@ -17,6 +17,7 @@ static PtGroup *group = NULL;
 static float extraLens = 0.0f, extraFocal = 0.0f;   // README extras (pathtraceExtras), off = the reference's renderer
 static bool extraDirect = false;
 static bool extraMoments = false;                   // pathtraceMoments: PT_FLAG_MOMENTS for the next pathtraceInit
+static bool extraDisplay = false;                   // pathtraceDisplayFilter: PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER for the next pathtraceInit
 
 static void checkPtError(int status, const char *msg) {
     if (status == PT_OK) return;
@@ -35,6 +36,11 @@ void pathtraceInit(Scene *scene) {
     opt.focal_distance = extraFocal;
     if (extraDirect) opt.flags |= PT_FLAG_DIRECT_LIGHTING;
     if (extraMoments) opt.flags |= PT_FLAG_MOMENTS;
+    // PT_AMD_DISPLAY_FILTER=1 (or pathtraceDisplayFilter): the `pbo` of pathtrace receives the variance-guided filter's bytes instead of the raw
+    // accumulator's -- for a host built against the reference's header unchanged.  state.image stays the raw sum.
+    bool display = extraDisplay;
+    if (const char *e = getenv("PT_AMD_DISPLAY_FILTER")) display = display || atoi(e) != 0;
+    if (display) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER;
     // The reference's host calls pathtrace(pbo, frame, iter) once per iteration with iter = 1, 2, 3, ... (src/main.cpp:97-103):
     // the library traces such a sequence in wavefront batches AHEAD of the calls (PT_FLAG_TRACE_AHEAD; same image after every
     // call, bit for bit), so a call costs a commit instead of eight small dependent launches.  A camera move goes through
@@ -115,6 +121,11 @@ void pathtraceInit(Scene *scene) {
 #endif
     int members = 1;
     if (const char *e = getenv("PT_AMD_DEVICES")) members = atoi(e);
+    if (members >= 2 && display) {
+        fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: the display filter (PT_AMD_DISPLAY_FILTER, pathtraceDisplayFilter) is not for "
+                        "PT_AMD_DEVICES: a group renders headless\n");
+        exit(EXIT_FAILURE);
+    }
     if (members >= 2) {
         if (group && pt_group_size(group) != members) {
             pt_group_destroy(group);
@@ -169,6 +180,11 @@ void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting)
 // Not a reference symbol either: the next pathtraceInit also keeps the samples' second moments (PT_FLAG_MOMENTS: pt_variance,
 // pt_denoise_var).  Not with PT_AMD_DEVICES: a group refuses the flag.
 void pathtraceMoments(bool on) { extraMoments = on; }
+
+// ... nor this one: the next pathtraceInit sets PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER, and the `pbo` of every pathtrace call from the second
+// iteration on receives the bytes of the variance-guided filter (include/pt_amd.h: "display filter"), made on the device behind the commit.
+// The environment variable PT_AMD_DISPLAY_FILTER=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
+void pathtraceDisplayFilter(bool on) { extraDisplay = on; }
 
 void pathtraceFree() {
     if (group) {
