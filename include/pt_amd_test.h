@@ -165,17 +165,17 @@ int pt_test_texture_uv(int kind, const float *in, const int32_t *face, int n, fl
  * mesh: the barycentric u, v, the corner UVs u0 v0 u1 v1 u2 v2 and the object-space corners p0 p1 p2 (tangents: the library's own host code).
  * out: 16 floats per hit {hu, hv, Pu (3), Pv (3), Ns (3), bumped (0 / 1), u, v, 0, 0}; Ns = N where the hit stays unbumped. */
 int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, const float *in, int n, float *out);
-/* the denoiser (pt_amd.h, csrc/pt_denoise.h): pt_denoise of THIS library's renderer with the form of k_atrous named -- 0: the product's
+/* the denoiser (pt_amd.h, csrc/pt_denoise.h): pt_denoise of THIS library's renderer with the form of k_atrous_*<AtrousPlain> named -- 0: the product's
  * choice per level, 1: the plain gather, 2 / 3: LDS tiles of 64 x 4 / 64 x 8 pixels of a residue class -- every form gives the same bits.
  * ms (or NULL): 1 + levels kernel times by HIP events, k_gbuffer first (0 when the guide buffers were cached), then each level. */
 int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms);
-/* ... and pt_denoise_var with the form of k_atrous_var named, the same four forms; var_host may be NULL; ms as above (on a renderer whose context
+/* ... and pt_denoise_var with the form of k_atrous_*<AtrousGuided> named, the same four forms; var_host may be NULL; ms as above (on a renderer whose context
  * holds history -- PT_FLAG_TEMPORAL -- k_temporal runs between k_gbuffer and level 0 and belongs to neither time). */
 int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms);
 /* the display path (PT_FLAG_DISPLAY_FILTER, pt_amd.h) of THIS library's renderer -- any PT_FLAG_MOMENTS renderer, the flag itself is not needed
- * -- with the form of k_atrous_var named for every level, the last included: what pt_iterate(..., rgba8_dev) enqueues behind the commit, into
+ * -- with the form of k_atrous_*<AtrousGuided> named for every level, the last included: what pt_iterate(..., rgba8_dev) enqueues behind the commit, into
  * rgba8_dev (DEVICE memory, W * H * 4 bytes), on the renderer's stream, without a synchronisation unless ms is given.  form: the four of
- * pt_test_denoise.  fused 1: the last level writes the bytes itself (k_atrous_var_*<false, true, ., true>); 0: it writes packed RGB and
+ * pt_test_denoise.  fused 1: the last level writes the bytes itself (k_atrous_*<AtrousGuided, false, true, ., true>); 0: it writes packed RGB and
  * k_to_rgba8 converts it -- the same bytes.  samples 1: the plain conversion.  ms (or NULL): 1 + PT_DISPLAY_LEVELS kernel times as
  * pt_test_denoise_var's, the last level's with the k_to_rgba8 launch where fused is 0 (all 0 for samples 1). */
 int pt_test_display(int samples, int form, int fused, void *rgba8_dev, float *ms);

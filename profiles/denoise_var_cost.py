@@ -1,5 +1,5 @@
 """What the second moments and the variance-guided filter cost on one MI355X, Cornell, against their yardsticks from the same build: each
-level of each form of k_atrous_var against the plain filter's same level and the five levels as the library launches them (HIP events:
+level of each form of k_atrous_*<AtrousGuided> against the plain filter's same level and the five levels as the library launches them (HIP events:
 pt_test_denoise_var / pt_test_denoise, the two alternating; at 1280x720 and once more at 1920x1080, so that the tiled / gather thresholds
 do not rest on one frame size), the iteration rate of a renderer with PT_FLAG_MOMENTS against one without (1280x720; HIP events on the
 caller's stream around batches of 1 and of 32, the two alternating), and the commit kernels themselves -- k_commit_one / k_commit, <false>

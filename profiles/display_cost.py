@@ -4,7 +4,7 @@ frame size alternating in one run, HIP events, best and median of 35:
   1. per displayed frame, what a host does today for the filtered preview -- pt_denoise_var_rgba8 into page-locked host memory (it synchronises)
      and the upload of those bytes into the device buffer it displays from -- against the flagged pt_iterate(..., rgba8_dev), both next to the
      pt_iterate(..., NULL) they come on top of (events on the renderer's stream around each call; every timed pt_iterate adds one sample);
-  2. the last level that writes the bytes itself against the two launches it replaces -- the parent's k_atrous_var_*<false, true> and
+  2. the last level that writes the bytes itself against the two launches it replaces -- the parent's k_atrous_*<AtrousGuided, false, true> and
      k_to_rgba8, which this build holds instruction for instruction (profiles/display_resource_usage.txt) -- through pt_test_display's
      per-kernel times at exactly 16 samples, and the rule of the issue: the fused level stays only if it is not slower than the pair by more than
      the pair's own best-to-median spread.
@@ -137,8 +137,8 @@ def fused_against_pair(w, h):
     keep = slower <= spread
     return ["%dx%d, Cornell at %d samples: the last of the %d levels (step 16, the gather), HIP events, %d each, the two alternating: ms best (median, worst)"
             % (w, h, SAMPLES, pt.PT_DISPLAY_LEVELS, REPS),
-            "  fused: k_atrous_var_gather<false, true, true> writes the bytes          %s" % _fmt(last[True]),
-            "  pair:  k_atrous_var_gather<false, true> (packed RGB), then k_to_rgba8   %s" % _fmt(last[False]),
+            "  fused: k_atrous_gather<AtrousGuided, false, true, true> writes the bytes  %s" % _fmt(last[True]),
+            "  pair:  k_atrous_gather<AtrousGuided, false, true>, then k_to_rgba8        %s" % _fmt(last[False]),
             "  the five levels together: fused %s, pair %s" % (_fmt(whole[True]), _fmt(whole[False])),
             "  fused - pair: %+.4f ms (best - best), %+.4f ms (median - median); the pair's best-to-median spread: %.4f ms -> the fused level %s"
             % (slower, _med(last[True]) - _med(last[False]), spread, "stays" if keep else "GOES: keep the two launches")]

@@ -1,5 +1,5 @@
 """What temporal reprojection costs on one MI355X, Cornell, against its yardsticks from the same build and the same run: k_temporal in both
-forms (pt_test_temporal over the device's own accumulators, guides and captured history: HIP events) next to one tiled level of k_atrous_var
+forms (pt_test_temporal over the device's own accumulators, guides and captured history: HIP events) next to one tiled level of k_atrous_tiled<AtrousGuided>
 and k_gbuffer (pt_test_denoise_var's per-kernel times) on the same frame, the three alternating, at 1280x720 and 1920x1080; and the wall time
 of a pt_init over a live renderer with PT_FLAG_TEMPORAL (the capture: k_temporal<true>, the guides' hand-over, one stream synchronisation)
 against the same call without the flag, the two alternating.  Prints the first part of profiles/temporal_cost.txt (the bench.py comparison
@@ -80,7 +80,7 @@ def frame(w, h):
                  % (76 * px / 1e6, 76 * px / (HBM_PEAK_GBS * 1e6), HBM_PEAK_GBS))
     lines.append("  k_temporal<false> (filter form)                  %s" % _fmt(t_filter))
     lines.append("  k_temporal<true>  (capture form)                 %s" % _fmt(t_capture))
-    lines.append("  k_atrous_var, level 0 (step 1, tiled 64x8)       %s" % _fmt(t_level))
+    lines.append("  k_atrous_tiled<AtrousGuided>, level 0 (step 1, 64x8)  %s" % _fmt(t_level))
     lines.append("  k_gbuffer                                        %s" % _fmt(t_gbuf))
     lines.append("  k_temporal<false> / one filter level: %.2f (best over best), %.2f (median over median)"
                  % (min(t_filter) / min(t_level), float(np.median(t_filter)) / float(np.median(t_level))))

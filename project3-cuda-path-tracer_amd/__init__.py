@@ -709,7 +709,7 @@ def gbuffer(guide_iter=1):
 
 def test_denoise(samples, form, levels=5, sigma_color=DENOISE_SIGMA_COLOR, sigma_normal=DENOISE_SIGMA_NORMAL,
                  sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1, timing=False):
-    """denoise() with the form of k_atrous named (test library, inside renderer_from_test_library): 0 the product's choice, 1 the plain gather,
+    """denoise() with the form of k_atrous_*<AtrousPlain> named (test library, inside renderer_from_test_library): 0 the product's choice, 1 the plain gather,
     2 / 3 LDS tiles of 64 x 4 / 64 x 8.  timing=True: also the kernel times in ms, k_gbuffer first (0 when cached), then each level."""
     out = np.empty(_frame_pixels() * 3, np.float32)
     ms = np.zeros(1 + levels, np.float32)
@@ -759,7 +759,7 @@ def denoise_var_rgba8(samples, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma_norm
 
 def test_denoise_var(samples, form, levels=5, sigma_lum=DENOISE_SIGMA_LUM, sigma_normal=DENOISE_SIGMA_NORMAL,
                      sigma_position=DENOISE_SIGMA_POSITION, guide_iter=1, timing=False):
-    """denoise_var(with_variance=True) with the form of k_atrous_var named, as test_denoise: (rgb, variance[, ms])."""
+    """denoise_var(with_variance=True) with the form of k_atrous_*<AtrousGuided> named, as test_denoise: (rgb, variance[, ms])."""
     n = _frame_pixels()
     out, var = np.empty(n * 3, np.float32), np.empty(n, np.float32)
     ms = np.zeros(1 + levels, np.float32)

@@ -679,11 +679,19 @@ void register_exit_handler() {
 // which form of k_atrous a level takes: the plain gather, or the LDS-tiled one with one or two rows per wave
 enum { kAtrousAuto = 0, kAtrousGather = 1, kAtrousTiled4 = 2, kAtrousTiled8 = 3 };
 
-template <bool F, bool L>
-const void *atrous_kernel(int form) {
-    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_gather<F, L>);
-    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_tiled<F, L, 1>);
-    return reinterpret_cast<const void *>(k_atrous_tiled<F, L, 2>);
+// the kernel of a level by (first, last, bytes, form): 12 per filter, and the guided one's three <false, true, ., BYTES>
+template <class Filter, bool F, bool L, bool BYTES = false>
+const void *atrous_forms(int form) {
+    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_gather<Filter, F, L, BYTES>);
+    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_tiled<Filter, F, L, 1, BYTES>);
+    return reinterpret_cast<const void *>(k_atrous_tiled<Filter, F, L, 2, BYTES>);
+}
+template <class Filter>
+const void *atrous_kernel(bool first, bool last, bool bytes, int form) {
+    if constexpr (Filter::kVariance)
+        if (bytes) return atrous_forms<Filter, false, true, true>(form);
+    return first ? (last ? atrous_forms<Filter, true, true>(form) : atrous_forms<Filter, true, false>(form))
+                 : (last ? atrous_forms<Filter, false, true>(form) : atrous_forms<Filter, false, false>(form));
 }
 
 // timing events that go away on every path out of their scope
@@ -735,30 +743,34 @@ int ensure_guides(int guideIter, float *ms) {
     return PT_OK;
 }
 
-// The filter's levels on the caller's stream, behind every committed iteration; the result is left in R().dnOut (packed RGB).
-// form: kAtrousAuto is the product's choice per level (UNMEASURED so far: see below); ms (or NULL): 1 + levels kernel times, k_gbuffer first.
-int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, float *ms, const char *who) {
-    int rc = denoise_refusals(who);
-    if (rc) return rc;
-    if (!p || bytes != sizeof(PtDenoiseParams))
-        return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseParams));
-    if (samples < 1) return fail(PT_ERR_INVALID, "%s: samples must be >= 1", who);
+// The levels of either filter (pt_denoise.h: a filter description) on the caller's stream, behind every committed iteration; the result is
+// left in R().dnOut (packed RGB).  p: the caller's PtDenoiseParams or PtDenoiseVarParams, sigmaColour its first sigma; A: the filter's own
+// members set, the rest is filled here.  form: kAtrousAuto is the product's choice per level; ms (or NULL): 1 + levels kernel times, k_gbuffer first.
+// front(): what the filter puts between the guides and level 0; `blended`: it leaves level 0's input in R().dnPing[1], the half the level
+// before level 0 would have written, so level 0 runs as a later level at step 1.
+// bytesOut (the display path; a filter with a BYTES form): sendImageToPBO's bytes of the filtered mean go there instead -- device memory of
+// P uchar4 -- written by the last level itself (`fused`, the product's way: k_atrous_*<AtrousGuided, false, true, ., true>, measured faster
+// than the pair in profiles/display_cost.txt; R().dnOut is not touched then), or by k_to_rgba8 of R().dnOut behind it -- the test build's
+// reference -- which belongs to the last level's time in `ms`.  A last level that reads the accumulators (levels 1, not blended) has no fused
+// form and takes the two launches.
+template <class Filter, class Params, class Front>
+int atrous_run(typename Filter::Args &A, int samples, const Params *p, float sigmaColour, int form, float *ms, const char *who, bool blended, Front front,
+               uchar4 *bytesOut = nullptr, bool fused = true) {
     if (p->levels < 1 || p->levels > 8) return fail(PT_ERR_INVALID, "%s: levels must be 1..8", who);
-    for (float sg : {p->sigma_color, p->sigma_normal, p->sigma_position})
+    for (float sg : {sigmaColour, p->sigma_normal, p->sigma_position})
         if (!(sg > 0.0f)) return fail(PT_ERR_INVALID, "%s: a sigma must be > 0 (+inf switches its term off)", who);
     if (form < kAtrousAuto || form > kAtrousTiled8) return fail(PT_ERR_INVALID, "%s: unknown kernel form %d", who, form);
-    rc = ensure_guides(p->guide_iter, ms);
-    if (rc) return rc;
+    PTCHECK(ensure_guides(p->guide_iter, ms));
     const size_t P = (size_t)R().P;
-    if (!R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
+    const bool bytesFused = Filter::kVariance && bytesOut && fused && (p->levels > 1 || blended);
+    if (!bytesFused && !R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
     for (int k = 0; k < 2 && k < p->levels - 1; ++k)
         if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
-    AtrousArgs A;
+    PTCHECK(front());
     A.accum = R().image;
     A.posT = R().dnPosT.p; A.nrmId = R().dnNrmId.p;
     A.W = R().prm.W; A.H = R().prm.H;
     A.samples = (float)samples;
-    const float invC0 = 1.0f / (p->sigma_color * p->sigma_color);
     A.invN = 1.0f / (p->sigma_normal * p->sigma_normal);
     A.invP = 1.0f / (p->sigma_position * p->sigma_position);
     EventSet es;
@@ -766,25 +778,27 @@ int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, f
     if (ms)
         for (int i = 0; i <= p->levels; ++i) HIPCHECK(hipEventCreate(&ev[i]));
     for (int i = 0; i < p->levels; ++i) {
-        const bool first = i == 0, last = i == p->levels - 1;
+        const bool first = i == 0 && !blended, last = i == p->levels - 1;
         A.step = 1 << i;
-        A.invC = invC0 * (float)(1 << (2 * i));
-        A.cin = first ? nullptr : R().dnPing[(i - 1) & 1].p;
+        Filter::hostColourScale(A, sigmaColour, i);
+        A.cin = first ? nullptr : R().dnPing[(i + 1) & 1].p;
         A.cout = last ? nullptr : R().dnPing[i & 1].p;
         A.out3 = last ? R().dnOut.p : nullptr;
-        // (NOT measured yet -- profiles/denoise_cost.py is the measurement to run: the expectation is that the tiled form wins while a class's
-        // rows still share cache lines, and the gather, whose taps stay coalesced at every step, beyond)
-        int f = form != kAtrousAuto ? form : (A.step <= kAtrousTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
+        if constexpr (Filter::kVariance)
+            if (last && bytesFused) A.out8 = bytesOut;
+        int f = form != kAtrousAuto ? form : (A.step <= Filter::kTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
         unsigned long long grid = f == kAtrousGather ? atrousGridGather(A.W, A.H) : atrousGridTiled(A.W, A.H, A.step, f == kAtrousTiled4 ? 1 : 2);
         if (grid > 0x7fffffffull) {       // (a frame of few, very long rows at a large step: more tiles than a launch holds)
             f = kAtrousGather;
             grid = atrousGridGather(A.W, A.H);
         }
-        const void *kern = first ? (last ? atrous_kernel<true, true>(f) : atrous_kernel<true, false>(f))
-                                 : (last ? atrous_kernel<false, true>(f) : atrous_kernel<false, false>(f));
         void *kargs[] = {&A};
         if (ms) HIPCHECK(hipEventRecord(ev[i], R().stream));
-        HIPCHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
+        HIPCHECK(hipLaunchKernel(atrous_kernel<Filter>(first, last, last && bytesFused, f), dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
+    }
+    if (bytesOut && !bytesFused) {
+        // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
+        hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut.p, R().P, 1, bytesOut);
     }
     if (ms) {
         HIPCHECK(hipEventRecord(ev[p->levels], R().stream));
@@ -795,13 +809,30 @@ int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, f
     return PT_OK;
 }
 
-int denoise_to_host(int samples, const PtDenoiseParams *p, size_t bytes, int form, float *ms, float *rgb_mean_host, const char *who) {
-    if (!rgb_mean_host) return fail(PT_ERR_INVALID, "%s: null", who);
-    int rc = denoise_run(samples, p, bytes, form, ms, who);
-    if (rc) return rc;
+// pt_denoise's levels (AtrousPlain).  kAtrousAuto: NOT measured yet for this filter -- profiles/denoise_cost.py is the measurement to run: the
+// expectation is that the tiled form wins while a class's rows still share cache lines, and the gather, whose taps stay coalesced at every
+// step, beyond.
+int denoise_run(int samples, const PtDenoiseParams *p, size_t bytes, int form, float *ms, const char *who) {
+    PTCHECK(denoise_refusals(who));
+    if (!p || bytes != sizeof(PtDenoiseParams))
+        return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseParams));
+    if (samples < 1) return fail(PT_ERR_INVALID, "%s: samples must be >= 1", who);
+    AtrousArgs A;
+    return atrous_run<AtrousPlain>(A, samples, p, p->sigma_color, form, ms, who, false, [] { return PT_OK; });
+}
+
+// a finished run's packed RGB and, asked for, its variance image to the host
+int denoise_result_to_host(float *rgb_mean_host, float *var_host) {
     HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut.p, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
+    if (var_host) HIPCHECK(hipMemcpyAsync(var_host, R().dnVar.p, (size_t)R().P * sizeof(float), hipMemcpyDeviceToHost, R().stream));
     HIPCHECK(hipStreamSynchronize(R().stream));
     return readback_fault();
+}
+
+int denoise_to_host(int samples, const PtDenoiseParams *p, size_t bytes, int form, float *ms, float *rgb_mean_host, const char *who) {
+    if (!rgb_mean_host) return fail(PT_ERR_INVALID, "%s: null", who);
+    PTCHECK(denoise_run(samples, p, bytes, form, ms, who));
+    return denoise_result_to_host(rgb_mean_host, nullptr);
 }
 
 // ---- temporal reprojection (pt_temporal.h) -----------------------------------------------------------------------------------------------
@@ -828,6 +859,26 @@ TemporalCam temporal_camera(const KParams &k) {
     return c;
 }
 
+// k_temporal over the renderer and its context's history, on its stream: the blend of `samples` committed iterations with the history -- the
+// halves a live history holds; none: every pixel goes without -- into out (and outN: the capture form); needs the guides (ensure_guides)
+template <bool CAPTURE>
+int temporal_blend(float samples, float4 *out, float *outN) {
+    const State &S = R();
+    const History &hs = S.hist;
+    TemporalArgs T;
+    T.accum = S.image; T.moments = S.moments.p;
+    T.posT = S.dnPosT.p; T.nrmId = S.dnNrmId.p;
+    T.hc = hs.live ? hs.hc[hs.cur].p : nullptr; T.hn = hs.live ? hs.hn[hs.cur].p : nullptr;
+    T.hpos = hs.hpos.p; T.hnrm = hs.hnrm.p;
+    T.cam = hs.cam;
+    T.W = S.prm.W; T.H = S.prm.H;
+    T.samples = samples;
+    T.out = out; T.outN = outN;
+    hipLaunchKernelGGL(k_temporal<CAPTURE>, dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
+    HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
 // pt_init over a live PT_FLAG_TEMPORAL renderer that has committed R().committed >= 1 iterations: the old view's blend of ITS history with
 // ITS samples becomes the context's history (k_temporal<true> into the other half of the ping-pong pair), its guide buffers of iteration 1
 // -- the cached ones, or one k_gbuffer launch -- are handed over, and its camera is kept.  On the old renderer's stream, behind its commits.
@@ -840,17 +891,8 @@ int capture_history() {
     const int nxt = hs.live ? hs.cur ^ 1 : 0;
     if (!hs.hc[nxt].p) PTCHECK(hs.hc[nxt].alloc(P));
     if (!hs.hn[nxt].p) PTCHECK(hs.hn[nxt].alloc(P));
-    TemporalArgs T;
-    T.accum = S.image; T.moments = S.moments.p;
-    T.posT = S.dnPosT.p; T.nrmId = S.dnNrmId.p;
-    T.hc = hs.live ? hs.hc[hs.cur].p : nullptr; T.hn = hs.live ? hs.hn[hs.cur].p : nullptr;
-    T.hpos = hs.hpos.p; T.hnrm = hs.hnrm.p;
-    T.cam = hs.cam;
-    T.W = S.prm.W; T.H = S.prm.H;
-    T.samples = (float)S.committed;       // (not `iterations`: pt_counters_reset zeroes that one and leaves the accumulators)
-    T.out = hs.hc[nxt].p; T.outN = hs.hn[nxt].p;
-    hipLaunchKernelGGL(k_temporal<true>, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
-    HIPCHECK(hipGetLastError());
+    // (S.committed, not `iterations`: pt_counters_reset zeroes that one and leaves the accumulators)
+    PTCHECK(temporal_blend<true>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p));
     HIPCHECK(hipStreamSynchronize(S.stream));      // (the guides it read are released next)
     hs.hpos = std::move(S.dnPosT);
     hs.hnrm = std::move(S.dnNrmId);
@@ -861,108 +903,37 @@ int capture_history() {
     return PT_OK;
 }
 
-// ---- the second moments and the variance-guided filter (pt_denoise.h, k_atrous_var_*) ---------------------------------------------------
+// ---- the second moments and the variance-guided filter (pt_denoise.h, AtrousGuided) -----------------------------------------------------
 int moments_refusals(const char *who) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
     if (!R().moments.p) return fail(PT_ERR_INVALID, "%s: the renderer was initialised without PT_FLAG_MOMENTS", who);
     return PT_OK;
 }
 
-template <bool F, bool L, bool BYTES = false>
-const void *atrous_var_kernel(int form) {
-    if (form == kAtrousGather) return reinterpret_cast<const void *>(k_atrous_var_gather<F, L, BYTES>);
-    if (form == kAtrousTiled4) return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 1, BYTES>);
-    return reinterpret_cast<const void *>(k_atrous_var_tiled<F, L, 2, BYTES>);
-}
-
 // PT_FLAG_DISPLAY_FILTER: the one setting of the display path (include/pt_amd.h)
 const PtDenoiseVarParams kDisplayParams = {PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA_NORMAL, PT_DISPLAY_SIGMA_POSITION};
 
-// The variance-guided filter's levels on the caller's stream, as denoise_run: packed RGB in R().dnOut, the filtered variance in R().dnVar when
-// `wantVar`; ms (or NULL): 1 + levels kernel times, k_gbuffer first.
-// bytesOut (the display path; not with wantVar): sendImageToPBO's bytes of the filtered mean go there instead -- device memory of P uchar4 --
-// written by the last level itself (`fused`, the product's way: k_atrous_var_*<false, true, ., true>, measured faster than the pair in
-// profiles/display_cost.txt; R().dnOut is not touched then), or by k_to_rgba8 of R().dnOut behind it -- the test build's reference -- which
-// belongs to the last level's time in `ms`.  A last level that is also the first (levels 1, no history) has no fused form and takes the two launches.
+// pt_denoise_var's levels (AtrousGuided; atrous_run): packed RGB in R().dnOut, the filtered variance in R().dnVar when `wantVar`; bytesOut,
+// fused (the display path; not with wantVar): atrous_run's.
 int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, bool wantVar, float *ms, const char *who,
                     uchar4 *bytesOut = nullptr, bool fused = true) {
     PTCHECK(moments_refusals(who));
     if (!p || bytes != sizeof(PtDenoiseVarParams))
         return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseVarParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseVarParams));
     if (samples < 2) return fail(PT_ERR_INVALID, "%s: samples must be >= 2 (a variance needs two)", who);
-    if (p->levels < 1 || p->levels > 8) return fail(PT_ERR_INVALID, "%s: levels must be 1..8", who);
-    for (float sg : {p->sigma_lum, p->sigma_normal, p->sigma_position})
-        if (!(sg > 0.0f)) return fail(PT_ERR_INVALID, "%s: a sigma must be > 0 (+inf switches its term off)", who);
-    if (form < kAtrousAuto || form > kAtrousTiled8) return fail(PT_ERR_INVALID, "%s: unknown kernel form %d", who, form);
-    PTCHECK(ensure_guides(p->guide_iter, ms));
-    const size_t P = (size_t)R().P;
-    // PT_FLAG_TEMPORAL with history: level 0 reads the blend of the reprojected history with the accumulators (k_temporal, into the ping-pong
-    // half the level before level 0 would have written) and so runs as a later level at step 1
+    // PT_FLAG_TEMPORAL with history: level 0 reads the blend of the reprojected history with the accumulators (k_temporal<false>)
     const History &hist = R().hist;
     const bool temporal = (R().flags & PT_FLAG_TEMPORAL) && hist.live && hist.W == R().prm.W && hist.H == R().prm.H;
-    const bool bytesFused = bytesOut && fused && (p->levels > 1 || temporal);
-    if (!bytesFused && !R().dnOut.p) PTCHECK(R().dnOut.alloc(P * 3));
-    if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc(P));
-    for (int k = 0; k < 2 && k < p->levels - 1; ++k)
-        if (!R().dnPing[k].p) PTCHECK(R().dnPing[k].alloc(P));
-    if (temporal) {
-        if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc(P));
-        TemporalArgs T;
-        T.accum = R().image; T.moments = R().moments.p;
-        T.posT = R().dnPosT.p; T.nrmId = R().dnNrmId.p;
-        T.hc = hist.hc[hist.cur].p; T.hn = hist.hn[hist.cur].p; T.hpos = hist.hpos.p; T.hnrm = hist.hnrm.p;
-        T.cam = hist.cam;
-        T.W = R().prm.W; T.H = R().prm.H;
-        T.samples = (float)samples;
-        T.out = R().dnPing[1].p; T.outN = nullptr;
-        hipLaunchKernelGGL(k_temporal<false>, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), 0, R().stream, T);
-        HIPCHECK(hipGetLastError());
-    }
     AtrousVarArgs A;
-    A.accum = R().image; A.moments = R().moments.p;
-    A.posT = R().dnPosT.p; A.nrmId = R().dnNrmId.p;
-    A.W = R().prm.W; A.H = R().prm.H;
-    A.samples = (float)samples; A.samplesM1 = (float)(samples - 1);
-    A.sl2 = p->sigma_lum * p->sigma_lum;
-    A.invN = 1.0f / (p->sigma_normal * p->sigma_normal);
-    A.invP = 1.0f / (p->sigma_position * p->sigma_position);
-    EventSet es;
-    hipEvent_t *const ev = es.ev;
-    if (ms)
-        for (int i = 0; i <= p->levels; ++i) HIPCHECK(hipEventCreate(&ev[i]));
-    for (int i = 0; i < p->levels; ++i) {
-        const bool first = i == 0 && !temporal, last = i == p->levels - 1;
-        A.step = 1 << i;
-        A.cin = first ? nullptr : R().dnPing[(i + 1) & 1].p;
-        A.cout = last ? nullptr : R().dnPing[i & 1].p;
-        A.out3 = last ? R().dnOut.p : nullptr;
-        if (last && bytesFused) A.out8 = bytesOut;
-        A.outVar = last && wantVar ? R().dnVar.p : nullptr;
-        // the form per level: 64 x 8 tiles up to the largest step they were measured to win clearly at (profiles/denoise_var_cost.txt), the gather above
-        int f = form != kAtrousAuto ? form : (A.step <= kAtrousVarTiledMaxStep ? kAtrousTiled8 : kAtrousGather);
-        unsigned long long grid = f == kAtrousGather ? atrousGridGather(A.W, A.H) : atrousGridTiled(A.W, A.H, A.step, f == kAtrousTiled4 ? 1 : 2);
-        if (grid > 0x7fffffffull) {
-            f = kAtrousGather;
-            grid = atrousGridGather(A.W, A.H);
-        }
-        const void *kern = first ? (last ? atrous_var_kernel<true, true>(f) : atrous_var_kernel<true, false>(f))
-                                 : (last ? (bytesFused ? atrous_var_kernel<false, true, true>(f) : atrous_var_kernel<false, true>(f))
-                                         : atrous_var_kernel<false, false>(f));
-        void *kargs[] = {&A};
-        if (ms) HIPCHECK(hipEventRecord(ev[i], R().stream));
-        HIPCHECK(hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
-    }
-    if (bytesOut && !bytesFused) {
-        // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
-        hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().dnOut.p, R().P, 1, bytesOut);
-    }
-    if (ms) {
-        HIPCHECK(hipEventRecord(ev[p->levels], R().stream));
-        HIPCHECK(hipEventSynchronize(ev[p->levels]));
-        for (int i = 0; i < p->levels; ++i) HIPCHECK(hipEventElapsedTime(&ms[1 + i], ev[i], ev[i + 1]));
-    }
-    HIPCHECK(hipGetLastError());
-    return PT_OK;
+    A.moments = R().moments.p;
+    A.samplesM1 = (float)(samples - 1);
+    return atrous_run<AtrousGuided>(A, samples, p, p->sigma_lum, form, ms, who, temporal, [&]() -> int {
+        if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc((size_t)R().P));
+        A.outVar = wantVar ? R().dnVar.p : nullptr;       // (read by a last level alone)
+        if (!temporal) return PT_OK;
+        if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc((size_t)R().P));
+        return temporal_blend<false>((float)samples, R().dnPing[1].p, nullptr);
+    }, bytesOut, fused);
 }
 
 // PT_FLAG_DISPLAY_FILTER: the bytes of `samples` committed iterations as the display sees them, into device memory, on the renderer's stream
@@ -980,10 +951,7 @@ int display_bytes(int samples, uchar4 *out, const char *who, int form = kAtrousA
 int denoise_var_to_host(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, float *ms, float *rgb_mean_host, float *var_host, const char *who) {
     if (!rgb_mean_host) return fail(PT_ERR_INVALID, "%s: null", who);
     PTCHECK(denoise_var_run(samples, p, bytes, form, var_host != nullptr, ms, who));
-    HIPCHECK(hipMemcpyAsync(rgb_mean_host, R().dnOut.p, (size_t)R().P * 3 * sizeof(float), hipMemcpyDeviceToHost, R().stream));
-    if (var_host) HIPCHECK(hipMemcpyAsync(var_host, R().dnVar.p, (size_t)R().P * sizeof(float), hipMemcpyDeviceToHost, R().stream));
-    HIPCHECK(hipStreamSynchronize(R().stream));
-    return readback_fault();
+    return denoise_result_to_host(rgb_mean_host, var_host);
 }
 
 

@@ -2,7 +2,7 @@
 // moving pinhole camera.  One kernel, outside the render path like the denoiser's (k_bounce, k_mesh_walk, k_commit and their arguments do not
 // know of it); included by pt_api.hip only.
 //   k_temporal<false>   the FILTER form: per pixel of the new view the count-weighted blend of the reprojected history with the new samples, as
-//                       the (r, g, b, variance) image level 0 of k_atrous_var_* then reads in place of meanAndVariance(S, Q)
+//                       the (r, g, b, variance) image level 0 of k_atrous_*<AtrousGuided> then reads in place of meanAndVariance(S, Q)
 //   k_temporal<true>    the CAPTURE form: the same blend, stored as the next history (mean colour, mean squared luminance; the capped count)
 //
 // ---- the kernel, operation by operation (tests/temporal_ref.py restates it in numpy, bit for bit: every fp32 operation below is one IEEE

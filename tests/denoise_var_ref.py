@@ -1,5 +1,5 @@
 """numpy float32 restatement of the second moments, the variance of the mean and the variance-guided a-trous filter (csrc/pt_denoise.h gives
-every operation: k_commit<true>, k_variance, k_atrous_var_*), vectorised over the pixels like denoise_ref.py: every operation is one fp32
+every operation: k_commit<true>, k_variance, k_atrous_*<AtrousGuided>), vectorised over the pixels like denoise_ref.py: every operation is one fp32
 operation in the kernels' order, so the GPU's result equals this one bit for bit."""
 import numpy as np
 

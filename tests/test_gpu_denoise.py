@@ -1,6 +1,6 @@
 """The denoiser on the MI355X, every comparison bit for bit: the guide buffers against the CPU oracle (camera_ray + intersect / mesh_intersect
 with the nearest_hit rule), the filter against the numpy restatement (tests/denoise_ref.py) fed with the device's own readback and guides --
-frames that cross tile borders, residue classes and frame borders in both axes --, every form of k_atrous against the others, the 8-bit
+frames that cross tile borders, residue classes and frame borders in both axes --, every form of k_atrous_*<AtrousPlain> against the others, the 8-bit
 form, what the calls leave behind, the refusals and the headless driver's --denoise."""
 import ctypes as C
 import os

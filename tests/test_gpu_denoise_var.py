@@ -1,6 +1,6 @@
 """Second moments, the variance of the mean and the variance-guided filter on the MI355X, every comparison bit for bit: the moments buffer
 against the CPU oracle's single iterations under every commit schedule, pt_variance and pt_denoise_var against the numpy restatement
-(tests/denoise_var_ref.py) fed with the device's own accumulators and guides, every form of k_atrous_var against the others, the 8-bit form,
+(tests/denoise_var_ref.py) fed with the device's own accumulators and guides, every form of k_atrous_*<AtrousGuided> against the others, the 8-bit form,
 what the calls leave behind, the refusals and the headless driver's --denoise-var.  Frames as in test_gpu_denoise.py: widths off a multiple
 of 64, heights off a multiple of 8.  pt_denoise_var (and form 0) takes 64 x 8 tiles up to step 8 (kAtrousVarTiledMaxStep) and the gather above:
 the cases of five and of eight levels cross that switch -- tiled levels hand their ping-pong image to gather levels, at steps 16 and
@@ -157,6 +157,19 @@ def test_every_kernel_form_gives_the_same_bits(gpu, scene, w, h, levels):
         outs = [gpu.test_denoise_var(2, form, levels, *SIGMAS) for form in (0, 1, 2, 3)]
     for o, v in outs:
         assert _same(o, want) and _same(v, wantv)
+
+
+@pytest.mark.parametrize("scene,w,h,levels", FRAMES[:2])
+def test_the_two_filters_share_one_skeleton(gpu, scene, w, h, levels):
+    """AtrousPlain and AtrousGuided differ in the colour term alone once it is off: with sigma_lum = +inf the guided filter's RGB is the
+    plain filter's with sigma_color = +inf, bit for bit (both terms are an exact + 0), in each kernel form, over the same accumulator,
+    sample count, sigma_normal, sigma_position and guides (tests/test_denoise_var_cpu.py holds the two restatements to the same)."""
+    _, sn, sp = SIGMAS
+    with gpu.renderer_from_test_library():
+        _init(gpu, scene, w, h, MN)
+        outs = [(gpu.test_denoise(MN, form, levels, np.inf, sn, sp), gpu.test_denoise_var(MN, form, levels, np.inf, sn, sp)[0]) for form in (0, 1, 2, 3)]
+    for plain, guided in outs:
+        assert np.isfinite(plain).all() and plain.any() and _same(guided, plain)
 
 
 # ---- 3: neighbours ------------------------------------------------------------------------------------------------------------------------

@@ -196,7 +196,7 @@ def _history_equals(got, want):
 @pytest.mark.parametrize("scene,w,h,levels", FRAMES)
 def test_chain_of_three_views(gpu, scene, w, h, levels):
     """init (moments + temporal), render 8; re-init with a moved camera: the history is the restatement's capture; render 2: pt_denoise_var and
-    _rgba8 are the restatement's blend-then-filter, in every form of k_atrous_var; re-init again: the recursive capture.  The 64 x 48 case makes
+    _rgba8 are the restatement's blend-then-filter, in every form of k_atrous_*<AtrousGuided>; re-init again: the recursive capture.  The 64 x 48 case makes
     the capture run k_gbuffer itself (the cached guides are another iteration's); the others hand over the cached ones."""
     sc = _scene(gpu, scene, w, h)
     e0, e1, e2 = _eyes(sc, scene)
