@@ -109,7 +109,12 @@ enum {
                                     pt_denoise_var_rgba8 with the PT_DISPLAY_* setting would return at that point of the stream, on the device and
                                     without a synchronisation.  Everything else is the unflagged renderer's bit for bit.  PT_ERR_INVALID without
                                     PT_FLAG_MOMENTS, and for a scene whose guide buffers cannot be made. */
-    PT_FLAG_DIRECT_LIGHTING = 4 /* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
+    PT_FLAG_SPATIAL_VARIANCE = 256,/* the spatial variance estimate (section "spatial variance" below): pt_denoise_var / pt_denoise_var_rgba8 accept
+                                    samples == 1, and a pixel whose effective sample count is below PT_SPATIAL_MIN_COUNT -- which has no variance of
+                                    its own -- is filtered under a variance estimated from its neighbours' luminance moments; with
+                                    PT_FLAG_DISPLAY_FILTER the display's first frame is filtered too.  From two samples on everything is the
+                                    unflagged renderer's bit for bit, launch for launch.  PT_ERR_INVALID without PT_FLAG_MOMENTS. */
+    PT_FLAG_DIRECT_LIGHTING = 4/* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
                                     that ray hits (traceDepth + 1 launches; traceDepth <= PT_MAX_DEPTH - 1).  A mesh is an
@@ -412,7 +417,7 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
  *   pt_denoise_var_rgba8(n, &{PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA_NORMAL, PT_DISPLAY_SIGMA_POSITION},
  *   ...) would return at that point of the stream: n is the count those calls divide by today (first_iter + count - 1, resp. iter), and where
  *   the context holds history (PT_FLAG_TEMPORAL) the bytes include the blend with it.  With n == 1 -- a variance needs two samples -- the bytes
- *   are the unfiltered conversion, as without the flag.
+ *   are the unfiltered conversion, as without the flag (unless PT_FLAG_SPATIAL_VARIANCE estimates one: section "spatial variance" below).
  *   pt_iterate_batch enqueues the filter on the renderer's stream behind the commit: the guide buffers (once per renderer, while no pt_denoise*
  *   or pt_gbuffer call asks for another guide_iter), the blend with the history where there is one, the levels, the last of which writes the
  *   bytes itself.  No host synchronisation, no allocation: pt_init allocates the filter's buffers (guide buffers, two float4 images, one image of
@@ -429,6 +434,30 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
 #define PT_DISPLAY_SIGMA_LUM 4.0f
 #define PT_DISPLAY_SIGMA_NORMAL 0.35f
 #define PT_DISPLAY_SIGMA_POSITION 2.0f
+
+/* ---- spatial variance (PT_FLAG_SPATIAL_VARIANCE, with PT_FLAG_MOMENTS; SVGF's estimate for pixels of short history, Schied et al., HPG 2017,
+ * section 4.2; csrc/pt_spatial_var.h gives every operation, tests/spatial_var_ref.py restates it).  No function of its own: a flag, and what
+ * pt_denoise_var*, and under PT_FLAG_DISPLAY_FILTER the display path, do under it.
+ *   One sample has no variance, so without the flag pt_denoise_var* refuse samples < 2, the display's first frame is the raw conversion, and
+ *   under PT_FLAG_TEMPORAL a disoccluded pixel of a one-sample view stays a raw sample inside a filtered frame.  Under the flag
+ *   pt_denoise_var / pt_denoise_var_rgba8 accept samples >= 1.  With samples == 1 two launches go in front of the filter's levels: the
+ *   pixel's mean colour, mean squared luminance m2 and effective sample count N (with history under PT_FLAG_TEMPORAL: the blend's, N = Nh + n
+ *   uncapped; without: S / n, Q / n, n), and then per pixel the variance level 0 reads:
+ *     N >= PT_SPATIAL_MIN_COUNT   the pixel's own, max(m2 - lum(c)^2, 0) / (N - 1): what it gets without the flag, to the bit
+ *     otherwise                   over the (2 PT_SPATIAL_RADIUS + 1)^2 window around it, weighted by the filter's normal and position terms
+ *                                 (the call's sigma_normal, sigma_position; the centre 1; never across the hit / miss border):
+ *                                 M1 = sum w lum(c_q) / sum w, M2 = sum w m2_q / sum w, variance max(M2 - M1^2, 0) / N -- N, not N - 1: the
+ *                                 mean comes from the window, not from the pixel
+ *   With samples >= 2 no pixel's count is below 2 and the renderer enqueues exactly the launches it enqueues without the flag.
+ *   With PT_FLAG_DISPLAY_FILTER the display path filters at n == 1 too: pt_iterate(.., rgba8_dev) and pt_readback_rgba8 give the bytes
+ *   pt_denoise_var_rgba8(1, PT_DISPLAY_*) would return.  No host synchronisation, no allocation: pt_init allocates the one image the flag adds
+ *   (W*H floats, the counts) and counts it in its memory check.
+ *   pt_variance, pt_noise_stats and pt_iterate_until keep their samples >= 2; both accumulators and everything else are the unflagged
+ *   renderer's bit for bit.  pt_init answers PT_ERR_INVALID, before anything is touched, to the flag without PT_FLAG_MOMENTS (so: with row
+ *   shards, and from pt_group_init).  PT_FLAG_TEMPORAL, PT_FLAG_DISPLAY_FILTER, PT_FLAG_TRACE_AHEAD, direct lighting and a thin lens go with it.
+ * PT_SPATIAL_RADIUS is chosen by the study of tests/test_spatial_var_cpu.py (README, "Spatial variance"). */
+#define PT_SPATIAL_MIN_COUNT 2.0f
+#define PT_SPATIAL_RADIUS 1
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

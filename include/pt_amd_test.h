@@ -170,21 +170,23 @@ int pt_test_bump_normal(const float *height, int w, int h, const int32_t *kind, 
  * ms (or NULL): 1 + levels kernel times by HIP events, k_gbuffer first (0 when the guide buffers were cached), then each level. */
 int pt_test_denoise(int samples, const PtDenoiseParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *ms);
 /* ... and pt_denoise_var with the form of k_atrous_*<AtrousGuided> named, the same four forms; var_host may be NULL; ms as above (on a renderer whose context
- * holds history -- PT_FLAG_TEMPORAL -- k_temporal runs between k_gbuffer and level 0 and belongs to neither time). */
+ * holds history -- PT_FLAG_TEMPORAL -- k_temporal runs between k_gbuffer and level 0 and belongs to neither time; so do the two launches of the
+ * spatial variance estimate for samples 1, which only a PT_FLAG_SPATIAL_VARIANCE renderer accepts). */
 int pt_test_denoise_var(int samples, const PtDenoiseVarParams *p, size_t params_struct_bytes, int form, float *rgb_mean_host, float *var_host, float *ms);
 /* the display path (PT_FLAG_DISPLAY_FILTER, pt_amd.h) of THIS library's renderer -- any PT_FLAG_MOMENTS renderer, the flag itself is not needed
  * -- with the form of k_atrous_*<AtrousGuided> named for every level, the last included: what pt_iterate(..., rgba8_dev) enqueues behind the commit, into
  * rgba8_dev (DEVICE memory, W * H * 4 bytes), on the renderer's stream, without a synchronisation unless ms is given.  form: the four of
  * pt_test_denoise.  fused 1: the last level writes the bytes itself (k_atrous_*<AtrousGuided, false, true, ., true>); 0: it writes packed RGB and
- * k_to_rgba8 converts it -- the same bytes.  samples 1: the plain conversion.  ms (or NULL): 1 + PT_DISPLAY_LEVELS kernel times as
- * pt_test_denoise_var's, the last level's with the k_to_rgba8 launch where fused is 0 (all 0 for samples 1). */
+ * k_to_rgba8 converts it -- the same bytes.  samples 1: the plain conversion -- on a PT_FLAG_SPATIAL_VARIANCE renderer the filter, as for
+ * every other count.  ms (or NULL): 1 + PT_DISPLAY_LEVELS kernel times as pt_test_denoise_var's, the last level's with the k_to_rgba8 launch
+ * where fused is 0 (all 0 for the plain conversion). */
 int pt_test_display(int samples, int form, int fused, void *rgba8_dev, float *ms);
 int pt_test_exp_neg_poly(const float *a, int n, float *out);   /* the filter's range weight, ptd::expNegPoly */
 /* temporal reprojection (pt_amd.h, csrc/pt_temporal.h).  cam16 = the old view's camera as k_temporal takes it, 16 floats: eye (3), pixLenX,
  * pixLenY, halfW, halfH, then the rows r0, r1, r2 of the inverse of [view | -right | -up].
  * pt_test_temporal_camera (host only, no GPU needed): cam16 of a PtCamera, by the function pt_init's capture calls.
  * pt_test_temporal: k_temporal over host arrays of any w x h, no renderer needed -- capture 0: the filter form, out4 = (c, variance), out_n unused
- * (may be NULL); capture 1: out4 = Hc', out_n = Hn'.  The current view: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h), pos_t4 / nrm_id4 its guide
+ * (may be NULL); capture 1: out4 = Hc', out_n = Hn'; capture 2: the moments form, out4 = M, out_n = N (uncapped).  The current view: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h), pos_t4 / nrm_id4 its guide
  * buffers as the device holds them (w * h * 4 each, .w of the second = the bits of the int32 primitive index); the history: hc4, hn, hpos_t4,
  * hnrm_id4 likewise.  ms (or NULL) with reps >= 1: `reps` kernel times by HIP events, after one untimed launch.
  * pt_test_history: the history THIS library's current context holds -- wh2 = its frame size, {0, 0}: none (nothing else is written then); every
@@ -194,6 +196,13 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
                      const float *hc4, const float *hn, const float *hpos_t4, const float *hnrm_id4, const float *cam16, float *out4, float *out_n,
                      int reps, float *ms);
 int pt_test_history(int32_t *wh2, float *hc4, float *hn, float *hpos_t4, float *hnrm_id4, float *cam16);
+/* the spatial variance estimate (pt_amd.h, csrc/pt_spatial_var.h): k_spatial_variance_*<radius> over host arrays of any w x h, no renderer
+ * needed.  radius 1, 2 or 3 (the product holds PT_SPATIAL_RADIUS only); form 0: the plain gather, 1: the LDS tiles -- both give the same bits.
+ * m4 = M (w * h * 4: mean r, g, b, m2), n = N (w * h), pos_t4 / nrm_id4 the guide buffers as the device holds them; sigma_normal, sigma_position
+ * > 0 as pt_denoise_var takes them (+inf: term off).  out4 = (c, variance), w * h * 4.  ms (or NULL) with reps >= 1: `reps` kernel times by HIP
+ * events, after one untimed launch. */
+int pt_test_spatial_variance(int radius, int form, int w, int h, const float *m4, const float *n, const float *pos_t4, const float *nrm_id4,
+                             float sigma_normal, float sigma_position, float *out4, int reps, float *ms);
 /* the noise statistics (pt_amd.h, csrc/pt_noise.h): k_noise_stats -- the kernel pt_noise_stats launches -- over host arrays of any w x h, no
  * renderer needed: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h); out, tile_rel_var_host (or NULL) as pt_noise_stats.  tiles_per_wave: how many
  * tiles a wave of the grid takes, 1..64, 0 = the library's choice -- every value gives the same bits.  ms (or NULL) with

@@ -53,6 +53,9 @@ PT_TEMPORAL_MAX_HISTORY, PT_TEMPORAL_NORMAL_DOT, PT_TEMPORAL_PLANE_FRACTION, PT_
 PT_FLAG_DISPLAY_FILTER = 128
 # the display filter's one setting (include/pt_amd.h): denoise_var's defaults
 PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA_NORMAL, PT_DISPLAY_SIGMA_POSITION = 5, 1, 4.0, 0.35, 2.0
+PT_FLAG_SPATIAL_VARIANCE = 256
+# the spatial variance estimate (include/pt_amd.h): the count below which a pixel takes it, and the radius of its window
+PT_SPATIAL_MIN_COUNT, PT_SPATIAL_RADIUS = 2.0, 1
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -83,7 +86,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
-    "pt_test_display",
+    "pt_test_display", "pt_test_spatial_variance",
 ]
 
 
@@ -253,6 +256,7 @@ def _bind(L, with_tests):
         L.pt_test_temporal.argtypes = [i32, i32, i32, i32] + [vp] * 11 + [i32, vp]
         L.pt_test_history.argtypes = [vp] * 6
         L.pt_test_display.argtypes = [i32, i32, i32, vp, vp]
+        L.pt_test_spatial_variance.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
@@ -439,8 +443,11 @@ _scene = None
 
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
-                  mixture_weighted=False, moments=False, temporal=False, display_filter=False):
+                  mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    spatial_variance: PT_FLAG_SPATIAL_VARIANCE (with moments=True) -- denoise_var / denoise_var_rgba8 accept samples=1: a pixel with fewer than
+    PT_SPATIAL_MIN_COUNT effective samples is filtered under a variance estimated from its neighbours, and with display_filter=True the first
+    displayed frame is filtered too.  From two samples on everything is the unflagged renderer's.
     display_filter: PT_FLAG_DISPLAY_FILTER (moments=True must be given with it: it implies nothing) -- the `pbo` of pathtrace / pathtrace_batch
     and readback_rgba8 receive the bytes of denoise_var_rgba8 with its defaults (PT_DISPLAY_*) instead of the raw accumulator's, made on the
     device behind the commit, on the renderer's stream, without a synchronisation.  Everything else is the unflagged renderer's.
@@ -464,6 +471,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_TEMPORAL
     if display_filter:
         flags |= PT_FLAG_DISPLAY_FILTER
+    if spatial_variance:
+        flags |= PT_FLAG_SPATIAL_VARIANCE
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -846,17 +855,31 @@ def test_temporal_camera(camera):
 def test_temporal(capture, w, h, samples, rgb_sum, lum_sq_sum, pos_t, nrm_id, hc, hn, hpos_t, hnrm_id, cam16, timing_reps=0):
     """k_temporal over host arrays (test library, no renderer): the current view's S (h, w, 3), Q (h, w) and guide buffers pos_t, nrm_id
     ((h, w, 4) float32 each, nrm_id[..., 3] = the bits of the int32 primitive index), the history hc (h, w, 4), hn (h, w) and its guides, the old
-    camera's 16 floats.  capture=False: the filter form, (h * w, 4) = (c, variance); capture=True: (Hc' (h * w, 4), Hn' (h * w,)).
-    timing_reps > 0: also the kernel times in ms."""
+    camera's 16 floats.  capture=False: the filter form, (h * w, 4) = (c, variance); capture=True: (Hc' (h * w, 4), Hn' (h * w,)); capture=2: the
+    moments form, (M (h * w, 4), N (h * w,)) with the count uncapped.  timing_reps > 0: also the kernel times in ms."""
     f = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(w * h * k)
     S, Q, pos, nrm, Hc, Hn, Hpos, Hnrm = f(rgb_sum, 3), f(lum_sq_sum, 1), f(pos_t, 4), f(nrm_id, 4), f(hc, 4), f(hn, 1), f(hpos_t, 4), f(hnrm_id, 4)
     cam = np.ascontiguousarray(cam16, np.float32).reshape(16)
     out, out_n = np.empty((w * h, 4), np.float32), np.empty(w * h, np.float32)
     ms = np.zeros(max(timing_reps, 1), np.float32)
-    _tcheck(test_lib().pt_test_temporal(1 if capture else 0, w, h, samples, _p(S), _p(Q), _p(pos), _p(nrm), _p(Hc), _p(Hn), _p(Hpos), _p(Hnrm), _p(cam),
+    _tcheck(test_lib().pt_test_temporal(int(capture), w, h, samples, _p(S), _p(Q), _p(pos), _p(nrm), _p(Hc), _p(Hn), _p(Hpos), _p(Hnrm), _p(cam),
                                         _p(out), _p(out_n), timing_reps, _p(ms) if timing_reps > 0 else None))
     res = (out, out_n) if capture else out
     return (res, ms) if timing_reps > 0 else res
+
+
+def test_spatial_variance(radius, form, w, h, m4, n, pos_t, nrm_id, sigma_normal=DENOISE_SIGMA_NORMAL, sigma_position=DENOISE_SIGMA_POSITION,
+                          timing_reps=0):
+    """k_spatial_variance_*<radius> over host arrays (test library, no renderer): M (h, w, 4) = (mean r, g, b, m2), N (h, w) the effective sample
+    counts and the guide buffers pos_t, nrm_id ((h, w, 4) each, as test_temporal takes them).  radius 1, 2 or 3; form 0: the gather, 1: the LDS
+    tiles.  Returns (h * w, 4) = (c, variance); timing_reps > 0: also the kernel times in ms."""
+    f = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(w * h * k)
+    M, N, pos, nrm = f(m4, 4), f(n, 1), f(pos_t, 4), f(nrm_id, 4)
+    out = np.empty((w * h, 4), np.float32)
+    ms = np.zeros(max(timing_reps, 1), np.float32)
+    _tcheck(test_lib().pt_test_spatial_variance(radius, form, w, h, _p(M), _p(N), _p(pos), _p(nrm), sigma_normal, sigma_position, _p(out), timing_reps,
+                                                _p(ms) if timing_reps > 0 else None))
+    return (out, ms) if timing_reps > 0 else out
 
 
 def test_history():

@@ -43,6 +43,7 @@
 #include "pt_denoise.h"
 #include "pt_noise.h"
 #include "pt_temporal.h"
+#include "pt_spatial_var.h"
 // The entry points of include/pt_amd_test.h (device primitives one by one, soundness sweeps, the fault-word hook) exist only in
 // the second link target of this source, libpt_amd_test.so (-DPT_TEST_API): the product library exports none of them.
 #ifdef PT_TEST_API
@@ -211,6 +212,7 @@ struct State : PlanScalars {
     DevBuf<float> dnOut;
     DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes, and pt_readback_rgba8's under PT_FLAG_DISPLAY_FILTER
     DevBuf<float> dnVar;            // pt_variance's / pt_denoise_var's variance image
+    DevBuf<float> dnCount;          // PT_FLAG_SPATIAL_VARIANCE: the effective sample counts of a one-sample frame (pt_spatial_var.h); pt_init's
     int dnGuideIter = 0;
     // the noise statistics (pt_noise.h), all allocated on first use: the frame's two result words on the device, the tile map, and -- for
     // pt_iterate_until, whose checks the host reads while the stream runs on -- two copies of the words in page-locked memory, each with the
@@ -860,21 +862,23 @@ TemporalCam temporal_camera(const KParams &k) {
 }
 
 // k_temporal over the renderer and its context's history, on its stream: the blend of `samples` committed iterations with the history -- the
-// halves a live history holds; none: every pixel goes without -- into out (and outN: the capture form); needs the guides (ensure_guides)
-template <bool CAPTURE>
-int temporal_blend(float samples, float4 *out, float *outN) {
+// halves a live history holds; none, or useHistory false: every pixel goes without -- into out (and outN: the capture and the moments form);
+// needs the guides (ensure_guides)
+template <int FORM>
+int temporal_blend(float samples, float4 *out, float *outN, bool useHistory = true) {
     const State &S = R();
     const History &hs = S.hist;
+    const bool live = useHistory && hs.live;
     TemporalArgs T;
     T.accum = S.image; T.moments = S.moments.p;
     T.posT = S.dnPosT.p; T.nrmId = S.dnNrmId.p;
-    T.hc = hs.live ? hs.hc[hs.cur].p : nullptr; T.hn = hs.live ? hs.hn[hs.cur].p : nullptr;
+    T.hc = live ? hs.hc[hs.cur].p : nullptr; T.hn = live ? hs.hn[hs.cur].p : nullptr;
     T.hpos = hs.hpos.p; T.hnrm = hs.hnrm.p;
     T.cam = hs.cam;
     T.W = S.prm.W; T.H = S.prm.H;
     T.samples = samples;
     T.out = out; T.outN = outN;
-    hipLaunchKernelGGL(k_temporal<CAPTURE>, dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
+    hipLaunchKernelGGL(k_temporal<FORM>, dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
     HIPCHECK(hipGetLastError());
     return PT_OK;
 }
@@ -892,7 +896,7 @@ int capture_history() {
     if (!hs.hc[nxt].p) PTCHECK(hs.hc[nxt].alloc(P));
     if (!hs.hn[nxt].p) PTCHECK(hs.hn[nxt].alloc(P));
     // (S.committed, not `iterations`: pt_counters_reset zeroes that one and leaves the accumulators)
-    PTCHECK(temporal_blend<true>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p));
+    PTCHECK(temporal_blend<kTemporalCapture>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p));
     HIPCHECK(hipStreamSynchronize(S.stream));      // (the guides it read are released next)
     hs.hpos = std::move(S.dnPosT);
     hs.hnrm = std::move(S.dnNrmId);
@@ -900,6 +904,47 @@ int capture_history() {
     hs.cam = temporal_camera(S.prm);
     hs.cur = nxt; hs.W = S.prm.W; hs.H = S.prm.H;
     hs.live = true;
+    return PT_OK;
+}
+
+// ---- the spatial variance estimate (pt_spatial_var.h) -------------------------------------------------------------------------------------
+enum { kSpatialGather = 0, kSpatialTiled = 1 };
+// The form the product launches: measured (profiles/spatial_var_cost.txt) -- at 1280 x 720 the LDS tiles take 0.023 ms against the gather's 0.032
+// where every pixel estimates (a renderer's first frame), 0.019 against 0.021 where one pixel in sixteen does (a view with history), both
+// many times the gather's best-to-median spread of 0.0004 ms; at 1920 x 1080 0.043 against 0.064.  The gather stays in the test build alone.
+constexpr int kSpatialForm = kSpatialTiled;
+
+template <int RADIUS>
+const void *spatial_kernel_of(int form) {
+    return form == kSpatialTiled ? reinterpret_cast<const void *>(k_spatial_variance_tiled<RADIUS>)
+                                 : reinterpret_cast<const void *>(k_spatial_variance_gather<RADIUS>);
+}
+
+// (a template, so that the form not taken is not instantiated)
+template <int FORM>
+const void *spatial_product_kernel() {
+    if constexpr (FORM == kSpatialTiled) return reinterpret_cast<const void *>(k_spatial_variance_tiled<PT_SPATIAL_RADIUS>);
+    else return reinterpret_cast<const void *>(k_spatial_variance_gather<PT_SPATIAL_RADIUS>);
+}
+
+// the product instantiates the shipped radius in the shipped form only; the test build every radius in both
+const void *spatial_kernel(int radius, int form) {
+#ifdef PT_TEST_API
+    if (radius == 1) return spatial_kernel_of<1>(form);
+    if (radius == 2) return spatial_kernel_of<2>(form);
+    if (radius == 3) return spatial_kernel_of<3>(form);
+    return nullptr;
+#else
+    if (radius != PT_SPATIAL_RADIUS || form != kSpatialForm) return nullptr;
+    return spatial_product_kernel<kSpatialForm>();
+#endif
+}
+
+int spatial_launch(SpatialArgs &A, int radius, int form, hipStream_t st) {
+    const void *k = spatial_kernel(radius, form);
+    if (!k) return fail(PT_ERR_INVALID, "spatial variance: radius %d in form %d is not in this build", radius, form);
+    void *kargs[] = {&A};
+    HIPCHECK(hipLaunchKernel(k, dim3(atrousGridGather(A.W, A.H)), dim3(kBlock), kargs, 0, st));
     return PT_OK;
 }
 
@@ -920,27 +965,46 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     PTCHECK(moments_refusals(who));
     if (!p || bytes != sizeof(PtDenoiseVarParams))
         return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseVarParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseVarParams));
-    if (samples < 2) return fail(PT_ERR_INVALID, "%s: samples must be >= 2 (a variance needs two)", who);
-    // PT_FLAG_TEMPORAL with history: level 0 reads the blend of the reprojected history with the accumulators (k_temporal<false>)
+    if (R().flags & PT_FLAG_SPATIAL_VARIANCE) {
+        if (samples < 1) return fail(PT_ERR_INVALID, "%s: samples must be >= 1", who);
+    } else if (samples < 2) {
+        return fail(PT_ERR_INVALID, "%s: samples must be >= 2 (a variance needs two)", who);
+    }
+    // PT_FLAG_TEMPORAL with history: level 0 reads the blend of the reprojected history with the accumulators (k_temporal<kTemporalFilter>)
     const History &hist = R().hist;
     const bool temporal = (R().flags & PT_FLAG_TEMPORAL) && hist.live && hist.W == R().prm.W && hist.H == R().prm.H;
+    // PT_FLAG_SPATIAL_VARIANCE: the counts are Nh + samples, so only a one-sample frame holds a pixel below PT_SPATIAL_MIN_COUNT; level 0 then reads
+    // the blend's colour with the variance k_spatial_variance_* gives it (pt_spatial_var.h).  From two samples on: today's launches.
+    const bool spatial = samples < 2;
     AtrousVarArgs A;
     A.moments = R().moments.p;
     A.samplesM1 = (float)(samples - 1);
-    return atrous_run<AtrousGuided>(A, samples, p, p->sigma_lum, form, ms, who, temporal, [&]() -> int {
+    return atrous_run<AtrousGuided>(A, samples, p, p->sigma_lum, form, ms, who, temporal || spatial, [&]() -> int {
         if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc((size_t)R().P));
         A.outVar = wantVar ? R().dnVar.p : nullptr;       // (read by a last level alone)
-        if (!temporal) return PT_OK;
+        if (!temporal && !spatial) return PT_OK;
         if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc((size_t)R().P));
-        return temporal_blend<false>((float)samples, R().dnPing[1].p, nullptr);
+        if (!spatial) return temporal_blend<kTemporalFilter>((float)samples, R().dnPing[1].p, nullptr);
+        // the moments image goes into dnPing[0], which level 0 overwrites only afterwards
+        if (!R().dnPing[0].p) PTCHECK(R().dnPing[0].alloc((size_t)R().P));
+        PTCHECK(temporal_blend<kTemporalMoments>((float)samples, R().dnPing[0].p, R().dnCount.p, temporal));
+        SpatialArgs B;
+        B.m4 = R().dnPing[0].p; B.cnt = R().dnCount.p;
+        B.posT = R().dnPosT.p; B.nrmId = R().dnNrmId.p;
+        B.W = R().prm.W; B.H = R().prm.H;
+        B.invN = 1.0f / (p->sigma_normal * p->sigma_normal);      // (atrous_run's, which has checked the sigmas)
+        B.invP = 1.0f / (p->sigma_position * p->sigma_position);
+        B.out = R().dnPing[1].p;
+        return spatial_launch(B, PT_SPATIAL_RADIUS, kSpatialForm, R().stream);
     }, bytesOut, fused);
 }
 
 // PT_FLAG_DISPLAY_FILTER: the bytes of `samples` committed iterations as the display sees them, into device memory, on the renderer's stream
-// behind everything enqueued: pt_denoise_var_rgba8's with the shipped setting, or -- one sample has no variance -- the plain conversion.
+// behind everything enqueued: pt_denoise_var_rgba8's with the shipped setting, or -- one sample has no variance -- the plain conversion
+// (not under PT_FLAG_SPATIAL_VARIANCE, which estimates one from the neighbours: the first frame is filtered too).
 // pt_init allocated every buffer this touches; nothing here waits for the device.
 int display_bytes(int samples, uchar4 *out, const char *who, int form = kAtrousAuto, bool fused = true, float *ms = nullptr) {
-    if (samples < 2) {
+    if (samples < 2 && !(R().flags & PT_FLAG_SPATIAL_VARIANCE)) {
         hipLaunchKernelGGL(k_to_rgba8, dim3((R().P + kBlock - 1) / kBlock), dim3(kBlock), 0, R().stream, R().image, R().P, samples, out);
         HIPCHECK(hipGetLastError());
         return PT_OK;
@@ -1208,7 +1272,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
                                contribFloats * sizeof(float) + maskWords * sizeof(uint32_t) + S.meshHitWords * sizeof(unsigned long long);
         // ... and PT_FLAG_DISPLAY_FILTER's buffers: the guide buffers, the two float4 images of the levels, the bytes pt_readback_rgba8 copies
         const size_t display = (S.flags & PT_FLAG_DISPLAY_FILTER) ? (size_t)S.P * (4 * sizeof(float4) + sizeof(uchar4)) : 0;
-        const size_t need = perSlot * (size_t)S.nslots + display;
+        // ... and PT_FLAG_SPATIAL_VARIANCE's one image, the counts
+        const size_t spatial = (S.flags & PT_FLAG_SPATIAL_VARIANCE) ? (size_t)S.P * sizeof(float) : 0;
+        const size_t need = perSlot * (size_t)S.nslots + display + spatial;
         size_t freeB = 0, totalB = 0;
         HIPCHECK(hipMemGetInfo(&freeB, &totalB));
         if (need > freeB)
@@ -1221,6 +1287,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         for (auto &ping : S.dnPing) PTCHECK(ping.alloc((size_t)S.P));
         PTCHECK(S.dnRgba.alloc((size_t)S.P));
     }
+    if (S.flags & PT_FLAG_SPATIAL_VARIANCE) PTCHECK(S.dnCount.alloc((size_t)S.P));
     for (int i = 0; i < S.nslots; ++i) {
         Slot &sl = S.slot[i];
         HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));

@@ -244,6 +244,8 @@ int check_scene(const SceneIn &in) {
     }
     if ((o.flags & PT_FLAG_DISPLAY_FILTER) && !(o.flags & PT_FLAG_MOMENTS))
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DISPLAY_FILTER needs PT_FLAG_MOMENTS (the filter is guided by the variance)");
+    if ((o.flags & PT_FLAG_SPATIAL_VARIANCE) && !(o.flags & PT_FLAG_MOMENTS))
+        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_SPATIAL_VARIANCE needs PT_FLAG_MOMENTS (the estimate is made of the second moments)");
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;

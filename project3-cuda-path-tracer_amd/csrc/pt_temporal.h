@@ -1,9 +1,11 @@
 // pt_temporal.h -- temporal reprojection (PT_FLAG_TEMPORAL): the temporal half of SVGF (Schied et al., HPG 2017) for a static scene under a
 // moving pinhole camera.  One kernel, outside the render path like the denoiser's (k_bounce, k_mesh_walk, k_commit and their arguments do not
 // know of it); included by pt_api.hip only.
-//   k_temporal<false>   the FILTER form: per pixel of the new view the count-weighted blend of the reprojected history with the new samples, as
-//                       the (r, g, b, variance) image level 0 of k_atrous_*<AtrousGuided> then reads in place of meanAndVariance(S, Q)
-//   k_temporal<true>    the CAPTURE form: the same blend, stored as the next history (mean colour, mean squared luminance; the capped count)
+//   k_temporal<kTemporalFilter>    the FILTER form: per pixel of the new view the count-weighted blend of the reprojected history with the new samples, as
+//                                  the (r, g, b, variance) image level 0 of k_atrous_*<AtrousGuided> then reads in place of meanAndVariance(S, Q)
+//   k_temporal<kTemporalCapture>   the CAPTURE form: the same blend, stored as the next history (mean colour, mean squared luminance; the capped count)
+//   k_temporal<kTemporalMoments>   the MOMENTS form: the same blend, stored with the count uncapped -- what the spatial variance estimate reads
+//                                  (PT_FLAG_SPATIAL_VARIANCE: pt_spatial_var.h)
 //
 // ---- the kernel, operation by operation (tests/temporal_ref.py restates it in numpy, bit for bit: every fp32 operation below is one IEEE
 // operation, -ffp-contract=off, in the order written; dot = (x + y) + z as ptd::dot) ----
@@ -24,6 +26,7 @@
 //   7           no history: hc = 0, Nh = 0.  tot = Nh + n;  c.k = (hc.k * Nh + S.k) / tot;  m2 = (hc.m2 * Nh + Q) / tot
 //   8  filter   L = atrousLum(c);  dd = m2 - L * L;  dd = dd > 0 ? dd : 0 (a NaN gives 0);  out = (c, dd / (tot - 1))
 //      capture  Hc' = (c, m2);  Hn' = tot < cap ? tot : cap
+//      moments  M = (c, m2);  N = tot
 // Without history step 7 is 0 * 0 + S = S over n and step 8 is meanAndVariance(S, Q) to the bit (sums are never -0: they grow from +0).
 // cap, c_n, c_p, w_min: PT_TEMPORAL_MAX_HISTORY, _NORMAL_DOT, _PLANE_FRACTION, _MIN_WEIGHT of include/pt_amd.h.
 //
@@ -51,11 +54,13 @@ struct TemporalArgs {
     TemporalCam cam;
     int W, H;
     float samples;
-    float4 *out;                      // filter: (c, variance); capture: Hc'
-    float *outN;                      // capture: Hn'
+    float4 *out;                      // filter: (c, variance); capture: Hc'; moments: M
+    float *outN;                      // capture: Hn'; moments: N
 };
 
-template <bool CAPTURE>
+enum { kTemporalFilter = 0, kTemporalCapture = 1, kTemporalMoments = 2 };
+
+template <int FORM>
 __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
     const int npix = A.W * A.H;
     const int pix = blockIdx.x * kBlock + threadIdx.x;
@@ -118,9 +123,12 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
     const float tot = Nh + A.samples;
     const float r = (hcx * Nh + S[0]) / tot, g = (hcy * Nh + S[1]) / tot, b = (hcz * Nh + S[2]) / tot;
     const float m2 = (hcw * Nh + A.moments[pix]) / tot;
-    if (CAPTURE) {
+    if (FORM == kTemporalCapture) {
         A.out[pix] = make_float4(r, g, b, m2);
         A.outN[pix] = tot < cap ? tot : cap;
+    } else if (FORM == kTemporalMoments) {
+        A.out[pix] = make_float4(r, g, b, m2);
+        A.outN[pix] = tot;
     } else {
         const float L = atrousLum(r, g, b);
         float dd = m2 - L * L;

@@ -971,7 +971,7 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
                      const float *hc4, const float *hn, const float *hpos_t4, const float *hnrm_id4, const float *cam16, float *out4, float *out_n,
                      int reps, float *ms) {
     NEED_GPU();
-    if (w < 1 || h < 1 || (long long)w * h > (1ll << 30) || samples < 1 || !rgb_sum || !lum_sq_sum || !pos_t4 || !nrm_id4 || !hc4 || !hn || !hpos_t4 ||
+    if (capture < 0 || capture > 2 || w < 1 || h < 1 || (long long)w * h > (1ll << 30) || samples < 1 || !rgb_sum || !lum_sq_sum || !pos_t4 || !nrm_id4 || !hc4 || !hn || !hpos_t4 ||
         !hnrm_id4 || !cam16 || !out4 || (capture && !out_n) || (ms && reps < 1))
         return fail(PT_ERR_INVALID, "pt_test_temporal: bad argument");
     const size_t P = (size_t)w * h;
@@ -998,8 +998,9 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
     if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
     for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
         if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
-        if (capture) hipLaunchKernelGGL(k_temporal<true>, grid, dim3(kBlock), 0, nullptr, T);
-        else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(kBlock), 0, nullptr, T);
+        if (capture == 2) hipLaunchKernelGGL(k_temporal<kTemporalMoments>, grid, dim3(kBlock), 0, nullptr, T);
+        else if (capture) hipLaunchKernelGGL(k_temporal<kTemporalCapture>, grid, dim3(kBlock), 0, nullptr, T);
+        else hipLaunchKernelGGL(k_temporal<kTemporalFilter>, grid, dim3(kBlock), 0, nullptr, T);
         if (ms && r) {
             HIPCHECK(hipEventRecord(es.ev[1], nullptr));
             HIPCHECK(hipEventSynchronize(es.ev[1]));
@@ -1010,6 +1011,43 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
     if (capture) PTCHECK(download(out_n, outN, P));
+    return PT_OK;
+}
+
+int pt_test_spatial_variance(int radius, int form, int w, int h, const float *m4, const float *n, const float *pos_t4, const float *nrm_id4,
+                             float sigma_normal, float sigma_position, float *out4, int reps, float *ms) {
+    NEED_GPU();
+    if (radius < 1 || radius > 3 || (form != kSpatialGather && form != kSpatialTiled) || w < 1 || h < 1 || (long long)w * h > (1ll << 30) || !m4 || !n ||
+        !pos_t4 || !nrm_id4 || !(sigma_normal > 0.0f) || !(sigma_position > 0.0f) || !out4 || (ms && reps < 1))
+        return fail(PT_ERR_INVALID, "pt_test_spatial_variance: bad argument");
+    const size_t P = (size_t)w * h;
+    DevBuf<float> N;
+    DevBuf<float4> M, pos, nrm, out;
+    PTCHECK(M.upload(reinterpret_cast<const float4 *>(m4), P));
+    PTCHECK(N.upload(n, P));
+    PTCHECK(pos.upload(reinterpret_cast<const float4 *>(pos_t4), P));
+    PTCHECK(nrm.upload(reinterpret_cast<const float4 *>(nrm_id4), P));
+    int rc = out.alloc(P); if (rc) return rc;
+    SpatialArgs A;
+    A.m4 = M.p; A.cnt = N.p; A.posT = pos.p; A.nrmId = nrm.p;
+    A.W = w; A.H = h;
+    A.invN = 1.0f / (sigma_normal * sigma_normal);
+    A.invP = 1.0f / (sigma_position * sigma_position);
+    A.out = out.p;
+    EventSet es;
+    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
+        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        PTCHECK(spatial_launch(A, radius, form, nullptr));
+        if (ms && r) {
+            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+            HIPCHECK(hipEventSynchronize(es.ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

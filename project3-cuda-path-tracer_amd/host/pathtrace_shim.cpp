@@ -17,6 +17,7 @@ static PtGroup *group = NULL;
 static float extraLens = 0.0f, extraFocal = 0.0f;   // README extras (pathtraceExtras), off = the reference's renderer
 static bool extraDirect = false;
 static bool extraMoments = false;                   // pathtraceMoments: PT_FLAG_MOMENTS for the next pathtraceInit
+static bool extraSpatial = false;                   // pathtraceSpatialVariance: PT_FLAG_MOMENTS | PT_FLAG_SPATIAL_VARIANCE for the next pathtraceInit
 static bool extraDisplay = false;                   // pathtraceDisplayFilter: PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER for the next pathtraceInit
 
 static void checkPtError(int status, const char *msg) {
@@ -41,6 +42,11 @@ void pathtraceInit(Scene *scene) {
     bool display = extraDisplay;
     if (const char *e = getenv("PT_AMD_DISPLAY_FILTER")) display = display || atoi(e) != 0;
     if (display) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER;
+    // PT_AMD_SPATIAL_VARIANCE=1 (or pathtraceSpatialVariance): a pixel with fewer than two samples is filtered under a variance estimated from its
+    // neighbours -- with the display filter the `pbo` of the FIRST pathtrace call after an Init is filtered too (the frame a camera drag shows).
+    bool spatial = extraSpatial;
+    if (const char *e = getenv("PT_AMD_SPATIAL_VARIANCE")) spatial = spatial || atoi(e) != 0;
+    if (spatial) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_SPATIAL_VARIANCE;
     // The reference's host calls pathtrace(pbo, frame, iter) once per iteration with iter = 1, 2, 3, ... (src/main.cpp:97-103):
     // the library traces such a sequence in wavefront batches AHEAD of the calls (PT_FLAG_TRACE_AHEAD; same image after every
     // call, bit for bit), so a call costs a commit instead of eight small dependent launches.  A camera move goes through
@@ -121,6 +127,11 @@ void pathtraceInit(Scene *scene) {
 #endif
     int members = 1;
     if (const char *e = getenv("PT_AMD_DEVICES")) members = atoi(e);
+    if (members >= 2 && spatial) {
+        fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: the spatial variance estimate (PT_AMD_SPATIAL_VARIANCE, pathtraceSpatialVariance) "
+                        "is not for PT_AMD_DEVICES: a group keeps no second moments\n");
+        exit(EXIT_FAILURE);
+    }
     if (members >= 2 && display) {
         fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: the display filter (PT_AMD_DISPLAY_FILTER, pathtraceDisplayFilter) is not for "
                         "PT_AMD_DEVICES: a group renders headless\n");
@@ -185,6 +196,11 @@ void pathtraceMoments(bool on) { extraMoments = on; }
 // iteration on receives the bytes of the variance-guided filter (include/pt_amd.h: "display filter"), made on the device behind the commit.
 // The environment variable PT_AMD_DISPLAY_FILTER=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
 void pathtraceDisplayFilter(bool on) { extraDisplay = on; }
+
+// ... nor this one: the next pathtraceInit sets PT_FLAG_MOMENTS | PT_FLAG_SPATIAL_VARIANCE (include/pt_amd.h: "spatial variance"): pt_denoise_var accepts
+// one sample, and with the display filter the first frame's `pbo` is filtered as well.  The environment variable PT_AMD_SPATIAL_VARIANCE=1 does the
+// same for a host that cannot call it.  Not with PT_AMD_DEVICES.
+void pathtraceSpatialVariance(bool on) { extraSpatial = on; }
 
 void pathtraceFree() {
     if (group) {
