@@ -99,6 +99,22 @@ int pt_test_camera_resolved(const PtCamera *cam, const PtGeom *geoms, int ngeoms
  * footprint -- the resolved wave's box test (pt_device.h: boxFaceHit) against boxIntersectionTest.  counts = {rays, rays on which
  * (t > 0, outside, face, P bit for bit) differ -- must be 0 --, resolved pixels}. */
 int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t seed, uint64_t counts[3]);
+/* The later bounces' counterpart (pt_device.h: wallFaceCertificate, boxFacePoint; pt_host_scene.h: choose_wall_faces).
+ * pt_test_wall_faces (host only): what pt_init would plan for the scene, per primitive -- face[i] = the inner face 2 axis + (side > 0) of a
+ * wall that has one, else -1; beyond[i] = the least side * o_axis (object space) the certificate is issued from, else 0; ngeoms entries
+ * each.  PT_AMD_NO_WALL_RESOLVE=1 (read by the plan, tests only): every face -1.
+ * pt_test_wall_face_sweep: `geoms` = cubes, the walls of a room as pt_init chooses and numbers them; `rays` pseudo-random rays from the
+ * room at the walls' inner faces -- dense at their edges and corners and in grazes, a few with NaN, inf and zero components.  counts =
+ * {rays the certificate accepts; of those, rays on which boxFacePoint and boxIntersectionTest<true, false>(., false, true) differ in
+ * (return value > 0, outside, face, P bit for bit) -- must be 0; rays it rejects although the box test hits from outside through the
+ * face; rays it rejects in all}.
+ * pt_test_wall_resolve_tally: the test library's own tally of its renderer's later bounces since the last call, per wave and tile --
+ * {wave-tiles that hold a path; of them one-wall tiles whose wall has a face; of those the waves that took the face; lanes whose
+ * certificate failed} -- read and cleared.  The product library keeps no such tally. */
+int pt_test_wall_faces(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
+                       int32_t *face, float *beyond);
+int pt_test_wall_face_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t counts[4]);
+int pt_test_wall_resolve_tally(uint64_t counts[4]);
 /* Triangle meshes.  pt_test_mesh_intersect: `n` rays against ONE mesh geom on the GPU, through the hierarchy (flat = 0) or a
  * plain list of its triangles (flat = 1: the brute-force rule); outputs keep their input values on a miss; culled[i] = 1 when
  * the bounding-ball test (certainMiss) rejected the ray -- t[i] is NaN if the full test hits nevertheless (must not happen).

@@ -81,7 +81,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_slab_quotients", "pt_test_slab_quotients_sweep", "pt_test_box_fast_sweep", "pt_test_sphere_cull_sweep", "pt_test_unscaled_sqrt_sweep",
     "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_intersect2", "pt_test_mesh_bvh",
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
-    "pt_test_camera_resolved", "pt_test_face_hit_sweep",
+    "pt_test_camera_resolved", "pt_test_face_hit_sweep", "pt_test_wall_faces", "pt_test_wall_face_sweep", "pt_test_wall_resolve_tally",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
@@ -240,6 +240,9 @@ def _bind(L, with_tests):
         L.pt_test_camera_list.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.pt_test_camera_resolved.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
         L.pt_test_face_hit_sweep.argtypes = [vp, vp, i32, i32, C.c_uint64, u64p]
+        L.pt_test_wall_faces.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(PtOptions), vp, vp]
+        L.pt_test_wall_face_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p]
+        L.pt_test_wall_resolve_tally.argtypes = [u64p]
         L.pt_test_camera_cull_margin.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_double), u64p]
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
@@ -1308,6 +1311,35 @@ def camera_resolved(camera, geoms, shard_rank=0, shard_count=1):
 def test_face_hit_sweep(camera, geoms, samples=64, seed=1):
     """Device sweep of the resolved waves' box test against the full one.  Returns (rays, mismatches, resolved pixels)."""
     return _u64_outs(test_lib().pt_test_face_hit_sweep, (3,), *_camera_args(camera, geoms), samples, seed)
+
+
+def wall_faces(scene, traceDepth=None, **options):
+    """pt_test_wall_faces: the inner face pt_init would name per primitive of the scene (2 axis + (side > 0), -1: none) and the clearance
+    that goes with it, on the host alone (no GPU).  options: PtOptions fields by name, as for scene_plan."""
+    T = test_lib()
+    set_meshes(getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None), L=T)
+    set_textures(*_scene_textures(scene), L=T)
+    set_bump_maps(*_scene_bumps(scene), L=T)
+    opt = PtOptions(shard_count=1, device=-1)
+    for name, value in options.items():
+        setattr(opt, name, value)
+    geoms, mats, cam = np.ascontiguousarray(scene.geoms), np.ascontiguousarray(scene.materials), np.ascontiguousarray(scene.camera)
+    face, beyond = np.full(len(geoms), -2, np.int32), np.zeros(len(geoms), np.float32)
+    _check(T.pt_test_wall_faces(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), scene.traceDepth if traceDepth is None else traceDepth,
+                                C.byref(opt), _p(face), _p(beyond)), T)
+    return face, beyond
+
+
+def test_wall_face_sweep(geoms, seed, rays):
+    """Device sweep of the later bounces' face certificate and its resolved box test against the box test, on the walls among `geoms`
+    (cubes).  Returns (accepted, mismatching, rejected although the box test hits through the face, rejected in all)."""
+    return _u64_outs(test_lib().pt_test_wall_face_sweep, (4,), *_geoms_args(geoms), seed, rays)
+
+
+def wall_resolve_tally():
+    """The test library's tally of its renderer's later bounces since the last call (read and cleared): (wave-tiles that hold a path, of
+    them one-wall tiles whose wall has a face, of those the waves that took the face, lanes whose certificate failed)."""
+    return _u64_outs(test_lib().pt_test_wall_resolve_tally, (4,))
 
 
 def test_camera_cull_sweep(camera, geoms, samples=1):

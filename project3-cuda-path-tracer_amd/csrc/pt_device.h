@@ -30,6 +30,22 @@ __device__ __forceinline__ void censusLeave() {}
 #define PT_EXP_EXTRA_BARRIER()
 #endif
 
+// The test library's tally of the later bounces' resolved one-wall tiles (-DPT_TEST_API builds only, read and cleared by
+// pt_test_wall_resolve_tally; the product's kernels count nothing and PtCounters does not know of it).  Per wave and tile:
+// [0] later wave-tiles that hold a path, [1] of them one-wall tiles whose wall has a face (every lane runs the certificate), [2] of those
+// the waves that took the face (no lane failed), [3] the lanes that failed.
+#ifdef PT_TEST_API
+namespace ptd {
+__device__ unsigned long long g_wallResolve[4];
+__device__ __forceinline__ void tallyWallResolve(int k, unsigned long long n) {
+    if (n != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_wallResolve[k], n);
+}
+}  // namespace ptd
+#define PT_TALLY_WALL_RESOLVE(k, n) ptd::tallyWallResolve(k, n)
+#else
+#define PT_TALLY_WALL_RESOLVE(k, n)
+#endif
+
 namespace ptd {
 
 struct F3 {
@@ -575,10 +591,16 @@ __device__ __forceinline__ float boxIntersectionTest(const GD &g, F3 ro, F3 rd, 
 // (the numerator as boxSlabsFastFinish and the reference's loop form it: +-.5 - o), the hit point.  No slab decision, no per-lane axis
 // select (`face` is wave-uniform), no distance (it is compared with nothing: the pixel's signature is g alone).  The caller supplies
 // outside = true and the face.  tests/test_gpu_camera_resolve.py sweeps it against boxIntersectionTest bit for bit.
+// boxFacePoint: the same from the object-space origin and the unnormalised object-space direction -- the camera's (boxFaceHit), or a later
+// bounce's own (k_bounce's resolved one-wall tiles: wallFaceCertificate below).
+template <typename GD>
+__device__ __forceinline__ F3 boxFacePoint(const GD &g, int face, F3 qo, F3 qdu);
 template <typename GD>
 __device__ __forceinline__ F3 boxFaceHit(const GD &g, int face, F3 rd) {
-    const F3 qo = f3(g.camObj[0], g.camObj[1], g.camObj[2]);
-    const F3 qdu = mulMV0(g.inv, g.invZ, rd);
+    return boxFacePoint(g, face, f3(g.camObj[0], g.camObj[1], g.camObj[2]), mulMV0(g.inv, g.invZ, rd));
+}
+template <typename GD>
+__device__ __forceinline__ F3 boxFacePoint(const GD &g, int face, F3 qo, F3 qdu) {
     const float s = sqrtUnscaled(dot(qdu, qdu));
     const float inv = divUnscaled(1.0f, s, __builtin_amdgcn_rcpf(s));
     const F3 qd = qdu * inv;
@@ -587,6 +609,70 @@ __device__ __forceinline__ F3 boxFaceHit(const GD &g, int face, F3 rd) {
     const float aK = ((face & 1) ? 0.5f : -0.5f) - oK;
     const float tmin = divUnscaled(aK, dK, __builtin_amdgcn_rcpf(dK));
     return mulMV(g.xf, getPointOnRay(qo, qd, tmin), 1.0f);
+}
+
+// THE FACE CERTIFICATE of a later bounce's ray against the ONE wall its tile lists (k_bounce: a class without candidates whose list is
+// one wall).  The scatter that queued the ray excluded every other wall and ended what leaves through the room's open side, so nearly
+// every lane of such a tile hits the wall's inner face from the room -- and still ran the whole box test to learn which of six slab
+// quotients is the answer.  pt_init names the face per wall (pt_host_scene.h: wall_inner_face; `face` = 2 K + (s > 0), wave-uniform) and
+// the least s o_K it is certified from (`beyond`); this function says per lane, on the operands the box test forms anyway -- qo =
+// mulMV(inv, origin, 1), qdu = mulMV0(inv, invZ, direction), the reference's q.origin and its q.direction before normalize -- that the
+// reference's loop (src/intersections.h:51-77) on this ray returns a hit, from outside, through exactly that face, with every operand of
+// boxFacePoint inside the ranges of sqrtUnscaled / divUnscaled.  One v_rcp_f32, no correctly rounded division, no normalize.
+//
+// It accepts when, with o = qo, u = qdu, (I, J) the two other axes, rho = 2^-12:
+//   (i)   2^-80 <= |u|^2 < 2^80 (the fast path's own test: NaN, inf and 0 fail), every |u_i| >= 2^-39 (|u_x| + |u_y| + |u_z|),
+//         |o_I| + |o_J| <= 8 and |o_K| <= 2^19 (NaN fails each);
+//   (ii)  s o_K >= beyond (>= 1/2 + 2e-4: the origin lies beyond the face's plane) and s u_K < 0 (the ray approaches it);
+//   (iii) at t- = (1 - rho) t and t+ = (1 + rho) t, t = (s/2 - o_K) * v_rcp_f32(u_K), the points o + t-+ u have
+//         |coordinate| <= 1/2 - 2^-16 on both other axes (fused multiply-adds; a NaN fails).
+// Why that is enough.  Everything is a statement about the SAME float32 numbers o and u the reference's loop starts from; only their
+// evaluation differs.  Let t* = (s/2 - o_K) / u_K > 0 exactly (ii).  The computed t is t* (1 + e), |e| < 2^-22 (the subtraction, the
+// reciprocal -- one ulp --, the product), and each computed point is off the exact o + (1 -+ rho) t u by less than 2^-21 (|o_j| + 1) <
+// 2^-17 (i): with the inset 2^-16 the EXACT points at (1 - rho) t* (1 + e) and (1 + rho) t* (1 + e) lie strictly inside the slabs of I
+// and J.  A slab is convex: on axis j (u_j != 0 by (i)) the exact entry parameter lies below (1 - rho)(1 + e) t* and the exact exit
+// parameter above (1 + rho)(1 + e) t*.  The loop works with the unit direction qd = u / |u| (1 + d_i), |d_i| < 2^-22, and forms every
+// quotient from a numerator RN(+-1/2 - o_j) and one correctly rounded division: each of its six parameters is the exact one times |u|
+// up to a RELATIVE 2^-21 (no underflow: numerators are 0 or >= 2^-25, quotients below 2^61 < 1e38, the loop's initial bounds).  So
+//     ta_j <= (1 + 2^-21)(1 - rho)(1 + e) t* |u|  <  (1 - 2^-21) t* |u| <= ta_K  <  tb_j      (j = I, J; rho = 2^-12 >> 2^-20)
+// with ta_K = RN(RN(s/2 - o_K) / qd_K) > 0 the near parameter of axis K -- near because the origin is beyond the face and approaches
+// it: both of K's parameters are positive and the face's is the smaller; its slab normal is n_K = -sign(qd_K) = s, face 2 K + (s > 0);
+// K's far parameter is larger still (the two numerators differ by 1).  Hence tmin = ta_K STRICTLY above the other axes' entries -- no
+// tie, so the order in which the loop visits the axes (first axis wins a tie) does not matter --, tmax = the least exit > tmin > 0:
+// `tmax >= tmin && tmax > 0` holds, `tmin <= 0` does not: a hit, from outside, through (K, s), tmin = RN((s/2 - o_K) / qd_K).
+// The ranges: |u|^2 is inside sqrtUnscaled's and the fast path's [2^-80, 2^80), its root inside divUnscaled's exhaustively tested
+// [2^-40, 2^40]; |qd_K| >= 2^-39 / (1 + 2^-21) > 2^-40 (|u|_1 >= |u|_2) and 2e-4 <= |s/2 - o_K| <= 2^19 + 1/2 are inside the range on
+// which divUnscaled equals IEEE division (tests/test_gpu_parity.py).  So boxFacePoint's one quotient is bit for bit the reference's tmin
+// -- whether boxSlabsFastDecide or boxSlabsExact would have got there -- and P follows by the same operations.
+// The hit's distance is positive, which is all a one-wall tile asks of it: the point lies (tmin - 1e-4) object units along the unit
+// direction from the origin, tmin >= s o_K - 1/2 >= beyond - 1/2, and pt_init chooses `beyond` so that this is clear of the rounding of
+// the three transforms in world space (wall_inner_face).
+// tests/test_wall_face_cpu.py restates this and the loop in numpy float32; tests/test_gpu_wall_face.py sweeps boxFacePoint against
+// boxIntersectionTest bit for bit on the rays this accepts.
+constexpr float kWallFaceRho = 0x1p-12f, kWallFaceInset = 0x1p-16f, kWallFaceOtherMax = 8.0f, kWallFaceOriginMax = 0x1p+19f, kWallFaceMinShare = 0x1p-39f;
+__device__ __forceinline__ bool wallFaceCertificate(F3 qo, F3 qdu, int face, float beyond) {
+    const int K = face >> 1;                                              // (wave-uniform)
+    const float s = (face & 1) ? 1.0f : -1.0f;
+    const float oK = K == 0 ? qo.x : (K == 1 ? qo.y : qo.z), uK = K == 0 ? qdu.x : (K == 1 ? qdu.y : qdu.z);
+    const float oI = K == 0 ? qo.y : qo.x, uI = K == 0 ? qdu.y : qdu.x;
+    const float oJ = K == 2 ? qo.y : qo.z, uJ = K == 2 ? qdu.y : qdu.z;
+    const float x = dot(qdu, qdu);
+    bool ok = (__float_as_uint(x) - 0x17800000u) < 0x50000000u;            // 2^-80 <= x < 2^80 (NaN, inf, 0, negative: no)
+    const float l1 = (__builtin_fabsf(qdu.x) + __builtin_fabsf(qdu.y)) + __builtin_fabsf(qdu.z);
+    ok &= __builtin_fminf(__builtin_fminf(__builtin_fabsf(qdu.x), __builtin_fabsf(qdu.y)), __builtin_fabsf(qdu.z)) >= kWallFaceMinShare * l1;
+    ok &= __builtin_fabsf(oI) + __builtin_fabsf(oJ) <= kWallFaceOtherMax;  // (NaN fails)
+    ok &= __builtin_fabsf(oK) <= kWallFaceOriginMax;
+    ok &= s * oK >= beyond;
+    ok &= s * uK < 0.0f;
+    const float a = 0.5f * s - oK;                                        // (= +-.5 - o_K, the numerator as the loop forms it)
+    const float t = a * __builtin_amdgcn_rcpf(uK);
+    const float tm = t * (1.0f - kWallFaceRho), tp = t * (1.0f + kWallFaceRho);
+    constexpr float kIn = 0.5f - kWallFaceInset;
+    ok &= __builtin_fabsf(__builtin_fmaf(tm, uI, oI)) <= kIn;
+    ok &= __builtin_fabsf(__builtin_fmaf(tp, uI, oI)) <= kIn;
+    ok &= __builtin_fabsf(__builtin_fmaf(tm, uJ, oJ)) <= kIn;
+    ok &= __builtin_fabsf(__builtin_fmaf(tp, uJ, oJ)) <= kIn;
+    return ok;
 }
 
 // Certain miss of a primitive, decided in WORLD space against its bounding ball for ~20 instructions.  Not an
@@ -664,7 +750,10 @@ __device__ __forceinline__ float sphereHalfLineExcessScaled(F3 centre, F3 org, F
 struct WallBox {
     float lo[3];
     float hi[3];
-    float pad[2];
+    // the wall's inner face, 2 K + (s > 0), for wallFaceCertificate -- or -1 -- and the least s o_K the certificate is issued from (pt_init:
+    // wall_inner_face; they ride in the box's padding, so the wall table is still one upload of 32 bytes per wall)
+    int face;
+    float beyond;
 };
 static_assert(sizeof(WallBox) == 32, "one s_load_dwordx8");
 template <typename WB>

@@ -150,6 +150,7 @@ double wall_box(const PtGeom &g, WallBox &w, double *omax = nullptr) {
     const double delta = 4e-5 * S_;
     if (omax) *omax = 5.0 * S_ - big;
     memset(&w, 0, sizeof w);
+    w.face = -1;                            // (no inner face: choose_wall_faces names one)
     for (int r = 0; r < 3; ++r) {
         w.lo[r] = std::nextafter((float)(lo[r] - delta), -INFINITY);
         w.hi[r] = std::nextafter((float)(hi[r] + delta), INFINITY);
@@ -500,6 +501,74 @@ void choose_walls(const PtGeom *geoms, int ngeoms, const std::vector<GeomDev> &h
     for (int a = 0; a < 3; ++a) {       // rounded outwards
         k.outerLo[a] = std::nextafter((float)lo[a], -INFINITY);
         k.outerHi[a] = std::nextafter((float)hi[a], INFINITY);
+    }
+}
+
+// The INNER FACE of every wall, for the later bounces' face certificate (ptd::wallFaceCertificate, where the argument is written out): the
+// face of the wall's cube that looks at the middle C of `outer` -- the one a ray from the room enters the wall through --, as
+// 2 K + (s > 0), and `beyond`, the least s o_K (object space) from which the certificate is issued.  Which face is named decides nothing
+// about results: the certificate tests every ray against the face it is given.  What the host owes it is `beyond`, which keeps the hit's
+// distance positive in the kernel's float32:
+//     beyond = 1/2 + 2e-4 + 2^-18 (1 + wallOMax + |translation|_1 + |transform|_F) / smin(transform).
+// The hit point lies tmin - 1e-4 >= beyond - 1/2 - 1e-4 object units along the unit object-space direction from the origin, i.e. at least
+// smin (beyond - 1/2 - 1e-4) world units away, while the three transforms between the world origin and the world hit point -- origin to
+// object space, the point along the ray, the point back to the world: sums of four products of magnitude at most |o|_1 + |translation|_1
+// and 1.5 |transform|_F + |translation|_1, origins within wallOMax -- move them by less than 2^-20 (1 + wallOMax + |translation|_1 +
+// |transform|_F) together: a quarter of the room that is left.  smin >= |det| / |transform|_F^2.
+// A wall whose data cannot be bounded that way (a non-finite entry, a singular transform), or none of whose faces clearly looks at C,
+// gets -1: its tiles run the box test.  `off` (PT_AMD_NO_WALL_RESOLVE, tests only): every wall -1.
+void choose_wall_faces(const PtGeom *geoms, const KParams &k, const std::vector<int> &wallGeom, bool off, std::vector<WallBox> &hw) {
+    for (WallBox &b : hw) { b.face = -1; b.beyond = 0.0f; }
+    if (off) return;
+    double C[3], diag = 0;
+    for (int a = 0; a < 3; ++a) {
+        C[a] = 0.5 * ((double)k.outerLo[a] + (double)k.outerHi[a]);
+        diag += ((double)k.outerHi[a] - (double)k.outerLo[a]) * ((double)k.outerHi[a] - (double)k.outerLo[a]);
+    }
+    diag = std::sqrt(diag);
+    if (!std::isfinite(diag)) return;
+    for (size_t w = 0; w < wallGeom.size() && w < hw.size(); ++w) {
+        const PtGeom &g = geoms[wallGeom[w]];
+        double T2 = 0, l1t = 0;
+        for (int r = 0; r < 3; ++r) {
+            l1t += std::fabs((double)g.transform[12 + r]);
+            for (int j = 0; j < 3; ++j) T2 += (double)g.transform[j * 4 + r] * (double)g.transform[j * 4 + r];
+        }
+        const double detT = (double)g.transform[0] * ((double)g.transform[5] * g.transform[10] - (double)g.transform[9] * g.transform[6]) -
+                            (double)g.transform[4] * ((double)g.transform[1] * g.transform[10] - (double)g.transform[9] * g.transform[2]) +
+                            (double)g.transform[8] * ((double)g.transform[1] * g.transform[6] - (double)g.transform[5] * g.transform[2]);
+        if (!std::isfinite(T2) || !std::isfinite(detT) || !std::isfinite(l1t) || !(T2 > 0) || !(std::fabs(detT) > 0)) continue;
+        const double smin = std::fabs(detT) / T2;
+        const double beyond = 0.5 + 2e-4 + 0x1p-18 * (1.0 + (double)k.wallOMax + l1t + std::sqrt(T2)) / smin;
+        if (!std::isfinite(beyond) || !(beyond <= 0x1p+18)) continue;
+        double corner[8][3];
+        bool fin = true;
+        for (int q = 0; q < 8; ++q) {
+            const double o[3] = {(q & 1) ? 0.5 : -0.5, (q & 2) ? 0.5 : -0.5, (q & 4) ? 0.5 : -0.5};
+            for (int r = 0; r < 3; ++r) {
+                corner[q][r] = (double)g.transform[0 + r] * o[0] + (double)g.transform[4 + r] * o[1] + (double)g.transform[8 + r] * o[2] + (double)g.transform[12 + r];
+                fin = fin && std::isfinite(corner[q][r]);
+            }
+        }
+        if (!fin) continue;
+        double bestGap = 1e-3 * diag;           // (C clearly on the far side of the face, or no face)
+        int best = -1;
+        for (int a = 0; a < 3; ++a)
+            for (int sgn = -1; sgn <= 1; sgn += 2) {
+                // the outward normal of face (a, sgn): sgn x row a of the inverse transform -- C must lie beyond every corner along it
+                double nn[3] = {sgn * (double)g.inverseTransform[0 + a], sgn * (double)g.inverseTransform[4 + a], sgn * (double)g.inverseTransform[8 + a]};
+                const double len = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);
+                if (!(len > 0) || !std::isfinite(len)) continue;
+                for (double &v : nn) v /= len;
+                double th = -INFINITY;
+                for (int q = 0; q < 8; ++q) th = std::max(th, nn[0] * corner[q][0] + nn[1] * corner[q][1] + nn[2] * corner[q][2]);
+                const double gap = (nn[0] * C[0] + nn[1] * C[1] + nn[2] * C[2]) - th;
+                if (gap > bestGap && std::isfinite(th)) { bestGap = gap; best = 2 * a + (sgn > 0 ? 1 : 0); }
+            }
+        if (best < 0) continue;
+        const float bf = (float)beyond;
+        hw[w].face = best;
+        hw[w].beyond = (double)bf < beyond ? std::nextafter(bf, INFINITY) : bf;      // (upwards: the certificate may only get rarer)
     }
 }
 

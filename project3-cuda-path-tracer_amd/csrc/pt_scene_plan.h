@@ -511,6 +511,9 @@ void plan_walls(const SceneIn &in, ScenePlan &p) {
     p.hw.resize(kWallMax);
     std::vector<int> wallGeom;
     choose_walls(in.geoms, in.ngeoms, hg, k, p.hw, wallGeom);
+    // the walls' inner faces, in the wall table's own entries: a later tile whose list is one wall takes the face without the slab test
+    // where every lane's certificate holds (k_bounce; PT_AMD_NO_WALL_RESOLVE, tests only: every wall -1)
+    choose_wall_faces(in.geoms, k, wallGeom, env_flag("PT_AMD_NO_WALL_RESOLVE"), p.hw);
     for (int w = 0; w < k.nWalls; ++w) {
         hg[wallGeom[w]].flags |= (w + 1) << 2;
         hg[wallGeom[w]].cullFlags |= (w + 1) << 2;

@@ -804,6 +804,79 @@ int pt_test_wall_plane_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int
     return cnt.read({certified, violations, single});
 }
 
+// (host only) the inner face pt_init names per primitive of the scene -- 2 K + (s > 0) for a wall that has one, else -1 -- and the clearance
+// that goes with it: plan_scene, no device (PT_AMD_NO_WALL_RESOLVE: every face -1)
+int pt_test_wall_faces(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
+                       int32_t *face, float *beyond) {
+    if (!face || !beyond) return fail(PT_ERR_INVALID, "pt_test_wall_faces: bad argument");
+    ScenePlan p;
+    PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings}, p));
+    for (int i = 0; i < ngeoms; ++i) {
+        const int w = (p.hg[(size_t)i].flags >> 2) & 7;                  // 1 + index among the walls, 0: not one
+        face[i] = w != 0 ? p.hw[(size_t)w - 1].face : -1;
+        beyond[i] = w != 0 ? p.hw[(size_t)w - 1].beyond : 0.0f;
+    }
+    return PT_OK;
+}
+
+int pt_test_wall_face_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t counts[4]) {
+    NEED_GPU();
+    if (!geoms || ngeoms < 1 || !counts || rays < 0) return fail(PT_ERR_INVALID, "pt_test_wall_face_sweep: bad argument");
+    std::vector<GeomDev> hg;
+    KParams k;
+    std::vector<WallBox> hw;
+    std::vector<int> wallGeom;
+    PTCHECK(test_choose_walls(geoms, ngeoms, "pt_test_wall_face_sweep", hg, k, hw, wallGeom));
+    choose_wall_faces(geoms, k, wallGeom, false, hw);
+    for (int q = 0; q < 4; ++q) counts[q] = 0;
+    std::vector<int> faced;
+    for (int w = 0; w < k.nWalls; ++w)
+        if (hw[(size_t)w].face >= 0) faced.push_back(w);
+    if (faced.empty()) return PT_OK;
+    // the room: per axis the innermost planes of the walls' (inflated) boxes on either side of the middle of the box around them all
+    F3 lo = F3{k.outerLo[0], k.outerLo[1], k.outerLo[2]}, hi = F3{k.outerHi[0], k.outerHi[1], k.outerHi[2]};
+    {
+        float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
+        for (int a = 0; a < 3; ++a) {
+            const float mid = 0.5f * (l[a] + h[a]);
+            float nl = l[a], nh = h[a];
+            for (int w = 0; w < k.nWalls; ++w) {
+                if (hw[(size_t)w].hi[a] < mid) nl = std::max(nl, hw[(size_t)w].hi[a]);
+                if (hw[(size_t)w].lo[a] > mid) nh = std::min(nh, hw[(size_t)w].lo[a]);
+            }
+            l[a] = nl; h[a] = nh;
+        }
+        lo = F3{l[0], l[1], l[2]};
+        hi = F3{h[0], h[1], h[2]};
+    }
+    std::vector<GeomDev> wg((size_t)k.nWalls);
+    for (int w = 0; w < k.nWalls; ++w) wg[(size_t)w] = hg[(size_t)wallGeom[(size_t)w]];
+    DevBuf<GeomDev> dg;
+    DevBuf<WallBox> dw;
+    DevBuf<int> df;
+    Counters<4> cnt;
+    PTCHECK(dg.upload(wg));
+    PTCHECK(dw.upload(hw.data(), (size_t)k.nWalls));
+    PTCHECK(df.upload(faced));
+    PTCHECK(cnt.zero());
+    const int per_thread = 64;
+    PTCHECK(launch_wait(k_sweep_wall_face, sweep_grid(rays, per_thread, kTestThreads, 1 << 20), 0, dg.p, dw.p, df.p, (int)faced.size(), lo, hi, seed, per_thread,
+                        cnt.at(0)));
+    return cnt.read({counts, counts + 1, counts + 2, counts + 3});
+}
+
+// the test library's tally of the later bounces' resolved one-wall tiles (ptd::g_wallResolve), read and cleared
+int pt_test_wall_resolve_tally(uint64_t counts[4]) {
+    NEED_GPU();
+    if (!counts) return fail(PT_ERR_INVALID, "pt_test_wall_resolve_tally: bad argument");
+    unsigned long long h[4], z[4] = {0, 0, 0, 0};
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(ptd::g_wallResolve), sizeof h));
+    HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(ptd::g_wallResolve), z, sizeof z));
+    for (int q = 0; q < 4; ++q) counts[q] = h[q];
+    return PT_OK;
+}
+
 int pt_test_box_fast_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t counts[4], uint64_t div_mismatches[2]) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !counts || !div_mismatches || rays < 0) return fail(PT_ERR_INVALID, "pt_test_box_fast_sweep: bad argument");

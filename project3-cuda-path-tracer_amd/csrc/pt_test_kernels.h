@@ -764,6 +764,81 @@ __global__ void k_sweep_face_hit(const GeomDev *geoms, const float *cam16, const
     sweepFlush(&cnt[0], nr);
     sweepFlush(&cnt[1], bad);
 }
+// wallFaceCertificate + boxFacePoint (a later bounce's resolved one-wall tile) next to boxIntersectionTest<true, false>(., false, true), the test
+// such a tile runs otherwise, on the rays of tests/wall_face_ref.py's families, generated here: wall w = the ray's number modulo the walls
+// (`wallGeoms[w]` = the cube that is wall w, `walls[w]` its face and clearance), origins in the room [roomLo, roomHi] shrunk by 1e-3 -- a third of
+// them on the shrunk room's border, 1e-3 off a wall's inner face --, directions at a point of the face widened by 5 %, within 1e-3 .. 1e-7 of
+// an edge, of a corner, grazing (the component along the face's normal down to 2^-45 of the others), anywhere, and a few with NaN, inf and
+// exact-zero components.  Every ray is sent to a wall that HAS a face.  cnt[0] = rays the certificate accepts; [1] = of those, rays on
+// which the two tests differ (return value > 0, outside, face, P bit for bit) -- must be 0; [2] = rays it rejects although the box test
+// hits from outside through the face; [3] = rays it rejects in all (the wave falls back on the box test).
+__global__ void k_sweep_wall_face(const GeomDev *wallGeoms, const WallBox *walls, const int *faced, int nfaced, F3 roomLo, F3 roomHi,
+                                  unsigned long long seed, int per_thread, unsigned long long *cnt) {
+    SweepRng rng(seed);
+    unsigned int na = 0, bad = 0, nrh = 0, nrej = 0;
+    const F3 lo = roomLo + f3(1e-3f, 1e-3f, 1e-3f), ext = (roomHi - f3(1e-3f, 1e-3f, 1e-3f)) - lo;
+    for (int k = 0; k < per_thread; ++k) {
+        float u[16];
+        for (int j = 0; j < 16; ++j) u[j] = rng.next();
+        const int w = faced[(int)(u[0] * (float)nfaced) % nfaced];
+        const GeomDev &G = wallGeoms[w];
+        const int face = walls[w].face;
+        const float beyond = walls[w].beyond;
+        const int K = face >> 1;
+        const float s = (face & 1) ? 1.0f : -1.0f;
+        F3 org = lo + f3(u[1] * ext.x, u[2] * ext.y, u[3] * ext.z);
+        if (u[4] < 1.0f / 3.0f) {                                   // onto the border of the shrunk room
+            const int a = (int)(u[4] * 9.0f);
+            const bool high = u[5] < 0.5f;
+            if (a == 0) org.x = high ? lo.x + ext.x : lo.x; else if (a == 1) org.y = high ? lo.y + ext.y : lo.y; else org.z = high ? lo.z + ext.z : lo.z;
+        }
+        // a point of the face's plane in object space: (a, b) on the two other axes
+        const int fam = (int)(u[6] * 16.0f);
+        float a = u[7] * 1.05f - 0.525f, b = u[8] * 1.05f - 0.525f;
+        const float eps = __builtin_exp2f(-3.3219281f * (3.0f + 4.0f * u[9])) * (u[10] < 0.5f ? 1.0f : -1.0f);     // 1e-3 .. 1e-7, either side
+        const float sa = u[11] < 0.5f ? 0.5f : -0.5f, sb = u[12] < 0.5f ? 0.5f : -0.5f;
+        if (fam >= 6 && fam < 12) a = sa * (1.0f + eps);
+        if (fam >= 10 && fam < 12) b = sb * (1.0f + eps * u[13]);
+        if (fam >= 6 && fam < 10 && u[13] < 0.5f) { const float t = a; a = b; b = t; }
+        const F3 q = K == 0 ? f3(0.5f * s, a, b) : (K == 1 ? f3(a, 0.5f * s, b) : f3(a, b, 0.5f * s));
+        F3 dir = mulMV(G.xf, q, 1.0f) - org;
+        if (fam == 12) {                                           // grazing: the object-space component along the normal scaled down
+            F3 qd = mulMV(G.inv, dir, 0.0f);
+            const float sc = __builtin_exp2f(-45.0f * u[14]);
+            if (K == 0) qd.x = -s * __builtin_fabsf(qd.x) * sc; else if (K == 1) qd.y = -s * __builtin_fabsf(qd.y) * sc; else qd.z = -s * __builtin_fabsf(qd.z) * sc;
+            dir = mulMV(G.xf, qd, 0.0f);
+        } else if (fam == 13) {
+            dir = f3(u[7] - 0.5f, u[8] - 0.5f, u[14] - 0.5f);
+        }
+        dir = normalize(dir);
+        if (fam >= 14) {                                           // NaN / inf / exact zeros, in a direction or an origin
+            const int kind = (int)(u[14] * 5.0f), comp = (int)(u[15] * 3.0f);
+            const float v = kind == 0 ? __uint_as_float(0x7fc00000u) : (kind == 1 ? __uint_as_float(0x7f800000u) : 0.0f);
+            if (kind < 3) { if (comp == 0) dir.x = v; else if (comp == 1) dir.y = v; else dir.z = v; }
+            else if (kind == 3) { if (comp == 0) org.x = __uint_as_float(0x7fc00000u); else if (comp == 1) org.y = __uint_as_float(0x7fc00000u); else org.z = __uint_as_float(0x7fc00000u); }
+            else dir = f3(0.0f, 0.0f, 0.0f);
+        }
+        F3 P1 = f3(1, 2, 3), N1 = f3(4, 5, 6);
+        bool o1 = false;
+        const float t1 = boxIntersectionTest<true, false>(G, org, dir, P1, N1, o1, false, true);
+        const bool through = t1 > 0.0f && o1 && __float_as_int(N1.x) == face;
+        const F3 qo = mulMV(G.inv, org, 1.0f), qdu = mulMV0(G.inv, G.invZ, dir);
+        if (wallFaceCertificate(qo, qdu, face, beyond)) {
+            const F3 P2 = boxFacePoint(G, face, qo, qdu);
+            const bool eq = through && __float_as_uint(P1.x) == __float_as_uint(P2.x) && __float_as_uint(P1.y) == __float_as_uint(P2.y) &&
+                            __float_as_uint(P1.z) == __float_as_uint(P2.z);
+            ++na;
+            bad += eq ? 0u : 1u;
+        } else {
+            ++nrej;
+            nrh += through ? 1u : 0u;
+        }
+    }
+    sweepFlush(&cnt[0], na);
+    sweepFlush(&cnt[1], bad);
+    sweepFlush(&cnt[2], nrh);
+    sweepFlush(&cnt[3], nrej);
+}
 // divUnscaled(1, s) = 1.0f / s on EVERY float of [2^-40, 2^40] (the fast normalize's reciprocal), and divUnscaled(a, d) = a / d on
 // pseudo-random pairs of the box test's range (|a| <= 2^20 + 1, 2^-40 <= |d| <= 2): bad[0] / bad[1] count bit mismatches
 __global__ void k_sweep_div_unscaled(unsigned long long seed, int per_thread, unsigned long long *bad) {

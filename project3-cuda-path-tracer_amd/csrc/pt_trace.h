@@ -813,6 +813,9 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
     // textured forms, which keep the code they ran before.
     constexpr bool kResolveOk = kCamListOk && !TEX && !BUMP;
     int camFace = -1;
+    // ... and the later bounces' counterpart: a one-wall tile whose lanes are all certified to enter the wall through its inner face
+    // (ptd::wallFaceCertificate, per lane and tile: the rays are the scatter's, not the host's).  The small-scene forms, PLAIN and not.
+    constexpr bool kWallResolveOk = !FIRST && !MANY && !MESH && !TEX && !BUMP;
     auto requestCam = [&](uint32_t Tq, uint32_t tid) {
         const ArgsPtr A = launder(kargs);
         const uint32_t idx0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)Tq) * kBlock;
@@ -987,6 +990,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
             }
 
             if (FIRST) { if (inScene) probe(8); } else probe(7);                                   // tiles (waves with at least one valid path) and valid paths
+            if (!FIRST) { PT_TALLY_WALL_RESOLVE(0, 1ull); }
             // nearest hit, geoms in file order, strict '<' so the first geom wins ties (S3)
             probe(15);                                          // (nearest-hit loop)
             float tbest = anyFloat();
@@ -1096,7 +1100,34 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 // a later tile whose class lists ONE primitive (its paths' one wall): a hit's distance is compared with nothing (PACKED: the spheres follow)
                 // (... and an unresolved wave of the work list whose signature is one primitive)
                 const bool onlyOne = ((!FIRST && !PACKED) || (kResolveOk && camList)) && gk1 - gk0 == 1;
-                for (int gk = gk0; gk < gk1; ++gk) {
+                // A later tile whose class is ONE wall and no candidate (class bit 3 clear; the list is that wall alone), where pt_init named the
+                // wall's inner face (WallBox::face): every lane says whether its ray is certified to hit the wall from outside through that face
+                // (ptd::wallFaceCertificate, on the operands the box test forms anyway).  When every lane of the wave is, the wave takes the
+                // face's one quotient (ptd::boxFacePoint: no slab decision, no axis select, no distance); one lane in doubt -- the margin band
+                // at the face's edges -- and the whole wave runs the loop below as it always did.
+                bool wallResolved = false;
+                if (kWallResolveOk && onlyOne && (tileCls & 8u) == 0u && (tileCls & 7u) < 6u && hotWalls(hotNow()) != 0u) {
+                    const PT_CAS WallBox &wb = *(launder((WallPtr)(A->walls)) + (tileCls & 7u));
+                    const int wface = wb.face;
+                    if (wface >= 0) {
+                        const int g = classIdx[gk0];
+                        const PT_CAS GeomDev &G = *(launder(geoms) + g);
+                        const F3 qo = mulMV(G.inv, org, 1.0f);
+                        const F3 qdu = mulMV0(G.inv, G.invZ, dir);
+                        const unsigned long long failed = __ballot(!wallFaceCertificate(qo, qdu, wface, wb.beyond));
+                        PT_TALLY_WALL_RESOLVE(1, 1ull);
+                        PT_TALLY_WALL_RESOLVE(2, failed == 0ull ? 1ull : 0ull);
+                        PT_TALLY_WALL_RESOLVE(3, (unsigned long long)__popcll(failed));
+                        if (failed == 0ull) {
+                            P = boxFacePoint(G, wface, qo, qdu);
+                            hit = g;
+                            nsrc = f3(__int_as_float(wface), 0.0f, 0.0f);
+                            outsideI = 1;
+                            wallResolved = true;
+                        }
+                    }
+                }
+                for (int gk = wallResolved ? gk1 : gk0; gk < gk1; ++gk) {
                     int g, span = 0;
                     if (FIRST && listed && !camList) {
                         const int2v e = rowList[gk];
