@@ -503,8 +503,12 @@ int        pt_ctx_destroy(PtContext *ctx);    /* PT_ERR_INVALID while the contex
  *   pt_group_reduce          assembles the frame from what has been committed so far, asynchronously: members on DISTINCT devices (and
  *                              librccl.so loadable: dlopen, never linked) by ONE ncclReduce(sum, float32, 3 W H, root = member 0's device) over
  *                              xGMI of double-buffered snapshots of the devices' accumulators on a collective stream per device -- the next
- *                              iteration's commits wait on the device for the snapshot only, never for the reduce, and nothing waits on the host;
- *                              members that all share ONE device need no collective (their accumulator is the frame).
+ *                              iteration's commits wait on the device for the snapshot only, never for the reduce, and nothing waits on the host.
+ *                              A commit writes its member's rows of a snapshot and nothing else, so a snapshot's other rows must stay zero:
+ *                              across devices the root receives the sum into a result frame of its own, which pt_group_readback copies
+ *                              (the root's snapshot as the receive buffer would add its stale copy of the other devices' rows at every later
+ *                              reduce of it); in a one-rank communicator the reduce is the identity and runs on the snapshot itself.
+ *                              Members that all share ONE device need no collective (their accumulator is the frame).
  *   pt_group_iterate         = pt_group_iterate_batch(frame, iter, 1) + pt_group_reduce: BASELINE config C3 as written -- the reference's
  *                              per-iteration full-frame transfer (src/pathtrace.cu:170-171, src/main.cpp:97-106) with the reduce in its place.
  *                              With PT_FLAG_TRACE_AHEAD in opts->flags the iteration comes out of batches traced ahead (one small commit per call).

@@ -163,6 +163,18 @@ int pt_test_force_fault(int which);
 /* the next `count` assemblies of the group issue their ncclReduce with a NULL communicator (ncclInvalidArgument): the error path of
  * pt_group_reduce / pt_group_iterate / pt_group_readback -- ncclGroupEnd must still run and a later call must succeed */
 int pt_test_group_fail_next_reduce(PtGroup *g, int count);
+/* a group whose member i sits on VIRTUAL device vdev[i] (0 <= vdev[i] < 8, vdev[0] == 0: the root), every one of them on the current HIP device.
+ * Each distinct virtual device is a GroupDevice of its own -- its own full-frame accumulator, snapshot pair, collective stream and events --
+ * exactly as a distinct HIP device would be; everything downstream (pt_group_init / iterate / reduce / readback / sync / counters / destroy,
+ * pt_test_group_fail_next_reduce) is the product's code, unchanged.  collective 0: host gather; 1: the emulated reduce below.
+ * pt_group_collective() answers "host gather" or "emulated reduce (virtual devices: test library)". */
+int pt_test_group_create_virtual(PtGroup **out, int n, const int32_t *vdev, int collective);
+/* The emulated reduce (csrc/pt_group.h: EmulatedReduce -- ncclReduce's semantics in one process: at the end of a call group the root's
+ * recvbuf[i] = sendbuf_0[i] + sendbuf_1[i] + ... in ascending rank order, fp32, in place allowed, by ONE kernel on the root's stream behind an
+ * event of every other rank's stream) on its own: send_host[r] = rank r's `count` floats, 1..8 ranks, root 0; in_place 1: the root receives into
+ * its own send buffer.  recv_host = what the root received; send_after_host (or NULL; entries may be NULL) = every rank's device send buffer as
+ * the call left it -- the other ranks' unchanged, the root's too unless in place. */
+int pt_test_emulated_reduce(const float *const *send_host, int ranks, int64_t count, int in_place, float *recv_host, float *const *send_after_host);
 int pt_test_hemisphere(const float *normals3, const int32_t *iter_index_depth3, int n, float *out3);
 int pt_test_sincos(const float *x, int n, float *s, float *c);
 int pt_test_pow(const float *x, const float *e, int n, float *out);   /* build-defined x^e of the imperfect-specular sampler */

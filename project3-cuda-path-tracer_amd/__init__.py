@@ -87,6 +87,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
     "pt_test_display", "pt_test_spatial_variance",
+    "pt_test_group_create_virtual", "pt_test_emulated_reduce",
 ]
 
 
@@ -247,6 +248,8 @@ def _bind(L, with_tests):
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
         L.pt_test_group_fail_next_reduce.argtypes = [vp, i32]
+        L.pt_test_group_create_virtual.argtypes = [C.POINTER(vp), i32, C.POINTER(C.c_int32), i32]
+        L.pt_test_emulated_reduce.argtypes = [C.POINTER(vp), i32, i64, i32, vp, C.POINTER(vp)]
         L.pt_test_sphere_group_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p, u64p, C.POINTER(C.c_int32)]
         L.pt_test_texture_sample.argtypes = [vp, i32, i32, vp, i32, vp]
         L.pt_test_texture_uv.argtypes = [i32, vp, vp, i32, vp]
@@ -907,6 +910,20 @@ def test_exp_neg_poly(a):
     return out
 
 
+def test_emulated_reduce(sends, in_place=False):
+    """pt_test_emulated_reduce: the emulated reduce of virtual device groups on its own (test library).  sends: 1..8 float32 arrays of one length,
+    rank by rank; root 0.  Returns (what the root received, every rank's device send buffer as the call left it)."""
+    sends = [np.ascontiguousarray(s, np.float32).reshape(-1) for s in sends]
+    n = sends[0].size
+    if any(s.size != n for s in sends):
+        raise PtError("test_emulated_reduce: send buffers of one length")
+    recv = np.empty(n, np.float32)
+    after = [np.empty(n, np.float32) for _ in sends]
+    ptrs = lambda arrs: (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    _tcheck(test_lib().pt_test_emulated_reduce(ptrs(sends), len(sends), n, 1 if in_place else 0, _p(recv), ptrs(after)))
+    return recv, after
+
+
 def counters():
     c = PtCounters()
     _check(lib().pt_counters(C.byref(c)))
@@ -971,12 +988,21 @@ class Context:
 
 
 class Group:
-    """pt_group_*: n contexts rendering the row shards y % n of one frame, member i on devices[i] (default: i % device count)."""
+    """pt_group_*: n contexts rendering the row shards y % n of one frame, member i on devices[i] (default: i % device count).
+    virtual=[...] (test library only, inside renderer_from_test_library): member i on VIRTUAL device virtual[i] of the one HIP device, each a
+    device of its own to the group (pt_test_group_create_virtual), the frame assembled by collective "reduce" (the emulated reduce) or "host"."""
 
-    def __init__(self, n, devices=None):
+    def __init__(self, n, devices=None, virtual=None, collective="reduce"):
         h = C.c_void_p()
-        dv = None if devices is None else (C.c_int32 * n)(*devices)
-        _check(lib().pt_group_create(C.byref(h), n, dv))
+        if virtual is not None:
+            if _lib is None or _lib is not _test:
+                raise PtError("Group(virtual=...) exists in the test library only: use it inside renderer_from_test_library()")
+            if devices is not None or len(virtual) != n or collective not in ("reduce", "host"):
+                raise PtError("Group(virtual=...): n virtual device indices, no devices, collective 'reduce' or 'host'")
+            _check(lib().pt_test_group_create_virtual(C.byref(h), n, (C.c_int32 * n)(*virtual), 1 if collective == "reduce" else 0))
+        else:
+            dv = None if devices is None else (C.c_int32 * n)(*devices)
+            _check(lib().pt_group_create(C.byref(h), n, dv))
         self.handle, self.n, self._scene = h, n, None
 
     @property

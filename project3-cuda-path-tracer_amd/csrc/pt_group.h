@@ -16,17 +16,30 @@
 //       "rccl reduce"         distinct devices, librccl.so loaded (dlopen; single process, ncclCommInitAll): every member's commit
 //                             ALSO writes its rows' new values into one of two SNAPSHOT frames of its device (k_commit's `snap`: the
 //                             accumulator is read once, for the addition and the copy), then ONE ncclReduce(sum, float32, 3 W H, root =
-//                             member 0's device) of the snapshots, in place at the root, on the device's collective stream behind the
-//                             members' commit events -- x + 0 is exact: disjoint rows.  Nothing waits on the host: the reduce of
-//                             iteration i runs while iteration i + 1 is committed into the OTHER snapshot and the batches traced ahead keep
-//                             tracing; a snapshot is written again two calls later, behind its reduce's event.  pt_group_readback = one
-//                             D2H copy of the latest reduced snapshot on the root's collective stream + a wait for THAT stream only.
+//                             member 0's device) of the snapshots on the device's collective stream behind the members' commit events --
+//                             x + 0 is exact: disjoint rows.  Across devices the root receives into a RESULT frame of its own
+//                             (PtGroup::reduced); a one-rank communicator, where the reduce is the identity, reduces the snapshot onto
+//                             itself.  Nothing waits on the host: the reduce of iteration i runs while iteration i + 1 is committed
+//                             into the OTHER snapshot and the batches traced ahead keep tracing; a snapshot is written again two calls
+//                             later, behind its reduce's event.  pt_group_readback = one D2H copy of the latest assembled frame on the
+//                             root's collective stream + a wait for THAT stream only.
 //       "shared accumulator"  every member on ONE device: the accumulator is the frame; readback copies it behind the members' commit events.
 //       "host gather"         several devices without RCCL (PT_AMD_COLLECTIVE=host, no librccl.so): every device's frame is copied to the host
 //                             and the rows are taken from their owners' (synchronous; a fallback).
 //   * ncclGroupStart / ncclGroupEnd are balanced on EVERY path: the loop between them records the first error and goes on to GroupEnd.
 // Across DISTINCT devices the RCCL leg is UNMEASURED: no multi-GPU node was available to any build round (pt_group_collective() says so);
-// what has run is the same pipeline in a one-rank communicator (PT_AMD_COLLECTIVE=rccl), bit-identical after every call.
+// what has run is the same pipeline in a one-rank communicator (PT_AMD_COLLECTIVE=rccl), bit-identical after every call, and -- in the test
+// library only -- the multi-device PROTOCOL on VIRTUAL devices: pt_test_group_create_virtual (include/pt_amd_test.h) gives every member a
+// virtual device index, each distinct index a GroupDevice of its own on the one HIP device (its own accumulator, snapshots, collective stream,
+// events), and an emulated reduce with ncclReduce's semantics (EmulatedReduce below) or the host gather in RCCL's place.  Everything after
+// group_build is the product's code.  That proves the snapshot / event protocol, not RCCL or the links between devices.
+//
+// The stale-row bug the virtual devices found (tests/test_gpu_group_devices.py).  Until then the root reduced IN PLACE: the sum landed in the
+// root's own snapshot k.  A commit writes only its member's rows into a snapshot, so the other devices' rows of the root's snapshot -- zero
+// before the first reduce, which is all "x + 0" needs -- held the frame of that reduce ever after: the third assembly (snapshot 0 again) summed
+// {A3 | B1 stale} and {0 | B3} to {A3 | B1 + B3}.  A one-rank communicator never shows it (the root's members write every row there is).  The
+// fix: with two or more GroupDevices the root receives into PtGroup::reduced, which no commit writes, and every snapshot keeps zeros in the
+// rows its device does not own.
 // Included by pt_api.hip inside its extern "C" block.
 #pragma once
 #include <dlfcn.h>      // (the C++ headers this file needs -- <atomic>, <condition_variable>, <functional>, <thread> -- are included by pt_api.hip)
@@ -96,6 +109,8 @@ int pt_ctx_destroy(PtContext *ctx) {
 
 // ---- groups ---------------------------------------------------------------------------------------------------------------------------
 namespace {
+// the collective's function table: librccl.so's entry points -- or, for the test library's virtual devices, the emulation's (EmulatedReduce).
+// A group calls its collective through PtGroup::api only.
 struct Rccl {
     void *lib = nullptr;
     int (*CommInitAll)(void **, int, const int *) = nullptr;
@@ -128,6 +143,141 @@ Rccl *rcclPtr() {
 #define rccl() (*rcclPtr())
 std::mutex g_rcclMutex;                          // (loading; the calls themselves go through one group's host thread)
 constexpr int kNcclFloat = 7, kNcclSum = 0;      // rccl.h: ncclFloat32, ncclSum
+
+#ifdef PT_TEST_API
+// ---- the emulated reduce: a second table of the Rccl shape, for the virtual devices of the test library --------------------------------
+// Semantics: ncclReduce's in one process.  Between GroupStart and GroupEnd every rank of a communicator posts (sendbuf, recvbuf, count, root,
+// comm, stream); at GroupEnd the root's recvbuf[i] = sendbuf_0[i] + sendbuf_1[i] + ... in ASCENDING RANK order, fp32, one IEEE addition each.
+// recvbuf may be the root's own sendbuf (in place); the other ranks' recvbuf is ignored.  A NULL communicator answers ncclInvalidArgument and
+// posts nothing; GroupEnd closes the group whatever was refused (a group that ends with no post enqueues nothing and succeeds, as RCCL's does).
+// A group that ends with posts from only SOME ranks, or with ranks that disagree on count or root, would hang real RCCL; here it is refused
+// with ncclInvalidUsage and nothing is enqueued.  float32 and sum only; at most kEmuMaxRanks (8) ranks, every one on the current HIP device.
+//
+// Stream order -- what makes the call behave on each rank's stream as the real one does.  GroupEnd enqueues everything from the host and
+// waits for nothing:
+//   1. a "posted" event is recorded on every non-root rank's stream;
+//   2. the root's stream waits for all of them;
+//   3. ONE kernel (k_emulated_reduce, pt_test_kernels.h) on the root's stream adds the send buffers into the root's recvbuf;
+//   4. a "done" event is recorded on the root's stream;
+//   5. every non-root rank's stream waits for it.
+// So a rank's operation is complete on its stream only when its send buffer has been read -- which is what a group's evRed[k] records and
+// what the next commit into snapshot k waits for.  Every wait is for an event recorded EARLIER in the same GroupEnd: the dependencies are
+// acyclic in enqueue order, and nothing can wait for work that is not yet enqueued.
+struct EmulatedReduce {
+    enum { kSuccess = 0, kUnhandledHipError = 1, kInvalidArgument = 4, kInvalidUsage = 5 };      // rccl.h: ncclResult_t
+    struct World {                     // what CommInitAll makes: the ranks of one communicator
+        int n = 0, live = 0;
+        hipEvent_t posted[kEmuMaxRanks] = {};
+        hipEvent_t done = nullptr;
+    };
+    struct Comm { World *w; int rank; };
+    struct Post { const float *send; float *recv; size_t count; int root; Comm *comm; hipStream_t stream; };
+    struct Calls { int depth = 0; std::vector<Post> posts; };      // the calling thread's open group (RCCL's group state is per thread too)
+    static Calls &calls() {
+        thread_local Calls c;
+        return c;
+    }
+    static void release(World *w) {
+        for (hipEvent_t e : w->posted)
+            if (e) (void)hipEventDestroy(e);
+        if (w->done) (void)hipEventDestroy(w->done);
+        delete w;
+    }
+    static int CommInitAll(void **comms, int n, const int *) {
+        if (!comms || n < 1 || n > kEmuMaxRanks) return kInvalidArgument;
+        World *w = new World();
+        w->n = w->live = n;
+        bool ok = hipEventCreateWithFlags(&w->done, hipEventDisableTiming) == hipSuccess;
+        for (int r = 0; r < n && ok; ++r) ok = hipEventCreateWithFlags(&w->posted[r], hipEventDisableTiming) == hipSuccess;
+        if (!ok) { release(w); return kUnhandledHipError; }
+        for (int r = 0; r < n; ++r) comms[r] = new Comm{w, r};
+        return kSuccess;
+    }
+    static int CommDestroy(void *comm) {
+        Comm *c = static_cast<Comm *>(comm);
+        if (!c) return kInvalidArgument;
+        World *w = c->w;
+        delete c;
+        if (--w->live == 0) release(w);
+        return kSuccess;
+    }
+    static int GroupStart() {
+        ++calls().depth;
+        return kSuccess;
+    }
+    static int Reduce(const void *send, void *recv, size_t count, int dtype, int op, int root, void *comm, hipStream_t stream) {
+        if (!comm || !send || dtype != kNcclFloat || op != kNcclSum) return kInvalidArgument;
+        const bool alone = calls().depth == 0;        // outside a group: a group of this one call
+        if (alone) GroupStart();
+        calls().posts.push_back(Post{static_cast<const float *>(send), static_cast<float *>(recv), count, root, static_cast<Comm *>(comm), stream});
+        return alone ? GroupEnd() : (int)kSuccess;
+    }
+    static int GroupEnd() {
+        Calls &c = calls();
+        if (c.depth <= 0) return kInvalidUsage;
+        if (--c.depth > 0) return kSuccess;
+        std::vector<Post> posts;
+        posts.swap(c.posts);
+        if (posts.empty()) return kSuccess;
+        // one post per rank of ONE communicator, all of one count and root
+        World *w = posts[0].comm->w;
+        const int root = posts[0].root;
+        const size_t count = posts[0].count;
+        if ((int)posts.size() != w->n || root < 0 || root >= w->n) return kInvalidUsage;
+        const Post *byRank[kEmuMaxRanks] = {};
+        for (const Post &p : posts) {
+            if (p.comm->w != w || p.root != root || p.count != count || byRank[p.comm->rank]) return kInvalidUsage;
+            byRank[p.comm->rank] = &p;
+        }
+        const Post &rp = *byRank[root];
+        if (!rp.recv) return kInvalidArgument;
+        if (count == 0) return kSuccess;
+        ptk::EmuSources src{};
+        bool aligned = (reinterpret_cast<uintptr_t>(rp.recv) & 15u) == 0;
+        for (int r = 0; r < w->n; ++r) {
+            src.p[r] = byRank[r]->send;
+            aligned = aligned && (reinterpret_cast<uintptr_t>(src.p[r]) & 15u) == 0;
+        }
+        const long long nvec4 = aligned ? (long long)(count / 4) : 0;
+        const long long lanes = nvec4 + ((long long)count - 4 * nvec4);
+        bool ok = true;
+        for (int r = 0; r < w->n && ok; ++r)
+            if (r != root) ok = hipEventRecord(w->posted[r], byRank[r]->stream) == hipSuccess;
+        for (int r = 0; r < w->n && ok; ++r)
+            if (r != root) ok = hipStreamWaitEvent(rp.stream, w->posted[r], 0) == hipSuccess;
+        if (ok) {
+            hipLaunchKernelGGL(ptk::k_emulated_reduce, dim3((unsigned)((lanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, rp.stream, src, w->n, rp.recv, nvec4,
+                               (long long)count);
+            ok = hipGetLastError() == hipSuccess && hipEventRecord(w->done, rp.stream) == hipSuccess;
+        }
+        for (int r = 0; r < w->n && ok; ++r)
+            if (r != root) ok = hipStreamWaitEvent(byRank[r]->stream, w->done, 0) == hipSuccess;
+        return ok ? kSuccess : kUnhandledHipError;
+    }
+    static const char *GetErrorString(int r) {
+        switch (r) {
+            case kSuccess: return "no error";
+            case kUnhandledHipError: return "unhandled HIP error (emulated reduce)";
+            case kInvalidArgument: return "invalid argument (emulated reduce)";
+            case kInvalidUsage: return "invalid usage (emulated reduce)";
+        }
+        return "unknown result code (emulated reduce)";
+    }
+    static const Rccl *table() {
+        static const Rccl t = [] {
+            Rccl r;
+            r.CommInitAll = CommInitAll;
+            r.CommDestroy = CommDestroy;
+            r.Reduce = Reduce;
+            r.GroupStart = GroupStart;
+            r.GroupEnd = GroupEnd;
+            r.GetErrorString = GetErrorString;
+            return r;
+        }();
+        return &t;
+    }
+};
+#endif  // PT_TEST_API
 // the calling thread's current context and device, put back when a group call returns
 struct CurrentGuard {
     State *saved = t_ctx;
@@ -195,12 +345,15 @@ struct Worker {
     }
 };
 
-// what a group holds per DISTINCT device
+// what a group holds per DISTINCT device.  `id` is the device's identity -- what members are grouped by -- and `device` the HIP ordinal its
+// buffers, streams and events live on: the same number in a product group, the virtual index and the one real device in a virtual group
+// (pt_test_group_create_virtual).  Members of different GroupDevices share nothing below, whatever their HIP ordinals.
 struct GroupDevice {
+    int id = 0;
     int device = 0;
     std::vector<int> members;              // indices into PtGroup::ctx
     float *full = nullptr;                 // the zero-padded full-frame accumulator the members on this device commit into
-    float *snap[2] = {nullptr, nullptr};   // rccl: the members' commits copy their rows here (k_commit's `snap`); the reduce reads -- at the root: in place
+    float *snap[2] = {nullptr, nullptr};   // rccl: the members' commits copy their rows here (k_commit's `snap`), every other row stays zero; the reduce's send buffer
     hipStream_t coll = nullptr;            // the collective's stream (and the read-back's)
     hipEvent_t evRed[2] = {nullptr, nullptr};     // the reduce that read snapshot k is through (collective stream)
     void *comm = nullptr;                  // ncclComm_t
@@ -216,11 +369,14 @@ struct PtGroup {
     std::vector<std::unique_ptr<Worker>> worker;   // [n] or empty (PT_AMD_GROUP_THREADS=0, one member)
     std::vector<GroupDevice> dev;          // distinct devices, dev[0] = member 0's = the reduce's root
     bool rccl = false;                     // the frame is assembled by ncclReduce (else: shared accumulator / on the host)
-    std::vector<char> waitRed;             // [n] rccl: the member's next commit writes a snapshot a reduce may still be reading: wait for evRed first
+    const Rccl *api = nullptr;             // ... through this table: librccl.so's, or the emulated reduce of a virtual group (test library)
+    float *reduced = nullptr;              // rccl, two or more devices: the frame the root (dev[0]) receives the reduce into.  No commit writes it.  ONE
+                                           // buffer: the reduce that writes it and the read-back that copies it are both on dev[0].coll, in call order
+    std::vector<char> waitRed;            // [n] rccl: the member's next commit writes a snapshot a reduce may still be reading: wait for evRed first
     int W = 0, H = 0;
     bool inited = false;
     bool dirty = false;                    // commits were enqueued since the frame was last assembled
-    int k = 0;                             // the snapshot / result buffer the NEXT assembly takes
+    int k = 0;                             // the snapshot the NEXT assembly takes
     int last = -1;                         // ... and the one that holds the latest assembled frame
     int failReduces = 0;                   // tests (pt_test_group_fail_next_reduce): the next reduces are issued with a null communicator
     std::vector<float> stage;              // host gather: one device's frame
@@ -259,6 +415,11 @@ void group_release_buffers(PtGroup *g) {
         for (int q = 0; q < 2; ++q)
             if (d.snap[q]) { (void)hipFree(d.snap[q]); d.snap[q] = nullptr; }
     }
+    if (g->reduced) {       // (on the root's device)
+        (void)hipSetDevice(g->dev[0].device);
+        (void)hipFree(g->reduced);
+        g->reduced = nullptr;
+    }
     g->inited = false;
     g->dirty = false;
     g->last = -1;
@@ -276,16 +437,19 @@ int assemble(PtGroup *g) {
     if (!g->dirty && g->last >= 0) return PT_OK;                 // nothing was committed since the last assembly: its frame stands
     // 1. (per device, the collective stream already waits for the commits that wrote snapshot k: every member's last call wrote its rows
     //    there and queued the wait -- pt_group_iterate_batch)
-    // 2. ONE ncclReduce(sum) of the snapshots to dev[0].  No early return between GroupStart and GroupEnd: the first error is
-    //    kept, the group is always closed, then the call fails -- an open RCCL group would swallow every later collective of the process.
-    Rccl &rc_ = rccl();
+    // 2. ONE ncclReduce(sum) of the snapshots to dev[0] -- into g->reduced where there are other devices: the root's own snapshot
+    //    must keep zeros in their rows for the reduce after next (a commit rewrites its member's rows only); a one-rank reduce is the
+    //    identity and stays in place.  No early return between GroupStart and GroupEnd: the first error is kept, the group is always
+    //    closed, then the call fails -- an open RCCL group would swallow every later collective of the process.
+    const Rccl &rc_ = *g->api;
     int r = rc_.GroupStart(), rHip = 0;
     if (r == 0) {
         for (size_t di = 0; di < g->dev.size(); ++di) {
             GroupDevice &d = g->dev[di];
             if (hipSetDevice(d.device) != hipSuccess) { rHip = 1; continue; }
             void *comm = g->failReduces > 0 ? nullptr : d.comm;
-            const int ri = rc_.Reduce(d.snap[k], di == 0 ? d.snap[k] : nullptr, (size_t)g->W * g->H * 3, kNcclFloat, kNcclSum, 0, comm, d.coll);
+            float *const recv = di != 0 ? nullptr : g->reduced ? g->reduced : d.snap[k];
+            const int ri = rc_.Reduce(d.snap[k], recv, (size_t)g->W * g->H * 3, kNcclFloat, kNcclSum, 0, comm, d.coll);
             if (ri != 0 && r == 0) r = ri;
         }
         const int r2 = rc_.GroupEnd();
@@ -321,9 +485,9 @@ int ensure_collective(PtGroup *g) {
         std::vector<int> devs;
         for (const GroupDevice &d : g->dev) devs.push_back(d.device);
         std::lock_guard<std::mutex> lock(g_rcclMutex);
-        const int r = rccl().CommInitAll(comms.data(), nd, devs.data());
+        const int r = g->api->CommInitAll(comms.data(), nd, devs.data());
         if (r != 0) {
-            fprintf(stderr, "pt_group_init: ncclCommInitAll failed (%s): the frame is assembled %s\n", rccl().GetErrorString(r), nd > 1 ? "on the host" : "in place");
+            fprintf(stderr, "pt_group_init: ncclCommInitAll failed (%s): the frame is assembled %s\n", g->api->GetErrorString(r), nd > 1 ? "on the host" : "in place");
             g->rccl = false;
             g->how = nd > 1 ? "host gather" : "shared accumulator";
         } else {
@@ -334,30 +498,34 @@ int ensure_collective(PtGroup *g) {
 }
 }  // namespace
 
-int pt_group_create(PtGroup **out, int n, const int32_t *devices) {
-    if (!out || n < 1 || n > 64) return fail(PT_ERR_INVALID, "pt_group_create: 1..64 members");
-    const int ndev = count_devices();
-    if (ndev < 1) return fail(PT_ERR_NO_GPU, "pt_group_create: no HIP device (this library has no CPU fallback)");
+namespace {
+// Creating a group, first half: WHERE its members sit.  Member g->device.size() joins the GroupDevice of identity `id` -- a new one, on
+// HIP device `hip`, when it is the first member there.  (pt_group_create: id = the HIP ordinal; pt_test_group_create_virtual: id = the
+// virtual index, every one on the current HIP device.)
+void group_place(PtGroup *g, int id, int hip) {
+    const int i = (int)g->device.size();
+    g->device.push_back(hip);
+    int di = -1;
+    for (size_t q = 0; q < g->dev.size(); ++q)
+        if (g->dev[q].id == id) di = (int)q;
+    if (di < 0) {
+        GroupDevice gd;
+        gd.id = id;
+        gd.device = hip;
+        g->dev.push_back(gd);
+        di = (int)g->dev.size() - 1;
+    }
+    g->dev[di].members.push_back(i);
+    g->devIndex.push_back(di);
+}
+
+// ... second half: the group from that map -- contexts, commit streams, the collective, the issuing threads.  `emulated` (test library): a
+// VIRTUAL group, assembled by that table's reduce (collective 1) or on the host (0); null: the product's choice -- RCCL where there is
+// something to reduce and librccl.so loads, PT_AMD_COLLECTIVE permitting.  Takes `g` over: destroyed on failure.
+int group_build(PtGroup **out, PtGroup *g, const Rccl *emulated, int collective, const char *fn) {
     register_exit_handler();
     CurrentGuard guard;
-    PtGroup *g = new (std::nothrow) PtGroup();
-    if (!g) return fail(PT_ERR_INVALID, "pt_group_create: out of memory");
-    for (int i = 0; i < n; ++i) {
-        const int d = devices ? devices[i] : i % ndev;
-        if (d < 0 || d >= ndev) { delete g; return fail(PT_ERR_INVALID, "pt_group_create: device %d of %d", d, ndev); }
-        g->device.push_back(d);
-        int di = -1;
-        for (size_t q = 0; q < g->dev.size(); ++q)
-            if (g->dev[q].device == d) di = (int)q;
-        if (di < 0) {
-            GroupDevice gd;
-            gd.device = d;
-            g->dev.push_back(gd);
-            di = (int)g->dev.size() - 1;
-        }
-        g->dev[di].members.push_back(i);
-        g->devIndex.push_back(di);
-    }
+    const int n = (int)g->device.size();
     for (int i = 0; i < n; ++i) {
         PtContext *c = pt_ctx_create();
         if (!c) { pt_group_destroy(g); return PT_ERR_INVALID; }
@@ -370,31 +538,40 @@ int pt_group_create(PtGroup **out, int n, const int32_t *devices) {
     // itself commits on that device's NULL stream (the renderer's other streams are non-blocking: nothing synchronises with it implicitly),
     // and everything the collective needs -- its stream, RCCL's communicator with the streams IT creates -- is made AFTER the members'
     // first pt_init has created their tracing streams (ensure_collective, from pt_group_init): null, two tracing streams, collective.
-    // Members that share a device (the one-GPU rehearsal) get a commit stream each.
+    // Members that share a device (the one-GPU rehearsal) get a commit stream each -- "alone" means alone on the HIP device: the members of a
+    // virtual group sit on GroupDevices of their own and on ONE null stream all the same.
     g->stream.assign(n, nullptr);
     g->evCommit.assign(n, nullptr);
     bool ok = true;
     const char *ownStreams = getenv("PT_AMD_GROUP_OWN_STREAMS");      // experiments only
     for (int i = 0; i < n && ok; ++i) {
-        const bool alone = g->dev[g->devIndex[i]].members.size() == 1 && !(ownStreams && atoi(ownStreams));
+        const bool alone = std::count(g->device.begin(), g->device.end(), g->device[i]) == 1 && !(ownStreams && atoi(ownStreams));
         ok = hipSetDevice(g->device[i]) == hipSuccess && (alone || hipStreamCreateWithFlags(&g->stream[i], hipStreamNonBlocking) == hipSuccess) &&
              hipEventCreateWithFlags(&g->evCommit[i], hipEventDisableTiming) == hipSuccess;
     }
     if (!ok) {
         pt_group_destroy(g);
-        return fail(PT_ERR_HIP, "pt_group_create: no stream / event on a member's device");
+        return fail(PT_ERR_HIP, "%s: no stream / event on a member's device", fn);
     }
     // RCCL: one rank per DISTINCT device, one process (ncclCommInitAll).  Members that all share one device need no collective
     // (PT_AMD_COLLECTIVE=rccl sends their frame through a one-rank communicator all the same: the call path on a one-GPU box).
     // The library is loaded here -- pt_group_collective() answers from now on --, the communicator is made by the first pt_group_init.
-    const char *want = getenv("PT_AMD_COLLECTIVE");
+    // A virtual group takes what its creator named and reads no environment.
+    const char *want = emulated ? nullptr : getenv("PT_AMD_COLLECTIVE");
     const bool forbid = want && !strcmp(want, "host");
     const bool force = want && !strcmp(want, "rccl");
     const int nd = (int)g->dev.size();
     if (nd > 1) g->how = "host gather";
-    if (!forbid && (nd > 1 || force)) {
+    if (emulated) {
+        if (collective == 1) {
+            g->api = emulated;
+            g->rccl = true;
+            g->how = "emulated reduce (virtual devices: test library)";
+        }
+    } else if (!forbid && (nd > 1 || force)) {
         std::lock_guard<std::mutex> lock(g_rcclMutex);
         if (rccl().load()) {
+            g->api = &rccl();
             g->rccl = true;
             g->how = nd > 1 ? "rccl reduce (unmeasured across devices: no multi-GPU node was available to the build)" : "rccl reduce (one-rank communicator)";
         }
@@ -419,6 +596,21 @@ int pt_group_create(PtGroup **out, int n, const int32_t *devices) {
     }
     *out = g;
     return PT_OK;
+}
+}  // namespace
+
+int pt_group_create(PtGroup **out, int n, const int32_t *devices) {
+    if (!out || n < 1 || n > 64) return fail(PT_ERR_INVALID, "pt_group_create: 1..64 members");
+    const int ndev = count_devices();
+    if (ndev < 1) return fail(PT_ERR_NO_GPU, "pt_group_create: no HIP device (this library has no CPU fallback)");
+    PtGroup *g = new (std::nothrow) PtGroup();
+    if (!g) return fail(PT_ERR_INVALID, "pt_group_create: out of memory");
+    for (int i = 0; i < n; ++i) {
+        const int d = devices ? devices[i] : i % ndev;
+        if (d < 0 || d >= ndev) { delete g; return fail(PT_ERR_INVALID, "pt_group_create: device %d of %d", d, ndev); }
+        group_place(g, d, d);
+    }
+    return group_build(out, g, nullptr, -1, "pt_group_create");
 }
 
 void pt_group_destroy(PtGroup *g) {
@@ -445,7 +637,7 @@ void pt_group_destroy(PtGroup *g) {
         for (int q = 0; q < 2; ++q)
             if (d.evRed[q]) (void)hipEventDestroy(d.evRed[q]);
         if (d.coll) (void)hipStreamDestroy(d.coll);
-        if (d.comm) (void)rccl().CommDestroy(d.comm);
+        if (d.comm) (void)g->api->CommDestroy(d.comm);
     }
     {
         std::lock_guard<std::mutex> lock(g_groupMutex);
@@ -511,10 +703,15 @@ int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeo
         HIPCHECK(hipMalloc(&d.full, frameBytes));
         HIPCHECK(hipMemset(d.full, 0, frameBytes));
         if (g->rccl)
-            for (int q = 0; q < 2; ++q) {       // (zeroed: the rows of the OTHER devices' members stay zero, which is what the sum needs)
+            for (int q = 0; q < 2; ++q) {       // (zeroed: the rows of the OTHER devices' members stay zero for good -- no commit and no reduce
+                                                // writes them --, which is what the sum needs)
                 HIPCHECK(hipMalloc(&d.snap[q], frameBytes));
                 HIPCHECK(hipMemset(d.snap[q], 0, frameBytes));
             }
+        if (g->rccl && g->dev.size() > 1 && &d == &g->dev[0]) {      // the root's result frame (see assemble)
+            HIPCHECK(hipMalloc(&g->reduced, frameBytes));
+            HIPCHECK(hipMemset(g->reduced, 0, frameBytes));
+        }
         HIPCHECK(hipDeviceSynchronize());
     }
     g->waitRed.assign(n, 0);
@@ -606,7 +803,8 @@ int pt_group_readback(PtGroup *g, float *rgb_sum_host) {
     }
     if (g->rccl) {
         HIPCHECK(hipSetDevice(g->dev[0].device));
-        HIPCHECK(hipMemcpyAsync(rgb_sum_host, g->dev[0].snap[g->last], frameFloats * sizeof(float), hipMemcpyDeviceToHost, g->dev[0].coll));
+        const float *const frame = g->reduced ? g->reduced : g->dev[0].snap[g->last];
+        HIPCHECK(hipMemcpyAsync(rgb_sum_host, frame, frameFloats * sizeof(float), hipMemcpyDeviceToHost, g->dev[0].coll));
         HIPCHECK(hipStreamSynchronize(g->dev[0].coll));
     } else if (g->dev.size() == 1) {
         HIPCHECK(hipSetDevice(g->dev[0].device));

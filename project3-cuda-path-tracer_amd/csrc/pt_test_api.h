@@ -161,6 +161,77 @@ int pt_test_group_fail_next_reduce(PtGroup *g, int count) {
     return PT_OK;
 }
 
+// A group on VIRTUAL devices: pt_group_create's second half (pt_group.h: group_build) over a map that groups the members by vdev[i] instead of
+// by HIP ordinal, with the emulated reduce's table -- or the host gather -- as its collective.
+int pt_test_group_create_virtual(PtGroup **out, int n, const int32_t *vdev, int collective) {
+    if (!out || !vdev || n < 1 || n > 64) return fail(PT_ERR_INVALID, "pt_test_group_create_virtual: 1..64 members");
+    if (collective != 0 && collective != 1) return fail(PT_ERR_INVALID, "pt_test_group_create_virtual: collective 0 (host gather) or 1 (emulated reduce)");
+    if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_test_group_create_virtual: no HIP device");
+    if (vdev[0] != 0) return fail(PT_ERR_INVALID, "pt_test_group_create_virtual: member 0 sits on virtual device 0, the root");
+    for (int i = 0; i < n; ++i)
+        if (vdev[i] < 0 || vdev[i] >= kEmuMaxRanks) return fail(PT_ERR_INVALID, "pt_test_group_create_virtual: virtual device %d of %d", vdev[i], kEmuMaxRanks);
+    int hip = 0;
+    HIPCHECK(hipGetDevice(&hip));
+    PtGroup *g = new (std::nothrow) PtGroup();
+    if (!g) return fail(PT_ERR_INVALID, "pt_test_group_create_virtual: out of memory");
+    for (int i = 0; i < n; ++i) group_place(g, vdev[i], hip);
+    return group_build(out, g, EmulatedReduce::table(), collective, "pt_test_group_create_virtual");
+}
+
+// The emulated reduce alone, through its function table as a group calls it: `ranks` send buffers of `count` floats uploaded to the device, one
+// stream per rank, GroupStart, one Reduce per rank (root 0; in_place: the root receives into its own send buffer), GroupEnd; then the streams
+// are waited for and the root's receive buffer and every rank's send buffer are read back.
+int pt_test_emulated_reduce(const float *const *send_host, int ranks, int64_t count, int in_place, float *recv_host, float *const *send_after_host) {
+    if (!send_host || !recv_host || ranks < 1 || ranks > kEmuMaxRanks || count < 1) return fail(PT_ERR_INVALID, "pt_test_emulated_reduce: bad argument");
+    if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "no HIP device");
+    const Rccl &api = *EmulatedReduce::table();
+    struct Rank {
+        DevBuf<float> send;
+        hipStream_t stream = nullptr;
+        void *comm = nullptr;
+    };
+    std::vector<Rank> rk(ranks);
+    DevBuf<float> recv;
+    std::vector<void *> comms(ranks, nullptr);
+    int rc = PT_OK, r = 0;
+    for (int i = 0; i < ranks && rc == PT_OK; ++i) {
+        rc = rk[i].send.upload(send_host[i], (size_t)count);
+        if (rc == PT_OK && hipStreamCreateWithFlags(&rk[i].stream, hipStreamNonBlocking) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: no stream");
+    }
+    if (rc == PT_OK && !in_place) rc = recv.alloc_zeroed((size_t)count);
+    if (rc == PT_OK && (r = api.CommInitAll(comms.data(), ranks, nullptr)) != 0) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: CommInitAll: %s", api.GetErrorString(r));
+    if (rc == PT_OK) {
+        for (int i = 0; i < ranks; ++i) rk[i].comm = comms[i];
+        if (hipDeviceSynchronize() != hipSuccess) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: the uploads failed");      // (the uploads: the streams below are non-blocking)
+    }
+    if (rc == PT_OK) {
+        r = api.GroupStart();
+        if (r == 0) {
+            for (int i = 0; i < ranks; ++i) {
+                float *const dst = i != 0 ? nullptr : in_place ? rk[0].send.p : recv.p;
+                const int ri = api.Reduce(rk[i].send.p, dst, (size_t)count, kNcclFloat, kNcclSum, 0, rk[i].comm, rk[i].stream);
+                if (ri != 0 && r == 0) r = ri;
+            }
+            const int r2 = api.GroupEnd();
+            if (r == 0) r = r2;
+        }
+        if (r != 0) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: %s", api.GetErrorString(r));
+    }
+    // every rank's stream: the operation is complete on each of them
+    for (int i = 0; i < ranks; ++i)
+        if (rk[i].stream && hipStreamSynchronize(rk[i].stream) != hipSuccess && rc == PT_OK) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: a rank's stream failed");
+    if (rc == PT_OK && hipMemcpy(recv_host, in_place ? rk[0].send.p : recv.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: read-back");
+    for (int i = 0; i < ranks && rc == PT_OK && send_after_host; ++i)
+        if (send_after_host[i] && hipMemcpy(send_after_host[i], rk[i].send.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: read-back");
+    for (int i = 0; i < ranks; ++i) {
+        if (rk[i].comm) (void)api.CommDestroy(rk[i].comm);
+        if (rk[i].stream) (void)hipStreamDestroy(rk[i].stream);
+    }
+    return rc;
+}
+
 // ---- what the entry points below share: launch, counters, grids, packed scenes ------------------------------
 #define NEED_GPU() do { if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "no HIP device"); } while (0)
 

@@ -995,4 +995,28 @@ __global__ void k_test_reflect_refract(const float *I, const float *N, const flo
     rr[3 * i] = r2.x; rr[3 * i + 1] = r2.y; rr[3 * i + 2] = r2.z;
 }
 
+// ---- the emulated reduce of virtual device groups (pt_group.h: EmulatedReduce) ---------------------------------
+// dst[i] = src[0][i] + src[1][i] + ... + src[ranks - 1][i], added in that order in fp32 (one IEEE addition each: -ffp-contract=off, denormals
+// kept).  One lane per float4 of the first nvec4 * 4 elements -- the host passes nvec4 = 0 unless every pointer is 16-byte aligned --, then one
+// lane per element of the rest.  dst may be src[k] itself: a lane reads the elements it writes, and no other lane's.
+constexpr int kEmuMaxRanks = 8;
+struct EmuSources { const float *p[kEmuMaxRanks]; };
+__global__ __launch_bounds__(kBlock) void k_emulated_reduce(EmuSources src, int ranks, float *dst, long long nvec4, long long count) {
+    const long long j = blockIdx.x * (long long)kBlock + threadIdx.x;
+    if (j < nvec4) {
+        float4 acc = reinterpret_cast<const float4 *>(src.p[0])[j];
+        for (int r = 1; r < ranks; ++r) {
+            const float4 v = reinterpret_cast<const float4 *>(src.p[r])[j];
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+        }
+        reinterpret_cast<float4 *>(dst)[j] = acc;
+        return;
+    }
+    const long long i = nvec4 * 4 + (j - nvec4);
+    if (i >= count) return;
+    float acc = src.p[0][i];
+    for (int r = 1; r < ranks; ++r) acc += src.p[r][i];
+    dst[i] = acc;
+}
+
 }  // namespace ptk
