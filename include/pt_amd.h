@@ -131,7 +131,7 @@ typedef struct PtOptions {
                                  Results do not depend on it: radiance is committed in iteration order. */
     int32_t max_batch;        /* largest `count` pt_iterate_batch will be given (sizes the path pools: two pools of
                                  44 B x pixels x max_batch per slot plus ~10 % of chunk slack -- 81 MB per iteration of a
-                                 1280x720 frame and slot -- and pixels x max_batch must stay below 2^29);
+                                 1280x720 frame and slot; 32 B and 59 MB where the scene takes the PLAIN kernels -- and pixels x max_batch must stay below 2^29);
                                  0 = 1, max PT_MAX_BATCH */
     void   *stream;           /* hipStream_t to enqueue on; NULL = the default stream */
     float  *accum_dev;        /* optional caller-owned device accumulator, W*H*3 floats (or the shard's rows only

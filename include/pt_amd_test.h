@@ -252,6 +252,8 @@ typedef struct PtTestPlanSummary {
     uint32_t state_bits;
     int32_t nBinned, nWalls, nSphCull, nSphGroups, nLocalPad, firstSkipped, poolChunks;
     uint64_t ldsBytes, ldsBytesNext;
+    int32_t histBits;       /* 0: the path pools carry a path's throughput (44 B); b > 0: its material history in codes of b bits (32 B: the PLAIN forms) */
+    int32_t reserved;
 } PtTestPlanSummary;
 int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
                        PtTestPlanSummary *out);

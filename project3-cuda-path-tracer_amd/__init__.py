@@ -99,7 +99,7 @@ class PtOptions(C.Structure):
 
 class PtTestPlanSummary(C.Structure):      # include/pt_amd_test.h
     _fields_ = [("state_bits", C.c_uint32)] + [(n, C.c_int32) for n in ("nBinned", "nWalls", "nSphCull", "nSphGroups", "nLocalPad", "firstSkipped", "poolChunks")] + \
-               [("ldsBytes", C.c_uint64), ("ldsBytesNext", C.c_uint64)]
+               [("ldsBytes", C.c_uint64), ("ldsBytesNext", C.c_uint64), ("histBits", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PtMesh(C.Structure):

@@ -400,6 +400,7 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     BounceArgs ba;
     ba.prm = R().prm;
     ba.iter = iter; ba.batch = batch; ba.depth = depth; ba.lastBounce = lastBounce ? 1 : 0; ba.parity = sl.parity;
+    ba.histShift = R().prm.histBits * (depth - 1);
     ba.genIn = genIn; ba.genOut = genOut;
     ba.in = in; ba.out = out;
     ba.tile.inBase = in.base; ba.tile.inList = in.list; ba.tile.inCap = in.cap;
@@ -1225,6 +1226,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     const void *kernFirst = nullptr, *kernNext = nullptr;
     PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
     PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
+    // (the pools' layout is the later launches' form's: history-coded for PLAIN, and for no other)
+    if ((plan.prm.histBits != 0) != ((bounce_form(false, plan.dof, plan.many, plan.sweptCubes, plan.mesh, plan.grouped, plan.tex, plan.bump, plan.plain) & kbPlain) != 0))
+        return fail(PT_ERR_INVALID, "pt_init: internal error: history bits %d and the later bounces' form disagree", plan.prm.histBits);
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
     register_exit_handler();
     // PT_FLAG_TEMPORAL on the renderer that goes and on the one that comes, the same frame size and device: the context's history lives on,
@@ -1268,7 +1272,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     const size_t cpx = S.prm.contribLocal ? (size_t)(S.nLocal > 0 ? S.nLocal : 1) : (size_t)S.P;
     const size_t contribFloats = (size_t)S.maxBatch * cpx * 3, maskWords = (size_t)((S.maxBatch + 31) / 32) * cpx;
     {   // the memory budget BEFORE the first large allocation: a batch that does not fit fails here, with nothing to undo
-        const size_t perSlot = 2 * (S.poolCap * kNumArrays * sizeof(float) + (size_t)kSeg * S.poolChunks * sizeof(unsigned long long)) + sizeof(Ctrl) +
+        const size_t perSlot = 2 * (S.poolCap * poolDwords(S.prm.histBits) * sizeof(float) + (size_t)kSeg * S.poolChunks * sizeof(unsigned long long)) + sizeof(Ctrl) +
                                contribFloats * sizeof(float) + maskWords * sizeof(uint32_t) + S.meshHitWords * sizeof(unsigned long long);
         // ... and PT_FLAG_DISPLAY_FILTER's buffers: the guide buffers, the two float4 images of the levels, the bytes pt_readback_rgba8 copies
         const size_t display = (S.flags & PT_FLAG_DISPLAY_FILTER) ? (size_t)S.P * (4 * sizeof(float4) + sizeof(uchar4)) : 0;
@@ -1292,7 +1296,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         Slot &sl = S.slot[i];
         HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
         for (int b = 0; b < 2; ++b) {
-            PTCHECK(sl.pathbuf[b].alloc(S.poolCap * kNumArrays));
+            PTCHECK(sl.pathbuf[b].alloc(S.poolCap * poolDwords(S.prm.histBits)));
             PTCHECK(sl.chunkList[b].alloc_zeroed((size_t)kSeg * S.poolChunks));
         }
         PTCHECK(sl.ctrl.alloc(1));

@@ -45,6 +45,13 @@ PtOptions effective_options(const PtOptions *opts) {
     return o;
 }
 
+// bits of one code of a path's material history (ptk::PathPool): 2 * material + (specular ? 1 : 0) < 2 nmats -- max(1, ceil(log2(2 nmats)))
+inline int history_code_bits(int nmats) {
+    int b = 1;
+    while ((1ll << b) < 2ll * nmats) ++b;
+    return b;
+}
+
 // dynamic LDS k_gbuffer needs for a scene: the lanes' mesh traversal stacks (a launch holds at most 64 KB)
 inline size_t guideStackBytes(bool mesh, int meshStackNeed) { return mesh ? (size_t)std::max(meshStackNeed, 1) * kBlock * sizeof(uint32_t) : 0; }
 
@@ -286,6 +293,10 @@ int plan_frame(const SceneIn &in, ScenePlan &p) {
     p.plain = !in.direct() && !(o.flags & PT_FLAG_MIXTURE_WEIGHTED) && !env_flag("PT_AMD_NO_PLAIN");
     for (int i = 0; i < in.nmats; ++i)
         if (in.mats[i].hasRefractive > 0.0f || (in.mats[i].hasReflective > 0.0f && in.mats[i].specularExponent > 0.0f)) p.plain = false;
+    // ... and a path's material history fits one word: the PLAIN forms' pools carry one code of history_code_bits per scatter instead of the
+    // throughput (ptk::PathPool), and traceDepth - 1 scatters lie behind a path that enters the last bounce.  A scene beyond that takes
+    // the general forms: the same frame.
+    if (history_code_bits(in.nmats) * (k.traceDepth - 1) > 32) p.plain = false;
     return PT_OK;
 }
 
@@ -866,5 +877,7 @@ int plan_scene(const SceneIn &in, ScenePlan &p) {
     plan_classes(in, p);
     PTCHECK(plan_camera_list(in, p));
     PTCHECK(plan_walks(in, p));
+    // the pools are history-coded exactly where the later bounces take the PLAIN form (pt_api.hip: bounce_form; pt_init checks the two agree)
+    p.prm.histBits = (p.plain && !p.tex && !p.mesh && !p.many) ? history_code_bits(in.nmats) : 0;
     return plan_lds(in, p);
 }

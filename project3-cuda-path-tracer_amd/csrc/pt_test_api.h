@@ -64,6 +64,18 @@ int pt_debug_trace_paths(int iter, int bounces, float *origin3, float *dir3, flo
     // the pool's three arrays (A: 16 B, B: 16 B, C: 12 B per path), chunk by chunk, into the eleven columns
     std::vector<float> cols[kNumArrays];
     for (int k = 0; k < kNumArrays; ++k) cols[k].resize(n);
+    // A history-coded pool (ptk::PathPool; B: {direction.yz, hist, pk}, no array C) comes back as the same eleven columns: the
+    // throughput is rebuilt here from `hist` -- `bounces` codes, low end first -- and the material table, by the ordered fp32 products the
+    // emitter hit takes (this file is compiled with -ffp-contract=off; products only: nothing to contract either way).
+    const int hb = R().prm.histBits;
+    std::vector<MaterialDev> hmat;
+    if (hb != 0) {
+        if (hb * bounces > 32)
+            return fail(PT_ERR_INVALID, "pt_debug_trace_paths: %d codes of %d bits do not fit a path's history word (the renderer itself scatters %d times)",
+                        bounces, hb, R().prm.traceDepth - 1);
+        hmat.resize((size_t)R().prm.nmats);
+        HIPCHECK(hipMemcpy(hmat.data(), R().dmats.p, hmat.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
+    }
     {
         std::vector<float> bufA((size_t)chunkPaths * 4), bufB((size_t)chunkPaths * 4), bufC((size_t)chunkPaths * 3);
         size_t off = 0;
@@ -77,9 +89,23 @@ int pt_debug_trace_paths(int iter, int bounces, float *origin3, float *dir3, flo
                 const size_t first = (size_t)c << R().prm.chunkShift;
                 HIPCHECK(hipMemcpy(bufA.data(), pb.arrA(first), (size_t)m * 16, hipMemcpyDeviceToHost));
                 HIPCHECK(hipMemcpy(bufB.data(), pb.arrB(first), (size_t)m * 16, hipMemcpyDeviceToHost));
-                HIPCHECK(hipMemcpy(bufC.data(), pb.arrC(first), (size_t)m * 12, hipMemcpyDeviceToHost));
+                if (hb == 0) HIPCHECK(hipMemcpy(bufC.data(), pb.arrC(first), (size_t)m * 12, hipMemcpyDeviceToHost));
                 for (uint32_t i = 0; i < m; ++i) {
                     const float *a = &bufA[4 * (size_t)i], *b = &bufB[4 * (size_t)i], *cc = &bufC[3 * (size_t)i];
+                    if (hb != 0) {
+                        uint32_t h;
+                        memcpy(&h, &b[2], sizeof h);
+                        float col[3] = {1.0f, 1.0f, 1.0f};
+                        for (int s = 0; s < bounces; ++s, h >>= hb) {
+                            const uint32_t code = h & ((1u << hb) - 1u);
+                            if ((code >> 1) >= (uint32_t)hmat.size()) return fail(PT_ERR_DEVICE, "pt_debug_trace_paths: corrupt history word");
+                            const float *t = (code & 1u) ? hmat[code >> 1].specColor : hmat[code >> 1].color;
+                            for (int q = 0; q < 3; ++q) col[q] = col[q] * t[q];
+                        }
+                        const float v[kNumArrays] = {a[0], a[1], a[2], a[3], b[0], b[1], col[0], col[1], col[2], 0.0f, b[3]};      // (no hash in such a pool; nobody reads that column)
+                        for (int k = 0; k < kNumArrays; ++k) cols[k][off + i] = v[k];
+                        continue;
+                    }
                     const float v[kNumArrays] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3], cc[0], cc[1], cc[2]};
                     for (int k = 0; k < kNumArrays; ++k) cols[k][off + i] = v[k];
                 }
@@ -149,7 +175,7 @@ int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
     ScenePlan p;
     PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings}, p));
     *out = PtTestPlanSummary{plan_state_bits(p), p.prm.nBinned, p.prm.nWalls, p.prm.nSphCull, p.prm.nSphGroups, p.prm.nLocalPad, p.prm.firstSkipped, p.poolChunks,
-                             (uint64_t)p.ldsBytes, (uint64_t)p.ldsBytesNext};
+                             (uint64_t)p.ldsBytes, (uint64_t)p.ldsBytesNext, p.prm.histBits, 0};
     return PT_OK;
 }
 

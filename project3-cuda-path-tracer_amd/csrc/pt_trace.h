@@ -12,6 +12,9 @@ namespace ptk {
 using namespace ptd;
 
 constexpr int kNumArrays = 11;       // PathSegment: origin3, dir3, throughput3, the pixel's hash, pixelIndex | batch index = 11 dwords = 44 bytes per path
+constexpr int kNumArraysHist = 8;    // ... of a history-coded pool (PathPool; the PLAIN forms): origin3, dir3, one word of material history, pixelIndex | batch index = 32 bytes
+// dwords per path of a pool: histBits = KParams::histBits (0: the general layout)
+__host__ __device__ constexpr int poolDwords(int histBits) { return histBits ? kNumArraysHist : kNumArrays; }
 constexpr int kMaxDepthSlots = PT_MAX_DEPTH + 2;
 
 // ---- device control block ------------------------------------------------------------------------
@@ -86,6 +89,8 @@ struct KParams {
     int   ngeoms, nmats;
     int   traceDepth;
     int   pixBits;      // bits of a global pixel index (W * H - 1): PathC::pk = pixelIndex | batch index << pixBits
+    int   histBits;     // 0: the pools carry a path's throughput (44 B per path).  b > 0: the PLAIN forms' pools carry its material HISTORY instead
+                        // (32 B, see PathPool): one code of b bits per scatter, 2 * material + (specular ? 1 : 0), b = max(1, ceil(log2(2 nmats)))
     int   poolChunks;   // chunks of a path pool (chunk 0 is the trash chunk: never handed out, written only after a fault)
     int   chunkShift;   // log2(paths per chunk), >= kMinChunkShift
     int   sceneRect[4]; // union of the primitives' pixel rectangles (GeomDev::rect): camera rays outside miss everything
@@ -170,6 +175,15 @@ struct KParams {
 // list[s * poolChunks + j] = {generation : 32 | chunk : 32} of the j-th chunk (j >= 1) of segment s of the queue the pool
 // holds; the generation is the serial number of the launch that filled the queue, so entries of earlier launches read as
 // "not there yet" without any clearing.  The 0-th chunk of segment s is always chunk 1 + s.
+// HISTORY-CODED pools (KParams::histBits > 0: the scenes whose later bounces take k_bounce<false, ..., PLAIN>).  In those forms a path's
+// throughput is only ever multiplied by a material's colour or specular colour, once per scatter, starting from (1, 1, 1), and only read when
+// the path ends on an emitter: it is a function of the ordered list of (material, diffuse | specular) choices.  The pool carries that list
+// -- `hist`, code k (b bits) at bit b * (k - 1) for the scatter of bounce k; the bounce is launch-uniform, so the list needs no length -- and
+// the emitter hit replays the products in order with the same fp32 multiplications (no additions: nothing to contract; 1 * x = x exactly):
+// bit-identical.  A as above; B: float4 {direction.yz, hist, pixelIndex | batch index << pixBits}; NO array C: 32 bytes per path, 2 + 2
+// vector-memory instructions.  The pixel's hash is computed again at every scatter (~20 integer instructions, as in rounds 1-4): measured
+// against the 36-byte form that keeps it in a one-dword array C, the 32-byte form is 4 % faster on C2 (profiles/path_history.txt).
+// (k_mesh_walk's view -- A and B's first eight bytes -- holds.)
 struct PathPool {
     float              *base;
     unsigned long long *list;
@@ -406,6 +420,7 @@ struct BounceArgs {
     TileArgs tile;                      // (first: offset 0)
     KParams prm;
     int iter, batch, depth, lastBounce, parity;
+    int histShift;                      // history-coded pools: where this bounce's scatter appends its code, prm.histBits * (depth - 1)
     uint32_t genIn, genOut;             // serial numbers of the launches that filled / fill the input / output pool
     PathPool in, out;
     Ctrl *ctrl;
@@ -742,7 +757,12 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
         const float *base;                  // the input pool's arrays (from setupTile's one scalar load to loadTile; dead afterwards)
         uint32_t cap;
     };
-    struct PathRegs { F3 org, dir, col; uint32_t pixHash, pk; };
+    // PLAIN: the pools are history-coded (PathPool) -- `hist` stands where the general forms carry `col`
+    constexpr bool HIST = PLAIN;
+    // ... and the one general form whose survivors a PLAIN launch can read: the camera-ray bounce with a lens, which has no PLAIN form of its
+    // own (bounce_form).  It writes whichever layout the renderer's pools have (KParams::histBits), its scatter's code beside its product.
+    constexpr bool kFeedsHist = FIRST && DOF && !MANY && !MESH && !TEX;
+    struct PathRegs { F3 org, dir, col; uint32_t pixHash, pk, hist; };
     // tile T of the queue -> its segment, class and the lane's slot; false: the tile needs no work at all
     auto setupTile = [&](uint32_t T, uint32_t tid, TileMeta &m) -> bool {
         // everything the set-up needs from the argument block: one scalar load, in flight while the segment is looked up in LDS
@@ -792,12 +812,20 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
             const size_t cap = (size_t)m.cap;
             const float4 a = *reinterpret_cast<const float4 *>(src + 16 * (size_t)m.idx);
             const float4 b = *reinterpret_cast<const float4 *>(src + 16 * cap + 16 * (size_t)m.idx);
-            const PathC c = *reinterpret_cast<const PathC *>(src + 32 * cap + 12 * (size_t)m.idx);
-            r.org = f3(a.x, a.y, a.z);
-            r.dir = f3(a.w, b.x, b.y);
-            r.col = f3(b.z, b.w, c.cz);
-            r.pixHash = c.pixHash;
-            r.pk = c.pk;                                        // pixelIndex | batch index << pixBits
+            if (HIST) {
+                // (history-coded: 16 + 16 bytes)
+                r.org = f3(a.x, a.y, a.z);
+                r.dir = f3(a.w, b.x, b.y);
+                r.hist = __float_as_uint(b.z);
+                r.pk = __float_as_uint(b.w);                    // pixelIndex | batch index << pixBits
+            } else {
+                const PathC c = *reinterpret_cast<const PathC *>(src + 32 * cap + 12 * (size_t)m.idx);
+                r.org = f3(a.x, a.y, a.z);
+                r.dir = f3(a.w, b.x, b.y);
+                r.col = f3(b.z, b.w, c.cz);
+                r.pixHash = c.pixHash;
+                r.pk = c.pk;                                    // pixelIndex | batch index << pixBits
+            }
         }
     };
     // ---- camera rays from the packed work list (pinhole scenes without meshes or many small primitives, where pt_init built one:
@@ -831,7 +859,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
     // the first tile of this workgroup that needs work, and its paths
     uint32_t T = blockIdx.x - rowShift;      // (FIRST with rotated bands: the first tile of the row; else the tile itself)
     TileMeta nextMeta = {false, 0u, 0u, nullptr, 0u};
-    PathRegs nextRegs = {f3(0, 0, 0), f3(0, 0, 1), f3(0, 0, 0), 0, 0};
+    PathRegs nextRegs = {f3(0, 0, 0), f3(0, 0, 1), f3(0, 0, 0), 0, 0, 0};
     if (!FIRST) {
         while (T < numTiles && !setupTile(T, threadIdx.x, nextMeta)) T += gridDim.x;
         if (T < numTiles) loadTile(nextMeta, nextRegs);
@@ -935,7 +963,9 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
         uint32_t pkCur = __float_as_uint(anyFloat());           // later bounces: pixelIndex | batch index << pixBits, as loaded (ONE register
                                                                 // across the tile; the iteration is shifted out where it is needed)
         auto iterOf = [&]() -> int { return FIRST ? itb : (int)(pkCur >> (uint32_t)launder(kargs)->prm.pixBits); };
-        uint32_t pixHash = __float_as_uint(anyFloat());         // utilhash(pix): FIRST computes it (the camera jitter's and the scatter's engines share it), later bounces load it
+        uint32_t pixHash = __float_as_uint(anyFloat());         // utilhash(pix): FIRST computes it (the camera jitter's and the scatter's engines share it), later bounces load it (HIST: compute it at the scatter)
+        uint32_t hist = 0u;                                     // HIST: the path's material history (PathPool); none yet behind the camera
+        if (HIST && !FIRST) hist = __float_as_uint(anyFloat());
         if (valid) {
             // Camera rays (FIRST): a primitive is reachable only from the pixels inside the projection of its bounding
             // cube (GeomDev::rect, 2-pixel margin >> any rounding of the reference's tests), and nothing is reachable
@@ -975,18 +1005,26 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         dir = normalize(focus - org);
                     }
                 }
-                col = f3(1.0f, 1.0f, 1.0f);
+                if (!HIST) col = f3(1.0f, 1.0f, 1.0f);
             } else {
-                org = cur.org; dir = cur.dir; col = cur.col;        // requested one tile ahead (loadTile)
+                org = cur.org; dir = cur.dir;                       // requested one tile ahead (loadTile)
+                if (!HIST) col = cur.col;
                 // The pixel index and the packed word outlive the next tile's loads (the stores need them), so they cannot stay in the
                 // register tuple array C's element is loaded into: their copies out of it are made HERE, where the data has long
                 // arrived.  (Left to itself the register allocator copied the NEXT tile's pixel index right behind its load -- v_mov
                 // behind s_waitcnt vmcnt(2) -- and every wave sat out a memory round trip BEFORE the compaction's barriers instead of
                 // under them: the "3 loads issued: 7 %" of round 3's timeline.)
-                uint32_t chash = cur.pixHash, cpk = cur.pk;
-                if (!MANY) asm volatile("" : "+v"(chash), "+v"(cpk));      // (sphere-heavy variants: no register to spare for the copies)
-                pixHash = chash;
-                pkCur = cpk;
+                if (HIST) {                                         // (hist and pk ride in B's tuple; no hash: the scatter computes it)
+                    uint32_t chist = cur.hist, cpk = cur.pk;
+                    asm volatile("" : "+v"(chist), "+v"(cpk));
+                    hist = chist;
+                    pkCur = cpk;
+                } else {
+                    uint32_t chash = cur.pixHash, cpk = cur.pk;
+                    if (!MANY) asm volatile("" : "+v"(chash), "+v"(cpk));      // (sphere-heavy variants: no register to spare for the copies)
+                    pixHash = chash;
+                    pkCur = cpk;
+                }
             }
 
             if (FIRST) { if (inScene) probe(8); } else probe(7);                                   // tiles (waves with at least one valid path) and valid paths
@@ -1625,6 +1663,24 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         // Deferred accumulation: iterations overlap on several streams, so the radiance
                         // is parked in this iteration's own buffer (one path per pixel: race-free, no
                         // read) and k_commit adds it to the accumulator in iteration order.
+                        if (HIST) {
+                            // the throughput, replayed from the history: the colour or specular colour of each scatter's material, in
+                            // the scatters' order, by the multiplications the general forms do one per bounce (PathPool).  The trip
+                            // count is the launch's -- depth - 1 scatters lie behind every path of it -- and stays in scalar registers.
+                            col = f3(1.0f, 1.0f, 1.0f);
+                            if (!FIRST) {
+                                const uint32_t hb = (uint32_t)A->prm.histBits, steps = (uint32_t)A->depth - 1u;
+                                const uint32_t mask = (1u << hb) - 1u;
+                                uint32_t h = hist;
+                                for (uint32_t s = 0; s < steps; ++s) {
+                                    const uint32_t code = h & mask;
+                                    h >>= hb;
+                                    const MaterialDev &Mk = smats[code >> 1];
+                                    const float *const t = (code & 1u) ? Mk.specColor : Mk.color;
+                                    col = col * f3(t[0], t[1], t[2]);
+                                }
+                            }
+                        }
                         const F3 c = (col * mcol) * mEmit;
                         // (index of the pixel in the radiance buffers: the frame's, or, for a row shard, the shard's own)
                         size_t frame = (size_t)A->prm.W * A->prm.H;
@@ -1647,11 +1703,14 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     }
                 } else if (!(hotNow() & kHotLast)) {                  // S6 scatter (S7: skipped on the last bounce)
                     probe(10);
+                    // (HIST: a history-coded pool does not carry the pixel's hash)
+                    if (HIST && !FIRST) pixHash = utilhash(pkCur & ((1u << (uint32_t)launder(kargs)->prm.pixBits) - 1u));
                     Rng rng = seedEngine(s_iterHash[iterOf()] ^ pixHash);   // = makeSeededRandomEngineHashed(., pix)
                     const F3 scol = f3(M.specColor[0], M.specColor[1], M.specColor[2]);
                     F3 ndir = dir, norg;
                     bool diffuse = false;                        // the hemisphere is sampled at one place, after the branches
                     bool through = false;                        // (BUMP: the new ray is the transmitted one)
+                    uint32_t hcode = 0u;                         // (HIST: the specular bit of this scatter's code)
                     if (!PLAIN && mRefr > 0.0f) {
                         const float eta = outside ? M.invIor : M.ior;
                         const float c = dot(Ns, dir);
@@ -1685,7 +1744,8 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         if (u < 0.5f) {
                             ndir = reflect(dir, Ns);
                             if (!PLAIN && M.invSpecExp1 > 0.0f) ndir = specularLobeDirection(ndir, Ns, M.invSpecExp1, rng);   // SPECEX > 0
-                            col = col * scol;
+                            if (HIST || kFeedsHist) hcode = 1u;
+                            if (!HIST) col = col * scol;
                         } else {
                             diffuse = true;
                         }
@@ -1736,10 +1796,14 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             // in scratch across this block -- the scratch traffic inside the tile loop of the non-PLAIN later-bounce kernel,
                             // VERDICT round 5 weak #4; C4 itself never enters this block)
                             rng.x = __float_as_uint(anyFloat());
-                        } else {
+                        } else if (!HIST) {
                             col = col * mcol;
                         }
                     }
+                    // HIST: the scatter appends its code -- 2 * material + (specular ? 1 : 0) -- where the general forms multiply
+                    // (kFeedsHist: a code that only a history-coded pool keeps; bounce 1 appends at bit 0)
+                    if (HIST) hist |= (2u * (uint32_t)ghMaterial + hcode) << (uint32_t)launder(kargs)->histShift;
+                    else if (kFeedsHist) hist = 2u * (uint32_t)ghMaterial + hcode;
                     if (diffuse && !toLight) {
                         probe(11);
                         float up, cOver, sOver;
@@ -1929,10 +1993,15 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 char *const dst = reinterpret_cast<char *>(A->out.base);
                 const size_t ocap = (size_t)A->out.cap;
                 *reinterpret_cast<float4 *>(dst + 16 * (size_t)slot) = make_float4(org.x, org.y, org.z, dir.x);
-                *reinterpret_cast<float4 *>(dst + 16 * ocap + 16 * (size_t)slot) = make_float4(dir.y, dir.z, col.x, col.y);
-                PathC c;
-                c.cz = col.z; c.pixHash = pixHash; c.pk = FIRST ? ((uint32_t)pix | ((uint32_t)itb << (uint32_t)launder(kargs)->prm.pixBits)) : pkCur;
-                *reinterpret_cast<PathC *>(dst + 32 * ocap + 12 * (size_t)slot) = c;
+                if (HIST || (kFeedsHist && A->prm.histBits != 0)) {      // (history-coded: 16 + 16 bytes; kFeedsHist: wave-uniform)
+                    const uint32_t pk = FIRST ? ((uint32_t)pix | ((uint32_t)itb << (uint32_t)launder(kargs)->prm.pixBits)) : pkCur;
+                    *reinterpret_cast<float4 *>(dst + 16 * ocap + 16 * (size_t)slot) = make_float4(dir.y, dir.z, __uint_as_float(hist), __uint_as_float(pk));
+                } else {
+                    *reinterpret_cast<float4 *>(dst + 16 * ocap + 16 * (size_t)slot) = make_float4(dir.y, dir.z, col.x, col.y);
+                    PathC c;
+                    c.cz = col.z; c.pixHash = pixHash; c.pk = FIRST ? ((uint32_t)pix | ((uint32_t)itb << (uint32_t)launder(kargs)->prm.pixBits)) : pkCur;
+                    *reinterpret_cast<PathC *>(dst + 32 * ocap + 12 * (size_t)slot) = c;
+                }
             }
             // No third barrier: the counts are double-buffered.  The other half was last read in the previous tile, and every
             // wave finished those reads before it arrived at THIS tile's first barrier, so each wave may now clear its own
