@@ -114,6 +114,12 @@ enum {
                                     its own -- is filtered under a variance estimated from its neighbours' luminance moments; with
                                     PT_FLAG_DISPLAY_FILTER the display's first frame is filtered too.  From two samples on everything is the
                                     unflagged renderer's bit for bit, launch for launch.  PT_ERR_INVALID without PT_FLAG_MOMENTS. */
+    PT_FLAG_DEMODULATE = 512,    /* albedo demodulation (section "demodulation" below): the renderer also keeps, per pixel, the sum of the first-hit
+                                    albedo of every committed iteration's camera ray (one more device buffer of W*H float4, always the library's
+                                    own), and pt_denoise_var / pt_denoise_var_rgba8 -- under PT_FLAG_DISPLAY_FILTER the display path too -- divide
+                                    the pixel's mean albedo out in front of the filter's levels and multiply it back behind them.  Everything else
+                                    is the unflagged renderer's bit for bit.  PT_ERR_INVALID without PT_FLAG_MOMENTS, with PT_FLAG_TEMPORAL, with
+                                    PT_FLAG_TRACE_AHEAD, and for a scene whose guide buffers cannot be made. */
     PT_FLAG_DIRECT_LIGHTING = 4/* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
@@ -458,6 +464,37 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
  * PT_SPATIAL_RADIUS is chosen by the study of tests/test_spatial_var_cpu.py (README, "Spatial variance"). */
 #define PT_SPATIAL_MIN_COUNT 2.0f
 #define PT_SPATIAL_RADIUS 1
+
+/* ---- demodulation (PT_FLAG_DEMODULATE, with PT_FLAG_MOMENTS; csrc/pt_albedo.h gives every operation, tests/demod_ref.py restates it).  No
+ * function of its own: a flag, and what pt_iterate*, pt_denoise_var* and, under PT_FLAG_DISPLAY_FILTER, the display path do under it.
+ *   The variance-guided filter handles textures worst: a texel border under its stencil is an edge the luminance term can only keep by
+ *   keeping the noise.  Under the flag the filter's levels see the light that reaches the surface instead: every pixel's colour is divided by
+ *   its MEAN first-hit albedo A over the very iterations that were committed, filtered, and multiplied by A again.
+ *   The albedo accumulator: pt_init allocates one more image of its own, W*H float4 (.xyz the albedo sum, .w the number of iterations added),
+ *   zeroed, and counts it in its memory check.  Every pt_iterate / pt_iterate_batch -- pt_iterate_until's rounds included -- enqueues one
+ *   more launch for its iterations first_iter .. first_iter + count - 1 on the renderer's stream, without a host synchronisation: per pixel
+ *   and iteration the nearest hit of the camera ray the renderer traces (its jitter, its lens sample), found as pt_gbuffer finds it, adds
+ *     (1, 1, 1)                                  for a miss, and for a hit whose material emits, reflects or refracts (emittance > 0,
+ *                                                hasReflective > 0, hasRefractive > 0; a mesh face's own material where it has one)
+ *     material colour x the bound texture's texel  otherwise: the colour the path is multiplied with at that hit, to the bit
+ *   in ascending order of the iterations, one fp32 addition per channel: a batch equals its single calls bit for bit.
+ *   The filter: with n = (float)samples and eps = PT_DEMOD_MIN_ALBEDO, A.k = max(Asum.k / n, eps) (a NaN gives eps).  In front of level 0 the
+ *   pixel's (c, v) -- the accumulators' mean and variance, or at one sample under PT_FLAG_SPATIAL_VARIANCE the estimate's -- becomes
+ *   (c / A, v rho^2), rho = lum(c / A) / lum(c) (1 where lum(c) is not positive): the relative standard error of the luminance is kept.  The
+ *   levels run as without the flag, level 0 as a later level at step 1.  The last level stores co * A for its filtered colour co and, where
+ *   the variance is asked for, vo rho'^2 with rho' = lum(co * A) / lum(co) (1 where lum(co) is not positive) -- or the bytes of co * A, so
+ *   the display path stays one fused launch.
+ *   pt_denoise_var, pt_denoise_var_rgba8 and, with PT_FLAG_DISPLAY_FILTER, pt_iterate(.., rgba8_dev) / pt_readback_rgba8 give that result;
+ *   their `samples` refusals stay.  `samples` should be the number of iterations committed: the sums are divided by it.
+ *   Both accumulators, every other read-back, pt_variance, pt_noise_stats, pt_iterate_until, pt_denoise and pt_gbuffer are the unflagged
+ *   renderer's bit for bit, and a renderer without the flag launches exactly what it launched before.
+ *   pt_init answers PT_ERR_INVALID, before anything is touched, to the flag without PT_FLAG_MOMENTS (so: with row shards, and from
+ *   pt_group_init), with PT_FLAG_TEMPORAL (history carries no albedo yet), with PT_FLAG_TRACE_AHEAD (judged on the caller's flags), and for a
+ *   scene whose guide buffers cannot be made.  A thin lens, direct lighting, PT_FLAG_DISPLAY_FILTER and PT_FLAG_SPATIAL_VARIANCE go with it.
+ *   Known cost: mirrors, glass and lights stay un-demodulated; at high sample counts on textures with (nearly) black texels the floor eps
+ *   makes the demodulated filter lose a little to the plain one (README, "Demodulation").
+ * PT_DEMOD_MIN_ALBEDO is chosen by the study of tests/test_demod_cpu.py among 1/256, 1/64 and 1/16 (README, "Demodulation"). */
+#define PT_DEMOD_MIN_ALBEDO 0.015625f
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

@@ -231,6 +231,22 @@ int pt_test_history(int32_t *wh2, float *hc4, float *hn, float *hpos_t4, float *
  * events, after one untimed launch. */
 int pt_test_spatial_variance(int radius, int form, int w, int h, const float *m4, const float *n, const float *pos_t4, const float *nrm_id4,
                              float sigma_normal, float sigma_position, float *out4, int reps, float *ms);
+/* albedo demodulation (pt_amd.h, csrc/pt_albedo.h).
+ * pt_test_albedo: the albedo sums of THIS library's renderer (PT_FLAG_DEMODULATE) behind everything enqueued, W * H * 4 floats: .xyz the sum of
+ * the committed iterations' first-hit albedo, .w their number.  Synchronises.
+ * pt_test_demodulate: k_demodulate and the levels behind it over host arrays of any w x h, no renderer needed: `levels` levels of the
+ * variance-guided filter, level 0 as a later level at step 1, the last one AtrousDemod's, every level in the form named (1: the plain gather,
+ * 2 / 3: LDS tiles of 64 x 4 / 64 x 8 pixels -- every form gives the same bits).  asum4 = the albedo sums (w * h * 4), samples >= 1 the count
+ * they are divided by, min_albedo the floor.  inplace 0: k_demodulate reads the accumulators rgb_sum (w * h * 3) and lum_sq_sum (w * h),
+ * samples >= 2, img4 unused; inplace 1: it rewrites img4 (w * h * 4: r, g, b, variance), the accumulators unused.  pos_t4 / nrm_id4: the guide buffers as the device holds
+ * them; the sigmas as pt_denoise_var takes them.  demod4_out (or NULL): k_demodulate's image.  bytes 0: rgb_out (w * h * 3) and var_out (or
+ * NULL) receive the last level's packed RGB and variance; bytes 1: rgba_out (w * h * 4 bytes) receives its BYTES form's, rgb_out / var_out
+ * unused.  ms (or NULL) with reps >= 1: 2 * reps kernel times by HIP events, {k_demodulate, the last level} alternating, after one untimed
+ * run (a timed inplace run demodulates an image again and again: its results are void). */
+int pt_test_albedo(float *asum4_host);
+int pt_test_demodulate(int form, int inplace, int bytes, int w, int h, int samples, int levels, const float *rgb_sum, const float *lum_sq_sum, const float *img4,
+                       const float *asum4, const float *pos_t4, const float *nrm_id4, float sigma_lum, float sigma_normal, float sigma_position,
+                       float min_albedo, float *demod4_out, float *rgb_out, float *var_out, uint8_t *rgba_out, int reps, float *ms);
 /* the noise statistics (pt_amd.h, csrc/pt_noise.h): k_noise_stats -- the kernel pt_noise_stats launches -- over host arrays of any w x h, no
  * renderer needed: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h); out, tile_rel_var_host (or NULL) as pt_noise_stats.  tiles_per_wave: how many
  * tiles a wave of the grid takes, 1..64, 0 = the library's choice -- every value gives the same bits.  ms (or NULL) with

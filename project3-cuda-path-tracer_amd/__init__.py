@@ -56,6 +56,9 @@ PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_ITER, PT_DISPLAY_SIGMA_LUM, PT_DISPLAY_SIGMA
 PT_FLAG_SPATIAL_VARIANCE = 256
 # the spatial variance estimate (include/pt_amd.h): the count below which a pixel takes it, and the radius of its window
 PT_SPATIAL_MIN_COUNT, PT_SPATIAL_RADIUS = 2.0, 1
+PT_FLAG_DEMODULATE = 512
+# albedo demodulation (include/pt_amd.h): the floor of a pixel's mean first-hit albedo
+PT_DEMOD_MIN_ALBEDO = 0.015625
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -86,7 +89,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
-    "pt_test_display", "pt_test_spatial_variance",
+    "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce",
 ]
 
@@ -263,6 +266,8 @@ def _bind(L, with_tests):
         L.pt_test_history.argtypes = [vp] * 6
         L.pt_test_display.argtypes = [i32, i32, i32, vp, vp]
         L.pt_test_spatial_variance.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, vp]
+        L.pt_test_albedo.argtypes = [vp]
+        L.pt_test_demodulate.argtypes = [i32] * 7 + [vp] * 6 + [C.c_float] * 4 + [vp] * 4 + [i32, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
@@ -449,8 +454,12 @@ _scene = None
 
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
-                  mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False):
+                  mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False, demodulate=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    demodulate: PT_FLAG_DEMODULATE (with moments=True; not with temporal or trace_ahead) -- every pathtrace / pathtrace_batch also adds the
+    first-hit albedo of its iterations' camera rays to a per-pixel sum, and denoise_var / denoise_var_rgba8 -- with display_filter=True the
+    display's bytes too -- divide the pixel's mean albedo out in front of the filter and multiply it back behind it: textures survive.
+    Everything else is the unflagged renderer's.
     spatial_variance: PT_FLAG_SPATIAL_VARIANCE (with moments=True) -- denoise_var / denoise_var_rgba8 accept samples=1: a pixel with fewer than
     PT_SPATIAL_MIN_COUNT effective samples is filtered under a variance estimated from its neighbours, and with display_filter=True the first
     displayed frame is filtered too.  From two samples on everything is the unflagged renderer's.
@@ -479,6 +488,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_DISPLAY_FILTER
     if spatial_variance:
         flags |= PT_FLAG_SPATIAL_VARIANCE
+    if demodulate:
+        flags |= PT_FLAG_DEMODULATE
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -886,6 +897,43 @@ def test_spatial_variance(radius, form, w, h, m4, n, pos_t, nrm_id, sigma_normal
     _tcheck(test_lib().pt_test_spatial_variance(radius, form, w, h, _p(M), _p(N), _p(pos), _p(nrm), sigma_normal, sigma_position, _p(out), timing_reps,
                                                 _p(ms) if timing_reps > 0 else None))
     return (out, ms) if timing_reps > 0 else out
+
+
+def test_albedo():
+    """pt_test_albedo (inside renderer_from_test_library, a demodulate=True renderer): the albedo sums, (npixels, 4) -- [:, :3] the sum of the
+    committed iterations' first-hit albedo, [:, 3] their number."""
+    out = np.empty((_frame_pixels(), 4), np.float32)
+    _tcheck(test_lib().pt_test_albedo(_p(out)))
+    return out
+
+
+def test_demodulate(form, w, h, samples, levels, asum, pos_t, nrm_id, rgb_sum=None, lum_sq_sum=None, img=None, bytes_out=False, want_var=True,
+                    sigma_lum=DENOISE_SIGMA_LUM, sigma_normal=DENOISE_SIGMA_NORMAL, sigma_position=DENOISE_SIGMA_POSITION,
+                    min_albedo=PT_DEMOD_MIN_ALBEDO, timing_reps=0):
+    """k_demodulate and the `levels` levels behind it over host arrays (test library, no renderer; pt_test_demodulate): asum (h, w, 4) the albedo
+    sums, the guide buffers as test_temporal takes them, every level in `form` (1 the gather, 2 / 3 the tiles), the last one AtrousDemod's.
+    img=None: from the accumulators rgb_sum (h, w, 3), lum_sq_sum (h, w); img (h, w, 4) = (r, g, b, variance): rewritten in place.
+    Returns a dict: "demod" (h * w, 4) k_demodulate's image, and "rgb" (h * w, 3) with "var" (h * w,) or None -- or, bytes_out=True, "rgba"
+    (h * w, 4) uint8; timing_reps > 0: also "ms" (reps, 2), k_demodulate's and the last level's kernel times."""
+    f = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(w * h * k)
+    inplace = img is not None
+    A, pos, nrm = f(asum, 4), f(pos_t, 4), f(nrm_id, 4)
+    S = None if inplace else f(rgb_sum, 3)
+    Q = None if inplace else f(lum_sq_sum, 1)
+    I = f(img, 4) if inplace else None
+    demod = np.empty((w * h, 4), np.float32)
+    rgb = None if bytes_out else np.empty((w * h, 3), np.float32)
+    var = np.empty(w * h, np.float32) if (want_var and not bytes_out) else None
+    rgba = np.empty((w * h, 4), np.uint8) if bytes_out else None
+    ms = np.zeros((max(timing_reps, 1), 2), np.float32)
+    q = lambda a: None if a is None else _p(a)
+    _tcheck(test_lib().pt_test_demodulate(form, 1 if inplace else 0, 1 if bytes_out else 0, w, h, samples, levels, q(S), q(Q), q(I), _p(A), _p(pos), _p(nrm),
+                                          sigma_lum, sigma_normal, sigma_position, min_albedo, _p(demod), q(rgb), q(var), q(rgba), timing_reps,
+                                          _p(ms) if timing_reps > 0 else None))
+    res = {"demod": demod, "rgb": rgb, "var": var, "rgba": rgba}
+    if timing_reps > 0:
+        res["ms"] = ms
+    return res
 
 
 def test_history():

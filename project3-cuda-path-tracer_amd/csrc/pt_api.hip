@@ -30,6 +30,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -44,6 +45,7 @@
 #include "pt_noise.h"
 #include "pt_temporal.h"
 #include "pt_spatial_var.h"
+#include "pt_albedo.h"
 // The entry points of include/pt_amd_test.h (device primitives one by one, soundness sweeps, the fault-word hook) exist only in
 // the second link target of this source, libpt_amd_test.so (-DPT_TEST_API): the product library exports none of them.
 #ifdef PT_TEST_API
@@ -213,6 +215,7 @@ struct State : PlanScalars {
     DevBuf<uchar4> dnRgba;          // pt_denoise_rgba8's bytes, and pt_readback_rgba8's under PT_FLAG_DISPLAY_FILTER
     DevBuf<float> dnVar;            // pt_variance's / pt_denoise_var's variance image
     DevBuf<float> dnCount;          // PT_FLAG_SPATIAL_VARIANCE: the effective sample counts of a one-sample frame (pt_spatial_var.h); pt_init's
+    DevBuf<float4> albedo;          // PT_FLAG_DEMODULATE: per pixel (the sum of the committed iterations' first-hit albedo, their number) (pt_albedo.h); pt_init's
     int dnGuideIter = 0;
     // the noise statistics (pt_noise.h), all allocated on first use: the frame's two result words on the device, the tile map, and -- for
     // pt_iterate_until, whose checks the host reads while the stream runs on -- two copies of the words in page-locked memory, each with the
@@ -697,6 +700,12 @@ const void *atrous_kernel(bool first, bool last, bool bytes, int form) {
                  : (last ? atrous_forms<Filter, false, true>(form) : atrous_forms<Filter, false, false>(form));
 }
 
+// ... and of a description that differs from its filter in the last level's store alone (AtrousDemod): <false, true, ., BYTES> and no other
+template <class Last>
+const void *atrous_last_kernel(bool bytes, int form) {
+    return bytes ? atrous_forms<Last, false, true, true>(form) : atrous_forms<Last, false, true>(form);
+}
+
 // timing events that go away on every path out of their scope
 struct EventSet {
     hipEvent_t ev[10] = {nullptr};
@@ -756,13 +765,17 @@ int ensure_guides(int guideIter, float *ms) {
 // than the pair in profiles/display_cost.txt; R().dnOut is not touched then), or by k_to_rgba8 of R().dnOut behind it -- the test build's
 // reference -- which belongs to the last level's time in `ms`.  A last level that reads the accumulators (levels 1, not blended) has no fused
 // form and takes the two launches.
-template <class Filter, class Params, class Front>
-int atrous_run(typename Filter::Args &A, int samples, const Params *p, float sigmaColour, int form, float *ms, const char *who, bool blended, Front front,
+// Last: the description of the last level where it is not the filter's own (AtrousDemod: its Args extend the filter's, and the levels below
+// the last are the filter's kernels over the part they share); such a run is always `blended`.
+template <class Filter, class Last = Filter, class Params, class Front>
+int atrous_run(typename Last::Args &A, int samples, const Params *p, float sigmaColour, int form, float *ms, const char *who, bool blended, Front front,
                uchar4 *bytesOut = nullptr, bool fused = true) {
     if (p->levels < 1 || p->levels > 8) return fail(PT_ERR_INVALID, "%s: levels must be 1..8", who);
     for (float sg : {sigmaColour, p->sigma_normal, p->sigma_position})
         if (!(sg > 0.0f)) return fail(PT_ERR_INVALID, "%s: a sigma must be > 0 (+inf switches its term off)", who);
     if (form < kAtrousAuto || form > kAtrousTiled8) return fail(PT_ERR_INVALID, "%s: unknown kernel form %d", who, form);
+    constexpr bool ownLast = std::is_same<Filter, Last>::value;
+    if (!ownLast && !blended) return fail(PT_ERR_INVALID, "%s: internal error: a last level of its own needs a blended level 0", who);
     PTCHECK(ensure_guides(p->guide_iter, ms));
     const size_t P = (size_t)R().P;
     const bool bytesFused = Filter::kVariance && bytesOut && fused && (p->levels > 1 || blended);
@@ -795,9 +808,12 @@ int atrous_run(typename Filter::Args &A, int samples, const Params *p, float sig
             f = kAtrousGather;
             grid = atrousGridGather(A.W, A.H);
         }
-        void *kargs[] = {&A};
+        void *kargs[] = {&A};       // (Last::Args begins with Filter::Args: a level below the last reads the part it knows)
+        const void *kernel;
+        if constexpr (ownLast) kernel = atrous_kernel<Filter>(first, last, last && bytesFused, f);
+        else kernel = last ? atrous_last_kernel<Last>(bytesFused, f) : atrous_kernel<Filter>(false, false, false, f);
         if (ms) HIPCHECK(hipEventRecord(ev[i], R().stream));
-        HIPCHECK(hipLaunchKernel(atrous_kernel<Filter>(first, last, last && bytesFused, f), dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
+        HIPCHECK(hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(kBlock), kargs, 0, R().stream));
     }
     if (bytesOut && !bytesFused) {
         // sendImageToPBO's conversion of the filtered MEAN: k_to_rgba8 with one sample (x / 1 is exact)
@@ -949,6 +965,31 @@ int spatial_launch(SpatialArgs &A, int radius, int form, hipStream_t st) {
     return PT_OK;
 }
 
+// ---- albedo demodulation (pt_albedo.h) ------------------------------------------------------------------------------------------------------
+// k_albedo for iterations first .. first + count - 1 of the renderer's scene, on its stream: no host synchronisation
+int albedo_launch(int first, int count) {
+    const State &S = R();
+    AlbedoArgs A;
+    A.prm = S.prm;
+    A.ggeoms = S.dgeoms.p; A.gmats = S.dmats.p;
+    A.meshRecs = reinterpret_cast<const float4 *>(S.dMeshRecs.p);
+    A.texGeom = S.tex ? S.dTexGeom.p : nullptr;       // (a scene without a bound texture has no table)
+    A.texDesc = S.dTexDesc.p; A.texels = S.dTexels.p; A.texUV = S.dTexUV.p;
+    A.firstIter = first; A.count = count;
+    A.asum = S.albedo.p;
+    hipLaunchKernelGGL(k_albedo, dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), guide_stack_bytes(), S.stream, A);
+    HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
+int demod_launch(DemodArgs &D, bool inplace, hipStream_t st) {
+    const dim3 grid((unsigned)(((size_t)D.npix + kBlock - 1) / kBlock));
+    if (inplace) hipLaunchKernelGGL(k_demodulate<true>, grid, dim3(kBlock), 0, st, D);
+    else hipLaunchKernelGGL(k_demodulate<false>, grid, dim3(kBlock), 0, st, D);
+    HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
 // ---- the second moments and the variance-guided filter (pt_denoise.h, AtrousGuided) -----------------------------------------------------
 int moments_refusals(const char *who) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
@@ -977,10 +1018,14 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     // PT_FLAG_SPATIAL_VARIANCE: the counts are Nh + samples, so only a one-sample frame holds a pixel below PT_SPATIAL_MIN_COUNT; level 0 then reads
     // the blend's colour with the variance k_spatial_variance_* gives it (pt_spatial_var.h).  From two samples on: today's launches.
     const bool spatial = samples < 2;
-    AtrousVarArgs A;
+    // PT_FLAG_DEMODULATE (pt_albedo.h): k_demodulate between the front and level 0, which then always runs as a later level at step 1, and
+    // AtrousDemod's last level, which multiplies the albedo back
+    const bool demod = (R().flags & PT_FLAG_DEMODULATE) != 0;
+    AtrousDemodArgs A;                 // (AtrousVarArgs and, behind them, what AtrousDemod's last level alone reads)
     A.moments = R().moments.p;
     A.samplesM1 = (float)(samples - 1);
-    return atrous_run<AtrousGuided>(A, samples, p, p->sigma_lum, form, ms, who, temporal || spatial, [&]() -> int {
+    A.asum = R().albedo.p; A.demodN = (float)samples; A.demodEps = PT_DEMOD_MIN_ALBEDO;
+    const auto prepare = [&]() -> int {
         if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc((size_t)R().P));
         A.outVar = wantVar ? R().dnVar.p : nullptr;       // (read by a last level alone)
         if (!temporal && !spatial) return PT_OK;
@@ -997,6 +1042,17 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
         B.invP = 1.0f / (p->sigma_position * p->sigma_position);
         B.out = R().dnPing[1].p;
         return spatial_launch(B, PT_SPATIAL_RADIUS, kSpatialForm, R().stream);
+    };
+    if (!demod) return atrous_run<AtrousGuided>(A, samples, p, p->sigma_lum, form, ms, who, temporal || spatial, prepare, bytesOut, fused);
+    return atrous_run<AtrousGuided, AtrousDemod>(A, samples, p, p->sigma_lum, form, ms, who, true, [&]() -> int {
+        PTCHECK(prepare());
+        if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc((size_t)R().P));
+        DemodArgs D;
+        D.accum = R().image; D.moments = R().moments.p;
+        D.img = R().dnPing[1].p; D.asum = R().albedo.p;
+        D.npix = R().P;
+        D.samples = (float)samples; D.samplesM1 = (float)(samples - 1); D.eps = PT_DEMOD_MIN_ALBEDO;
+        return demod_launch(D, spatial, R().stream);      // (in place on the image k_spatial_variance_* left, or from the accumulators)
     }, bytesOut, fused);
 }
 
@@ -1278,7 +1334,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         const size_t display = (S.flags & PT_FLAG_DISPLAY_FILTER) ? (size_t)S.P * (4 * sizeof(float4) + sizeof(uchar4)) : 0;
         // ... and PT_FLAG_SPATIAL_VARIANCE's one image, the counts
         const size_t spatial = (S.flags & PT_FLAG_SPATIAL_VARIANCE) ? (size_t)S.P * sizeof(float) : 0;
-        const size_t need = perSlot * (size_t)S.nslots + display + spatial;
+        // ... and PT_FLAG_DEMODULATE's one image, the albedo sums
+        const size_t albedo = (S.flags & PT_FLAG_DEMODULATE) ? (size_t)S.P * sizeof(float4) : 0;
+        const size_t need = perSlot * (size_t)S.nslots + display + spatial + albedo;
         size_t freeB = 0, totalB = 0;
         HIPCHECK(hipMemGetInfo(&freeB, &totalB));
         if (need > freeB)
@@ -1292,6 +1350,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         PTCHECK(S.dnRgba.alloc((size_t)S.P));
     }
     if (S.flags & PT_FLAG_SPATIAL_VARIANCE) PTCHECK(S.dnCount.alloc((size_t)S.P));
+    if (S.flags & PT_FLAG_DEMODULATE) PTCHECK(S.albedo.alloc_zeroed((size_t)S.P));
     for (int i = 0; i < S.nslots; ++i) {
         Slot &sl = S.slot[i];
         HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
@@ -1443,6 +1502,8 @@ int pt_iterate_batch(int frame, int first_iter, int count, void *rgba8_dev) {
         HIPCHECK(hipEventRecord(sl.evCommitted, R().stream));
         R().seq += 1;
     }
+    // PT_FLAG_DEMODULATE: the albedo of the iterations just committed, behind the commit on the caller's stream (never with batches traced ahead)
+    if (R().flags & PT_FLAG_DEMODULATE) PTCHECK(albedo_launch(first_iter, count));
     if (rgba8_dev && (R().flags & PT_FLAG_DISPLAY_FILTER)) {
         // the display filter: the guide buffers (once), the blend with the history, the levels, the bytes -- all behind the commit
         PTCHECK(display_bytes(first_iter + count - 1, reinterpret_cast<uchar4 *>(rgba8_dev), "pt_iterate"));

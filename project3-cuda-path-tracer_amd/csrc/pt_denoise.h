@@ -5,7 +5,8 @@
 //   k_gbuffer     the guide buffers: the nearest hit of the camera rays of ONE iteration, brute force over the scene's primitives
 //   k_variance    the variance of every pixel's mean luminance, from the accumulator and the second moments (PT_FLAG_MOMENTS)
 //   k_atrous_*    one level of a filter (the hot path): a 5 x 5 stencil with holes, LDS-tiled per residue class or a plain gather.  One skeleton
-//                 each; a filter -- AtrousPlain, AtrousGuided -- is a description of its four differences (below)
+//                 each; a filter -- AtrousPlain, AtrousGuided -- is a description of its four differences (below).  (A third description,
+//                 AtrousDemod, is AtrousGuided with another last store: pt_albedo.h.)
 // Included by pt_api.hip only.
 //
 // ---- the filters, operation by operation (tests/denoise_ref.py restates the plain one in numpy, tests/denoise_var_ref.py the guided one,

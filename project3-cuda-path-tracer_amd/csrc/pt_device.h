@@ -995,9 +995,11 @@ __device__ __forceinline__ bool meshPlanesPass(uint32_t w0, uint32_t w1, uint32_
 // object-space vector the normal is made of -- here the unit face normal -- and `outside` = front side).
 // (NaN operands: every triangle test fails whatever the slab tests say -- a, or s, is NaN -- like in the oracle's loop.)
 // `faceMat`: 1 + the scene material of the triangle that was hit when it has one of its own (`usemtl`), else 0.
-template <bool CAM_ORIGIN = false, int STRIDE = 256, typename GD>
-__device__ __forceinline__ float meshIntersectionTest(const GD &g, const float4 *recs, uint32_t root, uint32_t stride, uint32_t *stack,
-                                                      F3 ro_w, F3 rd_w, F3 &P, F3 &nsrc, bool &outside, int &faceMat) {
+// WINNER (k_albedo, pt_albedo.h): the winning triangle's unit index into *unit and the hit's barycentric (u, v) into *bary as well -- what
+// meshWinner<., true> leaves of a walk's winner, from the same operands: the texture coordinates of the hit.
+template <bool CAM_ORIGIN, int STRIDE, bool WINNER, typename GD>
+__device__ __forceinline__ float meshIntersectionWalk(const GD &g, const float4 *recs, uint32_t root, uint32_t stride, uint32_t *stack,
+                                                      F3 ro_w, F3 rd_w, F3 &P, F3 &nsrc, bool &outside, int &faceMat, uint32_t *unit, float2 *bary) {
     const F3 ro = CAM_ORIGIN ? f3(g.camObj[0], g.camObj[1], g.camObj[2]) : mulMV(g.inv, ro_w, 1.0f);
     const F3 rd = normalize(mulMV0(g.inv, g.invZ, rd_w));
     const F3 inv = f3(guardedReciprocal(rd.x), guardedReciprocal(rd.y), guardedReciprocal(rd.z));
@@ -1069,6 +1071,14 @@ __device__ __forceinline__ float meshIntersectionTest(const GD &g, const float4 
     F3 nobj = normalize(nface);
     faceMat = (int)__float_as_uint(c.z);
     const uint32_t nref = __float_as_uint(c.w);
+    if (WINNER) {
+        const F3 p = cross(rd, e2);
+        const float f = 1.0f / dot(e1, p);
+        const F3 sv = ro - w0;
+        const F3 q = cross(sv, e1);
+        *unit = (uint32_t)best;
+        *bary = make_float2(f * dot(sv, p), f * dot(rd, q));
+    }
     if (nref != 0u) {
         // vertex normals: the blend n0 (1 - u - v) + n1 u + n2 v with the hit's own (u, v) -- the triangle test's, evaluated once more
         // for the winner (same operands, same bits) --, turned to the face normal's side; a blend of length zero keeps the face normal
@@ -1127,6 +1137,18 @@ __device__ __forceinline__ float meshWinner(const GD &g, const float4 *recs, uin
     nsrc = nobj;
     outside = front;
     return length(ro_w - P);
+}
+
+template <bool CAM_ORIGIN = false, int STRIDE = 256, typename GD>
+__device__ __forceinline__ float meshIntersectionTest(const GD &g, const float4 *recs, uint32_t root, uint32_t stride, uint32_t *stack,
+                                                      F3 ro_w, F3 rd_w, F3 &P, F3 &nsrc, bool &outside, int &faceMat) {
+    return meshIntersectionWalk<CAM_ORIGIN, STRIDE, false>(g, recs, root, stride, stack, ro_w, rd_w, P, nsrc, outside, faceMat, nullptr, nullptr);
+}
+// ... and with the winner's unit and barycentrics (WINNER above)
+template <bool CAM_ORIGIN = false, int STRIDE = 256, typename GD>
+__device__ __forceinline__ float meshIntersectionTest(const GD &g, const float4 *recs, uint32_t root, uint32_t stride, uint32_t *stack,
+                                                      F3 ro_w, F3 rd_w, F3 &P, F3 &nsrc, bool &outside, int &faceMat, uint32_t &unit, float2 &bary) {
+    return meshIntersectionWalk<CAM_ORIGIN, STRIDE, true>(g, recs, root, stride, stack, ro_w, rd_w, P, nsrc, outside, faceMat, &unit, &bary);
 }
 
 template <bool CAM_ORIGIN = false, int STRIDE = 256, typename GD>

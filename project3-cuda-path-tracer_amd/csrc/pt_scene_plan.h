@@ -253,6 +253,12 @@ int check_scene(const SceneIn &in) {
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DISPLAY_FILTER needs PT_FLAG_MOMENTS (the filter is guided by the variance)");
     if ((o.flags & PT_FLAG_SPATIAL_VARIANCE) && !(o.flags & PT_FLAG_MOMENTS))
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_SPATIAL_VARIANCE needs PT_FLAG_MOMENTS (the estimate is made of the second moments)");
+    if (o.flags & PT_FLAG_DEMODULATE) {
+        if (!(o.flags & PT_FLAG_MOMENTS)) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE needs PT_FLAG_MOMENTS (the filter it feeds is guided by the variance)");
+        if (o.flags & PT_FLAG_TEMPORAL) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE is not for PT_FLAG_TEMPORAL renderers (history carries no albedo)");
+        if (o.flags & PT_FLAG_TRACE_AHEAD)
+            return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE is not for PT_FLAG_TRACE_AHEAD renderers (the albedo follows the committed iterations)");
+    }
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;
@@ -853,6 +859,9 @@ int plan_lds(const SceneIn &in, ScenePlan &p) {
         // (the display filter launches k_gbuffer from pt_iterate: what ensure_guides would refuse there is refused here, with its message)
         if ((p.flags & PT_FLAG_DISPLAY_FILTER) && guideStackBytes(true, p.meshStackNeed) > 64 * 1024)
             return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DISPLAY_FILTER: guide buffers: a mesh hierarchy needs %d stack levels", p.meshStackNeed);
+        // (... and so does k_albedo, whose lanes walk the meshes with k_gbuffer's stacks)
+        if ((p.flags & PT_FLAG_DEMODULATE) && guideStackBytes(true, p.meshStackNeed) > 64 * 1024)
+            return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE: guide buffers: a mesh hierarchy needs %d stack levels", p.meshStackNeed);
     }
     if (p.ldsBytesNext == 0) p.ldsBytesNext = p.ldsBytes;
     if (p.ldsBytes > 160 * 1024) return fail(PT_ERR_INVALID, "pt_init: scene does not fit the 160 KiB LDS (%zu B)", p.ldsBytes);

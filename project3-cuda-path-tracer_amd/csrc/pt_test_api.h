@@ -1221,6 +1221,103 @@ int pt_test_spatial_variance(int radius, int form, int w, int h, const float *m4
     return PT_OK;
 }
 
+int pt_test_albedo(float *asum4_host) {
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_test_albedo before pt_init");
+    if (!R().albedo.p) return fail(PT_ERR_INVALID, "pt_test_albedo: the renderer was initialised without PT_FLAG_DEMODULATE");
+    if (!asum4_host) return fail(PT_ERR_INVALID, "pt_test_albedo: null");
+    HIPCHECK(hipMemcpyAsync(asum4_host, R().albedo.p, (size_t)R().P * sizeof(float4), hipMemcpyDeviceToHost, R().stream));
+    HIPCHECK(hipStreamSynchronize(R().stream));
+    return readback_fault();
+}
+
+int pt_test_demodulate(int form, int inplace, int bytes, int w, int h, int samples, int levels, const float *rgb_sum, const float *lum_sq_sum, const float *img4,
+                       const float *asum4, const float *pos_t4, const float *nrm_id4, float sigma_lum, float sigma_normal, float sigma_position,
+                       float min_albedo, float *demod4_out, float *rgb_out, float *var_out, uint8_t *rgba_out, int reps, float *ms) {
+    NEED_GPU();
+    if (form < kAtrousGather || form > kAtrousTiled8 || (inplace != 0 && inplace != 1) || (bytes != 0 && bytes != 1) || w < 1 || h < 1 ||
+        (long long)w * h > (1ll << 30) || samples < (inplace ? 1 : 2) || levels < 1 || levels > 8 || (inplace ? !img4 : (!rgb_sum || !lum_sq_sum)) || !asum4 ||
+        !pos_t4 || !nrm_id4 || !(sigma_lum > 0.0f) || !(sigma_normal > 0.0f) || !(sigma_position > 0.0f) || !(min_albedo > 0.0f) ||
+        (bytes ? !rgba_out : !rgb_out) || (ms && reps < 1))
+        return fail(PT_ERR_INVALID, "pt_test_demodulate: bad argument");
+    const size_t P = (size_t)w * h;
+    DevBuf<float> S, Q, out3, outVar;
+    DevBuf<float4> ping[2], asum, pos, nrm;
+    DevBuf<uchar4> out8;
+    if (inplace) {
+        PTCHECK(ping[1].upload(reinterpret_cast<const float4 *>(img4), P));
+    } else {
+        PTCHECK(S.upload(rgb_sum, P * 3));
+        PTCHECK(Q.upload(lum_sq_sum, P));
+        PTCHECK(ping[1].alloc(P));
+    }
+    PTCHECK(ping[0].alloc(P));
+    PTCHECK(asum.upload(reinterpret_cast<const float4 *>(asum4), P));
+    PTCHECK(pos.upload(reinterpret_cast<const float4 *>(pos_t4), P));
+    PTCHECK(nrm.upload(reinterpret_cast<const float4 *>(nrm_id4), P));
+    if (bytes) {
+        PTCHECK(out8.alloc(P));
+    } else {
+        PTCHECK(out3.alloc(P * 3));
+        if (var_out) PTCHECK(outVar.alloc(P));
+    }
+    DemodArgs D;
+    D.accum = S.p; D.moments = Q.p; D.img = ping[1].p; D.asum = asum.p;
+    D.npix = (int)P;
+    D.samples = (float)samples; D.samplesM1 = (float)(samples - 1); D.eps = min_albedo;
+    AtrousDemodArgs A;
+    A.accum = nullptr; A.moments = nullptr;
+    A.outVar = outVar.p;
+    A.posT = pos.p; A.nrmId = nrm.p;
+    A.W = w; A.H = h;
+    A.samples = (float)samples; A.samplesM1 = (float)(samples - 1);
+    A.invN = 1.0f / (sigma_normal * sigma_normal);
+    A.invP = 1.0f / (sigma_position * sigma_position);
+    A.asum = asum.p; A.demodN = (float)samples; A.demodEps = min_albedo;
+    EventSet es;
+    if (ms) for (int i = 0; i < 4; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed run first)
+        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        PTCHECK(demod_launch(D, inplace != 0, nullptr));
+        if (ms && r) HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+        if (r == 0 && demod4_out) HIPCHECK(hipMemcpy(demod4_out, ping[1].p, P * sizeof(float4), hipMemcpyDeviceToHost));
+        for (int i = 0; i < levels; ++i) {
+            const bool last = i == levels - 1;
+            A.step = 1 << i;
+            AtrousGuided::hostColourScale(A, sigma_lum, i);
+            A.cin = ping[(i + 1) & 1].p;
+            A.cout = last ? nullptr : ping[i & 1].p;
+            A.out3 = nullptr;
+            if (last && bytes) A.out8 = out8.p;
+            else if (last) A.out3 = out3.p;
+            int f = form;
+            unsigned long long grid = f == kAtrousGather ? atrousGridGather(w, h) : atrousGridTiled(w, h, A.step, f == kAtrousTiled4 ? 1 : 2);
+            if (grid > 0x7fffffffull) {
+                f = kAtrousGather;
+                grid = atrousGridGather(w, h);
+            }
+            void *kargs[] = {&A};
+            if (ms && r && last) HIPCHECK(hipEventRecord(es.ev[2], nullptr));
+            HIPCHECK(hipLaunchKernel(last ? atrous_last_kernel<AtrousDemod>(bytes != 0, f) : atrous_kernel<AtrousGuided>(false, false, false, f), dim3((unsigned)grid),
+                                     dim3(kBlock), kargs, 0, nullptr));
+        }
+        if (ms && r) {
+            HIPCHECK(hipEventRecord(es.ev[3], nullptr));
+            HIPCHECK(hipEventSynchronize(es.ev[3]));
+            HIPCHECK(hipEventElapsedTime(&ms[2 * (r - 1)], es.ev[0], es.ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[2 * (r - 1) + 1], es.ev[2], es.ev[3]));
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    if (bytes) {
+        HIPCHECK(hipMemcpy(rgba_out, out8.p, P * 4, hipMemcpyDeviceToHost));
+    } else {
+        PTCHECK(download(rgb_out, out3, P * 3));
+        if (var_out) PTCHECK(download(var_out, outVar, P));
+    }
+    return PT_OK;
+}
+
 int pt_test_history(int32_t *wh2, float *hc4, float *hn, float *hpos_t4, float *hnrm_id4, float *cam16) {
     if (!wh2) return fail(PT_ERR_INVALID, "pt_test_history: null");
     const History &hs = R().hist;

@@ -7,7 +7,7 @@
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 //                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
-//                           [--history-from EX EY EZ N] [--spatial-variance]
+//                           [--history-from EX EY EZ N] [--spatial-variance] [--demodulate]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
@@ -26,6 +26,8 @@
 // --spatial-variance (with --denoise-var) runs the renderer with PT_FLAG_SPATIAL_VARIANCE: a pixel with fewer than two effective samples is
 // filtered under a variance estimated from its neighbours (include/pt_amd.h, "spatial variance"), so --iterations 1 is allowed, and with
 // --history-from a new view of one sample.
+// --demodulate (with --denoise-var; not with --history-from) runs the renderer with PT_FLAG_DEMODULATE: <out>.denoised.png is the filter of the
+// frame divided by every pixel's mean first-hit albedo, multiplied back behind it (include/pt_amd.h, "demodulation").
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -64,9 +66,11 @@ static bool historyFrom = false;
 static float historyEye[3] = {0.0f, 0.0f, 0.0f};
 static int historyIterations = 0;
 static bool spatialVariance = false;
+static bool demodulate = false;
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 void pathtraceSpatialVariance(bool on);                                             // pathtrace_shim.cpp
+void pathtraceDemodulate(bool on);                                                  // pathtrace_shim.cpp
 
 static std::string currentTimeString() {
     time_t now;
@@ -146,6 +150,7 @@ static void renderBatched() {
     if (denoiseVar || noiseTarget) opt.flags |= PT_FLAG_MOMENTS;
     if (historyFrom) opt.flags |= PT_FLAG_TEMPORAL;
     if (spatialVariance) opt.flags |= PT_FLAG_SPATIAL_VARIANCE;
+    if (demodulate) opt.flags |= PT_FLAG_DEMODULATE;
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -206,7 +211,7 @@ static void renderBatched() {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N] [--spatial-variance]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N] [--spatial-variance] [--demodulate]\n", argv[0]);
         return 1;
     }
     try {
@@ -253,6 +258,7 @@ int main(int argc, char **argv) {
             i += 4;
         }
         else if (!strcmp(argv[i], "--spatial-variance")) spatialVariance = true;
+        else if (!strcmp(argv[i], "--demodulate")) demodulate = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
     if (denoise && denoiseVar) { fprintf(stderr, "--denoise and --denoise-var exclude each other\n"); return 1; }
@@ -263,7 +269,9 @@ int main(int argc, char **argv) {
     if (spatialVariance && !denoiseVar) { fprintf(stderr, "--spatial-variance needs --denoise-var\n"); return 1; }
     pathtraceExtras(lensRadius, focalDistance, directLighting);
     pathtraceMoments(denoiseVar);
+    if (demodulate && (!denoiseVar || historyFrom)) { fprintf(stderr, "--demodulate needs --denoise-var and does not go with --history-from\n"); return 1; }
     pathtraceSpatialVariance(spatialVariance);
+    pathtraceDemodulate(demodulate);
     iteration = 0;
     width = renderState->camera.resolution.x;
     height = renderState->camera.resolution.y;

@@ -18,6 +18,7 @@ static float extraLens = 0.0f, extraFocal = 0.0f;   // README extras (pathtraceE
 static bool extraDirect = false;
 static bool extraMoments = false;                   // pathtraceMoments: PT_FLAG_MOMENTS for the next pathtraceInit
 static bool extraSpatial = false;                   // pathtraceSpatialVariance: PT_FLAG_MOMENTS | PT_FLAG_SPATIAL_VARIANCE for the next pathtraceInit
+static bool extraDemod = false;                     // pathtraceDemodulate: PT_FLAG_MOMENTS | PT_FLAG_DEMODULATE for the next pathtraceInit
 static bool extraDisplay = false;                   // pathtraceDisplayFilter: PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER for the next pathtraceInit
 
 static void checkPtError(int status, const char *msg) {
@@ -47,6 +48,12 @@ void pathtraceInit(Scene *scene) {
     bool spatial = extraSpatial;
     if (const char *e = getenv("PT_AMD_SPATIAL_VARIANCE")) spatial = spatial || atoi(e) != 0;
     if (spatial) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_SPATIAL_VARIANCE;
+    // PT_AMD_DEMODULATE=1 (or pathtraceDemodulate): the variance-guided filter -- pt_denoise_var, and with the display filter the `pbo` -- runs on
+    // the frame divided by every pixel's mean first-hit albedo, which is multiplied back behind it: textures survive.  The albedo follows the
+    // committed iterations, so such a renderer traces nothing ahead (below).
+    bool demod = extraDemod;
+    if (const char *e = getenv("PT_AMD_DEMODULATE")) demod = demod || atoi(e) != 0;
+    if (demod) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_DEMODULATE;
     // The reference's host calls pathtrace(pbo, frame, iter) once per iteration with iter = 1, 2, 3, ... (src/main.cpp:97-103):
     // the library traces such a sequence in wavefront batches AHEAD of the calls (PT_FLAG_TRACE_AHEAD; same image after every
     // call, bit for bit), so a call costs a commit instead of eight small dependent launches.  A camera move goes through
@@ -56,6 +63,7 @@ void pathtraceInit(Scene *scene) {
     if (const char *e = getenv("PT_AMD_TRACE_AHEAD")) ahead = atoi(e);
     if (scene->state.iterations < (unsigned)(ahead > 0 ? ahead : 0)) ahead = (int)scene->state.iterations;
     if (ahead > PT_MAX_BATCH) ahead = PT_MAX_BATCH;
+    if (demod) ahead = 1;               // (PT_FLAG_DEMODULATE is not for PT_FLAG_TRACE_AHEAD renderers)
     // A host written against the reference's pathtraceInit knows nothing of batches, so tracing ahead must never be the
     // reason an Init fails: the batch is clamped to the library's limits for this frame (pixels x batch <= 2^29 paths,
     // rows x padded width x batch < 2^30 tile slots: an 8192 x 8192 frame still traces 8 iterations ahead), and should the
@@ -132,6 +140,11 @@ void pathtraceInit(Scene *scene) {
                         "is not for PT_AMD_DEVICES: a group keeps no second moments\n");
         exit(EXIT_FAILURE);
     }
+    if (members >= 2 && demod) {
+        fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: demodulation (PT_AMD_DEMODULATE, pathtraceDemodulate) is not for PT_AMD_DEVICES: "
+                        "a group keeps no second moments\n");
+        exit(EXIT_FAILURE);
+    }
     if (members >= 2 && display) {
         fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: the display filter (PT_AMD_DISPLAY_FILTER, pathtraceDisplayFilter) is not for "
                         "PT_AMD_DEVICES: a group renders headless\n");
@@ -201,6 +214,10 @@ void pathtraceDisplayFilter(bool on) { extraDisplay = on; }
 // one sample, and with the display filter the first frame's `pbo` is filtered as well.  The environment variable PT_AMD_SPATIAL_VARIANCE=1 does the
 // same for a host that cannot call it.  Not with PT_AMD_DEVICES.
 void pathtraceSpatialVariance(bool on) { extraSpatial = on; }
+
+// ... nor this one: the next pathtraceInit sets PT_FLAG_MOMENTS | PT_FLAG_DEMODULATE (include/pt_amd.h: "demodulation") and traces nothing ahead.
+// The environment variable PT_AMD_DEMODULATE=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
+void pathtraceDemodulate(bool on) { extraDemod = on; }
 
 void pathtraceFree() {
     if (group) {
