@@ -115,6 +115,14 @@ int pt_test_wall_faces(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
                        int32_t *face, float *beyond);
 int pt_test_wall_face_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t counts[4]);
 int pt_test_wall_resolve_tally(uint64_t counts[4]);
+/* pt_test_candidate_tally: the test library's tally of the later bounces' CANDIDATE tiles since the last call, read and cleared.  Per wave
+ * and tile: {[0] later wave-tiles that hold a path; [1] of them candidate tiles (a class bit above the wall's three set: their list holds
+ * binned primitives); [2] of those the tiles of ONE wall that has an inner face, in the forms that resolve one-wall tiles (the tiles a
+ * certified face inside candidate tiles would serve: measured and not kept, profiles/candidate_tiles.txt); [3] lanes of
+ * candidate tiles whose nearest hit is a binned primitive}.  Per scatter of a scene that bins: {[4] paths that live on; [5] of them the
+ * candidates by the bounding balls alone; [6] the candidates by the rule in force -- the ball, and a second certificate by the primitive's
+ * kind (KParams::binBox)}; [7] is 0.  PT_AMD_NO_TIGHT_CANDIDATES=1 (read by the plan, tests only): no second certificate, [6] = [5]. */
+int pt_test_candidate_tally(uint64_t counts[8]);
 /* Triangle meshes.  pt_test_mesh_intersect: `n` rays against ONE mesh geom on the GPU, through the hierarchy (flat = 0) or a
  * plain list of its triangles (flat = 1: the brute-force rule); outputs keep their input values on a miss; culled[i] = 1 when
  * the bounding-ball test (certainMiss) rejected the ray -- t[i] is NaN if the full test hits nevertheless (must not happen).

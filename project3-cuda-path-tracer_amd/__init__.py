@@ -84,7 +84,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_slab_quotients", "pt_test_slab_quotients_sweep", "pt_test_box_fast_sweep", "pt_test_sphere_cull_sweep", "pt_test_unscaled_sqrt_sweep",
     "pt_test_force_fault", "pt_test_pow", "pt_test_wall_box_sweep", "pt_test_mesh_intersect", "pt_test_mesh_intersect2", "pt_test_mesh_bvh",
     "pt_test_mesh_cull_sweep", "pt_test_camera_cull_sweep", "pt_test_camera_cull_tables", "pt_test_camera_list",
-    "pt_test_camera_resolved", "pt_test_face_hit_sweep", "pt_test_wall_faces", "pt_test_wall_face_sweep", "pt_test_wall_resolve_tally",
+    "pt_test_camera_resolved", "pt_test_face_hit_sweep", "pt_test_wall_faces", "pt_test_wall_face_sweep", "pt_test_wall_resolve_tally", "pt_test_candidate_tally",
     "pt_test_wall_plane_sweep", "pt_test_wall_planes", "pt_test_sphere_halfline_sweep", "pt_test_sphere_cluster_sweep", "pt_test_sphere_clusters", "pt_test_camera_cull_margin",
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
@@ -247,6 +247,7 @@ def _bind(L, with_tests):
         L.pt_test_wall_faces.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(PtOptions), vp, vp]
         L.pt_test_wall_face_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p]
         L.pt_test_wall_resolve_tally.argtypes = [u64p]
+        L.pt_test_candidate_tally.argtypes = [u64p]
         L.pt_test_camera_cull_margin.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_double), u64p]
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
@@ -1414,6 +1415,13 @@ def wall_resolve_tally():
     """The test library's tally of its renderer's later bounces since the last call (read and cleared): (wave-tiles that hold a path, of
     them one-wall tiles whose wall has a face, of those the waves that took the face, lanes whose certificate failed)."""
     return _u64_outs(test_lib().pt_test_wall_resolve_tally, (4,))
+
+
+def candidate_tally():
+    """The test library's tally of its renderer's candidate tiles since the last call (read and cleared): (later wave-tiles that hold a
+    path, of them candidate tiles, of those tiles of one wall that has an inner face, lanes of candidate tiles that hit a binned primitive,
+    scattered paths of a binning scene, of them candidates by the balls alone, candidates by the rule in force, 0)."""
+    return _u64_outs(test_lib().pt_test_candidate_tally, (8,))
 
 
 def test_camera_cull_sweep(camera, geoms, samples=1):

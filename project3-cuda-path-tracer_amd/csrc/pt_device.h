@@ -40,10 +40,24 @@ __device__ unsigned long long g_wallResolve[4];
 __device__ __forceinline__ void tallyWallResolve(int k, unsigned long long n) {
     if (n != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_wallResolve[k], n);
 }
+// ... and its tally of the later bounces' CANDIDATE tiles (read and cleared by pt_test_candidate_tally).  Per wave and tile: [0] later
+// wave-tiles that hold a path, [1] of them candidate tiles (a class bit above the wall's three set), [2] of those the tiles of one wall that has
+// an inner face (what a certified face inside candidate tiles would serve; no kernel takes it there: measured, not kept -- profiles/
+// candidate_tiles.txt), [3] the lanes of candidate tiles whose nearest hit is a binned primitive.  Per scatter that bins:
+// [4] the paths that live on, [5] of them the candidates by the bounding balls alone (certainMiss of every binned primitive), [6] the
+// candidates by the rule in force (KParams::binBox; equal to [5] under PT_AMD_NO_TIGHT_CANDIDATES).
+__device__ unsigned long long g_candidates[8];
+__device__ __forceinline__ void tallyCandidate(int k, unsigned long long n) {
+    if (n != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_candidates[k], n);
+}
 }  // namespace ptd
 #define PT_TALLY_WALL_RESOLVE(k, n) ptd::tallyWallResolve(k, n)
+#define PT_TALLY_CANDIDATE(k, n) ptd::tallyCandidate(k, n)
+#define PT_TEST_ONLY(...) __VA_ARGS__
 #else
 #define PT_TALLY_WALL_RESOLVE(k, n)
+#define PT_TALLY_CANDIDATE(k, n)
+#define PT_TEST_ONLY(...)
 #endif
 
 namespace ptd {
@@ -696,6 +710,28 @@ __device__ __forceinline__ bool certainMiss(const GD &g, F3 org, F3 dir, float d
     const float od = __builtin_fmaf(oc.z, dir.z, __builtin_fmaf(oc.y, dir.y, oc.x * dir.x));
     return __builtin_fmaf(oo, dd, -(od * od)) > __builtin_fmaf(g.cullK, oo, g.cullR2) * dd;
 }
+// certainMiss for the HALF-line { o + t dir, t >= 0 } when `halfLine` says so (wave-uniform; k_bounce's scatter: the candidacy of a binned
+// SPHERE), else certainMiss itself, operation for operation.  The half-line form clamps the projection from above, od' = min(oc.dir, 0): one
+// more instruction, sphereHalfLineExcess in certainMiss's product form -- the direction is NOT renormalised here, |dir|^2 stands on both
+// sides as it does above, so no slack for a nearly-unit direction is needed (K = cullK itself):
+//   oc.dir <= 0 (the centre ahead): od' = od, the line's condition and argument.
+//   oc.dir > 0 (the centre behind): od' = 0 and the condition reads |oc|^2 |dir|^2 > (K |oc|^2 + R2) |dir|^2, i.e. |oc|^2 > R2 + K |oc|^2 for
+//   any finite |dir|^2 > 0 (0, inf and NaN fail the comparison): the origin lies outside the inflated ball.  Along the half-line
+//   |o + t dir - c|^2 = |oc|^2 + 2 t oc.dir + t^2 |dir|^2 >= |oc|^2, so the whole half-line stays outside that ball, and sphereHalfLineExcess's
+//   proof applies with t = 0: in object space |ro|^2 - 1/4 > 1e-4 |ro|^2 and either the radicand is negative or both roots are, the larger
+//   by -5e-5 |ro| against ~1e-7 |ro| of rounding (intersections.h:121-123).  The two products by |dir|^2 round to 6e-8 each, against
+//   margins of 1e-3 and 1e-4.  Spheres only: a cube behind the origin is its slab certificate's business (wallCertainMiss: tmax < 0).
+// A NaN projection becomes 0 (v_min_f32 keeps the other operand); then |oc|^2 or |dir|^2 is NaN or infinite and the comparison fails as it
+// does above.
+// (a scalar branch around the v_min, not a clamp to a selected bound, +inf for the line: that form cost the textured later forms a spill)
+template <typename GD>
+__device__ __forceinline__ bool certainMissClamped(const GD &g, F3 org, F3 dir, float dd, bool halfLine) {
+    const F3 oc = org - f3(g.centre[0], g.centre[1], g.centre[2]);
+    const float oo = __builtin_fmaf(oc.z, oc.z, __builtin_fmaf(oc.y, oc.y, oc.x * oc.x));
+    float od = __builtin_fmaf(oc.z, dir.z, __builtin_fmaf(oc.y, dir.y, oc.x * dir.x));
+    if (halfLine) od = __builtin_fminf(od, 0.0f);
+    return __builtin_fmaf(oo, dd, -(od * od)) > __builtin_fmaf(g.cullK, oo, g.cullR2) * dd;
+}
 
 // Certain miss of a SPHERE by the HALF-line a ray is (sphere-heavy scenes, later bounces: k_bounce's packed sweep), against its
 // bounding ball with a direction the caller has normalised: dhat = dir * rsq(|dir|^2), unit to 5e-7.
@@ -766,6 +802,25 @@ __device__ __forceinline__ bool wallCertainMiss(const WB &w, F3 o, F3 inv) {
     const float tz1 = (w.lo[2] - o.z) * inv.z, tz2 = (w.hi[2] - o.z) * inv.z;
     const float tmin = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(tx1, tx2), __builtin_fminf(ty1, ty2)), __builtin_fminf(tz1, tz2));
     const float tmax = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(tx1, tx2), __builtin_fmaxf(ty1, ty2)), __builtin_fmaxf(tz1, tz2));
+    return (tmin - tmax > 1e-5f * (__builtin_fabsf(tmin) + __builtin_fabsf(tmax))) | (tmax < 0.0f);
+}
+// The same certificate from the direction itself, one axis after the other: each axis forms its reciprocal (v_rcp_f32, as the callers of
+// wallCertainMiss do), its two quotients, and folds them into the running tmin / tmax before the next begins -- two values carried instead
+// of three reciprocals and six quotients (k_bounce's scatter: the candidacy of a binned cube, in forms with no register to spare).  The
+// quotients are wallCertainMiss's, bit for bit; max and min drop a NaN whichever operand holds it, so folding from -inf / +inf gives the
+// nested form's tmin and tmax -- except when every axis is NaN, where that form returns NaN and this one -inf / +inf: no certificate
+// either way (-inf - inf > inf and inf < 0 are both false).
+template <typename WB>
+__device__ __forceinline__ bool wallCertainMissByAxis(const WB &w, F3 o, F3 d) {
+    const float ov[3] = {o.x, o.y, o.z}, dv[3] = {d.x, d.y, d.z};
+    float tmin = -__builtin_inff(), tmax = __builtin_inff();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float inv = __builtin_amdgcn_rcpf(dv[a]);
+        const float t1 = (w.lo[a] - ov[a]) * inv, t2 = (w.hi[a] - ov[a]) * inv;
+        tmin = __builtin_fmaxf(tmin, __builtin_fminf(t1, t2));
+        tmax = __builtin_fminf(tmax, __builtin_fmaxf(t1, t2));
+    }
     return (tmin - tmax > 1e-5f * (__builtin_fabsf(tmin) + __builtin_fabsf(tmax))) | (tmax < 0.0f);
 }
 

@@ -504,8 +504,10 @@ void plan_bins(const SceneIn &in, ScenePlan &p) {
             }
         if (bestB >= 0) p.binGroup[bestB] = 1;
     }
+    // (PT_AMD_NO_TIGHT_CANDIDATES, tests only: no second condition, the classes are those of the bounding balls alone)
+    const bool tight = !env_flag("PT_AMD_NO_TIGHT_CANDIDATES");
     for (int b = 0; b < kBinMax; ++b) {                      // (KParams::binCull: the binned primitives' culling groups, inline)
-        for (int q = 0; q < 8; ++q) k.binCull[b][q] = 0.0f;
+        for (int q = 0; q < 8; ++q) k.binCull[b][q] = k.binBox[b][q] = 0.0f;
         k.binCull[b][3] = -INFINITY;                          // beyond nBinned: certified for everybody
         if (b < k.nBinned) {
             const GeomDev &G = hg[k.binGeom[b]];
@@ -514,6 +516,25 @@ void plan_bins(const SceneIn &in, ScenePlan &p) {
             // word 5: the primitive's candidate bit in a survivor's class (k_bounce<..., MESH>): 1 = group 0, 2 = group 1
             const uint32_t bit = 1u << p.binGroup[b];
             memcpy(&k.binCull[b][5], &bit, sizeof bit);
+            // word 6: the KIND of the second sufficient condition for the miss (KParams::binBox) -- 2 a sphere: the half-line; 1 a cube: the
+            // slab certificate against its inflated world box, issued for origins within the bound wall_box states for that box.
+            // The inflation is wall_box's for a SMALL cube as it is: delta = 4e-5 S with S >= the cube's largest |coordinate| and >= its
+            // diagonal, while the reference's evaluation moves the boundary by ~2e-7 (|o| + S) whatever the cube's size or aspect -- the
+            // object-space products of a thin axis are larger by the aspect and scaled back by it -- and |o| <= omax < 5 S bounds that by
+            // 1.2e-6 S, a thirtieth of delta.  What a small cube changes is omax itself: an axis-aligned cube of extent 0.1 at the world's origin
+            // has S = 0.17 and gets certificates for origins within 0.8 of it only (turned by 10 / 20 / 30 degrees, as
+            // tests/test_candidate_certificates_cpu.py has it: S = 0.26, within 1.23); beyond the bound the ball alone decides.
+            // (pt_test_wall_box_sweep sweeps thin, small and rotated cubes from touching them to 64 box sizes away.)
+            int32_t kind = 0;
+            WallBox wb;
+            double om = 0;
+            if (tight && geoms[k.binGeom[b]].type == PT_SPHERE) kind = 2;
+            else if (tight && geoms[k.binGeom[b]].type == PT_CUBE && wall_box(geoms[k.binGeom[b]], wb, &om) >= 0 && om > 0) {
+                kind = 1;
+                for (int a = 0; a < 3; ++a) { k.binBox[b][a] = wb.lo[a]; k.binBox[b][3 + a] = wb.hi[a]; }
+                k.binBox[b][6] = std::nextafter((float)om, 0.0f);
+            }
+            memcpy(&k.binCull[b][6], &kind, sizeof kind);
         }
     }
 }

@@ -974,6 +974,18 @@ int pt_test_wall_resolve_tally(uint64_t counts[4]) {
     return PT_OK;
 }
 
+// ... and of the later bounces' candidate tiles and the scatters' candidacy (ptd::g_candidates), read and cleared
+int pt_test_candidate_tally(uint64_t counts[8]) {
+    NEED_GPU();
+    if (!counts) return fail(PT_ERR_INVALID, "pt_test_candidate_tally: bad argument");
+    unsigned long long h[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(ptd::g_candidates), sizeof h));
+    HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(ptd::g_candidates), z, sizeof z));
+    for (int q = 0; q < 8; ++q) counts[q] = h[q];
+    return PT_OK;
+}
+
 int pt_test_box_fast_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t counts[4], uint64_t div_mismatches[2]) {
     NEED_GPU();
     if (!geoms || ngeoms < 1 || !counts || !div_mismatches || rays < 0) return fail(PT_ERR_INVALID, "pt_test_box_fast_sweep: bad argument");

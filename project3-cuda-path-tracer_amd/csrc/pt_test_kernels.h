@@ -260,6 +260,14 @@ __global__ void k_sweep_sphere_halfline(const GeomDev *geoms, int ngeoms, unsign
             const float t = G.type == 1 ? boxIntersectionTest<false>(G, org, dir, P, N, o) : sphereIntersectionTest(G, org, dir, P, N, o);
             if (t != -1.0f) ++nv;
         }
+        // ... and the scatter's form of the same certificate for a binned sphere (certainMissClamped: the direction as it is, |dir|^2 on
+        // both sides, K = cullK): a violation like the other's
+        if (certainMissClamped(G, org, dir, dd, true)) {
+            F3 P, N;
+            bool o;
+            const float t = G.type == 1 ? boxIntersectionTest<false>(G, org, dir, P, N, o) : sphereIntersectionTest(G, org, dir, P, N, o);
+            if (t != -1.0f) ++nv;
+        }
     }
     sweepFlush(culled, nc);
     sweepFlush(behind, nb);
@@ -294,7 +302,11 @@ __global__ void k_sweep_wall_box(const GeomDev *geoms, const WallBox *walls, con
         const float l1 = (__builtin_fabsf(org.x) + __builtin_fabsf(org.y)) + __builtin_fabsf(org.z);
         if (!(l1 <= omax[gi])) continue;
         const F3 inv = f3(__builtin_amdgcn_rcpf(dir.x), __builtin_amdgcn_rcpf(dir.y), __builtin_amdgcn_rcpf(dir.z));
-        if (wallCertainMiss(W, org, inv)) {
+        // (both evaluations of the certificate: the walls' -- reciprocals from the caller -- and the scatter's for a binned cube, axis by
+        // axis; a hit that either certifies is a violation, and so is a ray on which the two disagree)
+        const bool nested = wallCertainMiss(W, org, inv), byAxis = wallCertainMissByAxis(W, org, dir);
+        if (nested != byAxis) ++nv;
+        if (nested || byAxis) {
             ++nc;
             F3 P, N;
             bool o;

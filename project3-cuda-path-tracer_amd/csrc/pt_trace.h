@@ -116,6 +116,13 @@ struct KParams {
     // cost ONE scalar load from the argument block instead of a chain of three (index -> primitive -> its culling group) each.
     // Rows beyond nBinned hold cullR2 = -inf: a ball nobody can miss being certified for.
     float binCull[kBinMax][8];
+    // ... and, row for row, a SECOND sufficient condition for the scatter's candidacy bit (a primitive is a candidate only when neither
+    // certifies the miss), chosen by the KIND in word 6 of the primitive's binCull row (an int): 1 = a cube: the slab certificate
+    // (ptd::wallCertainMiss) against its inflated world box (wall_box), binBox = {lo[3], hi[3], omax, -}, for ray origins with
+    // |x| + |y| + |z| <= omax; 2 = a sphere: the ball's certificate for the HALF-line (ptd::certainMissClamped); 0 = none -- meshes, rows
+    // beyond nBinned, and every row under PT_AMD_NO_TIGHT_CANDIDATES (tests only: the classes of the ball alone).  The sphere-heavy forms
+    // (k_bounce<..., MANY>) do not read the kind: they bin the light alone and keep the ball (measured: profiles/candidate_tiles.txt).
+    float binBox[kBinMax][8];
     // ---- walls: the scene's large cubes (non-binned, at most kWallMax).  With walls the three low class bits of a survivor
     // are not its direction octant but WHICH wall it can still hit: 0..5 = that wall only (every other wall certified
     // missed by wallCertainMiss), 6 = several or uncertified, 7 = none
@@ -310,8 +317,9 @@ __device__ __forceinline__ void cameraRayAt(const KParams &prm, uint32_t iterHas
 //   class     = bits 0-2 | candidate << 3.  Bits 0-2: in a scene with walls, WHICH wall the new ray can still hit
 //               (wallCertainMiss of every wall, see KParams::nWalls; 6 = several, 7 = none), else the octant of its
 //               direction; candidate = the new ray is not a certain miss (certainMiss: bounding ball with a 50x safety
-//               margin) of every SMALL primitive of the scene -- its spheres and the cubes much smaller than the scene,
-//               at most kBinMax, chosen by pt_init,
+//               margin; and a second certificate by the primitive's kind, KParams::binBox: a cube's inflated world box, a
+//               sphere's ball against the half-line) of every SMALL primitive of the scene -- its spheres and the cubes much
+//               smaller than the scene, at most kBinMax, chosen by pt_init,
 //   segment   = class * kSub + blockIdx % kSub,
 //   rank      = position among the wave's lanes of the same class (four bit ballots -> same-class mask -> mbcnt) plus
 //               the earlier waves' totals through LDS = workgroup-level exclusive scan per class,
@@ -1536,6 +1544,15 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     }
                 }
             }
+            if (!FIRST) {                                       // (the test library's tally of candidate tiles; nothing in the product)
+                PT_TALLY_CANDIDATE(0, 1ull);
+                PT_TALLY_CANDIDATE(1, (tileCls >> 3) != 0u ? 1ull : 0ull);
+                // (... of those, the tiles of ONE wall that has an inner face, in the forms that resolve one-wall tiles: what a certified face
+                // inside candidate tiles would serve -- measured and not kept, profiles/candidate_tiles.txt)
+                PT_TALLY_CANDIDATE(2, (kWallResolveOk && (tileCls & 8u) != 0u && (tileCls & 7u) < 6u && hotWalls(hotNow()) != 0u &&
+                                       (launder((WallPtr)(launder(kargs)->walls)) + (tileCls & 7u))->face >= 0) ? 1ull : 0ull);
+                PT_TALLY_CANDIDATE(3, (tileCls >> 3) != 0u ? (unsigned long long)__popcll(__ballot(hit >= 0 && ((launder((GeomPtr)(launder(kargs)->ggeoms)) + (hit >= 0 ? hit : 0))->cullFlags & 2) != 0)) : 0ull);
+            }
             probe(16);                                          // (shading)
             if (hit < 0) {
                 fl = 4u;                                         // S4: background is black
@@ -1765,12 +1782,15 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             const int ne = A->prm.nEmit;
                             int pick = (int)(u01(rng) * (float)ne);
                             pick = pick > ne - 1 ? ne - 1 : pick;
+                            // (the emitter's rho^2: selected beside `e` in the camera-ray forms; in the later forms where it is used, below --
+                            // selected here it sits in a register across the twelve loads of the matrix, the one register the general later form
+                            // at eight workgroups per CU does not have: it spilled.  The camera-ray forms lose a workgroup per CU the other way.)
                             int e = A->prm.emitGeom[0];
                             float rho2 = A->prm.emitRho2[0];
 #pragma unroll
                             for (int q = 1; q < kEmitMax; ++q) {
                                 e = pick == q ? A->prm.emitGeom[q] : e;
-                                rho2 = pick == q ? A->prm.emitRho2[q] : rho2;
+                                if (FIRST) rho2 = pick == q ? A->prm.emitRho2[q] : rho2;
                             }
                             const float ux = u01(rng) - 0.5f;
                             const float uy = u01(rng) - 0.5f;
@@ -1788,6 +1808,10 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             float w = dot(Ns, ndir);
                             w = w > 0.0f ? w : 0.0f;
                             // ... and by the share of the hemisphere the emitter's bounding ball covers, min(1, rho^2 / r^2)
+                            if (!FIRST) {
+#pragma unroll
+                                for (int q = 1; q < kEmitMax; ++q) rho2 = pick == q ? A->prm.emitRho2[q] : rho2;
+                            }
                             float cover = rho2 / dot(toward, toward);
                             cover = cover < 1.0f ? cover : 1.0f;
                             col = (col * mcol) * (w * cover);
@@ -1825,9 +1849,18 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         if (nBinned > 0) {
                             const float ndd = dot(ndir, ndir);
                             uint32_t cand = 0u;
+                            PT_TEST_ONLY(uint32_t candBall = 0u;)              // (the test library's tally: the candidacy the ball alone gives)
                             for (int sI = 0; sI < nBinned; sI += 2) { probe(12);          // two at a time: one 64-byte scalar load
                                 int16v v;
                                 asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(launder(kargs)), "s"((int)(offsetof(BounceArgs, prm) + offsetof(KParams, binCull)) + sI * 32) : "memory");
+                                // A candidate only if NEITHER of two sufficient conditions certifies the miss.  The first is the ball (for a sphere
+                                // against the HALF-line the ray is: the sphere a scattered ray leaves lies behind it, by next to nothing --
+                                // ptd::certainMissClamped; the row's word 6 is the primitive's kind, wave-uniform) ...
+                                // (per primitive of the pair: certified -- a per-lane flag that lives in a scalar register pair, on purpose: the forms
+                                // that run at eight workgroups per CU have no vector register to spare across the slab test --, its bit and its kind)
+                                bool miss[2] = {true, true};
+                                uint32_t bit[2] = {0u, 0u};
+                                int kind[2] = {0, 0};
 #pragma unroll
                                 for (int h = 0; h < 2; ++h) {
                                     // (sphere-heavy scenes bin one primitive, the light: the row behind it stands for nobody -- a scalar
@@ -1836,11 +1869,40 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                                     CullGroup cg;
                                     cg.centre[0] = __int_as_float(v[8 * h]); cg.centre[1] = __int_as_float(v[8 * h + 1]); cg.centre[2] = __int_as_float(v[8 * h + 2]);
                                     cg.cullR2 = __int_as_float(v[8 * h + 3]); cg.cullK = __int_as_float(v[8 * h + 4]);
+                                    // (not in the sphere-heavy forms: they bin the light alone, their tiles' cost is the sweep of the spheres whichever
+                                    // way the light's bit falls, and the slab test at every scatter cost C5 0.6 % -- measured, profiles/candidate_tiles.txt)
+                                    kind[h] = MANY ? 0 : v[8 * h + 6];
                                     // (the primitive's candidate bit: 1, or 2 for the mesh scenes' group 1 -- word 5 of its row)
-                                    cand |= certainMiss(cg, norg, ndir, ndd) ? 0u : (WIDE ? (uint32_t)v[8 * h + 5] : 1u);
+                                    bit[h] = WIDE ? (uint32_t)v[8 * h + 5] : 1u;
+                                    miss[h] = certainMissClamped(cg, norg, ndir, ndd, kind[h] == 2);
+                                    PT_TEST_ONLY(candBall |= certainMiss(cg, norg, ndir, ndd) ? 0u : 1u;)
                                 }
+                                // ... the second, for a cube, the slab certificate against its inflated world box (KParams::binBox: one more scalar
+                                // load for the pair, into the registers the balls have left): a thin slab's ball is many times the slab, and the slab
+                                // a ray leaves next to, or starts behind, is certified like a wall (ptd::wallCertainMiss, under its bound on the origin)
+                                if (kind[0] == 1 || kind[1] == 1) {
+                                    int16v bx;
+                                    asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(bx) : "s"(launder(kargs)), "s"((int)(offsetof(BounceArgs, prm) + offsetof(KParams, binBox)) + sI * 32) : "memory");
+                                    // (the origin's |x| + |y| + |z| is formed here and once more for the walls below, and the slab test takes its axes one
+                                    // after the other, each with its own reciprocal -- wallCertainMissByAxis --: held across the balls, or all three
+                                    // reciprocals at once, they were the registers the general later forms did not have)
+                                    const float nl1 = (__builtin_fabsf(norg.x) + __builtin_fabsf(norg.y)) + __builtin_fabsf(norg.z);
+#pragma unroll
+                                    for (int h = 0; h < 2; ++h) {
+                                        if (kind[h] != 1) continue;
+                                        WallBox wb;
+                                        wb.lo[0] = __int_as_float(bx[8 * h]); wb.lo[1] = __int_as_float(bx[8 * h + 1]); wb.lo[2] = __int_as_float(bx[8 * h + 2]);
+                                        wb.hi[0] = __int_as_float(bx[8 * h + 3]); wb.hi[1] = __int_as_float(bx[8 * h + 4]); wb.hi[2] = __int_as_float(bx[8 * h + 5]);
+                                        const bool boxMiss = wallCertainMissByAxis(wb, norg, ndir);
+                                        miss[h] = miss[h] || (boxMiss && nl1 <= __int_as_float(bx[8 * h + 6]));      // (NaN fails)
+                                    }
+                                }
+                                cand |= (miss[0] ? 0u : bit[0]) | (miss[1] ? 0u : bit[1]);
                             }
                             smallCandI = cand;
+                            PT_TALLY_CANDIDATE(4, (unsigned long long)__popcll(__ballot(1)));
+                            PT_TALLY_CANDIDATE(5, (unsigned long long)__popcll(__ballot(candBall != 0u)));
+                            PT_TALLY_CANDIDATE(6, (unsigned long long)__popcll(__ballot(cand != 0u)));
                         }
                     }
                     {                                            // class bits 0-2 with walls: which of them can the new ray still hit?
