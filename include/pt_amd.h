@@ -120,6 +120,12 @@ enum {
                                     the pixel's mean albedo out in front of the filter's levels and multiply it back behind them.  Everything else
                                     is the unflagged renderer's bit for bit.  PT_ERR_INVALID without PT_FLAG_MOMENTS, with PT_FLAG_TEMPORAL, with
                                     PT_FLAG_TRACE_AHEAD, and for a scene whose guide buffers cannot be made. */
+    PT_FLAG_DEMOD_HISTORY = 1024,/* history carries albedo (section "demodulated history" below): with PT_FLAG_MOMENTS, PT_FLAG_TEMPORAL and
+                                    PT_FLAG_DEMODULATE -- all three, which pt_init accepts together under this flag alone -- the context's history
+                                    also keeps the old view's mean first-hit albedo per pixel, and pt_denoise_var / pt_denoise_var_rgba8 / the
+                                    display path divide the blend of the reprojected history with the new samples by the BLENDED albedo.  While the
+                                    context holds no history the renderer is PT_FLAG_DEMODULATE's bit for bit.  PT_ERR_INVALID without any of the
+                                    three; every other refusal of PT_FLAG_TEMPORAL and of PT_FLAG_DEMODULATE stands. */
     PT_FLAG_DIRECT_LIGHTING = 4/* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
@@ -489,12 +495,32 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
  *   Both accumulators, every other read-back, pt_variance, pt_noise_stats, pt_iterate_until, pt_denoise and pt_gbuffer are the unflagged
  *   renderer's bit for bit, and a renderer without the flag launches exactly what it launched before.
  *   pt_init answers PT_ERR_INVALID, before anything is touched, to the flag without PT_FLAG_MOMENTS (so: with row shards, and from
- *   pt_group_init), with PT_FLAG_TEMPORAL (history carries no albedo yet), with PT_FLAG_TRACE_AHEAD (judged on the caller's flags), and for a
+ *   pt_group_init), with PT_FLAG_TEMPORAL (history carries no albedo yet -- unless PT_FLAG_DEMOD_HISTORY is given: "demodulated history" below), with PT_FLAG_TRACE_AHEAD (judged on the caller's flags), and for a
  *   scene whose guide buffers cannot be made.  A thin lens, direct lighting, PT_FLAG_DISPLAY_FILTER and PT_FLAG_SPATIAL_VARIANCE go with it.
  *   Known cost: mirrors, glass and lights stay un-demodulated; at high sample counts on textures with (nearly) black texels the floor eps
  *   makes the demodulated filter lose a little to the plain one (README, "Demodulation").
  * PT_DEMOD_MIN_ALBEDO is chosen by the study of tests/test_demod_cpu.py among 1/256, 1/64 and 1/16 (README, "Demodulation"). */
 #define PT_DEMOD_MIN_ALBEDO 0.015625f
+
+/* ---- demodulated history (PT_FLAG_DEMOD_HISTORY, with PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL | PT_FLAG_DEMODULATE; csrc/pt_temporal.h gives every
+ * operation under "ALBEDO", tests/temporal_demod_ref.py restates it).  No function of its own: a flag.
+ *   Without it a moving camera over a textured scene has to choose between history (PT_FLAG_TEMPORAL, which blurs texel borders through the
+ *   luminance term) and demodulation (PT_FLAG_DEMODULATE, which starts again from one or two samples after every move, where one sample's
+ *   albedo is a point sample of the texture).  SVGF accumulates demodulated light over time for this reason.
+ *   History gains an image: pt_init over a live renderer that carries the flag also captures Ha' = (Ab, tot), the blend of ITS reprojected
+ *   albedo history with ITS albedo sums (below), one more W*H float4 pair owned by the context.  History passes a pt_init only between two
+ *   renderers that AGREE on the flag; where they differ it is dropped, as it is when the frame size changes.
+ *   The blend: k_temporal's taps that count also add Ha[q] * w; ha = sumA / sumW (0 without history), and with Asum the renderer's albedo
+ *   sums  Ab.k = (ha.k * Nh + Asum.k) / tot,  tot = Nh + n.  Without history that is Asum / n: PT_FLAG_DEMODULATE's mean albedo to the bit.
+ *   The filter while the context holds history: the blend (c, v) of PT_FLAG_TEMPORAL -- at one sample under PT_FLAG_SPATIAL_VARIANCE the
+ *   estimate's -- is divided by A = max(Ab, PT_DEMOD_MIN_ALBEDO) as PT_FLAG_DEMODULATE divides by its own, the levels run, and the last
+ *   level multiplies back: Ab below PT_DEMOD_HISTORY_MIN_OWN samples (the reprojected albedo is anti-aliased but bilinearly blurred), the
+ *   renderer's own mean albedo Asum / n from there on (sharp, but aliased at low counts).  pt_init allocates one more W*H float4 of its own
+ *   for Ab and counts it in its memory check; the display path stays one fused last launch without a synchronisation or an allocation.
+ *   Known cost: README, "Demodulated history".
+ * PT_DEMOD_HISTORY_MIN_OWN is chosen by the study of tests/test_demod_history_cpu.py among 1, 2, 4, 8 and never (README, "Demodulated
+ * history"). */
+#define PT_DEMOD_HISTORY_MIN_OWN 2
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

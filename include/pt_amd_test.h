@@ -255,6 +255,19 @@ int pt_test_albedo(float *asum4_host);
 int pt_test_demodulate(int form, int inplace, int bytes, int w, int h, int samples, int levels, const float *rgb_sum, const float *lum_sq_sum, const float *img4,
                        const float *asum4, const float *pos_t4, const float *nrm_id4, float sigma_lum, float sigma_normal, float sigma_position,
                        float min_albedo, float *demod4_out, float *rgb_out, float *var_out, uint8_t *rgba_out, int reps, float *ms);
+/* demodulated history (pt_amd.h, csrc/pt_temporal.h under "ALBEDO").
+ * pt_test_temporal_albedo: the ALBEDO forms of k_temporal over host arrays of any w x h, no renderer needed.  form 0 / 1 / 2: the filter, the
+ * capture and the moments form as pt_test_temporal's `capture` names them; out4 / out_n as there.  asum4 = the current view's albedo sums
+ * (w * h * 4), ha4 = the history's albedo (w * h * 4; .w is not read), the rest as pt_test_temporal takes it; out_a4 receives (Ab, tot).
+ * front (form 0 alone, else 0): 0 the blend as it is; 1 the FUSED front, k_temporal<kTemporalFilterDemod, true>, one launch; 2 the two
+ * launches it fuses, k_temporal<kTemporalFilter, true> and k_demodulate<true> in place with (asum = Ab, samples = 1) -- 1 and 2 give the same
+ * bits; min_albedo is their floor.  ms (or NULL) with reps >= 1: `reps` times of the whole front by HIP events, after one untimed run.
+ * pt_test_history_albedo: the albedo image of the history THIS library's current context holds -- wh2 = its frame size, {0, 0}: no history,
+ * or one made by a renderer without PT_FLAG_DEMOD_HISTORY (nothing else is written then); ha4 (w * h * 4, or NULL): (Ab, tot). */
+int pt_test_temporal_albedo(int form, int front, int w, int h, int samples, const float *rgb_sum, const float *lum_sq_sum, const float *pos_t4,
+                            const float *nrm_id4, const float *asum4, const float *hc4, const float *hn, const float *ha4, const float *hpos_t4,
+                            const float *hnrm_id4, const float *cam16, float min_albedo, float *out4, float *out_n, float *out_a4, int reps, float *ms);
+int pt_test_history_albedo(int32_t *wh2, float *ha4);
 /* the noise statistics (pt_amd.h, csrc/pt_noise.h): k_noise_stats -- the kernel pt_noise_stats launches -- over host arrays of any w x h, no
  * renderer needed: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h); out, tile_rel_var_host (or NULL) as pt_noise_stats.  tiles_per_wave: how many
  * tiles a wave of the grid takes, 1..64, 0 = the library's choice -- every value gives the same bits.  ms (or NULL) with

@@ -59,6 +59,10 @@ PT_SPATIAL_MIN_COUNT, PT_SPATIAL_RADIUS = 2.0, 1
 PT_FLAG_DEMODULATE = 512
 # albedo demodulation (include/pt_amd.h): the floor of a pixel's mean first-hit albedo
 PT_DEMOD_MIN_ALBEDO = 0.015625
+# history carries albedo (include/pt_amd.h, "demodulated history"): the flag, and the smallest sample count from which the renderer's own mean
+# albedo -- not the blend with the reprojected one -- is multiplied back behind the filter
+PT_FLAG_DEMOD_HISTORY = 1024
+PT_DEMOD_HISTORY_MIN_OWN = 2
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -89,7 +93,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_group_fail_next_reduce", "pt_test_sphere_group_sweep", "pt_test_texture_sample", "pt_test_texture_uv",
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
-    "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate",
+    "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce",
 ]
 
@@ -268,6 +272,8 @@ def _bind(L, with_tests):
         L.pt_test_display.argtypes = [i32, i32, i32, vp, vp]
         L.pt_test_spatial_variance.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, vp]
         L.pt_test_albedo.argtypes = [vp]
+        L.pt_test_temporal_albedo.argtypes = [i32] * 5 + [vp] * 11 + [C.c_float] + [vp] * 3 + [i32, vp]
+        L.pt_test_history_albedo.argtypes = [vp, vp]
         L.pt_test_demodulate.argtypes = [i32] * 7 + [vp] * 6 + [C.c_float] * 4 + [vp] * 4 + [i32, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
@@ -455,8 +461,12 @@ _scene = None
 
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
-                  mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False, demodulate=False):
+                  mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False, demodulate=False,
+                  demod_history=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    demod_history: PT_FLAG_DEMOD_HISTORY (with moments=True, temporal=True and demodulate=True, which go together under it alone) -- the
+    history a re-initialisation carries over also holds the old view's mean first-hit albedo, and denoise_var / denoise_var_rgba8 / the display
+    divide the blend of history and new samples by the blended albedo.  History passes only between renderers that agree on the flag.
     demodulate: PT_FLAG_DEMODULATE (with moments=True; not with temporal or trace_ahead) -- every pathtrace / pathtrace_batch also adds the
     first-hit albedo of its iterations' camera rays to a per-pixel sum, and denoise_var / denoise_var_rgba8 -- with display_filter=True the
     display's bytes too -- divide the pixel's mean albedo out in front of the filter and multiply it back behind it: textures survive.
@@ -491,6 +501,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_SPATIAL_VARIANCE
     if demodulate:
         flags |= PT_FLAG_DEMODULATE
+    if demod_history:
+        flags |= PT_FLAG_DEMOD_HISTORY
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -950,6 +962,39 @@ def test_history():
     cam = np.empty(16, np.float32)
     _tcheck(T.pt_test_history(_p(wh), _p(hc), _p(hn), _p(hpos), _p(hnrm), _p(cam)))
     return dict(hc=hc, hn=hn, hpos_t=hpos, hnrm_id=hnrm, cam=cam)
+
+
+def test_temporal_albedo(form, w, h, samples, rgb_sum, lum_sq_sum, pos_t, nrm_id, asum, hc, hn, ha, hpos_t, hnrm_id, cam16, front=0,
+                         min_albedo=PT_DEMOD_MIN_ALBEDO, timing_reps=0):
+    """The ALBEDO forms of k_temporal over host arrays (test library, no renderer; pt_test_temporal_albedo): test_temporal's arguments, and asum
+    (h, w, 4) the current view's albedo sums, ha (h, w, 4) the history's albedo.  form 0 / 1 / 2: the filter, capture, moments form.  front (form
+    0): 0 the blend alone, 1 the fused front, 2 the two launches it fuses.  Returns (out (h * w, 4), out_n (h * w,) or None, (Ab, tot) (h * w, 4));
+    timing_reps > 0: also the times of the front in ms."""
+    f = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(w * h * k)
+    S, Q, pos, nrm, A = f(rgb_sum, 3), f(lum_sq_sum, 1), f(pos_t, 4), f(nrm_id, 4), f(asum, 4)
+    Hc, Hn, Ha, Hpos, Hnrm = f(hc, 4), f(hn, 1), f(ha, 4), f(hpos_t, 4), f(hnrm_id, 4)
+    cam = np.ascontiguousarray(cam16, np.float32).reshape(16)
+    out, out_n, out_a = np.empty((w * h, 4), np.float32), np.empty(w * h, np.float32), np.empty((w * h, 4), np.float32)
+    ms = np.zeros(max(timing_reps, 1), np.float32)
+    _tcheck(test_lib().pt_test_temporal_albedo(int(form), int(front), w, h, samples, _p(S), _p(Q), _p(pos), _p(nrm), _p(A), _p(Hc), _p(Hn), _p(Ha),
+                                               _p(Hpos), _p(Hnrm), _p(cam), min_albedo, _p(out), _p(out_n), _p(out_a), timing_reps,
+                                               _p(ms) if timing_reps > 0 else None))
+    res = (out, out_n if form else None, out_a)
+    return (res, ms) if timing_reps > 0 else res
+
+
+def test_history_albedo():
+    """pt_test_history_albedo: the albedo image (H, W, 4) = (Ab, tot) of the history the test library's current context holds (inside
+    renderer_from_test_library), or None: no history, or one made without demod_history=True."""
+    T = test_lib()
+    wh = np.zeros(2, np.int32)
+    _tcheck(T.pt_test_history_albedo(_p(wh), None))
+    w, h = int(wh[0]), int(wh[1])
+    if w == 0:
+        return None
+    ha = np.empty((h, w, 4), np.float32)
+    _tcheck(T.pt_test_history_albedo(_p(wh), _p(ha)))
+    return ha
 
 
 def test_exp_neg_poly(a):

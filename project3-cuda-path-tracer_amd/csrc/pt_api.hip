@@ -172,10 +172,12 @@ struct Slot {
 struct History {
     DevBuf<float4> hc[2];           // (mean r, g, b, mean squared luminance): a ping-pong pair, `cur` the half that holds the history ...
     DevBuf<float> hn[2];            // ... and the effective sample counts, 0 = none
+    DevBuf<float4> ha[2];           // PT_FLAG_DEMOD_HISTORY: ... and (the mean first-hit albedo, unfloored; the uncapped count), the same ping-pong
     DevBuf<float4> hpos, hnrm;      // the old view's guide buffers of guide_iter 1, handed over by its renderer
     TemporalCam cam = {};           // the old view's camera
     int cur = 0, W = 0, H = 0;
     bool live = false;
+    bool albedo = false;            // the renderer that made it carried PT_FLAG_DEMOD_HISTORY: ha[cur] is live too
 };
 
 // (it keeps the scalars of the scene's plan -- cam, prm, P, nLocal, flags, the flags that pick the forms of k_bounce, the sizes -- as its base)
@@ -216,6 +218,7 @@ struct State : PlanScalars {
     DevBuf<float> dnVar;            // pt_variance's / pt_denoise_var's variance image
     DevBuf<float> dnCount;          // PT_FLAG_SPATIAL_VARIANCE: the effective sample counts of a one-sample frame (pt_spatial_var.h); pt_init's
     DevBuf<float4> albedo;          // PT_FLAG_DEMODULATE: per pixel (the sum of the committed iterations' first-hit albedo, their number) (pt_albedo.h); pt_init's
+    DevBuf<float4> dnAlbedo;        // PT_FLAG_DEMOD_HISTORY: (Ab, tot), the blend of the reprojected albedo with `albedo` (pt_temporal.h, ALBEDO); pt_init's
     int dnGuideIter = 0;
     // the noise statistics (pt_noise.h), all allocated on first use: the frame's two result words on the device, the tile map, and -- for
     // pt_iterate_until, whose checks the host reads while the stream runs on -- two copies of the words in page-locked memory, each with the
@@ -880,9 +883,9 @@ TemporalCam temporal_camera(const KParams &k) {
 
 // k_temporal over the renderer and its context's history, on its stream: the blend of `samples` committed iterations with the history -- the
 // halves a live history holds; none, or useHistory false: every pixel goes without -- into out (and outN: the capture and the moments form);
-// needs the guides (ensure_guides)
-template <int FORM>
-int temporal_blend(float samples, float4 *out, float *outN, bool useHistory = true) {
+// needs the guides (ensure_guides).  ALBEDO (PT_FLAG_DEMOD_HISTORY): the blend of the albedo too, into outA.
+template <int FORM, bool ALBEDO = false>
+int temporal_blend(float samples, float4 *out, float *outN, bool useHistory = true, float4 *outA = nullptr) {
     const State &S = R();
     const History &hs = S.hist;
     const bool live = useHistory && hs.live;
@@ -895,7 +898,10 @@ int temporal_blend(float samples, float4 *out, float *outN, bool useHistory = tr
     T.W = S.prm.W; T.H = S.prm.H;
     T.samples = samples;
     T.out = out; T.outN = outN;
-    hipLaunchKernelGGL(k_temporal<FORM>, dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
+    T.ha = live && ALBEDO ? hs.ha[hs.cur].p : nullptr;
+    T.asum = S.albedo.p; T.outA = outA; T.eps = PT_DEMOD_MIN_ALBEDO;
+    if (ALBEDO && (!outA || !T.asum || (live && !hs.albedo))) return fail(PT_ERR_INVALID, "internal error: an albedo blend without its images");
+    hipLaunchKernelGGL((k_temporal<FORM, ALBEDO>), dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
     HIPCHECK(hipGetLastError());
     return PT_OK;
 }
@@ -912,8 +918,12 @@ int capture_history() {
     const int nxt = hs.live ? hs.cur ^ 1 : 0;
     if (!hs.hc[nxt].p) PTCHECK(hs.hc[nxt].alloc(P));
     if (!hs.hn[nxt].p) PTCHECK(hs.hn[nxt].alloc(P));
+    // PT_FLAG_DEMOD_HISTORY: Ha' = (Ab, tot) beside them (pt_init keeps history only between renderers that agree on the flag)
+    const bool withAlbedo = (S.flags & PT_FLAG_DEMOD_HISTORY) != 0;
+    if (withAlbedo && !hs.ha[nxt].p) PTCHECK(hs.ha[nxt].alloc(P));
     // (S.committed, not `iterations`: pt_counters_reset zeroes that one and leaves the accumulators)
-    PTCHECK(temporal_blend<kTemporalCapture>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p));
+    if (withAlbedo) PTCHECK((temporal_blend<kTemporalCapture, true>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p, true, hs.ha[nxt].p)));
+    else PTCHECK(temporal_blend<kTemporalCapture>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p));
     HIPCHECK(hipStreamSynchronize(S.stream));      // (the guides it read are released next)
     hs.hpos = std::move(S.dnPosT);
     hs.hnrm = std::move(S.dnNrmId);
@@ -921,8 +931,16 @@ int capture_history() {
     hs.cam = temporal_camera(S.prm);
     hs.cur = nxt; hs.W = S.prm.W; hs.H = S.prm.H;
     hs.live = true;
+    hs.albedo = withAlbedo;
     return PT_OK;
 }
+
+// PT_FLAG_DEMOD_HISTORY at two samples and more: the front as ONE launch, k_temporal<kTemporalFilterDemod, true>, or as the two it fuses,
+// k_temporal<kTemporalFilter, true> and k_demodulate<true> -- the same bits.  Measured (profiles/demod_history_cost.txt): at 1280 x 720 the
+// fused front takes 0.044 ms against the two launches' 0.051, at 1920 x 1080 0.074 against 0.089 -- ahead by 0.007 and 0.015 ms, several
+// times the two-launch form's best-to-median spread of 0.001 and 0.002 ms.  The two launches stay in the test build alone
+// (pt_test_temporal_albedo).
+constexpr bool kDemodHistoryFused = true;
 
 // ---- the spatial variance estimate (pt_spatial_var.h) -------------------------------------------------------------------------------------
 enum { kSpatialGather = 0, kSpatialTiled = 1 };
@@ -1021,19 +1039,30 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     // PT_FLAG_DEMODULATE (pt_albedo.h): k_demodulate between the front and level 0, which then always runs as a later level at step 1, and
     // AtrousDemod's last level, which multiplies the albedo back
     const bool demod = (R().flags & PT_FLAG_DEMODULATE) != 0;
+    // PT_FLAG_DEMOD_HISTORY while the context holds history of the flagged kind (pt_temporal.h, ALBEDO): the blends also leave (Ab, tot) in
+    // R().dnAlbedo, k_demodulate divides by it (samples 1: x / 1 is exact), and below PT_DEMOD_HISTORY_MIN_OWN samples the last level multiplies
+    // it back -- from there on the renderer's own sums.  Without live history: PT_FLAG_DEMODULATE's launches.
+    const bool demodHist = temporal && (R().flags & PT_FLAG_DEMOD_HISTORY) && hist.albedo;
     AtrousDemodArgs A;                 // (AtrousVarArgs and, behind them, what AtrousDemod's last level alone reads)
     A.moments = R().moments.p;
     A.samplesM1 = (float)(samples - 1);
     A.asum = R().albedo.p; A.demodN = (float)samples; A.demodEps = PT_DEMOD_MIN_ALBEDO;
+    if (demodHist && samples < PT_DEMOD_HISTORY_MIN_OWN) { A.asum = R().dnAlbedo.p; A.demodN = 1.0f; }
+    bool frontDemodulated = false;     // (the fused front has divided already)
     const auto prepare = [&]() -> int {
         if (wantVar && !R().dnVar.p) PTCHECK(R().dnVar.alloc((size_t)R().P));
         A.outVar = wantVar ? R().dnVar.p : nullptr;       // (read by a last level alone)
         if (!temporal && !spatial) return PT_OK;
         if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc((size_t)R().P));
+        if (!spatial && demodHist) {
+            frontDemodulated = kDemodHistoryFused;
+            return temporal_blend<kDemodHistoryFused ? kTemporalFilterDemod : kTemporalFilter, true>((float)samples, R().dnPing[1].p, nullptr, true, R().dnAlbedo.p);
+        }
         if (!spatial) return temporal_blend<kTemporalFilter>((float)samples, R().dnPing[1].p, nullptr);
         // the moments image goes into dnPing[0], which level 0 overwrites only afterwards
         if (!R().dnPing[0].p) PTCHECK(R().dnPing[0].alloc((size_t)R().P));
-        PTCHECK(temporal_blend<kTemporalMoments>((float)samples, R().dnPing[0].p, R().dnCount.p, temporal));
+        if (demodHist) PTCHECK((temporal_blend<kTemporalMoments, true>((float)samples, R().dnPing[0].p, R().dnCount.p, true, R().dnAlbedo.p)));
+        else PTCHECK(temporal_blend<kTemporalMoments>((float)samples, R().dnPing[0].p, R().dnCount.p, temporal));
         SpatialArgs B;
         B.m4 = R().dnPing[0].p; B.cnt = R().dnCount.p;
         B.posT = R().dnPosT.p; B.nrmId = R().dnNrmId.p;
@@ -1046,12 +1075,17 @@ int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int 
     if (!demod) return atrous_run<AtrousGuided>(A, samples, p, p->sigma_lum, form, ms, who, temporal || spatial, prepare, bytesOut, fused);
     return atrous_run<AtrousGuided, AtrousDemod>(A, samples, p, p->sigma_lum, form, ms, who, true, [&]() -> int {
         PTCHECK(prepare());
+        if (frontDemodulated) return PT_OK;
         if (!R().dnPing[1].p) PTCHECK(R().dnPing[1].alloc((size_t)R().P));
         DemodArgs D;
         D.accum = R().image; D.moments = R().moments.p;
         D.img = R().dnPing[1].p; D.asum = R().albedo.p;
         D.npix = R().P;
         D.samples = (float)samples; D.samplesM1 = (float)(samples - 1); D.eps = PT_DEMOD_MIN_ALBEDO;
+        if (demodHist) {      // in place on the blend (or on the estimate made of it), by the blended albedo as a mean of one
+            D.asum = R().dnAlbedo.p; D.samples = 1.0f; D.samplesM1 = 0.0f;
+            return demod_launch(D, true, R().stream);
+        }
         return demod_launch(D, spatial, R().stream);      // (in place on the image k_spatial_variance_* left, or from the accumulators)
     }, bytesOut, fused);
 }
@@ -1289,8 +1323,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     register_exit_handler();
     // PT_FLAG_TEMPORAL on the renderer that goes and on the one that comes, the same frame size and device: the context's history lives on,
     // and the old view -- if it committed anything -- is blended into it first, on the old renderer's stream (free_renderer waits for it)
-    bool keepHistory = R().init && (R().flags & plan.flags & PT_FLAG_TEMPORAL) && R().prm.W == plan.prm.W && R().prm.H == plan.prm.H &&
-                       (o.device < 0 || o.device == R().device);
+    // (PT_FLAG_DEMOD_HISTORY: only between two renderers that agree on it -- a history with albedo and one without are different things)
+    bool keepHistory = R().init && (R().flags & plan.flags & PT_FLAG_TEMPORAL) && !((R().flags ^ plan.flags) & PT_FLAG_DEMOD_HISTORY) &&
+                       R().prm.W == plan.prm.W && R().prm.H == plan.prm.H && (o.device < 0 || o.device == R().device);
     // (an old view whose scene k_gbuffer cannot trace -- a mesh hierarchy deeper than its 64 KB of stacks, the one thing pt_gbuffer answers
     // PT_ERR_INVALID to -- has no guides to reproject through: the history ends there, and pt_init goes on.  What is left to fail in the
     // capture is a HIP call: PT_ERR_HIP, which leaves the context without a renderer like every other one of pt_init's.)
@@ -1336,7 +1371,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         const size_t spatial = (S.flags & PT_FLAG_SPATIAL_VARIANCE) ? (size_t)S.P * sizeof(float) : 0;
         // ... and PT_FLAG_DEMODULATE's one image, the albedo sums
         const size_t albedo = (S.flags & PT_FLAG_DEMODULATE) ? (size_t)S.P * sizeof(float4) : 0;
-        const size_t need = perSlot * (size_t)S.nslots + display + spatial + albedo;
+        // ... and PT_FLAG_DEMOD_HISTORY's one image, the blended albedo
+        const size_t albedoBlend = (S.flags & PT_FLAG_DEMOD_HISTORY) ? (size_t)S.P * sizeof(float4) : 0;
+        const size_t need = perSlot * (size_t)S.nslots + display + spatial + albedo + albedoBlend;
         size_t freeB = 0, totalB = 0;
         HIPCHECK(hipMemGetInfo(&freeB, &totalB));
         if (need > freeB)
@@ -1351,6 +1388,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     }
     if (S.flags & PT_FLAG_SPATIAL_VARIANCE) PTCHECK(S.dnCount.alloc((size_t)S.P));
     if (S.flags & PT_FLAG_DEMODULATE) PTCHECK(S.albedo.alloc_zeroed((size_t)S.P));
+    if (S.flags & PT_FLAG_DEMOD_HISTORY) PTCHECK(S.dnAlbedo.alloc((size_t)S.P));
     for (int i = 0; i < S.nslots; ++i) {
         Slot &sl = S.slot[i];
         HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));

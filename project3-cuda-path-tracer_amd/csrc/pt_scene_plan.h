@@ -255,10 +255,13 @@ int check_scene(const SceneIn &in) {
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_SPATIAL_VARIANCE needs PT_FLAG_MOMENTS (the estimate is made of the second moments)");
     if (o.flags & PT_FLAG_DEMODULATE) {
         if (!(o.flags & PT_FLAG_MOMENTS)) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE needs PT_FLAG_MOMENTS (the filter it feeds is guided by the variance)");
-        if (o.flags & PT_FLAG_TEMPORAL) return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE is not for PT_FLAG_TEMPORAL renderers (history carries no albedo)");
+        if ((o.flags & PT_FLAG_TEMPORAL) && !(o.flags & PT_FLAG_DEMOD_HISTORY))
+            return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE is not for PT_FLAG_TEMPORAL renderers (history carries no albedo)");
         if (o.flags & PT_FLAG_TRACE_AHEAD)
             return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMODULATE is not for PT_FLAG_TRACE_AHEAD renderers (the albedo follows the committed iterations)");
     }
+    if ((o.flags & PT_FLAG_DEMOD_HISTORY) && (~o.flags & (PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL | PT_FLAG_DEMODULATE)))
+        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMOD_HISTORY needs PT_FLAG_MOMENTS, PT_FLAG_TEMPORAL and PT_FLAG_DEMODULATE (it joins the two)");
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;

@@ -6,6 +6,9 @@
 //   k_temporal<kTemporalCapture>   the CAPTURE form: the same blend, stored as the next history (mean colour, mean squared luminance; the capped count)
 //   k_temporal<kTemporalMoments>   the MOMENTS form: the same blend, stored with the count uncapped -- what the spatial variance estimate reads
 //                                  (PT_FLAG_SPATIAL_VARIANCE: pt_spatial_var.h)
+//   k_temporal<FORM, true>         ALBEDO (PT_FLAG_DEMOD_HISTORY): each of the three also blends the history's mean first-hit albedo with the
+//                                  renderer's albedo sums and writes it; kTemporalFilterDemod is the filter form with the division by that
+//                                  albedo folded into its store.  The ALBEDO = false forms are the kernels they were before.
 //
 // ---- the kernel, operation by operation (tests/temporal_ref.py restates it in numpy, bit for bit: every fp32 operation below is one IEEE
 // operation, -ffp-contract=off, in the order written; dot = (x + y) + z as ptd::dot) ----
@@ -27,12 +30,24 @@
 //   8  filter   L = atrousLum(c);  dd = m2 - L * L;  dd = dd > 0 ? dd : 0 (a NaN gives 0);  out = (c, dd / (tot - 1))
 //      capture  Hc' = (c, m2);  Hn' = tot < cap ? tot : cap
 //      moments  M = (c, m2);  N = tot
+// ---- ALBEDO (PT_FLAG_DEMOD_HISTORY: the history also carries the mean first-hit albedo; tests/temporal_demod_ref.py restates it) ----
+//   inputs      Ha = (mean first-hit albedo r, g, b; .w is never read) beside Hc, and Asum, the renderer's albedo sums (k_albedo's, pt_albedo.h)
+//   5           every tap that counts also adds  sumA.k += Ha[q].k * w  (k = r, g, b) -- from 0; taps, conditions and order as above
+//   6           ha.k = sumA.k / sumW
+//   7           no history: ha = 0.  Ab.k = (ha.k * Nh + Asum.k) / tot
+//   8           outA = (Ab, tot) in every form: the capture's is the next history's Ha', the filter's and the moments form's what k_demodulate
+//               divides out (with samples = 1: x / 1 is exact) and, below PT_DEMOD_HISTORY_MIN_OWN samples, what the last level multiplies back
+//      fused    kTemporalFilterDemod: the filter form with k_demodulate's operations (pt_albedo.h) applied to its own result before the store:
+//               A'.k = Ab.k > eps ? Ab.k : eps;  c'.k = c.k / A'.k;  L' = lum(c');  rho = L > 0 ? L' / L : 1;  out = (c', v * (rho * rho))
+//               -- the bits of k_temporal<kTemporalFilter, true> followed by k_demodulate<true>
+// Without history Ab = (0 * 0 + Asum) / n = Asum / n: the bits demodAlbedo forms before its floor.
 // Without history step 7 is 0 * 0 + S = S over n and step 8 is meanAndVariance(S, Q) to the bit (sums are never -0: they grow from +0).
 // cap, c_n, c_p, w_min: PT_TEMPORAL_MAX_HISTORY, _NORMAL_DOT, _PLANE_FRACTION, _MIN_WEIGHT of include/pt_amd.h.
 //
 // Cost: a gather.  A pixel reads its own 60 bytes (S 12, Q 4, two guide float4s 32, and 12 of padding it does not use), up to four taps of
 // 52 bytes from four arrays -- neighbouring pixels project to neighbouring old pixels, so a wave's taps fall into the cache lines its
-// neighbours fetch -- and writes 16 (filter) or 20 bytes (capture).
+// neighbours fetch -- and writes 16 (filter) or 20 bytes (capture).  ALBEDO: a tap reads 68 bytes from five arrays, a pixel 16 more of its own
+// (Asum) and writes 16 more (outA).
 #pragma once
 #include "pt_denoise.h"
 
@@ -56,12 +71,18 @@ struct TemporalArgs {
     float samples;
     float4 *out;                      // filter: (c, variance); capture: Hc'; moments: M
     float *outN;                      // capture: Hn'; moments: N
+    // ALBEDO alone reads what follows (behind the members every form reads: their places in the kernel's arguments are the unflagged build's)
+    const float4 *ha;                 // history: the mean first-hit albedo (NULL with hn)
+    const float4 *asum;               // the current view's albedo sums
+    float4 *outA;                     // (Ab, tot)
+    float eps;                        // kTemporalFilterDemod: PT_DEMOD_MIN_ALBEDO
 };
 
-enum { kTemporalFilter = 0, kTemporalCapture = 1, kTemporalMoments = 2 };
+enum { kTemporalFilter = 0, kTemporalCapture = 1, kTemporalMoments = 2, kTemporalFilterDemod = 3 };
 
-template <int FORM>
+template <int FORM, bool ALBEDO = false>
 __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
+    static_assert(FORM != kTemporalFilterDemod || ALBEDO, "the fused front divides by the blended albedo");
     const int npix = A.W * A.H;
     const int pix = blockIdx.x * kBlock + threadIdx.x;
     if (pix >= npix) return;
@@ -69,6 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
     const float4 pp = A.posT[pix], np = A.nrmId[pix];
     const int id = __float_as_int(np.w);
     float hcx = 0.0f, hcy = 0.0f, hcz = 0.0f, hcw = 0.0f, Nh = 0.0f;
+    float hax = 0.0f, hay = 0.0f, haz = 0.0f;
     if (A.hn != nullptr && id >= 0) {
         const TemporalCam &c = A.cam;
         const float dx = pp.x - c.e[0], dy = pp.y - c.e[1], dz = pp.z - c.e[2];
@@ -84,6 +106,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
                 const int x0 = (int)fx, y0 = (int)fy;
                 const float lim = PT_TEMPORAL_PLANE_FRACTION * pp.w;
                 float sumW = 0.0f, sumN = 0.0f, sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
+                float ax = 0.0f, ay = 0.0f, az = 0.0f;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int qy = y0 + j;
@@ -109,12 +132,19 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
                         sz += h.z * w;
                         sw += h.w * w;
                         sumN += nq * w;
+                        if (ALBEDO) {
+                            const float4 a = A.ha[q];
+                            ax += a.x * w;
+                            ay += a.y * w;
+                            az += a.z * w;
+                        }
                     }
                 }
                 if (sumW > PT_TEMPORAL_MIN_WEIGHT) {
                     hcx = sx / sumW; hcy = sy / sumW; hcz = sz / sumW; hcw = sw / sumW;
                     const float hn = sumN / sumW;
                     Nh = hn < cap ? hn : cap;
+                    if (ALBEDO) { hax = ax / sumW; hay = ay / sumW; haz = az / sumW; }
                 }
             }
         }
@@ -123,6 +153,12 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
     const float tot = Nh + A.samples;
     const float r = (hcx * Nh + S[0]) / tot, g = (hcy * Nh + S[1]) / tot, b = (hcz * Nh + S[2]) / tot;
     const float m2 = (hcw * Nh + A.moments[pix]) / tot;
+    float abx = 0.0f, aby = 0.0f, abz = 0.0f;
+    if (ALBEDO) {
+        const float4 as = A.asum[pix];
+        abx = (hax * Nh + as.x) / tot; aby = (hay * Nh + as.y) / tot; abz = (haz * Nh + as.z) / tot;
+        A.outA[pix] = make_float4(abx, aby, abz, tot);
+    }
     if (FORM == kTemporalCapture) {
         A.out[pix] = make_float4(r, g, b, m2);
         A.outN[pix] = tot < cap ? tot : cap;
@@ -133,7 +169,16 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
         const float L = atrousLum(r, g, b);
         float dd = m2 - L * L;
         dd = dd > 0.0f ? dd : 0.0f;
-        A.out[pix] = make_float4(r, g, b, dd / (tot - 1.0f));
+        const float var = dd / (tot - 1.0f);
+        if (FORM == kTemporalFilterDemod) {
+            const float alx = abx > A.eps ? abx : A.eps, aly = aby > A.eps ? aby : A.eps, alz = abz > A.eps ? abz : A.eps;
+            const float rd = r / alx, gd = g / aly, bd = b / alz;
+            const float Ld = atrousLum(rd, gd, bd);
+            const float rho = L > 0.0f ? Ld / L : 1.0f;
+            A.out[pix] = make_float4(rd, gd, bd, var * (rho * rho));
+        } else {
+            A.out[pix] = make_float4(r, g, b, var);
+        }
     }
 }
 

@@ -1345,6 +1345,76 @@ int pt_test_history(int32_t *wh2, float *hc4, float *hn, float *hpos_t4, float *
     return PT_OK;
 }
 
+int pt_test_history_albedo(int32_t *wh2, float *ha4) {
+    if (!wh2) return fail(PT_ERR_INVALID, "pt_test_history_albedo: null");
+    const History &hs = R().hist;
+    const bool has = hs.live && hs.albedo;
+    wh2[0] = has ? hs.W : 0;
+    wh2[1] = has ? hs.H : 0;
+    if (!has) return PT_OK;
+    if (ha4) HIPCHECK(hipMemcpy(ha4, hs.ha[hs.cur].p, (size_t)hs.W * hs.H * sizeof(float4), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_test_temporal_albedo(int form, int front, int w, int h, int samples, const float *rgb_sum, const float *lum_sq_sum, const float *pos_t4,
+                            const float *nrm_id4, const float *asum4, const float *hc4, const float *hn, const float *ha4, const float *hpos_t4,
+                            const float *hnrm_id4, const float *cam16, float min_albedo, float *out4, float *out_n, float *out_a4, int reps, float *ms) {
+    NEED_GPU();
+    if (form < 0 || form > 2 || front < 0 || front > 2 || (form != 0 && front != 0) || w < 1 || h < 1 || (long long)w * h > (1ll << 30) || samples < 1 ||
+        !rgb_sum || !lum_sq_sum || !pos_t4 || !nrm_id4 || !asum4 || !hc4 || !hn || !ha4 || !hpos_t4 || !hnrm_id4 || !cam16 || !(min_albedo > 0.0f) || !out4 ||
+        (form && !out_n) || !out_a4 || (ms && reps < 1))
+        return fail(PT_ERR_INVALID, "pt_test_temporal_albedo: bad argument");
+    const size_t P = (size_t)w * h;
+    DevBuf<float> S, Q, Hn, outN;
+    DevBuf<float4> pos, nrm, Asum, Hc, Ha, Hpos, Hnrm, out, outA;
+    PTCHECK(S.upload(rgb_sum, P * 3));
+    PTCHECK(Q.upload(lum_sq_sum, P));
+    PTCHECK(Hn.upload(hn, P));
+    PTCHECK(pos.upload(reinterpret_cast<const float4 *>(pos_t4), P));
+    PTCHECK(nrm.upload(reinterpret_cast<const float4 *>(nrm_id4), P));
+    PTCHECK(Asum.upload(reinterpret_cast<const float4 *>(asum4), P));
+    PTCHECK(Hc.upload(reinterpret_cast<const float4 *>(hc4), P));
+    PTCHECK(Ha.upload(reinterpret_cast<const float4 *>(ha4), P));
+    PTCHECK(Hpos.upload(reinterpret_cast<const float4 *>(hpos_t4), P));
+    PTCHECK(Hnrm.upload(reinterpret_cast<const float4 *>(hnrm_id4), P));
+    PTCHECK(out.alloc(P));
+    PTCHECK(outN.alloc(P));
+    PTCHECK(outA.alloc(P));
+    TemporalArgs T;
+    T.accum = S.p; T.moments = Q.p; T.posT = pos.p; T.nrmId = nrm.p;
+    T.hc = Hc.p; T.hn = Hn.p; T.hpos = Hpos.p; T.hnrm = Hnrm.p;
+    memcpy(&T.cam, cam16, sizeof T.cam);
+    T.W = w; T.H = h; T.samples = (float)samples;
+    T.out = out.p; T.outN = outN.p;
+    T.ha = Ha.p; T.asum = Asum.p; T.outA = outA.p; T.eps = min_albedo;
+    DemodArgs D;
+    D.accum = nullptr; D.moments = nullptr; D.img = out.p; D.asum = outA.p;
+    D.npix = (int)P;
+    D.samples = 1.0f; D.samplesM1 = 0.0f; D.eps = min_albedo;
+    const dim3 grid((unsigned)((P + kBlock - 1) / kBlock));
+    EventSet es;
+    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed run first)
+        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        if (form == 2) hipLaunchKernelGGL((k_temporal<kTemporalMoments, true>), grid, dim3(kBlock), 0, nullptr, T);
+        else if (form == 1) hipLaunchKernelGGL((k_temporal<kTemporalCapture, true>), grid, dim3(kBlock), 0, nullptr, T);
+        else if (front == 1) hipLaunchKernelGGL((k_temporal<kTemporalFilterDemod, true>), grid, dim3(kBlock), 0, nullptr, T);
+        else hipLaunchKernelGGL((k_temporal<kTemporalFilter, true>), grid, dim3(kBlock), 0, nullptr, T);
+        if (front == 2) PTCHECK(demod_launch(D, true, nullptr));
+        if (ms && r) {
+            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+            HIPCHECK(hipEventSynchronize(es.ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(out_a4, outA.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (form) PTCHECK(download(out_n, outN, P));
+    return PT_OK;
+}
+
 int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, int h, int samples, float threshold, float lum_floor, PtNoiseStats *out,
                         size_t stats_struct_bytes, float *tile_rel_var_host, int tiles_per_wave, int reps, float *ms) {
     NEED_GPU();

@@ -7,7 +7,7 @@
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 //                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
-//                           [--history-from EX EY EZ N] [--spatial-variance] [--demodulate]
+//                           [--history-from EX EY EZ N] [--spatial-variance] [--demodulate] [--history-albedo]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
@@ -28,6 +28,9 @@
 // --history-from a new view of one sample.
 // --demodulate (with --denoise-var; not with --history-from) runs the renderer with PT_FLAG_DEMODULATE: <out>.denoised.png is the filter of the
 // frame divided by every pixel's mean first-hit albedo, multiplied back behind it (include/pt_amd.h, "demodulation").
+// --history-albedo (with --denoise-var and --history-from) runs both renderers with PT_FLAG_TEMPORAL, PT_FLAG_DEMODULATE and
+// PT_FLAG_DEMOD_HISTORY: the history carries the first view's albedo, and <out>.denoised.png is the filter of the blend divided by the blended
+// albedo (include/pt_amd.h, "demodulated history").
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -67,6 +70,7 @@ static float historyEye[3] = {0.0f, 0.0f, 0.0f};
 static int historyIterations = 0;
 static bool spatialVariance = false;
 static bool demodulate = false;
+static bool historyAlbedo = false;
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 void pathtraceSpatialVariance(bool on);                                             // pathtrace_shim.cpp
@@ -151,6 +155,7 @@ static void renderBatched() {
     if (historyFrom) opt.flags |= PT_FLAG_TEMPORAL;
     if (spatialVariance) opt.flags |= PT_FLAG_SPATIAL_VARIANCE;
     if (demodulate) opt.flags |= PT_FLAG_DEMODULATE;
+    if (historyAlbedo) opt.flags |= PT_FLAG_DEMODULATE | PT_FLAG_DEMOD_HISTORY;      // (PT_FLAG_MOMENTS and PT_FLAG_TEMPORAL: set above, it needs both options)
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -162,6 +167,35 @@ static void renderBatched() {
         meshes.push_back(m);
     }
     check(pt_set_meshes(meshes.empty() ? NULL : meshes.data(), (int)meshes.size()), "pt_set_meshes");
+    // --history-albedo: the scene's textures and their bindings too (like pathtrace_shim.cpp) -- the albedo the history carries is theirs.
+    // (Every other run through here registers none, as before.)
+    std::vector<PtTexture> textures;
+    std::vector<PtTexBinding> bindings;
+    if (historyAlbedo) {
+        for (size_t i = 0; i < scene->textures.size(); ++i) {
+            PtTexture t;
+            t.width = scene->textures[i].width;
+            t.height = scene->textures[i].height;
+            t.rgb = scene->textures[i].rgb.data();
+            textures.push_back(t);
+        }
+        for (size_t g = 0; g < scene->geomTextures.size(); ++g) {
+            if (scene->geomTextures[g] < 0) continue;
+            PtTexBinding b;
+            b.geom = (int)g;
+            b.texture = scene->geomTextures[g];
+            b.ntris = 0;
+            b.uvs = NULL;
+            for (size_t i = 0; i < scene->meshes.size(); ++i)
+                if (scene->meshes[i].geom == (int)g) {
+                    b.ntris = (int)(scene->meshes[i].tris.size() / 9);
+                    b.uvs = scene->meshes[i].uvs.empty() ? NULL : scene->meshes[i].uvs.data();
+                }
+            bindings.push_back(b);
+        }
+        check(pt_set_textures(textures.empty() ? NULL : textures.data(), (int)textures.size(), sizeof(PtTexture),
+                              bindings.empty() ? NULL : bindings.data(), (int)bindings.size(), sizeof(PtTexBinding)), "pt_set_textures");
+    }
     int firstIter = 1;                 // the iteration number of the frame's first sample
     if (historyFrom) {                 // the view before the camera moved: its samples stay behind as the context's history
         PtCamera before;
@@ -211,7 +245,7 @@ static void renderBatched() {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N] [--spatial-variance] [--demodulate]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N] [--spatial-variance] [--demodulate] [--history-albedo]\n", argv[0]);
         return 1;
     }
     try {
@@ -259,9 +293,11 @@ int main(int argc, char **argv) {
         }
         else if (!strcmp(argv[i], "--spatial-variance")) spatialVariance = true;
         else if (!strcmp(argv[i], "--demodulate")) demodulate = true;
+        else if (!strcmp(argv[i], "--history-albedo")) historyAlbedo = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
     if (denoise && denoiseVar) { fprintf(stderr, "--denoise and --denoise-var exclude each other\n"); return 1; }
+    if (historyAlbedo && (!denoiseVar || !historyFrom)) { fprintf(stderr, "--history-albedo needs --denoise-var and --history-from\n"); return 1; }
     if (historyFrom && (!denoiseVar || noiseTarget || historyIterations < 1)) {
         fprintf(stderr, "--history-from needs --denoise-var and N >= 1, and does not go with --noise-threshold\n");
         return 1;
