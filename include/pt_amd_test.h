@@ -60,6 +60,11 @@ int pt_test_sphere_clusters(const PtGeom *geoms, int ngeoms, float *info18, int3
  * the wall a path can still hit) soundness: as above, for the cubes of `geoms`. */
 int pt_test_wall_box_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t *culled,
                            uint64_t *violations);
+/* The slab certificate's two evaluations on the caller's rays (rays: n x {origin3, direction3}) against ONE cube and its inflated world
+ * box: flags[i] bit 0 = wallCertainMiss from three reciprocals formed once (k_bounce's PLAIN forms: shared with the walls' block), bit 1 =
+ * wallCertainMissByAxis (the other forms), bit 2 = the origin's |x| + |y| + |z| lies within the box's bound, bit 3 = the full box test
+ * hits.  box7 (or NULL) = the box {lo3, hi3} and the bound.  n = 0: the box alone. */
+int pt_test_slab_decisions(const PtGeom *cube, const float *rays, int n, uint32_t *flags, float *box7);
 /* wallPlanesPossible / wallPlanesOriented (the one-plane-per-wall certificates of the survivors' queue classes; pt_init's choose_walls numbers the cubes of
  * `geoms` as walls exactly as a render would) soundness: `rays` pseudo-random rays from the walls' inner faces, the corners, the
  * interior and beyond; *violations = (ray, wall) pairs certified as missed although the full test hits (must be 0), *certified =
@@ -121,7 +126,9 @@ int pt_test_wall_resolve_tally(uint64_t counts[4]);
  * certified face inside candidate tiles would serve: measured and not kept, profiles/candidate_tiles.txt); [3] lanes of
  * candidate tiles whose nearest hit is a binned primitive}.  Per scatter of a scene that bins: {[4] paths that live on; [5] of them the
  * candidates by the bounding balls alone; [6] the candidates by the rule in force -- the ball, and a second certificate by the primitive's
- * kind (KParams::binBox)}; [7] is 0.  PT_AMD_NO_TIGHT_CANDIDATES=1 (read by the plan, tests only): no second certificate, [6] = [5]. */
+ * kind (KParams::binBox): for a cube the slab certificate ALONE, for a sphere the half-line ball; [7] the candidates by the ball beside
+ * that rule (<= [6]: what evaluating a cube's ball as well would leave)}.  PT_AMD_NO_TIGHT_CANDIDATES=1 (read by the plan, tests only): no second
+ * certificate, [7] = [6] = [5]. */
 int pt_test_candidate_tally(uint64_t counts[8]);
 /* Triangle meshes.  pt_test_mesh_intersect: `n` rays against ONE mesh geom on the GPU, through the hierarchy (flat = 0) or a
  * plain list of its triangles (flat = 1: the brute-force rule); outputs keep their input values on a miss; culled[i] = 1 when

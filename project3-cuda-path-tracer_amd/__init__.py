@@ -94,7 +94,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
-    "pt_test_group_create_virtual", "pt_test_emulated_reduce",
+    "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions",
 ]
 
 
@@ -252,6 +252,7 @@ def _bind(L, with_tests):
         L.pt_test_wall_face_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p]
         L.pt_test_wall_resolve_tally.argtypes = [u64p]
         L.pt_test_candidate_tally.argtypes = [u64p]
+        L.pt_test_slab_decisions.argtypes = [vp, vp, i32, vp, vp]
         L.pt_test_camera_cull_margin.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_double), u64p]
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
         L.pt_test_wall_planes.argtypes = [vp, i32, vp, vp] + [C.POINTER(C.c_int32)] * 3
@@ -1403,6 +1404,17 @@ def test_wall_box_sweep(geoms, seed, rays):
     return _u64_outs(test_lib().pt_test_wall_box_sweep, (1, 1), *_geoms_args(geoms), seed, rays)
 
 
+def test_slab_decisions(cube, org, dirs):
+    """pt_test_slab_decisions: the slab certificate's two evaluations on the caller's rays against one cube.  Returns (flags (n,) uint32 --
+    bit 0 shared reciprocals, bit 1 axis by axis, bit 2 the origin within the box's bound, bit 3 the full box test hits --, box lo (3,),
+    box hi (3,), the bound)."""
+    g = np.ascontiguousarray(cube).reshape(-1)[:1]
+    rays = np.ascontiguousarray(np.concatenate([np.asarray(org, np.float32).reshape(-1, 3), np.asarray(dirs, np.float32).reshape(-1, 3)], axis=1))
+    flags, box = np.zeros(len(rays), np.uint32), np.zeros(7, np.float32)
+    _tcheck(test_lib().pt_test_slab_decisions(_p(g), _p(rays), len(rays), _p(flags), _p(box)))
+    return flags, box[:3].copy(), box[3:6].copy(), np.float32(box[6])
+
+
 def camera_cull_tables(camera, geoms):
     """The camera-ray culling tables pt_init derives (host only).  Returns (rects (n, 4), scene rect (4,), spans (H, n, 2))."""
     H = int(np.ascontiguousarray(camera)["resolution"][0][1])
@@ -1465,7 +1477,8 @@ def wall_resolve_tally():
 def candidate_tally():
     """The test library's tally of its renderer's candidate tiles since the last call (read and cleared): (later wave-tiles that hold a
     path, of them candidate tiles, of those tiles of one wall that has an inner face, lanes of candidate tiles that hit a binned primitive,
-    scattered paths of a binning scene, of them candidates by the balls alone, candidates by the rule in force, 0)."""
+    scattered paths of a binning scene, of them candidates by the balls alone, candidates by the rule in force, candidates by the balls
+    beside that rule)."""
     return _u64_outs(test_lib().pt_test_candidate_tally, (8,))
 
 

@@ -45,7 +45,8 @@ __device__ __forceinline__ void tallyWallResolve(int k, unsigned long long n) {
 // an inner face (what a certified face inside candidate tiles would serve; no kernel takes it there: measured, not kept -- profiles/
 // candidate_tiles.txt), [3] the lanes of candidate tiles whose nearest hit is a binned primitive.  Per scatter that bins:
 // [4] the paths that live on, [5] of them the candidates by the bounding balls alone (certainMiss of every binned primitive), [6] the
-// candidates by the rule in force (KParams::binBox; equal to [5] under PT_AMD_NO_TIGHT_CANDIDATES).
+// candidates by the rule in force (KParams::binBox; equal to [5] under PT_AMD_NO_TIGHT_CANDIDATES), [7] the candidates the bounding ball
+// beside that rule would leave (a binned cube's rule is its slab certificate alone: [7] <= [6]).
 __device__ unsigned long long g_candidates[8];
 __device__ __forceinline__ void tallyCandidate(int k, unsigned long long n) {
     if (n != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_candidates[k], n);

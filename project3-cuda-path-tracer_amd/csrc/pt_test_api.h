@@ -726,6 +726,32 @@ int pt_test_wall_box_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64
     return cnt.read({culled, violations});
 }
 
+int pt_test_slab_decisions(const PtGeom *cube, const float *rays, int n, uint32_t *flags, float *box7) {
+    NEED_GPU();
+    if (!cube || !rays || !flags || n < 0) return fail(PT_ERR_INVALID, "pt_test_slab_decisions: bad argument");
+    std::vector<GeomDev> hg;
+    PTCHECK(pack_geoms(cube, 1, kCubes, nullptr, "pt_test_slab_decisions", hg));
+    std::vector<WallBox> hw(1);
+    double om = 0;
+    if (wall_box(cube[0], hw[0], &om) < 0) return fail(PT_ERR_INVALID, "pt_test_slab_decisions: the cube is not finite");
+    const float omax = (float)om;
+    if (box7) {
+        for (int a = 0; a < 3; ++a) box7[a] = hw[0].lo[a], box7[3 + a] = hw[0].hi[a];
+        box7[6] = omax;
+    }
+    if (n == 0) return PT_OK;
+    DevBuf<GeomDev> dg;
+    DevBuf<WallBox> dw;
+    DevBuf<float> dr;
+    DevBuf<uint32_t> df;
+    PTCHECK(dg.upload(hg));
+    PTCHECK(dw.upload(hw));
+    PTCHECK(dr.upload(rays, (size_t)n * 6));
+    PTCHECK(df.alloc(n));
+    PTCHECK(launch_wait(k_test_slab_decisions, blocks_for(n), 0, dg.p, dw.p, omax, dr.p, n, df.p));
+    return download(flags, df, n);
+}
+
 // host only: no GPU is touched
 int pt_test_camera_cull_tables(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int32_t *rects4, int32_t *scene_rect4, int32_t *spans2) {
     if (!cam || !geoms || ngeoms < 1 || !rects4 || !scene_rect4 || !spans2) return fail(PT_ERR_INVALID, "pt_test_camera_cull_tables: bad argument");

@@ -317,6 +317,23 @@ __global__ void k_sweep_wall_box(const GeomDev *geoms, const WallBox *walls, con
     sweepFlush(violations, nv);
 }
 
+// The slab certificate's two evaluations on the CALLER's rays (rays: n x {origin3, direction3}) against one cube `G`, its inflated world box
+// `W` and the box's bound on the origin: flags[i] bit 0 = ptd::wallCertainMiss from reciprocals formed once (the PLAIN forms' scatter), bit 1
+// = ptd::wallCertainMissByAxis (the other forms'), bit 2 = |o|_1 <= omax, bit 3 = the full box test hits.
+__global__ void k_test_slab_decisions(const GeomDev *geom, const WallBox *wall, float omax, const float *rays, int n, uint32_t *flags) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const GeomDev G = geom[0];
+    const WallBox W = wall[0];
+    const F3 org = f3(rays[6 * i], rays[6 * i + 1], rays[6 * i + 2]), dir = f3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
+    const F3 inv = f3(__builtin_amdgcn_rcpf(dir.x), __builtin_amdgcn_rcpf(dir.y), __builtin_amdgcn_rcpf(dir.z));
+    const float l1 = (__builtin_fabsf(org.x) + __builtin_fabsf(org.y)) + __builtin_fabsf(org.z);
+    F3 P, N;
+    bool o;
+    const bool hit = boxIntersectionTest<false>(G, org, dir, P, N, o) != -1.0f;
+    flags[i] = (wallCertainMiss(W, org, inv) ? 1u : 0u) | (wallCertainMissByAxis(W, org, dir) ? 2u : 0u) | (l1 <= omax ? 4u : 0u) | (hit ? 8u : 0u);
+}
+
 // Soundness sweep of the sphere CLUSTERS' box certificates (k_bounce: CLUSTER; pt_api.hip: build_sphere_clusters): `spheres` in table
 // order, the first n0 of them cluster 0; box[g] = cluster g's inflated world box; certificates are issued for origins with
 // |x| + |y| + |z| <= omax.  Rays in four families -- leaving a sphere's own surface as a scatter does (+-1e-3 along the normal); from a point

@@ -8,10 +8,19 @@
 #include "pt_common.h"
 #include "pt_device.h"
 
+// k_bounce's scatter, compile-time switches for A/B builds (make variant DEFS="-DPT_SCATTER_SLAB_ONLY=0"; profiles/scatter_diet.txt):
+// one set of reciprocals and one |o|_1 per scatter in the PLAIN forms; a binned cube's candidacy from its slab certificate alone.
+#ifndef PT_SCATTER_SHARED_RCP
+#define PT_SCATTER_SHARED_RCP 1
+#endif
+#ifndef PT_SCATTER_SLAB_ONLY
+#define PT_SCATTER_SLAB_ONLY 1
+#endif
+
 namespace ptk {
 using namespace ptd;
 
-constexpr int kNumArrays = 11;       // PathSegment: origin3, dir3, throughput3, the pixel's hash, pixelIndex | batch index = 11 dwords = 44 bytes per path
+constexpr int kNumArrays = 11;      // PathSegment: origin3, dir3, throughput3, the pixel's hash, pixelIndex | batch index = 11 dwords = 44 bytes per path
 constexpr int kNumArraysHist = 8;    // ... of a history-coded pool (PathPool; the PLAIN forms): origin3, dir3, one word of material history, pixelIndex | batch index = 32 bytes
 // dwords per path of a pool: histBits = KParams::histBits (0: the general layout)
 __host__ __device__ constexpr int poolDwords(int histBits) { return histBits ? kNumArraysHist : kNumArrays; }
@@ -122,6 +131,8 @@ struct KParams {
     // |x| + |y| + |z| <= omax; 2 = a sphere: the ball's certificate for the HALF-line (ptd::certainMissClamped); 0 = none -- meshes, rows
     // beyond nBinned, and every row under PT_AMD_NO_TIGHT_CANDIDATES (tests only: the classes of the ball alone).  The sphere-heavy forms
     // (k_bounce<..., MANY>) do not read the kind: they bin the light alone and keep the ball (measured: profiles/candidate_tiles.txt).
+    // A cube (kind 1) is a candidate by the slab certificate ALONE, its ball is not evaluated, in every form but the MANY and the mesh
+    // ones (k_bounce: kSlabOnly; profiles/scatter_diet.txt) -- where its origin bound fails it is a candidate outright.
     float binBox[kBinMax][8];
     // ---- walls: the scene's large cubes (non-binned, at most kWallMax).  With walls the three low class bits of a survivor
     // are not its direction octant but WHICH wall it can still hit: 0..5 = that wall only (every other wall certified
@@ -1844,12 +1855,21 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                     org = norg;
                     dir = ndir;
                     fl = 1u;
+                    // kSharedRcp: the new direction's reciprocals and the origin's |x| + |y| + |z| are formed ONCE, here, for the binned cubes' slab
+                    // certificate and for the walls' block below -- in the forms that have the registers to hold four values across the balls
+                    // (the PLAIN forms: profiles/scatter_diet.txt); the others form both twice, the cube's axis by axis, as before.
+                    // kSlabOnly: a binned cube's candidacy is its slab certificate alone, without the bounding ball beside it (MANY forms bin no
+                    // cube; the MESH forms measured 0.2 % slower with it and keep the ball: profiles/scatter_diet.txt, 5)
+                    constexpr bool kSharedRcp = PT_SCATTER_SHARED_RCP && PLAIN;
+                    constexpr bool kSlabOnly = PT_SCATTER_SLAB_ONLY && !MANY && !MESH;
+                    const F3 sInv = kSharedRcp ? f3(__builtin_amdgcn_rcpf(ndir.x), __builtin_amdgcn_rcpf(ndir.y), __builtin_amdgcn_rcpf(ndir.z)) : f3(0.0f, 0.0f, 0.0f);
+                    const float sL1 = kSharedRcp ? (__builtin_fabsf(norg.x) + __builtin_fabsf(norg.y)) + __builtin_fabsf(norg.z) : 0.0f;
                     {                                            // class bit 3: can the new ray hit a small primitive at all?
                         const int nBinned = (int)hotBinned(hotNow());
                         if (nBinned > 0) {
                             const float ndd = dot(ndir, ndir);
                             uint32_t cand = 0u;
-                            PT_TEST_ONLY(uint32_t candBall = 0u;)              // (the test library's tally: the candidacy the ball alone gives)
+                            PT_TEST_ONLY(uint32_t candBall = 0u; uint32_t candBoth = 0u;)      // (the test library's tally: the candidacy the ball alone gives, and the ball beside the rule in force)
                             for (int sI = 0; sI < nBinned; sI += 2) { probe(12);          // two at a time: one 64-byte scalar load
                                 int16v v;
                                 asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(launder(kargs)), "s"((int)(offsetof(BounceArgs, prm) + offsetof(KParams, binCull)) + sI * 32) : "memory");
@@ -1861,6 +1881,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                                 bool miss[2] = {true, true};
                                 uint32_t bit[2] = {0u, 0u};
                                 int kind[2] = {0, 0};
+                                PT_TEST_ONLY(bool ballMiss[2] = {true, true};)
 #pragma unroll
                                 for (int h = 0; h < 2; ++h) {
                                     // (sphere-heavy scenes bin one primitive, the light: the row behind it stands for nobody -- a scalar
@@ -1874,8 +1895,13 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                                     kind[h] = MANY ? 0 : v[8 * h + 6];
                                     // (the primitive's candidate bit: 1, or 2 for the mesh scenes' group 1 -- word 5 of its row)
                                     bit[h] = WIDE ? (uint32_t)v[8 * h + 5] : 1u;
-                                    miss[h] = certainMissClamped(cg, norg, ndir, ndd, kind[h] == 2);
+                                    // (kSlabOnly: not for a cube.  Its inflated world box lies inside its inflated ball and the slab sees the
+                                    // half-line where the ball sees the line: what the ball certified beside the slab was 13 instructions per
+                                    // scatter for next to no tile -- counted, profiles/scatter_diet.txt.  A scalar branch: the kind is wave-uniform.)
+                                    if (kSlabOnly && kind[h] == 1) miss[h] = false;
+                                    else miss[h] = certainMissClamped(cg, norg, ndir, ndd, kind[h] == 2);
                                     PT_TEST_ONLY(candBall |= certainMiss(cg, norg, ndir, ndd) ? 0u : 1u;)
+                                    PT_TEST_ONLY(ballMiss[h] = certainMissClamped(cg, norg, ndir, ndd, kind[h] == 2);)
                                 }
                                 // ... the second, for a cube, the slab certificate against its inflated world box (KParams::binBox: one more scalar
                                 // load for the pair, into the registers the balls have left): a thin slab's ball is many times the slab, and the slab
@@ -1883,26 +1909,30 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                                 if (kind[0] == 1 || kind[1] == 1) {
                                     int16v bx;
                                     asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(bx) : "s"(launder(kargs)), "s"((int)(offsetof(BounceArgs, prm) + offsetof(KParams, binBox)) + sI * 32) : "memory");
-                                    // (the origin's |x| + |y| + |z| is formed here and once more for the walls below, and the slab test takes its axes one
-                                    // after the other, each with its own reciprocal -- wallCertainMissByAxis --: held across the balls, or all three
-                                    // reciprocals at once, they were the registers the general later forms did not have)
-                                    const float nl1 = (__builtin_fabsf(norg.x) + __builtin_fabsf(norg.y)) + __builtin_fabsf(norg.z);
+                                    // (without kSharedRcp the origin's |x| + |y| + |z| is formed here and once more for the walls below, and the slab test
+                                    // takes its axes one after the other, each with its own reciprocal -- wallCertainMissByAxis --: held across the
+                                    // balls, or all three reciprocals at once, they were the registers the general later forms did not have.  The
+                                    // two evaluations see the same quotients, bit for bit, and decide alike: pt_test_slab_decisions.)
+                                    const float nl1 = kSharedRcp ? sL1 : (__builtin_fabsf(norg.x) + __builtin_fabsf(norg.y)) + __builtin_fabsf(norg.z);
 #pragma unroll
                                     for (int h = 0; h < 2; ++h) {
                                         if (kind[h] != 1) continue;
                                         WallBox wb;
                                         wb.lo[0] = __int_as_float(bx[8 * h]); wb.lo[1] = __int_as_float(bx[8 * h + 1]); wb.lo[2] = __int_as_float(bx[8 * h + 2]);
                                         wb.hi[0] = __int_as_float(bx[8 * h + 3]); wb.hi[1] = __int_as_float(bx[8 * h + 4]); wb.hi[2] = __int_as_float(bx[8 * h + 5]);
-                                        const bool boxMiss = wallCertainMissByAxis(wb, norg, ndir);
+                                        const bool boxMiss = kSharedRcp ? wallCertainMiss(wb, norg, sInv) : wallCertainMissByAxis(wb, norg, ndir);
                                         miss[h] = miss[h] || (boxMiss && nl1 <= __int_as_float(bx[8 * h + 6]));      // (NaN fails)
                                     }
                                 }
                                 cand |= (miss[0] ? 0u : bit[0]) | (miss[1] ? 0u : bit[1]);
+                                // (the test library's tally: the rule that ran the ball beside every second certificate)
+                                PT_TEST_ONLY(candBoth |= ((miss[0] || ballMiss[0]) ? 0u : bit[0]) | ((miss[1] || ballMiss[1]) ? 0u : bit[1]);)
                             }
                             smallCandI = cand;
                             PT_TALLY_CANDIDATE(4, (unsigned long long)__popcll(__ballot(1)));
                             PT_TALLY_CANDIDATE(5, (unsigned long long)__popcll(__ballot(candBall != 0u)));
                             PT_TALLY_CANDIDATE(6, (unsigned long long)__popcll(__ballot(cand != 0u)));
+                            PT_TALLY_CANDIDATE(7, (unsigned long long)__popcll(__ballot(candBoth != 0u)));
                         }
                     }
                     {                                            // class bits 0-2 with walls: which of them can the new ray still hit?
@@ -1914,11 +1944,11 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         uint32_t cb = CLUSTER ? 3u : 0u;
                         if (nWalls > 0 || CLUSTER) {
                             wallSel = 6u;
-                            const float l1 = (__builtin_fabsf(norg.x) + __builtin_fabsf(norg.y)) + __builtin_fabsf(norg.z);
+                            const float l1 = kSharedRcp ? sL1 : (__builtin_fabsf(norg.x) + __builtin_fabsf(norg.y)) + __builtin_fabsf(norg.z);
                             const bool wallsOk = nWalls > 0 && l1 <= A->prm.wallOMax;          // (NaN fails)
                             const bool sphOk = CLUSTER && l1 <= A->prm.sphOMax;
                             if (wallsOk || sphOk) {
-                                const F3 inv = f3(__builtin_amdgcn_rcpf(ndir.x), __builtin_amdgcn_rcpf(ndir.y), __builtin_amdgcn_rcpf(ndir.z));
+                                const F3 inv = kSharedRcp ? sInv : f3(__builtin_amdgcn_rcpf(ndir.x), __builtin_amdgcn_rcpf(ndir.y), __builtin_amdgcn_rcpf(ndir.z));
                                 if (sphOk) {
                                     int16v v;
                                     asm volatile("s_load_dwordx16 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(launder(kargs)), "s"((int)(offsetof(BounceArgs, prm) + offsetof(KParams, sphBox))) : "memory");
