@@ -1,7 +1,11 @@
-"""Randomised scenes on the HIP path against the oracle, bit for bit: every combination the kernels branch on -- walls or no
-walls, few or many spheres (the per-lane lists), cubes small enough to be binned, meshes, nested and overlapping primitives,
-exact and arbitrary rotations, flat and tiny scales, every material kind, the extras -- drawn from seeded generators, so a
-failure names its seed."""
+"""Randomised scenes on the HIP path against the oracle, bit for bit: the combinations the GENERAL forms of the kernels branch on -- walls or
+no walls, few or many spheres (the per-lane lists), cubes small enough to be binned, meshes, nested and overlapping primitives, exact and
+arbitrary rotations, flat and tiny scales, every material kind, the extras -- drawn from seeded generators, so a failure names its seed.
+
+Which families these seeds reach (tests/test_plain_fuzz_cpu.py pins it): many, many|mesh, mesh, many|sweptCubes|mesh, the form without any
+bit, and the lens with and without them.  They reach NO history-coded PLAIN form: both generators put a glass material into every table, and
+`_random_scene` turns walls into plane walls, and either clears `plain` in the plan.  The PLAIN family -- the form the benchmark scene
+runs -- lives in tests/plain_scenes.py and tests/test_gpu_plain_fuzz.py, which shares `_schedule` with this module."""
 import os
 import types
 
@@ -150,20 +154,26 @@ def _sphere_field(gpu, oracle, seed):
     return sc, res, extras, rng
 
 
+def _schedule(rng):
+    """How a seed is rendered, drawn from its own generator: (shards, this shard, batch, iterations, batches in flight, traced ahead)"""
+    world = int(rng.choice([1, 1, 2, 3]))
+    rank = int(rng.integers(0, world))
+    batch = int(rng.choice([1, 3, 8]))
+    iters = list(range(1, 1 + int(rng.choice([2, 3, 8]))))
+    pipeline = int(rng.choice([1, 2, 3]))
+    # a third of the scenes through the reference's protocol -- one call per iteration -- served from batches traced ahead
+    ahead = bool(rng.random() < 0.33)
+    return world, rank, batch, iters, pipeline, ahead
+
+
 def _check(gpu, oracle, sc, W, H, extras, rng, seed):
     depth = sc.traceDepth
     ref = oracle.Renderer(sc.camera.view(oracle.CAMERA_DTYPE), sc.geoms.view(oracle.GEOM_DTYPE), sc.materials.view(oracle.MATERIAL_DTYPE),
                           depth, meshes=sc.meshes, mesh_normals=sc.mesh_normals, mesh_materials=sc.mesh_materials)
     ref.set_extras(**extras)
-    world = int(rng.choice([1, 1, 2, 3]))
-    rank = int(rng.integers(0, world))
-    batch = int(rng.choice([1, 3, 8]))
-    iters = list(range(1, 1 + int(rng.choice([2, 3, 8]))))
+    world, rank, batch, iters, pipeline, ahead = _schedule(rng)
     want = np.zeros(W * H * 3, np.float32)
     live = np.zeros(64, np.int64)
-    pipeline = int(rng.choice([1, 2, 3]))
-    # a third of the scenes through the reference's protocol -- one call per iteration -- served from batches traced ahead
-    ahead = bool(rng.random() < 0.33)
     gpu.pathtraceFree()
     gpu.pathtraceInit(sc, traceDepth=depth, max_batch=batch, pipeline_depth=pipeline, shard_rank=rank, shard_count=world, trace_ahead=ahead, **extras)
     it = iters[0]
