@@ -131,7 +131,9 @@ enum {
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
                                     that ray hits (traceDepth + 1 launches; traceDepth <= PT_MAX_DEPTH - 1).  A mesh is an
                                     emissive primitive when its object's material or ANY of its faces' materials emits; the
-                                    point is drawn in the object-space bounding box of ALL its vertices either way */
+                                    point is drawn in the object-space bounding box of ALL its vertices either way.  At
+                                    most 8 emissive primitives: pt_init refuses a scene with more under this flag
+                                    (PT_ERR_INVALID) rather than choose among the first eight alone */
 };
 
 typedef struct PtOptions {

@@ -56,6 +56,15 @@ int pt_test_sphere_group_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, i
  * sweep's table (cluster 0 = entries 0 .. info18[1] - 1, padded to an even count with a copy of its last sphere; then cluster 1 -- whose end pt_init
  * pads likewise), *ntable entries (<= table_cap). */
 int pt_test_sphere_clusters(const PtGeom *geoms, int ngeoms, float *info18, int32_t *table, int32_t table_cap, int32_t *ntable);
+/* ... and the whole table of the swept primitives as pt_init would build it for a SCENE (host only, no GPU needed; pt_init's arguments as
+ * pt_test_scene_plan takes them): the plan's own phases up to plan_swept, which calls build_sphere_clusters and build_sphere_groups -- so a
+ * scene that a later phase refuses (plan_lds) still shows its table.  table[e] = the primitive behind entry e, padding included;
+ * entries5[5 e ..] = entry e's {centre (3), threshold (scaled), K} as the device reads them; info6 = {entries (nSphCull), n0 (entries of
+ * cluster 0, 0: no clusters), grpN0 (its groups), nSphGroups, swept primitives (0: the scene is not sphere-heavy), grouped (0 / 1)};
+ * bounds2 = {grpOMax, sphDirScale}; balls4[4 g ..] = group g's ball as the device reads it, {centre (3), threshold}, nSphGroups of them.
+ * A scene that is not grouped has no groups: entries in file order of its clusters, nSphGroups 0. */
+int pt_test_sphere_groups(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
+                          int32_t *table, float *entries5, int32_t table_cap, float *balls4, int32_t balls_cap, int32_t info6[6], float bounds2[2]);
 /* wallCertainMiss (world-space culling of large cubes against their inflated bounding boxes, which classes the queue by
  * the wall a path can still hit) soundness: as above, for the cubes of `geoms`. */
 int pt_test_wall_box_sweep(const PtGeom *geoms, int ngeoms, uint64_t seed, int64_t rays, uint64_t *culled,
@@ -130,6 +139,12 @@ int pt_test_wall_resolve_tally(uint64_t counts[4]);
  * that rule (<= [6]: what evaluating a cube's ball as well would leave)}.  PT_AMD_NO_TIGHT_CANDIDATES=1 (read by the plan, tests only): no second
  * certificate, [7] = [6] = [5]. */
 int pt_test_candidate_tally(uint64_t counts[8]);
+/* pt_test_group_tally: the test library's tally of the GROUPED sweep of the later bounces (k_bounce<..., GROUPS>) since the last call, read
+ * and cleared.  Per wave and tile: {[0] rounds of 64 groups run; [1] waves that ran level 2 from LDS; [2] waves that ran it from global
+ * memory (more than kGroupLdsMax entries); [3] calls of passes() from inside the group loop: a lane's column of kCandPairs parked words was
+ * full}.  Per lane: {[4] group words parked; [5] the largest number of words any lane had parked at once (a maximum)}.  A renderer that is
+ * not grouped tallies nothing. */
+int pt_test_group_tally(uint64_t counts[6]);
 /* Triangle meshes.  pt_test_mesh_intersect: `n` rays against ONE mesh geom on the GPU, through the hierarchy (flat = 0) or a
  * plain list of its triangles (flat = 1: the brute-force rule); outputs keep their input values on a miss; culled[i] = 1 when
  * the bounding-ball test (certainMiss) rejected the ray -- t[i] is NaN if the full test hits nevertheless (must not happen).
@@ -297,7 +312,7 @@ typedef struct PtTestPlanSummary {
     int32_t nBinned, nWalls, nSphCull, nSphGroups, nLocalPad, firstSkipped, poolChunks;
     uint64_t ldsBytes, ldsBytesNext;
     int32_t histBits;       /* 0: the path pools carry a path's throughput (44 B); b > 0: its material history in codes of b bits (32 B: the PLAIN forms) */
-    int32_t reserved;
+    int32_t grpLds;         /* grouped scenes: 1 = the later bounces stage the table's level-2 data in LDS, 0 = they read it from global memory (else 0) */
 } PtTestPlanSummary;
 int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
                        PtTestPlanSummary *out);

@@ -94,7 +94,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_bump_normal", "pt_test_denoise", "pt_test_denoise_var", "pt_test_noise_stats", "pt_test_exp_neg_poly", "pt_test_bounce_form", "pt_test_live_device_buffers",
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
-    "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions",
+    "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions", "pt_test_sphere_groups", "pt_test_group_tally",
 ]
 
 
@@ -106,7 +106,7 @@ class PtOptions(C.Structure):
 
 class PtTestPlanSummary(C.Structure):      # include/pt_amd_test.h
     _fields_ = [("state_bits", C.c_uint32)] + [(n, C.c_int32) for n in ("nBinned", "nWalls", "nSphCull", "nSphGroups", "nLocalPad", "firstSkipped", "poolChunks")] + \
-               [("ldsBytes", C.c_uint64), ("ldsBytesNext", C.c_uint64), ("histBits", C.c_int32), ("reserved", C.c_int32)]
+               [("ldsBytes", C.c_uint64), ("ldsBytesNext", C.c_uint64), ("histBits", C.c_int32), ("grpLds", C.c_int32)]
 
 
 class PtMesh(C.Structure):
@@ -252,6 +252,9 @@ def _bind(L, with_tests):
         L.pt_test_wall_face_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p]
         L.pt_test_wall_resolve_tally.argtypes = [u64p]
         L.pt_test_candidate_tally.argtypes = [u64p]
+        L.pt_test_group_tally.argtypes = [u64p]
+        L.pt_test_sphere_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(PtOptions), C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.pt_test_slab_decisions.argtypes = [vp, vp, i32, vp, vp]
         L.pt_test_camera_cull_margin.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_double), u64p]
         L.pt_test_wall_plane_sweep.argtypes = [vp, i32, C.c_uint64, i64, C.POINTER(C.c_int32)] + [u64p] * 3
@@ -1480,6 +1483,38 @@ def candidate_tally():
     scattered paths of a binning scene, of them candidates by the balls alone, candidates by the rule in force, candidates by the balls
     beside that rule)."""
     return _u64_outs(test_lib().pt_test_candidate_tally, (8,))
+
+
+def group_tally():
+    """The test library's tally of its renderer's grouped sweep since the last call (read and cleared): (rounds of 64 groups run, waves that
+    ran level 2 from LDS, waves that ran it from global memory, calls of passes() from inside the group loop, group words parked, the
+    largest number of words a lane had parked at once)."""
+    return _u64_outs(test_lib().pt_test_group_tally, (6,))
+
+
+def sphere_groups(scene, traceDepth=None, **options):
+    """pt_test_sphere_groups: the swept primitives' table pt_init would build for the scene, on the host alone (no GPU), even where a later
+    phase of the plan refuses the scene.  options: PtOptions fields by name, as for scene_plan.  -> a namespace of table (primitive per
+    entry, padding included), centre (n, 3), threshold (n,), K (n,) per entry, n0, grpN0, nSphGroups, nswept, grouped, grpOMax, sphDirScale,
+    balls (nSphGroups, 4): {centre, threshold}."""
+    import types
+    T = test_lib()
+    set_meshes(getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None), L=T)
+    set_textures(*_scene_textures(scene), L=T)
+    set_bump_maps(*_scene_bumps(scene), L=T)
+    opt = PtOptions(shard_count=1, device=-1)
+    for name, value in options.items():
+        setattr(opt, name, value)
+    geoms, mats, cam = np.ascontiguousarray(scene.geoms), np.ascontiguousarray(scene.materials), np.ascontiguousarray(scene.camera)
+    cap = 2 * len(geoms) + 32
+    table, entries, balls = np.zeros(cap, np.int32), np.zeros((cap, 5), np.float32), np.zeros((cap, 4), np.float32)
+    info, bounds = np.zeros(6, np.int32), np.zeros(2, np.float32)
+    _check(T.pt_test_sphere_groups(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), scene.traceDepth if traceDepth is None else traceDepth,
+                                   C.byref(opt), _p(table), _p(entries), cap, _p(balls), cap, _p(info), _p(bounds)), T)
+    n, ng = int(info[0]), int(info[3])
+    return types.SimpleNamespace(table=table[:n].copy(), centre=entries[:n, :3].copy(), threshold=entries[:n, 3].copy(), K=entries[:n, 4].copy(),
+                                 n0=int(info[1]), grpN0=int(info[2]), nSphGroups=ng, nswept=int(info[4]), grouped=bool(info[5]),
+                                 grpOMax=float(bounds[0]), sphDirScale=float(bounds[1]), balls=balls[:ng].copy())
 
 
 def test_camera_cull_sweep(camera, geoms, samples=1):

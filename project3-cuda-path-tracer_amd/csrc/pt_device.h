@@ -51,13 +51,30 @@ __device__ unsigned long long g_candidates[8];
 __device__ __forceinline__ void tallyCandidate(int k, unsigned long long n) {
     if (n != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_candidates[k], n);
 }
+// ... and its tally of the GROUPED sweep (k_bounce<..., GROUPS>; read and cleared by pt_test_group_tally).  Per later-bounce wave and tile:
+// [0] rounds of 64 groups run, [1] waves that ran level 2 from LDS (KParams::grpLds), [2] waves that ran it from global memory, [3] calls of
+// passes() from inside the group loop (a lane's column of kCandPairs words was full).  Per lane: [4] group words parked, [5] the largest
+// count of parked words any lane reached (a maximum, not a sum).
+__device__ unsigned long long g_groupSweep[6];
+__device__ __forceinline__ void tallyGroup(int k, unsigned long long n) {
+    if (n != 0ull && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == (unsigned)__builtin_ctzll(__ballot(1))) atomicAdd(&g_groupSweep[k], n);
+}
+// (per lane: every lane that holds a count adds it, and raises the maximum)
+__device__ __forceinline__ void tallyGroupLane(unsigned long long parked, unsigned long long most) {
+    if (parked != 0ull) atomicAdd(&g_groupSweep[4], parked);
+    if (most != 0ull) atomicMax(&g_groupSweep[5], most);
+}
 }  // namespace ptd
 #define PT_TALLY_WALL_RESOLVE(k, n) ptd::tallyWallResolve(k, n)
 #define PT_TALLY_CANDIDATE(k, n) ptd::tallyCandidate(k, n)
+#define PT_TALLY_GROUP(k, n) ptd::tallyGroup(k, n)
+#define PT_TALLY_GROUP_LANE(parked, most) ptd::tallyGroupLane(parked, most)
 #define PT_TEST_ONLY(...) __VA_ARGS__
 #else
 #define PT_TALLY_WALL_RESOLVE(k, n)
 #define PT_TALLY_CANDIDATE(k, n)
+#define PT_TALLY_GROUP(k, n)
+#define PT_TALLY_GROUP_LANE(parked, most)
 #define PT_TEST_ONLY(...)
 #endif
 

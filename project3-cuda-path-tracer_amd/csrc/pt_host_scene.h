@@ -300,7 +300,10 @@ void build_sphere_groups(std::vector<SphereCull> &sc, int &n0, double omax, floa
     std::vector<SphereCull> c0(sc.begin(), sc.begin() + n0), c1(sc.begin() + n0, sc.end());
     if (!c0.empty()) {
         order(c0);
-        if ((c0.size() / (size_t)S) % 2) c0.insert(c0.end(), c0.end() - S, c0.end());      // an even number of groups: the last one once more
+        if ((c0.size() / (size_t)S) % 2) {      // an even number of groups: the last one once more (a copy first: insert() takes no range of its own vector)
+            const std::vector<SphereCull> last(c0.end() - S, c0.end());
+            c0.insert(c0.end(), last.begin(), last.end());
+        }
     }
     if (!c1.empty()) order(c1);
     sc = c0;

@@ -312,9 +312,18 @@ int plan_frame(const SceneIn &in, ScenePlan &p) {
 // The emitters of the direct-lighting bounce, file order: primitives with an emissive material, sampled through their unit cube -- and
 // meshes (round 5) whose own or any of whose faces' materials emits, through the object-space bounds of their vertices
 // (the CPU oracle restates this loop operation for operation: its rebuild_emitters)
-void plan_emitters(const SceneIn &in, ScenePlan &p) {
+// A scene with more emissive primitives than the table holds is refused under PT_FLAG_DIRECT_LIGHTING: choosing among the first kEmitMax alone
+// is another estimator than the one the flag names (the oracle's, which chooses among all of them) -- a darker, differently lit frame.
+int plan_emitters(const SceneIn &in, ScenePlan &p) {
     KParams &k = p.prm;
     k.nEmit = 0;
+    if (in.o.flags & PT_FLAG_DIRECT_LIGHTING) {
+        int emitting = 0;
+        for (int i = 0; i < in.ngeoms; ++i)
+            if (geom_emits(in, i) && (in.geoms[i].type != PT_MESH || (in.mesh_of(i) && in.mesh_of(i)->tris.size() >= 9))) ++emitting;
+        if (emitting > kEmitMax)
+            return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DIRECT_LIGHTING samples at most %d emissive primitives, the scene has %d", kEmitMax, emitting);
+    }
     for (int i = 0; i < in.ngeoms && k.nEmit < kEmitMax; ++i) {
         float c[3] = {0.0f, 0.0f, 0.0f}, e[3] = {1.0f, 1.0f, 1.0f};
         if (in.geoms[i].type == PT_MESH) {
@@ -335,6 +344,7 @@ void plan_emitters(const SceneIn &in, ScenePlan &p) {
         for (int a = 0; a < 3; ++a) { k.emitBox[k.nEmit][a] = c[a]; k.emitBox[k.nEmit][3 + a] = e[a]; }
         k.emitGeom[k.nEmit++] = i;
     }
+    return PT_OK;
 }
 
 // Path pools: a bounce's queue is kSeg = kCls x kSub segments, each a list of chunks handed out on demand, one ahead of
@@ -897,7 +907,7 @@ int plan_lds(const SceneIn &in, ScenePlan &p) {
 int plan_scene(const SceneIn &in, ScenePlan &p) {
     PTCHECK(check_scene(in));
     PTCHECK(plan_frame(in, p));
-    plan_emitters(in, p);
+    PTCHECK(plan_emitters(in, p));
     PTCHECK(plan_pools(in, p));
     PTCHECK(plan_geoms(in, p));
     PTCHECK(plan_camera_cull(in, p));

@@ -175,7 +175,46 @@ int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
     ScenePlan p;
     PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings}, p));
     *out = PtTestPlanSummary{plan_state_bits(p), p.prm.nBinned, p.prm.nWalls, p.prm.nSphCull, p.prm.nSphGroups, p.prm.nLocalPad, p.prm.firstSkipped, p.poolChunks,
-                             (uint64_t)p.ldsBytes, (uint64_t)p.ldsBytesNext, p.prm.histBits, 0};
+                             (uint64_t)p.ldsBytes, (uint64_t)p.ldsBytesNext, p.prm.histBits, p.prm.grpLds};
+    return PT_OK;
+}
+
+// (host only) the swept primitives' table as pt_init would build it for the scene: the plan's own phases up to plan_swept (which calls
+// build_sphere_clusters and build_sphere_groups), so a scene that plan_lds refuses afterwards still shows its table
+int pt_test_sphere_groups(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions *opts,
+                          int32_t *table, float *entries5, int32_t table_cap, float *balls4, int32_t balls_cap, int32_t info6[6], float bounds2[2]) {
+    if (!table || !entries5 || !balls4 || !info6 || !bounds2 || table_cap < 0 || balls_cap < 0) return fail(PT_ERR_INVALID, "pt_test_sphere_groups: bad argument");
+    ScenePlan p;
+    const SceneIn in{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings};
+    PTCHECK(check_scene(in));
+    PTCHECK(plan_frame(in, p));
+    PTCHECK(plan_emitters(in, p));
+    PTCHECK(plan_pools(in, p));
+    PTCHECK(plan_geoms(in, p));
+    PTCHECK(plan_camera_cull(in, p));
+    plan_bins(in, p);
+    plan_walls(in, p);
+    PTCHECK(plan_textures(in, p));
+    PTCHECK(plan_bump_maps(in, p));
+    PTCHECK(plan_swept(in, p));
+    const KParams &k = p.prm;
+    if ((int)p.sc.size() > table_cap) return fail(PT_ERR_INVALID, "pt_test_sphere_groups: table_cap too small (%d entries)", (int)p.sc.size());
+    if (k.nSphGroups > balls_cap) return fail(PT_ERR_INVALID, "pt_test_sphere_groups: balls_cap too small (%d groups)", k.nSphGroups);
+    for (size_t i = 0; i < p.sc.size(); ++i) {
+        const SphereCull &e = p.sc[i];
+        table[i] = e.geom;
+        const float v[5] = {e.centre[0], e.centre[1], e.centre[2], e.cullR2, e.cullK};
+        memcpy(entries5 + 5 * i, v, sizeof v);
+    }
+    for (int g = 0; g < k.nSphGroups; ++g) {
+        const SphereCull &e = p.groups[(size_t)g];
+        const float v[4] = {e.centre[0], e.centre[1], e.centre[2], e.cullR2};
+        memcpy(balls4 + 4 * g, v, sizeof v);
+    }
+    const int32_t info[6] = {(int32_t)p.sc.size(), k.sphN0, k.grpN0, k.nSphGroups, p.many ? p.nswept : 0, p.grouped ? 1 : 0};
+    memcpy(info6, info, sizeof info);
+    bounds2[0] = k.grpOMax;
+    bounds2[1] = k.sphDirScale;
     return PT_OK;
 }
 
@@ -1009,6 +1048,18 @@ int pt_test_candidate_tally(uint64_t counts[8]) {
     HIPCHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(ptd::g_candidates), sizeof h));
     HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(ptd::g_candidates), z, sizeof z));
     for (int q = 0; q < 8; ++q) counts[q] = h[q];
+    return PT_OK;
+}
+
+// ... and of the grouped sweep of the later bounces (ptd::g_groupSweep), read and cleared
+int pt_test_group_tally(uint64_t counts[6]) {
+    NEED_GPU();
+    if (!counts) return fail(PT_ERR_INVALID, "pt_test_group_tally: bad argument");
+    unsigned long long h[6], z[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(ptd::g_groupSweep), sizeof h));
+    HIPCHECK(hipMemcpyToSymbol(HIP_SYMBOL(ptd::g_groupSweep), z, sizeof z));
+    for (int q = 0; q < 6; ++q) counts[q] = h[q];
     return PT_OK;
 }
 

@@ -1314,8 +1314,11 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                 const F3 dhat = unitDirectionScaled(dir, dd, A->prm.sphDirScale);
                 // (an origin beyond the bound the groups' balls were built for -- none of a scattered ray's -- takes every group)
                 const bool nearO = (__builtin_fabsf(org.x) + __builtin_fabsf(org.y)) + __builtin_fabsf(org.z) <= A->prm.grpOMax;
+                PT_TEST_ONLY(unsigned long long tallyParked = 0ull; unsigned long long tallyMost = 0ull;)      // (the test library's tally: pt_test_group_tally)
                 for (int base = gG0; base < gN; base += 64) {         // (wave-uniform: rounds of 64 groups)
                     uint32_t gHi = 0u, gLo = 0u;                      // group base + j: bit 31 - j of gHi (j < 32) / of gLo
+                    PT_TALLY_GROUP(0, 1ull);
+                    PT_TALLY_GROUP(A->prm.grpLds ? 1 : 2, base == gG0 ? 1ull : 0ull);
                     if (inScene) {
                         auto sweepG = [&](int k0, uint32_t &m) {
                             const int n = min(32, gN - k0);
@@ -1368,7 +1371,10 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                             nP = 0u;
                         };
                         while (__ballot((gHi | gLo) != 0u) != 0ull) { // wave-uniform trip count: the busiest lane's candidate groups
-                            if (__ballot(nP >= (uint32_t)kCandPairs) != 0ull) passes();      // (a lane's column is full: everybody tests what is parked)
+                            if (__ballot(nP >= (uint32_t)kCandPairs) != 0ull) {              // (a lane's column is full: everybody tests what is parked)
+                                PT_TALLY_GROUP(3, 1ull);
+                                passes();
+                            }
                             if ((gHi | gLo) != 0u) {
                                 const bool hi = gHi != 0u;
                                 const uint32_t mm = hi ? gHi : gLo;
@@ -1391,7 +1397,11 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                                         m = (m << 1) | (!(c[i].w < x) ? 1u : 0u);  // candidate = !(cullR2 < x) (NaN: candidate)
                                     }
                                 }
-                                if (m != 0u) { s_cand[nP * kBlock] = ((uint32_t)grp << 8) | m; ++nP; }
+                                if (m != 0u) {
+                                    s_cand[nP * kBlock] = ((uint32_t)grp << 8) | m;
+                                    ++nP;
+                                    PT_TEST_ONLY(++tallyParked; tallyMost = tallyMost > nP ? tallyMost : (unsigned long long)nP;)
+                                }
                             }
                         }
                         passes();
@@ -1404,6 +1414,7 @@ __global__ __launch_bounds__(kBlock, (MANY && CUBES) ? (GROUPS ? 4 : PT_CUBES_WG
                         level2([&](int e) { return ent[2 * e]; }, [&](int e) { return __float_as_int(ent[2 * e + 1].y); });
                     }
                 }
+                PT_TALLY_GROUP_LANE(tallyParked, tallyMost);
             }
             if (PACKED && !GROUPS) {
                 // The sweep keeps no list: the outcome of a sphere's bounding-ball test (sphereHalfLineExcess, pt_device.h) is SHIFTED into a per-lane bit mask (compare,

@@ -5,7 +5,13 @@ arbitrary rotations, flat and tiny scales, every material kind, the extras -- dr
 Which families these seeds reach (tests/test_plain_fuzz_cpu.py pins it): many, many|mesh, mesh, many|sweptCubes|mesh, the form without any
 bit, and the lens with and without them.  They reach NO history-coded PLAIN form: both generators put a glass material into every table, and
 `_random_scene` turns walls into plane walls, and either clears `plain` in the plan.  The PLAIN family -- the form the benchmark scene
-runs -- lives in tests/plain_scenes.py and tests/test_gpu_plain_fuzz.py, which shares `_schedule` with this module."""
+runs -- lives in tests/plain_scenes.py and tests/test_gpu_plain_fuzz.py, which shares `_schedule` with this module.
+
+Nor do they reach a `grouped` form (k_bounce<..., GROUPS>: 128 swept primitives and more), many|sweptCubes without a mesh, or dof|many without a
+mesh.  The GROUPED family -- tables of 128 to 2200 swept primitives: level 2 from LDS and from global memory, three rounds of 64 groups and more,
+a full candidate column, the plan's own edges, and the flat sweeps these seeds leave out -- lives in tests/grouped_scenes.py and
+tests/test_gpu_grouped_fuzz.py, which renders every scene through `_check` and `_schedule` of this module, unchanged
+(tests/test_grouped_fuzz_cpu.py is its ledger)."""
 import os
 import types
 
