@@ -281,6 +281,27 @@ int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t bindin
 int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats,
             int traceDepth, const PtOptions *opts /* may be NULL */);
 
+/* THE CAMERA MOVE: pt_init's same-scene form.  Called as
+ *     pt_init(cam, NULL, 0, NULL, 0, PT_SAME_SCENE, NULL)
+ * -- no geoms, no materials, PT_SAME_SCENE for the depth, no options: a call that was refused before -- it moves the camera of the live
+ * renderer in place.  The observable result is that of
+ *     pt_init(cam, <the geoms, materials, traceDepth and options the live renderer was initialised with>)
+ * called over the live renderer: the library's accumulators, second moments and albedo sums are zeroed (a caller-owned accum_dev stays
+ * the caller's to zero), the counters and the committed count start again, batches traced ahead are discarded, guide buffers are
+ * invalidated, and under PT_FLAG_TEMPORAL the old view is captured into the context's history first, exactly as the full call captures it
+ * (PT_FLAG_DEMOD_HISTORY's albedo included; an old view without a committed iteration leaves the history as it was).  The meshes, textures
+ * and height maps are the ones the renderer was initialised with, not those registered since.  Everything rendered, read back, filtered or
+ * displayed afterwards is bit for bit what it would be after the full call.
+ * What it saves is the cost: the renderer keeps its copy of the scene arguments, so where the new plan needs the allocations the renderer
+ * holds -- the same kernels and sizes; no planned size depends on the camera -- every device buffer, stream, event and pinned registration
+ * is kept, the work list's per-pixel face certificates are evaluated on the device, and only the tables whose bytes differ are uploaded
+ * (textures and mesh records never).  Otherwise, and for a renderer that carries a sticky device fault, it runs the full call inside.
+ * PT_ERR_NOT_INIT without a renderer; PT_ERR_INVALID for a NULL camera, a resolution other than the live renderer's, or a camera the full
+ * call would refuse -- each before anything is touched: the renderer stays usable with its old view.  A HIP call that fails before
+ * anything has been overwritten makes it run the full call instead; one that fails later leaves the context without a renderer, as the
+ * full call's do.  Acts on the calling thread's current context.  (Additive, and no new function: the ABI version stays.) */
+#define PT_SAME_SCENE 0
+
 /* pathtrace(pbo, frame, iter): one iteration (1 spp), iter is 1-based like src/main.cpp:97-103.
  * Enqueues camera-ray generation, traceDepth fused intersect+shade+compact launches and, when
  * rgba8_dev != NULL, the sendImageToPBO conversion (src/pathtrace.cu:48-68) into that DEVICE
@@ -404,7 +425,7 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
  * pt_free and pt_denoise_var do under it.
  *   HISTORY belongs to the context: per pixel of the OLD view its mean colour, mean squared luminance and effective sample count (at most
  *   PT_TEMPORAL_MAX_HISTORY), that view's guide buffers of guide_iter 1 and its camera.  It is made at one moment only: pt_init called over a
- *   live renderer (the "calling it twice re-initialises" path) when the old and the new renderer both carry the flag and have the same
+ *   live renderer (the "calling it twice re-initialises" path), or its same-scene form (PT_SAME_SCENE), which is that call with the renderer's own scene, when the old and the new renderer both carry the flag and have the same
  *   resolution, the new scene has been accepted, and the old renderer has committed at least one iteration (its sample count is the number of
  *   iterations it committed since its pt_init -- pt_counters_reset, which leaves the accumulators alone, leaves that count alone too).  The capture is recursive: what is kept is the old view's own blend of ITS history with ITS samples, so a camera
  *   dragged through many views of a few samples each keeps accumulating up to the cap.  An old renderer without a committed iteration leaves

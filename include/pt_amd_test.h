@@ -109,6 +109,13 @@ int pt_test_camera_list(const PtCamera *cam, const PtGeom *geoms, int ngeoms, in
  * (host only).  sizes4 = {lanes (-1: not built), entries of sig_idx, pixels listed, pixels in resolved waves}; face takes sizes4[0] / 64. */
 int pt_test_camera_resolved(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
                             int32_t *sig_idx, int32_t *face, int64_t *sizes4);
+/* The same list with the certificates evaluated on the DEVICE between the list's two passes, as the camera move (pt_init with PT_SAME_SCENE) evaluates them
+ * (csrc/pt_camera_faces.h: k_camera_faces): every array must equal pt_test_camera_resolved's.  kernel_ms (or NULL): the launches' time. */
+int pt_test_camera_resolved_device(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
+                                   int32_t *sig_idx, int32_t *face, int64_t *sizes4, float *kernel_ms);
+/* Which way the calling thread's last camera move (pt_init with PT_SAME_SCENE) went: *fast = 1 (every buffer kept), 0 (pt_init inside), -1 before the first move and
+ * after a refusal; the tables the fast path uploaded, and their bytes. */
+int pt_test_last_camera_move(int *fast, int *tables_uploaded, int *bytes_uploaded);
 /* Device sweep: for every resolved pixel of the unsharded list, `samples` seeded jitters and the four corners of the certificate's
  * footprint -- the resolved wave's box test (pt_device.h: boxFaceHit) against boxIntersectionTest.  counts = {rays, rays on which
  * (t > 0, outside, face, P bit for bit) differ -- must be 0 --, resolved pixels}. */

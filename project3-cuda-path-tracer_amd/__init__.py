@@ -81,6 +81,7 @@ ABI_SYMBOLS = [
     "pt_noise_stats", "pt_iterate_until",
 ]
 PT_AMD_ABI_VERSION = 7
+PT_SAME_SCENE = 0           # pt_init(cam, NULL, 0, NULL, 0, PT_SAME_SCENE, NULL): the camera move (pathtraceSetCamera)
 # every symbol include/pt_amd_test.h declares: libpt_amd_test.so only -- the product library must NOT export them
 TEST_ABI_SYMBOLS = [
     "pt_debug_trace_paths",
@@ -95,6 +96,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions", "pt_test_sphere_groups", "pt_test_group_tally",
+    "pt_test_camera_resolved_device", "pt_test_last_camera_move",
 ]
 
 
@@ -247,6 +249,8 @@ def _bind(L, with_tests):
         L.pt_test_camera_cull_tables.argtypes = [vp, vp, i32, vp, vp, vp]
         L.pt_test_camera_list.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
         L.pt_test_camera_resolved.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.pt_test_camera_resolved_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        L.pt_test_last_camera_move.argtypes = [vp, vp, vp]
         L.pt_test_face_hit_sweep.argtypes = [vp, vp, i32, i32, C.c_uint64, u64p]
         L.pt_test_wall_faces.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(PtOptions), vp, vp]
         L.pt_test_wall_face_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p]
@@ -530,6 +534,27 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
     _last_init = (cam, geoms, mats, depth, (shard_rank, shard_count, device, flags, lens_radius, focal_distance),
                   (getattr(scene, "meshes", None) or {}, getattr(scene, "mesh_normals", None), getattr(scene, "mesh_materials", None)),
                   _scene_textures(scene), _scene_bumps(scene))
+
+
+def pathtraceSetCamera(camera_or_scene):
+    """pt_init's same-scene form (include/pt_amd.h: PT_SAME_SCENE): move the camera of the live renderer in place -- what pathtraceInit called again with the same scene, arguments and
+    the new camera would leave behind, bit for bit (under temporal=True the old view becomes the history), without giving up the renderer's
+    buffers.  Takes a camera record (scene.camera, or a copy with another pose) or a Scene, whose camera it reads; the resolution must be
+    the live renderer's."""
+    global _last_init
+    cam = np.ascontiguousarray(getattr(camera_or_scene, "camera", camera_or_scene)).copy()
+    _check(lib().pt_init(_p(cam), None, 0, None, 0, PT_SAME_SCENE, None))
+    if _last_init is not None:
+        _last_init = (cam,) + tuple(_last_init[1:])
+
+
+def camera_move_info():
+    """pt_test_last_camera_move (test library; see renderer_from_test_library): which way this thread's last pathtraceSetCamera went --
+    {"fast": True / False / None (no move yet, or the last one was refused), "tables_uploaded": n, "bytes_uploaded": n}."""
+    out = [C.c_int(0) for _ in range(3)]
+    _tcheck(test_lib().pt_test_last_camera_move(*[C.byref(o) for o in out]))
+    fast = out[0].value
+    return {"fast": None if fast < 0 else bool(fast), "tables_uploaded": out[1].value, "bytes_uploaded": out[2].value}
 
 
 def scene_plan(scene, traceDepth=None, **options):
@@ -1441,6 +1466,16 @@ def camera_resolved(camera, geoms, shard_rank=0, shard_count=1):
     entries, per wave its face 2 axis + (side > 0) or -1)."""
     r = _sized_camera_list(test_lib().pt_test_camera_resolved, camera, geoms, shard_rank, shard_count, True)
     return r and tuple(r[0])
+
+
+def camera_resolved_device(camera, geoms, shard_rank=0, shard_count=1, with_ms=False):
+    """camera_resolved with the face certificates evaluated on the device (k_camera_faces), as the camera move (pathtraceSetCamera) evaluates them: the same four
+    arrays, or None.  with_ms: -> (arrays or None, the launches' time in ms by HIP events)."""
+    ms = C.c_float(0.0)
+    fn = test_lib().pt_test_camera_resolved_device
+    r = _sized_camera_list(lambda *a: fn(*a, C.byref(ms)), camera, geoms, shard_rank, shard_count, True)
+    res = r and tuple(r[0])
+    return (res, ms.value) if with_ms else res
 
 
 def test_face_hit_sweep(camera, geoms, samples=64, seed=1):

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <thread>
@@ -46,6 +47,7 @@
 #include "pt_temporal.h"
 #include "pt_spatial_var.h"
 #include "pt_albedo.h"
+#include "pt_camera_faces.h"
 // The entry points of include/pt_amd_test.h (device primitives one by one, soundness sweeps, the fault-word hook) exist only in
 // the second link target of this source, libpt_amd_test.so (-DPT_TEST_API): the product library exports none of them.
 #ifdef PT_TEST_API
@@ -113,12 +115,13 @@ inline void count_devbuf(int) {}
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
+    size_t cap = 0;                 // elements allocated (the camera move refreshes a table in place where it fits)
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
     DevBuf &operator=(DevBuf &&o) noexcept {
-        if (this != &o) { release(); p = o.p; o.p = nullptr; }
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
         return *this;
     }
     ~DevBuf() { release(); }
@@ -126,6 +129,7 @@ struct DevBuf {
         if (!p) return;
         (void)hipFree(p);
         p = nullptr;
+        cap = 0;
         count_devbuf(-1);
     }
     // n elements (at least one: a kernel may be handed the pointer of an empty table), uninitialised / zeroed / copied from the host
@@ -133,6 +137,7 @@ struct DevBuf {
     int alloc(size_t n) {
         release();
         HIPCHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
+        cap = std::max<size_t>(n, 1);
         count_devbuf(1);
         return PT_OK;
     }
@@ -271,6 +276,26 @@ struct State : PlanScalars {
     std::vector<HostBumpBinding> bumpBindings;
     // ... and, across a pt_init over the live renderer only, the last view's samples (PT_FLAG_TEMPORAL)
     History hist;
+    // the camera move: what the renderer was initialised with -- pt_init's scene arguments and effective options (a few hundred bytes per
+    // primitive) -- and the plan it holds: the tables as the device has them (texels and mesh records, which no camera changes, by their
+    // sizes alone), so that a move uploads only the tables whose bytes differ
+    std::vector<PtGeom> inGeoms;
+    std::vector<PtMaterial> inMats;
+    int inDepth = 0;
+    PtOptions inOpts = {};
+    std::unique_ptr<ScenePlan> held;
+    // ... and what its certificates on the device need (k_camera_faces), made by the first move: a stream of their own -- the renderer's may
+    // hold a frame's work -- and the pixel words and face bytes of one move
+    hipStream_t camStream = nullptr;
+    DevBuf<uint32_t> camPixScratch;
+    DevBuf<signed char> camFaceScratch;
+    size_t heldTexels = 0, heldMeshRecs = 0;
+    // ... and what was registered when it was initialised, where a pt_set_* call has registered something else since (moved here by that
+    // call; null: the registered ones above are still the renderer's)
+    std::unique_ptr<std::vector<ptm::HostMesh>> initMeshes;
+    std::unique_ptr<std::vector<HostTexture>> initTextures;
+    std::unique_ptr<std::vector<HostTexBinding>> initTexBindings;
+    std::unique_ptr<std::vector<HostBumpBinding>> initBumpBindings;
 };
 
 // Renderer instances.  The reference keeps its renderer in file-static globals (src/pathtrace.cu:70-71: one per process, not
@@ -925,8 +950,10 @@ int capture_history() {
     if (withAlbedo) PTCHECK((temporal_blend<kTemporalCapture, true>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p, true, hs.ha[nxt].p)));
     else PTCHECK(temporal_blend<kTemporalCapture>((float)S.committed, hs.hc[nxt].p, hs.hn[nxt].p));
     HIPCHECK(hipStreamSynchronize(S.stream));      // (the guides it read are released next)
-    hs.hpos = std::move(S.dnPosT);
-    hs.hnrm = std::move(S.dnNrmId);
+    // (an exchange: the guides the history held until now -- the blend above has just read them -- are left to the renderer as buffers without
+    // a content; pt_init frees them with it, the camera move renders the next view's guides into them)
+    std::swap(hs.hpos, S.dnPosT);
+    std::swap(hs.hnrm, S.dnNrmId);
     S.dnGuideIter = 0;
     hs.cam = temporal_camera(S.prm);
     hs.cur = nxt; hs.W = S.prm.W; hs.H = S.prm.H;
@@ -1202,6 +1229,7 @@ void free_renderer(bool keepHistory) {
     if (R().pinnedHost) (void)hipHostUnregister(R().pinnedHost);
     if (R().hostFault) (void)hipHostFree(R().hostFault);
     if (R().noiseHost) (void)hipHostFree(R().noiseHost);
+    if (R().camStream) (void)hipStreamDestroy(R().camStream);
     for (hipEvent_t e : R().noiseEv)
         if (e) (void)hipEventDestroy(e);
     // ... and every device table: the move-assignment below releases what the DevBufs of State and its Slots hold
@@ -1219,6 +1247,298 @@ void free_renderer(bool keepHistory) {
         R().bumpBindings = std::move(keepBump);
     }
 }
+
+// The end of pt_init, and of the camera move: what depends on the plan's scalars and on which camera tables the device holds -- the kernels'
+// LDS attributes, the persistent grids, and the camera-ray launch's column rotation (KParams::tilesPerRow).
+int size_launches(State &S) {
+    if (S.ldsBytes > 64 * 1024) {
+        HIPCHECK(hipFuncSetAttribute(S.kernFirst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsBytes));
+        HIPCHECK(hipFuncSetAttribute(S.kernNext, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsBytes));
+    }
+    if (S.mesh)
+        for (int first = 0; first < 2; ++first) {
+            const void *kw = walk_kernel(first != 0, first && S.dof);
+            if (S.ldsWalk > 64 * 1024) HIPCHECK(hipFuncSetAttribute(kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsWalk));
+            PTCHECK(persistent_grid(kw, S.ldsWalk, true, first ? &S.gridWalkFirst : &S.gridWalk));
+        }
+    for (int first = 0; first < 2; ++first) {
+        int &grid = first ? S.gridFirst : S.grid;
+        PTCHECK(persistent_grid(first ? S.kernFirst : S.kernNext, first ? S.ldsBytes : S.ldsBytesNext, false, &grid));
+        if (grid > S.numTilesMax) grid = S.numTilesMax;
+        grid = (grid / kSub) * kSub;      // T % kSub == blockIdx % kSub for every tile T of a workgroup (kSub: a multiple of the mesh scenes' 4 too)
+        if (grid < kSub) grid = kSub;
+    }
+    // Camera-ray bounce: tile T covers pixels 256 T ... of the row-major frame and a workgroup owns the tiles b, b + grid,
+    // ...  When the grid shares a factor with the tiles per row (1280 workgroups, 5 tiles per 1280-pixel row) a workgroup
+    // stays in few column bands of the frame, and the bands outside the scene rectangle finish 15x earlier than the
+    // others.  Either the grid can be made coprime to the tiles per row (both must stay multiples of kSub, so only for an
+    // odd tile count per row), or the kernel rotates the k-th tile of a workgroup k bands to the right inside its row,
+    // which needs a grid that is a multiple of the tiles per row (k_bounce<true, .>).
+    // (the packed work list of camera rays has no column bands: nothing to rotate)
+    const KParams &k = S.prm;
+    S.prm.tilesPerRow = 0;
+    if (k.Wp / kBlock > 1 && S.dCamPix.p == nullptr) {
+        const int perRow = k.Wp / kBlock;
+        auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
+        if (gcd(perRow, kSub) == 1) {
+            for (int tries = 0; tries < 64 && S.gridFirst > kSub && gcd(S.gridFirst, perRow) != 1; ++tries) S.gridFirst -= kSub;
+        } else {
+            const int unit = perRow / gcd(perRow, kSub) * kSub;        // lcm(perRow, kSub)
+            if (S.gridFirst >= 4 * unit) {
+                S.gridFirst = S.gridFirst / unit * unit;
+                S.prm.tilesPerRow = perRow;
+            }
+        }
+    }
+    return PT_OK;
+}
+
+// ---- the camera move ------------------------------------------------------------------------------------------------------------------------
+// which way the calling thread's last camera move went (pt_test_last_camera_move): fast 1 / 0, -1 before the first move or after a
+// refusal; the tables and bytes the fast path uploaded
+struct CameraMove { int fast = -1, tables = 0; long long bytes = 0; };
+thread_local CameraMove t_lastMove;
+
+// The work list's face certificates on the device, between build_camera_list's two passes: the pixel words of the one-cube groups whose
+// cube is CubeCert::ok go up as one array, k_camera_faces runs once per group -- the cube is uniform per group: a kernel argument -- and
+// the bytes come back as CameraGroups::faces.  pix / face: scratch buffers of the caller's, grown where needed; ms (or NULL): the kernels'
+// time by HIP events.
+int camera_faces_device(CameraGroups &G, const CameraResolve &cr, hipStream_t st, DevBuf<uint32_t> &pix, DevBuf<signed char> &face, float *ms) {
+    if (ms) *ms = 0.0f;
+    struct Run { size_t group, off, n; int cube; };
+    std::vector<Run> runs;
+    size_t total = 0;
+    for (size_t s = 0; s < G.groups.size(); ++s) {
+        const int cube = camera_group_cube(G, s, cr);
+        if (cube < 0 || G.groups[s].empty()) continue;
+        runs.push_back({s, total, G.groups[s].size(), cube});
+        total += G.groups[s].size();
+    }
+    if (!total) return PT_OK;
+    std::vector<uint32_t> words(total);
+    for (const Run &r : runs) memcpy(words.data() + r.off, G.groups[r.group].data(), r.n * sizeof(uint32_t));
+    if (pix.cap < total) PTCHECK(pix.alloc(total + total / 4));
+    if (face.cap < total) PTCHECK(face.alloc(total + total / 4));
+    EventSet es;
+    HIPCHECK(hipMemcpyAsync(pix.p, words.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (ms) {
+        HIPCHECK(hipEventCreate(&es.ev[0]));
+        HIPCHECK(hipEventCreate(&es.ev[1]));
+        HIPCHECK(hipEventRecord(es.ev[0], st));
+    }
+    for (const Run &r : runs) {
+        CameraFacesArgs A;
+        A.cube = cr.cube[(size_t)r.cube];
+        A.basis = cr;
+        A.pix = pix.p + r.off;
+        A.face = face.p + r.off;
+        A.n = (int)r.n;
+        hipLaunchKernelGGL(k_camera_faces, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, st, A);
+    }
+    HIPCHECK(hipGetLastError());
+    if (ms) HIPCHECK(hipEventRecord(es.ev[1], st));
+    std::vector<signed char> bytes(total);
+    HIPCHECK(hipMemcpyAsync(bytes.data(), face.p, total, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (ms) HIPCHECK(hipEventElapsedTime(ms, es.ev[0], es.ev[1]));
+    for (const Run &r : runs) {
+        std::vector<int> &f = G.faces[r.group];
+        f.resize(r.n);
+        for (size_t i = 0; i < r.n; ++i) {
+            const int v = bytes[r.off + i];
+            if (v < -1 || v > 5) return fail(PT_ERR_DEVICE, "pt_init (camera move): k_camera_faces answered %d", v);
+            f[i] = v;
+        }
+    }
+    return PT_OK;
+}
+
+// A table of the renderer against the new plan's: left alone where the device holds these very bytes, released where the plan has none
+// (pt_init leaves such a table without a buffer, and the kernels ask), written in place where it fits, reallocated where it grew.  The
+// copy is enqueued on `st` from `now`, which the caller keeps until the stream has been waited for.
+template <typename T>
+int refresh_table(DevBuf<T> &buf, const std::vector<T> &heldT, const std::vector<T> &now, bool keepEmpty, hipStream_t st, CameraMove &mv) {
+    if (now.empty() && !keepEmpty) { buf.release(); return PT_OK; }
+    const bool same = buf.p && heldT.size() == now.size() && (now.empty() || !memcmp(heldT.data(), now.data(), now.size() * sizeof(T)));
+    if (same) return PT_OK;
+    if (!buf.p || buf.cap < now.size()) PTCHECK(buf.alloc(now.size() + now.size() / 4));
+    if (!now.empty()) HIPCHECK(hipMemcpyAsync(buf.p, now.data(), now.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    mv.tables += 1;
+    mv.bytes += (long long)(now.size() * sizeof(T));
+    return PT_OK;
+}
+
+// pt_init over the live renderer with the scene it was initialised with: the camera move's slow path.  What was registered at that pt_init
+// is put back for the call where something else has been registered since, and what has been registered since stays registered behind it.
+int reinit_with_camera(const PtCamera &cam) {
+    State &S = R();
+    const std::vector<PtGeom> geoms = S.inGeoms;
+    const std::vector<PtMaterial> mats = S.inMats;
+    const int depth = S.inDepth;
+    const PtOptions o = S.inOpts;
+    auto initMeshes = std::move(S.initMeshes);
+    auto initTextures = std::move(S.initTextures);
+    auto initTexBindings = std::move(S.initTexBindings);
+    auto initBumpBindings = std::move(S.initBumpBindings);
+    if (initMeshes) std::swap(*initMeshes, S.meshes);
+    if (initTextures) std::swap(*initTextures, S.textures);
+    if (initTexBindings) std::swap(*initTexBindings, S.texBindings);
+    if (initBumpBindings) std::swap(*initBumpBindings, S.bumpBindings);
+    const int rc = pt_init(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), depth, &o);
+    const std::string err = g_err;
+    State &N = R();
+    if (initMeshes) std::swap(*initMeshes, N.meshes);
+    if (initTextures) std::swap(*initTextures, N.textures);
+    if (initTexBindings) std::swap(*initTexBindings, N.texBindings);
+    if (initBumpBindings) std::swap(*initBumpBindings, N.bumpBindings);
+    if (N.init) {
+        N.initMeshes = std::move(initMeshes);
+        N.initTextures = std::move(initTextures);
+        N.initTexBindings = std::move(initTexBindings);
+        N.initBumpBindings = std::move(initBumpBindings);
+    }
+    g_err = err;
+    return rc;
+}
+
+int set_camera(const PtCamera *cam) {
+    t_lastMove = CameraMove();
+    if (!cam) return fail(PT_ERR_INVALID, "pt_init (camera move): null camera");
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_init (camera move) before pt_init: there is no renderer whose scene it could name");
+    State &S = R();
+    if (cam->resolution[0] != S.prm.W || cam->resolution[1] != S.prm.H)
+        return fail(PT_ERR_INVALID, "pt_init (camera move): the camera's resolution %d x %d is not the renderer's %d x %d (pt_init makes a renderer of another size)",
+                    cam->resolution[0], cam->resolution[1], S.prm.W, S.prm.H);
+    const PtCamera camNew = *cam;        // (the caller may hand in the camera of a scene this call outlives)
+    if (S.device >= 0) HIPCHECK(hipSetDevice(S.device));
+    // 1. the plan for the new camera, the certificates of its work list on the device; a scene that is refused has touched nothing
+    if (!S.camStream) HIPCHECK(hipStreamCreateWithFlags(&S.camStream, hipStreamNonBlocking));
+    std::unique_ptr<ScenePlan> planPtr(new ScenePlan);
+    ScenePlan &plan = *planPtr;
+    {
+        SceneIn in{&camNew, S.inGeoms.data(), (int)S.inGeoms.size(), S.inMats.data(), (int)S.inMats.size(), S.inDepth, S.inOpts,
+                   S.initMeshes ? *S.initMeshes : S.meshes, S.initTextures ? *S.initTextures : S.textures,
+                   S.initTexBindings ? *S.initTexBindings : S.texBindings, S.initBumpBindings ? *S.initBumpBindings : S.bumpBindings};
+        in.faces = [&S](CameraGroups &G, const CameraResolve &cr) { return camera_faces_device(G, cr, S.camStream, S.camPixScratch, S.camFaceScratch, nullptr); };
+        PTCHECK(plan_scene(in, plan));
+    }
+    const void *kernFirst = nullptr, *kernNext = nullptr;
+    PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
+    PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
+    // 2. drain the renderer's streams, as free_renderer does
+    for (int i = 0; i < S.nslots; ++i) (void)hipStreamSynchronize(S.slot[i].stream);
+    (void)hipStreamSynchronize(S.stream);
+    // 3. does the plan need the allocations the renderer holds?  (It does unless planning changes: none of these sizes depends on the
+    // camera.)  A renderer that carries a sticky device fault is rebuilt like any other: pt_init.
+    const bool faulted = S.hostFault && *(volatile uint32_t *)S.hostFault != 0u;
+    const bool sameAllocations =
+        S.held && kernFirst == S.kernFirst && kernNext == S.kernNext && plan.mesh == S.mesh && plan.dof == S.dof && plan.walkMeshLds == S.walkMeshLds &&
+        plan.flags == S.flags && plan.nslots == S.nslots && plan.maxBatch == S.maxBatch && plan.poolCap == S.poolCap && plan.poolChunks == S.poolChunks &&
+        plan.prm.chunkShift == S.prm.chunkShift && plan.prm.poolChunks == S.prm.poolChunks && plan.prm.histBits == S.prm.histBits &&
+        plan.meshHitWords == S.meshHitWords && plan.prm.contribLocal == S.prm.contribLocal && plan.nLocal == S.nLocal && plan.P == S.P &&
+        plan.texels.size() == S.heldTexels && plan.meshRecs.size() == S.heldMeshRecs;
+    if (faulted || !sameAllocations) {
+        t_lastMove.fast = 0;
+        return reinit_with_camera(camNew);
+    }
+    // batches traced ahead are discarded: consumed without being added, which leaves the slots' iteration masks zeroed
+    // (A HIP call that fails up to the capture has overwritten nothing the full call needs: the full call is made instead.)
+    const auto slow = [&]() { t_lastMove.fast = 0; return reinit_with_camera(camNew); };
+    if (!S.ahead.empty() && (discard_ahead() != PT_OK || hipStreamSynchronize(S.stream) != hipSuccess)) return slow();
+    // 5. the old view becomes the context's history exactly as pt_init captures it -- or the history ends as it ends there
+    {
+        bool keepHistory = (S.flags & PT_FLAG_TEMPORAL) != 0;
+        if (keepHistory && S.committed >= 1 && guide_stack_bytes() > 64 * 1024) keepHistory = false;
+        if (keepHistory && S.committed >= 1) {
+            // (PT_FLAG_DISPLAY_FILTER, whose pt_iterate allocates nothing: the capture exchanges the renderer's guide buffers with the
+            // history's, so a history that has none yet is given a pair first)
+            if ((S.flags & PT_FLAG_DISPLAY_FILTER) && !S.hist.hpos.p && !S.hist.live &&
+                (S.hist.hpos.alloc((size_t)S.P) != PT_OK || S.hist.hnrm.alloc((size_t)S.P) != PT_OK)) {
+                S.hist.hpos.release(); S.hist.hnrm.release();
+                return slow();
+            }
+            const int rc = capture_history();
+            if (rc) {
+                free_renderer();
+                return rc == PT_ERR_INVALID ? fail(PT_ERR_HIP, "pt_init (camera move): the capture of the old view failed: %s", std::string(g_err).c_str()) : rc;
+            }
+        }
+        if (!keepHistory) S.hist = History();
+    }
+    // From here on the renderer is overwritten: a HIP call that fails leaves the context without a renderer, as pt_init's do.
+    const auto body = [&]() -> int {
+        // 6. the library's accumulators, on the renderer's stream (a caller-owned accum_dev stays the caller's to zero)
+        if (S.imageOwn.p) HIPCHECK(hipMemsetAsync(S.imageOwn.p, 0, S.imageOwn.cap * sizeof(float), S.stream));
+        if (S.moments.p) HIPCHECK(hipMemsetAsync(S.moments.p, 0, (size_t)S.P * sizeof(float), S.stream));
+        if (S.albedo.p) HIPCHECK(hipMemsetAsync(S.albedo.p, 0, (size_t)S.P * sizeof(float4), S.stream));
+        // 7. the slots' counters (the chunk lists' generations go on: an entry of the old view never carries a serial number to come), and the
+        // host's sequence, trace-ahead, guide and timing state
+        for (int i = 0; i < S.nslots; ++i) {
+            HIPCHECK(hipMemsetAsync(S.slot[i].ctrl.p, 0, sizeof(Ctrl), S.stream));
+            S.slot[i].parity = 0;
+        }
+        for (auto &pr : S.evBounce) { S.evFree.push_back(pr.first); S.evFree.push_back(pr.second); }
+        S.evBounce.clear();
+        S.msBounce = 0; S.nBounce = 0;
+        S.iterations = 0; S.committed = 0; S.seq = 0;
+        S.ahead.clear();
+        S.dnGuideIter = 0;
+        S.snapTarget = nullptr; S.snapWait = nullptr;
+        // 8. the new plan's scalars
+        static_cast<PlanScalars &>(S) = plan;
+        S.kernFirst = kernFirst;
+        S.kernNext = kernNext;
+        // 9. the tables whose bytes differ (textures and mesh records: never -- no camera changes them, and the plan is the same scene's)
+        const ScenePlan &h = *S.held;
+        CameraMove &mv = t_lastMove;
+        PTCHECK(refresh_table(S.dgeoms, h.hg, plan.hg, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dmats, h.hm, plan.hm, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dGeomHit, h.geomHit, plan.geomHit, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dRows, h.rowsGlobal, plan.rowsGlobal, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dwalls, h.hw, plan.hw, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dTexGeom, h.texGeom, plan.texGeom, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dTexDesc, h.texDesc, plan.texDesc, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dTexUV, h.texUV, plan.texUV, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dBumpGeom, h.bumpGeom, plan.bumpGeom, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dBumpUV, h.bumpUV, plan.bumpUV, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dBumpTan, h.bumpTan, plan.bumpTan, false, S.stream, mv));
+        if (S.mesh) {
+            PTCHECK(refresh_table(S.dWalkIdx, h.walkIdx, plan.walkIdx, true, S.stream, mv));
+            PTCHECK(refresh_table(S.dWalkMeshRows, h.walkMeshRows, plan.walkMeshRows, true, S.stream, mv));
+        }
+        PTCHECK(refresh_table(S.dSphCull, h.sc, plan.sc, false, S.stream, mv));
+        if (S.grouped) PTCHECK(refresh_table(S.dSphGroups, h.groups, plan.groups, true, S.stream, mv));
+        PTCHECK(refresh_table(S.dRowOff, h.cc.rowOff, plan.cc.rowOff, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dRowIdx, h.cc.rowIdx, plan.cc.rowIdx, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dCamPix, h.cl.pix, plan.cl.pix, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dCamWave, h.cl.wave, plan.cl.wave, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dCamSigIdx, h.cl.sigIdx, plan.cl.sigIdx, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dCamFace, h.cl.face, plan.cl.face, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dWalkRowOff, h.walkRowOff, plan.walkRowOff, false, S.stream, mv));
+        PTCHECK(refresh_table(S.dClassIdx, h.classIdx, plan.classIdx, false, S.stream, mv));
+        // 10. what depends on the tables: the LDS attributes, the grids, the packed list or the row bands
+        PTCHECK(size_launches(S));
+        // the copies read the plan's vectors and the slots' streams do not wait for the renderer's: everything above has landed before
+        // the next launch is enqueued
+        HIPCHECK(hipStreamSynchronize(S.stream));
+        return PT_OK;
+    };
+    const int rc = body();
+    if (rc) {
+        const std::string err = g_err;
+        free_renderer();
+        g_err = err;
+        t_lastMove = CameraMove();
+        return rc;
+    }
+    std::vector<float4>().swap(plan.texels);
+    std::vector<ptd::MeshUnit>().swap(plan.meshRecs);
+    S.held = std::move(planPtr);
+    t_lastMove.fast = 1;
+    g_err.clear();
+    return PT_OK;
+}
+
 }  // namespace
 #pragma GCC visibility push(default)
 extern "C" {
@@ -1242,6 +1562,7 @@ int pt_set_meshes(const PtMesh *meshes, int nmeshes) {
             for (size_t q = 0; q < 9 * (size_t)meshes[i].ntris; ++q)
                 if (!std::isfinite(meshes[i].normals[q])) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d holds a non-finite normal", i);
     }
+    if (R().init && !R().initMeshes) R().initMeshes.reset(new std::vector<ptm::HostMesh>(std::move(R().meshes)));     // (for the camera move)
     R().meshes.clear();
     for (int i = 0; i < nmeshes; ++i) {
         ptm::HostMesh m;
@@ -1262,6 +1583,7 @@ int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t bindin
     for (int i = 0; i < nbindings; ++i)
         if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: binding %d: bad UVs", i);
     // (indices, counts and the scale are checked by pt_init, against the scene)
+    if (R().init && !R().initBumpBindings) R().initBumpBindings.reset(new std::vector<HostBumpBinding>(std::move(R().bumpBindings)));
     R().bumpBindings.clear();
     for (int i = 0; i < nbindings; ++i) {
         HostBumpBinding b;
@@ -1284,6 +1606,10 @@ int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_str
             return fail(PT_ERR_INVALID, "pt_set_textures: texture %d has no texels", i);
     for (int i = 0; i < nbindings; ++i)
         if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_textures: binding %d: bad UVs", i);
+    if (R().init && !R().initTextures) {
+        R().initTextures.reset(new std::vector<HostTexture>(std::move(R().textures)));
+        R().initTexBindings.reset(new std::vector<HostTexBinding>(std::move(R().texBindings)));
+    }
     R().textures.clear();
     R().texBindings.clear();
     long long texels = 0;
@@ -1310,7 +1636,21 @@ int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_str
 // old renderer gave back) leaves the context without a renderer.
 int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
             const PtOptions *opts) {
+    // the camera move: no scene at all and PT_SAME_SCENE for the depth name the scene the live renderer was initialised with
+    if (!geoms && !mats && ngeoms == 0 && nmats == 0 && traceDepth == PT_SAME_SCENE && !opts) return set_camera(cam);
     const PtOptions o = effective_options(opts);
+    // PT_AMD_INIT_PHASES (measurements only: profiles/set_camera_cost.py): the host's clock around the call's phases, each ended by a
+    // device synchronise of its own, printed to stderr
+    const bool phases = env_flag("PT_AMD_INIT_PHASES");
+    double phaseMs[5] = {0, 0, 0, 0, 0};
+    auto phaseT0 = std::chrono::steady_clock::now();
+    const auto phase_end = [&](int i) {
+        if (!phases) return;
+        if (i > 0) (void)hipDeviceSynchronize();
+        const auto t = std::chrono::steady_clock::now();
+        phaseMs[i] = std::chrono::duration<double, std::milli>(t - phaseT0).count();
+        phaseT0 = t;
+    };
     ScenePlan plan;
     PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, o, R().meshes, R().textures, R().texBindings, R().bumpBindings}, plan));
     const void *kernFirst = nullptr, *kernNext = nullptr;
@@ -1321,6 +1661,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         return fail(PT_ERR_INVALID, "pt_init: internal error: history bits %d and the later bounces' form disagree", plan.prm.histBits);
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
     register_exit_handler();
+    phase_end(0);      // host planning
     // PT_FLAG_TEMPORAL on the renderer that goes and on the one that comes, the same frame size and device: the context's history lives on,
     // and the old view -- if it committed anything -- is blended into it first, on the old renderer's stream (free_renderer waits for it)
     // (PT_FLAG_DEMOD_HISTORY: only between two renderers that agree on it -- a history with albedo and one without are different things)
@@ -1338,6 +1679,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         }
     }
     free_renderer(keepHistory);
+    phase_end(1);      // the capture of history, the drain and the free
 
     State &S = R();
     static_cast<PlanScalars &>(S) = plan;
@@ -1407,6 +1749,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
 
     // the plan's tables, each once; a table the scene does not have is empty and stays without a buffer (the walks' tables of a scene with
     // meshes and the groups of a grouped one get theirs even when empty: a kernel may be handed the pointer of an empty table)
+    phase_end(2);      // streams, events and every allocation with its zeroing
     const auto up = [](auto &buf, const auto &table) { return table.empty() ? (int)PT_OK : buf.upload(table); };
     PTCHECK(up(S.dgeoms, plan.hg));
     PTCHECK(up(S.dmats, plan.hm));
@@ -1436,50 +1779,27 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     PTCHECK(up(S.dWalkRowOff, plan.walkRowOff));
     PTCHECK(up(S.dClassIdx, plan.classIdx));
 
-    if (S.ldsBytes > 64 * 1024) {
-        HIPCHECK(hipFuncSetAttribute(S.kernFirst, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsBytes));
-        HIPCHECK(hipFuncSetAttribute(S.kernNext, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsBytes));
-    }
-    if (S.mesh)
-        for (int first = 0; first < 2; ++first) {
-            const void *kw = walk_kernel(first != 0, first && S.dof);
-            if (S.ldsWalk > 64 * 1024) HIPCHECK(hipFuncSetAttribute(kw, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.ldsWalk));
-            PTCHECK(persistent_grid(kw, S.ldsWalk, true, first ? &S.gridWalkFirst : &S.gridWalk));
-        }
-    for (int first = 0; first < 2; ++first) {
-        int &grid = first ? S.gridFirst : S.grid;
-        PTCHECK(persistent_grid(first ? S.kernFirst : S.kernNext, first ? S.ldsBytes : S.ldsBytesNext, false, &grid));
-        if (grid > S.numTilesMax) grid = S.numTilesMax;
-        grid = (grid / kSub) * kSub;      // T % kSub == blockIdx % kSub for every tile T of a workgroup (kSub: a multiple of the mesh scenes' 4 too)
-        if (grid < kSub) grid = kSub;
-    }
-    // Camera-ray bounce: tile T covers pixels 256 T ... of the row-major frame and a workgroup owns the tiles b, b + grid,
-    // ...  When the grid shares a factor with the tiles per row (1280 workgroups, 5 tiles per 1280-pixel row) a workgroup
-    // stays in few column bands of the frame, and the bands outside the scene rectangle finish 15x earlier than the
-    // others.  Either the grid can be made coprime to the tiles per row (both must stay multiples of kSub, so only for an
-    // odd tile count per row), or the kernel rotates the k-th tile of a workgroup k bands to the right inside its row,
-    // which needs a grid that is a multiple of the tiles per row (k_bounce<true, .>).
-    // (the packed work list of camera rays has no column bands: nothing to rotate)
+    phase_end(3);      // the tables' uploads
+    PTCHECK(size_launches(S));
     const KParams &k = S.prm;
-    S.prm.tilesPerRow = 0;
-    if (k.Wp / kBlock > 1 && S.dCamPix.p == nullptr) {
-        const int perRow = k.Wp / kBlock;
-        auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
-        if (gcd(perRow, kSub) == 1) {
-            for (int tries = 0; tries < 64 && S.gridFirst > kSub && gcd(S.gridFirst, perRow) != 1; ++tries) S.gridFirst -= kSub;
-        } else {
-            const int unit = perRow / gcd(perRow, kSub) * kSub;        // lcm(perRow, kSub)
-            if (S.gridFirst >= 4 * unit) {
-                S.gridFirst = S.gridFirst / unit * unit;
-                S.prm.tilesPerRow = perRow;
-            }
-        }
-    }
     if (env_flag("PT_AMD_VERBOSE"))       // experiments: what pt_init decided
         fprintf(stderr, "pt_init: lds %zu / %zu B, grid %d / %d, mesh %d many %d plain %d, binned %d walls %d (slots %d, planes %d) allClassified %d, sphCull %d (cluster 0: %d) omax %g\n",
                 S.ldsBytes, S.ldsBytesNext, S.gridFirst, S.grid, (int)S.mesh, (int)S.many, (int)S.plain, k.nBinned, k.nWalls, k.nSlotWalls, k.nPlaneWalls, k.allClassified, k.nSphCull,
                 k.sphN0, (double)k.sphOMax);
     HIPCHECK(hipDeviceSynchronize());
+    phase_end(4);      // launch sizing and the final synchronise
+    if (phases)
+        fprintf(stderr, "pt_init phases ms: plan %.3f free %.3f allocate %.3f upload %.3f size+sync %.3f\n", phaseMs[0], phaseMs[1], phaseMs[2], phaseMs[3], phaseMs[4]);
+    // what the camera move needs of this call: its scene arguments, and the plan whose tables the device now holds
+    S.inGeoms.assign(geoms, geoms + ngeoms);
+    S.inMats.assign(mats, mats + nmats);
+    S.inDepth = traceDepth;
+    S.inOpts = o;
+    S.heldTexels = plan.texels.size();
+    S.heldMeshRecs = plan.meshRecs.size();
+    std::vector<float4>().swap(plan.texels);
+    std::vector<ptd::MeshUnit>().swap(plan.meshRecs);
+    S.held.reset(new ScenePlan(std::move(plan)));
     S.init = true;
     g_err.clear();
     return PT_OK;

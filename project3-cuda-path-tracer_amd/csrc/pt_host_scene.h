@@ -868,18 +868,14 @@ struct CameraList {
 // reference's tmin, and P follows from it by the same operations.  The hit's distance |eye - P| is positive by (i): P lies 1e-4 object
 // units in front of the face, at least smin(transform) (s o_K - 1/2 - 1e-4) world units from the eye.
 // Whatever cannot be bounded -- a non-finite entry, a singular matrix, an eye inside or near a slab -- leaves the pixel unresolved.
-struct CubeCert {
+// (the numbers the certificate reads are ptk::FaceCube and ptk::FaceBasis, pt_camera_faces.h: one body for the host and k_camera_faces)
+struct CubeCert : FaceCube {
     bool ok = false;
-    double o[3], L[3][3], inset[3];
-    double clear = 0;                       // the least s o_K - 1/2 - inset_K: (ii)'s room and (i)'s distance
 };
-struct CameraResolve {
+struct CameraResolve : FaceBasis {
     std::vector<CubeCert> cube;             // per primitive; ok only for a tame cube
-    double view[3], rx[3], uy[3];           // the camera basis: view, right * pixLenX, up * pixLenY
-    double halfW = 0, halfH = 0;
     bool off = false;                       // (PT_AMD_NO_CAMERA_RESOLVE: split as usual, every wave -1)
 };
-constexpr double kFaceFootprint = 2.0, kFaceRho = 1.0 / 4096, kFaceClear = 1e-2, kFaceInsetAbs = 1e-4, kFaceInsetD = 8.0, kFaceMinSlope = 1e-3;
 void build_camera_resolve(const PtGeom *geoms, int ngeoms, const KParams &k, const std::vector<GeomDev> &hg, CameraResolve &cr) {
     cr.cube.assign((size_t)(ngeoms > 0 ? ngeoms : 0), CubeCert());
     for (int a = 0; a < 3; ++a) {
@@ -940,53 +936,33 @@ void build_camera_resolve(const PtGeom *geoms, int ngeoms, const KParams &k, con
 // the face (2 K + (s > 0)) pixel (x, y) is resolved to on cube g, or -1
 int camera_face_certificate(const CameraResolve &cr, int g, int x, int y) {
     if (g < 0 || (size_t)g >= cr.cube.size() || !cr.cube[(size_t)g].ok) return -1;
-    const CubeCert &c = cr.cube[(size_t)g];
-    // the four corner directions of the footprint, object space
-    double q[4][3], qn[4];
-    for (int corner = 0; corner < 4; ++corner) {
-        const double cx = (corner & 1) ? (double)x + 1.0 + kFaceFootprint : (double)x - kFaceFootprint;
-        const double cy = (corner & 2) ? (double)y + 1.0 + kFaceFootprint : (double)y - kFaceFootprint;
-        const double sx = cx - cr.halfW, sy = cy - cr.halfH;
-        double d[3];
-        for (int a = 0; a < 3; ++a) d[a] = cr.view[a] - cr.rx[a] * sx - cr.uy[a] * sy;
-        for (int r = 0; r < 3; ++r) q[corner][r] = c.L[r][0] * d[0] + c.L[r][1] * d[1] + c.L[r][2] * d[2];
-        qn[corner] = std::sqrt(q[corner][0] * q[corner][0] + q[corner][1] * q[corner][1] + q[corner][2] * q[corner][2]);
-        if (!std::isfinite(qn[corner]) || !(qn[corner] > 0)) return -1;
-    }
-    for (int K = 0; K < 3; ++K) {
-        const double s = c.o[K] > 0 ? 1.0 : -1.0;
-        if (!(s * c.o[K] >= 0.5 + c.clear + c.inset[K])) continue;           // (ii), and (i)'s distance
-        const double a = 0.5 * s - c.o[K];                                  // (sign -s)
-        bool ok = true;
-        for (int corner = 0; corner < 4 && ok; ++corner) {
-            const double qK = q[corner][K];
-            ok = s * qK < 0 && std::fabs(qK) >= kFaceMinSlope * qn[corner];
-            for (int side = 0; side < 2 && ok; ++side) {
-                const double lam = a * (side ? 1.0 + kFaceRho : 1.0 - kFaceRho) / qK;
-                ok = std::isfinite(lam) && lam > 0;
-                for (int j = 0; j < 3 && ok; ++j) {
-                    if (j == K) continue;
-                    const double pj = c.o[j] + lam * q[corner][j];
-                    ok = std::fabs(pj) <= 0.5 - c.inset[j];                 // (NaN fails)
-                }
-            }
-        }
-        if (ok) return 2 * K + (s > 0 ? 1 : 0);
-    }
-    return -1;
+    return face_certificate(cr.cube[(size_t)g], cr, x, y);
 }
 
 // `cr` (optional): a one-cube signature's pixels are split into the groups its faces resolve (camera_face_certificate) and the
 // unresolved rest, each padded to whole waves like a signature; CameraList::face names a wave's face.  A split that makes the list
 // longer than maxLen is dropped (every wave -1): the list never visits more lanes than the tiles it replaces.
-bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int shardCount, long long maxLen, CameraList &cl,
-                       const CameraResolve *cr = nullptr) {
-    cl.pix.clear(); cl.wave.clear(); cl.sigIdx.clear(); cl.face.clear();
-    cl.nSig = 0; cl.listed = 0; cl.resolved = 0;
-    if (cc.rowOff.empty() || W > 32768 || H > 32768 || shardCount < 1 || shardRank < 0 || shardRank >= shardCount) return false;
-    std::map<std::vector<int>, int> ids;
+// The list is built in two passes.  (a) camera_list_groups: the spans are grouped into signature groups of pixels.  (b) camera_list_emit:
+// given a face per pixel of every one-cube group whose cube is CubeCert::ok (CameraGroups::faces, one entry per pixel; the other groups'
+// stay empty), the stable split by face, the padding to whole waves and the emission.  Between the two, build_camera_list evaluates the
+// certificates on the host (camera_list_faces_host); the camera move (pt_api.hip) evaluates them on the device (k_camera_faces) -- the same faces.
+struct CameraGroups {
     std::vector<std::vector<uint32_t>> groups;        // per signature its pixels, row-major
     std::vector<std::vector<int>> sigs;
+    std::vector<std::vector<int>> faces;              // per group: its pixels' faces, or empty (not a certified one-cube group; no `cr`)
+    long long listed = 0, len = 0;                    // pixels in the list; its length without a split
+};
+// the cube of group s where its pixels get certificates, else -1
+int camera_group_cube(const CameraGroups &G, size_t s, const CameraResolve &cr) {
+    if (G.sigs[s].size() != 1 || (size_t)G.sigs[s][0] >= cr.cube.size() || !cr.cube[(size_t)G.sigs[s][0]].ok) return -1;
+    return G.sigs[s][0];
+}
+bool camera_list_groups(const CameraCull &cc, int W, int H, int shardRank, int shardCount, long long maxLen, CameraGroups &G) {
+    G = CameraGroups();
+    if (cc.rowOff.empty() || W > 32768 || H > 32768 || shardCount < 1 || shardRank < 0 || shardRank >= shardCount) return false;
+    std::map<std::vector<int>, int> ids;
+    std::vector<std::vector<uint32_t>> &groups = G.groups;
+    std::vector<std::vector<int>> &sigs = G.sigs;
     std::vector<int> cuts, act;
     for (int y = shardRank; y < H; y += shardCount) {
         const int e0 = cc.rowOff[y], e1 = cc.rowOff[y + 1];
@@ -1015,31 +991,46 @@ bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int sh
             }
             std::vector<uint32_t> &g = groups[(size_t)it.first->second];
             for (int x = a; x < b; ++x) g.push_back((uint32_t)x | ((uint32_t)y << 16));
-            cl.listed += b - a;
+            G.listed += b - a;
         }
     }
-    auto padded = [](long long n) { return (n + 63) / 64 * 64; };
     long long len = 0;
-    for (const auto &g : groups) len += padded((long long)g.size());
-    len = (len + kBlock - 1) / kBlock * kBlock;
-    if (len > maxLen) return false;
+    for (const auto &g : groups) len += ((long long)g.size() + 63) / 64 * 64;
+    G.len = (len + kBlock - 1) / kBlock * kBlock;
+    G.faces.assign(groups.size(), std::vector<int>());
+    return G.len <= maxLen;
+}
+// the host's certificates between the passes: per pixel of every certified one-cube group
+void camera_list_faces_host(CameraGroups &G, const CameraResolve &cr) {
+    for (size_t s = 0; s < G.groups.size(); ++s) {
+        const int cube = camera_group_cube(G, s, cr);
+        if (cube < 0) continue;
+        const std::vector<uint32_t> &g = G.groups[s];
+        std::vector<int> &f = G.faces[s];
+        f.resize(g.size());
+        for (size_t i = 0; i < g.size(); ++i) f[i] = camera_face_certificate(cr, cube, (int)(g[i] & 0xffffu), (int)(g[i] >> 16));
+    }
+}
+void camera_list_emit(CameraGroups &G, long long maxLen, CameraList &cl, const CameraResolve *cr) {
+    cl.pix.clear(); cl.wave.clear(); cl.sigIdx.clear(); cl.face.clear();
+    cl.nSig = 0; cl.listed = G.listed; cl.resolved = 0;
+    std::vector<std::vector<uint32_t>> &groups = G.groups;
+    const std::vector<std::vector<int>> &sigs = G.sigs;
+    std::vector<std::vector<int>> &faces = G.faces;
+    auto padded = [](long long n) { return (n + 63) / 64 * 64; };
+    long long len = G.len;
     // the split of the one-cube signatures: per group its pixels' faces, stably sorted -- the unresolved rest (-1) first, then face by face
-    std::vector<std::vector<int>> faces(groups.size());
     if (cr) {
         long long lenSplit = 0;
         for (size_t s = 0; s < groups.size(); ++s) {
             std::vector<uint32_t> &g = groups[s];
-            if (sigs[s].size() != 1 || (size_t)sigs[s][0] >= cr->cube.size() || !cr->cube[(size_t)sigs[s][0]].ok) {
+            if (camera_group_cube(G, s, *cr) < 0) {
                 lenSplit += padded((long long)g.size());
                 continue;
             }
             std::vector<int> &f = faces[s];
-            f.resize(g.size());
             long long n[7] = {0, 0, 0, 0, 0, 0, 0};
-            for (size_t i = 0; i < g.size(); ++i) {
-                f[i] = camera_face_certificate(*cr, sigs[s][0], (int)(g[i] & 0xffffu), (int)(g[i] >> 16));
-                ++n[f[i] + 1];
-            }
+            for (size_t i = 0; i < g.size(); ++i) ++n[f[i] + 1];
             std::vector<uint32_t> gs(g.size());
             std::vector<int> fs(g.size());
             size_t at[7], o = 0;
@@ -1051,6 +1042,8 @@ bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int sh
         lenSplit = (lenSplit + kBlock - 1) / kBlock * kBlock;
         if (lenSplit > maxLen) for (auto &f : faces) f.clear();
         else len = lenSplit;
+    } else {
+        for (auto &f : faces) f.clear();
     }
     cl.pix.reserve((size_t)len);
     cl.wave.reserve((size_t)len / 32);
@@ -1078,6 +1071,17 @@ bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int sh
     cl.face.resize((size_t)len / 64, -1);
     if (cl.sigIdx.empty()) cl.sigIdx.push_back(0);
     cl.nSig = (int)sigs.size();
+}
+bool build_camera_list(const CameraCull &cc, int W, int H, int shardRank, int shardCount, long long maxLen, CameraList &cl,
+                       const CameraResolve *cr = nullptr) {
+    cl.pix.clear(); cl.wave.clear(); cl.sigIdx.clear(); cl.face.clear();
+    cl.nSig = 0; cl.listed = 0; cl.resolved = 0;
+    CameraGroups G;
+    const bool fits = camera_list_groups(cc, W, H, shardRank, shardCount, maxLen, G);
+    cl.listed = G.listed;       // (as before the split into passes: a refused list still says how many pixels it had gathered)
+    if (!fits) return false;
+    if (cr) camera_list_faces_host(G, *cr);
+    camera_list_emit(G, maxLen, cl, cr);
     return true;
 }
 

@@ -27,6 +27,9 @@ struct SceneIn {
     const std::vector<HostTexture> &textures;
     const std::vector<HostTexBinding> &texBindings;
     const std::vector<HostBumpBinding> &bumpBindings;
+    // who evaluates the work list's face certificates between build_camera_list's two passes: nobody named -- the host (pt_init, the
+    // host-only entry points); the camera move (pt_api.hip) names the device (k_camera_faces).  PT_OK, or what fail() returned.
+    std::function<int(CameraGroups &, const CameraResolve &)> faces = nullptr;
     const ptm::HostMesh *mesh_of(int geom) const {
         for (const ptm::HostMesh &m : meshes)
             if (m.geom == geom) return &m;
@@ -807,8 +810,20 @@ int plan_camera_list(const SceneIn &in, ScenePlan &p) {
         build_camera_resolve(in.geoms, in.ngeoms, k, p.hg, cr);
         cr.off = env_flag("PT_AMD_NO_CAMERA_RESOLVE");
     }
-    if (!listOff && !p.dof && !p.mesh && !p.many &&
-        build_camera_list(p.cc, k.W, k.H, in.o.shard_rank, in.o.shard_count, k.nLocalPad, p.cl, resolve ? &cr : nullptr) && !p.cl.pix.empty()) {
+    bool built = false;
+    if (!listOff && !p.dof && !p.mesh && !p.many) {
+        if (resolve && in.faces) {       // the two passes, the certificates between them where the caller says
+            CameraGroups G;
+            built = camera_list_groups(p.cc, k.W, k.H, in.o.shard_rank, in.o.shard_count, k.nLocalPad, G);
+            if (built) {
+                PTCHECK(in.faces(G, cr));
+                camera_list_emit(G, k.nLocalPad, p.cl, &cr);
+            }
+        } else {
+            built = build_camera_list(p.cc, k.W, k.H, in.o.shard_rank, in.o.shard_count, k.nLocalPad, p.cl, resolve ? &cr : nullptr);
+        }
+    }
+    if (built && !p.cl.pix.empty()) {
         k.firstSkipped = (int)((long long)p.nLocal - p.cl.listed);
         return set_tile_space(k, k.Wp, (int)p.cl.pix.size());
     }

@@ -856,6 +856,47 @@ int pt_test_camera_resolved(const PtCamera *cam, const PtGeom *geoms, int ngeoms
     return PT_OK;
 }
 
+// the same list with its certificates evaluated on the device between build_camera_list's two passes, as the camera move (pt_api.hip) evaluates them
+// (k_camera_faces); kernel_ms (or NULL): the launches' time by HIP events
+int pt_test_camera_resolved_device(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int shard_rank, int shard_count, uint32_t *pix, int32_t *wave2,
+                                   int32_t *sig_idx, int32_t *face, int64_t *sizes4, float *kernel_ms) {
+    NEED_GPU();
+    if (!cam || !geoms || ngeoms < 1 || !sizes4) return fail(PT_ERR_INVALID, "pt_test_camera_resolved_device: bad argument");
+    if (shard_count < 1 || shard_rank < 0 || shard_rank >= shard_count) return fail(PT_ERR_INVALID, "pt_test_camera_resolved_device: bad shard");
+    if (kernel_ms) *kernel_ms = 0.0f;
+    CameraFixture f;
+    CameraList cl;
+    PTCHECK(f.cull(cam, geoms, ngeoms, kAnyGeom, kAnyResolution, "pt_test_camera_resolved_device"));
+    CameraResolve cr;
+    build_camera_resolve(geoms, f.k.ngeoms, f.k, f.hg, cr);
+    CameraGroups G;
+    const long long noCap = std::numeric_limits<long long>::max();
+    const bool built = camera_list_groups(f.cc, f.k.W, f.k.H, shard_rank, shard_count, noCap, G);
+    cl.listed = G.listed;
+    if (built) {
+        DevBuf<uint32_t> dpix;
+        DevBuf<signed char> dface;
+        PTCHECK(camera_faces_device(G, cr, nullptr, dpix, dface, kernel_ms));
+        camera_list_emit(G, noCap, cl, &cr);
+    }
+    sizes4[0] = built ? (int64_t)cl.pix.size() : -1;
+    sizes4[1] = (int64_t)cl.sigIdx.size();
+    sizes4[2] = cl.listed;
+    sizes4[3] = cl.resolved;
+    if (built && pix && wave2 && sig_idx && face) copy_camera_list(cl, pix, wave2, sig_idx, face);
+    return PT_OK;
+}
+
+// which way the calling thread's last camera move (pt_api.hip: set_camera) went: *fast 1 (every buffer kept) or 0 (pt_init inside), -1 before the first move and
+// after a refusal; the tables the fast path uploaded and their bytes
+int pt_test_last_camera_move(int *fast, int *tables_uploaded, int *bytes_uploaded) {
+    if (!fast || !tables_uploaded || !bytes_uploaded) return fail(PT_ERR_INVALID, "pt_test_last_camera_move: bad argument");
+    *fast = t_lastMove.fast;
+    *tables_uploaded = t_lastMove.tables;
+    *bytes_uploaded = (int)std::min<long long>(t_lastMove.bytes, std::numeric_limits<int>::max());
+    return PT_OK;
+}
+
 int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t seed, uint64_t counts[3]) {
     NEED_GPU();
     if (!cam || !geoms || ngeoms < 1 || samples < 0 || samples > 4096 || !counts) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: bad argument");

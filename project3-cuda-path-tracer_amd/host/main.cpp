@@ -7,7 +7,7 @@
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 //                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
-//                           [--history-from EX EY EZ N] [--spatial-variance] [--demodulate] [--history-albedo]
+//                           [--history-from EX EY EZ N [--in-place]] [--spatial-variance] [--demodulate] [--history-albedo]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
@@ -66,6 +66,7 @@ static bool noiseTarget = false;
 static float noiseThreshold = 0.0f, noiseFraction = 0.0f;
 static int checkEvery = 8;
 static bool historyFrom = false;
+static bool inPlace = false;         // --in-place (with --history-from): the move is made by pt_init's same-scene form
 static float historyEye[3] = {0.0f, 0.0f, 0.0f};
 static int historyIterations = 0;
 static bool spatialVariance = false;
@@ -210,7 +211,10 @@ static void renderBatched() {
         }
         firstIter = historyIterations + 1;
     }
-    // (with --history-from: over the live renderer -- no pt_free -- which is what carries the history)
+    // (with --history-from: over the live renderer -- no pt_free -- which is what carries the history; --in-place: the same move by
+    // pt_init's same-scene form (PT_SAME_SCENE), which keeps the renderer's buffers -- the same PNGs)
+    if (historyFrom && inPlace) check(pt_init((const PtCamera *)&renderState->camera, NULL, 0, NULL, 0, PT_SAME_SCENE, NULL), "pt_init (camera move)");
+    else
     check(pt_init((const PtCamera *)&renderState->camera, (const PtGeom *)scene->geoms.data(), (int)scene->geoms.size(),
                   (const PtMaterial *)scene->materials.data(), (int)scene->materials.size(), renderState->traceDepth, &opt),
           "pt_init");
@@ -245,7 +249,7 @@ static void renderBatched() {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N] [--spatial-variance] [--demodulate] [--history-albedo]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place]] [--spatial-variance] [--demodulate] [--history-albedo]\n", argv[0]);
         return 1;
     }
     try {
@@ -285,6 +289,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--noise-threshold") && i + 1 < argc) { noiseTarget = true; noiseThreshold = (float)atof(argv[++i]); }
         else if (!strcmp(argv[i], "--noise-fraction") && i + 1 < argc) noiseFraction = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--check-every") && i + 1 < argc) checkEvery = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--in-place")) inPlace = true;
         else if (!strcmp(argv[i], "--history-from") && i + 4 < argc) {
             historyFrom = true;
             for (int a = 0; a < 3; ++a) historyEye[a] = (float)atof(argv[i + 1 + a]);
@@ -305,6 +310,7 @@ int main(int argc, char **argv) {
     if (spatialVariance && !denoiseVar) { fprintf(stderr, "--spatial-variance needs --denoise-var\n"); return 1; }
     pathtraceExtras(lensRadius, focalDistance, directLighting);
     pathtraceMoments(denoiseVar);
+    if (inPlace && !historyFrom) { fprintf(stderr, "--in-place needs --history-from\n"); return 1; }
     if (demodulate && (!denoiseVar || historyFrom)) { fprintf(stderr, "--demodulate needs --denoise-var and does not go with --history-from\n"); return 1; }
     pathtraceSpatialVariance(spatialVariance);
     pathtraceDemodulate(demodulate);
