@@ -126,6 +126,23 @@ enum {
                                     display path divide the blend of the reprojected history with the new samples by the BLENDED albedo.  While the
                                     context holds no history the renderer is PT_FLAG_DEMODULATE's bit for bit.  PT_ERR_INVALID without any of the
                                     three; every other refusal of PT_FLAG_TEMPORAL and of PT_FLAG_DEMODULATE stands. */
+    PT_FLAG_KEEP_RENDERER = 2048,/* a flag about COST alone, for callers that repeat the full pt_init whenever the camera moves (the reference's
+                                    Free -> Init restart, src/main.cpp:91-95; host/pathtrace_shim.cpp under PT_AMD_KEEP_RENDERER).  A full call
+                                    that carries it over a LIVE renderer of the same context is compared with what that renderer was initialised
+                                    with, and takes the same-scene form's path (PT_SAME_SCENE below: every buffer, stream and event kept) when all
+                                    of these are equal: ngeoms and the geoms' bytes; nmats and the materials' bytes; traceDepth; every field of
+                                    PtOptions, this flag included (stream, accum_dev and device as values); the camera's resolution; and what is
+                                    registered NOW with pt_set_meshes / pt_set_textures / pt_set_bump_maps against the renderer's own copies --
+                                    counts, sizes and bindings, the triangle, normal, face-material and UV arrays, and the texels, all byte for
+                                    byte (memcmp, no hash).  In every other case -- a renderer initialised without the flag included: the flags
+                                    differ -- the call is the full call it is today.  Either way the result is the full call's bit for bit (the
+                                    same-scene form's own definition: accumulators, moments and albedo sums zeroed, counters reset, parked batches
+                                    discarded, guide buffers invalidated, under PT_FLAG_TEMPORAL the old view captured into the history first),
+                                    every refusal of the full call stands and happens before anything is touched, and a renderer with a sticky
+                                    device fault, or a HIP failure before anything is overwritten, runs the full call inside.  Otherwise inert: a
+                                    flagged renderer allocates and launches exactly what an unflagged one does, pt_free is unchanged, and an
+                                    unflagged caller sees nothing new.  PT_ERR_INVALID from pt_group_init (groups re-initialise in place already).
+                                    (Additive, no new function, no struct changed: the ABI version stays.) */
     PT_FLAG_DIRECT_LIGHTING = 4/* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what

@@ -116,6 +116,10 @@ int pt_test_camera_resolved_device(const PtCamera *cam, const PtGeom *geoms, int
 /* Which way the calling thread's last camera move (pt_init with PT_SAME_SCENE) went: *fast = 1 (every buffer kept), 0 (pt_init inside), -1 before the first move and
  * after a refusal; the tables the fast path uploaded, and their bytes. */
 int pt_test_last_camera_move(int *fast, int *tables_uploaded, int *bytes_uploaded);
+/* A full pt_init call with PT_FLAG_KEEP_RENDERER reports through pt_test_last_camera_move as well: the move's figures where it matched the live renderer, the state
+ * "before the first move" (-1, 0, 0) where it ran the full call.  pt_test_keep_mismatch: WHY the calling thread's last such call did not match -- the name of the
+ * first comparison that failed ("geoms", "materials", "traceDepth", "flags", "max_batch", "texels", "texture UVs", "no live renderer", ...), "" where it matched. */
+int pt_test_keep_mismatch(char *why, int bytes);
 /* Device sweep: for every resolved pixel of the unsharded list, `samples` seeded jitters and the four corners of the certificate's
  * footprint -- the resolved wave's box test (pt_device.h: boxFaceHit) against boxIntersectionTest.  counts = {rays, rays on which
  * (t > 0, outside, face, P bit for bit) differ -- must be 0 --, resolved pixels}. */

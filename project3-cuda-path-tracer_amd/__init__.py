@@ -63,6 +63,8 @@ PT_DEMOD_MIN_ALBEDO = 0.015625
 # albedo -- not the blend with the reprojected one -- is multiplied back behind the filter
 PT_FLAG_DEMOD_HISTORY = 1024
 PT_DEMOD_HISTORY_MIN_OWN = 2
+# a flag about cost alone (include/pt_amd.h): a full pt_init that repeats the live renderer's own call with another pose moves the camera in place
+PT_FLAG_KEEP_RENDERER = 2048
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -96,7 +98,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_renderer_state", "pt_test_scene_plan", "pt_test_temporal", "pt_test_temporal_camera", "pt_test_history",
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions", "pt_test_sphere_groups", "pt_test_group_tally",
-    "pt_test_camera_resolved_device", "pt_test_last_camera_move",
+    "pt_test_camera_resolved_device", "pt_test_last_camera_move", "pt_test_keep_mismatch",
 ]
 
 
@@ -251,6 +253,7 @@ def _bind(L, with_tests):
         L.pt_test_camera_resolved.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
         L.pt_test_camera_resolved_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         L.pt_test_last_camera_move.argtypes = [vp, vp, vp]
+        L.pt_test_keep_mismatch.argtypes = [vp, i32]
         L.pt_test_face_hit_sweep.argtypes = [vp, vp, i32, i32, C.c_uint64, u64p]
         L.pt_test_wall_faces.argtypes = [vp, vp, i32, vp, i32, i32, C.POINTER(PtOptions), vp, vp]
         L.pt_test_wall_face_sweep.argtypes = [vp, i32, C.c_uint64, i64, u64p]
@@ -470,8 +473,11 @@ _scene = None
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
                   mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False, demodulate=False,
-                  demod_history=False):
+                  demod_history=False, keep=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    keep: PT_FLAG_KEEP_RENDERER -- a flag about cost alone: calling pathtraceInit AGAIN over the live renderer with the same scene, arguments
+    and registered meshes, textures and height maps (compared byte for byte) and another pose moves the camera in place, as pathtraceSetCamera
+    does; anything else is the full call.  The result is the full call's bit for bit either way.
     demod_history: PT_FLAG_DEMOD_HISTORY (with moments=True, temporal=True and demodulate=True, which go together under it alone) -- the
     history a re-initialisation carries over also holds the old view's mean first-hit albedo, and denoise_var / denoise_var_rgba8 / the display
     divide the blend of history and new samples by the blended albedo.  History passes only between renderers that agree on the flag.
@@ -511,6 +517,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_DEMODULATE
     if demod_history:
         flags |= PT_FLAG_DEMOD_HISTORY
+    if keep:
+        flags |= PT_FLAG_KEEP_RENDERER
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -549,12 +557,21 @@ def pathtraceSetCamera(camera_or_scene):
 
 
 def camera_move_info():
-    """pt_test_last_camera_move (test library; see renderer_from_test_library): which way this thread's last pathtraceSetCamera went --
-    {"fast": True / False / None (no move yet, or the last one was refused), "tables_uploaded": n, "bytes_uploaded": n}."""
+    """pt_test_last_camera_move (test library; see renderer_from_test_library): which way this thread's last pathtraceSetCamera -- or
+    pathtraceInit(..., keep=True) -- went: {"fast": True / False / None (no move yet, the last one was refused, or the keep=True call ran
+    the full call), "tables_uploaded": n, "bytes_uploaded": n}."""
     out = [C.c_int(0) for _ in range(3)]
     _tcheck(test_lib().pt_test_last_camera_move(*[C.byref(o) for o in out]))
     fast = out[0].value
     return {"fast": None if fast < 0 else bool(fast), "tables_uploaded": out[1].value, "bytes_uploaded": out[2].value}
+
+
+def keep_mismatch():
+    """pt_test_keep_mismatch (test library): why this thread's last pathtraceInit(..., keep=True) ran the full call -- the name of the first
+    comparison that failed ("geoms", "materials", "traceDepth", "flags", "texels", ..., "no live renderer"), "" where it moved in place."""
+    buf = C.create_string_buffer(64)
+    _tcheck(test_lib().pt_test_keep_mismatch(buf, len(buf)))
+    return buf.value.decode()
 
 
 def scene_plan(scene, traceDepth=None, **options):

@@ -1298,6 +1298,11 @@ int size_launches(State &S) {
 // refusal; the tables and bytes the fast path uploaded
 struct CameraMove { int fast = -1, tables = 0; long long bytes = 0; };
 thread_local CameraMove t_lastMove;
+// PT_FLAG_KEEP_RENDERER: why the calling thread's last flagged full call did not take the move's path (keep_renderer_mismatch's answer, or
+// that there was no renderer; null: it did, or there has been no such call), and the mark of the move's own full call inside, which
+// carries the renderer's options -- the flag with them -- and must not be compared again
+thread_local const char *t_keepWhy = nullptr;
+thread_local bool t_fullCallInside = false;
 
 // The work list's face certificates on the device, between build_camera_list's two passes: the pixel words of the one-cube groups whose
 // cube is CubeCert::ok go up as one array, k_camera_faces runs once per group -- the cube is uniform per group: a kernel argument -- and
@@ -1384,7 +1389,9 @@ int reinit_with_camera(const PtCamera &cam) {
     if (initTextures) std::swap(*initTextures, S.textures);
     if (initTexBindings) std::swap(*initTexBindings, S.texBindings);
     if (initBumpBindings) std::swap(*initBumpBindings, S.bumpBindings);
+    t_fullCallInside = true;
     const int rc = pt_init(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), depth, &o);
+    t_fullCallInside = false;
     const std::string err = g_err;
     State &N = R();
     if (initMeshes) std::swap(*initMeshes, N.meshes);
@@ -1399,6 +1406,19 @@ int reinit_with_camera(const PtCamera &cam) {
     }
     g_err = err;
     return rc;
+}
+
+// PT_FLAG_KEEP_RENDERER on a full call: the call against the live renderer's copies of its own (pt_scene_plan.h: keep_renderer_mismatch).
+// What is registered now and what the renderer was initialised with are one object while no pt_set_* call has come in between.
+const char *keep_mismatch(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions &o) {
+    State &S = R();
+    if (!S.init) return "no live renderer";
+    if (!cam) return "camera";
+    const InitCall now{geoms, ngeoms, mats, nmats, traceDepth, &o, cam->resolution[0], cam->resolution[1], {&S.meshes, &S.textures, &S.texBindings, &S.bumpBindings}};
+    const InitCall then{S.inGeoms.data(), (int)S.inGeoms.size(), S.inMats.data(), (int)S.inMats.size(), S.inDepth, &S.inOpts, S.prm.W, S.prm.H,
+                        {S.initMeshes ? S.initMeshes.get() : &S.meshes, S.initTextures ? S.initTextures.get() : &S.textures,
+                         S.initTexBindings ? S.initTexBindings.get() : &S.texBindings, S.initBumpBindings ? S.initBumpBindings.get() : &S.bumpBindings}};
+    return keep_renderer_mismatch(now, then);
 }
 
 int set_camera(const PtCamera *cam) {
@@ -1639,6 +1659,19 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // the camera move: no scene at all and PT_SAME_SCENE for the depth name the scene the live renderer was initialised with
     if (!geoms && !mats && ngeoms == 0 && nmats == 0 && traceDepth == PT_SAME_SCENE && !opts) return set_camera(cam);
     const PtOptions o = effective_options(opts);
+    // PT_FLAG_KEEP_RENDERER: the same call again with another pose is the camera move too.  (Equal registrations: the renderer's own copies
+    // of what a pt_set_* call has replaced with the same bytes are let go -- the registered ones serve.)
+    if ((o.flags & PT_FLAG_KEEP_RENDERER) && !t_fullCallInside) {
+        t_lastMove = CameraMove();
+        t_keepWhy = keep_mismatch(cam, geoms, ngeoms, mats, nmats, traceDepth, o);
+        if (!t_keepWhy) {
+            R().initMeshes.reset();
+            R().initTextures.reset();
+            R().initTexBindings.reset();
+            R().initBumpBindings.reset();
+            return set_camera(cam);
+        }
+    }
     // PT_AMD_INIT_PHASES (measurements only: profiles/set_camera_cost.py): the host's clock around the call's phases, each ended by a
     // device synchronise of its own, printed to stderr
     const bool phases = env_flag("PT_AMD_INIT_PHASES");

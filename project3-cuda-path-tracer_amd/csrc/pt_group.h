@@ -688,6 +688,8 @@ int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeo
     if (!g || !cam) return fail(PT_ERR_INVALID, "pt_group_init: null argument");
     if (cam->resolution[0] <= 0 || cam->resolution[1] <= 0) return fail(PT_ERR_INVALID, "pt_group_init: bad resolution");
     if (opts && (opts->flags & PT_FLAG_MOMENTS)) return fail(PT_ERR_INVALID, "pt_group_init: PT_FLAG_MOMENTS is not for groups (their members hold row shards)");
+    if (opts && (opts->flags & PT_FLAG_KEEP_RENDERER))
+        return fail(PT_ERR_INVALID, "pt_group_init: PT_FLAG_KEEP_RENDERER is not for groups (a group re-initialises its members in place already)");
     CurrentGuard guard;
     const int n = (int)g->ctx.size();
     {   // a re-init (the reference's Free -> Init restart): the old renderers go first, then the buffers they accumulate into

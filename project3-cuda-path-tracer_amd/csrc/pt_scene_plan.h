@@ -48,6 +48,86 @@ PtOptions effective_options(const PtOptions *opts) {
     return o;
 }
 
+// PT_FLAG_KEEP_RENDERER: is a full pt_init call the one the live renderer was initialised with, the camera's pose aside?  `now`: the call's
+// arguments (options made effective) and what is registered at this moment; `then`: the renderer's copies.  NULL where everything the flag's
+// definition lists (include/pt_amd.h) is equal, else the name of the first comparison that failed (pt_test_keep_mismatch).  Arrays are
+// compared byte for byte -- texels too: no hash --, so a -0.0 for a 0.0 is a difference: the full call, which is always right.
+struct RegisteredScene {
+    const std::vector<ptm::HostMesh> *meshes;
+    const std::vector<HostTexture> *textures;
+    const std::vector<HostTexBinding> *texBindings;
+    const std::vector<HostBumpBinding> *bumpBindings;
+};
+struct InitCall {
+    const PtGeom *geoms;
+    int ngeoms;
+    const PtMaterial *mats;
+    int nmats, traceDepth;
+    const PtOptions *o;
+    int W, H;
+    RegisteredScene reg;
+};
+template <typename T>
+inline bool same_bytes(const std::vector<T> &a, const std::vector<T> &b) {
+    return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(T)));
+}
+inline const char *keep_renderer_mismatch(const InitCall &now, const InitCall &then) {
+    if (!now.o || !then.o) return "options";
+    if (now.W != then.W || now.H != then.H) return "resolution";
+    if (now.ngeoms != then.ngeoms || now.ngeoms < 0 || (now.ngeoms > 0 && (!now.geoms || !then.geoms))) return "geom count";
+    if (now.nmats != then.nmats || now.nmats < 0 || (now.nmats > 0 && (!now.mats || !then.mats))) return "material count";
+    if (now.ngeoms > 0 && memcmp(now.geoms, then.geoms, (size_t)now.ngeoms * sizeof(PtGeom))) return "geoms";
+    if (now.nmats > 0 && memcmp(now.mats, then.mats, (size_t)now.nmats * sizeof(PtMaterial))) return "materials";
+    if (now.traceDepth != then.traceDepth) return "traceDepth";
+    const PtOptions &a = *now.o, &b = *then.o;
+    if (a.shard_rank != b.shard_rank || a.shard_count != b.shard_count) return "shard";
+    if (a.device != b.device) return "device";
+    if (a.flags != b.flags) return "flags";
+    if (a.pipeline_depth != b.pipeline_depth) return "pipeline_depth";
+    if (a.max_batch != b.max_batch) return "max_batch";
+    if (a.stream != b.stream) return "stream";
+    if (a.accum_dev != b.accum_dev) return "accum_dev";
+    if (memcmp(&a.lens_radius, &b.lens_radius, sizeof(float))) return "lens_radius";
+    if (memcmp(&a.focal_distance, &b.focal_distance, sizeof(float))) return "focal_distance";
+    const RegisteredScene &p = now.reg, &q = then.reg;
+    if (p.meshes != q.meshes) {
+        if (p.meshes->size() != q.meshes->size()) return "mesh count";
+        for (size_t i = 0; i < p.meshes->size(); ++i) {
+            const ptm::HostMesh &m = (*p.meshes)[i], &n = (*q.meshes)[i];
+            if (m.geom != n.geom) return "mesh geom";
+            if (!same_bytes(m.tris, n.tris)) return "mesh triangles";
+            if (!same_bytes(m.normals, n.normals)) return "mesh normals";
+            if (!same_bytes(m.mats, n.mats)) return "mesh face materials";
+        }
+    }
+    if (p.textures != q.textures) {
+        if (p.textures->size() != q.textures->size()) return "texture count";
+        for (size_t i = 0; i < p.textures->size(); ++i) {
+            const HostTexture &s = (*p.textures)[i], &t = (*q.textures)[i];
+            if (s.w != t.w || s.h != t.h) return "texture size";
+            if (!same_bytes(s.rgb, t.rgb)) return "texels";
+        }
+    }
+    if (p.texBindings != q.texBindings) {
+        if (p.texBindings->size() != q.texBindings->size()) return "texture binding count";
+        for (size_t i = 0; i < p.texBindings->size(); ++i) {
+            const HostTexBinding &s = (*p.texBindings)[i], &t = (*q.texBindings)[i];
+            if (s.geom != t.geom || s.texture != t.texture || s.ntris != t.ntris) return "texture binding";
+            if (!same_bytes(s.uvs, t.uvs)) return "texture UVs";
+        }
+    }
+    if (p.bumpBindings != q.bumpBindings) {
+        if (p.bumpBindings->size() != q.bumpBindings->size()) return "bump binding count";
+        for (size_t i = 0; i < p.bumpBindings->size(); ++i) {
+            const HostBumpBinding &s = (*p.bumpBindings)[i], &t = (*q.bumpBindings)[i];
+            if (s.geom != t.geom || s.texture != t.texture || s.ntris != t.ntris) return "bump binding";
+            if (memcmp(&s.scale, &t.scale, sizeof(float))) return "bump scale";
+            if (!same_bytes(s.uvs, t.uvs)) return "bump UVs";
+        }
+    }
+    return nullptr;
+}
+
 // bits of one code of a path's material history (ptk::PathPool): 2 * material + (specular ? 1 : 0) < 2 nmats -- max(1, ceil(log2(2 nmats)))
 inline int history_code_bits(int nmats) {
     int b = 1;

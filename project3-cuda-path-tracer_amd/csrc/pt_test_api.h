@@ -897,6 +897,14 @@ int pt_test_last_camera_move(int *fast, int *tables_uploaded, int *bytes_uploade
     return PT_OK;
 }
 
+// why the calling thread's last full pt_init call with PT_FLAG_KEEP_RENDERER did not move the camera in place (pt_api.hip: keep_mismatch): the name
+// of the comparison that failed, "" where it matched or there has been no such call
+int pt_test_keep_mismatch(char *why, int bytes) {
+    if (!why || bytes < 1) return fail(PT_ERR_INVALID, "pt_test_keep_mismatch: bad argument");
+    snprintf(why, (size_t)bytes, "%s", t_keepWhy ? t_keepWhy : "");
+    return PT_OK;
+}
+
 int pt_test_face_hit_sweep(const PtCamera *cam, const PtGeom *geoms, int ngeoms, int samples, uint64_t seed, uint64_t counts[3]) {
     NEED_GPU();
     if (!cam || !geoms || ngeoms < 1 || samples < 0 || samples > 4096 || !counts) return fail(PT_ERR_INVALID, "pt_test_face_hit_sweep: bad argument");

@@ -7,7 +7,7 @@
 //                           [--lens RADIUS FOCALDISTANCE] [--direct] [--denoise LEVELS SIGMACOLOR SIGMANORMAL SIGMAPOSITION]
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 //                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
-//                           [--history-from EX EY EZ N [--in-place]] [--spatial-variance] [--demodulate] [--history-albedo]
+//                           [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
@@ -23,6 +23,10 @@
 // first view's samples become the context's history (include/pt_amd.h, "temporal reprojection") --, --iterations more are rendered there
 // (numbered N + 1, ...: fresh random numbers), and <out>.denoised.png is the filter of the blend.  The usual image holds the second view's
 // own samples alone.  Through the C ABI like --noise-threshold (B may be 1); not together with it.
+// --in-place makes that move by pt_init's same-scene form (PT_SAME_SCENE), which keeps the renderer's buffers.  --protocol makes it the way
+// the reference's host does -- pathtraceFree(); pathtraceInit(scene); (src/main.cpp:91-95) -- through the shim's three symbols, one pathtrace
+// call per iteration, with pathtraceKeepRenderer and pathtraceTemporal switched on: Free parks the renderer, Init moves its camera in place
+// (PT_FLAG_KEEP_RENDERER).  The same PNGs, byte for byte, all three ways.  One of the two at most.
 // --spatial-variance (with --denoise-var) runs the renderer with PT_FLAG_SPATIAL_VARIANCE: a pixel with fewer than two effective samples is
 // filtered under a variance estimated from its neighbours (include/pt_amd.h, "spatial variance"), so --iterations 1 is allowed, and with
 // --history-from a new view of one sample.
@@ -67,6 +71,7 @@ static float noiseThreshold = 0.0f, noiseFraction = 0.0f;
 static int checkEvery = 8;
 static bool historyFrom = false;
 static bool inPlace = false;         // --in-place (with --history-from): the move is made by pt_init's same-scene form
+static bool protocol = false;        // --protocol (with --history-from): the move is made by pathtraceFree(); pathtraceInit(scene); through the shim
 static float historyEye[3] = {0.0f, 0.0f, 0.0f};
 static int historyIterations = 0;
 static bool spatialVariance = false;
@@ -76,6 +81,7 @@ void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting)
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 void pathtraceSpatialVariance(bool on);                                             // pathtrace_shim.cpp
 void pathtraceDemodulate(bool on);                                                  // pathtrace_shim.cpp
+// (pathtraceTemporal, pathtraceKeepRenderer: pathtrace.h)
 
 static std::string currentTimeString() {
     time_t now;
@@ -246,10 +252,41 @@ static void renderBatched() {
     pt_free();
 }
 
+// --history-from ... --protocol: the two views of renderBatched's --history-from as a host on the reference's three symbols renders them.
+// What is registered is what renderBatched registers -- the meshes; the textures under --history-albedo alone; no height map --, so the shim
+// is handed the scene without the rest.
+static void renderProtocol() {
+    if (!historyAlbedo) {
+        scene->textures.clear();
+        scene->geomTextures.assign(scene->geoms.size(), -1);
+    }
+    scene->geomBumps.assign(scene->geoms.size(), -1);
+    pathtraceKeepRenderer(true);
+    pathtraceTemporal(true);
+    if (historyAlbedo) pathtraceDemodulate(true);
+    const Camera after = renderState->camera;
+    PtCamera *cam = (PtCamera *)&renderState->camera;
+    cam->position.x = historyEye[0]; cam->position.y = historyEye[1]; cam->position.z = historyEye[2];
+    pathtraceFree();
+    pathtraceInit(scene);
+    for (int i = 1; i <= historyIterations; ++i) pathtrace(NULL, 0, i);
+    renderState->camera = after;        // the camera moved: the reference's restart
+    pathtraceFree();
+    pathtraceInit(scene);
+    const int total = (int)renderState->iterations;
+    while (iteration < total) {
+        iteration++;
+        pathtrace(NULL, 0, historyIterations + iteration);
+    }
+    saveImage();
+    saveDenoised();
+    pathtraceFree();                    // (parks; the library's exit handler frees)
+}
+
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place]] [--spatial-variance] [--demodulate] [--history-albedo]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo]\n", argv[0]);
         return 1;
     }
     try {
@@ -290,6 +327,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--noise-fraction") && i + 1 < argc) noiseFraction = (float)atof(argv[++i]);
         else if (!strcmp(argv[i], "--check-every") && i + 1 < argc) checkEvery = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--in-place")) inPlace = true;
+        else if (!strcmp(argv[i], "--protocol")) protocol = true;
         else if (!strcmp(argv[i], "--history-from") && i + 4 < argc) {
             historyFrom = true;
             for (int a = 0; a < 3; ++a) historyEye[a] = (float)atof(argv[i + 1 + a]);
@@ -311,6 +349,8 @@ int main(int argc, char **argv) {
     pathtraceExtras(lensRadius, focalDistance, directLighting);
     pathtraceMoments(denoiseVar);
     if (inPlace && !historyFrom) { fprintf(stderr, "--in-place needs --history-from\n"); return 1; }
+    if (protocol && !historyFrom) { fprintf(stderr, "--protocol needs --history-from\n"); return 1; }
+    if (protocol && inPlace) { fprintf(stderr, "--protocol and --in-place exclude each other\n"); return 1; }
     if (demodulate && (!denoiseVar || historyFrom)) { fprintf(stderr, "--demodulate needs --denoise-var and does not go with --history-from\n"); return 1; }
     pathtraceSpatialVariance(spatialVariance);
     pathtraceDemodulate(demodulate);
@@ -318,11 +358,12 @@ int main(int argc, char **argv) {
     width = renderState->camera.resolution.x;
     height = renderState->camera.resolution.y;
     const auto t0 = std::chrono::steady_clock::now();
-    if (batch > 1 || noiseTarget || historyFrom) renderBatched();
+    if (protocol) renderProtocol();
+    else if (batch > 1 || noiseTarget || historyFrom) renderBatched();
     else while (runHip()) {}
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("%d iterations of %dx%d, depth %d: %.3f s wall (init, %s and PNG included)\n", iteration, width, height,
-           renderState->traceDepth, s, batch > 1 || noiseTarget || historyFrom ? "one D2H copy" : "per-iteration D2H copy");
+           renderState->traceDepth, s, !protocol && (batch > 1 || noiseTarget || historyFrom) ? "one D2H copy" : "per-iteration D2H copy");
     delete scene;
     return 0;
 }

@@ -20,6 +20,22 @@ static bool extraMoments = false;                   // pathtraceMoments: PT_FLAG
 static bool extraSpatial = false;                   // pathtraceSpatialVariance: PT_FLAG_MOMENTS | PT_FLAG_SPATIAL_VARIANCE for the next pathtraceInit
 static bool extraDemod = false;                     // pathtraceDemodulate: PT_FLAG_MOMENTS | PT_FLAG_DEMODULATE for the next pathtraceInit
 static bool extraDisplay = false;                   // pathtraceDisplayFilter: PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER for the next pathtraceInit
+static bool extraTemporal = false;                  // pathtraceTemporal: PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL for the next pathtraceInit
+static bool extraKeep = false;                      // pathtraceKeepRenderer: pathtraceFree parks the renderer, pathtraceInit sets PT_FLAG_KEEP_RENDERER
+// a renderer of the default context exists (a pathtraceInit succeeded and pt_free has not been called since) / pathtraceFree has parked it
+static bool live = false, parked = false;
+
+// PT_AMD_KEEP_RENDERER=1 (or pathtraceKeepRenderer(true)): the reference's camera-move restart, pathtraceFree(); pathtraceInit(scene);
+// (src/main.cpp:91-95), keeps the renderer.  pathtraceFree only releases the page-locked registration of state.image and PARKS the renderer --
+// which goes on holding its device memory between Free and Init: pools, accumulators, tables, streams and events --, and the next pathtraceInit
+// calls the full pt_init with PT_FLAG_KEEP_RENDERER, so the library moves the camera in place where the scene, the options and everything
+// registered are the parked renderer's own, and runs the full call where they are not (include/pt_amd.h).  The image after every call is the
+// same bit for bit.  A parked renderer is freed by a pathtraceFree() called while it is parked, by a pathtraceFree() after the switch was
+// turned off, and by the library's exit handler.  The variable, where it is set, decides (0: off whatever the host called).
+static bool keepSwitch() {
+    if (const char *e = getenv("PT_AMD_KEEP_RENDERER")) return atoi(e) != 0;
+    return extraKeep;
+}
 
 static void checkPtError(int status, const char *msg) {
     if (status == PT_OK) return;
@@ -54,6 +70,16 @@ void pathtraceInit(Scene *scene) {
     bool demod = extraDemod;
     if (const char *e = getenv("PT_AMD_DEMODULATE")) demod = demod || atoi(e) != 0;
     if (demod) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_DEMODULATE;
+    // PT_AMD_TEMPORAL=1 (or pathtraceTemporal): temporal reprojection -- a pathtraceInit over a renderer that was NOT freed keeps the old view's
+    // samples as history, which pt_denoise_var and the display filter blend in.  That needs the switch above: without it pathtraceFree frees
+    // the renderer and the history with it.  With demodulation the history carries the albedo too.  Such a renderer traces nothing ahead
+    // (below): pt_init refuses PT_FLAG_TEMPORAL together with PT_FLAG_TRACE_AHEAD, so every pathtrace call traces its own iteration.
+    bool temporal = extraTemporal;
+    if (const char *e = getenv("PT_AMD_TEMPORAL")) temporal = temporal || atoi(e) != 0;
+    if (temporal) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL;
+    if (temporal && demod) opt.flags |= PT_FLAG_DEMOD_HISTORY;
+    const bool keep = keepSwitch();
+    if (keep) opt.flags |= PT_FLAG_KEEP_RENDERER;
     // The reference's host calls pathtrace(pbo, frame, iter) once per iteration with iter = 1, 2, 3, ... (src/main.cpp:97-103):
     // the library traces such a sequence in wavefront batches AHEAD of the calls (PT_FLAG_TRACE_AHEAD; same image after every
     // call, bit for bit), so a call costs a commit instead of eight small dependent launches.  A camera move goes through
@@ -64,6 +90,7 @@ void pathtraceInit(Scene *scene) {
     if (scene->state.iterations < (unsigned)(ahead > 0 ? ahead : 0)) ahead = (int)scene->state.iterations;
     if (ahead > PT_MAX_BATCH) ahead = PT_MAX_BATCH;
     if (demod) ahead = 1;               // (PT_FLAG_DEMODULATE is not for PT_FLAG_TRACE_AHEAD renderers)
+    if (temporal) ahead = 1;            // (nor is PT_FLAG_TEMPORAL)
     // A host written against the reference's pathtraceInit knows nothing of batches, so tracing ahead must never be the
     // reason an Init fails: the batch is clamped to the library's limits for this frame (pixels x batch <= 2^29 paths,
     // rows x padded width x batch < 2^30 tile slots: an 8192 x 8192 frame still traces 8 iterations ahead), and should the
@@ -150,7 +177,21 @@ void pathtraceInit(Scene *scene) {
                         "PT_AMD_DEVICES: a group renders headless\n");
         exit(EXIT_FAILURE);
     }
+    if (members >= 2 && temporal) {
+        fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: temporal reprojection (PT_AMD_TEMPORAL, pathtraceTemporal) is not for PT_AMD_DEVICES: "
+                        "a group keeps no second moments\n");
+        exit(EXIT_FAILURE);
+    }
+    if (members >= 2 && keep) {
+        fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: keeping the renderer (PT_AMD_KEEP_RENDERER, pathtraceKeepRenderer) is not for "
+                        "PT_AMD_DEVICES: a group re-initialises its members in place already\n");
+        exit(EXIT_FAILURE);
+    }
     if (members >= 2) {
+        if (parked) {                   // (a renderer parked before PT_AMD_DEVICES was set: the group takes its place)
+            pt_free();
+            live = parked = false;
+        }
         if (group && pt_group_size(group) != members) {
             pt_group_destroy(group);
             group = NULL;
@@ -186,6 +227,8 @@ void pathtraceInit(Scene *scene) {
         ahead /= 2;
     }
     checkPtError(status, "pathtraceInit");
+    live = !group;
+    parked = false;
     // state.image is owned by the Scene and lives from Init to Free: page-lock it for the per-iteration copy below
     // (an optimisation only; failure to register is not an error of the renderer)
     // (a group's read-back copies into the same buffer: the registration is process-wide, made through the default context)
@@ -219,11 +262,27 @@ void pathtraceSpatialVariance(bool on) { extraSpatial = on; }
 // The environment variable PT_AMD_DEMODULATE=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
 void pathtraceDemodulate(bool on) { extraDemod = on; }
 
+// ... nor this one: the next pathtraceInit sets PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL (include/pt_amd.h: "temporal reprojection"; with demodulation
+// PT_FLAG_DEMOD_HISTORY too) and traces nothing ahead.  History passes a pathtraceFree only with pathtraceKeepRenderer.  The environment variable
+// PT_AMD_TEMPORAL=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
+void pathtraceTemporal(bool on) { extraTemporal = on; }
+
+// ... nor this one: pathtraceFree parks the renderer instead of freeing it, and pathtraceInit lets the library move the camera in place
+// (keepSwitch above).  The environment variable PT_AMD_KEEP_RENDERER=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
+void pathtraceKeepRenderer(bool on) { extraKeep = on; }
+
 void pathtraceFree() {
     if (group) {
         pt_group_destroy(group);
         group = NULL;
     }
+    if (live && !parked && keepSwitch()) {
+        // state.image belongs to the host again (it may resize or release it before the next Init); everything else stays
+        checkPtError(pt_unpin_host(), "pathtraceFree");
+        parked = true;
+        return;
+    }
+    live = parked = false;
     pt_free();  // no-op when nothing was initialised (src/main.cpp:91-94 calls Free before the first Init)
 }
 
