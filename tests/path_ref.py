@@ -205,17 +205,19 @@ def uv(scene, hit):
 
 
 def cell(spec, u, v):
-    """spec = (texels per side, cells per side, margin in texels) of a square cell texture (row 0 = the top, v = 0 the bottom, repeating).
-    Returns the cell's index (row * cells + column) and a mask: within `margin` texels of a cell border, where the bilinear sampler may
-    blend two cells (it reads the two texels around u * size - 0.5: one cell from half a texel inside the border on)."""
-    size, cells, margin = spec
-    per = size / cells
-    x, y = (u - np.floor(u)) * size, (1 - (v - np.floor(v))) * size
-    y = np.where(y >= size, y - size, y)
-    cx, cy = np.floor(x / per).astype(int) % cells, np.floor(y / per).astype(int) % cells
-    nearx = np.abs(x / per - np.round(x / per)) * per < margin
-    neary = np.abs(y / per - np.round(y / per)) * per < margin
-    return cy * cells + cx, nearx | neary
+    """spec = (W, H, cx, cy, margin in texels) of a cell texture of W x H texels in cx x cy cells (row 0 = the top, v = 0 the bottom,
+    repeating); every entry a number or one value per hit, so that each hit may lie on another texture.  Returns the cell's index
+    (row * cx + column) and a mask: within `margin` texels of a cell border, where the bilinear sampler may blend two cells (it reads the
+    two texels around u * W - 0.5: one cell from half a texel inside the border on).  An axis of ONE cell has no border: the wrap meets
+    the same cell."""
+    W, H, cx, cy, margin = (np.asarray(s) for s in spec)
+    perx, pery = W / cx, H / cy
+    x, y = (u - np.floor(u)) * W, (1 - (v - np.floor(v))) * H
+    y = np.where(y >= H, y - H, y)
+    ix, iy = np.floor(x / perx).astype(int) % cx, np.floor(y / pery).astype(int) % cy
+    nearx = (cx > 1) & (np.abs(x / perx - np.round(x / perx)) * perx < margin)
+    neary = (cy > 1) & (np.abs(y / pery - np.round(y / pery)) * pery < margin)
+    return iy * cx + ix, nearx | neary
 
 
 def reflect(d, n):

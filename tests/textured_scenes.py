@@ -4,7 +4,11 @@ and the colour predicted.
 
 Every primitive carries a CELL texture: 4 x 4 cells of 32 x 32 texels, one colour per cell, every cell another colour.  The bilinear sampler
 returns a cell's colour exactly (a + (b - a) * fx with a == b) wherever its two texels lie in one cell, so the colour after a bounce is known
-to the bit although (u, v) is only known to float64 accuracy.  Four such textures are shared round the primitives (geom g: texture g % 4)."""
+to the bit although (u, v) is only known to float64 accuracy.  Four such textures are shared round the primitives (geom g: texture g % 4).
+
+The seeded family of tests/textured_fuzz_scenes.py takes the same step with a spec PER TEXTURE (sc.specs: W, H, cells across and down, margin;
+sc.cells their colours; sc.slopes every height map's ramp), unbound primitives (texel 1), face materials and vertex normals; a scene that
+names no specs, like the ones built here, has SPEC for every texture."""
 import os
 import types
 
@@ -15,7 +19,7 @@ from conftest import SCENES
 
 W, H, DEPTH = 96, 72, 6
 ITERS = (1, 37)
-SPEC = (128, 4, 1.0)                                                # texels per side, cells per side, margin in texels
+SPEC = (128, 128, 4, 4, 1.0)                                        # a texture's (W, H, cells across, cells down, margin in texels): path_ref.cell
 LENS = dict(lens_radius=0.3, focal_distance=10.0)
 STATE = ("first", "dof", "many", "sweptCubes", "mesh", "grouped", "tex", "bump", "plain")      # the bits of pt_test_bounce_form's state
 SLOPE_U, SLOPE_V = 0.5, 0.25                                        # the ramp's rise per unit of u and of v: unequal, so that swapped tangents show
@@ -30,17 +34,21 @@ def cell_colours():
 
 
 def cell_texture(colours):
-    size, cells, _ = SPEC
-    return np.repeat(np.repeat(colours.reshape(cells, cells, 3), size // cells, 0), size // cells, 1).copy()
+    return spec_texture(SPEC, colours)
 
 
-def ramp():
-    """height = SLOPE_U * u + SLOPE_V * v at the texel centres (multiples of 1 / 512: exact), so away from the wrap hu = scale * SLOPE_U
-    and hv = scale * SLOPE_V"""
-    size = SPEC[0]
-    a = np.arange(size, dtype=np.float32) / np.float32(size)
-    h = np.float32(SLOPE_U) * a[None, :] + np.float32(SLOPE_V) * a[::-1][:, None]
-    return np.repeat(h[:, :, None], 3, 2).copy()
+def spec_texture(spec, colours):
+    """the cell texture of `spec`: (H, W, 3), cell row * cx + column in colours[row * cx + column]"""
+    w, h, cx, cy, _ = spec
+    return np.repeat(np.repeat(np.asarray(colours, np.float32)[:cx * cy].reshape(cy, cx, 3), h // cy, 0), w // cx, 1).copy()
+
+
+def ramp(w=SPEC[0], h=SPEC[1], slope_u=SLOPE_U, slope_v=SLOPE_V):
+    """height = slope_u * u + slope_v * v at the texel centres of a w x h map (128 x 128: multiples of 1 / 512, exact), so away from the
+    wrap hu = scale * slope_u and hv = scale * slope_v whatever w and h are"""
+    au, av = np.arange(w, dtype=np.float32) / np.float32(w), np.arange(h, dtype=np.float32) / np.float32(h)
+    ht = np.float32(slope_u) * au[None, :] + np.float32(slope_v) * av[::-1][:, None]
+    return np.repeat(ht[:, :, None], 3, 2).copy()
 
 
 def _materials(pt):
@@ -122,16 +130,32 @@ def twin_renderer(orc, sc, lens):
     return ref
 
 
+def specs_of(sc):
+    """(textures, 5): every texture's (W, H, cx, cy, margin) -- sc.specs, or SPEC for each of a scene that names none"""
+    specs = getattr(sc, "specs", None)
+    return np.array([SPEC] * max(len(sc.textures), 1) if specs is None else specs, np.float64).reshape(-1, 5)
+
+
 def _classify(sc, o, d, white):
-    """cast + (u, v) + cell: the unambiguous hits (indices into o), their hit records, texture, cell, texel colour and (u, v)"""
+    """cast + (u, v) + cell: the unambiguous hits (indices into o), their hit records, texture, cell, texel colour and (u, v).  A scene
+    with sc.specs has a spec per texture, and its UNBOUND primitives (texture -1) carry the texel 1 and leave nothing out; a scene
+    without takes SPEC for every hit."""
     hit = pr.cast(sc, o, d)
     idx = np.flatnonzero((hit.prim >= 0) & ~hit.ambiguous)
     sub = pr.take(hit, idx)
     u, v, bad = pr.uv(sc, sub)
-    ci, border = pr.cell(SPEC, u, v)
     tex = sc.geom_textures[sub.prim]
-    texel = np.ones((len(idx), 3), np.float32) if white else sc.cells[tex, ci]
-    return idx, sub, tex, ci, texel, u, v, bad | border
+    if getattr(sc, "specs", None) is None:
+        ci, border = pr.cell(SPEC, u, v)
+        bound = np.ones(len(idx), bool)
+    else:
+        bound = tex >= 0
+        sp = specs_of(sc)[np.maximum(tex, 0)]
+        ci, border = pr.cell((sp[:, 0], sp[:, 1], sp[:, 2].astype(int), sp[:, 3].astype(int), sp[:, 4]), u, v)
+    texel = np.ones((len(idx), 3), np.float32)
+    if not white:
+        texel[bound] = sc.cells[tex[bound], ci[bound]]
+    return idx, sub, tex, ci, texel, u, v, (bad | border) & bound
 
 
 def step(sc, prev, cur, white=False):
@@ -148,13 +172,27 @@ def step(sc, prev, cur, white=False):
         bumped = sc.geom_bumps[sub.prim] >= 0
         Pu, Pv = pr.tangents(sc, sub)
         s = sc.bump_scales[sub.prim].astype(np.float64)
-        Ns, shaky = pr.tilt(sub.N, Pu, Pv, s * SLOPE_U, s * SLOPE_V, sub.outside, sub.d)
-        Ns = np.where(bumped[:, None], Ns, sub.N)
-        # the ramp's wrap: the central differences reach one texel to each side and the sampler half a texel further
-        x, y = (u - np.floor(u)) * SPEC[0], (v - np.floor(v)) * SPEC[0]
-        wrap = (np.minimum(x, SPEC[0] - x) < 2.5) | (np.minimum(y, SPEC[0] - y) < 2.5)
-        out = out | (bumped & (shaky | wrap))
+        # every height map a ramp: its slopes (sc.slopes per texture; SLOPE_U, SLOPE_V where the scene names none) and its own W and H
+        hmap = np.maximum(sc.geom_bumps[sub.prim], 0)
+        slopes = getattr(sc, "slopes", None)
+        su, sv = (SLOPE_U, SLOPE_V) if slopes is None else (np.asarray(slopes, np.float64)[hmap, 0], np.asarray(slopes, np.float64)[hmap, 1])
+        hw, hh = specs_of(sc)[hmap, 0], specs_of(sc)[hmap, 1]
+        # (the tilt starts from the normal the hit is shaded with: a mesh's blended vertex normal where it has them)
+        Ns, shaky = pr.tilt(sub.Ns, Pu, Pv, s * su, s * sv, sub.outside, sub.d)
+        Ns = np.where(bumped[:, None], Ns, sub.Ns)
+        # the ramp's wrap: the central differences reach one texel to each side and the sampler half a texel further; the sphere's seam
+        # and poles, where (u, v) is singular
+        badb = pr.uv(sc, sub)[2]
+        x, y = (u - np.floor(u)) * hw, (v - np.floor(v)) * hh
+        wrap = (np.minimum(x, hw - x) < 2.5) | (np.minimum(y, hh - y) < 2.5)
+        flat = (s * su == 0) & (s * sv == 0)                               # (a zero scale, a constant map: the hit stays unbumped whatever (u, v))
+        out = out | (bumped & ~flat & (shaky | wrap | badb))
+    elif sub.blended.any():
+        Ns = sub.Ns
     want, mirror, amb, side, off = pr.predict_colour(sc, sub, c0[j][idx], texel, o1[idx], d1[idx], Ns)
+    # a half mirror with an exponent samples a lobe about the mirror's direction: its two branches cannot be told apart from the new state
+    mats = sc.materials[sub.mat]
+    amb = amb | ((mats[mats.dtype.names[1]] > 0) & (mats["hasReflective"] > 0) & (mats["hasRefractive"] == 0))
     keep = ~(out | amb)
     r = pr.take(sub, keep)
     return types.SimpleNamespace(idx=idx[keep], hit=r, col=c0[j][idx][keep], texel=texel[keep], want=want[keep], mirror=mirror[keep], side=side[keep], off=off[keep], tex=tex[keep], cell=ci[keep],
