@@ -185,15 +185,20 @@ struct History {
     bool albedo = false;            // the renderer that made it carried PT_FLAG_DEMOD_HISTORY: ha[cur] is live too
 };
 
-// (it keeps the scalars of the scene's plan -- cam, prm, P, nLocal, flags, the flags that pick the forms of k_bounce, the sizes -- as its base)
-struct State : PlanScalars {
-    bool init = false;
-    int device = 0;
-    hipStream_t stream = nullptr;   // the caller's stream: commits, PBO conversion, readback
-    float *image = nullptr;         // the accumulator the kernels add to: the caller's (PtOptions::accum_dev, never freed here), or ...
-    DevBuf<float> imageOwn;         // ... the renderer's own
-    DevBuf<float> moments;          // PT_FLAG_MOMENTS: per pixel the sum of its samples' squared luminance (k_commit<true>); always the renderer's own
-    Slot slot[kMaxSlots];
+// How a scene table differs from the plain one -- a buffer where the plan's vector is not empty, of its size, refreshed by a camera move
+// whose plan holds other bytes.
+struct TableRule {
+    bool evenEmpty = false;         // a buffer even for an empty table: a kernel may be handed its pointer
+    size_t slack = 0;               // elements allocated behind the table's, left uninitialised
+    bool cameraInvariant = false;   // no camera changes it: pt_init uploads it and drops the host's copy, a move compares its size alone
+    // the elements pt_init allocates for a table of n (DevBuf::upload)
+    size_t allocated(size_t n) const { return n || evenEmpty ? std::max<size_t>(n + slack, 1) : 0; }
+};
+
+// The scene's tables on the device, each as the plan made it (ScenePlan).  A table is named three times in this file: its buffer here, its
+// line in for_each -- the plan's vector it comes from and its rule -- and its pointer in fill(); pt_init and the camera move are actions
+// handed to for_each.
+struct SceneTables {
     DevBuf<GeomDev> dgeoms;
     DevBuf<unsigned char> dGeomHit; // GeomHitDev[ngeoms], as the kernels stage it in LDS (scenes that are not sphere-heavy; those: one image of their tables)
     DevBuf<float> dRows;            // sphere-heavy scenes of hundreds of primitives: the matrix rows that do not go to LDS (BounceArgs::rows)
@@ -214,6 +219,75 @@ struct State : PlanScalars {
     // bump-mapped scenes (k_bounce<..., BUMP>): BounceArgs::bumpGeom / bumpUV / bumpTan
     DevBuf<ptd::BumpGeom> dBumpGeom;
     DevBuf<float4> dBumpUV, dBumpTan;
+    // scenes with meshes, whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
+    DevBuf<int> dWalkIdx, dWalkRowOff;
+    DevBuf<WalkMesh> dWalkMeshRows;    // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows)
+
+    // f(buffer, the held plan's vector -- nullptr without a held plan --, the new plan's vector, the table's rule) for every table, in
+    // pt_init's order of uploads; stops at the first f that does not answer PT_OK.  mesh, grouped: the new plan's (a scene without
+    // meshes has no walks' tables at all, an ungrouped one no groups' table).
+    template <class F>
+    int for_each(const ScenePlan *held, ScenePlan &now, bool mesh, bool grouped, F &&f) {
+        const ScenePlan &h = held ? *held : now;
+        const auto of = [held](const auto &v) { return held ? &v : nullptr; };
+        const TableRule plain{}, evenEmpty{true}, invariant{false, 0, true};
+        PTCHECK(f(dgeoms, of(h.hg), now.hg, plain));
+        PTCHECK(f(dmats, of(h.hm), now.hm, plain));
+        PTCHECK(f(dGeomHit, of(h.geomHit), now.geomHit, plain));
+        PTCHECK(f(dRows, of(h.rowsGlobal), now.rowsGlobal, plain));
+        PTCHECK(f(dwalls, of(h.hw), now.hw, plain));
+        PTCHECK(f(dTexGeom, of(h.texGeom), now.texGeom, plain));
+        PTCHECK(f(dTexDesc, of(h.texDesc), now.texDesc, plain));
+        PTCHECK(f(dTexels, of(h.texels), now.texels, invariant));
+        PTCHECK(f(dTexUV, of(h.texUV), now.texUV, plain));
+        PTCHECK(f(dBumpGeom, of(h.bumpGeom), now.bumpGeom, plain));
+        PTCHECK(f(dBumpUV, of(h.bumpUV), now.bumpUV, plain));
+        PTCHECK(f(dBumpTan, of(h.bumpTan), now.bumpTan, plain));
+        if (mesh) {
+            PTCHECK(f(dMeshRecs, of(h.meshRecs), now.meshRecs, TableRule{true, 4, true}));     // (+ 4: a walk may read the record behind the last one)
+            PTCHECK(f(dWalkIdx, of(h.walkIdx), now.walkIdx, evenEmpty));
+            PTCHECK(f(dWalkMeshRows, of(h.walkMeshRows), now.walkMeshRows, evenEmpty));
+        }
+        PTCHECK(f(dSphCull, of(h.sc), now.sc, plain));
+        if (grouped) PTCHECK(f(dSphGroups, of(h.groups), now.groups, evenEmpty));
+        PTCHECK(f(dRowOff, of(h.cc.rowOff), now.cc.rowOff, plain));
+        PTCHECK(f(dRowIdx, of(h.cc.rowIdx), now.cc.rowIdx, plain));
+        PTCHECK(f(dCamPix, of(h.cl.pix), now.cl.pix, plain));
+        PTCHECK(f(dCamWave, of(h.cl.wave), now.cl.wave, plain));
+        PTCHECK(f(dCamSigIdx, of(h.cl.sigIdx), now.cl.sigIdx, plain));
+        PTCHECK(f(dCamFace, of(h.cl.face), now.cl.face, plain));
+        PTCHECK(f(dWalkRowOff, of(h.walkRowOff), now.walkRowOff, plain));
+        PTCHECK(f(dClassIdx, of(h.classIdx), now.classIdx, plain));
+        return PT_OK;
+    }
+
+    // a launch's pointers to the tables (a table the scene does not have: null, and its kernels do not ask)
+    void fill(BounceArgs &ba) const {
+        ba.ggeoms = dgeoms.p; ba.gmats = dmats.p; ba.ghit = reinterpret_cast<const float4 *>(dGeomHit.p);
+        ba.sphCull = dSphCull.p; ba.classIdx = dClassIdx.p;
+        ba.rowOff = dRowOff.p; ba.rowIdx = dRowIdx.p;
+        ba.camPix = dCamPix.p; ba.camWave = dCamWave.p; ba.camSigIdx = dCamSigIdx.p; ba.camFace = dCamFace.p;
+        ba.walls = dwalls.p;
+        ba.meshRecs = reinterpret_cast<const float4 *>(dMeshRecs.p);
+        ba.rows = reinterpret_cast<const float4 *>(dRows.p);
+        ba.walkIdx = dWalkIdx.p; ba.walkRowOff = dWalkRowOff.p;
+        ba.walkMeshRows = reinterpret_cast<const float4 *>(dWalkMeshRows.p);
+        ba.sphGroups = dSphGroups.p;
+        ba.texGeom = dTexGeom.p; ba.texDesc = dTexDesc.p; ba.texels = dTexels.p; ba.texUV = dTexUV.p;
+        ba.bumpGeom = dBumpGeom.p; ba.bumpUV = dBumpUV.p; ba.bumpTan = dBumpTan.p;
+    }
+};
+
+// (it keeps the scalars of the scene's plan -- cam, prm, P, nLocal, flags, the flags that pick the forms of k_bounce, the sizes -- as its base)
+struct State : PlanScalars {
+    bool init = false;
+    int device = 0;
+    hipStream_t stream = nullptr;   // the caller's stream: commits, PBO conversion, readback
+    float *image = nullptr;         // the accumulator the kernels add to: the caller's (PtOptions::accum_dev, never freed here), or ...
+    DevBuf<float> imageOwn;         // ... the renderer's own
+    DevBuf<float> moments;          // PT_FLAG_MOMENTS: per pixel the sum of its samples' squared luminance (k_commit<true>); always the renderer's own
+    Slot slot[kMaxSlots];
+    SceneTables tab;                // the scene's tables
     // the denoiser (pt_denoise.h), all allocated on first use: the guide buffers of iteration dnGuideIter (0: none yet), the float4 images
     // the filter's levels pass on, and the packed RGB the last level writes.  (PT_FLAG_DISPLAY_FILTER: pt_init allocates the four float4
     // images and dnRgba -- what the display path touches -- so that pt_iterate allocates nothing.)
@@ -232,11 +306,8 @@ struct State : PlanScalars {
     DevBuf<float> noiseMap;
     uint32_t *noiseHost = nullptr;      // 2 x 2 words
     hipEvent_t noiseEv[2] = {nullptr, nullptr};
-    // ... whose walks run ahead of every bounce launch (k_mesh_walk): the meshes alone per queue class / in all / per image row
-    DevBuf<int> dWalkIdx, dWalkRowOff;
-    DevBuf<WalkMesh> dWalkMeshRows;    // ptk::WalkMesh per mesh (BounceArgs::walkMeshRows)
-    int gridWalk = 0, gridWalkFirst = 0;
-    int grid = 0;           // persistent grid of k_bounce<false>
+    int gridWalk = 0, gridWalkFirst = 0;      // the grids of the meshes' walks (k_mesh_walk) ...
+    int grid = 0;           // ... the persistent grid of k_bounce<false>
     int gridFirst = 0;      // ... and of k_bounce<true> (its own register budget, hence its own residency)
     const void *kernFirst = nullptr, *kernNext = nullptr;   // the forms of k_bounce the camera-ray launch / the later ones take (bounce_form)
     long long iterations = 0;
@@ -266,19 +337,15 @@ struct State : PlanScalars {
     // frame reduce reads), and the event -- the reduce that last read that buffer -- the commit has to wait for first.  Set per call.
     float *snapTarget = nullptr;
     hipEvent_t snapWait = nullptr;
-    // triangle soups registered by pt_set_meshes, consumed by the next pt_init (kept across pt_free: the reference's
-    // Free -> Init restart protocol re-initialises the same scene)
-    std::vector<ptm::HostMesh> meshes;
-    // ... and so are the textures and their bindings registered by pt_set_textures
-    std::vector<HostTexture> textures;
-    std::vector<HostTexBinding> texBindings;
-    // ... and the height maps registered by pt_set_bump_maps (texture: an index into `textures`)
-    std::vector<HostBumpBinding> bumpBindings;
+    // what the pt_set_* calls last registered, consumed by the next pt_init (kept across pt_free: the reference's Free -> Init restart
+    // protocol re-initialises the same scene), and what was registered when the renderer was initialised: the scene its camera moves
+    // plan, whatever has been registered since
+    Registered reg, initReg;
     // ... and, across a pt_init over the live renderer only, the last view's samples (PT_FLAG_TEMPORAL)
     History hist;
     // the camera move: what the renderer was initialised with -- pt_init's scene arguments and effective options (a few hundred bytes per
-    // primitive) -- and the plan it holds: the tables as the device has them (texels and mesh records, which no camera changes, by their
-    // sizes alone), so that a move uploads only the tables whose bytes differ
+    // primitive) -- and the plan it holds: the tables as the device has them (but the camera-invariant ones, whose buffers say their
+    // sizes), so that a move uploads only the tables whose bytes differ
     std::vector<PtGeom> inGeoms;
     std::vector<PtMaterial> inMats;
     int inDepth = 0;
@@ -289,13 +356,6 @@ struct State : PlanScalars {
     hipStream_t camStream = nullptr;
     DevBuf<uint32_t> camPixScratch;
     DevBuf<signed char> camFaceScratch;
-    size_t heldTexels = 0, heldMeshRecs = 0;
-    // ... and what was registered when it was initialised, where a pt_set_* call has registered something else since (moved here by that
-    // call; null: the registered ones above are still the renderer's)
-    std::unique_ptr<std::vector<ptm::HostMesh>> initMeshes;
-    std::unique_ptr<std::vector<HostTexture>> initTextures;
-    std::unique_ptr<std::vector<HostTexBinding>> initTexBindings;
-    std::unique_ptr<std::vector<HostBumpBinding>> initBumpBindings;
 };
 
 // Renderer instances.  The reference keeps its renderer in file-static globals (src/pathtrace.cu:70-71: one per process, not
@@ -446,21 +506,12 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     const bool lastBits = R().many && !R().mesh && R().prm.sphOMax > 0.0f && R().prm.emittersBinned;
     if (lastBits && nextIsLast) ba.tile.hot |= kHotWritesLastBits;
     if (lastBits && lastBounce && depth > 1) ba.tile.hot |= kHotReadsLastBits;
-    ba.ctrl = sl.ctrl.p; ba.ggeoms = R().dgeoms.p; ba.gmats = R().dmats.p; ba.ghit = reinterpret_cast<const float4 *>(R().dGeomHit.p); ba.contrib = contrib; ba.hitMask = sl.hitMask.p;
-    ba.sphCull = R().dSphCull.p; ba.classIdx = R().dClassIdx.p;
-    ba.rowOff = R().dRowOff.p; ba.rowIdx = R().dRowIdx.p;
-    ba.camPix = R().dCamPix.p; ba.camWave = R().dCamWave.p; ba.camSigIdx = R().dCamSigIdx.p; ba.camFace = R().dCamFace.p;
-    ba.walls = R().dwalls.p;
-    ba.meshRecs = reinterpret_cast<const float4 *>(R().dMeshRecs.p);
+    ba.ctrl = sl.ctrl.p; ba.contrib = contrib; ba.hitMask = sl.hitMask.p; ba.meshHit = sl.meshHit.p;
     ba.hostFault = R().hostFaultDev;
-    ba.rows = reinterpret_cast<const float4 *>(R().dRows.p);
-    ba.meshHit = sl.meshHit.p; ba.walkIdx = R().dWalkIdx.p; ba.walkRowOff = R().dWalkRowOff.p;
+    R().tab.fill(ba);
     memcpy(ba.walkClassOff, R().walkClassOff, sizeof ba.walkClassOff);
     ba.walkAll0 = R().walkAll0; ba.walkAll1 = R().walkAll1;
-    ba.walkMeshRows = reinterpret_cast<const float4 *>(R().dWalkMeshRows.p); ba.walkMeshLds = R().walkMeshLds;
-    ba.sphGroups = R().dSphGroups.p;
-    ba.texGeom = R().dTexGeom.p; ba.texDesc = R().dTexDesc.p; ba.texels = R().dTexels.p; ba.texUV = R().dTexUV.p;
-    ba.bumpGeom = R().dBumpGeom.p; ba.bumpUV = R().dBumpUV.p; ba.bumpTan = R().dBumpTan.p;
+    ba.walkMeshLds = R().walkMeshLds;
     void *kargs[] = {&ba};
     const bool first = depth == 1;
     // scenes with meshes: the walks of this bounce's rays, ahead of it (pt_mesh_walk.h)
@@ -771,8 +822,8 @@ int ensure_guides(int guideIter, float *ms) {
         HIPCHECK(hipEventRecord(e0, R().stream));
     }
     R().dnGuideIter = 0;
-    hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), stackBytes, R().stream, R().prm, R().dgeoms.p,
-                       reinterpret_cast<const float4 *>(R().dMeshRecs.p), guideIter, R().dnPosT.p, R().dnNrmId.p);
+    hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), stackBytes, R().stream, R().prm, R().tab.dgeoms.p,
+                       reinterpret_cast<const float4 *>(R().tab.dMeshRecs.p), guideIter, R().dnPosT.p, R().dnNrmId.p);
     HIPCHECK(hipGetLastError());
     if (ms) {
         HIPCHECK(hipEventRecord(e1, R().stream));
@@ -1016,10 +1067,10 @@ int albedo_launch(int first, int count) {
     const State &S = R();
     AlbedoArgs A;
     A.prm = S.prm;
-    A.ggeoms = S.dgeoms.p; A.gmats = S.dmats.p;
-    A.meshRecs = reinterpret_cast<const float4 *>(S.dMeshRecs.p);
-    A.texGeom = S.tex ? S.dTexGeom.p : nullptr;       // (a scene without a bound texture has no table)
-    A.texDesc = S.dTexDesc.p; A.texels = S.dTexels.p; A.texUV = S.dTexUV.p;
+    A.ggeoms = S.tab.dgeoms.p; A.gmats = S.tab.dmats.p;
+    A.meshRecs = reinterpret_cast<const float4 *>(S.tab.dMeshRecs.p);
+    A.texGeom = S.tex ? S.tab.dTexGeom.p : nullptr;       // (a scene without a bound texture has no table)
+    A.texDesc = S.tab.dTexDesc.p; A.texels = S.tab.dTexels.p; A.texUV = S.tab.dTexUV.p;
     A.firstIter = first; A.count = count;
     A.asum = S.albedo.p;
     hipLaunchKernelGGL(k_albedo, dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), guide_stack_bytes(), S.stream, A);
@@ -1210,7 +1261,7 @@ namespace {
 void free_renderer(bool keepHistory) {
     if (!keepHistory) R().hist = History();        // (pt_init alone keeps it: a re-initialisation of a PT_FLAG_TEMPORAL renderer)
     // pathtraceFree before the first Init (src/main.cpp:91-94) must be a no-op
-    if (!R().init && !R().image && !R().dgeoms.p && R().nslots == 0 && !R().hostFault && !R().pinnedHost) return;
+    if (!R().init && !R().image && !R().tab.dgeoms.p && R().nslots == 0 && !R().hostFault && !R().pinnedHost) return;
     if (R().device >= 0 && R().nslots > 0) (void)hipSetDevice(R().device);     // (a host that switched devices in between)
     for (int i = 0; i < kMaxSlots; ++i)
         if (R().slot[i].stream) (void)hipStreamSynchronize(R().slot[i].stream);
@@ -1233,18 +1284,12 @@ void free_renderer(bool keepHistory) {
     for (hipEvent_t e : R().noiseEv)
         if (e) (void)hipEventDestroy(e);
     // ... and every device table: the move-assignment below releases what the DevBufs of State and its Slots hold
-    {   // (the registered meshes, textures and height maps outlive the renderer: see State::meshes)
-        std::vector<ptm::HostMesh> keep = std::move(R().meshes);
-        std::vector<HostTexture> keepTex = std::move(R().textures);
-        std::vector<HostTexBinding> keepBind = std::move(R().texBindings);
-        std::vector<HostBumpBinding> keepBump = std::move(R().bumpBindings);
+    {   // (what is registered outlives the renderer: see State::reg)
+        const Registered keep = R().reg;
         History keepHist = std::move(R().hist);
         R() = State();
         R().hist = std::move(keepHist);
-        R().meshes = std::move(keep);
-        R().textures = std::move(keepTex);
-        R().texBindings = std::move(keepBind);
-        R().bumpBindings = std::move(keepBump);
+        R().reg = keep;
     }
 }
 
@@ -1277,7 +1322,7 @@ int size_launches(State &S) {
     // (the packed work list of camera rays has no column bands: nothing to rotate)
     const KParams &k = S.prm;
     S.prm.tilesPerRow = 0;
-    if (k.Wp / kBlock > 1 && S.dCamPix.p == nullptr) {
+    if (k.Wp / kBlock > 1 && S.tab.dCamPix.p == nullptr) {
         const int perRow = k.Wp / kBlock;
         auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
         if (gcd(perRow, kSub) == 1) {
@@ -1293,385 +1338,41 @@ int size_launches(State &S) {
     return PT_OK;
 }
 
-// ---- the camera move ------------------------------------------------------------------------------------------------------------------------
-// which way the calling thread's last camera move went (pt_test_last_camera_move): fast 1 / 0, -1 before the first move or after a
-// refusal; the tables and bytes the fast path uploaded
-struct CameraMove { int fast = -1, tables = 0; long long bytes = 0; };
-thread_local CameraMove t_lastMove;
-// PT_FLAG_KEEP_RENDERER: why the calling thread's last flagged full call did not take the move's path (keep_renderer_mismatch's answer, or
-// that there was no renderer; null: it did, or there has been no such call), and the mark of the move's own full call inside, which
-// carries the renderer's options -- the flag with them -- and must not be compared again
-thread_local const char *t_keepWhy = nullptr;
-thread_local bool t_fullCallInside = false;
-
-// The work list's face certificates on the device, between build_camera_list's two passes: the pixel words of the one-cube groups whose
-// cube is CubeCert::ok go up as one array, k_camera_faces runs once per group -- the cube is uniform per group: a kernel argument -- and
-// the bytes come back as CameraGroups::faces.  pix / face: scratch buffers of the caller's, grown where needed; ms (or NULL): the kernels'
-// time by HIP events.
-int camera_faces_device(CameraGroups &G, const CameraResolve &cr, hipStream_t st, DevBuf<uint32_t> &pix, DevBuf<signed char> &face, float *ms) {
-    if (ms) *ms = 0.0f;
-    struct Run { size_t group, off, n; int cube; };
-    std::vector<Run> runs;
-    size_t total = 0;
-    for (size_t s = 0; s < G.groups.size(); ++s) {
-        const int cube = camera_group_cube(G, s, cr);
-        if (cube < 0 || G.groups[s].empty()) continue;
-        runs.push_back({s, total, G.groups[s].size(), cube});
-        total += G.groups[s].size();
-    }
-    if (!total) return PT_OK;
-    std::vector<uint32_t> words(total);
-    for (const Run &r : runs) memcpy(words.data() + r.off, G.groups[r.group].data(), r.n * sizeof(uint32_t));
-    if (pix.cap < total) PTCHECK(pix.alloc(total + total / 4));
-    if (face.cap < total) PTCHECK(face.alloc(total + total / 4));
-    EventSet es;
-    HIPCHECK(hipMemcpyAsync(pix.p, words.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    if (ms) {
-        HIPCHECK(hipEventCreate(&es.ev[0]));
-        HIPCHECK(hipEventCreate(&es.ev[1]));
-        HIPCHECK(hipEventRecord(es.ev[0], st));
-    }
-    for (const Run &r : runs) {
-        CameraFacesArgs A;
-        A.cube = cr.cube[(size_t)r.cube];
-        A.basis = cr;
-        A.pix = pix.p + r.off;
-        A.face = face.p + r.off;
-        A.n = (int)r.n;
-        hipLaunchKernelGGL(k_camera_faces, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, st, A);
-    }
-    HIPCHECK(hipGetLastError());
-    if (ms) HIPCHECK(hipEventRecord(es.ev[1], st));
-    std::vector<signed char> bytes(total);
-    HIPCHECK(hipMemcpyAsync(bytes.data(), face.p, total, hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    if (ms) HIPCHECK(hipEventElapsedTime(ms, es.ev[0], es.ev[1]));
-    for (const Run &r : runs) {
-        std::vector<int> &f = G.faces[r.group];
-        f.resize(r.n);
-        for (size_t i = 0; i < r.n; ++i) {
-            const int v = bytes[r.off + i];
-            if (v < -1 || v > 5) return fail(PT_ERR_DEVICE, "pt_init (camera move): k_camera_faces answered %d", v);
-            f[i] = v;
-        }
-    }
-    return PT_OK;
+// The old view of a renderer that goes (pt_init) or moves on (the camera move), keepHistory: the history is to live on.  Is a capture due?
+// Not without committed samples: the history lives on as it is.  And not for an old view whose scene k_gbuffer cannot trace -- a mesh
+// hierarchy deeper than its 64 KB of stacks, the one thing pt_gbuffer answers PT_ERR_INVALID to: it has no guides to reproject through, the
+// history ends there (keepHistory is cleared), and the call goes on.
+bool capture_due(bool &keepHistory) {
+    if (keepHistory && R().committed >= 1 && guide_stack_bytes() > 64 * 1024) keepHistory = false;
+    return keepHistory && R().committed >= 1;
 }
 
-// A table of the renderer against the new plan's: left alone where the device holds these very bytes, released where the plan has none
-// (pt_init leaves such a table without a buffer, and the kernels ask), written in place where it fits, reallocated where it grew.  The
-// copy is enqueued on `st` from `now`, which the caller keeps until the stream has been waited for.
-template <typename T>
-int refresh_table(DevBuf<T> &buf, const std::vector<T> &heldT, const std::vector<T> &now, bool keepEmpty, hipStream_t st, CameraMove &mv) {
-    if (now.empty() && !keepEmpty) { buf.release(); return PT_OK; }
-    const bool same = buf.p && heldT.size() == now.size() && (now.empty() || !memcmp(heldT.data(), now.data(), now.size() * sizeof(T)));
-    if (same) return PT_OK;
-    if (!buf.p || buf.cap < now.size()) PTCHECK(buf.alloc(now.size() + now.size() / 4));
-    if (!now.empty()) HIPCHECK(hipMemcpyAsync(buf.p, now.data(), now.size() * sizeof(T), hipMemcpyHostToDevice, st));
-    mv.tables += 1;
-    mv.bytes += (long long)(now.size() * sizeof(T));
-    return PT_OK;
+// ... and the capture where it is due: the old view becomes the context's history.  What is left to fail in it is a HIP call: PT_ERR_HIP,
+// which leaves the context without a renderer like every other one of pt_init's.  who: the message's prefix.
+int retire_view(bool &keepHistory, const char *who) {
+    if (!capture_due(keepHistory)) return PT_OK;
+    const int rc = capture_history();
+    if (!rc) return PT_OK;
+    free_renderer();
+    return rc == PT_ERR_INVALID ? fail(PT_ERR_HIP, "%s: the capture of the old view failed: %s", who, std::string(g_err).c_str()) : rc;
 }
 
-// pt_init over the live renderer with the scene it was initialised with: the camera move's slow path.  What was registered at that pt_init
-// is put back for the call where something else has been registered since, and what has been registered since stays registered behind it.
-int reinit_with_camera(const PtCamera &cam) {
-    State &S = R();
-    const std::vector<PtGeom> geoms = S.inGeoms;
-    const std::vector<PtMaterial> mats = S.inMats;
-    const int depth = S.inDepth;
-    const PtOptions o = S.inOpts;
-    auto initMeshes = std::move(S.initMeshes);
-    auto initTextures = std::move(S.initTextures);
-    auto initTexBindings = std::move(S.initTexBindings);
-    auto initBumpBindings = std::move(S.initBumpBindings);
-    if (initMeshes) std::swap(*initMeshes, S.meshes);
-    if (initTextures) std::swap(*initTextures, S.textures);
-    if (initTexBindings) std::swap(*initTexBindings, S.texBindings);
-    if (initBumpBindings) std::swap(*initBumpBindings, S.bumpBindings);
-    t_fullCallInside = true;
-    const int rc = pt_init(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), depth, &o);
-    t_fullCallInside = false;
-    const std::string err = g_err;
-    State &N = R();
-    if (initMeshes) std::swap(*initMeshes, N.meshes);
-    if (initTextures) std::swap(*initTextures, N.textures);
-    if (initTexBindings) std::swap(*initTexBindings, N.texBindings);
-    if (initBumpBindings) std::swap(*initBumpBindings, N.bumpBindings);
-    if (N.init) {
-        N.initMeshes = std::move(initMeshes);
-        N.initTextures = std::move(initTextures);
-        N.initTexBindings = std::move(initTexBindings);
-        N.initBumpBindings = std::move(initBumpBindings);
-    }
-    g_err = err;
-    return rc;
-}
-
-// PT_FLAG_KEEP_RENDERER on a full call: the call against the live renderer's copies of its own (pt_scene_plan.h: keep_renderer_mismatch).
-// What is registered now and what the renderer was initialised with are one object while no pt_set_* call has come in between.
-const char *keep_mismatch(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions &o) {
-    State &S = R();
-    if (!S.init) return "no live renderer";
-    if (!cam) return "camera";
-    const InitCall now{geoms, ngeoms, mats, nmats, traceDepth, &o, cam->resolution[0], cam->resolution[1], {&S.meshes, &S.textures, &S.texBindings, &S.bumpBindings}};
-    const InitCall then{S.inGeoms.data(), (int)S.inGeoms.size(), S.inMats.data(), (int)S.inMats.size(), S.inDepth, &S.inOpts, S.prm.W, S.prm.H,
-                        {S.initMeshes ? S.initMeshes.get() : &S.meshes, S.initTextures ? S.initTextures.get() : &S.textures,
-                         S.initTexBindings ? S.initTexBindings.get() : &S.texBindings, S.initBumpBindings ? S.initBumpBindings.get() : &S.bumpBindings}};
-    return keep_renderer_mismatch(now, then);
-}
-
-int set_camera(const PtCamera *cam) {
-    t_lastMove = CameraMove();
-    if (!cam) return fail(PT_ERR_INVALID, "pt_init (camera move): null camera");
-    if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_init (camera move) before pt_init: there is no renderer whose scene it could name");
-    State &S = R();
-    if (cam->resolution[0] != S.prm.W || cam->resolution[1] != S.prm.H)
-        return fail(PT_ERR_INVALID, "pt_init (camera move): the camera's resolution %d x %d is not the renderer's %d x %d (pt_init makes a renderer of another size)",
-                    cam->resolution[0], cam->resolution[1], S.prm.W, S.prm.H);
-    const PtCamera camNew = *cam;        // (the caller may hand in the camera of a scene this call outlives)
-    if (S.device >= 0) HIPCHECK(hipSetDevice(S.device));
-    // 1. the plan for the new camera, the certificates of its work list on the device; a scene that is refused has touched nothing
-    if (!S.camStream) HIPCHECK(hipStreamCreateWithFlags(&S.camStream, hipStreamNonBlocking));
-    std::unique_ptr<ScenePlan> planPtr(new ScenePlan);
-    ScenePlan &plan = *planPtr;
-    {
-        SceneIn in{&camNew, S.inGeoms.data(), (int)S.inGeoms.size(), S.inMats.data(), (int)S.inMats.size(), S.inDepth, S.inOpts,
-                   S.initMeshes ? *S.initMeshes : S.meshes, S.initTextures ? *S.initTextures : S.textures,
-                   S.initTexBindings ? *S.initTexBindings : S.texBindings, S.initBumpBindings ? *S.initBumpBindings : S.bumpBindings};
-        in.faces = [&S](CameraGroups &G, const CameraResolve &cr) { return camera_faces_device(G, cr, S.camStream, S.camPixScratch, S.camFaceScratch, nullptr); };
-        PTCHECK(plan_scene(in, plan));
-    }
-    const void *kernFirst = nullptr, *kernNext = nullptr;
-    PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
-    PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
-    // 2. drain the renderer's streams, as free_renderer does
-    for (int i = 0; i < S.nslots; ++i) (void)hipStreamSynchronize(S.slot[i].stream);
-    (void)hipStreamSynchronize(S.stream);
-    // 3. does the plan need the allocations the renderer holds?  (It does unless planning changes: none of these sizes depends on the
-    // camera.)  A renderer that carries a sticky device fault is rebuilt like any other: pt_init.
-    const bool faulted = S.hostFault && *(volatile uint32_t *)S.hostFault != 0u;
-    const bool sameAllocations =
-        S.held && kernFirst == S.kernFirst && kernNext == S.kernNext && plan.mesh == S.mesh && plan.dof == S.dof && plan.walkMeshLds == S.walkMeshLds &&
-        plan.flags == S.flags && plan.nslots == S.nslots && plan.maxBatch == S.maxBatch && plan.poolCap == S.poolCap && plan.poolChunks == S.poolChunks &&
-        plan.prm.chunkShift == S.prm.chunkShift && plan.prm.poolChunks == S.prm.poolChunks && plan.prm.histBits == S.prm.histBits &&
-        plan.meshHitWords == S.meshHitWords && plan.prm.contribLocal == S.prm.contribLocal && plan.nLocal == S.nLocal && plan.P == S.P &&
-        plan.texels.size() == S.heldTexels && plan.meshRecs.size() == S.heldMeshRecs;
-    if (faulted || !sameAllocations) {
-        t_lastMove.fast = 0;
-        return reinit_with_camera(camNew);
-    }
-    // batches traced ahead are discarded: consumed without being added, which leaves the slots' iteration masks zeroed
-    // (A HIP call that fails up to the capture has overwritten nothing the full call needs: the full call is made instead.)
-    const auto slow = [&]() { t_lastMove.fast = 0; return reinit_with_camera(camNew); };
-    if (!S.ahead.empty() && (discard_ahead() != PT_OK || hipStreamSynchronize(S.stream) != hipSuccess)) return slow();
-    // 5. the old view becomes the context's history exactly as pt_init captures it -- or the history ends as it ends there
-    {
-        bool keepHistory = (S.flags & PT_FLAG_TEMPORAL) != 0;
-        if (keepHistory && S.committed >= 1 && guide_stack_bytes() > 64 * 1024) keepHistory = false;
-        if (keepHistory && S.committed >= 1) {
-            // (PT_FLAG_DISPLAY_FILTER, whose pt_iterate allocates nothing: the capture exchanges the renderer's guide buffers with the
-            // history's, so a history that has none yet is given a pair first)
-            if ((S.flags & PT_FLAG_DISPLAY_FILTER) && !S.hist.hpos.p && !S.hist.live &&
-                (S.hist.hpos.alloc((size_t)S.P) != PT_OK || S.hist.hnrm.alloc((size_t)S.P) != PT_OK)) {
-                S.hist.hpos.release(); S.hist.hnrm.release();
-                return slow();
-            }
-            const int rc = capture_history();
-            if (rc) {
-                free_renderer();
-                return rc == PT_ERR_INVALID ? fail(PT_ERR_HIP, "pt_init (camera move): the capture of the old view failed: %s", std::string(g_err).c_str()) : rc;
-            }
-        }
-        if (!keepHistory) S.hist = History();
-    }
-    // From here on the renderer is overwritten: a HIP call that fails leaves the context without a renderer, as pt_init's do.
-    const auto body = [&]() -> int {
-        // 6. the library's accumulators, on the renderer's stream (a caller-owned accum_dev stays the caller's to zero)
-        if (S.imageOwn.p) HIPCHECK(hipMemsetAsync(S.imageOwn.p, 0, S.imageOwn.cap * sizeof(float), S.stream));
-        if (S.moments.p) HIPCHECK(hipMemsetAsync(S.moments.p, 0, (size_t)S.P * sizeof(float), S.stream));
-        if (S.albedo.p) HIPCHECK(hipMemsetAsync(S.albedo.p, 0, (size_t)S.P * sizeof(float4), S.stream));
-        // 7. the slots' counters (the chunk lists' generations go on: an entry of the old view never carries a serial number to come), and the
-        // host's sequence, trace-ahead, guide and timing state
-        for (int i = 0; i < S.nslots; ++i) {
-            HIPCHECK(hipMemsetAsync(S.slot[i].ctrl.p, 0, sizeof(Ctrl), S.stream));
-            S.slot[i].parity = 0;
-        }
-        for (auto &pr : S.evBounce) { S.evFree.push_back(pr.first); S.evFree.push_back(pr.second); }
-        S.evBounce.clear();
-        S.msBounce = 0; S.nBounce = 0;
-        S.iterations = 0; S.committed = 0; S.seq = 0;
-        S.ahead.clear();
-        S.dnGuideIter = 0;
-        S.snapTarget = nullptr; S.snapWait = nullptr;
-        // 8. the new plan's scalars
-        static_cast<PlanScalars &>(S) = plan;
-        S.kernFirst = kernFirst;
-        S.kernNext = kernNext;
-        // 9. the tables whose bytes differ (textures and mesh records: never -- no camera changes them, and the plan is the same scene's)
-        const ScenePlan &h = *S.held;
-        CameraMove &mv = t_lastMove;
-        PTCHECK(refresh_table(S.dgeoms, h.hg, plan.hg, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dmats, h.hm, plan.hm, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dGeomHit, h.geomHit, plan.geomHit, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dRows, h.rowsGlobal, plan.rowsGlobal, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dwalls, h.hw, plan.hw, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dTexGeom, h.texGeom, plan.texGeom, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dTexDesc, h.texDesc, plan.texDesc, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dTexUV, h.texUV, plan.texUV, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dBumpGeom, h.bumpGeom, plan.bumpGeom, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dBumpUV, h.bumpUV, plan.bumpUV, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dBumpTan, h.bumpTan, plan.bumpTan, false, S.stream, mv));
-        if (S.mesh) {
-            PTCHECK(refresh_table(S.dWalkIdx, h.walkIdx, plan.walkIdx, true, S.stream, mv));
-            PTCHECK(refresh_table(S.dWalkMeshRows, h.walkMeshRows, plan.walkMeshRows, true, S.stream, mv));
-        }
-        PTCHECK(refresh_table(S.dSphCull, h.sc, plan.sc, false, S.stream, mv));
-        if (S.grouped) PTCHECK(refresh_table(S.dSphGroups, h.groups, plan.groups, true, S.stream, mv));
-        PTCHECK(refresh_table(S.dRowOff, h.cc.rowOff, plan.cc.rowOff, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dRowIdx, h.cc.rowIdx, plan.cc.rowIdx, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dCamPix, h.cl.pix, plan.cl.pix, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dCamWave, h.cl.wave, plan.cl.wave, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dCamSigIdx, h.cl.sigIdx, plan.cl.sigIdx, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dCamFace, h.cl.face, plan.cl.face, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dWalkRowOff, h.walkRowOff, plan.walkRowOff, false, S.stream, mv));
-        PTCHECK(refresh_table(S.dClassIdx, h.classIdx, plan.classIdx, false, S.stream, mv));
-        // 10. what depends on the tables: the LDS attributes, the grids, the packed list or the row bands
-        PTCHECK(size_launches(S));
-        // the copies read the plan's vectors and the slots' streams do not wait for the renderer's: everything above has landed before
-        // the next launch is enqueued
-        HIPCHECK(hipStreamSynchronize(S.stream));
-        return PT_OK;
-    };
-    const int rc = body();
-    if (rc) {
-        const std::string err = g_err;
-        free_renderer();
-        g_err = err;
-        t_lastMove = CameraMove();
-        return rc;
-    }
-    std::vector<float4>().swap(plan.texels);
-    std::vector<ptd::MeshUnit>().swap(plan.meshRecs);
-    S.held = std::move(planPtr);
-    t_lastMove.fast = 1;
-    g_err.clear();
-    return PT_OK;
-}
-
-}  // namespace
-#pragma GCC visibility push(default)
-extern "C" {
-
-int pt_set_meshes_sized(const PtMesh *meshes, int nmeshes, size_t mesh_struct_bytes) {
-    if (mesh_struct_bytes != sizeof(PtMesh))
-        return fail(PT_ERR_INVALID, "pt_set_meshes: the caller's PtMesh is %zu bytes, this library's %zu (built against another pt_amd.h: ABI version %d here)",
-                    mesh_struct_bytes, sizeof(PtMesh), PT_AMD_ABI_VERSION);
-    return pt_set_meshes(meshes, nmeshes);
-}
-
-int pt_set_meshes(const PtMesh *meshes, int nmeshes) {
-    if (nmeshes < 0 || (nmeshes && !meshes)) return fail(PT_ERR_INVALID, "pt_set_meshes: null argument");
-    for (int i = 0; i < nmeshes; ++i) {
-        if (meshes[i].geom < 0 || meshes[i].ntris < 1 || !meshes[i].tris) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d is empty", i);
-        for (int j = 0; j < i; ++j)
-            if (meshes[j].geom == meshes[i].geom) return fail(PT_ERR_INVALID, "pt_set_meshes: geom %d given twice", meshes[i].geom);
-        for (size_t q = 0; q < 9 * (size_t)meshes[i].ntris; ++q)
-            if (!std::isfinite(meshes[i].tris[q])) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d holds a non-finite coordinate", i);
-        if (meshes[i].normals)
-            for (size_t q = 0; q < 9 * (size_t)meshes[i].ntris; ++q)
-                if (!std::isfinite(meshes[i].normals[q])) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d holds a non-finite normal", i);
-    }
-    if (R().init && !R().initMeshes) R().initMeshes.reset(new std::vector<ptm::HostMesh>(std::move(R().meshes)));     // (for the camera move)
-    R().meshes.clear();
-    for (int i = 0; i < nmeshes; ++i) {
-        ptm::HostMesh m;
-        m.geom = meshes[i].geom;
-        m.tris.assign(meshes[i].tris, meshes[i].tris + 9 * (size_t)meshes[i].ntris);
-        if (meshes[i].normals) m.normals.assign(meshes[i].normals, meshes[i].normals + 9 * (size_t)meshes[i].ntris);
-        if (meshes[i].materials) m.mats.assign(meshes[i].materials, meshes[i].materials + (size_t)meshes[i].ntris);
-        R().meshes.push_back(std::move(m));
-    }
-    return PT_OK;
-}
-
-int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes) {
-    if (binding_struct_bytes != sizeof(PtBumpBinding))
-        return fail(PT_ERR_INVALID, "pt_set_bump_maps: the caller's PtBumpBinding is %zu bytes, this library's %zu (ABI version %d here)",
-                    binding_struct_bytes, sizeof(PtBumpBinding), PT_AMD_ABI_VERSION);
-    if (nbindings < 0 || (nbindings && !bindings)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: null argument");
-    for (int i = 0; i < nbindings; ++i)
-        if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: binding %d: bad UVs", i);
-    // (indices, counts and the scale are checked by pt_init, against the scene)
-    if (R().init && !R().initBumpBindings) R().initBumpBindings.reset(new std::vector<HostBumpBinding>(std::move(R().bumpBindings)));
-    R().bumpBindings.clear();
-    for (int i = 0; i < nbindings; ++i) {
-        HostBumpBinding b;
-        b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris; b.scale = bindings[i].scale;
-        if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
-        R().bumpBindings.push_back(std::move(b));
-    }
-    return PT_OK;
-}
-
-int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings, int nbindings,
-                    size_t binding_struct_bytes) {
-    if (texture_struct_bytes != sizeof(PtTexture) || binding_struct_bytes != sizeof(PtTexBinding))
-        return fail(PT_ERR_INVALID, "pt_set_textures: the caller's PtTexture / PtTexBinding are %zu / %zu bytes, this library's %zu / %zu (ABI version %d here)",
-                    texture_struct_bytes, binding_struct_bytes, sizeof(PtTexture), sizeof(PtTexBinding), PT_AMD_ABI_VERSION);
-    if (ntextures < 0 || nbindings < 0 || (ntextures && !textures) || (nbindings && !bindings)) return fail(PT_ERR_INVALID, "pt_set_textures: null argument");
-    // (sizes, indices and values are checked by pt_init, against the scene; what cannot be copied safely is not copied and refused there)
-    for (int i = 0; i < ntextures; ++i)
-        if (textures[i].width >= 1 && textures[i].width <= kTexSizeMax && textures[i].height >= 1 && textures[i].height <= kTexSizeMax && !textures[i].rgb)
-            return fail(PT_ERR_INVALID, "pt_set_textures: texture %d has no texels", i);
-    for (int i = 0; i < nbindings; ++i)
-        if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_textures: binding %d: bad UVs", i);
-    if (R().init && !R().initTextures) {
-        R().initTextures.reset(new std::vector<HostTexture>(std::move(R().textures)));
-        R().initTexBindings.reset(new std::vector<HostTexBinding>(std::move(R().texBindings)));
-    }
-    R().textures.clear();
-    R().texBindings.clear();
-    long long texels = 0;
-    for (int i = 0; i < ntextures; ++i) {
-        HostTexture t;
-        t.w = textures[i].width; t.h = textures[i].height;
-        const bool sized = t.w >= 1 && t.w <= kTexSizeMax && t.h >= 1 && t.h <= kTexSizeMax;
-        if (sized) texels += (long long)t.w * t.h;
-        if (sized && texels < kTexTexelsMax) t.rgb.assign(textures[i].rgb, textures[i].rgb + (size_t)t.w * t.h * 3);
-        R().textures.push_back(std::move(t));
-    }
-    for (int i = 0; i < nbindings; ++i) {
-        HostTexBinding b;
-        b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris;
-        if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
-        R().texBindings.push_back(std::move(b));
-    }
-    return PT_OK;
+// the host's copies of the camera-invariant tables, once the device holds them
+void drop_camera_invariant(SceneTables &tab, ScenePlan &plan) {
+    (void)tab.for_each(nullptr, plan, plan.mesh, plan.grouped, [](const auto &, const auto *, auto &table, TableRule rule) {
+        if (rule.cameraInvariant) std::decay_t<decltype(table)>().swap(table);
+        return (int)PT_OK;
+    });
 }
 
 // The device half of pt_init.  The scene is planned on the host first (pt_scene_plan.h: plan_scene), and a scene that is refused there --
 // every PT_ERR_INVALID -- has touched nothing: no allocation made or released, the renderer that was there still initialised and usable.
 // Only then the old renderer goes, and what can still fail (PT_ERR_NO_GPU, PT_ERR_HIP: the memory budget, which has to see the memory the
 // old renderer gave back) leaves the context without a renderer.
-int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
-            const PtOptions *opts) {
-    // the camera move: no scene at all and PT_SAME_SCENE for the depth name the scene the live renderer was initialised with
-    if (!geoms && !mats && ngeoms == 0 && nmats == 0 && traceDepth == PT_SAME_SCENE && !opts) return set_camera(cam);
-    const PtOptions o = effective_options(opts);
-    // PT_FLAG_KEEP_RENDERER: the same call again with another pose is the camera move too.  (Equal registrations: the renderer's own copies
-    // of what a pt_set_* call has replaced with the same bytes are let go -- the registered ones serve.)
-    if ((o.flags & PT_FLAG_KEEP_RENDERER) && !t_fullCallInside) {
-        t_lastMove = CameraMove();
-        t_keepWhy = keep_mismatch(cam, geoms, ngeoms, mats, nmats, traceDepth, o);
-        if (!t_keepWhy) {
-            R().initMeshes.reset();
-            R().initTextures.reset();
-            R().initTexBindings.reset();
-            R().initBumpBindings.reset();
-            return set_camera(cam);
-        }
-    }
+// o: the options made effective; reg: what the scene's meshes, textures and height maps are -- what is registered now (pt_init), or what
+// the live renderer was initialised with (the camera move's slow path); by value: the renderer that holds them goes.
+int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions &o,
+                  const Registered reg) {
     // PT_AMD_INIT_PHASES (measurements only: profiles/set_camera_cost.py): the host's clock around the call's phases, each ended by a
     // device synchronise of its own, printed to stderr
     const bool phases = env_flag("PT_AMD_INIT_PHASES");
@@ -1685,7 +1386,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
         phaseT0 = t;
     };
     ScenePlan plan;
-    PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, o, R().meshes, R().textures, R().texBindings, R().bumpBindings}, plan));
+    PTCHECK(plan_scene(SceneIn(cam, geoms, ngeoms, mats, nmats, traceDepth, o, reg), plan));
     const void *kernFirst = nullptr, *kernNext = nullptr;
     PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
     PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
@@ -1700,17 +1401,7 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // (PT_FLAG_DEMOD_HISTORY: only between two renderers that agree on it -- a history with albedo and one without are different things)
     bool keepHistory = R().init && (R().flags & plan.flags & PT_FLAG_TEMPORAL) && !((R().flags ^ plan.flags) & PT_FLAG_DEMOD_HISTORY) &&
                        R().prm.W == plan.prm.W && R().prm.H == plan.prm.H && (o.device < 0 || o.device == R().device);
-    // (an old view whose scene k_gbuffer cannot trace -- a mesh hierarchy deeper than its 64 KB of stacks, the one thing pt_gbuffer answers
-    // PT_ERR_INVALID to -- has no guides to reproject through: the history ends there, and pt_init goes on.  What is left to fail in the
-    // capture is a HIP call: PT_ERR_HIP, which leaves the context without a renderer like every other one of pt_init's.)
-    if (keepHistory && R().committed >= 1 && guide_stack_bytes() > 64 * 1024) keepHistory = false;
-    if (keepHistory && R().committed >= 1) {
-        const int rc = capture_history();
-        if (rc) {
-            free_renderer();
-            return rc == PT_ERR_INVALID ? fail(PT_ERR_HIP, "pt_init: the capture of the old view failed: %s", std::string(g_err).c_str()) : rc;
-        }
-    }
+    PTCHECK(retire_view(keepHistory, "pt_init"));
     free_renderer(keepHistory);
     phase_end(1);      // the capture of history, the drain and the free
 
@@ -1783,34 +1474,9 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     // the plan's tables, each once; a table the scene does not have is empty and stays without a buffer (the walks' tables of a scene with
     // meshes and the groups of a grouped one get theirs even when empty: a kernel may be handed the pointer of an empty table)
     phase_end(2);      // streams, events and every allocation with its zeroing
-    const auto up = [](auto &buf, const auto &table) { return table.empty() ? (int)PT_OK : buf.upload(table); };
-    PTCHECK(up(S.dgeoms, plan.hg));
-    PTCHECK(up(S.dmats, plan.hm));
-    PTCHECK(up(S.dGeomHit, plan.geomHit));
-    PTCHECK(up(S.dRows, plan.rowsGlobal));
-    PTCHECK(up(S.dwalls, plan.hw));
-    PTCHECK(up(S.dTexGeom, plan.texGeom));
-    PTCHECK(up(S.dTexDesc, plan.texDesc));
-    PTCHECK(up(S.dTexels, plan.texels));
-    PTCHECK(up(S.dTexUV, plan.texUV));
-    PTCHECK(up(S.dBumpGeom, plan.bumpGeom));
-    PTCHECK(up(S.dBumpUV, plan.bumpUV));
-    PTCHECK(up(S.dBumpTan, plan.bumpTan));
-    if (S.mesh) {
-        PTCHECK(S.dMeshRecs.upload(plan.meshRecs.data(), plan.meshRecs.size(), 4));     // (+ 4: a walk may read the record behind the last one)
-        PTCHECK(S.dWalkIdx.upload(plan.walkIdx));
-        PTCHECK(S.dWalkMeshRows.upload(plan.walkMeshRows));
-    }
-    PTCHECK(up(S.dSphCull, plan.sc));
-    if (S.grouped) PTCHECK(S.dSphGroups.upload(plan.groups));
-    PTCHECK(up(S.dRowOff, plan.cc.rowOff));
-    PTCHECK(up(S.dRowIdx, plan.cc.rowIdx));
-    PTCHECK(up(S.dCamPix, plan.cl.pix));
-    PTCHECK(up(S.dCamWave, plan.cl.wave));
-    PTCHECK(up(S.dCamSigIdx, plan.cl.sigIdx));
-    PTCHECK(up(S.dCamFace, plan.cl.face));
-    PTCHECK(up(S.dWalkRowOff, plan.walkRowOff));
-    PTCHECK(up(S.dClassIdx, plan.classIdx));
+    PTCHECK(S.tab.for_each(nullptr, plan, S.mesh, S.grouped, [](auto &buf, const auto *, const auto &table, TableRule rule) {
+        return rule.allocated(table.size()) ? buf.upload(table.data(), table.size(), rule.slack) : (int)PT_OK;
+    }));
 
     phase_end(3);      // the tables' uploads
     PTCHECK(size_launches(S));
@@ -1828,14 +1494,330 @@ int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMateri
     S.inMats.assign(mats, mats + nmats);
     S.inDepth = traceDepth;
     S.inOpts = o;
-    S.heldTexels = plan.texels.size();
-    S.heldMeshRecs = plan.meshRecs.size();
-    std::vector<float4>().swap(plan.texels);
-    std::vector<ptd::MeshUnit>().swap(plan.meshRecs);
+    S.initReg = reg;
+    drop_camera_invariant(S.tab, plan);
     S.held.reset(new ScenePlan(std::move(plan)));
     S.init = true;
     g_err.clear();
     return PT_OK;
+}
+
+// ---- the camera move ------------------------------------------------------------------------------------------------------------------------
+// which way the calling thread's last camera move went (pt_test_last_camera_move): fast 1 / 0, -1 before the first move or after a
+// refusal; the tables and bytes the fast path uploaded
+struct CameraMove { int fast = -1, tables = 0; long long bytes = 0; };
+thread_local CameraMove t_lastMove;
+// PT_FLAG_KEEP_RENDERER: why the calling thread's last flagged full call did not take the move's path (keep_renderer_mismatch's answer, or
+// that there was no renderer; null: it did, or there has been no such call)
+thread_local const char *t_keepWhy = nullptr;
+
+// The work list's face certificates on the device, between build_camera_list's two passes: the pixel words of the one-cube groups whose
+// cube is CubeCert::ok go up as one array, k_camera_faces runs once per group -- the cube is uniform per group: a kernel argument -- and
+// the bytes come back as CameraGroups::faces.  pix / face: scratch buffers of the caller's, grown where needed; ms (or NULL): the kernels'
+// time by HIP events.
+int camera_faces_device(CameraGroups &G, const CameraResolve &cr, hipStream_t st, DevBuf<uint32_t> &pix, DevBuf<signed char> &face, float *ms) {
+    if (ms) *ms = 0.0f;
+    struct Run { size_t group, off, n; int cube; };
+    std::vector<Run> runs;
+    size_t total = 0;
+    for (size_t s = 0; s < G.groups.size(); ++s) {
+        const int cube = camera_group_cube(G, s, cr);
+        if (cube < 0 || G.groups[s].empty()) continue;
+        runs.push_back({s, total, G.groups[s].size(), cube});
+        total += G.groups[s].size();
+    }
+    if (!total) return PT_OK;
+    std::vector<uint32_t> words(total);
+    for (const Run &r : runs) memcpy(words.data() + r.off, G.groups[r.group].data(), r.n * sizeof(uint32_t));
+    if (pix.cap < total) PTCHECK(pix.alloc(total + total / 4));
+    if (face.cap < total) PTCHECK(face.alloc(total + total / 4));
+    EventSet es;
+    HIPCHECK(hipMemcpyAsync(pix.p, words.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if (ms) {
+        HIPCHECK(hipEventCreate(&es.ev[0]));
+        HIPCHECK(hipEventCreate(&es.ev[1]));
+        HIPCHECK(hipEventRecord(es.ev[0], st));
+    }
+    for (const Run &r : runs) {
+        CameraFacesArgs A;
+        A.cube = cr.cube[(size_t)r.cube];
+        A.basis = cr;
+        A.pix = pix.p + r.off;
+        A.face = face.p + r.off;
+        A.n = (int)r.n;
+        hipLaunchKernelGGL(k_camera_faces, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, st, A);
+    }
+    HIPCHECK(hipGetLastError());
+    if (ms) HIPCHECK(hipEventRecord(es.ev[1], st));
+    std::vector<signed char> bytes(total);
+    HIPCHECK(hipMemcpyAsync(bytes.data(), face.p, total, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (ms) HIPCHECK(hipEventElapsedTime(ms, es.ev[0], es.ev[1]));
+    for (const Run &r : runs) {
+        std::vector<int> &f = G.faces[r.group];
+        f.resize(r.n);
+        for (size_t i = 0; i < r.n; ++i) {
+            const int v = bytes[r.off + i];
+            if (v < -1 || v > 5) return fail(PT_ERR_DEVICE, "pt_init (camera move): k_camera_faces answered %d", v);
+            f[i] = v;
+        }
+    }
+    return PT_OK;
+}
+
+// The camera move's action on a table (SceneTables::for_each): the renderer's against the new plan's -- left alone where the device holds
+// these very bytes (a camera-invariant one: always), released where the plan has none (pt_init leaves such a table without a buffer, and
+// the kernels ask), written in place where it fits, reallocated where it grew.  The copy is enqueued on `st` from `now`, which the caller
+// keeps until the stream has been waited for.
+template <typename T>
+int refresh_table(DevBuf<T> &buf, const std::vector<T> &heldT, const std::vector<T> &now, TableRule rule, hipStream_t st, CameraMove &mv) {
+    if (rule.cameraInvariant) return PT_OK;
+    if (now.empty() && !rule.evenEmpty) { buf.release(); return PT_OK; }
+    const bool same = buf.p && heldT.size() == now.size() && (now.empty() || !memcmp(heldT.data(), now.data(), now.size() * sizeof(T)));
+    if (same) return PT_OK;
+    if (!buf.p || buf.cap < now.size()) PTCHECK(buf.alloc(now.size() + now.size() / 4));
+    if (!now.empty()) HIPCHECK(hipMemcpyAsync(buf.p, now.data(), now.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    mv.tables += 1;
+    mv.bytes += (long long)(now.size() * sizeof(T));
+    return PT_OK;
+}
+
+// pt_init over the live renderer with the scene it was initialised with -- its arguments, and what was registered then --: the camera
+// move's slow path.  What has been registered since stays registered behind it.  (Copies: init_renderer frees the renderer that holds them.)
+int reinit_with_camera(const PtCamera &cam) {
+    const State &S = R();
+    const std::vector<PtGeom> geoms = S.inGeoms;
+    const std::vector<PtMaterial> mats = S.inMats;
+    const PtOptions o = S.inOpts;
+    return init_renderer(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), S.inDepth, o, S.initReg);
+}
+
+// PT_FLAG_KEEP_RENDERER on a full call: the call against the live renderer's copies of its own (pt_scene_plan.h: keep_renderer_mismatch).
+// What is registered now and what the renderer was initialised with share every part no pt_set_* call has replaced in between.
+const char *keep_mismatch(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions &o) {
+    const State &S = R();
+    if (!S.init) return "no live renderer";
+    if (!cam) return "camera";
+    const InitCall now{geoms, ngeoms, mats, nmats, traceDepth, &o, cam->resolution[0], cam->resolution[1], S.reg};
+    const InitCall then{S.inGeoms.data(), (int)S.inGeoms.size(), S.inMats.data(), (int)S.inMats.size(), S.inDepth, &S.inOpts, S.prm.W, S.prm.H, S.initReg};
+    return keep_renderer_mismatch(now, then);
+}
+
+int set_camera(const PtCamera *cam) {
+    t_lastMove = CameraMove();
+    if (!cam) return fail(PT_ERR_INVALID, "pt_init (camera move): null camera");
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_init (camera move) before pt_init: there is no renderer whose scene it could name");
+    State &S = R();
+    if (cam->resolution[0] != S.prm.W || cam->resolution[1] != S.prm.H)
+        return fail(PT_ERR_INVALID, "pt_init (camera move): the camera's resolution %d x %d is not the renderer's %d x %d (pt_init makes a renderer of another size)",
+                    cam->resolution[0], cam->resolution[1], S.prm.W, S.prm.H);
+    const PtCamera camNew = *cam;        // (the caller may hand in the camera of a scene this call outlives)
+    if (S.device >= 0) HIPCHECK(hipSetDevice(S.device));
+    // 1. the plan for the new camera, the certificates of its work list on the device; a scene that is refused has touched nothing
+    if (!S.camStream) HIPCHECK(hipStreamCreateWithFlags(&S.camStream, hipStreamNonBlocking));
+    std::unique_ptr<ScenePlan> planPtr(new ScenePlan);
+    ScenePlan &plan = *planPtr;
+    {
+        SceneIn in(&camNew, S.inGeoms.data(), (int)S.inGeoms.size(), S.inMats.data(), (int)S.inMats.size(), S.inDepth, S.inOpts, S.initReg);
+        in.faces = [&S](CameraGroups &G, const CameraResolve &cr) { return camera_faces_device(G, cr, S.camStream, S.camPixScratch, S.camFaceScratch, nullptr); };
+        PTCHECK(plan_scene(in, plan));
+    }
+    const void *kernFirst = nullptr, *kernNext = nullptr;
+    PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
+    PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
+    // 2. drain the renderer's streams, as free_renderer does
+    for (int i = 0; i < S.nslots; ++i) (void)hipStreamSynchronize(S.slot[i].stream);
+    (void)hipStreamSynchronize(S.stream);
+    // 3. does the plan need the allocations the renderer holds?  (It does unless planning changes: none of these sizes depends on the
+    // camera; a camera-invariant table's buffer is the one pt_init would make for the plan's.)  A renderer that carries a sticky device
+    // fault is rebuilt like any other: pt_init.
+    const bool faulted = S.hostFault && *(volatile uint32_t *)S.hostFault != 0u;
+    bool sameInvariants = true;
+    (void)S.tab.for_each(S.held.get(), plan, plan.mesh, plan.grouped, [&](const auto &buf, const auto *, const auto &now, TableRule rule) {
+        if (rule.cameraInvariant && buf.cap != rule.allocated(now.size())) sameInvariants = false;
+        return (int)PT_OK;
+    });
+    const bool sameAllocations =
+        S.held && kernFirst == S.kernFirst && kernNext == S.kernNext && plan.mesh == S.mesh && plan.dof == S.dof && plan.walkMeshLds == S.walkMeshLds &&
+        plan.flags == S.flags && plan.nslots == S.nslots && plan.maxBatch == S.maxBatch && plan.poolCap == S.poolCap && plan.poolChunks == S.poolChunks &&
+        plan.prm.chunkShift == S.prm.chunkShift && plan.prm.poolChunks == S.prm.poolChunks && plan.prm.histBits == S.prm.histBits &&
+        plan.meshHitWords == S.meshHitWords && plan.prm.contribLocal == S.prm.contribLocal && plan.nLocal == S.nLocal && plan.P == S.P && sameInvariants;
+    if (faulted || !sameAllocations) {
+        t_lastMove.fast = 0;
+        return reinit_with_camera(camNew);
+    }
+    // batches traced ahead are discarded: consumed without being added, which leaves the slots' iteration masks zeroed
+    // (A HIP call that fails up to the capture has overwritten nothing the full call needs: the full call is made instead.)
+    const auto slow = [&]() { t_lastMove.fast = 0; return reinit_with_camera(camNew); };
+    if (!S.ahead.empty() && (discard_ahead() != PT_OK || hipStreamSynchronize(S.stream) != hipSuccess)) return slow();
+    // 5. the old view becomes the context's history exactly as pt_init captures it -- or the history ends as it ends there
+    {
+        bool keepHistory = (S.flags & PT_FLAG_TEMPORAL) != 0;
+        // (PT_FLAG_DISPLAY_FILTER, whose pt_iterate allocates nothing: the capture exchanges the renderer's guide buffers with the
+        // history's, so a history that has none yet is given a pair first)
+        if (capture_due(keepHistory) && (S.flags & PT_FLAG_DISPLAY_FILTER) && !S.hist.hpos.p && !S.hist.live &&
+            (S.hist.hpos.alloc((size_t)S.P) != PT_OK || S.hist.hnrm.alloc((size_t)S.P) != PT_OK)) {
+            S.hist.hpos.release(); S.hist.hnrm.release();
+            return slow();
+        }
+        PTCHECK(retire_view(keepHistory, "pt_init (camera move)"));
+        if (!keepHistory) S.hist = History();
+    }
+    // From here on the renderer is overwritten: a HIP call that fails leaves the context without a renderer, as pt_init's do.
+    const auto body = [&]() -> int {
+        // 6. the library's accumulators, on the renderer's stream (a caller-owned accum_dev stays the caller's to zero)
+        if (S.imageOwn.p) HIPCHECK(hipMemsetAsync(S.imageOwn.p, 0, S.imageOwn.cap * sizeof(float), S.stream));
+        if (S.moments.p) HIPCHECK(hipMemsetAsync(S.moments.p, 0, (size_t)S.P * sizeof(float), S.stream));
+        if (S.albedo.p) HIPCHECK(hipMemsetAsync(S.albedo.p, 0, (size_t)S.P * sizeof(float4), S.stream));
+        // 7. the slots' counters (the chunk lists' generations go on: an entry of the old view never carries a serial number to come), and the
+        // host's sequence, trace-ahead, guide and timing state
+        for (int i = 0; i < S.nslots; ++i) {
+            HIPCHECK(hipMemsetAsync(S.slot[i].ctrl.p, 0, sizeof(Ctrl), S.stream));
+            S.slot[i].parity = 0;
+        }
+        for (auto &pr : S.evBounce) { S.evFree.push_back(pr.first); S.evFree.push_back(pr.second); }
+        S.evBounce.clear();
+        S.msBounce = 0; S.nBounce = 0;
+        S.iterations = 0; S.committed = 0; S.seq = 0;
+        S.ahead.clear();
+        S.dnGuideIter = 0;
+        S.snapTarget = nullptr; S.snapWait = nullptr;
+        // 8. the new plan's scalars
+        static_cast<PlanScalars &>(S) = plan;
+        S.kernFirst = kernFirst;
+        S.kernNext = kernNext;
+        // 9. the tables whose bytes differ (textures and mesh records: never -- no camera changes them, and the plan is the same scene's)
+        CameraMove &mv = t_lastMove;
+        PTCHECK(S.tab.for_each(S.held.get(), plan, S.mesh, S.grouped, [&](auto &buf, const auto *heldT, const auto &now, TableRule rule) {
+            return refresh_table(buf, *heldT, now, rule, S.stream, mv);
+        }));
+        // 10. what depends on the tables: the LDS attributes, the grids, the packed list or the row bands
+        PTCHECK(size_launches(S));
+        // the copies read the plan's vectors and the slots' streams do not wait for the renderer's: everything above has landed before
+        // the next launch is enqueued
+        HIPCHECK(hipStreamSynchronize(S.stream));
+        return PT_OK;
+    };
+    const int rc = body();
+    if (rc) {
+        const std::string err = g_err;
+        free_renderer();
+        g_err = err;
+        t_lastMove = CameraMove();
+        return rc;
+    }
+    drop_camera_invariant(S.tab, plan);
+    S.held = std::move(planPtr);
+    t_lastMove.fast = 1;
+    g_err.clear();
+    return PT_OK;
+}
+
+}  // namespace
+#pragma GCC visibility push(default)
+extern "C" {
+
+int pt_set_meshes_sized(const PtMesh *meshes, int nmeshes, size_t mesh_struct_bytes) {
+    if (mesh_struct_bytes != sizeof(PtMesh))
+        return fail(PT_ERR_INVALID, "pt_set_meshes: the caller's PtMesh is %zu bytes, this library's %zu (built against another pt_amd.h: ABI version %d here)",
+                    mesh_struct_bytes, sizeof(PtMesh), PT_AMD_ABI_VERSION);
+    return pt_set_meshes(meshes, nmeshes);
+}
+
+int pt_set_meshes(const PtMesh *meshes, int nmeshes) {
+    if (nmeshes < 0 || (nmeshes && !meshes)) return fail(PT_ERR_INVALID, "pt_set_meshes: null argument");
+    for (int i = 0; i < nmeshes; ++i) {
+        if (meshes[i].geom < 0 || meshes[i].ntris < 1 || !meshes[i].tris) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d is empty", i);
+        for (int j = 0; j < i; ++j)
+            if (meshes[j].geom == meshes[i].geom) return fail(PT_ERR_INVALID, "pt_set_meshes: geom %d given twice", meshes[i].geom);
+        for (size_t q = 0; q < 9 * (size_t)meshes[i].ntris; ++q)
+            if (!std::isfinite(meshes[i].tris[q])) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d holds a non-finite coordinate", i);
+        if (meshes[i].normals)
+            for (size_t q = 0; q < 9 * (size_t)meshes[i].ntris; ++q)
+                if (!std::isfinite(meshes[i].normals[q])) return fail(PT_ERR_INVALID, "pt_set_meshes: mesh %d holds a non-finite normal", i);
+    }
+    std::vector<ptm::HostMesh> reg;
+    for (int i = 0; i < nmeshes; ++i) {
+        ptm::HostMesh m;
+        m.geom = meshes[i].geom;
+        m.tris.assign(meshes[i].tris, meshes[i].tris + 9 * (size_t)meshes[i].ntris);
+        if (meshes[i].normals) m.normals.assign(meshes[i].normals, meshes[i].normals + 9 * (size_t)meshes[i].ntris);
+        if (meshes[i].materials) m.mats.assign(meshes[i].materials, meshes[i].materials + (size_t)meshes[i].ntris);
+        reg.push_back(std::move(m));
+    }
+    R().reg.meshes = std::make_shared<const std::vector<ptm::HostMesh>>(std::move(reg));      // (a live renderer keeps the part it was initialised with)
+    return PT_OK;
+}
+
+int pt_set_bump_maps(const PtBumpBinding *bindings, int nbindings, size_t binding_struct_bytes) {
+    if (binding_struct_bytes != sizeof(PtBumpBinding))
+        return fail(PT_ERR_INVALID, "pt_set_bump_maps: the caller's PtBumpBinding is %zu bytes, this library's %zu (ABI version %d here)",
+                    binding_struct_bytes, sizeof(PtBumpBinding), PT_AMD_ABI_VERSION);
+    if (nbindings < 0 || (nbindings && !bindings)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: null argument");
+    for (int i = 0; i < nbindings; ++i)
+        if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_bump_maps: binding %d: bad UVs", i);
+    // (indices, counts and the scale are checked by pt_init, against the scene)
+    std::vector<HostBumpBinding> reg;
+    for (int i = 0; i < nbindings; ++i) {
+        HostBumpBinding b;
+        b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris; b.scale = bindings[i].scale;
+        if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
+        reg.push_back(std::move(b));
+    }
+    R().reg.bumpBindings = std::make_shared<const std::vector<HostBumpBinding>>(std::move(reg));
+    return PT_OK;
+}
+
+int pt_set_textures(const PtTexture *textures, int ntextures, size_t texture_struct_bytes, const PtTexBinding *bindings, int nbindings,
+                    size_t binding_struct_bytes) {
+    if (texture_struct_bytes != sizeof(PtTexture) || binding_struct_bytes != sizeof(PtTexBinding))
+        return fail(PT_ERR_INVALID, "pt_set_textures: the caller's PtTexture / PtTexBinding are %zu / %zu bytes, this library's %zu / %zu (ABI version %d here)",
+                    texture_struct_bytes, binding_struct_bytes, sizeof(PtTexture), sizeof(PtTexBinding), PT_AMD_ABI_VERSION);
+    if (ntextures < 0 || nbindings < 0 || (ntextures && !textures) || (nbindings && !bindings)) return fail(PT_ERR_INVALID, "pt_set_textures: null argument");
+    // (sizes, indices and values are checked by pt_init, against the scene; what cannot be copied safely is not copied and refused there)
+    for (int i = 0; i < ntextures; ++i)
+        if (textures[i].width >= 1 && textures[i].width <= kTexSizeMax && textures[i].height >= 1 && textures[i].height <= kTexSizeMax && !textures[i].rgb)
+            return fail(PT_ERR_INVALID, "pt_set_textures: texture %d has no texels", i);
+    for (int i = 0; i < nbindings; ++i)
+        if (bindings[i].ntris < 0 || (bindings[i].ntris > 0 && !bindings[i].uvs)) return fail(PT_ERR_INVALID, "pt_set_textures: binding %d: bad UVs", i);
+    std::vector<HostTexture> regTex;
+    std::vector<HostTexBinding> regBind;
+    long long texels = 0;
+    for (int i = 0; i < ntextures; ++i) {
+        HostTexture t;
+        t.w = textures[i].width; t.h = textures[i].height;
+        const bool sized = t.w >= 1 && t.w <= kTexSizeMax && t.h >= 1 && t.h <= kTexSizeMax;
+        if (sized) texels += (long long)t.w * t.h;
+        if (sized && texels < kTexTexelsMax) t.rgb.assign(textures[i].rgb, textures[i].rgb + (size_t)t.w * t.h * 3);
+        regTex.push_back(std::move(t));
+    }
+    for (int i = 0; i < nbindings; ++i) {
+        HostTexBinding b;
+        b.geom = bindings[i].geom; b.texture = bindings[i].texture; b.ntris = bindings[i].ntris;
+        if (bindings[i].uvs) b.uvs.assign(bindings[i].uvs, bindings[i].uvs + 6 * (size_t)b.ntris);
+        regBind.push_back(std::move(b));
+    }
+    R().reg.textures = std::make_shared<const std::vector<HostTexture>>(std::move(regTex));
+    R().reg.texBindings = std::make_shared<const std::vector<HostTexBinding>>(std::move(regBind));
+    return PT_OK;
+}
+
+// pt_init's three forms: the camera move (no scene at all and PT_SAME_SCENE for the depth name the scene the live renderer was initialised
+// with), the full call that PT_FLAG_KEEP_RENDERER finds to be the live renderer's own with another pose -- the camera move too --, and the
+// full call (init_renderer, with what is registered now).
+int pt_init(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth,
+            const PtOptions *opts) {
+    if (!geoms && !mats && ngeoms == 0 && nmats == 0 && traceDepth == PT_SAME_SCENE && !opts) return set_camera(cam);
+    const PtOptions o = effective_options(opts);
+    if (o.flags & PT_FLAG_KEEP_RENDERER) {
+        t_lastMove = CameraMove();
+        t_keepWhy = keep_mismatch(cam, geoms, ngeoms, mats, nmats, traceDepth, o);
+        if (!t_keepWhy) {
+            R().initReg = R().reg;      // (equal registrations: the renderer's own copies of what a pt_set_* call has replaced with the same bytes are let go)
+            return set_camera(cam);
+        }
+    }
+    return init_renderer(cam, geoms, ngeoms, mats, nmats, traceDepth, o, R().reg);
 }
 
 int pt_iterate_batch(int frame, int first_iter, int count, void *rgba8_dev) {

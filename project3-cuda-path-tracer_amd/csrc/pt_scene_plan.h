@@ -15,7 +15,18 @@ struct HostTexture { int w = 0, h = 0; std::vector<float> rgb; };              /
 struct HostTexBinding { int geom = 0, texture = 0, ntris = 0; std::vector<float> uvs; };
 struct HostBumpBinding { int geom = 0, texture = 0, ntris = 0; float scale = 0.0f; std::vector<float> uvs; };
 
-// The arguments of pt_init with the options made effective (pt_init's defaults where the caller gave none), and what the calls before it registered.
+// What the pt_set_* calls registered: meshes (pt_set_meshes), textures and their bindings (pt_set_textures), height maps (pt_set_bump_maps).
+// A part is immutable once registered and shared by reference count: a pt_set_* call puts a new vector in the place of its part, and
+// whoever copied the old one -- the live renderer, for its camera moves -- still holds it.  Never null: an empty vector stands for "none".
+struct Registered {
+    std::shared_ptr<const std::vector<ptm::HostMesh>> meshes = std::make_shared<const std::vector<ptm::HostMesh>>();
+    std::shared_ptr<const std::vector<HostTexture>> textures = std::make_shared<const std::vector<HostTexture>>();
+    std::shared_ptr<const std::vector<HostTexBinding>> texBindings = std::make_shared<const std::vector<HostTexBinding>>();
+    std::shared_ptr<const std::vector<HostBumpBinding>> bumpBindings = std::make_shared<const std::vector<HostBumpBinding>>();
+};
+
+// The arguments of pt_init with the options made effective (pt_init's defaults where the caller gave none), and what the calls before it
+// registered (the caller keeps its Registered while the SceneIn is read).
 struct SceneIn {
     const PtCamera *cam;
     const PtGeom *geoms;
@@ -27,6 +38,9 @@ struct SceneIn {
     const std::vector<HostTexture> &textures;
     const std::vector<HostTexBinding> &texBindings;
     const std::vector<HostBumpBinding> &bumpBindings;
+    SceneIn(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, int traceDepth, const PtOptions &o, const Registered &reg)
+        : cam(cam), geoms(geoms), ngeoms(ngeoms), mats(mats), nmats(nmats), traceDepth(traceDepth), o(o), meshes(*reg.meshes), textures(*reg.textures),
+          texBindings(*reg.texBindings), bumpBindings(*reg.bumpBindings) {}
     // who evaluates the work list's face certificates between build_camera_list's two passes: nobody named -- the host (pt_init, the
     // host-only entry points); the camera move (pt_api.hip) names the device (k_camera_faces).  PT_OK, or what fail() returned.
     std::function<int(CameraGroups &, const CameraResolve &)> faces = nullptr;
@@ -52,12 +66,6 @@ PtOptions effective_options(const PtOptions *opts) {
 // arguments (options made effective) and what is registered at this moment; `then`: the renderer's copies.  NULL where everything the flag's
 // definition lists (include/pt_amd.h) is equal, else the name of the first comparison that failed (pt_test_keep_mismatch).  Arrays are
 // compared byte for byte -- texels too: no hash --, so a -0.0 for a 0.0 is a difference: the full call, which is always right.
-struct RegisteredScene {
-    const std::vector<ptm::HostMesh> *meshes;
-    const std::vector<HostTexture> *textures;
-    const std::vector<HostTexBinding> *texBindings;
-    const std::vector<HostBumpBinding> *bumpBindings;
-};
 struct InitCall {
     const PtGeom *geoms;
     int ngeoms;
@@ -65,7 +73,7 @@ struct InitCall {
     int nmats, traceDepth;
     const PtOptions *o;
     int W, H;
-    RegisteredScene reg;
+    Registered reg;      // (a part the two sides share -- one object -- is not compared byte for byte)
 };
 template <typename T>
 inline bool same_bytes(const std::vector<T> &a, const std::vector<T> &b) {
@@ -89,7 +97,7 @@ inline const char *keep_renderer_mismatch(const InitCall &now, const InitCall &t
     if (a.accum_dev != b.accum_dev) return "accum_dev";
     if (memcmp(&a.lens_radius, &b.lens_radius, sizeof(float))) return "lens_radius";
     if (memcmp(&a.focal_distance, &b.focal_distance, sizeof(float))) return "focal_distance";
-    const RegisteredScene &p = now.reg, &q = then.reg;
+    const Registered &p = now.reg, &q = then.reg;
     if (p.meshes != q.meshes) {
         if (p.meshes->size() != q.meshes->size()) return "mesh count";
         for (size_t i = 0; i < p.meshes->size(); ++i) {

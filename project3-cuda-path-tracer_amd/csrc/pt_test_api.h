@@ -74,7 +74,7 @@ int pt_debug_trace_paths(int iter, int bounces, float *origin3, float *dir3, flo
             return fail(PT_ERR_INVALID, "pt_debug_trace_paths: %d codes of %d bits do not fit a path's history word (the renderer itself scatters %d times)",
                         bounces, hb, R().prm.traceDepth - 1);
         hmat.resize((size_t)R().prm.nmats);
-        HIPCHECK(hipMemcpy(hmat.data(), R().dmats.p, hmat.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
+        HIPCHECK(hipMemcpy(hmat.data(), R().tab.dmats.p, hmat.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
     }
     {
         std::vector<float> bufA((size_t)chunkPaths * 4), bufB((size_t)chunkPaths * 4), bufC((size_t)chunkPaths * 3);
@@ -173,7 +173,7 @@ int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
                        PtTestPlanSummary *out) {
     if (!out) return fail(PT_ERR_INVALID, "pt_test_scene_plan: bad argument");
     ScenePlan p;
-    PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings}, p));
+    PTCHECK(plan_scene(SceneIn(cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().reg), p));
     *out = PtTestPlanSummary{plan_state_bits(p), p.prm.nBinned, p.prm.nWalls, p.prm.nSphCull, p.prm.nSphGroups, p.prm.nLocalPad, p.prm.firstSkipped, p.poolChunks,
                              (uint64_t)p.ldsBytes, (uint64_t)p.ldsBytesNext, p.prm.histBits, p.prm.grpLds};
     return PT_OK;
@@ -185,7 +185,7 @@ int pt_test_sphere_groups(const PtCamera *cam, const PtGeom *geoms, int ngeoms, 
                           int32_t *table, float *entries5, int32_t table_cap, float *balls4, int32_t balls_cap, int32_t info6[6], float bounds2[2]) {
     if (!table || !entries5 || !balls4 || !info6 || !bounds2 || table_cap < 0 || balls_cap < 0) return fail(PT_ERR_INVALID, "pt_test_sphere_groups: bad argument");
     ScenePlan p;
-    const SceneIn in{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings};
+    const SceneIn in(cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().reg);
     PTCHECK(check_scene(in));
     PTCHECK(plan_frame(in, p));
     PTCHECK(plan_emitters(in, p));
@@ -1021,7 +1021,7 @@ int pt_test_wall_faces(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
                        int32_t *face, float *beyond) {
     if (!face || !beyond) return fail(PT_ERR_INVALID, "pt_test_wall_faces: bad argument");
     ScenePlan p;
-    PTCHECK(plan_scene(SceneIn{cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().meshes, R().textures, R().texBindings, R().bumpBindings}, p));
+    PTCHECK(plan_scene(SceneIn(cam, geoms, ngeoms, mats, nmats, traceDepth, effective_options(opts), R().reg), p));
     for (int i = 0; i < ngeoms; ++i) {
         const int w = (p.hg[(size_t)i].flags >> 2) & 7;                  // 1 + index among the walls, 0: not one
         face[i] = w != 0 ? p.hw[(size_t)w - 1].face : -1;

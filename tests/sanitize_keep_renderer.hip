@@ -5,8 +5,8 @@
 // arrays live at other addresses (no difference), then against calls that differ in one thing each -- a material's colour, a geom's
 // translation, traceDepth, max_batch, pipeline_depth, lens_radius, a flag bit, the resolution, a texel, a UV, a triangle vertex, a face
 // material, a bump scale, a texture added, the meshes cleared -- and the edge cases of the routine itself: empty scenes, NULL arrays with a
-// count, arrays of other lengths, the registered data being the renderer's own objects.  Exit status 0 and "sanitizer run finished" when
-// every answer is the expected one.
+// count, arrays of other lengths, the registered data being the renderer's own objects -- all four parts, or three of them with the
+// fourth replaced.  Exit status 0 and "sanitizer run finished" when every answer is the expected one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,9 +61,16 @@ struct Side {
     std::vector<HostTexture> textures;
     std::vector<HostTexBinding> texBindings;
     std::vector<HostBumpBinding> bumpBindings;
-    InitCall call() const {
-        return InitCall{geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), depth, &o, W, H, {&meshes, &textures, &texBindings, &bumpBindings}};
+    // (the registrations as a pt_set_* call leaves them: every part a fresh object)
+    Registered reg() const {
+        Registered r;
+        r.meshes = std::make_shared<const std::vector<ptm::HostMesh>>(meshes);
+        r.textures = std::make_shared<const std::vector<HostTexture>>(textures);
+        r.texBindings = std::make_shared<const std::vector<HostTexBinding>>(texBindings);
+        r.bumpBindings = std::make_shared<const std::vector<HostBumpBinding>>(bumpBindings);
+        return r;
     }
+    InitCall call() const { return InitCall{geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), depth, &o, W, H, reg()}; }
 };
 
 Side base() {
@@ -200,6 +207,37 @@ int main() {
         shared.reg = then.call().reg;       // (no pt_set_* call since the renderer's pt_init: one set of objects)
         ++g_cases;
         if (keep_renderer_mismatch(shared, then.call())) { fprintf(stderr, "shared registrations differ\n"); ++g_bad; }
+    }
+    {   // two sets of registrations that share three parts -- no pt_set_* call has replaced those -- and differ in the fourth, each part in
+        // turn: the mismatch is that part's first comparison; and a fourth part that is another object with the same bytes matches
+        const Side full = base();
+        Side fewer = base();
+        fewer.meshes.clear(); fewer.textures.pop_back(); fewer.texBindings.clear(); fewer.bumpBindings.pop_back();
+        const Registered mine = full.reg(), equal = full.reg(), other = fewer.reg();
+        struct Part { const char *name, *want; std::function<void(Registered &, const Registered &)> take; };
+        const Part parts[] = {
+            {"meshes", "mesh count", [](Registered &r, const Registered &from) { r.meshes = from.meshes; }},
+            {"textures", "texture count", [](Registered &r, const Registered &from) { r.textures = from.textures; }},
+            {"texture bindings", "texture binding count", [](Registered &r, const Registered &from) { r.texBindings = from.texBindings; }},
+            {"bump bindings", "bump binding count", [](Registered &r, const Registered &from) { r.bumpBindings = from.bumpBindings; }},
+        };
+        for (const Part &part : parts) {
+            InitCall a = full.call(), b = full.call();
+            a.reg = b.reg = mine;
+            part.take(b.reg, other);
+            for (int way = 0; way < 2; ++way) {
+                const char *got = way ? keep_renderer_mismatch(b, a) : keep_renderer_mismatch(a, b);
+                ++g_cases;
+                if (!got || strcmp(got, part.want)) { fprintf(stderr, "three parts shared, other %s: expected %s, got %s\n", part.name, part.want, got ? got : "(equal)"); ++g_bad; }
+            }
+            part.take(b.reg, equal);
+            ++g_cases;
+            if (const char *got = keep_renderer_mismatch(a, b)) { fprintf(stderr, "three parts shared, equal %s in another object: got %s\n", part.name, got); ++g_bad; }
+        }
+        InitCall a = full.call(), b = full.call();
+        a.reg = mine; b.reg = equal;
+        ++g_cases;
+        if (keep_renderer_mismatch(a, b)) { fprintf(stderr, "four distinct parts with equal bytes differ\n"); ++g_bad; }
     }
     printf("%d comparisons, %d with an unexpected answer\n", g_cases, g_bad);
     if (g_bad) return 1;

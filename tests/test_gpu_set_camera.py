@@ -12,6 +12,9 @@ buffers, pt_denoise_var with the history the moves leave behind, the display fil
 that comes or goes: from the second move on (the first makes the two scratch buffers of the device certificates), under
 PT_FLAG_TEMPORAL from the third (the first two captures allocate the history's two halves, as pt_init's do).
 
+A move after a re-registration: pt_set_textures / pt_set_meshes between pathtraceInit and the move leave the move -- fast or slow -- with
+the scene the renderer was initialised with, and serve the next full pathtraceInit.
+
 Slow path and refusals: a renderer whose fault word is set by hand is rebuilt by pt_init inside the call and renders the right frame; a
 camera of another resolution is refused and the old view goes on bit for bit; a move in one context leaves another alone."""
 import os
@@ -188,7 +191,14 @@ CHAINS = [
     ("through_nothing_demod_history", "cornell.txt", 97, 61, ("own", "away", "own", "side_0.3", "yaw_30"),
      dict(traceDepth=4, moments=True, temporal=True, demodulate=True, demod_history=True, spatial_variance=True, display_filter=True, max_batch=4),
      "batch", ("moments", "gbuffer", "denoise_var1", "pbo")),
+    # the table rules no chain above reaches: the groups' table (it has a buffer even when empty) and the rows kept in global memory ...
+    ("spheres64_grouped", "spheres64.txt", 48, 36, [((0, 0, 0), 0), ((0.5, 0, 0), 0), ((0.5, 0.3, -0.5), 10), ((0, 0, 0), -15)],
+     dict(traceDepth=3), "single", ()),
+    # ... and the three bump tables with the tables of a mesh that carries UVs
+    ("bump_mapped", "cornell_bump.txt", 48, 32, [((0, 0, 0), 0), ((0.4, 0.1, -0.3), 0), ((0.4, 0.1, -0.3), 12), ((-0.8, 0, 0.2), -20)],
+     dict(traceDepth=3), "single", ()),
 ]
+CHAIN_ENV = {"spheres64_grouped": {"PT_AMD_GROUPS": "1"}}      # (set for the whole walk, both ways)
 
 
 def _chain_cams(gpu, sc, name, poses):
@@ -198,9 +208,13 @@ def _chain_cams(gpu, sc, name, poses):
 
 
 @pytest.mark.parametrize("cid,name,W,H,poses,opts,schedule,reads", CHAINS, ids=[c[0] for c in CHAINS])
-def test_a_chain_of_moves_equals_the_chain_of_reinitialisations(gpu, cid, name, W, H, poses, opts, schedule, reads):
+def test_a_chain_of_moves_equals_the_chain_of_reinitialisations(gpu, monkeypatch, cid, name, W, H, poses, opts, schedule, reads):
     import torch
+    for k, v in CHAIN_ENV.get(cid, {}).items():
+        monkeypatch.setenv(k, v)
     sc = _scene(gpu, name, W, H)
+    if name == "cornell_bump.txt":                       # (as tests/test_gpu_keep_renderer.py loads it: a face-material array for its mesh)
+        sc.mesh_materials = {7: np.full(len(sc.meshes[7]), -1, np.int32)}
     cams = _chain_cams(gpu, sc, name, poses)
     pbo = torch.zeros((W * H, 4), dtype=torch.uint8, device="cuda") if "pbo" in reads else None
     reads = tuple(r for r in reads if r != "pbo")
@@ -266,6 +280,68 @@ def test_the_final_pose_against_the_cpu_oracle(gpu, oracle):
     got = b[-1]["accum"]
     rel = np.abs(got - want) / np.maximum(np.abs(want), 1e-6)
     assert int((rel > 1e-3).sum()) == 0                  # (the criterion of the package's smoke run)
+
+
+# ---- a move after a re-registration --------------------------------------------------------------------------------------------------------
+def _other_textures(gpu, sc, new):
+    new.textures = [np.ascontiguousarray(np.roll(np.asarray(t, F), 1, axis=-1)) for t in sc.textures]      # (every texel's channels rotated)
+    assert any(not np.array_equal(a, b) for a, b in zip(new.textures, sc.textures))
+    return lambda: gpu.set_textures(*gpu._scene_textures(new))
+
+
+def _other_meshes(gpu, sc, new):
+    new.meshes = {g: np.asarray(t, F) + F(0.25) for g, t in sc.meshes.items()}                             # (translated in object space)
+    return lambda: gpu.set_meshes(new.meshes, getattr(new, "mesh_normals", None), getattr(new, "mesh_materials", None))
+
+
+@pytest.mark.parametrize("name,other", [("cornell_textured.txt", _other_textures), ("cornell_mesh.txt", _other_meshes)], ids=["textures", "meshes"])
+def test_a_move_after_a_re_registration_renders_what_the_renderer_was_initialised_with(gpu, name, other):
+    """pt_set_textures / pt_set_meshes between pathtraceInit and the move: the move -- the fast way, and the slow one of a faulted renderer --
+    renders the scene the renderer was initialised with, and what was registered since serves the next full pathtraceInit."""
+    W, H = 48, 32
+    P = W * H
+    sc, new = _scene(gpu, name, W, H), _scene(gpu, name, W, H)
+    register_new = other(gpu, sc, new)
+    own = np.array(sc.camera, copy=True)
+    pose2 = _pose(sc, (0.4, 0.1, -0.3), 12)
+
+    def frame():
+        for it in (1, 2):
+            gpu.pathtrace(None, 0, it, readback=False)
+        return gpu.readback(P).copy(), _counters(gpu)
+
+    def init(scene, cam):
+        scene.camera[:] = cam
+        gpu.pathtraceInit(scene, traceDepth=3)
+        return frame()
+
+    def same(a, b):
+        return np.array_equal(_bits(a[0]), _bits(b[0])) and a[1] == b[1]
+
+    with gpu.renderer_from_test_library():
+        gpu.pathtraceFree()
+        try:
+            want_old = init(sc, pose2)
+            gpu.pathtraceFree()
+            want_new = init(new, pose2)
+            gpu.pathtraceFree()
+            assert not same(want_old, want_new)
+            for fault in (False, True):
+                init(sc, own)
+                register_new()
+                if fault:
+                    gpu.force_fault(2)
+                gpu.pathtraceSetCamera(pose2)
+                assert gpu.camera_move_info()["fast"] is (not fault)
+                assert same(frame(), want_old), "fault %r: the move rendered something else than the renderer's own scene" % fault
+                if not fault:                            # the full call over the moved renderer: what is registered now
+                    got = init(new, pose2)
+                    assert not same(got, want_old) and same(got, want_new)
+                gpu.pathtraceFree()
+        finally:
+            gpu.pathtraceFree()
+            sc.camera[:] = own
+            new.camera[:] = own
 
 
 # ---- slow path and refusals ---------------------------------------------------------------------------------------------------------------
