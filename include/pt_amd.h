@@ -143,6 +143,14 @@ enum {
                                     flagged renderer allocates and launches exactly what an unflagged one does, pt_free is unchanged, and an
                                     unflagged caller sees nothing new.  PT_ERR_INVALID from pt_group_init (groups re-initialise in place already).
                                     (Additive, no new function, no struct changed: the ABI version stays.) */
+    PT_FLAG_OBJECT_HISTORY = 4096,/* history follows moved objects (section "object history" below): with PT_FLAG_MOMENTS and PT_FLAG_TEMPORAL.
+                                    Between two renderers that both carry it the history passes a pt_init only when the old and the new scene
+                                    describe the same objects -- ngeoms, every geom's type and materialid, nmats and the materials' bytes, and
+                                    what is registered, byte for byte -- and is dropped otherwise: the caller's promise becomes a check.  The
+                                    geoms' poses may differ: the reprojection then goes through each primitive's own motion.  PT_ERR_INVALID
+                                    without either of the two flags, and from pt_group_init; every refusal of PT_FLAG_TEMPORAL stands.  A
+                                    renderer without the flag is what it was in every respect.  (Additive, no new function, no struct changed:
+                                    the ABI version stays.) */
     PT_FLAG_DIRECT_LIGHTING = 4/* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
@@ -561,6 +569,37 @@ int pt_iterate_until(int frame, int first_iter, const PtNoiseTarget *t, size_t t
  * PT_DEMOD_HISTORY_MIN_OWN is chosen by the study of tests/test_demod_history_cpu.py among 1, 2, 4, 8 and never (README, "Demodulated
  * history"). */
 #define PT_DEMOD_HISTORY_MIN_OWN 2
+
+/* ---- object history (PT_FLAG_OBJECT_HISTORY, with PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL; SVGF's reprojection through per-object motion;
+ * csrc/pt_temporal.h gives every operation under "MOTION", tests/temporal_motion_ref.py restates it).  No function of its own: a flag, and
+ * what pt_init does under it.
+ *   Without it history survives a camera move and nothing else: "the same scene" is the caller's promise, and a caller that nudges a sphere
+ *   either calls pt_free -- every pixel starts again, the nine tenths of the frame that did not change included -- or breaks the promise.
+ *   When history passes: between two renderers that BOTH carry the flag (where they differ it is dropped, as under PT_FLAG_DEMOD_HISTORY),
+ *   next to PT_FLAG_TEMPORAL's conditions, pt_init compares the call with what the live renderer was initialised with: ngeoms; every geom's
+ *   type and materialid; nmats and the materials' bytes; and what is registered NOW with pt_set_meshes / pt_set_textures / pt_set_bump_maps
+ *   against the renderer's own copies, byte for byte (PT_FLAG_KEEP_RENDERER's comparison: memcmp, no hash).  translation, rotation, scale
+ *   and the three matrices may differ.  Any other difference drops the history and the call goes on as a full call without one.  A refused
+ *   pt_init leaves everything as it was.
+ *   The motion table: for every primitive g the host forms A = T_old[g] Tinv_new[g] in double -- `transform` of the geoms the history's
+ *   view was rendered with, `inverseTransform` of the call's: the new world to the old -- and rounds rows 0..2 once to fp32, m[3][4]; and
+ *   the inverse transpose of A's linear part, by cofactors over the determinant in double, rounded once, G[3][3].  A primitive whose
+ *   transform and inverseTransform are byte-equal on both sides is UNMOVED (state 0), one with a non-finite number among the 21 has NO
+ *   HISTORY (state 2: a zero scale), every other MOVED (state 1).  The table belongs to the context's history, beside the old camera.  With
+ *   every primitive unmoved -- always so for the same-scene form and for a repeated identical call -- the history holds no table and the
+ *   renderer launches exactly the kernels of PT_FLAG_TEMPORAL.  Chains work as the camera's do: the capture at the next pt_init reprojects
+ *   with the table the going renderer got at ITS pt_init; only then is the table for the coming view made.
+ *   The reprojection of a moved primitive's pixel: its hit P and normal N go to the old world first, P' = m (P, 1), N' = G N / |G N| (no
+ *   history where that length is not positive), and PT_FLAG_TEMPORAL's projection and tap tests take P' and N'; the plane test's distance
+ *   stays the new hit's own.  An unmoved primitive's pixel takes PT_FLAG_TEMPORAL's bits.
+ *   The cap: light changes when an object moves -- its shadow, its bounce light -- while the unmoved background passes every test and keeps
+ *   the old light.  A view whose table holds a moved primitive therefore blends with the history's count capped at PT_OBJECT_HISTORY_MAX in
+ *   the place of PT_TEMPORAL_MAX_HISTORY, so that the new samples wash the stale light out faster.  Stale light is not detected otherwise.
+ *   PT_FLAG_DEMOD_HISTORY, PT_FLAG_DISPLAY_FILTER (which still allocates nothing and waits for nothing: pt_init uploads the table),
+ *   PT_FLAG_SPATIAL_VARIANCE, PT_FLAG_KEEP_RENDERER, direct lighting and the same-scene form go with it.  Out of scope: deforming meshes,
+ *   objects added or removed and material edits (each drops the history), a thin lens, groups and row shards.
+ * PT_OBJECT_HISTORY_MAX is chosen by the study of tests/test_temporal_motion_cpu.py among 4, 8, 16 and 32 (README, "Object history"). */
+#define PT_OBJECT_HISTORY_MAX 4.0f
 
 int pt_counters(PtCounters *out);     /* synchronises */
 int pt_counters_reset(void);

@@ -301,6 +301,21 @@ int pt_test_temporal_albedo(int form, int front, int w, int h, int samples, cons
                             const float *nrm_id4, const float *asum4, const float *hc4, const float *hn, const float *ha4, const float *hpos_t4,
                             const float *hnrm_id4, const float *cam16, float min_albedo, float *out4, float *out_n, float *out_a4, int reps, float *ms);
 int pt_test_history_albedo(int32_t *wh2, float *ha4);
+/* object history (pt_amd.h, csrc/pt_temporal.h under "MOTION").  A motion table is `nrows` rows of 24 floats (ptk::MotionRow): m[3][4] row by
+ * row, then (G[0][0..2], the bits of the int32 state), (G[1][0..2], 0), (G[2][0..2], 0).
+ * pt_test_motion_table (host only, no GPU needed): the table pt_init makes between the geoms a history's view was rendered with (`then`) and
+ * a call's (`now`), ngeoms rows, by the function pt_init calls; *any = 1 where a row has another state than 0 (pt_init keeps a table then).
+ * pt_test_history_motion: the table of the history THIS library's current context holds, as the device holds it -- *nrows = 0: none (no
+ * history, or every primitive unmoved); rows24 (or NULL) receives nrows * 24 floats, cap (or NULL) the count's cap the blends take.
+ * pt_test_temporal_motion: any (FORM, ALBEDO, MOTION) form of k_temporal over host arrays of any w x h, no renderer needed.  form 0 / 1 / 2 as
+ * pt_test_temporal's `capture`, 3: kTemporalFilterDemod (albedo 1 alone).  albedo 0: asum4, ha4 and out_a4 are not read (NULL allowed);
+ * motion 0: rows24, nrows and hist_cap are not read.  hist_cap: step 6's cap.  Everything else as pt_test_temporal_albedo takes it. */
+int pt_test_motion_table(const PtGeom *then, const PtGeom *now, int ngeoms, float *rows24, int32_t *any);
+int pt_test_history_motion(int32_t *nrows, float *rows24, float *cap);
+int pt_test_temporal_motion(int form, int albedo, int motion, int w, int h, int samples, const float *rgb_sum, const float *lum_sq_sum,
+                            const float *pos_t4, const float *nrm_id4, const float *asum4, const float *hc4, const float *hn, const float *ha4,
+                            const float *hpos_t4, const float *hnrm_id4, const float *cam16, const float *rows24, int nrows, float hist_cap,
+                            float min_albedo, float *out4, float *out_n, float *out_a4, int reps, float *ms);
 /* the noise statistics (pt_amd.h, csrc/pt_noise.h): k_noise_stats -- the kernel pt_noise_stats launches -- over host arrays of any w x h, no
  * renderer needed: rgb_sum = S (w * h * 3), lum_sq_sum = Q (w * h); out, tile_rel_var_host (or NULL) as pt_noise_stats.  tiles_per_wave: how many
  * tiles a wave of the grid takes, 1..64, 0 = the library's choice -- every value gives the same bits.  ms (or NULL) with

@@ -65,6 +65,10 @@ PT_FLAG_DEMOD_HISTORY = 1024
 PT_DEMOD_HISTORY_MIN_OWN = 2
 # a flag about cost alone (include/pt_amd.h): a full pt_init that repeats the live renderer's own call with another pose moves the camera in place
 PT_FLAG_KEEP_RENDERER = 2048
+# history follows moved objects (include/pt_amd.h, "object history"): the flag, and the cap of the history's count in a view that shows a
+# primitive in another pose than the history's
+PT_FLAG_OBJECT_HISTORY = 4096
+PT_OBJECT_HISTORY_MAX = 4.0
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -99,6 +103,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions", "pt_test_sphere_groups", "pt_test_group_tally",
     "pt_test_camera_resolved_device", "pt_test_last_camera_move", "pt_test_keep_mismatch",
+    "pt_test_motion_table", "pt_test_history_motion", "pt_test_temporal_motion",
 ]
 
 
@@ -285,6 +290,9 @@ def _bind(L, with_tests):
         L.pt_test_albedo.argtypes = [vp]
         L.pt_test_temporal_albedo.argtypes = [i32] * 5 + [vp] * 11 + [C.c_float] + [vp] * 3 + [i32, vp]
         L.pt_test_history_albedo.argtypes = [vp, vp]
+        L.pt_test_motion_table.argtypes = [vp, vp, i32, vp, vp]
+        L.pt_test_history_motion.argtypes = [vp, vp, vp]
+        L.pt_test_temporal_motion.argtypes = [i32] * 6 + [vp] * 12 + [i32, C.c_float, C.c_float] + [vp] * 3 + [i32, vp]
         L.pt_test_demodulate.argtypes = [i32] * 7 + [vp] * 6 + [C.c_float] * 4 + [vp] * 4 + [i32, vp]
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
@@ -473,8 +481,12 @@ _scene = None
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
                   mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False, demodulate=False,
-                  demod_history=False, keep=False):
+                  demod_history=False, keep=False, object_history=False):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    object_history: PT_FLAG_OBJECT_HISTORY (with moments=True and temporal=True) -- calling pathtraceInit AGAIN over the live renderer with the
+    same objects in other poses (geoms' types and materials, the materials and everything registered equal byte for byte; translation,
+    rotation, scale and the matrices free) carries the history over and reprojects it through each primitive's own motion; any other change
+    of the scene drops the history.  History passes only between renderers that agree on the flag.
     keep: PT_FLAG_KEEP_RENDERER -- a flag about cost alone: calling pathtraceInit AGAIN over the live renderer with the same scene, arguments
     and registered meshes, textures and height maps (compared byte for byte) and another pose moves the camera in place, as pathtraceSetCamera
     does; anything else is the full call.  The result is the full call's bit for bit either way.
@@ -519,6 +531,8 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_DEMOD_HISTORY
     if keep:
         flags |= PT_FLAG_KEEP_RENDERER
+    if object_history:
+        flags |= PT_FLAG_OBJECT_HISTORY
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
     geoms = np.ascontiguousarray(scene.geoms)
@@ -997,7 +1011,8 @@ def test_demodulate(form, w, h, samples, levels, asum, pos_t, nrm_id, rgb_sum=No
 
 def test_history():
     """pt_test_history: the history the test library's current context holds (inside renderer_from_test_library) -- None, or a dict of hc
-    (H, W, 4), hn (H, W), hpos_t, hnrm_id (H, W, 4) and cam (16,)."""
+    (H, W, 4), hn (H, W), hpos_t, hnrm_id (H, W, 4) and cam (16,), and (pt_test_history_motion) motion: the motion table as the device holds it,
+    (ngeoms, 24) float32 as test_motion_table returns it, or None where the history holds none; cap: the count's cap the blends take."""
     T = test_lib()
     wh = np.zeros(2, np.int32)
     _tcheck(T.pt_test_history(_p(wh), None, None, None, None, None))
@@ -1007,7 +1022,49 @@ def test_history():
     hc, hn, hpos, hnrm = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32), np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
     cam = np.empty(16, np.float32)
     _tcheck(T.pt_test_history(_p(wh), _p(hc), _p(hn), _p(hpos), _p(hnrm), _p(cam)))
-    return dict(hc=hc, hn=hn, hpos_t=hpos, hnrm_id=hnrm, cam=cam)
+    n, cap = np.zeros(1, np.int32), np.zeros(1, np.float32)
+    _tcheck(T.pt_test_history_motion(_p(n), None, _p(cap)))
+    motion = None
+    if int(n[0]) > 0:
+        motion = np.empty((int(n[0]), 24), np.float32)
+        _tcheck(T.pt_test_history_motion(_p(n), _p(motion), None))
+    return dict(hc=hc, hn=hn, hpos_t=hpos, hnrm_id=hnrm, cam=cam, motion=motion, cap=float(cap[0]))
+
+
+def test_motion_table(geoms_then, geoms_now):
+    """pt_test_motion_table (host only): the motion table pt_init makes under object_history=True between the geoms the history's view was
+    rendered with and a call's (GEOM_DTYPE records of equal number).  Returns (rows (n, 24) float32, any): a row is m[3][4] row by row, then
+    (G[0], state bits), (G[1], 0), (G[2], 0) -- rows[:, 15].view(int32) is the state 0 / 1 / 2; any: a row has another state than 0."""
+    a, b = np.ascontiguousarray(geoms_then), np.ascontiguousarray(geoms_now)
+    if len(a) != len(b) or len(a) < 1:
+        raise ValueError("test_motion_table: two geom arrays of one length >= 1")
+    rows, flag = np.zeros((len(a), 24), np.float32), np.zeros(1, np.int32)
+    _tcheck(test_lib().pt_test_motion_table(_p(a), _p(b), len(a), _p(rows), _p(flag)))
+    return rows, bool(flag[0])
+
+
+def test_temporal_motion(form, albedo, motion, w, h, samples, rgb_sum, lum_sq_sum, pos_t, nrm_id, hc, hn, hpos_t, hnrm_id, cam16, rows=None,
+                         hist_cap=PT_OBJECT_HISTORY_MAX, asum=None, ha=None, min_albedo=PT_DEMOD_MIN_ALBEDO, timing_reps=0):
+    """Any (FORM, ALBEDO, MOTION) form of k_temporal over host arrays (test library, no renderer; pt_test_temporal_motion): test_temporal's
+    arrays; form 0 / 1 / 2 / 3: the filter, capture, moments form and -- albedo=True alone -- the fused demodulating filter; albedo=True: asum and
+    ha as test_temporal_albedo takes them; motion=True: rows (n, 24) as test_motion_table returns them, hist_cap step 6's cap.  Returns
+    (out (h * w, 4), out_n (h * w,) or None, (Ab, tot) (h * w, 4) or None); timing_reps > 0: also the kernel times in ms."""
+    f = lambda a, k: np.ascontiguousarray(a, np.float32).reshape(w * h * k)
+    S, Q, pos, nrm = f(rgb_sum, 3), f(lum_sq_sum, 1), f(pos_t, 4), f(nrm_id, 4)
+    Hc, Hn, Hpos, Hnrm = f(hc, 4), f(hn, 1), f(hpos_t, 4), f(hnrm_id, 4)
+    A = f(asum, 4) if albedo else None
+    Ha = f(ha, 4) if albedo else None
+    R = np.ascontiguousarray(rows, np.float32).reshape(-1, 24) if motion else None
+    cam = np.ascontiguousarray(cam16, np.float32).reshape(16)
+    out, out_n = np.empty((w * h, 4), np.float32), np.empty(w * h, np.float32)
+    out_a = np.empty((w * h, 4), np.float32) if albedo else None
+    ms = np.zeros(max(timing_reps, 1), np.float32)
+    q = lambda a: None if a is None else _p(a)
+    _tcheck(test_lib().pt_test_temporal_motion(int(form), int(bool(albedo)), int(bool(motion)), w, h, samples, _p(S), _p(Q), _p(pos), _p(nrm), q(A),
+                                               _p(Hc), _p(Hn), q(Ha), _p(Hpos), _p(Hnrm), _p(cam), q(R), 0 if R is None else len(R), float(hist_cap),
+                                               float(min_albedo), _p(out), _p(out_n), q(out_a), timing_reps, _p(ms) if timing_reps > 0 else None))
+    res = (out, out_n if form in (1, 2) else None, out_a)
+    return (res, ms) if timing_reps > 0 else res
 
 
 def test_temporal_albedo(form, w, h, samples, rgb_sum, lum_sq_sum, pos_t, nrm_id, asum, hc, hn, ha, hpos_t, hnrm_id, cam16, front=0,

@@ -183,6 +183,12 @@ struct History {
     int cur = 0, W = 0, H = 0;
     bool live = false;
     bool albedo = false;            // the renderer that made it carried PT_FLAG_DEMOD_HISTORY: ha[cur] is live too
+    // PT_FLAG_OBJECT_HISTORY: the geoms of the view the history was captured from -- the poses it is in --, and, while the renderer that
+    // reads it shows a primitive in another pose, the motion table (pt_temporal.h, MOTION) with its host copy and the cap that goes with it
+    std::vector<PtGeom> pose;
+    DevBuf<float4> motion;          // MotionRow per primitive; none: every primitive unmoved -- PT_FLAG_TEMPORAL's launches
+    std::vector<MotionRow> motionHost;
+    float cap = PT_TEMPORAL_MAX_HISTORY;
 };
 
 // How a scene table differs from the plain one -- a buffer where the plan's vector is not empty, of its size, refreshed by a camera move
@@ -957,9 +963,47 @@ TemporalCam temporal_camera(const KParams &k) {
     return c;
 }
 
+// PT_FLAG_OBJECT_HISTORY: the motion table between the geoms the history's view was rendered with and the coming view's (include/pt_amd.h,
+// "object history"; tests/temporal_motion_ref.py restates it in float64).  Matrices are column-major, m[col * 4 + row]; every double
+// operation is one IEEE operation in the order written (-ffp-contract=off holds for the host too).  An unmoved primitive's row holds the
+// identity, which no kernel reads.  Answers whether a row has another state than 0.
+bool motion_table(const PtGeom *then, const PtGeom *now, int n, std::vector<MotionRow> &rows) {
+    rows.assign((size_t)(n > 0 ? n : 0), MotionRow{});
+    bool any = false;
+    for (int g = 0; g < n; ++g) {
+        MotionRow &r = rows[(size_t)g];
+        float *const G[3] = {r.g0, r.g1, r.g2};
+        if (!memcmp(then[g].transform, now[g].transform, sizeof now[g].transform) &&
+            !memcmp(then[g].inverseTransform, now[g].inverseTransform, sizeof now[g].inverseTransform)) {
+            for (int k = 0; k < 3; ++k) { r.m[k][k] = 1.0f; G[k][k] = 1.0f; }
+            r.state = 0;
+            continue;
+        }
+        any = true;
+        const float *T = then[g].transform, *Ti = now[g].inverseTransform;
+        double A[3][4];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 4; ++j)
+                A[i][j] = (((double)T[0 + i] * (double)Ti[j * 4 + 0] + (double)T[4 + i] * (double)Ti[j * 4 + 1]) + (double)T[8 + i] * (double)Ti[j * 4 + 2]) +
+                          (double)T[12 + i] * (double)Ti[j * 4 + 3];
+        const double c[3][3] = {{A[1][1] * A[2][2] - A[1][2] * A[2][1], A[1][2] * A[2][0] - A[1][0] * A[2][2], A[1][0] * A[2][1] - A[1][1] * A[2][0]},
+                                {A[0][2] * A[2][1] - A[0][1] * A[2][2], A[0][0] * A[2][2] - A[0][2] * A[2][0], A[0][1] * A[2][0] - A[0][0] * A[2][1]},
+                                {A[0][1] * A[1][2] - A[0][2] * A[1][1], A[0][2] * A[1][0] - A[0][0] * A[1][2], A[0][0] * A[1][1] - A[0][1] * A[1][0]}};
+        const double det = (A[0][0] * c[0][0] + A[0][1] * c[0][1]) + A[0][2] * c[0][2];
+        bool finite = true;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 4; ++j) { r.m[i][j] = (float)A[i][j]; finite = finite && std::isfinite(r.m[i][j]); }
+            for (int j = 0; j < 3; ++j) { G[i][j] = (float)(c[i][j] / det); finite = finite && std::isfinite(G[i][j]); }
+        }
+        r.state = finite ? 1 : 2;
+    }
+    return any;
+}
+
 // k_temporal over the renderer and its context's history, on its stream: the blend of `samples` committed iterations with the history -- the
 // halves a live history holds; none, or useHistory false: every pixel goes without -- into out (and outN: the capture and the moments form);
-// needs the guides (ensure_guides).  ALBEDO (PT_FLAG_DEMOD_HISTORY): the blend of the albedo too, into outA.
+// needs the guides (ensure_guides).  ALBEDO (PT_FLAG_DEMOD_HISTORY): the blend of the albedo too, into outA.  A live history that holds a
+// motion table (PT_FLAG_OBJECT_HISTORY with a primitive in another pose) takes the MOTION form; every other launch is what it was.
 template <int FORM, bool ALBEDO = false>
 int temporal_blend(float samples, float4 *out, float *outN, bool useHistory = true, float4 *outA = nullptr) {
     const State &S = R();
@@ -977,8 +1021,36 @@ int temporal_blend(float samples, float4 *out, float *outN, bool useHistory = tr
     T.ha = live && ALBEDO ? hs.ha[hs.cur].p : nullptr;
     T.asum = S.albedo.p; T.outA = outA; T.eps = PT_DEMOD_MIN_ALBEDO;
     if (ALBEDO && (!outA || !T.asum || (live && !hs.albedo))) return fail(PT_ERR_INVALID, "internal error: an albedo blend without its images");
-    hipLaunchKernelGGL((k_temporal<FORM, ALBEDO>), dim3((unsigned)(((size_t)S.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, S.stream, T);
+    const bool motion = live && hs.motion.p != nullptr;
+    T.motion = motion ? hs.motion.p : nullptr;
+    T.motionN = motion ? (int)hs.motionHost.size() : 0;
+    T.histCap = motion ? hs.cap : PT_TEMPORAL_MAX_HISTORY;
+    const dim3 grid((unsigned)(((size_t)S.P + kBlock - 1) / kBlock));
+    if (motion) hipLaunchKernelGGL((k_temporal<FORM, ALBEDO, true>), grid, dim3(kBlock), 0, S.stream, T);
+    else hipLaunchKernelGGL((k_temporal<FORM, ALBEDO>), grid, dim3(kBlock), 0, S.stream, T);
     HIPCHECK(hipGetLastError());
+    return PT_OK;
+}
+
+// one form of k_temporal over arguments of the caller's, on the null stream (the test library's pt_test_temporal_motion)
+template <int FORM, bool ALBEDO>
+void temporal_motion_launch(bool motion, dim3 grid, const TemporalArgs &T) {
+    if (motion) hipLaunchKernelGGL((k_temporal<FORM, ALBEDO, true>), grid, dim3(kBlock), 0, nullptr, T);
+    else hipLaunchKernelGGL((k_temporal<FORM, ALBEDO, false>), grid, dim3(kBlock), 0, nullptr, T);
+}
+
+// PT_FLAG_OBJECT_HISTORY, behind the capture (or where none was due): the table between the poses the history is in and the coming view's
+// geoms -- none where the context holds no history, where it was not captured under the flag, or where no primitive moved.
+int refresh_motion(History &hs, bool flagged, const PtGeom *geoms, int ngeoms) {
+    hs.motion.release();
+    hs.motionHost.clear();
+    hs.cap = PT_TEMPORAL_MAX_HISTORY;
+    if (!flagged || !hs.live || hs.pose.empty() || (int)hs.pose.size() != ngeoms) return PT_OK;
+    std::vector<MotionRow> rows;
+    if (!motion_table(hs.pose.data(), geoms, ngeoms, rows)) return PT_OK;
+    PTCHECK(hs.motion.upload(reinterpret_cast<const float4 *>(rows.data()), rows.size() * kMotionRowVec));
+    hs.motionHost = std::move(rows);
+    hs.cap = PT_OBJECT_HISTORY_MAX;
     return PT_OK;
 }
 
@@ -1010,6 +1082,9 @@ int capture_history() {
     hs.cur = nxt; hs.W = S.prm.W; hs.H = S.prm.H;
     hs.live = true;
     hs.albedo = withAlbedo;
+    // PT_FLAG_OBJECT_HISTORY: the history is in this view's poses now (the table it was read through is replaced by the coming view's)
+    if (S.flags & PT_FLAG_OBJECT_HISTORY) hs.pose = S.inGeoms;
+    else hs.pose.clear();
     return PT_OK;
 }
 
@@ -1357,6 +1432,17 @@ int retire_view(bool &keepHistory, const char *who) {
     return rc == PT_ERR_INVALID ? fail(PT_ERR_HIP, "%s: the capture of the old view failed: %s", who, std::string(g_err).c_str()) : rc;
 }
 
+// PT_FLAG_OBJECT_HISTORY: does a pt_init call describe the objects the live renderer was initialised with?  ngeoms, every geom's type and
+// materialid, nmats and the materials' bytes, and what is registered now against the renderer's own copies (registered_mismatch: byte for
+// byte, no hash).  translation, rotation, scale and the three matrices may differ.
+bool same_objects(const State &S, const PtGeom *geoms, int ngeoms, const PtMaterial *mats, int nmats, const Registered &reg) {
+    if (ngeoms != (int)S.inGeoms.size() || nmats != (int)S.inMats.size()) return false;
+    for (int g = 0; g < ngeoms; ++g)
+        if (geoms[g].type != S.inGeoms[(size_t)g].type || geoms[g].materialid != S.inGeoms[(size_t)g].materialid) return false;
+    if (nmats > 0 && memcmp(mats, S.inMats.data(), (size_t)nmats * sizeof(PtMaterial))) return false;
+    return registered_mismatch(reg, S.initReg) == nullptr;
+}
+
 // the host's copies of the camera-invariant tables, once the device holds them
 void drop_camera_invariant(SceneTables &tab, ScenePlan &plan) {
     (void)tab.for_each(nullptr, plan, plan.mesh, plan.grouped, [](const auto &, const auto *, auto &table, TableRule rule) {
@@ -1399,8 +1485,13 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
     // PT_FLAG_TEMPORAL on the renderer that goes and on the one that comes, the same frame size and device: the context's history lives on,
     // and the old view -- if it committed anything -- is blended into it first, on the old renderer's stream (free_renderer waits for it)
     // (PT_FLAG_DEMOD_HISTORY: only between two renderers that agree on it -- a history with albedo and one without are different things)
-    bool keepHistory = R().init && (R().flags & plan.flags & PT_FLAG_TEMPORAL) && !((R().flags ^ plan.flags) & PT_FLAG_DEMOD_HISTORY) &&
+    // (PT_FLAG_OBJECT_HISTORY: likewise only between two renderers that agree on it -- and between two that carry it only where the old and
+    // the new scene describe the same objects, their poses aside: the caller's promise as a check)
+    bool keepHistory = R().init && (R().flags & plan.flags & PT_FLAG_TEMPORAL) &&
+                       !((R().flags ^ plan.flags) & (PT_FLAG_DEMOD_HISTORY | PT_FLAG_OBJECT_HISTORY)) &&
                        R().prm.W == plan.prm.W && R().prm.H == plan.prm.H && (o.device < 0 || o.device == R().device);
+    const bool objectHistory = (plan.flags & PT_FLAG_OBJECT_HISTORY) != 0;
+    if (keepHistory && objectHistory && !same_objects(R(), geoms, ngeoms, mats, nmats, reg)) keepHistory = false;
     PTCHECK(retire_view(keepHistory, "pt_init"));
     free_renderer(keepHistory);
     phase_end(1);      // the capture of history, the drain and the free
@@ -1412,6 +1503,7 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
     if (o.device >= 0) HIPCHECK(hipSetDevice(o.device));
     HIPCHECK(hipGetDevice(&S.device));
     S.stream = (hipStream_t)o.stream;
+    PTCHECK(refresh_motion(S.hist, objectHistory, geoms, ngeoms));      // (the capture, where one was due, is behind us)
     HIPCHECK(hipHostMalloc((void **)&S.hostFault, sizeof(uint32_t), hipHostMallocMapped));
     *S.hostFault = 0u;
     HIPCHECK(hipHostGetDevicePointer((void **)&S.hostFaultDev, S.hostFault, 0));
@@ -1662,6 +1754,8 @@ int set_camera(const PtCamera *cam) {
         }
         PTCHECK(retire_view(keepHistory, "pt_init (camera move)"));
         if (!keepHistory) S.hist = History();
+        // (PT_FLAG_OBJECT_HISTORY: the same scene in the poses just captured -- no table; a history no capture was due for keeps its poses)
+        PTCHECK(refresh_motion(S.hist, (S.flags & PT_FLAG_OBJECT_HISTORY) != 0, S.inGeoms.data(), (int)S.inGeoms.size()));
     }
     // From here on the renderer is overwritten: a HIP call that fails leaves the context without a renderer, as pt_init's do.
     const auto body = [&]() -> int {

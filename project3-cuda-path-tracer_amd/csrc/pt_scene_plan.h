@@ -79,25 +79,9 @@ template <typename T>
 inline bool same_bytes(const std::vector<T> &a, const std::vector<T> &b) {
     return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(T)));
 }
-inline const char *keep_renderer_mismatch(const InitCall &now, const InitCall &then) {
-    if (!now.o || !then.o) return "options";
-    if (now.W != then.W || now.H != then.H) return "resolution";
-    if (now.ngeoms != then.ngeoms || now.ngeoms < 0 || (now.ngeoms > 0 && (!now.geoms || !then.geoms))) return "geom count";
-    if (now.nmats != then.nmats || now.nmats < 0 || (now.nmats > 0 && (!now.mats || !then.mats))) return "material count";
-    if (now.ngeoms > 0 && memcmp(now.geoms, then.geoms, (size_t)now.ngeoms * sizeof(PtGeom))) return "geoms";
-    if (now.nmats > 0 && memcmp(now.mats, then.mats, (size_t)now.nmats * sizeof(PtMaterial))) return "materials";
-    if (now.traceDepth != then.traceDepth) return "traceDepth";
-    const PtOptions &a = *now.o, &b = *then.o;
-    if (a.shard_rank != b.shard_rank || a.shard_count != b.shard_count) return "shard";
-    if (a.device != b.device) return "device";
-    if (a.flags != b.flags) return "flags";
-    if (a.pipeline_depth != b.pipeline_depth) return "pipeline_depth";
-    if (a.max_batch != b.max_batch) return "max_batch";
-    if (a.stream != b.stream) return "stream";
-    if (a.accum_dev != b.accum_dev) return "accum_dev";
-    if (memcmp(&a.lens_radius, &b.lens_radius, sizeof(float))) return "lens_radius";
-    if (memcmp(&a.focal_distance, &b.focal_distance, sizeof(float))) return "focal_distance";
-    const Registered &p = now.reg, &q = then.reg;
+// what two sets of registrations differ in -- counts, sizes and bindings, the triangle, normal, face-material and UV arrays, the texels, all
+// byte for byte --, or NULL (PT_FLAG_KEEP_RENDERER; PT_FLAG_OBJECT_HISTORY's scene comparison)
+inline const char *registered_mismatch(const Registered &p, const Registered &q) {
     if (p.meshes != q.meshes) {
         if (p.meshes->size() != q.meshes->size()) return "mesh count";
         for (size_t i = 0; i < p.meshes->size(); ++i) {
@@ -134,6 +118,26 @@ inline const char *keep_renderer_mismatch(const InitCall &now, const InitCall &t
         }
     }
     return nullptr;
+}
+inline const char *keep_renderer_mismatch(const InitCall &now, const InitCall &then) {
+    if (!now.o || !then.o) return "options";
+    if (now.W != then.W || now.H != then.H) return "resolution";
+    if (now.ngeoms != then.ngeoms || now.ngeoms < 0 || (now.ngeoms > 0 && (!now.geoms || !then.geoms))) return "geom count";
+    if (now.nmats != then.nmats || now.nmats < 0 || (now.nmats > 0 && (!now.mats || !then.mats))) return "material count";
+    if (now.ngeoms > 0 && memcmp(now.geoms, then.geoms, (size_t)now.ngeoms * sizeof(PtGeom))) return "geoms";
+    if (now.nmats > 0 && memcmp(now.mats, then.mats, (size_t)now.nmats * sizeof(PtMaterial))) return "materials";
+    if (now.traceDepth != then.traceDepth) return "traceDepth";
+    const PtOptions &a = *now.o, &b = *then.o;
+    if (a.shard_rank != b.shard_rank || a.shard_count != b.shard_count) return "shard";
+    if (a.device != b.device) return "device";
+    if (a.flags != b.flags) return "flags";
+    if (a.pipeline_depth != b.pipeline_depth) return "pipeline_depth";
+    if (a.max_batch != b.max_batch) return "max_batch";
+    if (a.stream != b.stream) return "stream";
+    if (a.accum_dev != b.accum_dev) return "accum_dev";
+    if (memcmp(&a.lens_radius, &b.lens_radius, sizeof(float))) return "lens_radius";
+    if (memcmp(&a.focal_distance, &b.focal_distance, sizeof(float))) return "focal_distance";
+    return registered_mismatch(now.reg, then.reg);
 }
 
 // bits of one code of a path's material history (ptk::PathPool): 2 * material + (specular ? 1 : 0) < 2 nmats -- max(1, ceil(log2(2 nmats)))
@@ -353,6 +357,8 @@ int check_scene(const SceneIn &in) {
     }
     if ((o.flags & PT_FLAG_DEMOD_HISTORY) && (~o.flags & (PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL | PT_FLAG_DEMODULATE)))
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMOD_HISTORY needs PT_FLAG_MOMENTS, PT_FLAG_TEMPORAL and PT_FLAG_DEMODULATE (it joins the two)");
+    if ((o.flags & PT_FLAG_OBJECT_HISTORY) && (~o.flags & (PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL)))
+        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_OBJECT_HISTORY needs PT_FLAG_MOMENTS and PT_FLAG_TEMPORAL (it is the history that follows the objects)");
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;

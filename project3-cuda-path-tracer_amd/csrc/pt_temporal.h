@@ -42,12 +42,27 @@
 //               -- the bits of k_temporal<kTemporalFilter, true> followed by k_demodulate<true>
 // Without history Ab = (0 * 0 + Asum) / n = Asum / n: the bits demodAlbedo forms before its floor.
 // Without history step 7 is 0 * 0 + S = S over n and step 8 is meanAndVariance(S, Q) to the bit (sums are never -0: they grow from +0).
+// ---- MOTION (PT_FLAG_OBJECT_HISTORY: the history follows primitives that moved between the two views; tests/temporal_motion_ref.py restates it) ----
+//   inputs      the motion table, one row of 96 bytes per primitive (MotionRow): m[3][4], rows 0..2 of A = T_old Tinv_new -- the new world to the
+//               old --, G[3][3], the inverse transpose of A's linear part, and the primitive's state (0 unmoved, 1 moved, 2 no history); the host
+//               forms both in double and rounds once (pt_api.hip: motion_table).  capH: the cap step 6 takes in the place of `cap`
+//               (PT_OBJECT_HISTORY_MAX for a table that holds a row of another state than 0)
+//   1'          st = row[id].state (an id past the table: 0)
+//               st == 2: no history
+//               st == 1: P'.k = ((m[k][0] * P.x + m[k][1] * P.y) + m[k][2] * P.z) + m[k][3];  g.k = (G[k][0] * N.x + G[k][1] * N.y) + G[k][2] * N.z;
+//                        l = (g.x * g.x + g.y * g.y) + g.z * g.z;  !(l > 0): no history (a NaN lands here);  N' = g / sqrtf(l)
+//               st == 0: P' = P, N' = N -- the values themselves, not their product with an identity: an unmoved primitive takes the bits above
+//   2 .. 5      with P' for P and N' for N: d = P' - e, dot(N_q, N') >= c_n, |dot(P_q - P', N')| <= c_p * t.  t stays the new hit's own distance,
+//               id_q == id stays
+//   6           Nh = hn < capH ? hn : capH.  Steps 7, 8 and all of ALBEDO as above (the capture's and the moments form's counts keep `cap`)
+// The MOTION = false forms are the kernels they were before.
 // cap, c_n, c_p, w_min: PT_TEMPORAL_MAX_HISTORY, _NORMAL_DOT, _PLANE_FRACTION, _MIN_WEIGHT of include/pt_amd.h.
 //
 // Cost: a gather.  A pixel reads its own 60 bytes (S 12, Q 4, two guide float4s 32, and 12 of padding it does not use), up to four taps of
 // 52 bytes from four arrays -- neighbouring pixels project to neighbouring old pixels, so a wave's taps fall into the cache lines its
 // neighbours fetch -- and writes 16 (filter) or 20 bytes (capture).  ALBEDO: a tap reads 68 bytes from five arrays, a pixel 16 more of its own
-// (Asum) and writes 16 more (outA).
+// (Asum) and writes 16 more (outA).  MOTION: a pixel reads 16 bytes of its primitive's row for the state, and 80 more where it moved -- per
+// lane, but a wave shows few primitives: the rows are cache lines its lanes share.
 #pragma once
 #include "pt_denoise.h"
 
@@ -76,22 +91,62 @@ struct TemporalArgs {
     const float4 *asum;               // the current view's albedo sums
     float4 *outA;                     // (Ab, tot)
     float eps;                        // kTemporalFilterDemod: PT_DEMOD_MIN_ALBEDO
+    // MOTION alone reads what follows
+    const float4 *motion;             // MotionRow[motionN] as six float4 per primitive
+    int motionN;
+    float histCap;                    // step 6's cap
 };
+
+// a primitive's row of the motion table (PT_FLAG_OBJECT_HISTORY): six float4, so that a lane fetches it in 16-byte loads -- g0 first, for the state
+struct MotionRow {
+    float m[3][4];                    // rows 0..2 of A: new world -> old world
+    float g0[3]; int state;           // row 0 of G, the inverse transpose of A's linear part; 0 unmoved, 1 moved, 2 no history
+    float g1[3], pad1;
+    float g2[3], pad2;
+};
+static_assert(sizeof(MotionRow) == 96, "six float4 per primitive");
+enum { kMotionRowVec = 6 };
 
 enum { kTemporalFilter = 0, kTemporalCapture = 1, kTemporalMoments = 2, kTemporalFilterDemod = 3 };
 
-template <int FORM, bool ALBEDO = false>
+template <int FORM, bool ALBEDO = false, bool MOTION = false>
 __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
     static_assert(FORM != kTemporalFilterDemod || ALBEDO, "the fused front divides by the blended albedo");
     const int npix = A.W * A.H;
     const int pix = blockIdx.x * kBlock + threadIdx.x;
     if (pix >= npix) return;
     const float cap = PT_TEMPORAL_MAX_HISTORY;
-    const float4 pp = A.posT[pix], np = A.nrmId[pix];
+    float4 pp = A.posT[pix], np = A.nrmId[pix];
     const int id = __float_as_int(np.w);
+    const float capH = MOTION ? A.histCap : cap;
+    bool follow = true;               // MOTION, step 1': false where the primitive's row says there is no history to follow
+    if (MOTION && A.hn != nullptr && id >= 0 && id < A.motionN) {
+        const float4 *row = A.motion + (size_t)id * kMotionRowVec;
+        const float4 g0 = row[3];
+        const int st = __float_as_int(g0.w);
+        if (st == 1) {
+            const float4 m0 = row[0], m1 = row[1], m2r = row[2], g1 = row[4], g2 = row[5];
+            const float px = ((m0.x * pp.x + m0.y * pp.y) + m0.z * pp.z) + m0.w;
+            const float py = ((m1.x * pp.x + m1.y * pp.y) + m1.z * pp.z) + m1.w;
+            const float pz = ((m2r.x * pp.x + m2r.y * pp.y) + m2r.z * pp.z) + m2r.w;
+            const float gx = (g0.x * np.x + g0.y * np.y) + g0.z * np.z;
+            const float gy = (g1.x * np.x + g1.y * np.y) + g1.z * np.z;
+            const float gz = (g2.x * np.x + g2.y * np.y) + g2.z * np.z;
+            const float l = (gx * gx + gy * gy) + gz * gz;
+            if (l > 0.0f) {
+                const float len = __builtin_sqrtf(l);
+                pp.x = px; pp.y = py; pp.z = pz;
+                np.x = gx / len; np.y = gy / len; np.z = gz / len;
+            } else {
+                follow = false;
+            }
+        } else if (st != 0) {
+            follow = false;
+        }
+    }
     float hcx = 0.0f, hcy = 0.0f, hcz = 0.0f, hcw = 0.0f, Nh = 0.0f;
     float hax = 0.0f, hay = 0.0f, haz = 0.0f;
-    if (A.hn != nullptr && id >= 0) {
+    if (A.hn != nullptr && id >= 0 && (!MOTION || follow)) {
         const TemporalCam &c = A.cam;
         const float dx = pp.x - c.e[0], dy = pp.y - c.e[1], dz = pp.z - c.e[2];
         const float s = (c.r0[0] * dx + c.r0[1] * dy) + c.r0[2] * dz;
@@ -143,7 +198,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal(TemporalArgs A) {
                 if (sumW > PT_TEMPORAL_MIN_WEIGHT) {
                     hcx = sx / sumW; hcy = sy / sumW; hcz = sz / sumW; hcw = sw / sumW;
                     const float hn = sumN / sumW;
-                    Nh = hn < cap ? hn : cap;
+                    Nh = hn < capH ? hn : capH;
                     if (ALBEDO) { hax = ax / sumW; hay = ay / sumW; haz = az / sumW; }
                 }
             }

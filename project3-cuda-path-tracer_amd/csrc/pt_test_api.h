@@ -1541,6 +1541,93 @@ int pt_test_temporal_albedo(int form, int front, int w, int h, int samples, cons
     return PT_OK;
 }
 
+int pt_test_motion_table(const PtGeom *then, const PtGeom *now, int ngeoms, float *rows24, int32_t *any) {
+    if (!then || !now || ngeoms < 1 || !rows24 || !any) return fail(PT_ERR_INVALID, "pt_test_motion_table: bad argument");
+    std::vector<MotionRow> rows;
+    *any = motion_table(then, now, ngeoms, rows) ? 1 : 0;
+    memcpy(rows24, rows.data(), rows.size() * sizeof(MotionRow));
+    return PT_OK;
+}
+
+int pt_test_history_motion(int32_t *nrows, float *rows24, float *cap) {
+    if (!nrows) return fail(PT_ERR_INVALID, "pt_test_history_motion: null");
+    const History &hs = R().hist;
+    const bool has = hs.live && hs.motion.p;
+    *nrows = has ? (int32_t)hs.motionHost.size() : 0;
+    if (cap) *cap = hs.cap;
+    if (!has) return PT_OK;
+    // (the device's bytes: what the kernels read)
+    if (rows24) HIPCHECK(hipMemcpy(rows24, hs.motion.p, hs.motionHost.size() * sizeof(MotionRow), hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+int pt_test_temporal_motion(int form, int albedo, int motion, int w, int h, int samples, const float *rgb_sum, const float *lum_sq_sum,
+                            const float *pos_t4, const float *nrm_id4, const float *asum4, const float *hc4, const float *hn, const float *ha4,
+                            const float *hpos_t4, const float *hnrm_id4, const float *cam16, const float *rows24, int nrows, float hist_cap,
+                            float min_albedo, float *out4, float *out_n, float *out_a4, int reps, float *ms) {
+    NEED_GPU();
+    const bool needN = form == 1 || form == 2;
+    if (form < 0 || form > 3 || (albedo != 0 && albedo != 1) || (motion != 0 && motion != 1) || (form == 3 && !albedo) || w < 1 || h < 1 ||
+        (long long)w * h > (1ll << 30) || samples < 1 || !rgb_sum || !lum_sq_sum || !pos_t4 || !nrm_id4 || !hc4 || !hn || !hpos_t4 || !hnrm_id4 || !cam16 ||
+        !out4 || (needN && !out_n) || (albedo && (!asum4 || !ha4 || !out_a4 || !(min_albedo > 0.0f))) || (motion && (!rows24 || nrows < 1 || nrows > (1 << 24))) ||
+        (ms && reps < 1))
+        return fail(PT_ERR_INVALID, "pt_test_temporal_motion: bad argument");
+    const size_t P = (size_t)w * h;
+    DevBuf<float> S, Q, Hn, outN;
+    DevBuf<float4> pos, nrm, Asum, Hc, Ha, Hpos, Hnrm, out, outA, rows;
+    PTCHECK(S.upload(rgb_sum, P * 3));
+    PTCHECK(Q.upload(lum_sq_sum, P));
+    PTCHECK(Hn.upload(hn, P));
+    PTCHECK(pos.upload(reinterpret_cast<const float4 *>(pos_t4), P));
+    PTCHECK(nrm.upload(reinterpret_cast<const float4 *>(nrm_id4), P));
+    PTCHECK(Hc.upload(reinterpret_cast<const float4 *>(hc4), P));
+    PTCHECK(Hpos.upload(reinterpret_cast<const float4 *>(hpos_t4), P));
+    PTCHECK(Hnrm.upload(reinterpret_cast<const float4 *>(hnrm_id4), P));
+    if (albedo) {
+        PTCHECK(Asum.upload(reinterpret_cast<const float4 *>(asum4), P));
+        PTCHECK(Ha.upload(reinterpret_cast<const float4 *>(ha4), P));
+        PTCHECK(outA.alloc(P));
+    }
+    if (motion) PTCHECK(rows.upload(reinterpret_cast<const float4 *>(rows24), (size_t)nrows * kMotionRowVec));
+    PTCHECK(out.alloc(P));
+    PTCHECK(outN.alloc(P));
+    TemporalArgs T;
+    T.accum = S.p; T.moments = Q.p; T.posT = pos.p; T.nrmId = nrm.p;
+    T.hc = Hc.p; T.hn = Hn.p; T.hpos = Hpos.p; T.hnrm = Hnrm.p;
+    memcpy(&T.cam, cam16, sizeof T.cam);
+    T.W = w; T.H = h; T.samples = (float)samples;
+    T.out = out.p; T.outN = outN.p;
+    T.ha = Ha.p; T.asum = Asum.p; T.outA = outA.p; T.eps = min_albedo;
+    T.motion = rows.p; T.motionN = motion ? nrows : 0; T.histCap = hist_cap;
+    const dim3 grid((unsigned)((P + kBlock - 1) / kBlock));
+    EventSet es;
+    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
+        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        if (albedo) {
+            if (form == 3) temporal_motion_launch<kTemporalFilterDemod, true>(motion != 0, grid, T);
+            else if (form == 2) temporal_motion_launch<kTemporalMoments, true>(motion != 0, grid, T);
+            else if (form == 1) temporal_motion_launch<kTemporalCapture, true>(motion != 0, grid, T);
+            else temporal_motion_launch<kTemporalFilter, true>(motion != 0, grid, T);
+        } else {
+            if (form == 2) temporal_motion_launch<kTemporalMoments, false>(motion != 0, grid, T);
+            else if (form == 1) temporal_motion_launch<kTemporalCapture, false>(motion != 0, grid, T);
+            else temporal_motion_launch<kTemporalFilter, false>(motion != 0, grid, T);
+        }
+        if (ms && r) {
+            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+            HIPCHECK(hipEventSynchronize(es.ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
+        }
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipDeviceSynchronize());
+    HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (albedo) HIPCHECK(hipMemcpy(out_a4, outA.p, P * sizeof(float4), hipMemcpyDeviceToHost));
+    if (needN) PTCHECK(download(out_n, outN, P));
+    return PT_OK;
+}
+
 int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, int h, int samples, float threshold, float lum_floor, PtNoiseStats *out,
                         size_t stats_struct_bytes, float *tile_rel_var_host, int tiles_per_wave, int reps, float *ms) {
     NEED_GPU();

@@ -32,6 +32,9 @@
 // --history-from a new view of one sample.
 // --demodulate (with --denoise-var; not with --history-from) runs the renderer with PT_FLAG_DEMODULATE: <out>.denoised.png is the filter of the
 // frame divided by every pixel's mean first-hit albedo, multiplied back behind it (include/pt_amd.h, "demodulation").
+// --history-move ID TX TY TZ [RX RY RZ] (with --denoise-var and --history-from) runs both renderers with PT_FLAG_OBJECT_HISTORY, and the history
+// view renders object ID displaced by that translation (and rotation, in degrees) from the scene file's pose; the final view renders the
+// file's pose, and its history follows the object (include/pt_amd.h, "object history").
 // --history-albedo (with --denoise-var and --history-from) runs both renderers with PT_FLAG_TEMPORAL, PT_FLAG_DEMODULATE and
 // PT_FLAG_DEMOD_HISTORY: the history carries the first view's albedo, and <out>.denoised.png is the filter of the blend divided by the blended
 // albedo (include/pt_amd.h, "demodulated history").
@@ -51,6 +54,7 @@
 #include "image.h"
 #include "pathtrace.h"
 #include "pt_amd.h"
+#include "utilities.h"
 
 static std::string startTimeString;
 static Scene *scene;
@@ -77,6 +81,9 @@ static int historyIterations = 0;
 static bool spatialVariance = false;
 static bool demodulate = false;
 static bool historyAlbedo = false;
+static bool historyMove = false;     // --history-move (with --history-from): the history view shows object historyMoveId in another pose
+static int historyMoveId = 0;
+static float historyMoveT[3] = {0.0f, 0.0f, 0.0f}, historyMoveR[3] = {0.0f, 0.0f, 0.0f};
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 void pathtraceSpatialVariance(bool on);                                             // pathtrace_shim.cpp
@@ -163,6 +170,7 @@ static void renderBatched() {
     if (spatialVariance) opt.flags |= PT_FLAG_SPATIAL_VARIANCE;
     if (demodulate) opt.flags |= PT_FLAG_DEMODULATE;
     if (historyAlbedo) opt.flags |= PT_FLAG_DEMODULATE | PT_FLAG_DEMOD_HISTORY;      // (PT_FLAG_MOMENTS and PT_FLAG_TEMPORAL: set above, it needs both options)
+    if (historyMove) opt.flags |= PT_FLAG_OBJECT_HISTORY;
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -208,7 +216,16 @@ static void renderBatched() {
         PtCamera before;
         memcpy(&before, &renderState->camera, sizeof before);
         before.position.x = historyEye[0]; before.position.y = historyEye[1]; before.position.z = historyEye[2];
-        check(pt_init(&before, (const PtGeom *)scene->geoms.data(), (int)scene->geoms.size(), (const PtMaterial *)scene->materials.data(),
+        std::vector<Geom> geomsBefore = scene->geoms;       // --history-move: one object in the pose it had before
+        if (historyMove) {
+            Geom &g = geomsBefore[(size_t)historyMoveId];
+            g.translation = lin::vec3(g.translation.x + historyMoveT[0], g.translation.y + historyMoveT[1], g.translation.z + historyMoveT[2]);
+            g.rotation = lin::vec3(g.rotation.x + historyMoveR[0], g.rotation.y + historyMoveR[1], g.rotation.z + historyMoveR[2]);
+            g.transform = utilityCore::buildTransformationMatrix(g.translation, g.rotation, g.scale);
+            g.inverseTransform = lin::inverse(g.transform);
+            g.invTranspose = lin::inverseTranspose(g.transform);
+        }
+        check(pt_init(&before, (const PtGeom *)geomsBefore.data(), (int)geomsBefore.size(), (const PtMaterial *)scene->materials.data(),
                       (int)scene->materials.size(), renderState->traceDepth, &opt), "pt_init");
         for (int done = 0; done < historyIterations;) {
             const int n = historyIterations - done < batch ? historyIterations - done : batch;
@@ -283,10 +300,19 @@ static void renderProtocol() {
     pathtraceFree();                    // (parks; the library's exit handler frees)
 }
 
+// a token that is a number from its first character to its last
+static bool wholeNumber(const char *s, float *out) {
+    char *end = NULL;
+    const double v = strtod(s, &end);
+    if (end == s || *end != '\0') return false;
+    *out = (float)v;
+    return true;
+}
+
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo] [--history-move ID TX TY TZ [RX RY RZ]]\n", argv[0]);
         return 1;
     }
     try {
@@ -337,6 +363,21 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--spatial-variance")) spatialVariance = true;
         else if (!strcmp(argv[i], "--demodulate")) demodulate = true;
         else if (!strcmp(argv[i], "--history-albedo")) historyAlbedo = true;
+        else if (!strcmp(argv[i], "--history-move") && i + 4 < argc) {
+            historyMove = true;
+            float id = 0.0f;
+            bool ok = wholeNumber(argv[i + 1], &id) && id == (float)(int)id;
+            historyMoveId = (int)id;
+            for (int a = 0; a < 3; ++a) ok = wholeNumber(argv[i + 2 + a], &historyMoveT[a]) && ok;
+            if (!ok) { fprintf(stderr, "--history-move ID TX TY TZ [RX RY RZ]: ID, TX, TY and TZ must be numbers\n"); return 1; }
+            i += 4;
+            // the rotation: all three of the next tokens are numbers, or none of them is read
+            float r[3];
+            if (i + 3 < argc && wholeNumber(argv[i + 1], &r[0]) && wholeNumber(argv[i + 2], &r[1]) && wholeNumber(argv[i + 3], &r[2])) {
+                for (int a = 0; a < 3; ++a) historyMoveR[a] = r[a];
+                i += 3;
+            }
+        }
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 1; }
     }
     if (denoise && denoiseVar) { fprintf(stderr, "--denoise and --denoise-var exclude each other\n"); return 1; }
@@ -348,6 +389,10 @@ int main(int argc, char **argv) {
     if (spatialVariance && !denoiseVar) { fprintf(stderr, "--spatial-variance needs --denoise-var\n"); return 1; }
     pathtraceExtras(lensRadius, focalDistance, directLighting);
     pathtraceMoments(denoiseVar);
+    if (historyMove && (!denoiseVar || !historyFrom || inPlace || protocol || historyMoveId < 0 || historyMoveId >= (int)scene->geoms.size())) {
+        fprintf(stderr, "--history-move needs --denoise-var, --history-from and an object of the scene, and goes with neither --in-place nor --protocol\n");
+        return 1;
+    }
     if (inPlace && !historyFrom) { fprintf(stderr, "--in-place needs --history-from\n"); return 1; }
     if (protocol && !historyFrom) { fprintf(stderr, "--protocol needs --history-from\n"); return 1; }
     if (protocol && inPlace) { fprintf(stderr, "--protocol and --in-place exclude each other\n"); return 1; }

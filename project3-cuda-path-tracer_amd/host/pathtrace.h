@@ -30,3 +30,7 @@ void pathtraceTemporal(bool on);
 // It is freed by a pathtraceFree() called while it is parked, by a pathtraceFree() after the switch was turned off, and at exit.
 // PT_AMD_KEEP_RENDERER=1 (the variable, where set, decides: 0 switches it off).
 void pathtraceKeepRenderer(bool on);
+// Where pathtraceTemporal is on, the next pathtraceInit also sets PT_FLAG_OBJECT_HISTORY (include/pt_amd.h): a pathtraceInit whose scene shows
+// the same objects in other poses keeps the history and reprojects it through each object's own motion; any other change of the scene drops
+// it.  PT_AMD_OBJECT_HISTORY=1.
+void pathtraceObjectHistory(bool on);

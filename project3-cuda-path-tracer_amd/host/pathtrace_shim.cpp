@@ -21,6 +21,7 @@ static bool extraSpatial = false;                   // pathtraceSpatialVariance:
 static bool extraDemod = false;                     // pathtraceDemodulate: PT_FLAG_MOMENTS | PT_FLAG_DEMODULATE for the next pathtraceInit
 static bool extraDisplay = false;                   // pathtraceDisplayFilter: PT_FLAG_MOMENTS | PT_FLAG_DISPLAY_FILTER for the next pathtraceInit
 static bool extraTemporal = false;                  // pathtraceTemporal: PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL for the next pathtraceInit
+static bool extraObjectHistory = false;             // pathtraceObjectHistory: PT_FLAG_OBJECT_HISTORY where the next pathtraceInit sets PT_FLAG_TEMPORAL
 static bool extraKeep = false;                      // pathtraceKeepRenderer: pathtraceFree parks the renderer, pathtraceInit sets PT_FLAG_KEEP_RENDERER
 // a renderer of the default context exists (a pathtraceInit succeeded and pt_free has not been called since) / pathtraceFree has parked it
 static bool live = false, parked = false;
@@ -78,6 +79,11 @@ void pathtraceInit(Scene *scene) {
     if (const char *e = getenv("PT_AMD_TEMPORAL")) temporal = temporal || atoi(e) != 0;
     if (temporal) opt.flags |= PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL;
     if (temporal && demod) opt.flags |= PT_FLAG_DEMOD_HISTORY;
+    // PT_AMD_OBJECT_HISTORY=1 (or pathtraceObjectHistory), where temporal reprojection is on: the history also survives a pathtraceInit whose
+    // scene shows the same objects in other poses, and follows them (include/pt_amd.h: "object history"); any other change of the scene drops it.
+    bool objectHistory = extraObjectHistory;
+    if (const char *e = getenv("PT_AMD_OBJECT_HISTORY")) objectHistory = objectHistory || atoi(e) != 0;
+    if (temporal && objectHistory) opt.flags |= PT_FLAG_OBJECT_HISTORY;
     const bool keep = keepSwitch();
     if (keep) opt.flags |= PT_FLAG_KEEP_RENDERER;
     // The reference's host calls pathtrace(pbo, frame, iter) once per iteration with iter = 1, 2, 3, ... (src/main.cpp:97-103):
@@ -182,6 +188,11 @@ void pathtraceInit(Scene *scene) {
                         "a group keeps no second moments\n");
         exit(EXIT_FAILURE);
     }
+    if (members >= 2 && objectHistory) {
+        fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: object history (PT_AMD_OBJECT_HISTORY, pathtraceObjectHistory) is not for "
+                        "PT_AMD_DEVICES: a group keeps no history\n");
+        exit(EXIT_FAILURE);
+    }
     if (members >= 2 && keep) {
         fprintf(stderr, "HIP error (pathtrace_shim.cpp): pathtraceInit: keeping the renderer (PT_AMD_KEEP_RENDERER, pathtraceKeepRenderer) is not for "
                         "PT_AMD_DEVICES: a group re-initialises its members in place already\n");
@@ -270,6 +281,10 @@ void pathtraceTemporal(bool on) { extraTemporal = on; }
 // ... nor this one: pathtraceFree parks the renderer instead of freeing it, and pathtraceInit lets the library move the camera in place
 // (keepSwitch above).  The environment variable PT_AMD_KEEP_RENDERER=1 does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
 void pathtraceKeepRenderer(bool on) { extraKeep = on; }
+// ... and where temporal reprojection is on, the next pathtraceInit sets PT_FLAG_OBJECT_HISTORY too (include/pt_amd.h: "object history"): a
+// scene that shows the same objects in other poses keeps the history, which follows them.  The environment variable PT_AMD_OBJECT_HISTORY=1
+// does the same for a host that cannot call it.  Not with PT_AMD_DEVICES.
+void pathtraceObjectHistory(bool on) { extraObjectHistory = on; }
 
 void pathtraceFree() {
     if (group) {
