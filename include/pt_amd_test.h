@@ -345,6 +345,9 @@ int pt_test_scene_plan(const PtCamera *cam, const PtGeom *geoms, int ngeoms, con
 /* device allocations THIS library's renderers and temporaries hold right now (every one has one owner type, which counts in this
  * library only): 0 after pt_free */
 int64_t pt_test_live_device_buffers(void);
+/* ... and the streams plus events plus page-locked host allocations they, its groups and the scan library hold (the same: one owner type
+ * each, counted in this library only): 0 after pt_free and pt_group_destroy */
+int64_t pt_test_live_handles(void);
 
 #ifdef __cplusplus
 }

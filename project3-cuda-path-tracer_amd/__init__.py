@@ -103,7 +103,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions", "pt_test_sphere_groups", "pt_test_group_tally",
     "pt_test_camera_resolved_device", "pt_test_last_camera_move", "pt_test_keep_mismatch",
-    "pt_test_motion_table", "pt_test_history_motion", "pt_test_temporal_motion",
+    "pt_test_motion_table", "pt_test_history_motion", "pt_test_temporal_motion", "pt_test_live_handles",
 ]
 
 
@@ -297,6 +297,8 @@ def _bind(L, with_tests):
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
+        L.pt_test_live_handles.argtypes = []
+        L.pt_test_live_handles.restype = i64
         L.pt_test_renderer_state.argtypes = [C.POINTER(C.c_uint32)]
         L.pt_test_scene_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(PtOptions), C.POINTER(PtTestPlanSummary)]
     return L

@@ -102,64 +102,13 @@ bool env_flag(const char *name) {
     return e && atoi(e);
 }
 
-#ifdef PT_TEST_API
-std::atomic<long long> g_liveDevBufs{0};     // pt_test_live_device_buffers(): allocations DevBufs hold right now (the product carries no counter)
-inline void count_devbuf(int d) { g_liveDevBufs += d; }
-#else
-inline void count_devbuf(int) {}
-#endif
-
-// The owner of one device allocation: every table of a renderer (State, Slot) and every temporary of this file.  Move-only; a buffer
-// that has been released -- or moved from -- does nothing in its destructor, so a State that free_renderer has emptied makes no HIP
-// call when it is destroyed (the default context is destroyed after the runtime's own exit handlers: see exit_handler).
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;                 // elements allocated (the camera move refreshes a table in place where it fits)
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    DevBuf &operator=(DevBuf &&o) noexcept {
-        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    void release() {
-        if (!p) return;
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        count_devbuf(-1);
-    }
-    // n elements (at least one: a kernel may be handed the pointer of an empty table), uninitialised / zeroed / copied from the host
-    // (`slack`: elements behind the copied ones, left uninitialised)
-    int alloc(size_t n) {
-        release();
-        HIPCHECK(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-        cap = std::max<size_t>(n, 1);
-        count_devbuf(1);
-        return PT_OK;
-    }
-    int alloc_zeroed(size_t n) {
-        PTCHECK(alloc(n));
-        HIPCHECK(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T)));
-        return PT_OK;
-    }
-    int upload(const T *src, size_t n, size_t slack = 0) {
-        PTCHECK(alloc(n + slack));
-        if (n) HIPCHECK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-        return PT_OK;
-    }
-    int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
-};
-
+#include "pt_owned.h"      // DevBuf, Stream, Event, HostBuf: the owners of everything this file holds on the device side, and the rule for process exit
 #include "pt_host_scene.h"
 #include "pt_scene_plan.h"
 
 // One in-flight iteration: its own stream, path buffers, counters and deferred-radiance buffer.
 struct Slot {
-    hipStream_t stream = nullptr;
+    Stream stream;
     DevBuf<float> pathbuf[2];      // two path pools (ping-pong by bounce), poolChunks * kChunk paths per array
     DevBuf<unsigned long long> chunkList[2];   // per pool: [kSeg][poolChunks] chunk lists of the queue it holds
     uint32_t gen[2] = {0, 0};      // per pool: serial number of the launch that filled it (tags the chunk-list entries)
@@ -167,8 +116,8 @@ struct Slot {
     DevBuf<float> contrib;         // maxBatch x W*H*3: an entry is valid while its bit of `hitMask` is set
     DevBuf<uint32_t> hitMask;      // ceil(maxBatch / 32) x W*H: which iterations of the batch wrote a pixel's `contrib`, zero between batches
     DevBuf<unsigned long long> meshHit;   // scenes with meshes: the walks' result per path of the bounce being launched (BounceArgs::meshHit)
-    hipEvent_t evDone = nullptr;       // all bounce launches of the slot's current iteration finished
-    hipEvent_t evCommitted = nullptr;  // k_commit consumed `contrib` (cleared the masks' bits)
+    Event evDone;                      // all bounce launches of the slot's current iteration finished
+    Event evCommitted;                 // k_commit consumed `contrib` (cleared the masks' bits)
     int parity = 0;                // which half of Ctrl::cursor the slot's next batch uses
 };
 
@@ -288,7 +237,7 @@ struct SceneTables {
 struct State : PlanScalars {
     bool init = false;
     int device = 0;
-    hipStream_t stream = nullptr;   // the caller's stream: commits, PBO conversion, readback
+    hipStream_t stream = nullptr;   // the caller's stream, borrowed: commits, PBO conversion, readback
     float *image = nullptr;         // the accumulator the kernels add to: the caller's (PtOptions::accum_dev, never freed here), or ...
     DevBuf<float> imageOwn;         // ... the renderer's own
     DevBuf<float> moments;          // PT_FLAG_MOMENTS: per pixel the sum of its samples' squared luminance (k_commit<true>); always the renderer's own
@@ -310,8 +259,8 @@ struct State : PlanScalars {
     // event that says its copy has landed
     DevBuf<uint32_t> noiseFrame;
     DevBuf<float> noiseMap;
-    uint32_t *noiseHost = nullptr;      // 2 x 2 words
-    hipEvent_t noiseEv[2] = {nullptr, nullptr};
+    HostBuf<uint32_t> noiseHost;        // 2 x 2 words
+    Event noiseEv[2];
     int gridWalk = 0, gridWalkFirst = 0;      // the grids of the meshes' walks (k_mesh_walk) ...
     int grid = 0;           // ... the persistent grid of k_bounce<false>
     int gridFirst = 0;      // ... and of k_bounce<true> (its own register budget, hence its own residency)
@@ -328,21 +277,21 @@ struct State : PlanScalars {
     uint32_t launchSerial = 0;   // bounce launches since pt_init
     // host buffer of pt_readback, page-locked on first use so the per-iteration D2H copy of the reference protocol
     // (src/pathtrace.cu:170-171) runs at PCIe rate instead of through a pageable staging copy
-    void *pinnedHost = nullptr;
+    void *pinnedHost = nullptr;     // the caller's memory, borrowed: registered and unregistered by hand (pt_owned.h: the rule for process exit)
     size_t pinnedBytes = 0;
     // kernel timing
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evBounce;
-    std::vector<hipEvent_t> evFree;   // resolved timing events, reused (creating two per launch cost 1 % of a timed step)
+    std::vector<Event> evBounce;      // the timed launches not yet resolved: each one's start and end, in pairs
+    std::vector<Event> evFree;        // resolved timing events, reused (creating two per launch cost 1 % of a timed step)
     double msBounce = 0;
     long long nBounce = 0;
     // The sticky fault word once more, in page-locked HOST memory the kernels can write (a fault path stores it there too): pt_readback
     // and pt_readback_rgba8, which synchronise anyway, then report a faulted render without a device-to-host copy of their own.
-    uint32_t *hostFault = nullptr;       // host address
-    uint32_t *hostFaultDev = nullptr;    // the same word as the kernels address it
+    HostBuf<uint32_t> hostFault;         // host address
+    uint32_t *hostFaultDev = nullptr;    // the same word as the kernels address it (derived from hostFault, not owned)
     // device groups (pt_group.h): the full frame the NEXT commit also copies this shard's pixels into (k_commit's `snap`: the snapshot a
     // frame reduce reads), and the event -- the reduce that last read that buffer -- the commit has to wait for first.  Set per call.
-    float *snapTarget = nullptr;
-    hipEvent_t snapWait = nullptr;
+    float *snapTarget = nullptr;    // the group's, borrowed
+    hipEvent_t snapWait = nullptr;  // the group's, borrowed
     // what the pt_set_* calls last registered, consumed by the next pt_init (kept across pt_free: the reference's Free -> Init restart
     // protocol re-initialises the same scene), and what was registered when the renderer was initialised: the scene its camera moves
     // plan, whatever has been registered since
@@ -359,9 +308,12 @@ struct State : PlanScalars {
     std::unique_ptr<ScenePlan> held;
     // ... and what its certificates on the device need (k_camera_faces), made by the first move: a stream of their own -- the renderer's may
     // hold a frame's work -- and the pixel words and face bytes of one move
-    hipStream_t camStream = nullptr;
+    Stream camStream;
     DevBuf<uint32_t> camPixScratch;
     DevBuf<signed char> camFaceScratch;
+    // Nothing to drain or release (the history aside): no pt_init has come as far as its device half since the last free -- it begins by taking the
+    // plan's scalars, nslots >= 1 among them, before its first allocation -- and no host buffer is registered.  Answered without a HIP call.
+    bool holds_nothing() const { return nslots == 0 && !pinnedHost; }
 };
 
 // Renderer instances.  The reference keeps its renderer in file-static globals (src/pathtrace.cu:70-71: one per process, not
@@ -397,17 +349,20 @@ PathPool pool(const Slot &sl, int which) {
     return p;
 }
 
-int resolve_events(std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms, long long &n) {
-    for (auto &pr : v) {
+void recycle_events(std::vector<Event> &v) {      // the timing events of `v` back into the pool
+    for (Event &e : v) R().evFree.push_back(std::move(e));
+    v.clear();
+}
+
+int resolve_events(std::vector<Event> &v, double &ms, long long &n) {
+    for (size_t i = 0; i + 1 < v.size(); i += 2) {
         float t = 0;
-        HIPCHECK(hipEventSynchronize(pr.second));
-        HIPCHECK(hipEventElapsedTime(&t, pr.first, pr.second));
+        HIPCHECK(hipEventSynchronize(v[i + 1]));
+        HIPCHECK(hipEventElapsedTime(&t, v[i], v[i + 1]));
         ms += t;
         n += 1;
-        R().evFree.push_back(pr.first);
-        R().evFree.push_back(pr.second);
     }
-    v.clear();
+    recycle_events(v);
     return PT_OK;
 }
 
@@ -486,11 +441,11 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     const uint32_t genIn = sl.gen[(depth - 1) & 1];
     if (++R().launchSerial == 0u) ++R().launchSerial;
     const uint32_t genOut = sl.gen[depth & 1] = R().launchSerial;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     if (R().flags & PT_FLAG_KERNEL_TIMING) {
-        for (hipEvent_t *e : {&e0, &e1}) {
-            if (!R().evFree.empty()) { *e = R().evFree.back(); R().evFree.pop_back(); }
-            else HIPCHECK(hipEventCreate(e));
+        for (Event *e : {&e0, &e1}) {
+            if (!R().evFree.empty()) { *e = std::move(R().evFree.back()); R().evFree.pop_back(); }
+            else PTCHECK(e->create(hipEventDefault));
         }
         HIPCHECK(hipEventRecord(e0, sl.stream));
     }
@@ -526,8 +481,9 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
     HIPCHECK(hipLaunchKernel(first ? R().kernFirst : R().kernNext, dim3(first ? R().gridFirst : R().grid), dim3(kBlock), kargs, first ? R().ldsBytes : R().ldsBytesNext, sl.stream));
     if (e0) {
         HIPCHECK(hipEventRecord(e1, sl.stream));
-        R().evBounce.emplace_back(e0, e1);
-        if (R().evBounce.size() > 8192) {
+        R().evBounce.push_back(std::move(e0));
+        R().evBounce.push_back(std::move(e1));
+        if (R().evBounce.size() > 2 * 8192) {
             int rc = resolve_events(R().evBounce, R().msBounce, R().nBounce);
             if (rc) return rc;
         }
@@ -540,8 +496,8 @@ int launch_bounce(Slot &sl, int iter, int batch, int depth, bool lastBounce, flo
 // stream are ordered, so they share it)
 struct ScanWs {
     int device = -1;                 // the device the buffers live on
-    uint32_t *partial = nullptr;     // [kScanChunksMax + 1]
-    unsigned long long *chained = nullptr;   // k_scan_chained: {ticket, sums[kScanChunksMax]}
+    DevBuf<uint32_t> partial;        // [kScanChunksMax + 1]
+    DevBuf<unsigned long long> chained;      // k_scan_chained: {ticket, sums[kScanChunksMax]}
     uint32_t gen = 0;                // calls of the chained scan on this stream (tags the sums; never 0)
 };
 std::map<std::pair<int, hipStream_t>, ScanWs> g_scan;   // per (device, stream): the NULL stream -- or an equal handle -- of another device is another workspace
@@ -555,11 +511,8 @@ int scan_ws(hipStream_t st, ScanWs **out) {
     HIPCHECK(hipGetDevice(&dev));    // the device current at the call: where the caller's buffers live and the kernels will run
     ScanWs &W = g_scan[std::make_pair(dev, st)];          // (std::map: the reference stays valid while other streams are added)
     W.device = dev;
-    if (!W.partial) HIPCHECK(hipMalloc(&W.partial, (size_t)(kScanChunksMax + 1) * sizeof(uint32_t)));
-    if (!W.chained) {
-        HIPCHECK(hipMalloc(&W.chained, (size_t)(kScanChunksMax + 1) * sizeof(unsigned long long)));
-        HIPCHECK(hipMemset(W.chained, 0, (size_t)(kScanChunksMax + 1) * sizeof(unsigned long long)));
-    }
+    if (!W.partial.p) PTCHECK(W.partial.alloc((size_t)kScanChunksMax + 1));
+    if (!W.chained.p) PTCHECK(W.chained.alloc_zeroed((size_t)kScanChunksMax + 1));
     *out = &W;
     return PT_OK;
 }
@@ -577,8 +530,8 @@ void scan_release() {
             (void)hipDeviceSynchronize();
             synced = kv.second.device;
         }
-        if (kv.second.partial) (void)hipFree(kv.second.partial);
-        if (kv.second.chained) (void)hipFree(kv.second.chained);
+        kv.second.partial.release();
+        kv.second.chained.release();
     }
     g_scan.clear();
     if (cur >= 0) (void)hipSetDevice(cur);
@@ -791,15 +744,6 @@ const void *atrous_last_kernel(bool bytes, int form) {
     return bytes ? atrous_forms<Last, false, true, true>(form) : atrous_forms<Last, false, true>(form);
 }
 
-// timing events that go away on every path out of their scope
-struct EventSet {
-    hipEvent_t ev[10] = {nullptr};
-    ~EventSet() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
 int denoise_refusals(const char *who) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
     if (R().prm.shardCount > 1 || (R().flags & PT_FLAG_ACCUM_SHARD_ROWS))
@@ -820,21 +764,19 @@ int ensure_guides(int guideIter, float *ms) {
     if (R().dnGuideIter == guideIter) return PT_OK;
     const size_t stackBytes = guide_stack_bytes();
     if (stackBytes > 64 * 1024) return fail(PT_ERR_INVALID, "guide buffers: a mesh hierarchy needs %d stack levels", R().meshStackNeed);
-    EventSet es;
-    hipEvent_t &e0 = es.ev[0], &e1 = es.ev[1];
+    Event ev[2];
     if (ms) {
-        HIPCHECK(hipEventCreate(&e0));
-        HIPCHECK(hipEventCreate(&e1));
-        HIPCHECK(hipEventRecord(e0, R().stream));
+        for (Event &e : ev) PTCHECK(e.create(hipEventDefault));
+        HIPCHECK(hipEventRecord(ev[0], R().stream));
     }
     R().dnGuideIter = 0;
     hipLaunchKernelGGL(k_gbuffer, dim3((unsigned)((P + kBlock - 1) / kBlock)), dim3(kBlock), stackBytes, R().stream, R().prm, R().tab.dgeoms.p,
                        reinterpret_cast<const float4 *>(R().tab.dMeshRecs.p), guideIter, R().dnPosT.p, R().dnNrmId.p);
     HIPCHECK(hipGetLastError());
     if (ms) {
-        HIPCHECK(hipEventRecord(e1, R().stream));
-        HIPCHECK(hipEventSynchronize(e1));
-        HIPCHECK(hipEventElapsedTime(ms, e0, e1));
+        HIPCHECK(hipEventRecord(ev[1], R().stream));
+        HIPCHECK(hipEventSynchronize(ev[1]));
+        HIPCHECK(hipEventElapsedTime(ms, ev[0], ev[1]));
     }
     R().dnGuideIter = guideIter;
     return PT_OK;
@@ -874,10 +816,9 @@ int atrous_run(typename Last::Args &A, int samples, const Params *p, float sigma
     A.samples = (float)samples;
     A.invN = 1.0f / (p->sigma_normal * p->sigma_normal);
     A.invP = 1.0f / (p->sigma_position * p->sigma_position);
-    EventSet es;
-    hipEvent_t *const ev = es.ev;
+    Event ev[9];                    // (levels <= 8)
     if (ms)
-        for (int i = 0; i <= p->levels; ++i) HIPCHECK(hipEventCreate(&ev[i]));
+        for (int i = 0; i <= p->levels; ++i) PTCHECK(ev[i].create(hipEventDefault));
     for (int i = 0; i < p->levels; ++i) {
         const bool first = i == 0 && !blended, last = i == p->levels - 1;
         A.step = 1 << i;
@@ -1295,10 +1236,9 @@ void noise_fill(PtNoiseStats *out, int W, int H, int samples, float thr2, const 
 
 int noise_buffers() {
     if (!R().noiseFrame.p) PTCHECK(R().noiseFrame.alloc(2));
-    if (!R().noiseHost) {
-        HIPCHECK(hipHostMalloc((void **)&R().noiseHost, 4 * sizeof(uint32_t), hipHostMallocDefault));
-        for (hipEvent_t &e : R().noiseEv) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    if (!R().noiseHost) PTCHECK(R().noiseHost.alloc(4, hipHostMallocDefault));
+    for (Event &e : R().noiseEv)
+        if (!e) PTCHECK(e.create(hipEventDisableTiming));
     return PT_OK;
 }
 
@@ -1336,29 +1276,14 @@ namespace {
 void free_renderer(bool keepHistory) {
     if (!keepHistory) R().hist = History();        // (pt_init alone keeps it: a re-initialisation of a PT_FLAG_TEMPORAL renderer)
     // pathtraceFree before the first Init (src/main.cpp:91-94) must be a no-op
-    if (!R().init && !R().image && !R().tab.dgeoms.p && R().nslots == 0 && !R().hostFault && !R().pinnedHost) return;
+    if (R().holds_nothing()) return;
     if (R().device >= 0 && R().nslots > 0) (void)hipSetDevice(R().device);     // (a host that switched devices in between)
+    // wait for everything, then let go: hipFree synchronises by itself, the destruction of a stream does not wait in the same way
     for (int i = 0; i < kMaxSlots; ++i)
         if (R().slot[i].stream) (void)hipStreamSynchronize(R().slot[i].stream);
     (void)hipStreamSynchronize(R().stream);
-    for (auto &pr : R().evBounce) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (hipEvent_t e : R().evFree) (void)hipEventDestroy(e);
-    for (int i = 0; i < kMaxSlots; ++i) {
-        Slot &sl = R().slot[i];
-        if (sl.evDone) (void)hipEventDestroy(sl.evDone);
-        if (sl.evCommitted) (void)hipEventDestroy(sl.evCommitted);
-        if (sl.stream) (void)hipStreamDestroy(sl.stream);
-    }
     if (R().pinnedHost) (void)hipHostUnregister(R().pinnedHost);
-    if (R().hostFault) (void)hipHostFree(R().hostFault);
-    if (R().noiseHost) (void)hipHostFree(R().noiseHost);
-    if (R().camStream) (void)hipStreamDestroy(R().camStream);
-    for (hipEvent_t e : R().noiseEv)
-        if (e) (void)hipEventDestroy(e);
-    // ... and every device table: the move-assignment below releases what the DevBufs of State and its Slots hold
+    // ... and everything else: the move-assignment below releases what the owners of State and its Slots hold (pt_owned.h)
     {   // (what is registered outlives the renderer: see State::reg)
         const Registered keep = R().reg;
         History keepHist = std::move(R().hist);
@@ -1504,7 +1429,7 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
     HIPCHECK(hipGetDevice(&S.device));
     S.stream = (hipStream_t)o.stream;
     PTCHECK(refresh_motion(S.hist, objectHistory, geoms, ngeoms));      // (the capture, where one was due, is behind us)
-    HIPCHECK(hipHostMalloc((void **)&S.hostFault, sizeof(uint32_t), hipHostMallocMapped));
+    PTCHECK(S.hostFault.alloc(1, hipHostMallocMapped));
     *S.hostFault = 0u;
     HIPCHECK(hipHostGetDevicePointer((void **)&S.hostFaultDev, S.hostFault, 0));
 
@@ -1549,7 +1474,7 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
     if (S.flags & PT_FLAG_DEMOD_HISTORY) PTCHECK(S.dnAlbedo.alloc((size_t)S.P));
     for (int i = 0; i < S.nslots; ++i) {
         Slot &sl = S.slot[i];
-        HIPCHECK(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
+        PTCHECK(sl.stream.create(hipStreamNonBlocking));
         for (int b = 0; b < 2; ++b) {
             PTCHECK(sl.pathbuf[b].alloc(S.poolCap * poolDwords(S.prm.histBits)));
             PTCHECK(sl.chunkList[b].alloc_zeroed((size_t)kSeg * S.poolChunks));
@@ -1559,8 +1484,8 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
         PTCHECK(sl.contrib.alloc_zeroed(contribFloats));
         PTCHECK(sl.hitMask.alloc_zeroed(maskWords));
         if (S.meshHitWords) PTCHECK(sl.meshHit.alloc(S.meshHitWords));
-        HIPCHECK(hipEventCreateWithFlags(&sl.evDone, hipEventDisableTiming));
-        HIPCHECK(hipEventCreateWithFlags(&sl.evCommitted, hipEventDisableTiming));
+        PTCHECK(sl.evDone.create(hipEventDisableTiming));
+        PTCHECK(sl.evCommitted.create(hipEventDisableTiming));
     }
 
     // the plan's tables, each once; a table the scene does not have is empty and stays without a buffer (the walks' tables of a scene with
@@ -1623,12 +1548,11 @@ int camera_faces_device(CameraGroups &G, const CameraResolve &cr, hipStream_t st
     for (const Run &r : runs) memcpy(words.data() + r.off, G.groups[r.group].data(), r.n * sizeof(uint32_t));
     if (pix.cap < total) PTCHECK(pix.alloc(total + total / 4));
     if (face.cap < total) PTCHECK(face.alloc(total + total / 4));
-    EventSet es;
+    Event ev[2];
     HIPCHECK(hipMemcpyAsync(pix.p, words.data(), total * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (ms) {
-        HIPCHECK(hipEventCreate(&es.ev[0]));
-        HIPCHECK(hipEventCreate(&es.ev[1]));
-        HIPCHECK(hipEventRecord(es.ev[0], st));
+        for (Event &e : ev) PTCHECK(e.create(hipEventDefault));
+        HIPCHECK(hipEventRecord(ev[0], st));
     }
     for (const Run &r : runs) {
         CameraFacesArgs A;
@@ -1640,11 +1564,11 @@ int camera_faces_device(CameraGroups &G, const CameraResolve &cr, hipStream_t st
         hipLaunchKernelGGL(k_camera_faces, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, st, A);
     }
     HIPCHECK(hipGetLastError());
-    if (ms) HIPCHECK(hipEventRecord(es.ev[1], st));
+    if (ms) HIPCHECK(hipEventRecord(ev[1], st));
     std::vector<signed char> bytes(total);
     HIPCHECK(hipMemcpyAsync(bytes.data(), face.p, total, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    if (ms) HIPCHECK(hipEventElapsedTime(ms, es.ev[0], es.ev[1]));
+    if (ms) HIPCHECK(hipEventElapsedTime(ms, ev[0], ev[1]));
     for (const Run &r : runs) {
         std::vector<int> &f = G.faces[r.group];
         f.resize(r.n);
@@ -1677,11 +1601,14 @@ int refresh_table(DevBuf<T> &buf, const std::vector<T> &heldT, const std::vector
 // pt_init over the live renderer with the scene it was initialised with -- its arguments, and what was registered then --: the camera
 // move's slow path.  What has been registered since stays registered behind it.  (Copies: init_renderer frees the renderer that holds them.)
 int reinit_with_camera(const PtCamera &cam) {
-    const State &S = R();
+    State &S = R();
     const std::vector<PtGeom> geoms = S.inGeoms;
     const std::vector<PtMaterial> mats = S.inMats;
     const PtOptions o = S.inOpts;
-    return init_renderer(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), S.inDepth, o, S.initReg);
+    Stream camStream = std::move(S.camStream);      // (the moves' own stream outlives a rebuild -- not one that fails and leaves a State that holds nothing)
+    const int rc = init_renderer(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), S.inDepth, o, S.initReg);
+    if (!S.holds_nothing()) S.camStream = std::move(camStream);
+    return rc;
 }
 
 // PT_FLAG_KEEP_RENDERER on a full call: the call against the live renderer's copies of its own (pt_scene_plan.h: keep_renderer_mismatch).
@@ -1706,7 +1633,7 @@ int set_camera(const PtCamera *cam) {
     const PtCamera camNew = *cam;        // (the caller may hand in the camera of a scene this call outlives)
     if (S.device >= 0) HIPCHECK(hipSetDevice(S.device));
     // 1. the plan for the new camera, the certificates of its work list on the device; a scene that is refused has touched nothing
-    if (!S.camStream) HIPCHECK(hipStreamCreateWithFlags(&S.camStream, hipStreamNonBlocking));
+    if (!S.camStream) PTCHECK(S.camStream.create(hipStreamNonBlocking));
     std::unique_ptr<ScenePlan> planPtr(new ScenePlan);
     ScenePlan &plan = *planPtr;
     {
@@ -1769,8 +1696,7 @@ int set_camera(const PtCamera *cam) {
             HIPCHECK(hipMemsetAsync(S.slot[i].ctrl.p, 0, sizeof(Ctrl), S.stream));
             S.slot[i].parity = 0;
         }
-        for (auto &pr : S.evBounce) { S.evFree.push_back(pr.first); S.evFree.push_back(pr.second); }
-        S.evBounce.clear();
+        recycle_events(S.evBounce);
         S.msBounce = 0; S.nBounce = 0;
         S.iterations = 0; S.committed = 0; S.seq = 0;
         S.ahead.clear();
@@ -2299,14 +2225,14 @@ int pt_scan_exclusive_i32(const int32_t *in_dev, int32_t *out_dev, int64_t n, vo
     const char *mode = getenv("PT_AMD_SCAN");
     if (!(mode && atoi(mode) == 1)) {
         // (chunks of four tiles or more take the kernels that load a tile ahead; the apply adds up the totals before its chunk itself)
-        if (per >= 4) hipLaunchKernelGGL((k_scan_reduce<false, true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial);
-        else hipLaunchKernelGGL((k_scan_reduce<false, false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial);
-        if (per >= 4) hipLaunchKernelGGL((k_scan_apply<true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial);
-        else hipLaunchKernelGGL((k_scan_apply<false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial);
+        if (per >= 4) hipLaunchKernelGGL((k_scan_reduce<false, true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial.p);
+        else hipLaunchKernelGGL((k_scan_reduce<false, false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial.p);
+        if (per >= 4) hipLaunchKernelGGL((k_scan_apply<true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial.p);
+        else hipLaunchKernelGGL((k_scan_apply<false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial.p);
     } else {
         if (++wp->gen == 0u) ++wp->gen;
-        HIPCHECK(hipMemsetAsync(wp->chained, 0, sizeof(uint32_t), st));          // the ticket (the sums are tagged with the call's generation)
-        hipLaunchKernelGGL(k_scan_chained, dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->chained, wp->gen);
+        HIPCHECK(hipMemsetAsync(wp->chained.p, 0, sizeof(uint32_t), st));          // the ticket (the sums are tagged with the call's generation)
+        hipLaunchKernelGGL(k_scan_chained, dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->chained.p, wp->gen);
     }
     HIPCHECK(hipGetLastError());
     return PT_OK;
@@ -2329,12 +2255,12 @@ int pt_compact_nonzero_i32(const int32_t *in_dev, int32_t *out_dev, int64_t n, i
     long long per;
     int chunks;
     scan_chunks(n, &per, &chunks);
-    if (per >= 4) hipLaunchKernelGGL((k_scan_reduce<true, true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial);
-    else hipLaunchKernelGGL((k_scan_reduce<true, false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial);
+    if (per >= 4) hipLaunchKernelGGL((k_scan_reduce<true, true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial.p);
+    else hipLaunchKernelGGL((k_scan_reduce<true, false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, (long long)n, per, wp->partial.p);
     if (per >= 4)
-        hipLaunchKernelGGL((k_compact_apply<true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial, reinterpret_cast<long long *>(count_dev));
+        hipLaunchKernelGGL((k_compact_apply<true>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial.p, reinterpret_cast<long long *>(count_dev));
     else
-        hipLaunchKernelGGL((k_compact_apply<false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial, reinterpret_cast<long long *>(count_dev));
+        hipLaunchKernelGGL((k_compact_apply<false>), dim3(chunks), dim3(kBlock), 0, st, in_dev, out_dev, (long long)n, per, wp->partial.p, reinterpret_cast<long long *>(count_dev));
     HIPCHECK(hipGetLastError());
     return PT_OK;
 }

@@ -167,8 +167,8 @@ struct EmulatedReduce {
     enum { kSuccess = 0, kUnhandledHipError = 1, kInvalidArgument = 4, kInvalidUsage = 5 };      // rccl.h: ncclResult_t
     struct World {                     // what CommInitAll makes: the ranks of one communicator
         int n = 0, live = 0;
-        hipEvent_t posted[kEmuMaxRanks] = {};
-        hipEvent_t done = nullptr;
+        Event posted[kEmuMaxRanks];
+        Event done;
     };
     struct Comm { World *w; int rank; };
     struct Post { const float *send; float *recv; size_t count; int root; Comm *comm; hipStream_t stream; };
@@ -177,19 +177,13 @@ struct EmulatedReduce {
         thread_local Calls c;
         return c;
     }
-    static void release(World *w) {
-        for (hipEvent_t e : w->posted)
-            if (e) (void)hipEventDestroy(e);
-        if (w->done) (void)hipEventDestroy(w->done);
-        delete w;
-    }
     static int CommInitAll(void **comms, int n, const int *) {
         if (!comms || n < 1 || n > kEmuMaxRanks) return kInvalidArgument;
         World *w = new World();
         w->n = w->live = n;
-        bool ok = hipEventCreateWithFlags(&w->done, hipEventDisableTiming) == hipSuccess;
-        for (int r = 0; r < n && ok; ++r) ok = hipEventCreateWithFlags(&w->posted[r], hipEventDisableTiming) == hipSuccess;
-        if (!ok) { release(w); return kUnhandledHipError; }
+        bool ok = w->done.create(hipEventDisableTiming) == PT_OK;
+        for (int r = 0; r < n && ok; ++r) ok = w->posted[r].create(hipEventDisableTiming) == PT_OK;
+        if (!ok) { delete w; return kUnhandledHipError; }
         for (int r = 0; r < n; ++r) comms[r] = new Comm{w, r};
         return kSuccess;
     }
@@ -198,7 +192,7 @@ struct EmulatedReduce {
         if (!c) return kInvalidArgument;
         World *w = c->w;
         delete c;
-        if (--w->live == 0) release(w);
+        if (--w->live == 0) delete w;
         return kSuccess;
     }
     static int GroupStart() {
@@ -352,11 +346,11 @@ struct GroupDevice {
     int id = 0;
     int device = 0;
     std::vector<int> members;              // indices into PtGroup::ctx
-    float *full = nullptr;                 // the zero-padded full-frame accumulator the members on this device commit into
-    float *snap[2] = {nullptr, nullptr};   // rccl: the members' commits copy their rows here (k_commit's `snap`), every other row stays zero; the reduce's send buffer
-    hipStream_t coll = nullptr;            // the collective's stream (and the read-back's)
-    hipEvent_t evRed[2] = {nullptr, nullptr};     // the reduce that read snapshot k is through (collective stream)
-    void *comm = nullptr;                  // ncclComm_t
+    DevBuf<float> full;                    // the zero-padded full-frame accumulator the members on this device commit into
+    DevBuf<float> snap[2];                 // rccl: the members' commits copy their rows here (k_commit's `snap`), every other row stays zero; the reduce's send buffer
+    Stream coll;                           // the collective's stream (and the read-back's)
+    Event evRed[2];                        // the reduce that read snapshot k is through (collective stream)
+    void *comm = nullptr;                  // ncclComm_t: the function table's (PtGroup::api), destroyed through it
 };
 }  // namespace
 
@@ -364,13 +358,13 @@ struct PtGroup {
     std::vector<PtContext *> ctx;
     std::vector<int> device;               // [n] member -> HIP device
     std::vector<int> devIndex;             // [n] member -> index into dev
-    std::vector<hipStream_t> stream;       // [n] the member's own "caller's stream": commits, in call order
-    std::vector<hipEvent_t> evCommit;      // [n] the member's commits so far (recorded behind every call's enqueue)
+    std::vector<Stream> stream;            // [n] the member's own "caller's stream": commits, in call order (empty: the NULL stream)
+    std::vector<Event> evCommit;           // [n] the member's commits so far (recorded behind every call's enqueue)
     std::vector<std::unique_ptr<Worker>> worker;   // [n] or empty (PT_AMD_GROUP_THREADS=0, one member)
     std::vector<GroupDevice> dev;          // distinct devices, dev[0] = member 0's = the reduce's root
     bool rccl = false;                     // the frame is assembled by ncclReduce (else: shared accumulator / on the host)
     const Rccl *api = nullptr;             // ... through this table: librccl.so's, or the emulated reduce of a virtual group (test library)
-    float *reduced = nullptr;              // rccl, two or more devices: the frame the root (dev[0]) receives the reduce into.  No commit writes it.  ONE
+    DevBuf<float> reduced;                 // rccl, two or more devices: the frame the root (dev[0]) receives the reduce into.  No commit writes it.  ONE
                                            // buffer: the reduce that writes it and the read-back that copies it are both on dev[0].coll, in call order
     std::vector<char> waitRed;            // [n] rccl: the member's next commit writes a snapshot a reduce may still be reading: wait for evRed first
     int W = 0, H = 0;
@@ -411,14 +405,12 @@ void group_release_buffers(PtGroup *g) {
     for (GroupDevice &d : g->dev) {
         (void)hipSetDevice(d.device);
         if (d.coll) (void)hipStreamSynchronize(d.coll);
-        if (d.full) { (void)hipFree(d.full); d.full = nullptr; }
-        for (int q = 0; q < 2; ++q)
-            if (d.snap[q]) { (void)hipFree(d.snap[q]); d.snap[q] = nullptr; }
+        d.full.release();
+        for (DevBuf<float> &s : d.snap) s.release();
     }
-    if (g->reduced) {       // (on the root's device)
+    if (g->reduced.p) {     // (on the root's device)
         (void)hipSetDevice(g->dev[0].device);
-        (void)hipFree(g->reduced);
-        g->reduced = nullptr;
+        g->reduced.release();
     }
     g->inited = false;
     g->dirty = false;
@@ -448,8 +440,8 @@ int assemble(PtGroup *g) {
             GroupDevice &d = g->dev[di];
             if (hipSetDevice(d.device) != hipSuccess) { rHip = 1; continue; }
             void *comm = g->failReduces > 0 ? nullptr : d.comm;
-            float *const recv = di != 0 ? nullptr : g->reduced ? g->reduced : d.snap[k];
-            const int ri = rc_.Reduce(d.snap[k], recv, (size_t)g->W * g->H * 3, kNcclFloat, kNcclSum, 0, comm, d.coll);
+            float *const recv = di != 0 ? nullptr : g->reduced.p ? g->reduced.p : d.snap[k].p;
+            const int ri = rc_.Reduce(d.snap[k].p, recv, (size_t)g->W * g->H * 3, kNcclFloat, kNcclSum, 0, comm, d.coll);
             if (ri != 0 && r == 0) r = ri;
         }
         const int r2 = rc_.GroupEnd();
@@ -474,10 +466,10 @@ namespace {
 // the collective's streams, events and RCCL's communicator: once per group, behind the members' first pt_init (see pt_group_create)
 int ensure_collective(PtGroup *g) {
     for (GroupDevice &d : g->dev) {
-        if (d.coll) continue;
-        HIPCHECK(hipSetDevice(d.device));
-        HIPCHECK(hipStreamCreateWithFlags(&d.coll, hipStreamNonBlocking));
-        for (int q = 0; q < 2; ++q) HIPCHECK(hipEventCreateWithFlags(&d.evRed[q], hipEventDisableTiming));
+        HIPCHECK(hipSetDevice(d.device));      // (each member by itself: a call that failed half-way is made up for by the next)
+        if (!d.coll) PTCHECK(d.coll.create(hipStreamNonBlocking));
+        for (Event &e : d.evRed)
+            if (!e) PTCHECK(e.create(hipEventDisableTiming));
     }
     if (g->rccl && !g->dev[0].comm) {
         const int nd = (int)g->dev.size();
@@ -512,7 +504,7 @@ void group_place(PtGroup *g, int id, int hip) {
         GroupDevice gd;
         gd.id = id;
         gd.device = hip;
-        g->dev.push_back(gd);
+        g->dev.push_back(std::move(gd));
         di = (int)g->dev.size() - 1;
     }
     g->dev[di].members.push_back(i);
@@ -540,14 +532,14 @@ int group_build(PtGroup **out, PtGroup *g, const Rccl *emulated, int collective,
     // first pt_init has created their tracing streams (ensure_collective, from pt_group_init): null, two tracing streams, collective.
     // Members that share a device (the one-GPU rehearsal) get a commit stream each -- "alone" means alone on the HIP device: the members of a
     // virtual group sit on GroupDevices of their own and on ONE null stream all the same.
-    g->stream.assign(n, nullptr);
-    g->evCommit.assign(n, nullptr);
+    g->stream = std::vector<Stream>(n);
+    g->evCommit = std::vector<Event>(n);
     bool ok = true;
     const char *ownStreams = getenv("PT_AMD_GROUP_OWN_STREAMS");      // experiments only
     for (int i = 0; i < n && ok; ++i) {
         const bool alone = std::count(g->device.begin(), g->device.end(), g->device[i]) == 1 && !(ownStreams && atoi(ownStreams));
-        ok = hipSetDevice(g->device[i]) == hipSuccess && (alone || hipStreamCreateWithFlags(&g->stream[i], hipStreamNonBlocking) == hipSuccess) &&
-             hipEventCreateWithFlags(&g->evCommit[i], hipEventDisableTiming) == hipSuccess;
+        ok = hipSetDevice(g->device[i]) == hipSuccess && (alone || g->stream[i].create(hipStreamNonBlocking) == PT_OK) &&
+             g->evCommit[i].create(hipEventDisableTiming) == PT_OK;
     }
     if (!ok) {
         pt_group_destroy(g);
@@ -628,15 +620,14 @@ void pt_group_destroy(PtGroup *g) {
     group_release_buffers(g);
     for (size_t i = 0; i < g->stream.size(); ++i) {
         (void)hipSetDevice(g->device[i]);
-        if (g->evCommit[i]) (void)hipEventDestroy(g->evCommit[i]);
+        g->evCommit[i].release();
         (void)hipStreamSynchronize(g->stream[i]);
-        if (g->stream[i]) (void)hipStreamDestroy(g->stream[i]);
+        g->stream[i].release();
     }
     for (GroupDevice &d : g->dev) {
         (void)hipSetDevice(d.device);
-        for (int q = 0; q < 2; ++q)
-            if (d.evRed[q]) (void)hipEventDestroy(d.evRed[q]);
-        if (d.coll) (void)hipStreamDestroy(d.coll);
+        for (Event &e : d.evRed) e.release();
+        d.coll.release();
         if (d.comm) (void)g->api->CommDestroy(d.comm);
     }
     {
@@ -701,23 +692,20 @@ int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeo
     group_release_buffers(g);
     g->W = cam->resolution[0];
     g->H = cam->resolution[1];
-    const size_t frameBytes = (size_t)g->W * (size_t)g->H * 3 * sizeof(float);
-    for (GroupDevice &d : g->dev) {
-        HIPCHECK(hipSetDevice(d.device));
-        HIPCHECK(hipMalloc(&d.full, frameBytes));
-        HIPCHECK(hipMemset(d.full, 0, frameBytes));
-        if (g->rccl)
-            for (int q = 0; q < 2; ++q) {       // (zeroed: the rows of the OTHER devices' members stay zero for good -- no commit and no reduce
-                                                // writes them --, which is what the sum needs)
-                HIPCHECK(hipMalloc(&d.snap[q], frameBytes));
-                HIPCHECK(hipMemset(d.snap[q], 0, frameBytes));
-            }
-        if (g->rccl && g->dev.size() > 1 && &d == &g->dev[0]) {      // the root's result frame (see assemble)
-            HIPCHECK(hipMalloc(&g->reduced, frameBytes));
-            HIPCHECK(hipMemset(g->reduced, 0, frameBytes));
+    const size_t frameFloats = (size_t)g->W * (size_t)g->H * 3;
+    const auto frames = [&]() -> int {
+        for (GroupDevice &d : g->dev) {
+            HIPCHECK(hipSetDevice(d.device));
+            PTCHECK(d.full.alloc_zeroed(frameFloats));
+            if (g->rccl)      // (zeroed: the rows of the OTHER devices' members stay zero for good -- no commit and no reduce writes them --,
+                              // which is what the sum needs)
+                for (DevBuf<float> &s : d.snap) PTCHECK(s.alloc_zeroed(frameFloats));
+            if (g->rccl && g->dev.size() > 1 && &d == &g->dev[0]) PTCHECK(g->reduced.alloc_zeroed(frameFloats));      // the root's result frame (see assemble)
+            HIPCHECK(hipDeviceSynchronize());
         }
-        HIPCHECK(hipDeviceSynchronize());
-    }
+        return PT_OK;
+    };
+    if (const int rc = frames()) { group_release_buffers(g); return rc; }      // (a failure between two allocations leaves none behind)
     g->waitRed.assign(n, 0);
     PtOptions base;
     memset(&base, 0, sizeof base);
@@ -729,7 +717,7 @@ int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeo
         o.device = g->device[i];
         o.stream = g->stream[i];
         o.flags &= ~PT_FLAG_ACCUM_SHARD_ROWS;
-        o.accum_dev = g->dev[g->devIndex[i]].full;          // own rows in place, the co-members' beside them, zeros for the other devices' rows
+        o.accum_dev = g->dev[g->devIndex[i]].full.p;        // own rows in place, the co-members' beside them, zeros for the other devices' rows
         return pt_init(cam, geoms, ngeoms, mats, nmats, traceDepth, &o);
     });
     if (rc) return rc;
@@ -749,8 +737,8 @@ int pt_group_iterate_batch(PtGroup *g, int frame, int first_iter, int count) {
     int rc = for_members(g, [&](int i) -> int {
         if (g->rccl) {      // this call's commit copies the member's rows into snapshot k as well
             GroupDevice &d = g->dev[g->devIndex[i]];
-            R().snapTarget = d.snap[g->k];
-            R().snapWait = g->waitRed[i] ? d.evRed[g->k] : nullptr;
+            R().snapTarget = d.snap[g->k].p;
+            R().snapWait = g->waitRed[i] ? d.evRed[g->k].h : nullptr;
             g->waitRed[i] = 0;
         }
         int r = pt_iterate_batch(frame, first_iter, count, nullptr);
@@ -807,12 +795,12 @@ int pt_group_readback(PtGroup *g, float *rgb_sum_host) {
     }
     if (g->rccl) {
         HIPCHECK(hipSetDevice(g->dev[0].device));
-        const float *const frame = g->reduced ? g->reduced : g->dev[0].snap[g->last];
+        const float *const frame = g->reduced.p ? g->reduced.p : g->dev[0].snap[g->last].p;
         HIPCHECK(hipMemcpyAsync(rgb_sum_host, frame, frameFloats * sizeof(float), hipMemcpyDeviceToHost, g->dev[0].coll));
         HIPCHECK(hipStreamSynchronize(g->dev[0].coll));
     } else if (g->dev.size() == 1) {
         HIPCHECK(hipSetDevice(g->dev[0].device));
-        HIPCHECK(hipMemcpyAsync(rgb_sum_host, g->dev[0].full, frameFloats * sizeof(float), hipMemcpyDeviceToHost, g->dev[0].coll));
+        HIPCHECK(hipMemcpyAsync(rgb_sum_host, g->dev[0].full.p, frameFloats * sizeof(float), hipMemcpyDeviceToHost, g->dev[0].coll));
         HIPCHECK(hipStreamSynchronize(g->dev[0].coll));
     } else {
         // host gather: row y belongs to member y % n, i.e. to that member's device
@@ -822,7 +810,7 @@ int pt_group_readback(PtGroup *g, float *rgb_sum_host) {
         for (size_t di = 0; di < g->dev.size(); ++di) {
             GroupDevice &d = g->dev[di];
             HIPCHECK(hipSetDevice(d.device));
-            HIPCHECK(hipMemcpyAsync(g->stage.data(), d.full, frameFloats * sizeof(float), hipMemcpyDeviceToHost, d.coll));
+            HIPCHECK(hipMemcpyAsync(g->stage.data(), d.full.p, frameFloats * sizeof(float), hipMemcpyDeviceToHost, d.coll));
             HIPCHECK(hipStreamSynchronize(d.coll));
             for (int y = 0; y < g->H; ++y)
                 if (g->devIndex[y % n] == (int)di) memcpy(rgb_sum_host + (size_t)y * rowFloats, g->stage.data() + (size_t)y * rowFloats, rowFloats * sizeof(float));

@@ -219,6 +219,7 @@ int pt_test_sphere_groups(const PtCamera *cam, const PtGeom *geoms, int ngeoms, 
 }
 
 int64_t pt_test_live_device_buffers(void) { return (int64_t)g_liveDevBufs.load(); }
+int64_t pt_test_live_handles(void) { return (int64_t)g_liveHandles.load(); }
 
 int pt_test_group_fail_next_reduce(PtGroup *g, int count) {
     if (!g || count < 0) return fail(PT_ERR_INVALID, "pt_test_group_fail_next_reduce: bad argument");
@@ -252,7 +253,7 @@ int pt_test_emulated_reduce(const float *const *send_host, int ranks, int64_t co
     const Rccl &api = *EmulatedReduce::table();
     struct Rank {
         DevBuf<float> send;
-        hipStream_t stream = nullptr;
+        Stream stream;
         void *comm = nullptr;
     };
     std::vector<Rank> rk(ranks);
@@ -261,7 +262,7 @@ int pt_test_emulated_reduce(const float *const *send_host, int ranks, int64_t co
     int rc = PT_OK, r = 0;
     for (int i = 0; i < ranks && rc == PT_OK; ++i) {
         rc = rk[i].send.upload(send_host[i], (size_t)count);
-        if (rc == PT_OK && hipStreamCreateWithFlags(&rk[i].stream, hipStreamNonBlocking) != hipSuccess) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: no stream");
+        if (rc == PT_OK && rk[i].stream.create(hipStreamNonBlocking) != PT_OK) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: no stream");
     }
     if (rc == PT_OK && !in_place) rc = recv.alloc_zeroed((size_t)count);
     if (rc == PT_OK && (r = api.CommInitAll(comms.data(), ranks, nullptr)) != 0) rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: CommInitAll: %s", api.GetErrorString(r));
@@ -290,10 +291,8 @@ int pt_test_emulated_reduce(const float *const *send_host, int ranks, int64_t co
     for (int i = 0; i < ranks && rc == PT_OK && send_after_host; ++i)
         if (send_after_host[i] && hipMemcpy(send_after_host[i], rk[i].send.p, (size_t)count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(PT_ERR_HIP, "pt_test_emulated_reduce: read-back");
-    for (int i = 0; i < ranks; ++i) {
+    for (int i = 0; i < ranks; ++i)      // (the communicators before the streams, which go with `rk`)
         if (rk[i].comm) (void)api.CommDestroy(rk[i].comm);
-        if (rk[i].stream) (void)hipStreamDestroy(rk[i].stream);
-    }
     return rc;
 }
 
@@ -318,6 +317,23 @@ int launch_wait(void (*kernel)(P...), dim3 grid, size_t ldsBytes, const A &...ar
     hipLaunchKernelGGL(kernel, grid, dim3(kTestThreads), ldsBytes, nullptr, args...);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
+    return PT_OK;
+}
+
+// launch() on the null stream, once; with `ms`: once untimed, then `reps` times between two events, ms[r] the r-th one's time
+template <class Launch>
+int timed_launches(int reps, float *ms, Launch launch) {
+    Event ev[2];
+    if (ms) for (Event &e : ev) PTCHECK(e.create(hipEventDefault));
+    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {
+        if (ms && r) HIPCHECK(hipEventRecord(ev[0], nullptr));
+        PTCHECK(launch());
+        if (ms && r) {
+            HIPCHECK(hipEventRecord(ev[1], nullptr));
+            HIPCHECK(hipEventSynchronize(ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[r - 1], ev[0], ev[1]));
+        }
+    }
     return PT_OK;
 }
 
@@ -1302,19 +1318,12 @@ int pt_test_temporal(int capture, int w, int h, int samples, const float *rgb_su
     T.W = w; T.H = h; T.samples = (float)samples;
     T.out = out.p; T.outN = outN.p;
     const dim3 grid((unsigned)((P + kBlock - 1) / kBlock));
-    EventSet es;
-    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
-    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
-        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+    PTCHECK(timed_launches(reps, ms, [&]() -> int {
         if (capture == 2) hipLaunchKernelGGL(k_temporal<kTemporalMoments>, grid, dim3(kBlock), 0, nullptr, T);
         else if (capture) hipLaunchKernelGGL(k_temporal<kTemporalCapture>, grid, dim3(kBlock), 0, nullptr, T);
         else hipLaunchKernelGGL(k_temporal<kTemporalFilter>, grid, dim3(kBlock), 0, nullptr, T);
-        if (ms && r) {
-            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
-            HIPCHECK(hipEventSynchronize(es.ev[1]));
-            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
-        }
-    }
+        return PT_OK;
+    }));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1342,17 +1351,7 @@ int pt_test_spatial_variance(int radius, int form, int w, int h, const float *m4
     A.invN = 1.0f / (sigma_normal * sigma_normal);
     A.invP = 1.0f / (sigma_position * sigma_position);
     A.out = out.p;
-    EventSet es;
-    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
-    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
-        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
-        PTCHECK(spatial_launch(A, radius, form, nullptr));
-        if (ms && r) {
-            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
-            HIPCHECK(hipEventSynchronize(es.ev[1]));
-            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
-        }
-    }
+    PTCHECK(timed_launches(reps, ms, [&] { return spatial_launch(A, radius, form, nullptr); }));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1411,12 +1410,12 @@ int pt_test_demodulate(int form, int inplace, int bytes, int w, int h, int sampl
     A.invN = 1.0f / (sigma_normal * sigma_normal);
     A.invP = 1.0f / (sigma_position * sigma_position);
     A.asum = asum.p; A.demodN = (float)samples; A.demodEps = min_albedo;
-    EventSet es;
-    if (ms) for (int i = 0; i < 4; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    Event ev[4];
+    if (ms) for (Event &e : ev) PTCHECK(e.create(hipEventDefault));
     for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed run first)
-        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        if (ms && r) HIPCHECK(hipEventRecord(ev[0], nullptr));
         PTCHECK(demod_launch(D, inplace != 0, nullptr));
-        if (ms && r) HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+        if (ms && r) HIPCHECK(hipEventRecord(ev[1], nullptr));
         if (r == 0 && demod4_out) HIPCHECK(hipMemcpy(demod4_out, ping[1].p, P * sizeof(float4), hipMemcpyDeviceToHost));
         for (int i = 0; i < levels; ++i) {
             const bool last = i == levels - 1;
@@ -1434,15 +1433,15 @@ int pt_test_demodulate(int form, int inplace, int bytes, int w, int h, int sampl
                 grid = atrousGridGather(w, h);
             }
             void *kargs[] = {&A};
-            if (ms && r && last) HIPCHECK(hipEventRecord(es.ev[2], nullptr));
+            if (ms && r && last) HIPCHECK(hipEventRecord(ev[2], nullptr));
             HIPCHECK(hipLaunchKernel(last ? atrous_last_kernel<AtrousDemod>(bytes != 0, f) : atrous_kernel<AtrousGuided>(false, false, false, f), dim3((unsigned)grid),
                                      dim3(kBlock), kargs, 0, nullptr));
         }
         if (ms && r) {
-            HIPCHECK(hipEventRecord(es.ev[3], nullptr));
-            HIPCHECK(hipEventSynchronize(es.ev[3]));
-            HIPCHECK(hipEventElapsedTime(&ms[2 * (r - 1)], es.ev[0], es.ev[1]));
-            HIPCHECK(hipEventElapsedTime(&ms[2 * (r - 1) + 1], es.ev[2], es.ev[3]));
+            HIPCHECK(hipEventRecord(ev[3], nullptr));
+            HIPCHECK(hipEventSynchronize(ev[3]));
+            HIPCHECK(hipEventElapsedTime(&ms[2 * (r - 1)], ev[0], ev[1]));
+            HIPCHECK(hipEventElapsedTime(&ms[2 * (r - 1) + 1], ev[2], ev[3]));
         }
     }
     HIPCHECK(hipGetLastError());
@@ -1518,21 +1517,13 @@ int pt_test_temporal_albedo(int form, int front, int w, int h, int samples, cons
     D.npix = (int)P;
     D.samples = 1.0f; D.samplesM1 = 0.0f; D.eps = min_albedo;
     const dim3 grid((unsigned)((P + kBlock - 1) / kBlock));
-    EventSet es;
-    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
-    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed run first)
-        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+    PTCHECK(timed_launches(reps, ms, [&]() -> int {
         if (form == 2) hipLaunchKernelGGL((k_temporal<kTemporalMoments, true>), grid, dim3(kBlock), 0, nullptr, T);
         else if (form == 1) hipLaunchKernelGGL((k_temporal<kTemporalCapture, true>), grid, dim3(kBlock), 0, nullptr, T);
         else if (front == 1) hipLaunchKernelGGL((k_temporal<kTemporalFilterDemod, true>), grid, dim3(kBlock), 0, nullptr, T);
         else hipLaunchKernelGGL((k_temporal<kTemporalFilter, true>), grid, dim3(kBlock), 0, nullptr, T);
-        if (front == 2) PTCHECK(demod_launch(D, true, nullptr));
-        if (ms && r) {
-            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
-            HIPCHECK(hipEventSynchronize(es.ev[1]));
-            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
-        }
-    }
+        return front == 2 ? demod_launch(D, true, nullptr) : (int)PT_OK;
+    }));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1600,10 +1591,7 @@ int pt_test_temporal_motion(int form, int albedo, int motion, int w, int h, int 
     T.ha = Ha.p; T.asum = Asum.p; T.outA = outA.p; T.eps = min_albedo;
     T.motion = rows.p; T.motionN = motion ? nrows : 0; T.histCap = hist_cap;
     const dim3 grid((unsigned)((P + kBlock - 1) / kBlock));
-    EventSet es;
-    if (ms) for (int i = 0; i < 2; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
-    for (int r = 0; r < (ms ? reps + 1 : 1); ++r) {           // (timed: one untimed launch first)
-        if (ms && r) HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+    PTCHECK(timed_launches(reps, ms, [&]() -> int {
         if (albedo) {
             if (form == 3) temporal_motion_launch<kTemporalFilterDemod, true>(motion != 0, grid, T);
             else if (form == 2) temporal_motion_launch<kTemporalMoments, true>(motion != 0, grid, T);
@@ -1614,12 +1602,8 @@ int pt_test_temporal_motion(int form, int albedo, int motion, int w, int h, int 
             else if (form == 1) temporal_motion_launch<kTemporalCapture, false>(motion != 0, grid, T);
             else temporal_motion_launch<kTemporalFilter, false>(motion != 0, grid, T);
         }
-        if (ms && r) {
-            HIPCHECK(hipEventRecord(es.ev[1], nullptr));
-            HIPCHECK(hipEventSynchronize(es.ev[1]));
-            HIPCHECK(hipEventElapsedTime(&ms[r - 1], es.ev[0], es.ev[1]));
-        }
-    }
+        return PT_OK;
+    }));
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out4, out.p, P * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1655,19 +1639,19 @@ int pt_test_noise_stats(const float *rgb_sum, const float *lum_sq_sum, int w, in
     const int tilesX = (w + kNoiseTile - 1) / kNoiseTile;
     const dim3 gridN((unsigned)((tiles + 4 * tpw - 1) / (4 * tpw))), gridV((unsigned)((P + kBlock - 1) / kBlock));
     const float n = (float)samples, nM1 = (float)(samples - 1);
-    EventSet es;
-    for (int i = 0; i < 3; ++i) HIPCHECK(hipEventCreate(&es.ev[i]));
+    Event ev[3];
+    for (Event &e : ev) PTCHECK(e.create(hipEventDefault));
     hipLaunchKernelGGL(k_variance, gridV, dim3(kBlock), 0, nullptr, S.p, Q.p, (int)P, n, nM1, var.p);      // (k_noise_stats has run above)
     for (int r = 0; r < reps; ++r) {
         HIPCHECK(hipMemsetAsync(frame.p, 0, 2 * sizeof(uint32_t), nullptr));
-        HIPCHECK(hipEventRecord(es.ev[0], nullptr));
+        HIPCHECK(hipEventRecord(ev[0], nullptr));
         hipLaunchKernelGGL(k_noise_stats, gridN, dim3(kBlock), 0, nullptr, S.p, Q.p, w, h, tilesX, (int)tiles, tpw, n, nM1, lum_floor, thr2, frame.p, map.p);
-        HIPCHECK(hipEventRecord(es.ev[1], nullptr));
+        HIPCHECK(hipEventRecord(ev[1], nullptr));
         hipLaunchKernelGGL(k_variance, gridV, dim3(kBlock), 0, nullptr, S.p, Q.p, (int)P, n, nM1, var.p);
-        HIPCHECK(hipEventRecord(es.ev[2], nullptr));
-        HIPCHECK(hipEventSynchronize(es.ev[2]));
-        HIPCHECK(hipEventElapsedTime(&ms[2 * r], es.ev[0], es.ev[1]));
-        HIPCHECK(hipEventElapsedTime(&ms[2 * r + 1], es.ev[1], es.ev[2]));
+        HIPCHECK(hipEventRecord(ev[2], nullptr));
+        HIPCHECK(hipEventSynchronize(ev[2]));
+        HIPCHECK(hipEventElapsedTime(&ms[2 * r], ev[0], ev[1]));
+        HIPCHECK(hipEventElapsedTime(&ms[2 * r + 1], ev[1], ev[2]));
     }
     HIPCHECK(hipGetLastError());
     return PT_OK;

@@ -104,3 +104,5 @@ def test_no_device_buffer_lives_before_the_first_init(pt):
     T = pt.test_lib()
     T.pt_free()                      # (before the first pt_init: a no-op)
     assert T.pt_test_live_device_buffers() == 0
+    assert "pt_test_live_handles" in pt.TEST_ABI_SYMBOLS and not hasattr(pt.lib(), "pt_test_live_handles")
+    assert T.pt_test_live_handles() == 0
