@@ -151,6 +151,11 @@ enum {
                                     without either of the two flags, and from pt_group_init; every refusal of PT_FLAG_TEMPORAL stands.  A
                                     renderer without the flag is what it was in every respect.  (Additive, no new function, no struct changed:
                                     the ABI version stays.) */
+    PT_FLAG_MOTION = 8192,       /* motion blur (section "motion blur" below): `geoms` of a full pt_init holds PT_MOTION_STEPS x ngeoms records,
+                                    the scene in 16 poses across the shutter, and iteration i renders the pose PT_MOTION_STEP(i) alone.
+                                    PT_ERR_INVALID with PT_FLAG_TEMPORAL, PT_FLAG_OBJECT_HISTORY, PT_FLAG_DISPLAY_FILTER, PT_FLAG_DEMODULATE,
+                                    PT_FLAG_SPATIAL_VARIANCE or PT_FLAG_KEEP_RENDERER, and from pt_group_init.  A renderer without the flag is
+                                    what it was in every respect.  (Additive, no new function, no struct changed: the ABI version stays.) */
     PT_FLAG_DIRECT_LIGHTING = 4/* README.md:107-108: "a final ray directly to a random point on an emissive object": at the
                                     last of the traceDepth bounces a diffuse scatter aims at a uniformly chosen point of a
                                     uniformly chosen emissive primitive (cosine-weighted), and ONE more bounce collects what
@@ -187,6 +192,38 @@ typedef struct PtOptions {
 
 #define PT_MAX_DEPTH 62
 #define PT_MAX_BATCH 256
+
+/* ---- motion blur (PT_FLAG_MOTION) ---------------------------------------------------------------------------------------------------
+ * "Some method of defining object motion, and motion blur by averaging samples at different times" (the course README's extra): a frame
+ * averages iterations, so an iteration that sees the scene at ONE time of the shutter is a sample at that time.
+ *
+ * Under the flag `geoms` of a full pt_init holds PT_MOTION_STEPS x ngeoms records: step s's scene is geoms[s * ngeoms .. (s + 1) * ngeoms),
+ * the scene at shutter time t_s = (s + 0.5) / PT_MOTION_STEPS.  The library knows no time and interpolates nothing: the caller supplies each
+ * step's complete PtGeom, matrices included.  Steps must agree on every geom's type and materialid; what pt_set_meshes, pt_set_textures and
+ * pt_set_bump_maps registered applies to geom g of every step.
+ *
+ * Iteration i renders step PT_MOTION_STEP(i): runs of PT_MOTION_RUN consecutive iterations share a step (an aligned batch of 8 is one set
+ * of launches), and the runs visit the steps in bit-reversed order, so that any prefix of a cycle of PT_MOTION_STEPS x PT_MOTION_RUN = 128
+ * iterations spreads over the shutter.  The step is a function of i alone: batching never changes a frame.  pt_iterate_batch cuts its
+ * range at run boundaries and does for each piece what it does for a whole call; PT_FLAG_TRACE_AHEAD's batches end with their run.
+ *
+ * THE LAW: after iterations 1..n both accumulators, PtCounters and every read-back equal, bit for bit, what comes of adding, in iteration
+ * order, iteration i of an unflagged renderer initialised with step PT_MOTION_STEP(i)'s geoms.
+ *
+ * The renderer plans all 16 steps before anything is touched; a step that is refused refuses the call, and the message names the step.  The
+ * steps may take different forms of k_bounce; what the in-flight slots share (pool sizes, path layout, batch size, frame) must agree across
+ * steps, else PT_ERR_INVALID.  Texels and mesh records, which no pose changes, are held once.  Row shards, PT_FLAG_MOMENTS,
+ * PT_FLAG_DIRECT_LIGHTING (emitters per step), PT_FLAG_MIXTURE_WEIGHTED, PT_FLAG_TRACE_AHEAD, a thin lens and PT_FLAG_KERNEL_TIMING go with
+ * the flag.  On a flagged renderer pt_denoise*, pt_gbuffer are refused (a first-hit guide has no single pose), and the same-scene camera
+ * move runs the full call inside with all 16 steps.
+ *
+ * Known costs: 16 poses are 16 ghosts when an object moves by much more than its own size on screen, and a frame of n iterations weights
+ * the steps equally only when n is a multiple of 128. */
+#define PT_MOTION_STEPS 16
+#define PT_MOTION_RUN 8
+/* bitrev4(((i - 1) / PT_MOTION_RUN) % PT_MOTION_STEPS), i >= 1 */
+#define PT_MOTION_BITREV4(r) (((((r) >> 0) & 1) << 3) | ((((r) >> 1) & 1) << 2) | ((((r) >> 2) & 1) << 1) | (((r) >> 3) & 1))
+#define PT_MOTION_STEP(i) PT_MOTION_BITREV4((((i) - 1) / PT_MOTION_RUN) % PT_MOTION_STEPS)
 /* Bumped whenever a struct of this header changes size or meaning (7: PtTexture / PtTexBinding, pt_set_textures; 6: round 6 -- pt_group_iterate / pt_group_reduce, the group's asynchronous
  * assembly; 5: contexts and groups; PtMesh has carried `normals` and `materials` since 4).  A host built against another header finds out with
  * pt_abi_version() != PT_AMD_ABI_VERSION before it passes structs. */

@@ -348,6 +348,11 @@ int64_t pt_test_live_device_buffers(void);
 /* ... and the streams plus events plus page-locked host allocations they, its groups and the scan library hold (the same: one owner type
  * each, counted in this library only): 0 after pt_free and pt_group_destroy */
 int64_t pt_test_live_handles(void);
+/* The scene tables pt_init allocated for THIS library's renderer (host only, from the plans): out[0] the poses it holds (1, or
+ * PT_MOTION_STEPS under PT_FLAG_MOTION), out[1] / out[2] the device buffers and bytes of ONE pose's own tables (step 0's), out[3] / out[4] of
+ * the tables held once whatever the number of poses (texels, mesh records), out[5] the bytes of every pose's own tables together: the
+ * renderer's scene tables are out[4] + out[5] bytes in out[3] + out[0] x out[1] buffers.  PT_ERR_NOT_INIT before pt_init. */
+int pt_test_pose_tables(int64_t out[6]);
 
 #ifdef __cplusplus
 }

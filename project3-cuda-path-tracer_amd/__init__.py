@@ -69,6 +69,16 @@ PT_FLAG_KEEP_RENDERER = 2048
 # primitive in another pose than the history's
 PT_FLAG_OBJECT_HISTORY = 4096
 PT_OBJECT_HISTORY_MAX = 4.0
+# motion blur (include/pt_amd.h, "motion blur"): the flag, the poses across the shutter, the iterations that share one
+PT_FLAG_MOTION = 8192            # motion blur: pt_init takes PT_MOTION_STEPS poses of the scene, iteration i renders PT_MOTION_STEP(i)'s
+PT_MOTION_STEPS = 16
+PT_MOTION_RUN = 8
+
+
+def motion_step(iteration):
+    """PT_MOTION_STEP (include/pt_amd.h): the step iteration `iteration` >= 1 renders -- runs of PT_MOTION_RUN iterations, bit-reversed."""
+    r = ((iteration - 1) // PT_MOTION_RUN) % PT_MOTION_STEPS
+    return ((r & 1) << 3) | ((r & 2) << 1) | ((r & 4) >> 1) | ((r & 8) >> 3)
 
 # second link target of the same source: + the test-only entry points of include/pt_amd_test.h (tests/ and profiles/ only)
 TEST_LIB_PATH = os.path.join(HERE, "csrc", "libpt_amd_test.so")
@@ -103,7 +113,7 @@ TEST_ABI_SYMBOLS = [
     "pt_test_display", "pt_test_spatial_variance", "pt_test_albedo", "pt_test_demodulate", "pt_test_temporal_albedo", "pt_test_history_albedo",
     "pt_test_group_create_virtual", "pt_test_emulated_reduce", "pt_test_slab_decisions", "pt_test_sphere_groups", "pt_test_group_tally",
     "pt_test_camera_resolved_device", "pt_test_last_camera_move", "pt_test_keep_mismatch",
-    "pt_test_motion_table", "pt_test_history_motion", "pt_test_temporal_motion", "pt_test_live_handles",
+    "pt_test_motion_table", "pt_test_history_motion", "pt_test_temporal_motion", "pt_test_live_handles", "pt_test_pose_tables",
 ]
 
 
@@ -297,6 +307,7 @@ def _bind(L, with_tests):
         L.pt_test_bounce_form.argtypes = [C.c_uint32, C.POINTER(C.c_uint32)]
         L.pt_test_live_device_buffers.argtypes = []
         L.pt_test_live_device_buffers.restype = i64
+        L.pt_test_pose_tables.argtypes = [C.POINTER(C.c_int64)]
         L.pt_test_live_handles.argtypes = []
         L.pt_test_live_handles.restype = i64
         L.pt_test_renderer_state.argtypes = [C.POINTER(C.c_uint32)]
@@ -388,6 +399,9 @@ def host_lib():
             getattr(H, n).restype = vp
         H.pth_scene_image_name.argtypes = [vp]
         H.pth_scene_image_name.restype = C.c_char_p
+        H.pth_scene_motion_steps.argtypes = [vp]
+        H.pth_scene_step_geoms.argtypes = [vp, C.c_int]
+        H.pth_scene_step_geoms.restype = vp
         H.pth_scene_set_resolution.argtypes = [vp, C.c_int, C.c_int]
         H.pth_scene_set_resolution.restype = None
         H.pth_scene_num_meshes.argtypes = [vp]
@@ -462,6 +476,11 @@ class Scene:
         # `BUMP <file> <scale>` lines: per geom the index of its height map among `textures` or -1, and its scale (0 where unbumped)
         self.geom_bumps = np.array([H.pth_scene_geom_bump(h, g) for g in range(ng)], np.int32)
         self.bump_scales = np.array([H.pth_scene_geom_bump_scale(h, g) for g in range(ng)], np.float32)
+        # TRANS_END / ROTAT_END / SCALE_END lines: the scene in PT_MOTION_STEPS poses across the shutter, (steps, ngeoms) records -- step s
+        # is byte for byte the geoms of a static scene file with the values interpolated at (s + 0.5) / steps -- or None: nothing moves
+        steps = H.pth_scene_motion_steps(h)
+        self.step_geoms = np.stack([np.frombuffer(C.string_at(H.pth_scene_step_geoms(h, k), GEOM_DTYPE.itemsize * ng), GEOM_DTYPE) for k in range(steps)]) \
+            if steps and ng else None
         w, hh = (int(v) for v in self.camera["resolution"][0])
         self.image = np.zeros((hh, w, 3), np.float32)   # RenderState::image (src/sceneStructs.h:53)
 
@@ -483,8 +502,13 @@ _scene = None
 def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, device=-1, flags=0, traceDepth=None,
                   pipeline_depth=0, max_batch=0, lens_radius=0.0, focal_distance=0.0, direct_lighting=False, trace_ahead=False,
                   mixture_weighted=False, moments=False, temporal=False, display_filter=False, spatial_variance=False, demodulate=False,
-                  demod_history=False, keep=False, object_history=False):
+                  demod_history=False, keep=False, object_history=False, motion=None):
     """reference src/pathtrace.cu:75-85.  `scene` is borrowed until pathtraceFree().
+    motion: PT_FLAG_MOTION (include/pt_amd.h, "motion blur") -- None: motion-blurred where the scene file defines motion (scene.step_geoms),
+    static otherwise; False: the static scene (scene.geoms); True: scene.step_geoms, which must exist; or an array of PT_MOTION_STEPS x
+    len(scene.geoms) geom records of the caller's own, step-major.  Iteration i then renders step motion_step(i) alone, and the frame is, bit
+    for bit, the sum of those iterations of static renderers.  Not with temporal, object_history, display_filter, demodulate,
+    spatial_variance or keep; denoise* and gbuffer refuse a motion-blurred renderer.
     object_history: PT_FLAG_OBJECT_HISTORY (with moments=True and temporal=True) -- calling pathtraceInit AGAIN over the live renderer with the
     same objects in other poses (geoms' types and materials, the materials and everything registered equal byte for byte; translation,
     rotation, scale and the matrices free) carries the history over and reprojects it through each primitive's own motion; any other change
@@ -535,9 +559,21 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         flags |= PT_FLAG_KEEP_RENDERER
     if object_history:
         flags |= PT_FLAG_OBJECT_HISTORY
+    geoms = np.ascontiguousarray(scene.geoms)
+    ngeoms = len(geoms)
+    if motion is None:
+        motion = getattr(scene, "step_geoms", None) is not None
+    if motion is True:
+        if getattr(scene, "step_geoms", None) is None:
+            raise PtError("pathtraceInit(motion=True): the scene defines no motion (TRANS_END / ROTAT_END / SCALE_END)")
+        motion = scene.step_geoms
+    if motion is not False:
+        geoms = np.ascontiguousarray(np.asarray(motion, GEOM_DTYPE).reshape(-1))
+        if len(geoms) != PT_MOTION_STEPS * ngeoms:
+            raise PtError("pathtraceInit(motion=...): %d geom records, PT_MOTION_STEPS x %d expected" % (len(geoms), ngeoms))
+        flags |= PT_FLAG_MOTION
     opt = PtOptions(shard_rank, shard_count, device, flags, pipeline_depth, max_batch, stream or None, accum_dev or None,
                     lens_radius, focal_distance)
-    geoms = np.ascontiguousarray(scene.geoms)
     mats = np.ascontiguousarray(scene.materials)
     cam = np.ascontiguousarray(scene.camera)
     depth = scene.traceDepth if traceDepth is None else traceDepth
@@ -552,7 +588,7 @@ def pathtraceInit(scene, shard_rank=0, shard_count=1, stream=0, accum_dev=0, dev
         import atexit
         atexit.register(pathtraceFree)
         _atexit_registered = True
-    _check(lib().pt_init(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), depth, C.byref(opt)))
+    _check(lib().pt_init(_p(cam), _p(geoms), ngeoms, _p(mats), len(mats), depth, C.byref(opt)))
     _scene = scene
     global _last_init
     _last_init = (cam, geoms, mats, depth, (shard_rank, shard_count, device, flags, lens_radius, focal_distance),
@@ -570,6 +606,15 @@ def pathtraceSetCamera(camera_or_scene):
     _check(lib().pt_init(_p(cam), None, 0, None, 0, PT_SAME_SCENE, None))
     if _last_init is not None:
         _last_init = (cam,) + tuple(_last_init[1:])
+
+
+def pose_tables():
+    """pt_test_pose_tables (test library; see renderer_from_test_library): the scene tables the live renderer's pt_init allocated --
+    {"poses", "own_buffers", "own_bytes" (one pose's own tables), "shared_buffers", "shared_bytes" (held once: texels, mesh records),
+    "all_own_bytes" (every pose's own tables together)}."""
+    out = (C.c_int64 * 6)()
+    _tcheck(test_lib().pt_test_pose_tables(out))
+    return dict(zip(("poses", "own_buffers", "own_bytes", "shared_buffers", "shared_bytes", "all_own_bytes"), (int(v) for v in out)))
 
 
 def camera_move_info():
@@ -1149,7 +1194,8 @@ def debug_trace_paths(iteration, bounces, npixels):
         set_textures(*textures, L=T)
         set_bump_maps(*bumps, L=T)
         opt = PtOptions(rank, count, device, flags & ~(PT_FLAG_TRACE_AHEAD | PT_FLAG_KERNEL_TIMING), 1, 1, None, None, lens_radius, focal_distance)
-        _tcheck(T.pt_init(_p(cam), _p(geoms), len(geoms), _p(mats), len(mats), depth, C.byref(opt)))
+        ngeoms = len(geoms) // (PT_MOTION_STEPS if flags & PT_FLAG_MOTION else 1)      # (motion blur: every step's geoms)
+        _tcheck(T.pt_init(_p(cam), _p(geoms), ngeoms, _p(mats), len(mats), depth, C.byref(opt)))
     try:
         o, d, c = (np.empty((npixels, 3), np.float32) for _ in range(3))
         pix = np.empty(npixels, np.int32)

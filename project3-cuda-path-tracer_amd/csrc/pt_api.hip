@@ -233,6 +233,16 @@ struct SceneTables {
     }
 };
 
+// PT_FLAG_MOTION: one planned pose of the scene -- everything a launch reads that the pose decides: the plan's scalars, the tables (but
+// the ones no pose changes, texels and mesh records, which stay in State::tab: held once), the forms of k_bounce and the grids.  The
+// pose the renderer is in lives in State's own members; the others wait here, and activate_step exchanges the two on the host.
+struct Pose {
+    PlanScalars scalars;
+    SceneTables tab;
+    const void *kernFirst = nullptr, *kernNext = nullptr;
+    int gridWalk = 0, gridWalkFirst = 0, grid = 0, gridFirst = 0;
+};
+
 // (it keeps the scalars of the scene's plan -- cam, prm, P, nLocal, flags, the flags that pick the forms of k_bounce, the sizes -- as its base)
 struct State : PlanScalars {
     bool init = false;
@@ -265,6 +275,12 @@ struct State : PlanScalars {
     int grid = 0;           // ... the persistent grid of k_bounce<false>
     int gridFirst = 0;      // ... and of k_bounce<true> (its own register budget, hence its own residency)
     const void *kernFirst = nullptr, *kernNext = nullptr;   // the forms of k_bounce the camera-ray launch / the later ones take (bounce_form)
+    // PT_FLAG_MOTION: the PT_MOTION_STEPS poses (none without the flag); poses[step] is the slot of the one the members above hold now
+    std::vector<Pose> poses;
+    int step = 0;
+    // what pt_init allocated of scene tables (pt_test_pose_tables): the buffers and bytes of ONE pose's own tables (step 0's), of the
+    // tables held once whatever the number of poses (the camera-invariant ones), and the bytes of every pose's own tables together
+    struct TableCount { long long ownBuffers = 0, ownBytes = 0, sharedBuffers = 0, sharedBytes = 0, allOwnBytes = 0; } tables;
     long long iterations = 0;
     long long committed = 0; // iterations committed into the accumulators since pt_init: `iterations` without pt_counters_reset's zeroing (the capture's n)
     long long seq = 0;      // batches enqueued since pt_init: slot = seq % nslots
@@ -328,6 +344,27 @@ std::vector<State *> g_contexts;          // every context pt_ctx_create made an
 std::mutex g_groupMutex;                  // guards g_groups
 std::vector<PtGroup *> g_groups;          // every group pt_group_create made and pt_group_destroy has not released (the exit handler destroys them:
                                           // their issuing threads, communicators, streams and frame buffers -- pt_group.h)
+
+// PT_FLAG_MOTION: the renderer's pose against a waiting one -- a host-side exchange of the members a launch reads.  Launches take
+// pointers by value and no table is ever rewritten, so batches of different poses may be in flight on neighbouring slots: no drain.
+void exchange_pose(State &S, Pose &p) {
+    std::swap(static_cast<PlanScalars &>(S), p.scalars);
+    std::swap(S.tab, p.tab);
+    std::swap(S.tab.dTexels, p.tab.dTexels);        // (held once: they stay where they are)
+    std::swap(S.tab.dMeshRecs, p.tab.dMeshRecs);
+    std::swap(S.kernFirst, p.kernFirst); std::swap(S.kernNext, p.kernNext);
+    std::swap(S.gridWalk, p.gridWalk); std::swap(S.gridWalkFirst, p.gridWalkFirst);
+    std::swap(S.grid, p.grid); std::swap(S.gridFirst, p.gridFirst);
+}
+void activate_step(State &S, int step) {
+    if (S.poses.empty() || step == S.step) return;
+    exchange_pose(S, S.poses[(size_t)S.step]);
+    exchange_pose(S, S.poses[(size_t)step]);
+    S.step = step;
+}
+// the step iteration `iter` renders, and the first iteration behind its run (include/pt_amd.h, "motion blur")
+inline int motion_step(int iter) { return PT_MOTION_STEP(iter); }
+inline int motion_run_end(int iter) { return ((iter - 1) / PT_MOTION_RUN + 1) * PT_MOTION_RUN + 1; }
 
 int count_devices() {
     int n = 0;
@@ -661,7 +698,11 @@ int commit_range(Slot &sl, int count, int b0, int b1, bool discard) {
 
 // PT_FLAG_TRACE_AHEAD: trace the batch that starts at iteration `first` into the next slot of the rotation and park it
 int trace_ahead(int first) {
-    const int count = std::min(R().maxBatch, kIterEnd - first);
+    int count = std::min(R().maxBatch, kIterEnd - first);
+    if (!R().poses.empty()) {        // PT_FLAG_MOTION: a batch sees one pose, so it ends with its run
+        count = std::min(count, motion_run_end(first) - first);
+        activate_step(R(), motion_step(first));
+    }
     const int slot = (int)(R().seq % R().nslots);
     int rc = trace_batch(R().slot[slot], first, count);
     if (rc) return rc;
@@ -748,6 +789,8 @@ int denoise_refusals(const char *who) {
     if (!R().init) return fail(PT_ERR_NOT_INIT, "%s before pt_init", who);
     if (R().prm.shardCount > 1 || (R().flags & PT_FLAG_ACCUM_SHARD_ROWS))
         return fail(PT_ERR_INVALID, "%s: the renderer holds a row shard, its accumulator is not a frame", who);
+    if (R().flags & PT_FLAG_MOTION)
+        return fail(PT_ERR_INVALID, "%s: the renderer was initialised with PT_FLAG_MOTION (a first-hit guide has no single pose)", who);
     return PT_OK;
 }
 
@@ -1117,6 +1160,7 @@ const PtDenoiseVarParams kDisplayParams = {PT_DISPLAY_LEVELS, PT_DISPLAY_GUIDE_I
 int denoise_var_run(int samples, const PtDenoiseVarParams *p, size_t bytes, int form, bool wantVar, float *ms, const char *who,
                     uchar4 *bytesOut = nullptr, bool fused = true) {
     PTCHECK(moments_refusals(who));
+    PTCHECK(denoise_refusals(who));      // (the moments need the whole frame, so this adds PT_FLAG_MOTION's refusal alone)
     if (!p || bytes != sizeof(PtDenoiseVarParams))
         return fail(PT_ERR_INVALID, "%s: the caller's PtDenoiseVarParams is %zu bytes, this library's %zu", who, p ? bytes : (size_t)0, sizeof(PtDenoiseVarParams));
     if (R().flags & PT_FLAG_SPATIAL_VARIANCE) {
@@ -1368,6 +1412,75 @@ bool same_objects(const State &S, const PtGeom *geoms, int ngeoms, const PtMater
     return registered_mismatch(reg, S.initReg) == nullptr;
 }
 
+// What the renderer's slots, accumulators and walks share whatever the plan's tables hold -- the allocations pt_init sized by a plan and the
+// launches' common shape: do two plans agree on it?  NULL, or the name of the first member that differs.  The camera move asks it of the new
+// camera's plan against the renderer (a difference: the full call); PT_FLAG_MOTION of every step against step 0 (a difference: refused).
+const char *slots_mismatch(const PlanScalars &a, const PlanScalars &b) {
+    if (a.mesh != b.mesh) return "mesh";
+    if (a.dof != b.dof) return "dof";
+    if (a.walkMeshLds != b.walkMeshLds) return "walkMeshLds";
+    if (a.flags != b.flags) return "flags";
+    if (a.nslots != b.nslots) return "nslots";
+    if (a.maxBatch != b.maxBatch) return "maxBatch";
+    if (a.poolCap != b.poolCap || a.poolChunks != b.poolChunks || a.prm.poolChunks != b.prm.poolChunks) return "the path pools' size";
+    if (a.prm.chunkShift != b.prm.chunkShift) return "the path pools' chunk size";
+    if (a.prm.histBits != b.prm.histBits) return "the path pools' layout (history bits)";
+    if (a.meshHitWords != b.meshHitWords) return "meshHitWords";
+    if (a.prm.contribLocal != b.prm.contribLocal) return "contribLocal";
+    if (a.nLocal != b.nLocal || a.P != b.P) return "the frame";
+    return nullptr;
+}
+
+// The dynamic-LDS attribute of every kernel the renderer's poses launch, set to the largest value any pose needs (size_launches sets each
+// pose's own as it goes; poses that share a kernel would leave the last one's).  A renderer of one pose: what size_launches set.
+int lds_attributes(State &S) {
+    if (S.poses.empty()) return PT_OK;
+    std::map<const void *, size_t> need;
+    const int was = S.step;
+    for (int s = 0; s < (int)S.poses.size(); ++s) {
+        activate_step(S, s);
+        for (const void *k : {S.kernFirst, S.kernNext}) need[k] = std::max(need[k], S.ldsBytes);
+        if (S.mesh)
+            for (int first = 0; first < 2; ++first) {
+                const void *kw = walk_kernel(first != 0, first && S.dof);
+                need[kw] = std::max(need[kw], S.ldsWalk);
+            }
+    }
+    activate_step(S, was);
+    for (const auto &kv : need)
+        if (kv.second > 64 * 1024) HIPCHECK(hipFuncSetAttribute(kv.first, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kv.second));
+    return PT_OK;
+}
+
+// a plan's tables in device bytes as pt_init allocates them; `invariant`: the camera-invariant ones (PT_FLAG_MOTION holds them once) or the rest
+size_t table_bytes(ScenePlan &plan, bool invariant, long long *buffers = nullptr) {
+    size_t bytes = 0;
+    SceneTables none;
+    (void)none.for_each(nullptr, plan, plan.mesh, plan.grouped, [&](const auto &, const auto *, const auto &table, TableRule rule) {
+        if (rule.cameraInvariant != invariant || !rule.allocated(table.size())) return (int)PT_OK;
+        bytes += rule.allocated(table.size()) * sizeof(table[0]);
+        if (buffers) *buffers += 1;
+        return (int)PT_OK;
+    });
+    return bytes;
+}
+
+// PT_FLAG_MOTION holds the camera-invariant tables once by leaving them in State::tab when poses are exchanged (exchange_pose names them):
+// is that list the set SceneTables::for_each marks camera-invariant?  A table marked so and not named there would be null in every pose but
+// the first.
+bool invariant_tables_are_the_exchanged_ones(SceneTables &tab, ScenePlan &plan) {
+    bool ok = true;
+    int n = 0;
+    (void)tab.for_each(nullptr, plan, true, true, [&](const auto &buf, const auto *, const auto &, TableRule rule) {
+        if (!rule.cameraInvariant) return (int)PT_OK;
+        n += 1;
+        const void *at = &buf;
+        if (at != (const void *)&tab.dTexels && at != (const void *)&tab.dMeshRecs) ok = false;
+        return (int)PT_OK;
+    });
+    return ok && n == 2;
+}
+
 // the host's copies of the camera-invariant tables, once the device holds them
 void drop_camera_invariant(SceneTables &tab, ScenePlan &plan) {
     (void)tab.for_each(nullptr, plan, plan.mesh, plan.grouped, [](const auto &, const auto *, auto &table, TableRule rule) {
@@ -1375,6 +1488,8 @@ void drop_camera_invariant(SceneTables &tab, ScenePlan &plan) {
         return (int)PT_OK;
     });
 }
+
+int camera_faces_device(CameraGroups &G, const CameraResolve &cr, hipStream_t st, DevBuf<uint32_t> &pix, DevBuf<signed char> &face, float *ms);
 
 // The device half of pt_init.  The scene is planned on the host first (pt_scene_plan.h: plan_scene), and a scene that is refused there --
 // every PT_ERR_INVALID -- has touched nothing: no allocation made or released, the renderer that was there still initialised and usable.
@@ -1396,14 +1511,72 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
         phaseMs[i] = std::chrono::duration<double, std::milli>(t - phaseT0).count();
         phaseT0 = t;
     };
-    ScenePlan plan;
-    PTCHECK(plan_scene(SceneIn(cam, geoms, ngeoms, mats, nmats, traceDepth, o, reg), plan));
-    const void *kernFirst = nullptr, *kernNext = nullptr;
-    PTCHECK(resolve_bounce_kernel(plan, true, &kernFirst));
-    PTCHECK(resolve_bounce_kernel(plan, false, &kernNext));
-    // (the pools' layout is the later launches' form's: history-coded for PLAIN, and for no other)
-    if ((plan.prm.histBits != 0) != ((bounce_form(false, plan.dof, plan.many, plan.sweptCubes, plan.mesh, plan.grouped, plan.tex, plan.bump, plan.plain) & kbPlain) != 0))
-        return fail(PT_ERR_INVALID, "pt_init: internal error: history bits %d and the later bounces' form disagree", plan.prm.histBits);
+    // PT_FLAG_MOTION: `geoms` holds PT_MOTION_STEPS scenes of ngeoms records; every step is planned like a call of its own before anything
+    // is touched.  `plan` is step 0's -- the pose the renderer starts in, and without the flag the one there is --, `later` the others'.
+    const int steps = (o.flags & PT_FLAG_MOTION) ? PT_MOTION_STEPS : 1;
+    struct Planned { ScenePlan plan; const void *kernFirst = nullptr, *kernNext = nullptr; };
+    // ... and the work list's face certificates, nearly all of a plan's host time, are evaluated on the device for every step, as the
+    // camera move evaluates them (k_camera_faces through SceneIn::faces: the host's values, bit for bit), on a stream and in scratch
+    // buffers of this call's own -- nothing of the live renderer is touched.  (PT_AMD_MOTION_HOST_FACES, measurements only: on the host;
+    // without a device the host evaluates them too, and the call ends with PT_ERR_NO_GPU below as it always did.)
+    const bool deviceFaces = steps > 1 && !env_flag("PT_AMD_MOTION_HOST_FACES") && count_devices() >= 1;
+    Stream faceStream;
+    DevBuf<uint32_t> facePix;
+    DevBuf<signed char> faceBytes;
+    struct DeviceGuard {      // the device current at the call, put back where planning ends in a refusal
+        int prev = -1;
+        bool armed = false;
+        ~DeviceGuard() { if (armed && prev >= 0) (void)hipSetDevice(prev); }
+    } deviceGuard;
+    if (deviceFaces) {
+        register_exit_handler();
+        HIPCHECK(hipGetDevice(&deviceGuard.prev));
+        deviceGuard.armed = true;
+        if (o.device >= 0) HIPCHECK(hipSetDevice(o.device));
+        PTCHECK(faceStream.create(hipStreamNonBlocking));
+    }
+    const auto plan_step = [&](const PtGeom *g, Planned &out) -> int {
+        ScenePlan &plan = out.plan;
+        SceneIn in(cam, g, ngeoms, mats, nmats, traceDepth, o, reg);
+        if (deviceFaces)
+            in.faces = [&](CameraGroups &G, const CameraResolve &cr) { return camera_faces_device(G, cr, faceStream, facePix, faceBytes, nullptr); };
+        PTCHECK(plan_scene(in, plan));
+        PTCHECK(resolve_bounce_kernel(plan, true, &out.kernFirst));
+        PTCHECK(resolve_bounce_kernel(plan, false, &out.kernNext));
+        // (the pools' layout is the later launches' form's: history-coded for PLAIN, and for no other)
+        if ((plan.prm.histBits != 0) != ((bounce_form(false, plan.dof, plan.many, plan.sweptCubes, plan.mesh, plan.grouped, plan.tex, plan.bump, plan.plain) & kbPlain) != 0))
+            return fail(PT_ERR_INVALID, "pt_init: internal error: history bits %d and the later bounces' form disagree", plan.prm.histBits);
+        return PT_OK;
+    };
+    Planned step0;
+    std::vector<Planned> later((size_t)steps - 1);
+    if (steps > 1) {
+        if (ngeoms > 0 && !geoms) return fail(PT_ERR_INVALID, "pt_init: null argument");
+        for (int s = 1; s < steps; ++s)
+            for (int g = 0; g < ngeoms; ++g) {
+                const PtGeom &a = geoms[g], &b = geoms[(size_t)s * ngeoms + g];
+                if (a.type != b.type || a.materialid != b.materialid)
+                    return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOTION step %d: geom %d has another type or materialid than in step 0", s, g);
+            }
+        for (int s = 0; s < steps; ++s) {
+            Planned &pl = s ? later[(size_t)s - 1] : step0;
+            if (const int rc = plan_step(geoms + (size_t)s * (ngeoms > 0 ? ngeoms : 0), pl))
+                return fail(rc, "pt_init: PT_FLAG_MOTION step %d: %s", s, std::string(g_err).c_str());
+            if (!s) continue;
+            if (const char *why = slots_mismatch(pl.plan, step0.plan))
+                return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOTION step %d: its plan and step 0's differ in what the in-flight batches share: %s", s, why);
+            if (!same_bytes(pl.plan.texels, step0.plan.texels) || !same_bytes(pl.plan.meshRecs, step0.plan.meshRecs))
+                return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOTION step %d: internal error: its texels or mesh records are not step 0's", s);
+        }
+    } else {
+        PTCHECK(plan_step(geoms, step0));
+    }
+    deviceGuard.armed = false;      // (planned: from here on the call's device is set as it always was)
+    faceStream.release(); facePix.release(); faceBytes.release();
+    ScenePlan &plan = step0.plan;
+    const void *const kernFirst = step0.kernFirst, *const kernNext = step0.kernNext;
+    if (steps > 1 && !invariant_tables_are_the_exchanged_ones(R().tab, plan))
+        return fail(PT_ERR_INVALID, "pt_init: internal error: the tables PT_FLAG_MOTION holds once are not the camera-invariant ones");
     if (count_devices() < 1) return fail(PT_ERR_NO_GPU, "pt_init: no HIP device (this library has no CPU fallback)");
     register_exit_handler();
     phase_end(0);      // host planning
@@ -1456,7 +1629,13 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
         const size_t albedo = (S.flags & PT_FLAG_DEMODULATE) ? (size_t)S.P * sizeof(float4) : 0;
         // ... and PT_FLAG_DEMOD_HISTORY's one image, the blended albedo
         const size_t albedoBlend = (S.flags & PT_FLAG_DEMOD_HISTORY) ? (size_t)S.P * sizeof(float4) : 0;
-        const size_t need = perSlot * (size_t)S.nslots + display + spatial + albedo + albedoBlend;
+        // ... and PT_FLAG_MOTION's tables: every step's own, and the ones no pose changes once
+        size_t poseTables = 0;
+        if (steps > 1) {
+            poseTables = table_bytes(plan, true) + table_bytes(plan, false);
+            for (Planned &pl : later) poseTables += table_bytes(pl.plan, false);
+        }
+        const size_t need = perSlot * (size_t)S.nslots + display + spatial + albedo + albedoBlend + poseTables;
         size_t freeB = 0, totalB = 0;
         HIPCHECK(hipMemGetInfo(&freeB, &totalB));
         if (need > freeB)
@@ -1495,8 +1674,32 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
         return rule.allocated(table.size()) ? buf.upload(table.data(), table.size(), rule.slack) : (int)PT_OK;
     }));
 
+    // PT_FLAG_MOTION: the later steps' poses -- scalars, kernels, tables (but the ones step 0's upload holds for all), each sized like step 0
+    if (steps > 1) {
+        S.poses.resize((size_t)steps);
+        S.step = 0;
+        for (int s = 1; s < steps; ++s) {
+            Planned &pl = later[(size_t)s - 1];
+            Pose &p = S.poses[(size_t)s];
+            p.scalars = pl.plan;
+            p.kernFirst = pl.kernFirst;
+            p.kernNext = pl.kernNext;
+            PTCHECK(p.tab.for_each(nullptr, pl.plan, pl.plan.mesh, pl.plan.grouped, [](auto &buf, const auto *, const auto &table, TableRule rule) {
+                return !rule.cameraInvariant && rule.allocated(table.size()) ? buf.upload(table.data(), table.size(), rule.slack) : (int)PT_OK;
+            }));
+        }
+    }
+    S.tables = State::TableCount();
+    S.tables.ownBytes = (long long)table_bytes(plan, false, &S.tables.ownBuffers);
+    S.tables.sharedBytes = (long long)table_bytes(plan, true, &S.tables.sharedBuffers);
+    S.tables.allOwnBytes = S.tables.ownBytes;
+    for (Planned &pl : later) S.tables.allOwnBytes += (long long)table_bytes(pl.plan, false);
     phase_end(3);      // the tables' uploads
-    PTCHECK(size_launches(S));
+    for (int s = steps - 1; s >= 0; --s) {      // (step 0 last: the pose the renderer starts in)
+        activate_step(S, s);
+        PTCHECK(size_launches(S));
+    }
+    PTCHECK(lds_attributes(S));
     const KParams &k = S.prm;
     if (env_flag("PT_AMD_VERBOSE"))       // experiments: what pt_init decided
         fprintf(stderr, "pt_init: lds %zu / %zu B, grid %d / %d, mesh %d many %d plain %d, binned %d walls %d (slots %d, planes %d) allClassified %d, sphCull %d (cluster 0: %d) omax %g\n",
@@ -1507,13 +1710,16 @@ int init_renderer(const PtCamera *cam, const PtGeom *geoms, int ngeoms, const Pt
     if (phases)
         fprintf(stderr, "pt_init phases ms: plan %.3f free %.3f allocate %.3f upload %.3f size+sync %.3f\n", phaseMs[0], phaseMs[1], phaseMs[2], phaseMs[3], phaseMs[4]);
     // what the camera move needs of this call: its scene arguments, and the plan whose tables the device now holds
-    S.inGeoms.assign(geoms, geoms + ngeoms);
+    // (PT_FLAG_MOTION: every step's geoms -- its move is the full call --, and no held plan)
+    S.inGeoms.assign(geoms, geoms + (size_t)steps * ngeoms);
     S.inMats.assign(mats, mats + nmats);
     S.inDepth = traceDepth;
     S.inOpts = o;
     S.initReg = reg;
-    drop_camera_invariant(S.tab, plan);
-    S.held.reset(new ScenePlan(std::move(plan)));
+    if (steps == 1) {
+        drop_camera_invariant(S.tab, plan);
+        S.held.reset(new ScenePlan(std::move(plan)));
+    }
     S.init = true;
     g_err.clear();
     return PT_OK;
@@ -1606,7 +1812,8 @@ int reinit_with_camera(const PtCamera &cam) {
     const std::vector<PtMaterial> mats = S.inMats;
     const PtOptions o = S.inOpts;
     Stream camStream = std::move(S.camStream);      // (the moves' own stream outlives a rebuild -- not one that fails and leaves a State that holds nothing)
-    const int rc = init_renderer(&cam, geoms.data(), (int)geoms.size(), mats.data(), (int)mats.size(), S.inDepth, o, S.initReg);
+    const int ngeoms = (int)(geoms.size() / ((o.flags & PT_FLAG_MOTION) ? PT_MOTION_STEPS : 1));      // (PT_FLAG_MOTION: every step's geoms)
+    const int rc = init_renderer(&cam, geoms.data(), ngeoms, mats.data(), (int)mats.size(), S.inDepth, o, S.initReg);
     if (!S.holds_nothing()) S.camStream = std::move(camStream);
     return rc;
 }
@@ -1632,6 +1839,11 @@ int set_camera(const PtCamera *cam) {
                     cam->resolution[0], cam->resolution[1], S.prm.W, S.prm.H);
     const PtCamera camNew = *cam;        // (the caller may hand in the camera of a scene this call outlives)
     if (S.device >= 0) HIPCHECK(hipSetDevice(S.device));
+    // PT_FLAG_MOTION: the full call with all of the renderer's steps, which plans them before it touches anything
+    if (S.flags & PT_FLAG_MOTION) {
+        t_lastMove.fast = 0;
+        return reinit_with_camera(camNew);
+    }
     // 1. the plan for the new camera, the certificates of its work list on the device; a scene that is refused has touched nothing
     if (!S.camStream) PTCHECK(S.camStream.create(hipStreamNonBlocking));
     std::unique_ptr<ScenePlan> planPtr(new ScenePlan);
@@ -1656,11 +1868,7 @@ int set_camera(const PtCamera *cam) {
         if (rule.cameraInvariant && buf.cap != rule.allocated(now.size())) sameInvariants = false;
         return (int)PT_OK;
     });
-    const bool sameAllocations =
-        S.held && kernFirst == S.kernFirst && kernNext == S.kernNext && plan.mesh == S.mesh && plan.dof == S.dof && plan.walkMeshLds == S.walkMeshLds &&
-        plan.flags == S.flags && plan.nslots == S.nslots && plan.maxBatch == S.maxBatch && plan.poolCap == S.poolCap && plan.poolChunks == S.poolChunks &&
-        plan.prm.chunkShift == S.prm.chunkShift && plan.prm.poolChunks == S.prm.poolChunks && plan.prm.histBits == S.prm.histBits &&
-        plan.meshHitWords == S.meshHitWords && plan.prm.contribLocal == S.prm.contribLocal && plan.nLocal == S.nLocal && plan.P == S.P && sameInvariants;
+    const bool sameAllocations = S.held && kernFirst == S.kernFirst && kernNext == S.kernNext && !slots_mismatch(plan, S) && sameInvariants;
     if (faulted || !sameAllocations) {
         t_lastMove.fast = 0;
         return reinit_with_camera(camNew);
@@ -1730,6 +1938,60 @@ int set_camera(const PtCamera *cam) {
     S.held = std::move(planPtr);
     t_lastMove.fast = 1;
     g_err.clear();
+    return PT_OK;
+}
+
+// What pt_iterate_batch does for iterations first_iter .. first_iter + count - 1, its checks behind it: the next slot, trace, wait, commit in
+// order -- for a whole call, or under PT_FLAG_MOTION for each piece of it that lies in one run, which sees one pose.  single: the CALL is
+// one iteration (a piece of one iteration cut from a longer call is no reason to trace ahead).
+int iterate_piece(int first_iter, int count, bool single) {
+    int rc;
+    if ((R().flags & PT_FLAG_TRACE_AHEAD) && single) {
+        // the reference's protocol, one call per iteration: the iteration comes out of a batch that was traced ahead
+        if (!R().ahead.empty() && R().ahead.front().first + R().ahead.front().next != first_iter) {
+            rc = discard_ahead();                    // not the iteration the parked batches continue with
+            if (rc) return rc;
+        }
+        if (R().ahead.empty()) {
+            rc = trace_ahead(first_iter);
+            if (rc) return rc;
+        }
+        State::Parked &p = R().ahead.front();
+        Slot &sl = R().slot[p.slot];
+        if (!p.waited) {      // (once per batch: the commits that follow on the caller's stream are ordered behind this one)
+            HIPCHECK(hipStreamWaitEvent(R().stream, sl.evDone, 0));
+            p.waited = true;
+        }
+        rc = commit_range(sl, p.count, p.next, p.next + 1, false);
+        if (rc) return rc;
+        int after = p.first + p.count;               // first iteration behind the parked batches
+        if (++p.next == p.count) {
+            HIPCHECK(hipEventRecord(sl.evCommitted, R().stream));
+            R().ahead.pop_front();
+        }
+        // every free slot traces on: the GPU stays ahead of the caller by at least a batch
+        if (!R().ahead.empty()) after = R().ahead.back().first + R().ahead.back().count;
+        while ((int)R().ahead.size() < R().nslots && after < kIterEnd) {
+            rc = trace_ahead(after);
+            if (rc) return rc;
+            after = R().ahead.back().first + R().ahead.back().count;
+        }
+    } else {
+        if (!R().ahead.empty()) {
+            rc = discard_ahead();
+            if (rc) return rc;
+        }
+        activate_step(R(), motion_step(first_iter));      // (PT_FLAG_MOTION: the piece's pose; else nothing)
+        Slot &sl = R().slot[R().seq % R().nslots];
+        rc = trace_batch(sl, first_iter, count);
+        if (rc) return rc;
+        // commit on the caller's stream: commits are therefore ordered like the pt_iterate calls
+        HIPCHECK(hipStreamWaitEvent(R().stream, sl.evDone, 0));
+        rc = commit_range(sl, count, 0, count, false);
+        if (rc) return rc;
+        HIPCHECK(hipEventRecord(sl.evCommitted, R().stream));
+        R().seq += 1;
+    }
     return PT_OK;
 }
 
@@ -1849,51 +2111,14 @@ int pt_iterate_batch(int frame, int first_iter, int count, void *rgba8_dev) {
     // every argument is checked BEFORE anything is enqueued: a rejected call leaves the image and the counters untouched
     if (rgba8_dev && (R().flags & PT_FLAG_ACCUM_SHARD_ROWS))
         return fail(PT_ERR_INVALID, "pt_iterate: no PBO conversion from a row-sharded accumulator");
-    int rc;
-    if ((R().flags & PT_FLAG_TRACE_AHEAD) && count == 1) {
-        // the reference's protocol, one call per iteration: the iteration comes out of a batch that was traced ahead
-        if (!R().ahead.empty() && R().ahead.front().first + R().ahead.front().next != first_iter) {
-            rc = discard_ahead();                    // not the iteration the parked batches continue with
-            if (rc) return rc;
+    if (R().poses.empty()) {
+        PTCHECK(iterate_piece(first_iter, count, count == 1));
+    } else {      // PT_FLAG_MOTION: cut at the run boundaries; the PBO conversion happens once, after the last piece
+        for (int i = first_iter, end = first_iter + count; i < end;) {
+            const int n = std::min(end, motion_run_end(i)) - i;
+            PTCHECK(iterate_piece(i, n, count == 1));
+            i += n;
         }
-        if (R().ahead.empty()) {
-            rc = trace_ahead(first_iter);
-            if (rc) return rc;
-        }
-        State::Parked &p = R().ahead.front();
-        Slot &sl = R().slot[p.slot];
-        if (!p.waited) {      // (once per batch: the commits that follow on the caller's stream are ordered behind this one)
-            HIPCHECK(hipStreamWaitEvent(R().stream, sl.evDone, 0));
-            p.waited = true;
-        }
-        rc = commit_range(sl, p.count, p.next, p.next + 1, false);
-        if (rc) return rc;
-        int after = p.first + p.count;               // first iteration behind the parked batches
-        if (++p.next == p.count) {
-            HIPCHECK(hipEventRecord(sl.evCommitted, R().stream));
-            R().ahead.pop_front();
-        }
-        // every free slot traces on: the GPU stays ahead of the caller by at least a batch
-        if (!R().ahead.empty()) after = R().ahead.back().first + R().ahead.back().count;
-        while ((int)R().ahead.size() < R().nslots && after < kIterEnd) {
-            rc = trace_ahead(after);
-            if (rc) return rc;
-            after = R().ahead.back().first + R().ahead.back().count;
-        }
-    } else {
-        if (!R().ahead.empty()) {
-            rc = discard_ahead();
-            if (rc) return rc;
-        }
-        Slot &sl = R().slot[R().seq % R().nslots];
-        rc = trace_batch(sl, first_iter, count);
-        if (rc) return rc;
-        // commit on the caller's stream: commits are therefore ordered like the pt_iterate calls
-        HIPCHECK(hipStreamWaitEvent(R().stream, sl.evDone, 0));
-        rc = commit_range(sl, count, 0, count, false);
-        if (rc) return rc;
-        HIPCHECK(hipEventRecord(sl.evCommitted, R().stream));
-        R().seq += 1;
     }
     // PT_FLAG_DEMODULATE: the albedo of the iterations just committed, behind the commit on the caller's stream (never with batches traced ahead)
     if (R().flags & PT_FLAG_DEMODULATE) PTCHECK(albedo_launch(first_iter, count));

@@ -683,6 +683,8 @@ int pt_group_init(PtGroup *g, const PtCamera *cam, const PtGeom *geoms, int ngeo
         return fail(PT_ERR_INVALID, "pt_group_init: PT_FLAG_KEEP_RENDERER is not for groups (a group re-initialises its members in place already)");
     if (opts && (opts->flags & PT_FLAG_OBJECT_HISTORY))
         return fail(PT_ERR_INVALID, "pt_group_init: PT_FLAG_OBJECT_HISTORY is not for groups (their members keep no history)");
+    if (opts && (opts->flags & PT_FLAG_MOTION))
+        return fail(PT_ERR_INVALID, "pt_group_init: PT_FLAG_MOTION is not for groups (pt_group_init takes one pose of the scene)");
     CurrentGuard guard;
     const int n = (int)g->ctx.size();
     {   // a re-init (the reference's Free -> Init restart): the old renderers go first, then the buffers they accumulate into

@@ -359,6 +359,10 @@ int check_scene(const SceneIn &in) {
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_DEMOD_HISTORY needs PT_FLAG_MOMENTS, PT_FLAG_TEMPORAL and PT_FLAG_DEMODULATE (it joins the two)");
     if ((o.flags & PT_FLAG_OBJECT_HISTORY) && (~o.flags & (PT_FLAG_MOMENTS | PT_FLAG_TEMPORAL)))
         return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_OBJECT_HISTORY needs PT_FLAG_MOMENTS and PT_FLAG_TEMPORAL (it is the history that follows the objects)");
+    if ((o.flags & PT_FLAG_MOTION) && (o.flags & (PT_FLAG_TEMPORAL | PT_FLAG_OBJECT_HISTORY | PT_FLAG_DISPLAY_FILTER | PT_FLAG_DEMODULATE |
+                                                  PT_FLAG_SPATIAL_VARIANCE | PT_FLAG_KEEP_RENDERER)))
+        return fail(PT_ERR_INVALID, "pt_init: PT_FLAG_MOTION is not for PT_FLAG_TEMPORAL, PT_FLAG_OBJECT_HISTORY, PT_FLAG_DISPLAY_FILTER, PT_FLAG_DEMODULATE, "
+                    "PT_FLAG_SPATIAL_VARIANCE or PT_FLAG_KEEP_RENDERER renderers (a first-hit guide, and a renderer kept across calls, have one pose)");
     if (o.pipeline_depth < 0 || o.pipeline_depth > kMaxSlots) return fail(PT_ERR_INVALID, "pt_init: pipeline_depth must be 0..%d", kMaxSlots);
     if (o.max_batch < 0 || o.max_batch > PT_MAX_BATCH) return fail(PT_ERR_INVALID, "pt_init: max_batch must be 0..%d", PT_MAX_BATCH);
     return PT_OK;

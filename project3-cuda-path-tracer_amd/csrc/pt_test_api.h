@@ -11,6 +11,7 @@ int pt_debug_trace_paths(int iter, int bounces, float *origin3, float *dir3, flo
     if (bounces > R().prm.traceDepth) return fail(PT_ERR_INVALID, "pt_debug_trace_paths: bounces > traceDepth");
     int rc = sync_all();
     if (rc) return rc;
+    if (iter >= 1) activate_step(R(), motion_step(iter));      // (PT_FLAG_MOTION: the iteration's pose; else nothing)
     Slot &sl = R().slot[0];
     if (bounces == 0) {   // camera rays only (they never exist in HBM: generation is fused into bounce 1)
         const int nl = R().nLocal;
@@ -220,6 +221,15 @@ int pt_test_sphere_groups(const PtCamera *cam, const PtGeom *geoms, int ngeoms, 
 
 int64_t pt_test_live_device_buffers(void) { return (int64_t)g_liveDevBufs.load(); }
 int64_t pt_test_live_handles(void) { return (int64_t)g_liveHandles.load(); }
+
+int pt_test_pose_tables(int64_t out[6]) {
+    if (!R().init) return fail(PT_ERR_NOT_INIT, "pt_test_pose_tables before pt_init");
+    if (!out) return fail(PT_ERR_INVALID, "pt_test_pose_tables: null");
+    const auto &t = R().tables;
+    out[0] = R().poses.empty() ? 1 : (int64_t)R().poses.size();
+    out[1] = t.ownBuffers; out[2] = t.ownBytes; out[3] = t.sharedBuffers; out[4] = t.sharedBytes; out[5] = t.allOwnBytes;
+    return PT_OK;
+}
 
 int pt_test_group_fail_next_reduce(PtGroup *g, int count) {
     if (!g || count < 0) return fail(PT_ERR_INVALID, "pt_test_group_fail_next_reduce: bad argument");

@@ -52,6 +52,13 @@ int pth_scene_geom_texture(void *s, int g) { return static_cast<Scene *>(s)->geo
 // height maps (`BUMP <file> <scale>`): per geom the index of its texture or -1, and its scale
 int pth_scene_geom_bump(void *s, int g) { return static_cast<Scene *>(s)->geomBumps[g]; }
 float pth_scene_geom_bump_scale(void *s, int g) { return static_cast<Scene *>(s)->bumpScales[g]; }
+// object motion (TRANS_END / ROTAT_END / SCALE_END): the number of steps, 0 for a scene without; step s's geoms, num_geoms records
+int pth_scene_motion_steps(void *s) { return static_cast<Scene *>(s)->hasMotion() ? Scene::kMotionSteps : 0; }
+const void *pth_scene_step_geoms(void *s, int step) {
+    Scene *sc = static_cast<Scene *>(s);
+    if (!sc->hasMotion() || step < 0 || step >= Scene::kMotionSteps) return NULL;
+    return sc->stepGeoms.data() + (size_t)step * sc->geoms.size();
+}
 void pth_scene_set_resolution(void *s, int w, int h) { static_cast<Scene *>(s)->setResolution(w, h); }
 
 // saveImage (reference src/main.cpp:49-70) on a W*H*3 running sum: /samples, X mirror, PNG

@@ -8,6 +8,7 @@
 //                           [--denoise-var LEVELS SIGMALUM SIGMANORMAL SIGMAPOSITION]
 //                           [--noise-threshold T [--noise-fraction F] [--check-every K]]
 //                           [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo]
+//                           [--no-motion]
 // --lens / --direct switch on the README extras (depth of field, README.md:100-101; direct lighting, :107-108);
 // imperfect specular needs no switch, it is a material's SPECEX > 0 in the scene file (README.md:171-185).
 // --denoise also writes <out>.denoised.png: the same frame through pt_denoise, the edge-avoiding a-trous filter guided by the first
@@ -38,6 +39,10 @@
 // --history-albedo (with --denoise-var and --history-from) runs both renderers with PT_FLAG_TEMPORAL, PT_FLAG_DEMODULATE and
 // PT_FLAG_DEMOD_HISTORY: the history carries the first view's albedo, and <out>.denoised.png is the filter of the blend divided by the blended
 // albedo (include/pt_amd.h, "demodulated history").
+// A scene whose OBJECT blocks carry TRANS_END / ROTAT_END / SCALE_END (scene.h: Scene::stepGeoms) is rendered motion-blurred: through the C
+// ABI like --noise-threshold (B may be 1) with PT_FLAG_MOTION and the loader's 16 poses (include/pt_amd.h, "motion blur"); the scene's
+// textures and height maps are registered with it.  Not with --denoise, --denoise-var or --history-from.  --no-motion renders the scene of step 0 instead,
+// static, every way a scene without the keywords is rendered.
 //
 // --batch B (B > 1) leaves the reference protocol where nothing can observe it: iterations are traced B at a time
 // through the C ABI (pt_iterate_batch) and the running sum is copied to the host once, before the image is saved,
@@ -84,6 +89,8 @@ static bool historyAlbedo = false;
 static bool historyMove = false;     // --history-move (with --history-from): the history view shows object historyMoveId in another pose
 static int historyMoveId = 0;
 static float historyMoveT[3] = {0.0f, 0.0f, 0.0f}, historyMoveR[3] = {0.0f, 0.0f, 0.0f};
+static bool noMotion = false;        // --no-motion: a scene that defines motion is rendered in step 0's pose
+static bool motion = false;          // the scene defines motion and --no-motion was not given: PT_FLAG_MOTION with Scene::stepGeoms
 void pathtraceExtras(float lensRadius, float focalDistance, bool directLighting);   // pathtrace_shim.cpp
 void pathtraceMoments(bool on);                                                     // pathtrace_shim.cpp
 void pathtraceSpatialVariance(bool on);                                             // pathtrace_shim.cpp
@@ -171,6 +178,7 @@ static void renderBatched() {
     if (demodulate) opt.flags |= PT_FLAG_DEMODULATE;
     if (historyAlbedo) opt.flags |= PT_FLAG_DEMODULATE | PT_FLAG_DEMOD_HISTORY;      // (PT_FLAG_MOMENTS and PT_FLAG_TEMPORAL: set above, it needs both options)
     if (historyMove) opt.flags |= PT_FLAG_OBJECT_HISTORY;
+    if (motion) opt.flags |= PT_FLAG_MOTION;
     std::vector<PtMesh> meshes;        // `mesh` objects: their triangles first (like pathtrace_shim.cpp)
     for (size_t i = 0; i < scene->meshes.size(); ++i) {
         PtMesh m;
@@ -186,7 +194,7 @@ static void renderBatched() {
     // (Every other run through here registers none, as before.)
     std::vector<PtTexture> textures;
     std::vector<PtTexBinding> bindings;
-    if (historyAlbedo) {
+    if (historyAlbedo || motion) {
         for (size_t i = 0; i < scene->textures.size(); ++i) {
             PtTexture t;
             t.width = scene->textures[i].width;
@@ -210,6 +218,27 @@ static void renderBatched() {
         }
         check(pt_set_textures(textures.empty() ? NULL : textures.data(), (int)textures.size(), sizeof(PtTexture),
                               bindings.empty() ? NULL : bindings.data(), (int)bindings.size(), sizeof(PtTexBinding)), "pt_set_textures");
+    }
+    // a scene in motion: its height maps too (like pathtrace_shim.cpp) -- what is registered applies to geom g of every step, and the frame
+    // is the Python path's.  (Every other run through here registers none, as before.)
+    std::vector<PtBumpBinding> bumps;
+    if (motion) {
+        for (size_t g = 0; g < scene->geomBumps.size(); ++g) {
+            if (scene->geomBumps[g] < 0) continue;
+            PtBumpBinding b;
+            b.geom = (int)g;
+            b.texture = scene->geomBumps[g];
+            b.scale = scene->bumpScales[g];
+            b.ntris = 0;
+            b.uvs = NULL;
+            for (size_t i = 0; i < scene->meshes.size(); ++i)
+                if (scene->meshes[i].geom == (int)g) {
+                    b.ntris = (int)(scene->meshes[i].tris.size() / 9);
+                    b.uvs = scene->meshes[i].uvs.empty() ? NULL : scene->meshes[i].uvs.data();
+                }
+            bumps.push_back(b);
+        }
+        check(pt_set_bump_maps(bumps.empty() ? NULL : bumps.data(), (int)bumps.size(), sizeof(PtBumpBinding)), "pt_set_bump_maps");
     }
     int firstIter = 1;                 // the iteration number of the frame's first sample
     if (historyFrom) {                 // the view before the camera moved: its samples stay behind as the context's history
@@ -238,7 +267,7 @@ static void renderBatched() {
     // pt_init's same-scene form (PT_SAME_SCENE), which keeps the renderer's buffers -- the same PNGs)
     if (historyFrom && inPlace) check(pt_init((const PtCamera *)&renderState->camera, NULL, 0, NULL, 0, PT_SAME_SCENE, NULL), "pt_init (camera move)");
     else
-    check(pt_init((const PtCamera *)&renderState->camera, (const PtGeom *)scene->geoms.data(), (int)scene->geoms.size(),
+    check(pt_init((const PtCamera *)&renderState->camera, (const PtGeom *)(motion ? scene->stepGeoms.data() : scene->geoms.data()), (int)scene->geoms.size(),
                   (const PtMaterial *)scene->materials.data(), (int)scene->materials.size(), renderState->traceDepth, &opt),
           "pt_init");
     const int total = (int)renderState->iterations;
@@ -312,7 +341,7 @@ static bool wholeNumber(const char *s, float *out) {
 int main(int argc, char **argv) {
     startTimeString = currentTimeString();
     if (argc < 2) {
-        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo] [--history-move ID TX TY TZ [RX RY RZ]]\n", argv[0]);
+        printf("Usage: %s SCENEFILE.txt [--res W H] [--iterations N] [--depth D] [--out BASENAME] [--hdr] [--batch B] [--lens R F] [--direct] [--denoise LEVELS SC SN SP | --denoise-var LEVELS SL SN SP] [--noise-threshold T [--noise-fraction F] [--check-every K]] [--history-from EX EY EZ N [--in-place | --protocol]] [--spatial-variance] [--demodulate] [--history-albedo] [--history-move ID TX TY TZ [RX RY RZ]] [--no-motion]\n", argv[0]);
         return 1;
     }
     try {
@@ -363,6 +392,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--spatial-variance")) spatialVariance = true;
         else if (!strcmp(argv[i], "--demodulate")) demodulate = true;
         else if (!strcmp(argv[i], "--history-albedo")) historyAlbedo = true;
+        else if (!strcmp(argv[i], "--no-motion")) noMotion = true;
         else if (!strcmp(argv[i], "--history-move") && i + 4 < argc) {
             historyMove = true;
             float id = 0.0f;
@@ -399,16 +429,25 @@ int main(int argc, char **argv) {
     if (demodulate && (!denoiseVar || historyFrom)) { fprintf(stderr, "--demodulate needs --denoise-var and does not go with --history-from\n"); return 1; }
     pathtraceSpatialVariance(spatialVariance);
     pathtraceDemodulate(demodulate);
+    if (scene->hasMotion() && noMotion) {        // step 0's scene, static
+        scene->geoms.assign(scene->stepGeoms.begin(), scene->stepGeoms.begin() + scene->geoms.size());
+        scene->stepGeoms.clear();
+    }
+    motion = scene->hasMotion();
+    if (motion && (denoise || denoiseVar || historyFrom)) {
+        fprintf(stderr, "a scene with motion (TRANS_END / ROTAT_END / SCALE_END) does not go with --denoise, --denoise-var or --history-from: --no-motion renders it static\n");
+        return 1;
+    }
     iteration = 0;
     width = renderState->camera.resolution.x;
     height = renderState->camera.resolution.y;
     const auto t0 = std::chrono::steady_clock::now();
     if (protocol) renderProtocol();
-    else if (batch > 1 || noiseTarget || historyFrom) renderBatched();
+    else if (batch > 1 || noiseTarget || historyFrom || motion) renderBatched();
     else while (runHip()) {}
     const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("%d iterations of %dx%d, depth %d: %.3f s wall (init, %s and PNG included)\n", iteration, width, height,
-           renderState->traceDepth, s, !protocol && (batch > 1 || noiseTarget || historyFrom) ? "one D2H copy" : "per-iteration D2H copy");
+           renderState->traceDepth, s, !protocol && (batch > 1 || noiseTarget || historyFrom || motion) ? "one D2H copy" : "per-iteration D2H copy");
     delete scene;
     return 0;
 }

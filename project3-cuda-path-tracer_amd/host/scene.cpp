@@ -10,8 +10,13 @@
 //     object (loadTexture); the reference's loader skips the unknown keyword, so a textured scene still loads there, untextured
 //   * `BUMP <file> <scale>` likewise binds a height map (any texture file; channel 0) and its scale: the files are shared with TEXTURE by
 //     resolved path; a missing or non-finite scale fails the load; the reference's loader skips this keyword too
+//   * `TRANS_END`, `ROTAT_END`, `SCALE_END` (three floats each) in an OBJECT block give the object's pose at shutter close: Scene::stepGeoms
+//     (scene.h) then holds the scene in 16 poses across the shutter; the reference's loader skips these keywords too, so such a file still
+//     loads there, unmoved
 // Unlike the reference, fields whose keyword is missing are zero instead of uninitialised.
 #include "scene.h"
+
+#include "pt_amd.h"
 
 #include <cctype>
 #include <cmath>
@@ -262,6 +267,34 @@ Scene::Scene(std::string filename, bool verbose_) : verbose(verbose_) {
             std::cout << "ERROR: object " << meshes[i].geom << " is bump-mapped and its mesh has no texture coordinates - aborting!" << std::endl;
             throw std::runtime_error("bump-mapped mesh without texture coordinates");
         }
+    buildStepGeoms();
+}
+
+void Scene::buildStepGeoms() {
+    static_assert(kMotionSteps == PT_MOTION_STEPS, "scene.h and include/pt_amd.h name one number of steps");
+    bool any = false;
+    for (const PoseEnd &e : poseEnds) any = any || e.trans || e.rotat || e.scale;
+    if (!any) return;
+    const auto lerp = [](const lin::vec3 &a, const lin::vec3 &b, float t) {
+        return lin::vec3(a.x + (b.x - a.x) * t, a.y + (b.y - a.y) * t, a.z + (b.z - a.z) * t);
+    };
+    stepGeoms.reserve((size_t)kMotionSteps * geoms.size());
+    for (int s = 0; s < kMotionSteps; ++s) {
+        const float t = ((float)s + 0.5f) / (float)kMotionSteps;
+        for (size_t i = 0; i < geoms.size(); ++i) {
+            Geom g = geoms[i];
+            const PoseEnd e = i < poseEnds.size() ? poseEnds[i] : PoseEnd();
+            if (e.trans) g.translation = lerp(geoms[i].translation, e.t, t);
+            if (e.rotat) g.rotation = lerp(geoms[i].rotation, e.r, t);
+            if (e.scale) g.scale = lerp(geoms[i].scale, e.s, t);
+            if (e.trans || e.rotat || e.scale) {
+                g.transform = utilityCore::buildTransformationMatrix(g.translation, g.rotation, g.scale);
+                g.inverseTransform = lin::inverse(g.transform);
+                g.invTranspose = lin::inverseTranspose(g.transform);
+            }
+            stepGeoms.push_back(g);
+        }
+    }
 }
 
 int Scene::textureIndex(const std::string &path) {
@@ -379,6 +412,13 @@ int Scene::loadGeom(std::string objectid) {
         if (key(t, "TRANS")) g.translation = triple(t);
         else if (key(t, "ROTAT")) g.rotation = triple(t);
         else if (key(t, "SCALE")) g.scale = triple(t);
+        else if (key(t, "TRANS_END") || key(t, "ROTAT_END") || key(t, "SCALE_END")) {
+            poseEnds.resize(geoms.size() + 1);
+            PoseEnd &e = poseEnds[geoms.size()];
+            if (t[0][0] == 'T') { e.trans = true; e.t = triple(t); }
+            else if (t[0][0] == 'R') { e.rotat = true; e.r = triple(t); }
+            else { e.scale = true; e.s = triple(t); }
+        }
         else if (key(t, "TEXTURE") && t.size() >= 2) {
             const int k = textureIndex(t[1][0] == '/' ? t[1] : dir + t[1]);
             geomTextures.resize(geoms.size() + 1, -1);

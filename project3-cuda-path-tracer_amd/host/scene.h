@@ -13,6 +13,8 @@
 #define PT_SCENE_HAS_TEXTURES 1
 // (... and `geomBumps`, `bumpScales`: height maps bound to objects by a `BUMP <file> <scale>` line of their OBJECT block)
 #define PT_SCENE_HAS_BUMPS 1
+// (... and `stepGeoms`: object motion across the shutter, by TRANS_END / ROTAT_END / SCALE_END lines of an OBJECT block)
+#define PT_SCENE_HAS_MOTION 1
 
 // Triangles of one `mesh` object (README.md:112-116, 236), in the OBJ file's coordinates = the geom's object space.
 struct Mesh {
@@ -42,6 +44,9 @@ private:
     int loadCamera();                             // CAMERA block: 5 keyword lines + EYE/VIEW/UP up to a blank line
     bool verbose;
     std::string dir;                              // directory of the scene file ("" or ending in '/'): mesh paths are relative to it
+    struct PoseEnd { bool trans = false, rotat = false, scale = false; lin::vec3 t, r, s; };
+    std::vector<PoseEnd> poseEnds;                // per geom, while parsing: the *_END lines of its block
+    void buildStepGeoms();                        // stepGeoms from geoms and poseEnds
 
 public:
     // Throws std::runtime_error when the file cannot be opened (the reference prints
@@ -59,5 +64,13 @@ public:
     std::vector<int> geomTextures;      // per geom: index into textures, or -1 (untextured)
     std::vector<int> geomBumps;         // per geom: index into textures of its height map, or -1 (unbumped)
     std::vector<float> bumpScales;      // per geom: the height map's scale (0 where unbumped)
+    // Object motion (include/pt_amd.h, "motion blur"): EMPTY unless an OBJECT block carries TRANS_END, ROTAT_END or SCALE_END, else
+    // kMotionSteps x geoms.size() records, step-major: step s is the scene at shutter time (s + 0.5) / kMotionSteps, every component
+    // a + (b - a) * t in float between its value and its *_END value (a missing one: the component does not move), the matrices built from
+    // the interpolated values as loadGeom builds them -- byte for byte the geoms of a static scene file with those values.  `geoms` keeps
+    // the pose at shutter open, which is all the reference's loader reads of such a file.
+    static const int kMotionSteps = 16;
+    std::vector<Geom> stepGeoms;
+    bool hasMotion() const { return !stepGeoms.empty(); }
     RenderState state;                  // camera, iteration count, depth, output name, host image
 };
